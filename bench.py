@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X hot path.  Contract: python bench.py --gpus N --steps K --warmup W prints ONE
 JSON line on rank 0.  A step = one pass of K1 (gmk_eval_batch) over one resident batch of synthetic
-boards (BASELINE.json configs[1]: 65 536 random 15x15 boards per GPU)."""
+boards (BASELINE.json configs[1]: 65 536 random 15x15 boards per GPU).
+
+A plain run does only what the headline figure needs: set-up, settle + warm-up, the K timed steps, the
+outputs of the last step if --dump-outputs DIR is given, and the line.  --full adds everything else the
+line used to carry: the cold (unsettled) K1 figure, the K2 / K3 / K6 / K7 / K8 legs, the self-play
+pipelines and the CPU baselines of the oracle."""
 import argparse
 import json
 import os
@@ -13,6 +18,24 @@ sys.path.insert(0, ROOT)
 
 ALG_BYTES_PER_EVAL = 64 + 3600 + 3600 + 44 + 4      # planes in; scores, density, totals, status out
 HBM_PEAK_GBS = 8000.0                               # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+# --dump-outputs: at most this many boards' totals + status (96 B each as float64) and scores + density (14.4 KB each): <= 36 MB in all
+DUMP_BOARDS_SMALL = 65536
+DUMP_BOARDS_CELLS = 2048
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, np, torch, outputs, n):
+    """Writes the K1 outputs of the last timed step ({name: (device tensor with the board as leading dimension, cap on boards)}) as
+    out_dir/<name>.npy in float64 (the int32 values exactly).  Where the batch has more boards than the cap, the same fixed seeded sample
+    of board ids is taken on every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, (t, cap) in outputs.items():
+        idx = None if n <= cap else np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=cap, replace=False))
+        host = (t if idx is None else t[torch.from_numpy(idx).to(t.device)]).cpu().numpy().astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), host)
+        written[name] = {"shape": list(host.shape), "boards": "all" if idx is None else "seeded sample of %d (seed %d)" % (len(idx), DUMP_SEED)}
+    return written
 
 
 def measured_traffic(kernel, units_key, units):
@@ -640,6 +663,14 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline K1 figure, run every other measurement: the cold K1 figure (roofline.without_settling), the K2 / K3 / K6 / K7 / K8 "
+                         "legs, the self-play pipelines and the CPU baselines; the --mcts-* / --selfplay-* / --evalstate-* / --az-* / --trad-* / --sup-* / "
+                         "--rave-* / --cpu-sample / --no-cpu-baseline options apply only with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed on rank 0 as DIR/<name>.npy (float64): totals and status of up to %d "
+                         "boards, scores and density of up to %d boards (all boards where the batch is no larger, else a fixed seeded sample)"
+                         % (DUMP_BOARDS_SMALL, DUMP_BOARDS_CELLS))
     ap.add_argument("--boards", type=int, default=65536, help="boards per GPU (BASELINE configs[1])")
     ap.add_argument("--kind", type=int, default=0, help="0 random-opening, 1 clustered")
     ap.add_argument("--cpu-sample", type=int, default=65536)
@@ -768,6 +799,8 @@ def stub_rank(args, world, rank):
 
 def main():
     args = parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be at least 1 and --warmup at least 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:], args.launch_timeout))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -838,22 +871,23 @@ def main():
     settle = {"ms": 0.0, "launches": 0}
     cold_ms = None
     if args.settle_ms > 0:
-        # (for the record, the same measurement WITHOUT settling first: W warm-up steps from idle, then K timed steps)
-        for _ in range(args.warmup):
-            step()
-        if graph is not None:
-            graph.replay()
-        torch.cuda.synchronize()
-        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        c0.record()
-        if graph is not None:
-            graph.replay()
-        else:
-            for _ in range(args.steps):
+        if args.full:
+            # (for the record, the same measurement WITHOUT settling first: W warm-up steps from idle, then K timed steps)
+            for _ in range(args.warmup):
                 step()
-        c1.record()
-        torch.cuda.synchronize()
-        cold_ms = c0.elapsed_time(c1) / args.steps
+            if graph is not None:
+                graph.replay()
+            torch.cuda.synchronize()
+            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            c0.record()
+            if graph is not None:
+                graph.replay()
+            else:
+                for _ in range(args.steps):
+                    step()
+            c1.record()
+            torch.cuda.synchronize()
+            cold_ms = c0.elapsed_time(c1) / args.steps
         s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s0.record()
         while True:
@@ -893,20 +927,26 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kernel_ms = float(t[0]), float(t[1])
 
+    # the buffers hold what the last timed step wrote (every step writes all of them)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, np, torch, {"scores": (d_scores, DUMP_BOARDS_CELLS), "density": (d_density, DUMP_BOARDS_CELLS),
+                                                              "totals": (d_totals, DUMP_BOARDS_SMALL), "status": (d_status, DUMP_BOARDS_SMALL)}, n)
+
     mcts = None
-    if args.mcts_games > 0:
+    if args.full and args.mcts_games > 0:
         mcts = bench_mcts(args, G, torch, dev, rank, world, distributed)
 
     incremental = None
-    if args.evalstate_games > 0:
+    if args.full and args.evalstate_games > 0:
         incremental = bench_evalstate(args, G, torch, dev, rank, world, distributed)
 
     trad = None
-    if args.trad_games > 0:
+    if args.full and args.trad_games > 0:
         trad = bench_trad(args, G, torch, dev, rank, world, distributed)
 
     sup_pipeline = sup_error = None
-    if args.sup_games > 0 and args.trad_games > 0:
+    if args.full and args.sup_games > 0 and args.trad_games > 0:
         try:
             sup_pipeline = bench_supervisor_pipeline(args, G, torch, dev, rank, world, distributed, trad["value"] if trad else None)
         except Exception as exc:                                  # noqa: BLE001
@@ -915,11 +955,11 @@ def main():
             sup_pipeline, sup_error = None, "LegFailed: the leg failed on another rank"
 
     rave = None
-    if args.rave_games > 0:
+    if args.full and args.rave_games > 0:
         rave = bench_rave(args, G, torch, dev, rank, world, distributed)
 
     az = az_error = None
-    if args.az_games > 0:
+    if args.full and args.az_games > 0:
         try:
             az = bench_az(args, G, torch, dev, rank, world, distributed)
         except Exception as exc:                                  # noqa: BLE001
@@ -928,7 +968,7 @@ def main():
             az, az_error = None, "LegFailed: the leg failed on another rank"
 
     pipeline = pipeline_error = None
-    if args.selfplay_games >= world:                            # every rank needs a game (the same decision on all ranks: the leg has barriers)
+    if args.full and args.selfplay_games >= world:              # every rank needs a game (the same decision on all ranks: the leg has barriers)
         # the headline line must not be lost to this leg: a failure is reported in its place -- by every rank alike (the leg's local stages
         # end in an agreement of the ranks, so no rank is left in a barrier of the leg; whatever still escapes that is agreed on here)
         try:
@@ -947,9 +987,10 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            # every untimed launch of the step ahead of the timed region: the table upload (1), with --settle-ms > 0 the cold measurement (W, the graph's
-            # upload replay K, its K timed steps -- reported as roofline.without_settling) and the settle launches, then the W warm-up steps and the graph's upload replay
-            "warmup_effective": 1 + (args.warmup + (args.steps if graph is not None else 0) + args.steps + settle["launches"] if args.settle_ms > 0 else 0)
+            # every untimed launch of the step ahead of the timed region: the table upload (1), with --settle-ms > 0 (and --full) the cold measurement (W,
+            # the graph's upload replay K, its K timed steps -- reported as roofline.without_settling) and the settle launches, then the W warm-up steps and
+            # the graph's upload replay
+            "warmup_effective": 1 + (args.warmup + (args.steps if graph is not None else 0) + args.steps if cold_ms is not None else 0) + settle["launches"]
                                 + args.warmup + (args.steps if graph is not None else 0),
             "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True,
@@ -975,6 +1016,8 @@ def main():
                              "note": "this rank, the same W warm-up + K timed steps straight after the idle spell of the set-up, before config.settle: "
                                      "the K steps then fall into the clock governor's dip (profiles/r03_ramp.txt)"}},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "dtype": "float64", "arrays": dumped}
         if mcts is not None:
             out["secondary"] = mcts
         if pipeline is not None or pipeline_error is not None:
@@ -989,7 +1032,7 @@ def main():
             out["poolrave"] = rave
         if az is not None or az_error is not None:
             out["network_guided"] = az if az is not None else {"error": az_error}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample, args.kind)
             if mcts is not None:
                 out["secondary"]["cpu_baseline"] = cpu_baseline_mcts(args.mcts_playouts)

@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-.}" && export TMPDIR=/tmp
 tag=${1:-r02x}
 out=gpurun_out/prof_k2_$tag; rm -rf $out; mkdir -p $out
-B="bench.py --steps 5 --warmup 1 --no-cpu-baseline --selfplay-games 0 --az-games 0 --trad-games 0 --rave-games 0 --mcts-games 0"
+B="bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --selfplay-games 0 --az-games 0 --trad-games 0 --rave-games 0 --mcts-games 0"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/trace -o t --output-format csv -- python3 $B > $out/trace.log 2>&1 || { echo "trace failed"; tail -5 $out/trace.log; exit 1; }
 find $out/trace -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \;
 rm -rf $out/trace
