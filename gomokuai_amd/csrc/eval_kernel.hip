@@ -27,8 +27,10 @@
 //     compact list of <= 4 score deposits -- a colour's own and opponent view of a cell are the halves of one 64-bit word, so a deposit is ONE
 //     ds_add_u64 whose value decides -- and 4-bit per-(cell, colour, direction, type) counters;
 //   * phase 3: one lane per cell: compound candidates from the counters; phase 3b: one lane per (candidate, colour):
-//     the density gate "count >= 2" from seven row popcounts, the compound decision in closed form (components n, threes s), +-600 deposits;
-//   * phase 4: eight lanes per compound component: its counter-move cells from the 13-symbol window around it;
+//     the density gate "count >= 2" from seven row popcounts, the compound decision in closed form (components n, threes s), +-600 deposits,
+//     components queued by ballot prefix with their line word and slot in the entry;
+//   * phase 4: seven lanes per compound component, nine per round: its counter-move cells from the 13-symbol window around it (one
+//     v_alignbit of the line word with its '?' pads);
 //   * phase 5: the 3.6 KB score block leaves LDS transposed to [group][cell]: sixteen non-temporal dword stores of 256 contiguous bytes, in
 //     ADDRESS order (the two parts of a cache line that two pieces share reach the L2 back to back);
 //   * phase D, once per group, in the board iteration that is the wavefront's turn within its workgroup: the density planes of the
@@ -66,11 +68,11 @@ constexpr int kColBase = 20, kDiagBase = 36, kAntiBase = 65;
 #define GMK_K1_TOTALS_COPIES 8
 #endif
 constexpr int kTotalsCopies = GMK_K1_TOTALS_COPIES;   // of the per-type totals, in the queue's last words (phase 0 says why); 8 x copies <= 64
-constexpr int kMiscWords = 48;                   // [0] stones black | white << 16, [1] winner bits, [2] error, [3] compound queue count, [4..14] totals,
+constexpr int kMiscWords = 48;                   // [0] stones black | white << 16, [1] winner bits, [2] error, [3] unused, [4..14] totals,
                                                  // [19..33] the rows (black | white << 16) between three zero rows on either side ([16..18], [34..36])
 constexpr int kBoardWords = kZeroWords + kLineWords + kQueueCap + kMiscWords;
 static_assert(kZeroWords % 4 == 0 && kBoardWords % 4 == 0, "16-byte alignment of the per-board blocks");
-constexpr int kStaticTableWords = 128 + kLineWords + 512 + 1560 + 4;   // lane jobs, initial line words, the bits-to-bytes table, the weight table of phase D,
+constexpr int kStaticTableWords = 128 + kLineWords + 512 + 1560 + 4;   // lane jobs, the lines' '?' pads (phase 4), the bits-to-bytes table, the weight table of phase D,
                                                                         // and the workgroup's two hand-out counters (boards, density bursts)
 
 // Lane -> line jobs.  A job word holds what the scan and the deposits need of a line, ready to use: bits 0..4 symbols in its stream
@@ -317,13 +319,17 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
 #define GMK_STAMP(k) do { } while (0)
 #endif
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    // layout: [trans (LDS address 0)][records (16-byte aligned)][lane jobs 128][initial line words 96][boards: kBoardsPerBlock * kBoardWords]
+    // layout: [trans (LDS address 0)][records (16-byte aligned)][lane jobs 128][line pads 96][boards: kBoardsPerBlock * kBoardWords]
     const uint4* s_rec = reinterpret_cast<const uint4*>(lds + trans_words);
     uint32_t* s_jobs = lds + trans_words + record_words;
 
     for (int i = threadIdx.x; i < trans_words; i += kThreads) lds[i] = g_trans[i];
     for (int i = threadIdx.x; i < record_words; i += kThreads) lds[trans_words + i] = g_records[i];
     if (threadIdx.x < 128) s_jobs[threadIdx.x] = c_lane_jobs[threadIdx.x];
+    // a line word's '?' pads: symbol 2 in every 2-bit slot of the word that is not one of the line's cells (phase 4 ORs them in: its
+    // window then reads '?' off the line wherever the line starts in its word)
+    uint32_t* s_pads = s_jobs + 128;
+    if (threadIdx.x < kLineWords) s_pads[threadIdx.x] = ~c_line_init[threadIdx.x] & 0xAAAAAAAAu;
     uint2* s_lut = reinterpret_cast<uint2*>(s_jobs + 128 + kLineWords);      // byte -> its eight bits as bytes (the stone operands of phase D)
     if (threadIdx.x < 256) s_lut[threadIdx.x] = make_uint2(((threadIdx.x & 15u) * 0x204081u) & 0x01010101u, ((threadIdx.x >> 4) * 0x204081u) & 0x01010101u);
     uint32_t* s_wtab_words = s_jobs + 128 + kLineWords + 512;
@@ -599,18 +605,19 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                     const uint32_t upper = (any >> 1) | (any >> 2) | (any >> 3);
                     // one nibble per (colour, direction): 0, 1 or 2 = the clipped count; the nibbles of a colour summed by one multiplication
                     const uint32_t clipped = ((any | upper) & 0x11111111u) + (upper & 0x11111111u);
-                    uint32_t cand = 0;
                     // (24-bit multiplies: bits 12..15 of the product depend on the low sixteen bits of the factor only, and a full 32-bit multiply --
                     // which the compiler picks once it has dropped the mask -- runs at a quarter of the rate)
-                    if ((mul24(clipped, 0x1111u) & 0xF000u) >= 0x2000u) cand |= 1u;
-                    if ((mul24(clipped >> 16, 0x1111u) & 0xF000u) >= 0x2000u) cand |= 2u;
+                    // The sums land at bits 12..15 (white) and 16..19 (black); "two or more" is then bits 13..15 resp. 17..19 non-zero, and those
+                    // bits ARE the entry's colour flags (no selects to turn them into two flag bits)
+                    uint32_t cand = mul24(clipped, 0x1111u) & 0xE000u;
+                    cand |= mul24(clipped >> 16, 0x11110u) & 0xE0000u;
                     if (pass == 3 && q >= kCells) cand = 0u;
                     const unsigned long long pushers = __ballot(cand != 0u);
                     if (pushers) {
                         if (cand) {
                             const int slot = n_cand + static_cast<int>(__builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(pushers >> 32),
                                                                        __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(pushers), 0u)));
-                            if (slot < kQueueCap / 2) s_queue[slot] = static_cast<uint32_t>(q) | (cand << 8);
+                            if (slot < kQueueCap / 2) s_queue[slot] = static_cast<uint32_t>(q) | cand;
                         }
                         n_cand += __popcll(pushers);
                     }
@@ -623,98 +630,126 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
             //      counter-move rescans queued in the upper half of the queue ----
             if (n_cand > kQueueCap / 2) { s_misc[2] = 1; n_cand = kQueueCap / 2; }
             if (phase_mask & 2048) n_cand = 0;
+            int n_comp_q = 0;                                       // components queued for phase 4 (wave-uniform: slots by ballot prefix)
             if (phase_mask & 8)
-            for (int v = lane; v < 2 * n_cand; v += 64) {                      // one lane per (candidate cell, colour): 0 white, 1 black
-                const uint32_t ce = s_queue[v >> 1];
+            for (int v0 = 0; v0 < 2 * n_cand; v0 += 64) {           // one lane per (candidate cell, colour): 0 white, 1 black
+                const int v = v0 + lane;
+                const int flag_shift = 13 + 4 * (v & 1);           // this lane's colour flags in a candidate entry (bits 13..15 white, 17..19 black)
+                const uint32_t ce = s_queue[v >> 1];                // (< n_cand + 32 <= 256: inside the queue; lanes past the end are masked below)
                 const int q = ce & 255, c = v & 1;
-                if (!((ce >> (8 + c)) & 1u)) continue;
-                // this colour's four direction nibbles of the three counter words (read together with the rows below: one round trip)
-                const uint32_t f3 = (s_cnt[q] >> (16 * c)) & 0xFFFFu, fd = (s_cnt[kCells + q] >> (16 * c)) & 0xFFFFu, f2 = (s_cnt[2 * kCells + q] >> (16 * c)) & 0xFFFFu;
-                // the density gate (Pattern.cpp:182): the colour's density COUNT at the cell must be two or more: its stones under the
-                // non-zero cells of the 7x7 BlockWeights mask around q, counted from the rows (black low, white high half word)
-                uint32_t dens = 0;
-                {
-                    const int qy = (q * 0x8889) >> 19, qx = q - 15 * qy, half = c ? 0 : 16;
+                bool queue = false;
+                uint32_t ent1 = 0, ent2 = 0;
+                if (v < 2 * n_cand && ((ce >> flag_shift) & 7u)) {
+                    // this colour's four direction nibbles of the three counter words (read together with the rows below: one round trip)
+                    const uint32_t f3 = (s_cnt[q] >> (16 * c)) & 0xFFFFu, fd = (s_cnt[kCells + q] >> (16 * c)) & 0xFFFFu, f2 = (s_cnt[2 * kCells + q] >> (16 * c)) & 0xFFFFu;
+                    // the density gate (Pattern.cpp:182): the colour's density COUNT at the cell must be two or more: its stones under the
+                    // non-zero cells of the 7x7 BlockWeights mask around q, counted from the rows (black low, white high half word)
+                    uint32_t dens = 0;
+                    const int qy = (q * 0x8889) >> 19, qx = q - 15 * qy;
+                    {
+                        const int half = c ? 0 : 16;
     #pragma unroll
-                    for (int dy = -3; dy <= 3; ++dy) {
-                        const uint32_t pattern = dy == 0 ? 0x77u : (dy == 3 || dy == -3) ? 0x49u : 0x3Eu;      // 1110111, 1001001, 0111110
-                        const uint32_t mask = ((pattern << qx) >> 3) & 0x7FFFu;
-                        dens += __popc((s_rows[3 + qy + dy] >> half) & mask);
+                        for (int dy = -3; dy <= 3; ++dy) {
+                            const uint32_t pattern = dy == 0 ? 0x77u : (dy == 3 || dy == -3) ? 0x49u : 0x3Eu;      // 1110111, 1001001, 0111110
+                            const uint32_t mask = ((pattern << qx) >> 3) & 0x7FFFu;
+                            dens += __popc((s_rows[3 + qy + dy] >> half) & mask);
+                        }
+                    }
+                    if (dens >= 2u) {
+                        // The reference walks the directions in order through a state machine S0, L2, LD3, To33, To43, To44 (Pattern.cpp:440-486); in
+                        // each direction the component is the first of LiveThree, DeadThree, LiveTwo with a non-zero counter, taken once or twice (the
+                        // counters count like its 2-bit shift flags: 0, 1, 2 or more, Pattern.cpp:395-400).  Its outcome does not depend on the order:
+                        // with n components of which s are threes (weight 2, a LiveTwo 1), the state ends at 3 + min(2, s) for n >= 2 -- the first two
+                        // transitions add w1 + w2 + 1, every further one w - 1, capped at 5 -- and the "triple" flag is n >= 3.  So: nibble masks.
+                        const uint32_t up3 = (f3 >> 1) | (f3 >> 2) | (f3 >> 3), upd = (fd >> 1) | (fd >> 2) | (fd >> 3), up2 = (f2 >> 1) | (f2 >> 2) | (f2 >> 3);
+                        const uint32_t sel3 = (f3 | up3) & 0x1111u;                                          // directions whose component is a LiveThree
+                        const uint32_t seld = (fd | upd) & 0x1111u & ~sel3;                                  // ... a DeadThree
+                        const uint32_t sel2 = (f2 | up2) & 0x1111u & ~(sel3 | seld);                         // ... a LiveTwo
+                        const uint32_t strong = sel3 | seld, any_dir = strong | sel2;
+                        const uint32_t twice_strong = (sel3 & up3) | (seld & upd), twice = twice_strong | (sel2 & up2);     // taken twice (counter >= 2)
+                        const int n_comp = __popc(any_dir) + __popc(twice), threes = __popc(strong) + __popc(twice_strong);
+                        if (n_comp < 2) {
+                            s_misc[2] = 1;                                                                   // reference reads out of bounds here
+                        } else {
+                            const int ctype = min(threes, 2);
+                            atomicAdd(&s_misc[12 + ctype], c ? 0x10000u : 1u);
+                            // updateCritical, both perspectives: the colour's pair of the cell
+                            const uint32_t crit = 600u * static_cast<uint32_t>(n_comp);
+                            atomicAdd(reinterpret_cast<unsigned long long*>(s_scores) + 2 * q + c, (static_cast<unsigned long long>(crit) << 32) | crit);
+                            // exactly two components, no live three among them: queue their counter-move rescans, in direction order, with what
+                            // phase 4 needs of each line ready in the entry: q | colour << 8 | direction << 9 | type slot << 11 | line word << 13 |
+                            // q's slot in the word << 20.  A line word holds cell x at slot x (rows, diagonals) or y (columns, anti-diagonals), so
+                            // per direction d = 0..3 the word is byte d of `lines` and the slot nibble d of `slots`
+                            queue = n_comp < 3 && !sel3;
+                            const uint32_t b1 = static_cast<uint32_t>(__ffs(any_dir) - 1);                   // 4 d1
+                            const uint32_t others = any_dir & (any_dir - 1u);
+                            const uint32_t b2 = others ? static_cast<uint32_t>(__ffs(others) - 1) : b1;       // 4 d2
+                            const uint32_t ux = static_cast<uint32_t>(qx), uy = static_cast<uint32_t>(qy);
+                            const uint32_t lines = (static_cast<uint32_t>(kColBase) << 8 | static_cast<uint32_t>(kDiagBase + 14) << 16 | static_cast<uint32_t>(kAntiBase) << 24)
+                                                   + ((ux << 8) * 0x10101u) + uy * 0xFF0001u;               // y | 20 + x | 50 + x - y | 65 + x + y
+                            const uint32_t slots = ux * 0x0101u + uy * 0x1010u;                              // x | y | x | y
+                            const uint32_t head = static_cast<uint32_t>(q) | (static_cast<uint32_t>(c) << 8);
+                            auto entry = [&](uint32_t b) {
+                                const uint32_t tslot = ((seld >> b) & 1u) ? 1u : 2u;                         // DeadThree 1, LiveTwo 2
+                                return head | (b >> 2) << 9 | tslot << 11 | __builtin_amdgcn_ubfe(lines, 2 * b, 8) << 13 | __builtin_amdgcn_ubfe(slots, b, 4) << 20;
+                            };
+                            ent1 = entry(b1);
+                            ent2 = entry(b2);
+                        }
                     }
                 }
-                if (dens < 2u) continue;
-                // The reference walks the directions in order through a state machine S0, L2, LD3, To33, To43, To44 (Pattern.cpp:440-486); in
-                // each direction the component is the first of LiveThree, DeadThree, LiveTwo with a non-zero counter, taken once or twice (the
-                // counters count like its 2-bit shift flags: 0, 1, 2 or more, Pattern.cpp:395-400).  Its outcome does not depend on the order:
-                // with n components of which s are threes (weight 2, a LiveTwo 1), the state ends at 3 + min(2, s) for n >= 2 -- the first two
-                // transitions add w1 + w2 + 1, every further one w - 1, capped at 5 -- and the "triple" flag is n >= 3.  So: nibble masks.
-                const uint32_t up3 = (f3 >> 1) | (f3 >> 2) | (f3 >> 3), upd = (fd >> 1) | (fd >> 2) | (fd >> 3), up2 = (f2 >> 1) | (f2 >> 2) | (f2 >> 3);
-                const uint32_t sel3 = (f3 | up3) & 0x1111u;                                          // directions whose component is a LiveThree
-                const uint32_t seld = (fd | upd) & 0x1111u & ~sel3;                                  // ... a DeadThree
-                const uint32_t sel2 = (f2 | up2) & 0x1111u & ~(sel3 | seld);                         // ... a LiveTwo
-                const uint32_t strong = sel3 | seld, any_dir = strong | sel2;
-                const uint32_t twice_strong = (sel3 & up3) | (seld & upd), twice = twice_strong | (sel2 & up2);     // taken twice (counter >= 2)
-                const int n_comp = __popc(any_dir) + __popc(twice), threes = __popc(strong) + __popc(twice_strong);
-                if (n_comp < 2) { s_misc[2] = 1; continue; }                                         // reference reads out of bounds here
-                const int ctype = min(threes, 2);
-                atomicAdd(&s_misc[12 + ctype], c ? 0x10000u : 1u);
-                // updateCritical, both perspectives: the colour's pair of the cell
-                const uint32_t crit = 600u * static_cast<uint32_t>(n_comp);
-                atomicAdd(reinterpret_cast<unsigned long long*>(s_scores) + 2 * q + c, (static_cast<unsigned long long>(crit) << 32) | crit);
-                if (n_comp >= 3 || sel3) continue;                                                   // a triple cross, or a live three among them
-                // exactly two components, in direction order: queue their counter-move rescans
-                const int d1 = (__ffs(any_dir) - 1) >> 2;
-                const uint32_t others = any_dir & (any_dir - 1u);
-                const int d2 = others ? (__ffs(others) - 1) >> 2 : d1;
-                const uint32_t cd1 = static_cast<uint32_t>(d1) | (((seld >> (4 * d1)) & 1u) ? 4u : 8u), cd2 = static_cast<uint32_t>(d2) | (((seld >> (4 * d2)) & 1u) ? 4u : 8u);
-                const uint32_t slot = atomicAdd(&s_misc[3], 2u);
-                const uint32_t head = static_cast<uint32_t>(q) | (static_cast<uint32_t>(c) << 8);
-                if (slot < kQueueCap / 2) s_queue[kQueueCap / 2 + slot] = head | (cd1 << 9);
-                if (slot + 1 < kQueueCap / 2) s_queue[kQueueCap / 2 + slot + 1] = head | (cd2 << 9);
-                else s_misc[2] = 1;
+                const unsigned long long queuers = __ballot(queue);
+                if (queue) {
+                    const uint32_t slot = static_cast<uint32_t>(n_comp_q) + 2u * __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(queuers >> 32),
+                                                                                                          __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(queuers), 0u));
+                    if (slot < kQueueCap / 2) { s_queue[kQueueCap / 2 + slot] = ent1; s_queue[kQueueCap / 2 + slot + 1] = ent2; }      // (slots are even)
+                    else s_misc[2] = 1;
+                }
+                n_comp_q += 2 * __popcll(queuers);
             }
             wave_phase_fence();
             GMK_STAMP(5);
 
             // ---- phase 4: the counter-move cells of every compound component: the FIRST match of its type that runs through
             //      the cell with a blank there (Compound::updateAntis, Pattern.cpp:520-543), scanning the 13-symbol window
-            //      centred on the cell.  Such a match ends at window index 6..12; eight lanes share a component, lane kk looks
-            //      at the transition at index 6 + kk only (the automaton forgets its start state after 7 symbols, so <= 8
-            //      lookups from the root bring it to the right state), and the lowest lane with a hit applies it ----
+            //      centred on the cell.  Such a match ends at window index 6..12; seven lanes share a component (nine components
+            //      per round, lane 63 idle), lane kk looks at the transition at index 6 + kk only (the automaton forgets its start
+            //      state after 7 symbols, so <= 8 lookups from the root bring it to the right state), and the lowest lane with a hit applies it ----
             if (phase_mask & 16) {
-                const int n_comp = min(static_cast<int>(s_misc[3]), kQueueCap / 2);
-                for (int m0 = 0; m0 < n_comp; m0 += 8) {
-                    const int m = m0 + (lane >> 3), kk = lane & 7, k = 6 + kk;
-                    const uint32_t ent = m < n_comp ? s_queue[kQueueCap / 2 + m] : 0u;
+                const int n_comp = min(n_comp_q, kQueueCap / 2);
+                int lane_4 = lane;                                  // (an opaque copy: the lane's place is derived here, not kept in registers
+                asm volatile("" : "+v"(lane_4));                    //  across the whole board loop)
+                const int grp = lane_4 / 7, kk = lane_4 - 7 * grp, k = 6 + kk, start = k > 7 ? k - 7 : 0;
+                for (int m0 = 0; m0 < n_comp; m0 += 9) {
+                    const int m = m0 + grp;
+                    const bool on = lane < 63 && m < n_comp;
+                    const uint32_t ent = on ? s_queue[kQueueCap / 2 + m] : 0u;
                     const int q = ent & 255, c = (ent >> 8) & 1, dir = (ent >> 9) & 3, tslot = (ent >> 11) & 3;
-                    const int want = tslot == 0 ? 5 : tslot == 1 ? 4 : 3;
-                    const int x = q % 15, y = q / 15, stride = dir_stride(dir);
+                    const int stride = dir_stride(dir);
                     uint32_t hit_w0 = 0;
                     int hit_back = -1;
-                    if (m < n_comp && kk < 7) {
-                        // the line through q in this direction: its word, q's position on it, its length
-                        const int diag = x - y + 14, anti = x + y;
-                        const int line = dir == 0 ? y : dir == 1 ? kColBase + x : dir == 2 ? kDiagBase + diag : kAntiBase + anti;
-                        const int at = dir == 0 ? x : dir == 1 ? y : dir == 2 ? min(x, y) : min(14 - x, y);
-                        const int first_at = dir == 2 ? 2 * (x - at) : dir == 3 ? 2 * (y - at) : 0;       // the line's first cell in its word (diagonals: bits 2 x / 2 y)
-                        const int len = dir < 2 ? 15 : dir == 2 ? 15 - abs(diag - 14) : min(anti, 28 - anti) + 1;
-                        // six '?' | cells | six '?', then the 13 symbols starting six before q
-                        const uint64_t syms = (0xAAAull | (static_cast<uint64_t>(s_lines[line] >> first_at) << 12) | (0xAAAull << (2 * len + 12))) >> (2 * at);
-                        const int start = k > 7 ? k - 7 : 0;
-                        const uint32_t cur = static_cast<uint32_t>(syms >> (2 * start)) << 2;      // kept shifted left by 2 as in phase 1
+                    if (on) {
+                        // the line through q in this direction, '?' off the line, and its symbols from window index `start` on (window index
+                        // 0 = six cells before q): slot `first` of the word and the ones after it, '?' beyond either end of the word
+                        const uint32_t line = (ent >> 13) & 127u;
+                        const uint32_t word = s_lines[line] | s_pads[line];
+                        const int first = static_cast<int>((ent >> 20) & 15u) + start - 6;                  // -6 .. 13
+                        const uint32_t cur = __builtin_amdgcn_alignbit(first >= 0 ? 0xAAAAAAAAu : word, first >= 0 ? word : 0xAAAAAAAAu,
+                                                                       static_cast<uint32_t>(2 * first) & 31u) << 2;      // kept shifted left by 2 as in phase 1
                         uint32_t tw = 0;
     #pragma unroll
                         for (int i = 0; i < 8; ++i)
                             if (start + i <= k) tw = *lds_word(dfa_address(tw, __builtin_amdgcn_ubfe(cur, 2 * i, 4)));      // v_bfe + v_bfi, as in phase 1
                         if ((gmk::dev_trans_kinds(tw) >> tslot) & 1u) {                     // the record holds the wanted type
                             const uint4 rec = s_rec[gmk::dev_trans_record(tw)];
+                            const int want = 5 - tslot;                                     // LiveThree 5, DeadThree 4, LiveTwo 3
                             hit_back = counter_match(rec.x, k, want);
                             hit_w0 = rec.x;
                             if (hit_back < 0) { hit_back = counter_match(rec.z, k, want); hit_w0 = rec.z; }
                         }
                     }
                     const unsigned long long hits = __ballot(hit_back >= 0);
-                    const uint32_t mine = static_cast<uint32_t>(hits >> (lane & ~7)) & 0xFFu;
+                    const uint32_t mine = static_cast<uint32_t>(hits >> (7 * grp)) & 0x7Fu;
                     if (hit_back >= 0 && (mine & ((1u << kk) - 1u)) == 0u) add_counter_cells(hit_w0, hit_back, q, stride, s_scores + (c ? 2 : 1));
                 }
             }

@@ -5,7 +5,7 @@
 # COUNTERS="..." picks another counter group (e.g. the LDS ones: SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS).
 cd "${GRAFT_REPO_ROOT:-.}" && export TMPDIR=/tmp
 out=gpurun_out/pmc_k1p; rm -rf $out; mkdir -p $out
-export GMK_EVAL_REPS=20 GMK_HIP_LIB=prof          # the phase masks live in the profiling flavour of the library only
+export GMK_EVAL_REPS=20 GMK_HIP_LIB=${K1_LIB:-prof}     # the phase masks live in the profiling flavour of the library only (K1_LIB: another build of it, by path)
 for m in ${MASKS:-1 3 7 15 31 63 127 1151 639}; do
   t=$(GMK_EVAL_PHASE_MASK=$m GMK_EVAL_REPS=100 timeout -k 10 120 python3 tools/eval_time.py all | tail -1)
   GMK_EVAL_PHASE_MASK=$m timeout -k 10 240 rocprofv3 --pmc ${COUNTERS:-SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU} -d $out/m_$m -o p --output-format csv -- python3 tools/eval_time.py all > $out/run_$m.log 2>&1 || { echo "mask $m failed"; tail -5 $out/run_$m.log; exit 1; }
