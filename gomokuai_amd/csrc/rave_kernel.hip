@@ -346,7 +346,7 @@ extern "C" int gmk_trad_run_poolrave(gmk_trad* t, int playouts, double c_puct, u
     if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
     if (!t || playouts < 0) { gmk::set_error("gmk_trad_run_poolrave: bad arguments"); return GMK_ERR_ARG; }
     if (!t->positioned) { gmk::set_error("gmk_trad_run_poolrave: gmk_trad_set_positions has not been called"); return GMK_ERR_STATE; }
-    if (t->policy == 1) { gmk::set_error("gmk_trad_run_poolrave: this handle searches with gmk_trad_run (its nodes carry no AMAF statistics)"); return GMK_ERR_STATE; }
+    if (t->policy == 1 || t->policy == 3) { gmk::set_error("gmk_trad_run_poolrave: this handle searches with gmk_trad_run%s", t->policy == 3 ? "_rave" : " (its nodes carry no AMAF statistics)"); return GMK_ERR_STATE; }
     t->policy = 2;
     if (!t->d_amaf) {
         const size_t nodes = static_cast<size_t>(t->n_games) * static_cast<size_t>(t->cap);
@@ -378,7 +378,7 @@ extern "C" int gmk_trad_run_poolrave(gmk_trad* t, int playouts, double c_puct, u
 
 extern "C" int gmk_trad_root_amaf(gmk_trad* t, uint32_t* h_amaf_visits, float* h_amaf_values) {
     if (!t || !h_amaf_visits || !h_amaf_values) { gmk::set_error("gmk_trad_root_amaf: bad arguments"); return GMK_ERR_ARG; }
-    if (!t->d_amaf) { gmk::set_error("gmk_trad_root_amaf: gmk_trad_run_poolrave has not been called on this handle"); return GMK_ERR_STATE; }
+    if (!t->d_amaf) { gmk::set_error("gmk_trad_root_amaf: neither gmk_trad_run_poolrave nor gmk_trad_run_rave has been called on this handle"); return GMK_ERR_STATE; }
     const size_t n = static_cast<size_t>(t->n_games);
     uint32_t* d_visits = nullptr;
     float* d_values = nullptr;

@@ -5,7 +5,8 @@
 //   simulate  Heuristic::EvaluationProbs -> DecisiveFilter -> EvaluationValue on the policy's own incremental Evaluator
 //             (Heuristic.hpp:16-45, 94-161), no rollout
 //   expand    Default::Expand without the legality check: one child per cell with a non-zero prior (MonteCarlo.hpp:71-80)
-//   backup    RAVE::BackPropogate<false>: per level, the child with the best PUCB + Q moves to the front (:160-184)
+//   backup    RAVE::BackPropogate<false>: per level, the child with the best PUCB + Q moves to the front (:160-184);
+//             TraditionalPolicy(use_rave=True) (gmk_trad_run_rave): BackPropogate<true> against the leaf position (kRave below)
 //   moves     Heuristic::CachedApplyMove / CachedRevertMove: the evaluator stays at the last leaf and is rolled back
 //             (or rebuilt) only as far as the next path differs (Heuristic.hpp:165-200)
 // The search has no random numbers; it is a serial chain per game, so the GPU runs MANY games: one wavefront per
@@ -71,6 +72,7 @@ struct TradParams {
     double c_puct;
     int selfplay;                                // != 0: every wavefront plays whole games, search after search, until the games have run out (sp)
     TradSelfPlay sp;
+    uint2* amaf;                                 // [n_games][cap] {amaf_visits, amaf_value bits}: kRave only
 };
 
 using gmk::noise::tree_sum;                      // the one summation order of the float reductions (noise_device.h; oracle/go_trad.c: sum225)
@@ -184,6 +186,7 @@ struct Game {
     uint32_t* link;
     uint2* front;
     uint8_t* ord;
+    uint2* amaf;
     int cached, init;
     unsigned long long updates;
 };
@@ -224,7 +227,10 @@ template <bool kWaveOnly> __device__ __forceinline__ void copy_sync();
 
 // kSelfPlay = false: one search per game (gmk_trad_run); true: the persistent self-play loop (gmk_trad_selfplay_run, persistent = 1).  Two
 // instantiations, so that the bare search does not carry the registers of the turn loop through its playouts.
-template <bool kSelfPlay>
+// kRave: TraditionalPolicy with RAVE::BackPropogate<true> (gmk_trad_run_rave, policy 2 of the self-play loop): the same playout, the backup
+// also keeps every child's all-moves-as-first statistics (the node's AMAF record, prm.amaf) against the LEAF position -- the evaluator's
+// row words -- and ranks the children by PUCB + the HandSelect-weighted value, as K8 does on its finished board.
+template <bool kSelfPlay, bool kRave>
 __global__ __launch_bounds__(kThreads)
 void trad_playouts_kernel(TradParams prm) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -255,6 +261,7 @@ void trad_playouts_kernel(TradParams prm) {
     auto use_arena = [&](uint32_t which) {
         const size_t at = arena + ((kSelfPlay && which) ? prm.sp.arena_stride : 0);
         g.stat = prm.stat + at; g.info = prm.info + at; g.link = prm.link + at; g.front = prm.front + at; g.ord = prm.ord + at;
+        if (kRave) g.amaf = prm.amaf + at;
     };
     use_arena(0);
     g.updates = 0;
@@ -385,6 +392,7 @@ void trad_playouts_kernel(TradParams prm) {
                     g.stat[0] = make_uint2(0u, 0u);
                     g.info[0] = make_uint2(kNoParent | ((n_position ? slot_moves[n_position - 1] : 255u) << 24), __float_as_uint(1.0f));
                     g.link[0] = 0u;
+                    if (kRave) g.amaf[0] = make_uint2(0u, 0u);
                     g.set_link(0, 0u);
                 }
                 n_nodes = 1;
@@ -456,6 +464,7 @@ void trad_playouts_kernel(TradParams prm) {
                             g.info[child] = make_uint2(node | (static_cast<uint32_t>(lane + 64 * j) << 24), __float_as_uint(probs.v[j]));
                             g.link[child] = 0u;
                             g.ord[child] = static_cast<uint8_t>(rank[j]);
+                            if (kRave) g.amaf[child] = make_uint2(0u, 0u);
                         }
                     link = n_nodes | (static_cast<uint32_t>(total) << 24);
                     if (lane == 0) {
@@ -479,7 +488,7 @@ void trad_playouts_kernel(TradParams prm) {
         if (status & 1u) break;
         if (gmk::kProfileBuild && prm.profile) { const unsigned long long t = __builtin_amdgcn_s_memtime(); prof_sim += t - prof_t0; prof_t0 = t; }
 
-        // ---- RAVE::BackPropogate<false> (MonteCarlo.hpp:160-184), leaf to root ----
+        // ---- RAVE::BackPropogate<kRave> (MonteCarlo.hpp:154-184), leaf to root; the leaf position is in the evaluator's row words ----
         int swap_level = -1;
         uint2 swap_rec = make_uint2(0u, 0u);
         uint32_t updated_id = 0xFFFFFFFFu;                      // the path node one level below: its statistics were just rewritten
@@ -493,6 +502,7 @@ void trad_playouts_kernel(TradParams prm) {
             const double sqrt_n = sqrt(static_cast<double>(cur.ns.x));
             double best_score = -INFINITY;
             uint32_t best_ord = 0xFFFFFFFFu;
+            const uint32_t child_sym = (((d + 1) & 1) ? !root_black : root_black) ? 0u : 1u;         // kRave: the children's stone in the row words, 0 black, 1 white
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const uint32_t i = lane + 64 * k;
@@ -501,7 +511,21 @@ void trad_playouts_kernel(TradParams prm) {
                 if (first + i == updated_id) cs = updated_stat;
                 const double p_i = __uint_as_float(cur.ci[k].y), n_i = static_cast<double>(cs.x + 1u);
                 double score = prm.c_puct * p_i * sqrt_n / n_i;                        // Default::PUCB (:23-28)
-                score += __uint_as_float(cs.y);
+                if constexpr (kRave) {
+                    const uint32_t cell = cur.ci[k].x >> 24, y = cell / 15u, x = cell - 15u * y;
+                    const uint2 ca = g.amaf[first + i];                 // the child's AMAF record: read here, not with the level in flight (registers)
+                    float aq = __uint_as_float(ca.y);
+                    if (((g.c.st[oLines + y] >> (2u * x)) & 3u) == child_sym) {        // board.moveState(child.player, child.position)
+                        const uint32_t av = ca.x + 1u;
+                        aq += (-value - aq) / static_cast<float>(av);
+                        g.amaf[first + i] = make_uint2(av, __float_as_uint(aq));
+                    }
+                    const double visits = static_cast<double>(cs.x), eqv = 800.0;
+                    const double weight = sqrt(eqv / (3 * visits + eqv));              // RAVE::HandSelect (:124-128)
+                    score += (1 - weight) * __uint_as_float(cs.y) + weight * aq;        // RAVE::WeightedValue (:138-142)
+                } else {
+                    score += __uint_as_float(cs.y);
+                }
                 // the reference scans the children in their current order and keeps the first maximum
                 if (score > best_score || (score == best_score && cur.co[k] < best_ord)) { best_score = score; best_ord = cur.co[k]; }
             }
@@ -599,9 +623,9 @@ void trad_playouts_kernel(TradParams prm) {
         bool kept = false;
         if (!over && sp.reuse) {
             // MCTS::stepForward (MCTS.cpp:129-134): the chosen child's subtree is the next search's tree -- compacted into the slot's other arena
-            const TradArena a{g.stat, g.info, g.link, g.front, g.ord, nullptr};
+            const TradArena a{g.stat, g.info, g.link, g.front, g.ord, kRave ? g.amaf : nullptr};
             use_arena(live ^ 1u);
-            const TradArena b{g.stat, g.info, g.link, g.front, g.ord, nullptr};
+            const TradArena b{g.stat, g.info, g.link, g.front, g.ord, kRave ? g.amaf : nullptr};
             n_nodes = copy_subtree<true>(a, b, 0, best_id, lane);
             live ^= 1u;
             root_black ^= 1;
@@ -955,9 +979,10 @@ void trad_root_stats_kernel(const uint2* stat, const uint2* info, const uint32_t
 
 extern "C" int gmk_trad_destroy(gmk_trad* t) {
     if (!t) return GMK_OK;
-    if (t->paired) {                                            // both arenas are halves of the five blocks
+    if (t->paired) {                                            // both arenas are halves of the five (six) blocks
         (void)gmk::device_free(t->block_stat); (void)gmk::device_free(t->block_info); (void)gmk::device_free(t->block_link); (void)gmk::device_free(t->block_front); (void)gmk::device_free(t->block_ord);
         t->d_stat = t->d_stat2 = t->d_info = t->d_info2 = t->d_front = t->d_front2 = nullptr; t->d_link = t->d_link2 = nullptr; t->d_ord = t->d_ord2 = nullptr;
+        if (t->block_amaf) { (void)gmk::device_free(t->block_amaf); t->block_amaf = t->d_amaf = t->d_amaf2 = nullptr; }
     }
     (void)gmk::device_free(t->d_states); (void)gmk::device_free(t->d_stat); (void)gmk::device_free(t->d_info); (void)gmk::device_free(t->d_link);
     (void)gmk::device_free(t->d_front); (void)gmk::device_free(t->d_ord); (void)gmk::device_free(t->d_stat2); (void)gmk::device_free(t->d_info2); (void)gmk::device_free(t->d_front2);
@@ -1016,9 +1041,13 @@ static int pair_arenas(gmk_trad* t) {
     auto point = [&]() {
         t->d_stat = t->block_stat; t->d_info = t->block_info; t->d_link = t->block_link; t->d_front = t->block_front; t->d_ord = t->block_ord;
         t->d_stat2 = t->block_stat + nodes; t->d_info2 = t->block_info + nodes; t->d_link2 = t->block_link + nodes; t->d_front2 = t->block_front + nodes; t->d_ord2 = t->block_ord + nodes;
+        if (t->block_amaf) { t->d_amaf = t->block_amaf; t->d_amaf2 = t->block_amaf + nodes; }
     };
     if (t->paired) { point(); return GMK_OK; }                  // (the lock-step loop may have left the halves swapped)
-    if (t->d_amaf) { gmk::set_error("gmk_trad_selfplay_run: the persistent loop keeps subtrees for TraditionalPolicy handles only"); return GMK_ERR_STATE; }
+    if (t->policy == 2) { gmk::set_error("gmk_trad_selfplay_run: the persistent loop keeps subtrees for TraditionalPolicy handles only"); return GMK_ERR_STATE; }
+    // (a TraditionalPolicy + RAVE handle's AMAF statistics go with its trees; ensure_amaf makes their block when a run needs it)
+    (void)gmk::device_free(t->d_amaf); (void)gmk::device_free(t->d_amaf2);
+    t->d_amaf = t->d_amaf2 = nullptr;
     uint2 *bs = nullptr, *bi = nullptr, *bf = nullptr;
     uint32_t* bl = nullptr;
     uint8_t* bo = nullptr;
@@ -1044,6 +1073,27 @@ static int pair_arenas(gmk_trad* t) {
     t->second_arena = true;
     if (!t->d_forced && gmk::device_malloc(&t->d_forced, static_cast<size_t>(t->n_games) * 2) != hipSuccess) { (void)hipGetLastError(); gmk::set_error("gmk_trad_selfplay_run: hipMalloc failed"); return GMK_ERR_HIP; }
     point();
+    return GMK_OK;
+}
+
+// The AMAF statistics of a TraditionalPolicy + RAVE handle (gmk_trad_run_rave, policy 2 of the self-play loop): one block of zeros per arena, or
+// the two halves of one block when the arenas are paired (the persistent loop re-points it with the five others).
+static int ensure_amaf(gmk_trad* t) {
+    const size_t nodes = static_cast<size_t>(t->n_games) * static_cast<size_t>(t->cap);
+    if (t->paired) {
+        if (t->block_amaf) return GMK_OK;
+        (void)gmk::device_free(t->d_amaf); (void)gmk::device_free(t->d_amaf2);
+        t->d_amaf = t->d_amaf2 = nullptr;
+        GMK_HIP_CHECK(gmk::device_malloc(&t->block_amaf, 2 * nodes * 8));
+        GMK_HIP_CHECK(hipMemset(t->block_amaf, 0, 2 * nodes * 8));
+        const bool swapped = t->d_stat != t->block_stat;        // (the lock-step loop may have left the halves swapped)
+        t->d_amaf = t->block_amaf + (swapped ? nodes : 0); t->d_amaf2 = t->block_amaf + (swapped ? 0 : nodes);
+        return GMK_OK;
+    }
+    if (!t->d_amaf) {
+        GMK_HIP_CHECK(gmk::device_malloc(&t->d_amaf, nodes * 8));
+        GMK_HIP_CHECK(hipMemset(t->d_amaf, 0, nodes * 8));
+    }
     return GMK_OK;
 }
 
@@ -1097,28 +1147,36 @@ extern "C" int gmk_trad_set_positions(gmk_trad* t, const uint8_t* h_moves, const
     return GMK_OK;
 }
 
-extern "C" int gmk_trad_run(gmk_trad* t, int playouts, double c_puct, void* stream) {
+// gmk_trad_run / gmk_trad_run_rave: `playouts` playouts per game with RAVE::BackPropogate<rave>
+template <bool kRave>
+static int trad_run(gmk_trad* t, int playouts, double c_puct, void* stream, const char* name) {
     gmk::DeviceState& st = gmk::device_state();
-    if (!t || playouts < 0) { gmk::set_error("gmk_trad_run: bad arguments"); return GMK_ERR_ARG; }
-    if (!t->positioned) { gmk::set_error("gmk_trad_run: gmk_trad_set_positions has not been called"); return GMK_ERR_STATE; }
-    if (t->policy == 2) { gmk::set_error("gmk_trad_run: this handle searches with gmk_trad_run_poolrave (its evaluators are not kept in step)"); return GMK_ERR_STATE; }
-    t->policy = 1;
+    if (!t || playouts < 0) { gmk::set_error("%s: bad arguments", name); return GMK_ERR_ARG; }
+    if (!t->positioned) { gmk::set_error("%s: gmk_trad_set_positions has not been called", name); return GMK_ERR_STATE; }
+    if (t->policy == 2) { gmk::set_error("%s: this handle searches with gmk_trad_run_poolrave (its evaluators are not kept in step)", name); return GMK_ERR_STATE; }
+    if (t->policy == (kRave ? 1 : 3)) {
+        gmk::set_error(kRave ? "%s: this handle searches with gmk_trad_run (its nodes carry no AMAF statistics)" : "%s: this handle searches with gmk_trad_run_rave (its backup keeps AMAF statistics)", name);
+        return GMK_ERR_STATE;
+    }
+    if (kRave) { const int rc = ensure_amaf(t); if (rc != GMK_OK) return rc; }
+    t->policy = kRave ? 3 : 1;
     const size_t lds = static_cast<size_t>(kGamesPerBlock * kPerGame + st.n_states * 4 + st.n_records * 4 + gmk::kPrefixWords) * 4;
-    if (lds > 160u * 1024u) { gmk::set_error("gmk_trad_run: tables do not fit in LDS (%zu bytes)", lds); return GMK_ERR_CAPACITY; }
-    if (!t->attr_set) {
-        GMK_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trad_playouts_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        t->attr_set = true;
+    if (lds > 160u * 1024u) { gmk::set_error("%s: tables do not fit in LDS (%zu bytes)", name, lds); return GMK_ERR_CAPACITY; }
+    bool& attr_set = kRave ? t->attr_set_rave : t->attr_set;
+    if (!attr_set) {
+        GMK_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trad_playouts_kernel<false, kRave>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_set = true;
     }
     TradParams prm;
     prm.states = t->d_states; prm.stat = t->d_stat; prm.info = t->d_info; prm.link = t->d_link; prm.front = t->d_front; prm.ord = t->d_ord; prm.hdr = t->d_hdr;
     prm.moves = t->d_moves; prm.lens = t->d_lens;
     prm.g_trans = st.d_trans; prm.g_records = st.d_records; prm.trans_words = st.n_states * 4; prm.record_words = st.n_records * 4 + gmk::kPrefixWords; prm.path_spill = t->d_path_spill;
     prm.n_games = t->n_games; prm.cap = t->cap; prm.playouts = playouts; prm.c_puct = c_puct;
-    prm.selfplay = 0; prm.sp = TradSelfPlay{};
+    prm.selfplay = 0; prm.sp = TradSelfPlay{}; prm.amaf = kRave ? t->d_amaf : nullptr;
     static const bool profile = gmk::profile_env("GMK_TRAD_PROFILE") != nullptr;
     prm.profile = profile ? 1 : 0;
     const int grid = (t->n_games + kGamesPerBlock - 1) / kGamesPerBlock;
-    hipLaunchKernelGGL(trad_playouts_kernel<false>, dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), prm);
+    hipLaunchKernelGGL((trad_playouts_kernel<false, kRave>), dim3(grid), dim3(kThreads), lds, static_cast<hipStream_t>(stream), prm);
     GMK_HIP_CHECK(hipGetLastError());
     if (profile) {                                              // share of a search spent per stage, mean over games
         std::vector<TradHeader> hdr(static_cast<size_t>(t->n_games));
@@ -1130,6 +1188,14 @@ extern "C" int gmk_trad_run(gmk_trad* t, int playouts, double c_puct, void* stre
                      100 * sum[0] / sum[3], 100 * sum[1] / sum[3], 100 * sum[2] / sum[3]);
     }
     return GMK_OK;
+}
+
+extern "C" int gmk_trad_run(gmk_trad* t, int playouts, double c_puct, void* stream) {
+    return trad_run<false>(t, playouts, c_puct, stream, "gmk_trad_run");
+}
+
+extern "C" int gmk_trad_run_rave(gmk_trad* t, int playouts, double c_puct, void* stream) {
+    return trad_run<true>(t, playouts, c_puct, stream, "gmk_trad_run_rave");
 }
 
 extern "C" int gmk_trad_root_stats(gmk_trad* t, uint32_t* h_visits, float* h_values, float* h_priors, int32_t* h_best,
@@ -1257,17 +1323,17 @@ extern "C" int gmk_trad_read_evaluators(gmk_trad* t, int32_t* h_scores, int32_t*
 // The self-play loop of network/data_helper.py:56-83 for the pattern-guided searchers, resident on the device: n_total games through the
 // handle's slots, every move = Default::AddNoise (if asked for) + one search of `playouts` playouts for every slot that has a game +
 // trad_advance_kernel; the host sees four bytes per move (slots that still play) and, with root noise, the slots' game numbers.
-extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int poolrave, int n_total, uint32_t first_game_id, int playouts, double c_puct, uint64_t seed,
+extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int policy, int n_total, uint32_t first_game_id, int playouts, double c_puct, uint64_t seed,
                                      int reuse_subtree, float noise_alpha, float noise_epsilon,
                                      const uint8_t* h_open_moves, int open_stride, const int32_t* h_open_lens,
                                      uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int persistent, int max_steps, int32_t* h_overflow, int32_t* h_steps, void* stream) {
     const bool noisy = noise_alpha > 0.0f && reuse_subtree;     // (a new root has no children: AddNoise is a no-op without kept subtrees)
     if (t && t->lockstep) persistent = 0;
-    if (persistent && (poolrave || max_steps > 0 || (noisy && t && t->noise_sampler != GMK_NOISE_SAMPLER_COUNTER))) {
-        gmk::set_error("gmk_trad_selfplay_run: the persistent loop plays TraditionalPolicy games to their end; root noise inside it comes from the counter-based sampler (GMK_OPT_NOISE_SAMPLER)");
+    if (persistent && (policy == 1 || max_steps > 0 || (noisy && t && t->noise_sampler != GMK_NOISE_SAMPLER_COUNTER))) {
+        gmk::set_error("gmk_trad_selfplay_run: the persistent loop plays TraditionalPolicy (+ RAVE) games to their end; root noise inside it comes from the counter-based sampler (GMK_OPT_NOISE_SAMPLER)");
         return GMK_ERR_ARG;
     }
-    if (!t || n_total <= 0 || playouts < 0 || max_steps < 0 || !d_moves || !d_lens || !d_winner || (h_open_moves && (!h_open_lens || open_stride <= 0))) {
+    if (!t || policy < 0 || policy > 2 || n_total <= 0 || playouts < 0 || max_steps < 0 || !d_moves || !d_lens || !d_winner || (h_open_moves && (!h_open_lens || open_stride <= 0))) {
         gmk::set_error("gmk_trad_selfplay_run: bad arguments");
         return GMK_ERR_ARG;
     }
@@ -1299,6 +1365,10 @@ extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int poolrave, int n_total, uin
     state[ns + 2] = 0;                                          // overflow
     int rc = GMK_OK;
     if (persistent && reuse_subtree) rc = pair_arenas(t);       // a slot's two arenas, a fixed stride apart
+    if (rc == GMK_OK && persistent && policy == 2) {            // (the lock-step loop's gmk_trad_run_rave makes them itself)
+        if (t->policy == 1 || t->policy == 2) { gmk::set_error("gmk_trad_selfplay_run: this handle searches with another policy"); return GMK_ERR_STATE; }
+        rc = ensure_amaf(t);
+    }
     if (rc == GMK_OK) rc = gmk_trad_set_game_ids(t, ids.data());
     if (rc == GMK_OK) { t->positioned = true; rc = gmk_trad_set_positions(t, slot_moves.data(), slot_lens.data()); }     // (every slot is positioned anew)
     if (rc != GMK_OK) return rc;
@@ -1351,20 +1421,24 @@ extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int poolrave, int n_total, uin
     if (persistent) {
         // ONE launch: every wavefront plays game after game at its own pace (trad_playouts_kernel, prm.selfplay)
         gmk::DeviceState& st = gmk::device_state();
-        if (t->policy == 2) { gmk::set_error("gmk_trad_selfplay_run: this handle searches with PoolRAVEPolicy"); cleanup(); return GMK_ERR_STATE; }
-        t->policy = 1;
+        const bool rave = policy == 2;
+        if (t->policy == 2 || t->policy == (rave ? 1 : 3)) { gmk::set_error("gmk_trad_selfplay_run: this handle searches with another policy"); cleanup(); return GMK_ERR_STATE; }
+        t->policy = rave ? 3 : 1;
         const size_t lds = static_cast<size_t>(kGamesPerBlock * kPerGame + st.n_states * 4 + st.n_records * 4 + gmk::kPrefixWords) * 4;
-        if (!t->attr_set_selfplay) {
-            GMK_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(trad_playouts_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            t->attr_set_selfplay = true;
+        bool& attr_set = rave ? t->attr_set_selfplay_rave : t->attr_set_selfplay;
+        if (!attr_set) {
+            GMK_TRY(hipFuncSetAttribute(rave ? reinterpret_cast<const void*>(trad_playouts_kernel<true, true>) : reinterpret_cast<const void*>(trad_playouts_kernel<true, false>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            attr_set = true;
         }
         TradParams prm;
         prm.states = t->d_states; prm.stat = t->d_stat; prm.info = t->d_info; prm.link = t->d_link; prm.front = t->d_front; prm.ord = t->d_ord; prm.hdr = t->d_hdr;
         prm.moves = t->d_moves; prm.lens = t->d_lens;
         prm.g_trans = st.d_trans; prm.g_records = st.d_records; prm.trans_words = st.n_states * 4; prm.record_words = st.n_records * 4 + gmk::kPrefixWords; prm.path_spill = t->d_path_spill;
         prm.n_games = n_slots; prm.cap = t->cap; prm.playouts = playouts; prm.c_puct = c_puct;
-        prm.profile = 0; prm.selfplay = 1; prm.sp = sp;
-        hipLaunchKernelGGL(trad_playouts_kernel<true>, dim3((n_slots + kGamesPerBlock - 1) / kGamesPerBlock), dim3(kThreads), lds, s, prm);
+        prm.profile = 0; prm.selfplay = 1; prm.sp = sp; prm.amaf = rave ? t->d_amaf : nullptr;
+        if (rave) hipLaunchKernelGGL((trad_playouts_kernel<true, true>), dim3((n_slots + kGamesPerBlock - 1) / kGamesPerBlock), dim3(kThreads), lds, s, prm);
+        else hipLaunchKernelGGL((trad_playouts_kernel<true, false>), dim3((n_slots + kGamesPerBlock - 1) / kGamesPerBlock), dim3(kThreads), lds, s, prm);
         GMK_TRY(hipGetLastError());
         GMK_TRY(hipStreamSynchronize(s));
         steps = 1;
@@ -1382,7 +1456,8 @@ extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int poolrave, int n_total, uin
             rc = gmk_trad_add_root_noise(t, noise_alpha, noise_epsilon, seed, first_game_id);
             if (rc != GMK_OK) break;
         }
-        rc = poolrave ? gmk_trad_run_poolrave(t, playouts, c_puct, seed, first_game_id, s) : gmk_trad_run(t, playouts, c_puct, s);
+        rc = policy == 1 ? gmk_trad_run_poolrave(t, playouts, c_puct, seed, first_game_id, s)
+           : policy == 2 ? gmk_trad_run_rave(t, playouts, c_puct, s) : gmk_trad_run(t, playouts, c_puct, s);
         if (rc != GMK_OK) break;
         if (reuse_subtree && t->d_amaf && !t->d_amaf2) GMK_TRY(gmk::device_malloc(&t->d_amaf2, ns * static_cast<size_t>(t->cap) * 8));
         GMK_TRY(hipMemsetAsync(sp.unfinished, 0, 4, s));

@@ -31,7 +31,7 @@ struct TradArena {
     uint32_t* link;                              // [n_games][cap] first child | children << 24
     uint2* front;                                // [n_games][cap] the child that is first in the CURRENT order: {id | cell << 24, its link word}
     uint8_t* ord;                                // [n_games][cap] the node's position in its parent's current child order
-    uint2* amaf;                                 // [n_games][cap] {amaf_visits, amaf_value bits} (AMAFNode, MonteCarlo.hpp:113-122); null for K6
+    uint2* amaf;                                 // [n_games][cap] {amaf_visits, amaf_value bits} (AMAFNode, MonteCarlo.hpp:113-122); null for K6 without RAVE
 };
 
 // What the device-resident self-play loop (gmk_trad_selfplay_run) hands its step kernel: the game a slot plays and the hand-over of a
@@ -96,7 +96,7 @@ struct gmk_trad {
     uint32_t* d_link = nullptr;
     uint2* d_front = nullptr;
     uint8_t* d_ord = nullptr;
-    uint2* d_amaf = nullptr;                                                // allocated by the first gmk_trad_run_poolrave
+    uint2* d_amaf = nullptr;                                                // allocated by the first gmk_trad_run_poolrave / gmk_trad_run_rave
     uint2 *d_stat2 = nullptr, *d_info2 = nullptr, *d_front2 = nullptr;      // second arena, allocated by the first gmk_trad_step
     uint32_t* d_link2 = nullptr;
     uint8_t* d_ord2 = nullptr;
@@ -109,7 +109,7 @@ struct gmk_trad {
     std::vector<uint32_t> game_ids;                                         // the game a slot is playing, relative to the callers' first_game_id (default: the slot number)
     uint32_t* d_game_ids = nullptr;
     uint32_t* d_path_spill = nullptr;            // [n_games][kPathSpill] K6: the child ranges of path levels the LDS copy has no room for
-    bool attr_set = false, attr_set_selfplay = false, positioned = false, second_arena = false;
+    bool attr_set = false, attr_set_selfplay = false, attr_set_rave = false, attr_set_selfplay_rave = false, positioned = false, second_arena = false;
     // gmk_trad_set_option
     int noise_sampler = 0;                       // GMK_NOISE_SAMPLER_STD: where Default::AddNoise draws from
     int lockstep = 0;
@@ -118,8 +118,10 @@ struct gmk_trad {
     uint2 *block_stat = nullptr, *block_info = nullptr, *block_front = nullptr;
     uint32_t* block_link = nullptr;
     uint8_t* block_ord = nullptr;
+    uint2* block_amaf = nullptr;                                            // TraditionalPolicy + RAVE handles: the sixth block (ensure_amaf, trad_kernel.hip)
     size_t arena_stride() const { return (paired && d_stat2 > d_stat) ? static_cast<size_t>(d_stat2 - d_stat) : 0; }
-    int policy = 0;                                                          // 0 not searched yet, 1 TraditionalPolicy (gmk_trad_run), 2 PoolRAVEPolicy (gmk_trad_run_poolrave): one per handle
+    int policy = 0;                                                          // 0 not searched yet, 1 TraditionalPolicy (gmk_trad_run), 2 PoolRAVEPolicy (gmk_trad_run_poolrave),
+                                                                             // 3 TraditionalPolicy + RAVE (gmk_trad_run_rave): one per handle
 
     gmk::tree::TradArena arena() const { return {d_stat, d_info, d_link, d_front, d_ord, d_amaf}; }
     gmk::tree::TradArena arena2() const { return {d_stat2, d_info2, d_link2, d_front2, d_ord2, d_amaf2}; }

@@ -42,7 +42,7 @@ EXPORTS = [
     "gmk_mcts_alg_bytes", "gmk_mcts_launch_info", "gmk_visits_to_pi", "gmk_mcts_advance", "gmk_mcts_step", "gmk_mcts_step_host", "gmk_mcts_add_root_noise", "gmk_mcts_set_option", "gmk_mcts_reserve", "gmk_selfplay_run", "gmk_samples_from_records",
     "gmk_evalstate_create", "gmk_evalstate_destroy", "gmk_evalstate_reset", "gmk_evalstate_update", "gmk_evalstate_update_host", "gmk_evalstate_read",
     "gmk_az_create", "gmk_az_destroy", "gmk_az_set_roots", "gmk_az_select", "gmk_az_expand", "gmk_az_select_host", "gmk_az_expand_host", "gmk_az_read_node_host", "gmk_az_read_children_host", "gmk_az_set_leaf_host", "gmk_az_rollout_host", "gmk_az_expand_stages_host", "gmk_az_write_stats_host", "gmk_az_step", "gmk_az_advance", "gmk_az_set_slots", "gmk_az_live_games", "gmk_az_set_game_ids", "gmk_az_add_root_noise", "gmk_az_set_option", "gmk_az_root_stats",
-    "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
+    "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_run_rave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
 ]
 
 
@@ -133,6 +133,7 @@ def load():
     L.gmk_trad_root_stats.argtypes = [vp] * 10
     L.gmk_trad_read_evaluators.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.gmk_trad_run_poolrave.argtypes = [vp, C.c_int, C.c_double, C.c_uint64, C.c_uint32, vp]
+    L.gmk_trad_run_rave.argtypes = [vp, C.c_int, C.c_double, vp]
     L.gmk_trad_selfplay_run.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_double, C.c_uint64, C.c_int, C.c_float, C.c_float,
                                         vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
     L.gmk_trad_root_amaf.argtypes = [vp, vp, vp]
@@ -535,6 +536,28 @@ class PoolRAVEMCTS(TraditionalMCTS):
 
     def add_root_noise(self, alpha=0.05, epsilon=0.25, seed=None, first_game_id=None):
         super().add_root_noise(alpha, epsilon, self.seed if seed is None else seed, self.first_game_id if first_game_id is None else first_game_id)
+
+    def root_stats(self):
+        out = super().root_stats()
+        out["amaf_visits"] = np.zeros((self.n, N), np.uint32)
+        out["amaf_values"] = np.zeros((self.n, N), np.float32)
+        _check(load().gmk_trad_root_amaf(self.h, out["amaf_visits"].ctypes.data, out["amaf_values"].ctypes.data))
+        return out
+
+
+class TraditionalRAVEMCTS(TraditionalMCTS):
+    """n_games searches of MCTS(policy=TraditionalPolicy(c_puct, use_rave=True)) side by side on the GPU (agents/mcts.py:44-47): K6's
+    playout with RAVE::BackPropogate<true> against the leaf position (gmk_trad_run_rave); root_stats() adds the root children's
+    AMAF statistics.  c_bias is accepted and unused, as in the reference (HandSelect, not MinMSE)."""
+
+    _POOLRAVE = 2                                        # gmk_trad_selfplay_run's policy
+
+    def __init__(self, n_games, node_capacity=1 << 20, c_puct=5.0, c_bias=0.0):
+        super().__init__(n_games, node_capacity, c_puct)
+        self.c_bias = float(c_bias)
+
+    def run(self, playouts, stream=0):
+        _check(load().gmk_trad_run_rave(self.h, int(playouts), self.c_puct, stream))
 
     def root_stats(self):
         out = super().root_stats()

@@ -286,6 +286,21 @@ class _HostGames:
         return last
 
 
+_POLICIES = ("traditional", "poolrave", "traditional_rave")
+
+
+def _supervisor_tree(policy, n, cap, c_puct, seed, first_game_id):
+    """The batched searcher of play_supervisor_games' policy: MCTS(TraditionalPolicy) (K6), MCTS(PoolRAVEPolicy) (K8) or
+    MCTS(TraditionalPolicy(use_rave=True)) (K6 with RAVE::BackPropogate<true>)."""
+    if policy == "poolrave":
+        return G.PoolRAVEMCTS(n, node_capacity=cap, c_puct=c_puct, seed=seed, first_game_id=first_game_id)
+    if policy == "traditional":
+        return G.TraditionalMCTS(n, node_capacity=cap, c_puct=c_puct)
+    if policy == "traditional_rave":
+        return G.TraditionalRAVEMCTS(n, node_capacity=cap, c_puct=c_puct)
+    raise ValueError("play_supervisor_games: policy must be one of %s" % (_POLICIES,))
+
+
 def _play_supervisor_on_device(n_games, n_slots, playouts, c_puct, seed, first_game_id, opening_plies, device, node_capacity, policy, reuse_subtree, root_noise, max_steps=0,
                                persistent=False, noise_sampler="std", prepare_only=False):
     """play_supervisor_games with the loop resident on the device (gmk_trad_selfplay_run): the searches, MCTS::stepForward's move, the
@@ -299,12 +314,7 @@ def _play_supervisor_on_device(n_games, n_slots, playouts, c_puct, seed, first_g
         m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
         open_moves, open_lens = m, np.minimum(l, opening_plies).astype(np.int32)
     cap = node_capacity if node_capacity is not None else min((3 if reuse_subtree else 1) * playouts * 226 + 1, (1 << 24) - 1)
-    if policy == "poolrave":
-        tree = G.PoolRAVEMCTS(n_slots, node_capacity=cap, c_puct=c_puct, seed=seed, first_game_id=first_game_id)
-    elif policy == "traditional":
-        tree = G.TraditionalMCTS(n_slots, node_capacity=cap, c_puct=c_puct)
-    else:
-        raise ValueError("play_supervisor_games: policy must be 'traditional' or 'poolrave'")
+    tree = _supervisor_tree(policy, n_slots, cap, c_puct, seed, first_game_id)
     tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS[noise_sampler])
     if prepare_only:                                             # the arenas this run would allocate go to the library's pool (see play_games)
         tree.reserve(two_arenas=bool(reuse_subtree and persistent))
@@ -333,7 +343,8 @@ def play_supervisor_games(n_games, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, fi
     (alpha, epsilon) mixes Default::AddNoise into the root priors before every search), then MCTS::stepForward's choice
     is played.  Without noise the search is deterministic; variety then comes from the openings (synthetic generator,
     `opening_plies` plies of game first_game_id + g).  policy="poolrave" plays the same loop with MCTS(PoolRAVEPolicy)
-    (agents/mcts.py:36-40) on both sides: K8 searches, random rollouts seeded by (seed, first_game_id + g).
+    (agents/mcts.py:36-40) on both sides: K8 searches, random rollouts seeded by (seed, first_game_id + g).  policy="traditional_rave"
+    plays it with MCTS(TraditionalPolicy(use_rave=True)) (agents/mcts.py:44-47): K6 searches with RAVE::BackPropogate<true>, on every loop.
     slots: at most that many games are in flight; a game that ends hands its slot -- tree arena, evaluator,
     wavefront -- to the next unstarted game, so the GPU stays full instead of waiting for the longest game of the batch (a search
     costs the same time however many of its games are still alive: one wavefront per game, latency bound).
@@ -344,8 +355,8 @@ def play_supervisor_games(n_games, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, fi
     persistent loop, so that the reference agent's semantics (reuse_subtree + root_noise) run at the pace of the plain loop; "std" = std::gamma_distribution
     over std::mt19937 on the host (lock step).  PoolRAVE games draw "std" whatever is asked (their loop is lock step anyway).
     Returns the same GameRecords as play_games (moves, per-move root visit counts, winner), so to_samples() / gather_records() apply."""
-    if policy not in ("traditional", "poolrave"):
-        raise ValueError("play_supervisor_games: policy must be 'traditional' or 'poolrave'")
+    if policy not in _POLICIES:
+        raise ValueError("play_supervisor_games: policy must be one of %s" % (_POLICIES,))
     if device_loop and max_moves >= N:
         n_slots = n_games if slots is None else max(1, min(int(slots), n_games))
         # "persistent": one launch, every slot plays game after game at its own pace (TraditionalPolicy, whole games; kept subtrees are compacted
@@ -355,9 +366,9 @@ def play_supervisor_games(n_games, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, fi
         if policy == "poolrave":
             noise_sampler = "std"
         noisy = root_noise is not None and reuse_subtree
-        can_persist = policy == "traditional" and not max_steps and not (noisy and noise_sampler != "counter")
+        can_persist = policy in ("traditional", "traditional_rave") and not max_steps and not (noisy and noise_sampler != "counter")
         if device_loop == "persistent" and not can_persist:
-            raise ValueError("play_supervisor_games: the persistent loop plays TraditionalPolicy games to their end, with root noise from the counter-based sampler only")
+            raise ValueError("play_supervisor_games: the persistent loop plays TraditionalPolicy (+ RAVE) games to their end, with root noise from the counter-based sampler only")
         persistent = can_persist and (device_loop == "persistent" or (device_loop is True and (n_slots < n_games or reuse_subtree)))
         return _play_supervisor_on_device(n_games, n_slots, playouts, c_puct, seed, first_game_id,
                                           opening_plies, device, node_capacity, policy, reuse_subtree, root_noise, max_steps, persistent, noise_sampler, prepare_only)
@@ -377,12 +388,7 @@ def play_supervisor_games(n_games, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, fi
         games.open_with(m, l, opening_plies)
     visits = np.zeros((n_games, N, N), dtype=np.uint16)
     cap = node_capacity if node_capacity is not None else min((3 if reuse_subtree else 1) * playouts * 226 + 1, (1 << 24) - 1)
-    if policy == "poolrave":
-        tree = G.PoolRAVEMCTS(n_games, node_capacity=cap, c_puct=c_puct, seed=seed, first_game_id=first_game_id)
-    elif policy == "traditional":
-        tree = G.TraditionalMCTS(n_games, node_capacity=cap, c_puct=c_puct)
-    else:
-        raise ValueError("play_supervisor_games: policy must be 'traditional' or 'poolrave'")
+    tree = _supervisor_tree(policy, n_games, cap, c_puct, seed, first_game_id)
     tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS["std" if policy == "poolrave" else noise_sampler])
     overflow = False
     for ply in range(max_moves):
@@ -418,12 +424,7 @@ def _play_supervisor_slots(n_games, slots, playouts, c_puct, seed, first_game_id
         games.open_with(m, l, opening_plies)
     visits = np.zeros((n_games, N, N), dtype=np.uint16)
     cap = node_capacity if node_capacity is not None else min((3 if reuse_subtree else 1) * playouts * 226 + 1, (1 << 24) - 1)
-    if policy == "poolrave":
-        tree = G.PoolRAVEMCTS(slots, node_capacity=cap, c_puct=c_puct, seed=seed, first_game_id=first_game_id)
-    elif policy == "traditional":
-        tree = G.TraditionalMCTS(slots, node_capacity=cap, c_puct=c_puct)
-    else:
-        raise ValueError("play_supervisor_games: policy must be 'traditional' or 'poolrave'")
+    tree = _supervisor_tree(policy, slots, cap, c_puct, seed, first_game_id)
     tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS["std" if policy == "poolrave" else noise_sampler])
     active = np.arange(slots)                                    # the game in each slot
     next_game = slots
@@ -607,7 +608,9 @@ class _Searcher:
         self.kind, self.n, self.playouts = kind, n, int(kw.get("c_iterations", playouts))
         c_puct = float(kw.get("c_puct", 5.0))
         self.first_game_id = first_game_id
-        if kind == "traditional_mcts":                       # AGENT_MAP names of the reference (agents/__init__.py, config.py:9-19)
+        if kind == "traditional_mcts" and kw.get("use_rave"):  # TraditionalAgent(c_puct, c_bias, use_rave=True) (agents/mcts.py:44-47)
+            self.tree = G.TraditionalRAVEMCTS(n, node_capacity=min(self.playouts * 226 + 256, (1 << 24) - 1), c_puct=c_puct, c_bias=float(kw.get("c_bias", 0.0)))
+        elif kind == "traditional_mcts":                     # AGENT_MAP names of the reference (agents/__init__.py, config.py:9-19)
             self.tree = G.TraditionalMCTS(n, node_capacity=min(self.playouts * 226 + 256, (1 << 24) - 1), c_puct=c_puct)
         elif kind == "rave_mcts":
             self.tree = G.PoolRAVEMCTS(n, node_capacity=min(self.playouts * 226 + 256, (1 << 24) - 1), c_puct=c_puct, seed=seed, first_game_id=first_game_id)
@@ -644,7 +647,7 @@ def play_match_games(n_games, supervisor, candidate, playouts=400, seed=G.DEFAUL
     """The reference's data generation pairing (network/data_helper.py:15-22, 56-63; config.py:6-20): every game is played by
     the SUPERVISOR against a CANDIDATE, sides drawn at random per game, and both players' searches are recorded.  supervisor /
     candidate = (name, kwargs) as in DATA_CONFIG["schedule"]: ("traditional_mcts" | "rave_mcts" | "random_mcts", {"c_puct": ..,
-    "c_iterations": .., "c_rollouts": ..}).  All games run side by side on the current GPU: the games in which the supervisor
+    "c_iterations": .., "c_rollouts": ..}); "traditional_mcts" with {"use_rave": True, "c_bias": ..} searches with TraditionalRAVEMCTS.  All games run side by side on the current GPU: the games in which the supervisor
     has black and the games in which it has white form two groups, each with one batched searcher per agent (K6 / K8 / K3), so
     that every ply is two searches (one per group) covering all unfinished games; roots are fresh at every move and every
     game's random streams are keyed by its own global id first_game_id + g, whatever group and slot it runs in.  slots: games in flight per group (default: all of them); a

@@ -265,19 +265,29 @@ int gmk_trad_root_stats(gmk_trad* t, uint32_t* h_visits, float* h_values, float*
 int gmk_trad_step(gmk_trad* t, const int16_t* h_moves);
 /* Default::AddNoise on every root with children (the reference does this at the start of every search, MCTS.cpp:182) */
 int gmk_trad_add_root_noise(gmk_trad* t, float alpha, float epsilon, uint64_t seed, uint32_t first_game_id);
+/* TraditionalPolicy(c_puct, use_rave = true) (agents/mcts.py:44-47): gmk_trad_run's playout with RAVE::BackPropogate<true> in place of
+ * <false> (MonteCarlo.hpp:113-184).  At every level of the backup each child whose cell the LEAF position holds for the child's player
+ * (the root position plus the path; there is no rollout) takes -value into its all-moves-as-first statistics, and the children are ranked
+ * by PUCB + the HandSelect-weighted value, (1 - w) Q + w Q_amaf with w = sqrt(800 / (3 n + 800)).  c_bias only reaches RAVE::MinMSE,
+ * which the reference leaves unused: no argument.  The first call allocates the handle's AMAF statistics; gmk_trad_root_amaf reads the
+ * root children's, and set_positions, step, add_root_noise and root_stats work as for gmk_trad_run.  A handle searches with ONE policy:
+ * mixing this call with gmk_trad_run or gmk_trad_run_poolrave on it returns GMK_ERR_STATE, whichever came first. */
+int gmk_trad_run_rave(gmk_trad* t, int playouts, double c_puct, void* stream);
 /* GMK_OPT_NOISE_SAMPLER / GMK_OPT_LOCKSTEP for a K6 / K8 handle (see gmk_mcts_set_option) */
 int gmk_trad_set_option(gmk_trad* t, int option, int value);
-/* gmk_mcts_reserve for a K6 / K8 handle (two_arenas = 0: nothing to do, gmk_trad_create allocates the one arena) */
+/* gmk_mcts_reserve for a K6 / K8 handle (two_arenas = 0: nothing to do, gmk_trad_create allocates the one arena).  The AMAF statistics
+ * of a TraditionalPolicy + RAVE handle are left to the run itself (gmk_trad_run_rave, gmk_trad_selfplay_run with policy 2). */
 int gmk_trad_reserve(gmk_trad* t, int two_arenas);
 /* The self-play loop of the pattern-guided searchers, resident on the device (replaces the host loop of network/data_helper.py:56-83
  * around agents/mcts.py:17-21 for config.py:9-12's supervisor): n_total games (global ids first_game_id ..) are played through the
  * handle's n_games SLOTS with continuous batching -- every move = Default::AddNoise (noise_alpha > 0; MCTS.cpp:182) + one search of
- * `playouts` playouts (poolrave = 0: TraditionalPolicy as gmk_trad_run, 1: PoolRAVEPolicy as gmk_trad_run_poolrave) + a step kernel
+ * `playouts` playouts (policy = 0: TraditionalPolicy as gmk_trad_run, 1: PoolRAVEPolicy as gmk_trad_run_poolrave, 2: TraditionalPolicy
+ * with RAVE as gmk_trad_run_rave) + a step kernel
  * that plays MCTS::stepForward()'s choice, checks the end of the game (Game.cpp:88-136) and hands a finished game's slot to the next
  * unstarted game (reuse_subtree = 1 keeps the chosen child's subtree as gmk_trad_step does, 0 starts every search from a new root as
  * gmk_trad_set_positions does).  Records by GAME, on the device: d_moves uint8[n_total][225], d_lens int32[n_total], d_winner
  * int8[n_total], d_visits uint16[n_total][225][225] (may be NULL).  h_open_moves / h_open_lens: the games' openings, or NULL.
- * persistent = 1 (TraditionalPolicy, whole games): ONE launch in which every slot's wavefront plays game after game at its own pace -- a
+ * persistent = 1 (TraditionalPolicy with or without RAVE, whole games): ONE launch in which every slot's wavefront plays game after game at its own pace -- a
  * search no longer waits for the slowest one of the batch -- taking the next unstarted game from a counter when its game ends; a game then
  * starts on a fresh evaluator (Evaluator::reset), so its record does not depend on the slot it landed in and equals the one the
  * all-games-at-once loop plays.  With reuse_subtree the chosen child's subtree is compacted into the slot's second arena inside the launch
@@ -288,7 +298,7 @@ int gmk_trad_reserve(gmk_trad* t, int two_arenas);
  * max_steps > 0 ends the loop after that many moves per slot (games still running keep the moves they have, winner 0): what a
  * throughput measurement with every slot busy needs; 0 = play every game to its end.
  * *h_overflow != 0: some search stopped at its node capacity.  Afterwards the handle must be positioned again before other use. */
-int gmk_trad_selfplay_run(gmk_trad* t, int poolrave, int n_total, uint32_t first_game_id, int playouts, double c_puct, uint64_t seed,
+int gmk_trad_selfplay_run(gmk_trad* t, int policy, int n_total, uint32_t first_game_id, int playouts, double c_puct, uint64_t seed,
                           int reuse_subtree, float noise_alpha, float noise_epsilon,
                           const uint8_t* h_open_moves, int open_stride, const int32_t* h_open_lens,
                           uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int persistent, int max_steps, int32_t* h_overflow, int32_t* h_steps, void* stream);
@@ -304,9 +314,10 @@ int gmk_trad_read_evaluators(gmk_trad* t, int32_t* h_scores, int32_t* h_density,
  * not used); this call runs `playouts` MCTS::playout iterations per game with PoolRAVE's stages.  Rollout draws: Philox4x32-10,
  * key = seed, counter = (first_game_id + game, playout since the root last changed, stones on the root board << 8, ply >> 3),
  * as K3 with rollout number 0.  c_bias only reaches RAVE::MinMSE, which the reference leaves unused (:130-139): no argument.
- * A handle searches with ONE policy: mixing gmk_trad_run and gmk_trad_run_poolrave on it returns GMK_ERR_STATE. */
+ * A handle searches with ONE policy: mixing gmk_trad_run, gmk_trad_run_rave and gmk_trad_run_poolrave on it returns GMK_ERR_STATE. */
 int gmk_trad_run_poolrave(gmk_trad* t, int playouts, double c_puct, uint64_t seed, uint32_t first_game_id, void* stream);
-/* the root children's all-moves-as-first statistics by cell (AMAFNode::amaf_visits / amaf_value), host [n][225] each */
+/* the root children's all-moves-as-first statistics by cell (AMAFNode::amaf_visits / amaf_value), host [n][225] each (K8 and
+ * gmk_trad_run_rave handles) */
 int gmk_trad_root_amaf(gmk_trad* t, uint32_t* h_amaf_visits, float* h_amaf_values);
 
 /* ---- K7: network-guided tree search, many games in lock step (BASELINE.json configs[4]) ----

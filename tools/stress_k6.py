@@ -2,7 +2,10 @@
 lengths, 100 .. 700 playouts, several c_puct, 1 .. 40 games per search (workgroups partly filled), a second search on the same handle from a
 continued position (the evaluator is synchronised, not rebuilt).  Compared exactly: visit counts, the bits of values and priors, the move to
 play, tree size, the number of evaluator updates, and the evaluator state left behind (scores, density, pattern and compound flag words).
-tools/stress_k6.py [seconds]; run(budget, seed) is what tests/test_stress_gpu.py calls for a bounded slice"""
+tools/stress_k6.py [seconds]; run(budget, seed) is what tests/test_stress_gpu.py calls for a bounded slice.
+tools/stress_k6.py --rave [seconds]: TraditionalPolicy(use_rave=True) (gmk_trad_run_rave) against the Python restatement of
+tests/trad_rave_reference.py (30 .. 150 playouts, the restatement on a pool of worker processes that do not touch the GPU), the AMAF
+statistics compared too (the evaluator state is not: the restatement's evaluator is the oracle's, which K6's plain leg checks)."""
 import ctypes as C
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -73,7 +76,73 @@ def run(budget=240.0, seed=4101, verbose=True):
     return searches, games, bad
 
 
+def _rave_reference(job):
+    """both searches of one game on one restatement object (its evaluator persists like the device's): root statistics of each"""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from trad_rave_reference import TradRAVEReference
+    c_puct, P, first, second = job
+    ref, out = TradRAVEReference(c_puct, use_rave=True), []
+    for pos, playouts in ((first, P), (second, P // 2)):
+        ref.search(pos, playouts)
+        out.append((ref.root_children(), ref.root_visits, ref.root_value, ref.n_nodes, ref.evaluator_updates))
+    return out
+
+
+def same_rave(st, g, got):
+    (v, q, p, av, aq, best), rv, rq, n_nodes, updates = got
+    return bool(st["status"][g] == 0 and (st["visits"][g] == v).all() and (st["values"][g].view(np.uint32) == q.view(np.uint32)).all() and
+                (st["priors"][g].view(np.uint32) == p.view(np.uint32)).all() and (st["amaf_visits"][g] == av).all() and
+                (st["amaf_values"][g].view(np.uint32) == aq.view(np.uint32)).all() and st["best"][g] == best and st["root_visits"][g] == rv and
+                np.float32(st["root_value"][g]).view(np.uint32) == np.float32(rq).view(np.uint32) and st["n_nodes"][g] == n_nodes and
+                st["evaluator_updates"][g] == updates)
+
+
+def run_rave(budget=240.0, seed=4201, verbose=True, workers=12):
+    """run() for TraditionalRAVEMCTS against tests/trad_rave_reference.py; returns (searches, game searches compared, mismatches)"""
+    import multiprocessing as mp
+    rng = np.random.RandomState(seed)
+    G.init(0)
+    pool = mp.get_context("spawn").Pool(workers)
+    t0 = time.time(); searches = games = 0; bad = []
+    try:
+        while time.time() - t0 < budget:
+            n = int(rng.randint(1, 41)); P = int(rng.randint(30, 151)); c_puct = float(rng.choice([2.0, 5.0])); kind = int(rng.randint(0, 2))
+            moves, lens, _ = G.synth_boards(n, kind, first_board=int(rng.randint(0, 2**24)))
+            cut = [int(min(lens[g], rng.randint(0, 61))) for g in range(n)]
+            pos = [[int(m) for m in moves[g, :cut[g]]] for g in range(n)]
+            more = [pos[g] + [int(m) for m in moves[g, cut[g]:min(int(lens[g]), cut[g] + 2)]] for g in range(n)]
+            refs = pool.map_async(_rave_reference, [(c_puct, P, pos[g], more[g]) for g in range(n)])
+            t = G.TraditionalRAVEMCTS(n, node_capacity=1 << 16, c_puct=c_puct)
+            t.set_positions(pos)
+            t.run(P)
+            stats = [t.root_stats()]
+            t.set_positions(more)
+            t.run(P // 2)
+            stats.append(t.root_stats())
+            t.close()
+            refs = refs.get()
+            for g in range(n):
+                for k in (0, 1):
+                    if not same_rave(stats[k], g, refs[g][k]):
+                        bad.append("search %d: n %d P %d c_puct %g kind %d game %d stones %d" % (searches + k, n, P, c_puct, kind, g, len((pos, more)[k][g])))
+                        if verbose:
+                            print("MISMATCH " + bad[-1], flush=True)
+                    games += 1
+            searches += 2
+            if verbose and searches % 20 == 0:
+                print("%d searches, %d game searches compared, %d mismatches, %.0f s" % (searches, games, len(bad), time.time() - t0), flush=True)
+    finally:
+        pool.close()
+        pool.join()
+    return searches, games, bad
+
+
 if __name__ == "__main__":
+    if "--rave" in sys.argv:
+        args = [a for a in sys.argv[1:] if a != "--rave"]
+        searches, games, bad = run_rave(float(args[0]) if args else 240.0)
+        print("K6 + RAVE stress parity: %d searches, %d game searches compared with the restatement (visits, value, prior and AMAF bits, AMAF visits, best move, tree size, evaluator updates): %d mismatches" % (searches, games, len(bad)))
+        sys.exit(1 if bad else 0)
     searches, games, bad = run(float(sys.argv[1]) if len(sys.argv) > 1 else 240.0)
     print("K6 stress parity: %d searches, %d game searches compared with the oracle (visits, value and prior bits, best move, tree size, evaluator updates, evaluator state with its flag words): %d mismatches" % (searches, games, len(bad)))
     sys.exit(1 if bad else 0)
