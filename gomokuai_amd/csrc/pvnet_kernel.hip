@@ -402,7 +402,7 @@ void pvnet_trunk_kernel(PvParams prm) {
 // activations are staged in LDS, every layer is Out[position][output] = sum_k Act[position][k] W^T[k][output] on v_mfma_f32_16x16x4_f32 (A =
 // activations, one conflict-free ds_read_b32 per step: row stride 900 and 452 floats = 4 banks; B = weights, packed on the host in lane order
 // per (wave, step of 4 k, output tile) and streamed from L2).  Wave w owns the policy's output tiles w, w + 4, w + 8, w + 12 (225 outputs = 15 tiles of
-// 16; the 16th is zero weights) and tile w of the 64 hidden units; the hidden layer's 450 k ride along the first 120 steps of the policy's 228.
+// 16; the 16th is zero weights) and tile w of the 64 hidden units; the hidden layer's 450 k ride along the first 113 steps of the policy's 225.
 // Steps come in bodies of twelve with all addresses `register + immediate` (vector instructions between f32 MFMAs cost 20-30 clocks each, a
 // load ~20 whatever its width: see conv_tiles()), a lane's B operands of four steps are one 16-byte buffer load, and a body fetches the NEXT
 // body's weights before its own MFMAs start (two register sets).  Then bias, the logits and hidden
@@ -410,9 +410,15 @@ void pvnet_trunk_kernel(PvParams prm) {
 constexpr int kDensePos = 16;                      // positions per workgroup
 constexpr int kDenseBody = 12;                     // steps (of 4 k) per body = three groups of four (one 16-byte weight load per lane and group)
 constexpr int kPolicySteps = 225;                  // -> 228 = 19 bodies; the hidden layer's 113 steps -> 120 ride along bodies 0 .. 9
+constexpr int kHiddenSteps = 113;
 constexpr int kDenseBodies = 19, kHiddenBodies = 10;
 constexpr int kVfStride = 452;
-constexpr int oDensePf = 0, oDenseVf = kDensePos * 900, kDenseLdsFloats = oDenseVf + kDensePos * kVfStride + 32;
+// Each row's MFMAs read its own activations only: policy steps < 225 read k < 900 of the row's policy activations, hidden steps < 113 read
+// k < 452 of its value activations (450 .. 451: the row's zero pad).  The steps the bodies run past them (225 .. 227, 113 .. 119) have zero
+// weights but would read the NEXT row's first floats (row 15's: value row 0's), where 0 x Inf of an overflowed neighbour is NaN: they issue
+// no MFMA.
+constexpr int oDensePf = 0, oDenseVf = kDensePos * 900, kDenseLdsFloats = oDenseVf + kDensePos * kVfStride;
+static_assert(4 * kPolicySteps == 900 && 4 * kHiddenSteps >= 450 && 4 * kHiddenSteps <= kVfStride, "the steps cover exactly one row");
 // after the MFMAs the logits [16][256] take the place of the policy activations, the hidden units [16][64] that of the value activations
 
 struct DenseParams {
@@ -454,10 +460,7 @@ void pvnet_dense_kernel(DenseParams prm) {
                 *reinterpret_cast<float2*>(lds + oDenseVf + r * kVfStride + 2 * c) = v2[j];
             }
         }
-        if (threadIdx.x < kDensePos + 16) {                                             // the two pad columns of every row and the 32 floats behind the last
-            if (threadIdx.x < kDensePos) *reinterpret_cast<float2*>(lds + oDenseVf + threadIdx.x * kVfStride + 450) = make_float2(0.0f, 0.0f);
-            else *reinterpret_cast<float2*>(lds + oDenseVf + kDensePos * kVfStride + 2 * (threadIdx.x - kDensePos)) = make_float2(0.0f, 0.0f);
-        }
+        if (threadIdx.x < kDensePos) *reinterpret_cast<float2*>(lds + oDenseVf + threadIdx.x * kVfStride + 450) = make_float2(0.0f, 0.0f);   // the two pad columns of every row
     }
     __syncthreads();
     f32x4 acc[4] = {}, acch = {};
@@ -483,10 +486,14 @@ void pvnet_dense_kernel(DenseParams prm) {
         const char* av = a_vf + body * kDenseBody * 16;
 #pragma unroll
         for (int s = 0; s < kDenseBody; ++s) {
-            const float a = *reinterpret_cast<const float*>(ap + s * 16);
+            const int step = body * kDenseBody + s;                               // a constant: the bodies are unrolled
+            if (step < kPolicySteps) {
+                const float a = *reinterpret_cast<const float*>(ap + s * 16);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, w4[s / 4][q][s % 4], acc[q], 0, 0, 0);
-            if (decltype(with_hidden)::value) acch = __builtin_amdgcn_mfma_f32_16x16x4f32(*reinterpret_cast<const float*>(av + s * 16), w1[s / 4][s % 4], acch, 0, 0, 0);
+                for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, w4[s / 4][q][s % 4], acc[q], 0, 0, 0);
+            }
+            if (decltype(with_hidden)::value && step < kHiddenSteps)
+                acch = __builtin_amdgcn_mfma_f32_16x16x4f32(*reinterpret_cast<const float*>(av + s * 16), w1[s / 4][s % 4], acch, 0, 0, 0);
         }
     };
     constexpr std::integral_constant<bool, true> yes{};

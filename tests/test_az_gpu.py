@@ -2,7 +2,7 @@
 (Policy(eval_state=f), agents/alphazero.py:5-9; Default::Select / Expand(extraCheck) / BackPropogate).  The evaluator of the
 parity test is a pure function of the feature planes that both sides compute on the host with the same numpy code, so
 the search itself is compared exactly (visit counts, value and prior bits, tree size); the real network is run end to end
-in a second test and checked against a float64 numpy forward pass with a tolerance."""
+in a second test and checked against a float64 forward pass (tests/pvnet_reference.py) with a tolerance."""
 import ctypes as C
 
 import numpy as np
@@ -107,27 +107,11 @@ def test_policy_value_network_end_to_end():
     assert (st["visits"].sum(1) == playouts - 1).all()
     assert ((st["priors"] > 0).sum(1) == 225 - lens).all()     # softmax never returns 0: one child per empty cell
     assert float(probs.sum(1).sub(1).abs().max()) < 1e-5 and float(value.abs().max()) <= 1.0
-    # float64 numpy forward pass of the same weights (model_tf.py:28-66) on a few rows
-    w = {k: v.detach().cpu().double().numpy() for k, v in net.state_dict().items()}
-    x = states[:4].cpu().double().numpy()
-
-    def conv(x, wt, b):                                         # 'same' convolution, NCHW
-        k = wt.shape[2]
-        xp = np.pad(x, ((0, 0), (0, 0), (k // 2, k // 2), (k // 2, k // 2)))
-        out = np.zeros((x.shape[0], wt.shape[0], 15, 15))
-        for dy in range(k):
-            for dx in range(k):
-                out += np.einsum("bchw,oc->bohw", xp[:, :, dy:dy + 15, dx:dx + 15], wt[:, :, dy, dx])
-        return out + b[None, :, None, None]
-    for i in range(3):
-        x = np.maximum(conv(x, w["conv.%d.weight" % i], w["conv.%d.bias" % i]), 0)
-    p = np.maximum(conv(x, w["policy_conv.weight"], w["policy_conv.bias"]), 0).transpose(0, 2, 3, 1).reshape(4, -1)
-    logits = p @ w["policy_dense.weight"].T + w["policy_dense.bias"]
-    ref_probs = np.exp(logits - logits.max(1, keepdims=True)); ref_probs /= ref_probs.sum(1, keepdims=True)
-    v = np.maximum(conv(x, w["value_conv.weight"], w["value_conv.bias"]), 0).transpose(0, 2, 3, 1).reshape(4, -1)
-    ref_value = np.tanh(np.maximum(v @ w["value_hidden.weight"].T + w["value_hidden.bias"], 0) @ w["value_out.weight"].T + w["value_out.bias"]).reshape(-1)
-    assert np.abs(probs[:4].cpu().numpy() - ref_probs).max() < 1e-4      # float32 convolutions vs float64: tolerance
-    assert np.abs(value[:4].cpu().numpy() - ref_value).max() < 1e-4
+    # float64 forward pass of the same weights (model_tf.py:28-66, tests/pvnet_reference.py) on a few rows
+    import pvnet_reference
+    ref = pvnet_reference.forward(pvnet_reference.weights(net), states[:4])
+    assert np.abs(probs[:4].cpu().numpy() - ref["probs"]).max() < 1e-4      # float32 convolutions vs float64: tolerance
+    assert np.abs(value[:4].cpu().numpy() - ref["value"]).max() < 1e-4
     tree.close()
 
 

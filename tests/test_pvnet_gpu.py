@@ -1,6 +1,8 @@
 """K9: the policy-value network in HIP -- the fused convolution trunk (gmk_pvnet_forward) and, behind it, the dense layers with softmax / tanh
 (gmk_pvnet_evaluate), both on the f32 matrix cores -- against the plain PyTorch float32 module of the same architecture (gomokuai_amd/network.py, network/model_tf.py:28-66).  Both compute in float32; the sums run in
-different orders, so the bar is a tolerance: 2e-5 absolute on activations of order 1 and on the final value / probabilities."""
+different orders, so the bar is a tolerance: 2e-5 absolute on activations of order 1 and on the final value / probabilities.  That says the two
+agree, not which is right: tests/test_pvnet_precision_gpu.py holds the kernels to a float64 forward pass under an element-wise rounding bound
+(tests/pvnet_reference.py) on scaled, saturating and dead-channel inputs and weights, and checks that rows of a batch do not affect each other."""
 import numpy as np
 import pytest
 import torch
