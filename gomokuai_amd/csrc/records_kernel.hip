@@ -9,6 +9,7 @@
 // Here one workgroup produces one sample (x8 when augmenting) straight from the record:
 //   K4  the six feature planes are rebuilt by replaying the first t moves of the record,
 //   K5  pi = softmax(log(v / |v|_2 + [v != 0] + eps) / tau) in double, tau = 1 below 15 stones else 0.01.
+// The same body serves the fixed-stride records (gmk_samples_from_records) and their wire form (gmk_samples_from_packed).
 #include "capi_common.h"
 
 namespace {
@@ -26,10 +27,45 @@ __device__ __forceinline__ int augment_source(int j, int k, bool flip) {
     return r * 15 + c;
 }
 
-__global__ __launch_bounds__(256)
-void samples_from_records_kernel(const uint8_t* __restrict__ moves, const int32_t* __restrict__ lens, const uint16_t* __restrict__ visits,
-                                 const int8_t* __restrict__ winner, const int32_t* __restrict__ sample_game, const int32_t* __restrict__ sample_move,
-                                 int n_samples, int augment, uint8_t* __restrict__ out_states, float* __restrict__ out_values, float* __restrict__ out_pi) {
+// Where a game's moves, visit rows and winner live.  The body below is written once over this accessor; the two instantiations are
+// the fixed-stride arrays gmk_mcts_advance writes and the wire form of selfplay.pack_records (records_wire.hip).
+struct StrideRecords {
+    const uint8_t* moves;
+    const uint16_t* visits;
+    const int8_t* winner;
+    struct Row {
+        const uint16_t* p;
+        __device__ __forceinline__ uint16_t operator[](int c) const { return p[c]; }
+    };
+    __device__ __forceinline__ const uint8_t* moves_of(int g) const { return moves + static_cast<size_t>(g) * 225; }
+    __device__ __forceinline__ Row visit_row(int g, int t) const { return Row{visits + (static_cast<size_t>(g) * 225 + static_cast<size_t>(t)) * 225}; }
+    __device__ __forceinline__ int8_t winner_of(int g) const { return winner[g]; }
+};
+
+// The wire form: lens int32[n] | winner int8[n] | moves uint8[T] | visits uint16[T][225], T = offsets[n].  Move t of game g is byte
+// 5n + offsets[g] + t; its visit row starts at byte 5n + T + 450 (offsets[g] + t), which is odd whenever 5n + T is: a count is read as
+// its two bytes, never as an unaligned 16-bit load.
+struct PackedRecords {
+    const uint8_t* buf;
+    const int64_t* offsets;
+    int n;
+    struct Row {
+        const uint8_t* p;
+        __device__ __forceinline__ uint16_t operator[](int c) const {
+            return static_cast<uint16_t>(p[2 * c] | (p[2 * c + 1] << 8));
+        }
+    };
+    __device__ __forceinline__ const uint8_t* moves_of(int g) const { return buf + 5 * static_cast<size_t>(n) + offsets[g]; }
+    __device__ __forceinline__ Row visit_row(int g, int t) const {
+        return Row{buf + 5 * static_cast<size_t>(n) + static_cast<size_t>(offsets[n]) + 450 * static_cast<size_t>(offsets[g] + t)};
+    }
+    __device__ __forceinline__ int8_t winner_of(int g) const { return static_cast<int8_t>(buf[4 * static_cast<size_t>(n) + g]); }
+};
+
+template <class Records>
+__device__ __forceinline__ void samples_body(const Records& rec, const int32_t* __restrict__ sample_game, const int32_t* __restrict__ sample_move,
+                                             int n_samples, int augment, uint8_t* __restrict__ out_states, float* __restrict__ out_values,
+                                             float* __restrict__ out_pi) {
     __shared__ int8_t s_cell[kCells];
     __shared__ float s_pi[kCells];
     __shared__ float s_red[256];
@@ -37,7 +73,7 @@ void samples_from_records_kernel(const uint8_t* __restrict__ moves, const int32_
     const int s = blockIdx.x;
     if (s >= n_samples) return;
     const int g = sample_game[s], t = sample_move[s], tid = threadIdx.x;
-    const uint8_t* mv = moves + static_cast<size_t>(g) * 225;
+    const uint8_t* mv = rec.moves_of(g);
 
     // ---- K4: position before move t (black moves first), player to move, last two moves ----
     if (tid < kCells) s_cell[tid] = 0;
@@ -47,7 +83,7 @@ void samples_from_records_kernel(const uint8_t* __restrict__ moves, const int32_
     const int cur = (t & 1) ? -1 : 1;
 
     // ---- K5: pi from the visit counts of move t ----
-    const uint16_t* vrow = visits + (static_cast<size_t>(g) * 225 + static_cast<size_t>(t)) * 225;
+    const auto vrow = rec.visit_row(g, t);
     float v = tid < kCells ? static_cast<float>(vrow[tid]) : 0.0f;
     s_red[tid] = v * v;
     __syncthreads();
@@ -82,8 +118,22 @@ void samples_from_records_kernel(const uint8_t* __restrict__ moves, const int32_
             st[5 * kCells + tid] = cur == 1;                                          // all ones iff black is to move
             out_pi[o * kCells + tid] = s_pi[src];
         }
-        if (tid == 0) out_values[o] = static_cast<float>(cur) * static_cast<float>(winner[g]);   // CalcScore (Game.h:34-36)
+        if (tid == 0) out_values[o] = static_cast<float>(cur) * static_cast<float>(rec.winner_of(g));   // CalcScore (Game.h:34-36)
     }
+}
+
+__global__ __launch_bounds__(256)
+void samples_from_records_kernel(const uint8_t* __restrict__ moves, const int32_t* __restrict__ lens, const uint16_t* __restrict__ visits,
+                                 const int8_t* __restrict__ winner, const int32_t* __restrict__ sample_game, const int32_t* __restrict__ sample_move,
+                                 int n_samples, int augment, uint8_t* __restrict__ out_states, float* __restrict__ out_values, float* __restrict__ out_pi) {
+    samples_body(StrideRecords{moves, visits, winner}, sample_game, sample_move, n_samples, augment, out_states, out_values, out_pi);
+}
+
+__global__ __launch_bounds__(256)
+void samples_from_packed_kernel(const uint8_t* __restrict__ buf, int n, const int64_t* __restrict__ offsets, const int32_t* __restrict__ sample_game,
+                                const int32_t* __restrict__ sample_move, int n_samples, int augment, uint8_t* __restrict__ out_states,
+                                float* __restrict__ out_values, float* __restrict__ out_pi) {
+    samples_body(PackedRecords{buf, offsets, n}, sample_game, sample_move, n_samples, augment, out_states, out_values, out_pi);
 }
 
 }  // namespace
@@ -100,6 +150,26 @@ extern "C" int gmk_samples_from_records(const uint8_t* d_moves, const int32_t* d
     if (n_samples == 0) return GMK_OK;
     hipLaunchKernelGGL(samples_from_records_kernel, dim3(n_samples), dim3(256), 0, static_cast<hipStream_t>(stream),
                        d_moves, d_lens, d_visits, d_winner, d_sample_game, d_sample_move, n_samples, augment, d_states, d_values, d_pi);
+    GMK_HIP_CHECK(hipGetLastError());
+    return GMK_OK;
+}
+
+extern "C" int gmk_samples_from_packed(const uint8_t* d_buf, int n, const int64_t* d_offsets, const int32_t* d_sample_game,
+                                       const int32_t* d_sample_move, int n_samples, int augment, uint8_t* d_states, float* d_values, float* d_pi,
+                                       void* stream) {
+    gmk::DeviceState& st = gmk::device_state();
+    if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    if (n < 0 || n_samples < 0 || (n_samples > 0 && (n == 0 || !d_buf || !d_offsets || !d_sample_game || !d_sample_move || !d_states || !d_values || !d_pi))) {
+        gmk::set_error("gmk_samples_from_packed: bad arguments");
+        return GMK_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(d_offsets) % 8) {
+        gmk::set_error("gmk_samples_from_packed: d_offsets must be 8-byte aligned");
+        return GMK_ERR_ARG;
+    }
+    if (n == 0 || n_samples == 0) return GMK_OK;
+    hipLaunchKernelGGL(samples_from_packed_kernel, dim3(n_samples), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       d_buf, n, d_offsets, d_sample_game, d_sample_move, n_samples, augment, d_states, d_values, d_pi);
     GMK_HIP_CHECK(hipGetLastError());
     return GMK_OK;
 }

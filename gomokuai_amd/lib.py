@@ -40,6 +40,7 @@ EXPORTS = [
     "gmk_eval_batch", "gmk_eval_batch_host", "gmk_eval_launch_info",
     "gmk_mcts_create", "gmk_mcts_destroy", "gmk_mcts_set_roots", "gmk_mcts_set_game_ids", "gmk_mcts_run", "gmk_mcts_root_stats",
     "gmk_mcts_alg_bytes", "gmk_mcts_launch_info", "gmk_visits_to_pi", "gmk_mcts_advance", "gmk_mcts_step", "gmk_mcts_step_host", "gmk_mcts_add_root_noise", "gmk_mcts_set_option", "gmk_mcts_reserve", "gmk_selfplay_run", "gmk_samples_from_records",
+    "gmk_records_scan", "gmk_records_packed_bytes", "gmk_records_pack", "gmk_records_unpack", "gmk_samples_from_packed",
     "gmk_evalstate_create", "gmk_evalstate_destroy", "gmk_evalstate_reset", "gmk_evalstate_update", "gmk_evalstate_update_host", "gmk_evalstate_read",
     "gmk_az_create", "gmk_az_destroy", "gmk_az_set_roots", "gmk_az_select", "gmk_az_expand", "gmk_az_select_host", "gmk_az_expand_host", "gmk_az_read_node_host", "gmk_az_read_children_host", "gmk_az_set_leaf_host", "gmk_az_rollout_host", "gmk_az_expand_stages_host", "gmk_az_write_stats_host", "gmk_az_step", "gmk_az_advance", "gmk_az_set_slots", "gmk_az_live_games", "gmk_az_set_game_ids", "gmk_az_add_root_noise", "gmk_az_set_option", "gmk_az_root_stats",
     "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_run_rave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
@@ -143,6 +144,11 @@ def load():
     L.gmk_pvnet_set_dense.argtypes = [vp] * 6 + [C.c_float]
     L.gmk_pvnet_evaluate.argtypes = [vp, vp, C.c_int, vp, vp, vp]
     L.gmk_samples_from_records.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.gmk_records_scan.argtypes = [vp, C.c_int, vp, vp]
+    L.gmk_records_packed_bytes.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_uint64), vp]
+    L.gmk_records_pack.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, C.c_uint64, vp, vp]
+    L.gmk_records_unpack.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.gmk_samples_from_packed.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -370,6 +376,39 @@ def samples_from_records(d_moves, d_lens, d_visits, d_winner, d_sample_game, d_s
     """Device-pointer form of gmk_samples_from_records (K4 + K5)."""
     _check(load().gmk_samples_from_records(d_moves, d_lens, d_visits, d_winner, d_sample_game, d_sample_move, n_samples,
                                            int(augment), d_states, d_values, d_pi, stream))
+
+
+# ---------------- game records on the wire (device pointers; include/gomoku_hip.h) ----------------
+WIRE_BAD_LENGTH, WIRE_BAD_SIZE = 1, 2       # the *d_status codes of records_pack / records_unpack
+
+
+def records_scan(d_lens, n, d_offsets, stream=None):
+    """gmk_records_scan: d_offsets int64[n+1] = exclusive prefix sum of d_lens (offsets[n] = -1 if a length is outside [0, 225])."""
+    _check(load().gmk_records_scan(d_lens, int(n), d_offsets, stream))
+
+
+def records_packed_bytes(d_offsets, n, has_visits, stream=None):
+    """gmk_records_packed_bytes: the wire size 5n + T (1 + 450 has_visits); synchronises `stream`; raises on a length outside [0, 225]."""
+    b = C.c_uint64()
+    _check(load().gmk_records_packed_bytes(d_offsets, int(n), int(bool(has_visits)), C.byref(b), stream))
+    return b.value
+
+
+def records_pack(d_moves, d_lens, d_winner, d_visits, n, d_offsets, d_out, out_bytes, d_status, stream=None):
+    """gmk_records_pack (d_visits None = no visit section); *d_status != 0: nothing was written."""
+    _check(load().gmk_records_pack(d_moves, d_lens, d_winner, d_visits, int(n), d_offsets, d_out, int(out_bytes), d_status, stream))
+
+
+def records_unpack(d_buf, n_bytes, n, has_visits, d_offsets, d_moves, d_lens, d_winner, d_visits, d_status, stream=None):
+    """gmk_records_unpack: whole fixed-stride rows (zeros past each length); *d_status != 0: the records were not touched."""
+    _check(load().gmk_records_unpack(d_buf, int(n_bytes), int(n), int(bool(has_visits)), d_offsets, d_moves, d_lens, d_winner, d_visits,
+                                     d_status, stream))
+
+
+def samples_from_packed(d_buf, n, d_offsets, d_sample_game, d_sample_move, n_samples, augment, d_states, d_values, d_pi, stream=None):
+    """Device-pointer form of gmk_samples_from_packed (K4 + K5 on the wire form)."""
+    _check(load().gmk_samples_from_packed(d_buf, int(n), d_offsets, d_sample_game, d_sample_move, int(n_samples), int(augment),
+                                          d_states, d_values, d_pi, stream))
 
 
 # ---------------- K2: incrementally maintained evaluator states ----------------

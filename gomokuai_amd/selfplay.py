@@ -37,9 +37,7 @@ class GameRecords:
         that were not searched."""
         assert self.visits is not None and self.moves.is_cuda
         dev = self.moves.device
-        lens = self.lens.cpu().numpy()
-        game = np.concatenate([np.full(max(int(l) - first_move, 0), g, dtype=np.int32) for g, l in enumerate(lens)] or [np.zeros(0, np.int32)])
-        move = np.concatenate([np.arange(first_move, int(l), dtype=np.int32) for l in lens] or [np.zeros(0, np.int32)])
+        game, move = _sample_lists(self.lens.cpu().numpy(), first_move)
         n = int(game.shape[0])
         copies = 8 if augment else 1
         d_game, d_move = torch.from_numpy(game).to(dev), torch.from_numpy(move).to(dev)
@@ -75,6 +73,13 @@ class GameRecords:
             out.append((states.reshape(6, 15, 15), np.array(float(cur * winner)), pi))
             cell[int(rec.moves[game, t])] = cur
         return out
+
+
+def _sample_lists(lens, first_move):
+    """(game, move) int32 lists of every sample, ordered by (game, move): moves first_move .. len - 1 of each game."""
+    game = np.concatenate([np.full(max(int(l) - first_move, 0), g, dtype=np.int32) for g, l in enumerate(lens)] or [np.zeros(0, np.int32)])
+    move = np.concatenate([np.arange(first_move, int(l), dtype=np.int32) for l in lens] or [np.zeros(0, np.int32)])
+    return game, move
 
 
 # Games in flight per MI355X for whole-game RandomPolicy self-play, and the number of search handles they are split over.  The loop is ONE
@@ -784,6 +789,83 @@ def unpack_records(buf, n, has_visits, first_game_id=0, overflow=False):
     visits = torch.zeros((n, N, N), dtype=torch.int16, device=dev) if has_visits else None
     unpack_records_into(buf, n, has_visits, moves, lens, winner, visits, 0)
     return GameRecords(moves, lens, winner, visits, first_game_id, overflow)
+
+
+# The same three steps through the C-ABI (gmk_records_*, records_wire.hip): what a binder without torch calls.
+def _stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def pack_records_device(rec):
+    """pack_records on the device: the same uint8 tensor, from a prefix sum of the lengths and one pack kernel.  It synchronises once, for
+    the size.  Raises GmkError if a length is outside [0, 225] (pack_records does not check)."""
+    lens = rec.lens.to(torch.int32).contiguous()
+    n = int(lens.shape[0])
+    dev = lens.device
+    if n == 0:
+        return torch.zeros(0, dtype=torch.uint8, device=dev)
+    moves = rec.moves.contiguous().view(torch.uint8)
+    winner = rec.winner.to(torch.int8).contiguous()
+    visits = None if rec.visits is None else rec.visits.contiguous()
+    assert moves.shape == (n, N) and winner.shape == (n,) and (visits is None or (visits.shape == (n, N, N) and visits.element_size() == 2))
+    stream = _stream(dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    G.records_scan(lens.data_ptr(), n, offsets.data_ptr(), stream)
+    size = G.records_packed_bytes(offsets.data_ptr(), n, visits is not None, stream)
+    out = torch.empty(size, dtype=torch.uint8, device=dev)
+    # status can only be set on a bad length or a short buffer, and records_packed_bytes has ruled out both: it is not read back
+    G.records_pack(moves.data_ptr(), lens.data_ptr(), winner.data_ptr(), None if visits is None else visits.data_ptr(), n, offsets.data_ptr(),
+                   out.data_ptr(), size, status.data_ptr(), stream)
+    return out
+
+
+def unpack_records_device(buf, n, has_visits, first_game_id=0, overflow=False):
+    """unpack_records on the device: the same GameRecords.  The kernel writes every byte of the fixed-stride rows (zeros past a game's
+    length), so they are allocated uncleared.  Raises ValueError if a length in buf is outside [0, 225] or buf's size is not the wire size
+    of its lengths."""
+    dev = buf.device
+    buf = buf.contiguous()
+    moves = torch.empty((n, N), dtype=torch.uint8, device=dev)
+    lens = torch.empty((n,), dtype=torch.int32, device=dev)
+    winner = torch.empty((n,), dtype=torch.int8, device=dev)
+    visits = torch.empty((n, N, N), dtype=torch.int16, device=dev) if has_visits else None
+    if n > 0:
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        G.records_unpack(buf.data_ptr(), buf.numel(), n, has_visits, offsets.data_ptr(), moves.data_ptr(), lens.data_ptr(), winner.data_ptr(),
+                         None if visits is None else visits.data_ptr(), status.data_ptr(), _stream(dev))
+        code = int(status.item())
+        if code:
+            raise ValueError("unpack_records_device: %s" % ("a game length is outside [0, 225]" if code == G.WIRE_BAD_LENGTH else
+                                                            "%d bytes are not the wire size of these %d games" % (buf.numel(), n)))
+    return GameRecords(moves, lens, winner, visits, first_game_id, overflow)
+
+
+def samples_from_packed(buf, n, augment=False, first_move=0):
+    """The training tuples of the n games of a wire-form block with visits, read from the block itself (K4 + K5, no fixed-stride copy):
+    the same (states, values, pi) as unpack_records(buf, n, True).to_samples(augment, first_move)."""
+    dev = buf.device
+    buf = buf.contiguous()
+    copies = 8 if augment else 1
+    if n == 0:
+        return (torch.empty((0, 6, 15, 15), dtype=torch.uint8, device=dev), torch.empty(0, dtype=torch.float32, device=dev),
+                torch.empty((0, N), dtype=torch.float32, device=dev))
+    stream = _stream(dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    G.records_scan(buf.data_ptr(), n, offsets.data_ptr(), stream)
+    size = G.records_packed_bytes(offsets.data_ptr(), n, True, stream)
+    if size != buf.numel():
+        raise ValueError("samples_from_packed: %d bytes are not the wire size (%d) of these %d games with visits" % (buf.numel(), size, n))
+    game, move = _sample_lists(buf[:4 * n].view(torch.int32).cpu().numpy(), first_move)
+    s = int(game.shape[0])
+    d_game, d_move = torch.from_numpy(game).to(dev), torch.from_numpy(move).to(dev)
+    states = torch.empty((s * copies, 6, 15, 15), dtype=torch.uint8, device=dev)
+    values = torch.empty(s * copies, dtype=torch.float32, device=dev)
+    pi = torch.empty((s * copies, N), dtype=torch.float32, device=dev)
+    G.samples_from_packed(buf.data_ptr(), n, offsets.data_ptr(), d_game.data_ptr(), d_move.data_ptr(), s, augment, states.data_ptr(),
+                          values.data_ptr(), pi.data_ptr(), stream)
+    return states, values, pi
 
 
 class GatherError(RuntimeError):

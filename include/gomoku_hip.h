@@ -234,6 +234,35 @@ int gmk_samples_from_records(const uint8_t *d_moves, const int32_t *d_lens, cons
                              const int32_t *d_sample_game, const int32_t *d_sample_move, int n_samples, int augment,
                              uint8_t *d_states, float *d_values, float *d_pi, void *stream);
 
+/* ---- game records on the wire (the exchange step: selfplay.pack_records / unpack_records, on the device) ----
+ * Wire form of n games, one byte block:  lens int32[n] | winner int8[n] | moves uint8[T] | visits uint16[T][225] (optional),
+ * T = sum(lens): only the played plies, in game order; the visit section starts at byte 5n + T and is odd-addressed when that is odd.
+ * The fixed-stride records are those of gmk_samples_from_records (moves uint8[n][225], visits uint16[n][225][225]).
+ * Every launch goes on `stream`; only gmk_records_packed_bytes synchronises (it).  n = 0 is a no-op that returns GMK_OK.
+ * gmk_records_scan: d_offsets int64[n+1] = exclusive prefix sum of d_lens, d_offsets[n] = T.  A length outside [0, 225] is not clamped:
+ *   d_offsets[n] becomes -1 (and so do the offsets after it).
+ * gmk_records_packed_bytes: *h_bytes = 5n + T (1 + 450 has_visits) from d_offsets[n]; GMK_ERR_ARG if a length was outside [0, 225].
+ * gmk_records_pack: the bytes of selfplay.pack_records into d_out[0, size) (d_visits NULL = no visit section); d_offsets from
+ *   gmk_records_scan of d_lens.  The size is checked on the device: *d_status = GMK_WIRE_BAD_LENGTH or GMK_WIRE_BAD_SIZE (out_bytes
+ *   below the wire size), and then nothing is written to d_out; 0 when packed.  Bytes of d_out past the wire size are not touched.
+ * gmk_records_unpack: the inverse, d_buf[0, n_bytes) -> the fixed-stride rows of n games.  It writes EVERY byte of those rows -- the
+ *   played plies from the block, zeros after a game's length -- so the destination needs no clearing first (selfplay.unpack_records_into
+ *   does need it).  d_offsets int64[n+1] is filled as scratch (the scan of the block's lens).  *d_status = GMK_WIRE_BAD_LENGTH or
+ *   GMK_WIRE_BAD_SIZE (n_bytes is not the wire size of those lens), and then the records are untouched; 0 when unpacked.
+ * gmk_samples_from_packed: K4 + K5 on the wire form (with visits): the same outputs as gmk_samples_from_records on the unpacked
+ *   records, for the same sample lists; d_offsets from gmk_records_scan of the block's lens.
+ * Alignment: d_lens, d_out, d_buf and d_status 4 bytes, d_offsets 8 bytes, d_visits 2 bytes (GMK_ERR_ARG otherwise). */
+enum { GMK_WIRE_BAD_LENGTH = 1, GMK_WIRE_BAD_SIZE = 2 };
+int gmk_records_scan(const int32_t *d_lens, int n, int64_t *d_offsets, void *stream);
+int gmk_records_packed_bytes(const int64_t *d_offsets, int n, int has_visits, uint64_t *h_bytes, void *stream);
+int gmk_records_pack(const uint8_t *d_moves, const int32_t *d_lens, const int8_t *d_winner, const uint16_t *d_visits, int n,
+                     const int64_t *d_offsets, uint8_t *d_out, uint64_t out_bytes, int32_t *d_status, void *stream);
+int gmk_records_unpack(const uint8_t *d_buf, uint64_t n_bytes, int n, int has_visits, int64_t *d_offsets, uint8_t *d_moves,
+                       int32_t *d_lens, int8_t *d_winner, uint16_t *d_visits, int32_t *d_status, void *stream);
+int gmk_samples_from_packed(const uint8_t *d_buf, int n, const int64_t *d_offsets, const int32_t *d_sample_game,
+                            const int32_t *d_sample_move, int n_samples, int augment, uint8_t *d_states, float *d_values,
+                            float *d_pi, void *stream);
+
 /* ---- K6: pattern-guided tree search, the reference's self-play supervisor ("traditional_mcts", config.py:9-12) ----
  * Replaces MCTS(policy = TraditionalPolicy(c_puct)) : core/lib/include/policies/Traditional.h:17-69 on top of
  * Heuristic (core/lib/include/algorithms/Heuristic.hpp:16-45, 94-200), RAVE::Select / BackPropogate<false>
