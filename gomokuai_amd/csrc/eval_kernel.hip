@@ -36,7 +36,11 @@
 //   * phase D, once per group, in the board iteration that is the wavefront's turn within its workgroup: the density planes of the
 //     sixteen boards on the matrix cores -- Out[board, colour][cell] = Stone[board, colour][cell'] * W[cell'][cell], the stones as
 //     the A operand and the constant banded weight matrix (rows of a 6 KB table in LDS) as the B operand of
-//     v_mfma_i32_32x32x32_i8 (14 passes of 3-5 MFMAs, small integers: exact), stored as 2 x 128 contiguous bytes per instruction.
+//     v_mfma_i32_32x32x32_i8 (14 passes of 3-5 MFMAs, small integers: exact), stored as 2 x 128 contiguous bytes per instruction.  A group whose
+//     sixteen boards all exist (every group but the last of a launch whose board count is not a multiple of sixteen) stores without guards, one
+//     straight-line block per pass: per pair of stores three vector instructions (the occupied bit, two XORs) and two scalar ones (the board's
+//     block added to a 64-bit scalar base: global_store_dword offset, value, s[base]); the occupied bits come from 7 x 16 words the burst puts
+//     in LDS once (two 16-byte reads per pass).  The per-lane constants of the prologue are one 16-byte read of a table the host uploads once.
 // HBM traffic per board: 64 B in, 7 248 B out (7 312 B algorithmic); everything else stays on chip.
 #include <algorithm>
 #include <cstdlib>
@@ -79,6 +83,10 @@ constexpr int kStaticTableWords = 128 + kLineWords + 512 + 1560 + 4;   // lane j
 // segment (len + 3: one leading and two trailing pads), 5..6 dir, 7..11 cell stride, 12..19 its first cell, 20..26 line word index.
 __constant__ uint32_t c_lane_jobs[64 * 2];
 __constant__ uint32_t c_line_init[kLineWords];   // all cells blank: (1 << 2 len) - 1
+// What else the kernel's prologue would derive from the lane number alone (upload_lane_jobs): [0] row * 4 and [1] column of the lane's cell in each of
+// the four passes over the board (cell = 64 pass + lane, the last one clamped to 224), a byte per pass; [2], [3] where the first cell of the lane's
+// two lines sits in its line word (bit 2 x0 for a diagonal, 2 y0 for an anti-diagonal, 0 for rows and columns)
+__constant__ uint4 c_lane_consts[64];
 constexpr int kScanSteps = 19;                    // symbols in the longest lane stream (upload_lane_jobs checks it)
 
 __device__ __forceinline__ int dir_stride(int dir) { return (0x0E100F01u >> (8 * dir)) & 0xFFu; }      // 1, 15, 16, 14: a shift, not three branches
@@ -116,6 +124,13 @@ __device__ __forceinline__ uint32_t mul24(uint32_t a, uint32_t b) {
     uint32_t r;
     asm("v_mul_u32_u24 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b));
     return r;
+}
+
+// global_store_dword with the address as a wave-uniform 64-bit base in scalar registers plus the lane's unsigned 32-bit byte offset, written out: from
+// C++ the compiler adds the two as a 64-bit vector value first (two vector instructions per store where the base changes from store to store).
+// A plain store, not a non-temporal one.
+__device__ __forceinline__ void store_saddr(uint32_t byte_offset, int32_t value, unsigned long long base) {
+    asm volatile("global_store_dword %0, %1, %2" : : "v"(byte_offset), "v"(value), "s"(base) : "memory");
 }
 
 __device__ __forceinline__ void wave_phase_fence() {
@@ -213,22 +228,20 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 // different cache lines: measured 2.4 TB/s for the density planes alone).  Spreading the fourteen passes over the group's board
 // iterations spreads the 3.6 KB per board over the kernel's run time instead of one burst at its start.
 // The stones are read again (64 B per board from L2) and become operand bytes through a 256-entry table in LDS (byte -> 8 bytes).
-template <int KIND, int M>
-__device__ __forceinline__ void density_tile_pass(const uint32_t (&own_rows)[8], const uint32_t (&other_rows)[8], int n_boards, int first_board, int lane,
-                                                  const v4i* __restrict__ s_wtab, int32_t* __restrict__ out_density,
-                                                  const uint2* __restrict__ s_lut, int plane_stride) {
+// Which cells are occupied (they hold ~v) comes from s_occ, the burst's [M tile][16 boards] words in LDS (density_planes_out): the eight
+// boards of this lane's half are eight consecutive words, two 16-byte reads per pass in front of its MFMAs.
+// kFull: all sixteen boards of the group exist (decided once per burst, on the scalar unit).  The eight store pairs are then one straight-line
+// block, and what differs between them -- the board's block, b * 3 600 bytes -- is added to the group's base on the scalar unit: a store is
+// global_store_dword <lane's 32-bit offset>, <value>, <64-bit scalar base>, no vector address arithmetic between the pairs of a pass.
+// Only the last group of a launch whose board count is not a multiple of sixteen takes the guarded form (columns without a board are not stored).
+template <bool kFull, int KIND, int M>
+__device__ __forceinline__ void density_tile_pass(const uint32_t (&own_rows)[8], int n_live, int lane,
+                                                  const v4i* __restrict__ s_wtab, const uint4* __restrict__ s_occ, int32_t* __restrict__ group_out,
+                                                  unsigned long long& board_base /* kFull: group_out, in scalar registers */, const uint2* __restrict__ s_lut, int plane_stride) {
     constexpr int lo = dens_kt_lo(M), hi = dens_kt_hi(M), nk = hi - lo + 1;
-    constexpr int y0 = (32 * M) / 15, y1 = (32 * M + 31) / 15;
     const int n = lane & 31, h = lane >> 5;
-    // occupied cells 32 M .. 32 M + 31 of this lane's board (rows y0 .. y1 of both planes)
-    uint32_t occ = 0;
-#pragma unroll
-    for (int y = y0; y <= y1; ++y) {
-        const uint32_t both = own_rows[y / 2] | other_rows[y / 2];
-        const uint32_t r = ((y & 1) ? both >> 16 : both) & 0x7FFFu;
-        const int at = 15 * y - 32 * M;
-        occ |= at >= 0 ? r << at : r >> -at;
-    }
+    const uint4 occ_lo = s_occ[4 * M + 2 * h], occ_hi = s_occ[4 * M + 2 * h + 1];
+    const uint32_t occ[8] = {occ_lo.x, occ_lo.y, occ_lo.z, occ_lo.w, occ_hi.x, occ_hi.y, occ_hi.z, occ_hi.w};
     const int cell = 32 * M + n, yo = (cell * 0x8889) >> 19, xo = cell - 15 * yo;
     const v4i* w = s_wtab + KIND * (kWtabKindWords / kWtabEntryWords) + (2 * lo + h - yo + 6) * 15 + xo;
     v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -240,16 +253,31 @@ __device__ __forceinline__ void density_tile_pass(const uint32_t (&own_rows)[8],
         acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(stones, w[30 * k], acc, 0, 0, 0);
     }
     // accumulator i = board-colour column 8 (i / 4) + 4 h + (i % 4) at cell 32 M + n; columns 2 b, 2 b + 1 are board b
-    const int n_live = n_boards - first_board;      // >= 16 except in the last group
-    int32_t* out = out_density + static_cast<size_t>(first_board) * 4 * plane_stride + KIND * plane_stride + 32 * M + n + h * (2 * 4 * plane_stride);
+    const uint32_t at = static_cast<uint32_t>(KIND * plane_stride + 32 * M + n + h * (2 * 4 * plane_stride));      // this lane's word in the block of board b
+    if (kFull) {
+        // the lane's two byte offsets within a board's block (white, black) once per pass, the board's block on the scalar unit
+        const uint32_t at_white = 4u * at, at_black = 4u * (at + 2u * static_cast<uint32_t>(plane_stride));
 #pragma unroll
-    for (int i = 0; i < 16; i += 2) {
-        const int b = 4 * (i / 4) + (i % 4) / 2;    // + 2 h
-        const uint32_t wd = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(8 * b + 16 * h, static_cast<int>(occ)));
-        const int neg = __builtin_amdgcn_sbfe(static_cast<int>(wd), n, 1);      // occupied cells hold -v - 1 = ~v (Pattern.cpp:253-265)
-        if (b + 2 * h < n_live && plane_stride > 0) {
-            out[b * 4 * plane_stride + 1 * 2 * plane_stride] = acc[i] ^ neg;                 // column 2 b: black, the second colour block
-            out[b * 4 * plane_stride + 0 * 2 * plane_stride] = acc[i + 1] ^ neg;             // column 2 b + 1: white, the first
+        for (int i = 0; i < 16; i += 2) {
+            const int neg = __builtin_amdgcn_sbfe(static_cast<int>(occ[i / 2]), n, 1);      // occupied cells hold -v - 1 = ~v (Pattern.cpp:253-265)
+            store_saddr(at_black, acc[i] ^ neg, board_base);                                // column 2 b: black, the second colour block
+            store_saddr(at_white, acc[i + 1] ^ neg, board_base);                            // column 2 b + 1: white, the first
+            // boards 0, 1, 4, 5, 8, 9, 12, 13 (+ 2 h), then back to the group's first for the next pass: ONE scalar register pair, advanced in place
+            // (left to itself the compiler keeps all eight boards' bases in sixteen scalar registers across the burst, and the board loop spills for it)
+            board_base += static_cast<long long>(i == 14 ? -13 : i % 4 ? 3 : 1) * (4 * 4 * plane_stride);
+            asm volatile("" : "+s"(board_base));
+        }
+    } else {
+        int32_t* out = group_out + at;
+#pragma unroll
+        for (int i = 0; i < 16; i += 2) {
+            const int b = 4 * (i / 4) + (i % 4) / 2;    // + 2 h
+            const int neg = __builtin_amdgcn_sbfe(static_cast<int>(occ[i / 2]), n, 1);
+            asm volatile("" : "+s"(n_live));            // (the guard is worked out pair by pair: eight lane masks kept across the burst are sixteen scalar registers)
+            if (b + 2 * h < n_live && plane_stride > 0) {
+                out[b * 4 * plane_stride + 1 * 2 * plane_stride] = acc[i] ^ neg;
+                out[b * 4 * plane_stride + 0 * 2 * plane_stride] = acc[i + 1] ^ neg;
+            }
         }
     }
 }
@@ -260,20 +288,43 @@ __device__ __forceinline__ void density_tile_pass(const uint32_t (&own_rows)[8],
 // credits: TCC_EA0_WRREQ 9.7 M per launch instead of 3.9 M for the scores alone, a fifth of them 32-byte pieces.)
 // The sixteen wavefronts of a workgroup take turns (the caller runs this in board iteration `wavefront number`), so that at any time
 // one wavefront per CU is storing planes while fifteen evaluate boards.
+// s_occ: 7 x 16 words of this wavefront's LDS that nothing else uses at this point (the caller passes its transition queue).
+template <bool kFull>
 __device__ __forceinline__ void density_planes_out(const uint16_t* __restrict__ planes, int n_boards, int first_board, int lane,
-                                                   const v4i* __restrict__ s_wtab, int32_t* __restrict__ out_density,
+                                                   const v4i* __restrict__ s_wtab, uint32_t* __restrict__ s_occ, int32_t* __restrict__ out_density,
                                                    const uint2* __restrict__ s_lut, int plane_stride) {
     const int n = lane & 31, plane = n & 1, board = first_board + (n >> 1);
     uint32_t own[8], other[8];
     {
         // (columns without a board read the group's first board: what they compute is never stored)
-        const uint4* p = reinterpret_cast<const uint4*>(planes + static_cast<size_t>(board < n_boards ? board : first_board) * 32);
+        const uint4* p = reinterpret_cast<const uint4*>(planes + static_cast<size_t>(kFull || board < n_boards ? board : first_board) * 32);
         const uint4 a0 = p[plane * 2], a1 = p[plane * 2 + 1], b0 = p[2 - plane * 2], b1 = p[3 - plane * 2];
         own[0] = a0.x; own[1] = a0.y; own[2] = a0.z; own[3] = a0.w; own[4] = a1.x; own[5] = a1.y; own[6] = a1.z; own[7] = a1.w;
         other[0] = b0.x; other[1] = b0.y; other[2] = b0.z; other[3] = b0.w; other[4] = b1.x; other[5] = b1.y; other[6] = b1.z; other[7] = b1.w;
     }
+    // The occupied cells 32 M .. 32 M + 31 of every board, once per burst: one lane per board puts the word of each M tile where the
+    // lanes of the half that stores the board read it.  Half h stores boards 4 j + 2 h and 4 j + 2 h + 1 in its pairs 2 j and 2 j + 1: board B
+    // is word 8 (B / 2 & 1) + 2 (B / 4) + (B & 1) of a tile's sixteen.  (LDS instructions of a wavefront run in issue order: no wait between this
+    // and the passes' reads.  Before: a ds_bpermute and a wait in front of each of the 112 store pairs.)
+    if ((lane & 33) == 0) {
+        const int bg = lane >> 1;
+        uint32_t* slot = s_occ + 8 * ((bg >> 1) & 1) + 2 * (bg >> 2) + (bg & 1);
+#pragma unroll
+        for (int m = 0; m < kDensTiles; ++m) {
+            const int y0 = (32 * m) / 15, y1 = (32 * m + 31) / 15;
+            uint32_t occ = 0;
+#pragma unroll
+            for (int y = y0; y <= y1; ++y) {
+                const uint32_t both = own[y / 2] | other[y / 2];
+                const uint32_t r = ((y & 1) ? both >> 16 : both) & 0x7FFFu;
+                const int at = 15 * y - 32 * m;
+                occ |= at >= 0 ? r << at : r >> -at;
+            }
+            slot[16 * m] = occ;
+        }
+    }
     // cell 224 = (14, 14), which no tile covers: the taps dy, dx in -3 .. 0 that lie on the board, by hand (one lane per column)
-    if ((lane >> 5) == 0 && board < n_boards && plane_stride > 0) {
+    if ((lane >> 5) == 0 && (kFull || (board < n_boards && plane_stride > 0))) {
         uint32_t c224 = 0, w224 = 0;
 #pragma unroll
         for (int dy = -3; dy <= 0; ++dy) {
@@ -292,7 +343,15 @@ __device__ __forceinline__ void density_planes_out(const uint16_t* __restrict__ 
         out[224] = static_cast<int32_t>(c224 ^ neg);
         out[plane_stride + 224] = static_cast<int32_t>(w224 ^ neg);
     }
-#define GMK_PASS(K, M) density_tile_pass<K, M>(own, other, n_boards, first_board, lane, s_wtab, out_density, s_lut, plane_stride); __builtin_amdgcn_sched_barrier(0);
+    const int n_live = __builtin_amdgcn_readfirstlane(n_boards - first_board);      // >= 16 except in the last group
+    int32_t* group_out = out_density + static_cast<size_t>(first_board) * 4 * plane_stride;        // wave-uniform
+    const uint4* occ_words = reinterpret_cast<const uint4*>(s_occ);
+    // (readfirstlane: the 64-bit product in the address may have been worked out on the vector unit)
+    const unsigned long long group_bits = reinterpret_cast<unsigned long long>(group_out);
+    unsigned long long board_base = static_cast<unsigned long long>(static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(group_bits >> 32)))) << 32
+                                    | static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(group_bits)));
+    asm volatile("" : "+s"(board_base));
+#define GMK_PASS(K, M) density_tile_pass<kFull, K, M>(own, n_live, lane, s_wtab, occ_words, group_out, board_base, s_lut, plane_stride); __builtin_amdgcn_sched_barrier(0);
     GMK_PASS(0, 0) GMK_PASS(1, 0) GMK_PASS(0, 1) GMK_PASS(1, 1) GMK_PASS(0, 2) GMK_PASS(1, 2) GMK_PASS(0, 3) GMK_PASS(1, 3)
     GMK_PASS(0, 4) GMK_PASS(1, 4) GMK_PASS(0, 5) GMK_PASS(1, 5) GMK_PASS(0, 6) GMK_PASS(1, 6)
 #undef GMK_PASS
@@ -360,20 +419,10 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
     // (from constant memory, not from their staged copies: those are not there yet)
     const uint32_t job_a = c_lane_jobs[lane * 2], job_b = c_lane_jobs[lane * 2 + 1];
     const uint32_t line_init_lo = c_line_init[lane], line_init_hi = c_line_init[min(64 + lane, kLineWords - 1)];
-    // where a line's first cell sits in its word: bit 2 x0 for a diagonal, 2 y0 for an anti-diagonal (first cell = job bits 12..19), 0 for rows and columns
-    auto first_bit = [](uint32_t job) -> uint32_t {
-        const uint32_t dir = (job >> 5) & 3u, first = (job >> 12) & 255u, y0 = (first * 0x8889u) >> 19, x0 = first - 15u * y0;
-        return dir == 2u ? 2u * x0 : dir == 3u ? 2u * y0 : 0u;
-    };
-    const uint32_t norm_a = first_bit(job_a), norm_b = first_bit(job_b);
+    // (one 16-byte read instead of ~100 vector instructions of multiply-shift divisions in every wavefront of every launch)
+    const uint4 lane_consts = c_lane_consts[lane];
+    const uint32_t cell_row4 = lane_consts.x, cell_col = lane_consts.y, norm_a = lane_consts.z, norm_b = lane_consts.w;
     uint32_t* s_rows = s_misc + 16;                      // row y at [3 + y]
-    // the cells this lane owns in the four passes over the board (cell = 64 pass + lane): 4 x row and column, a byte per pass
-    uint32_t cell_row4 = 0, cell_col = 0;
-    for (int pass = 0; pass < 4; ++pass) {
-        const int c = min(64 * pass + lane, kCells - 1), y = (c * 0x8889) >> 19;
-        cell_row4 |= static_cast<uint32_t>(4 * y) << (8 * pass);
-        cell_col |= static_cast<uint32_t>(c - 15 * y) << (8 * pass);
-    }
     // a board's 64 B are fetched while the board before it is evaluated.  No branch around the loads (every lane reads some valid
     // row, the result is masked where it is used), and the two halves stay apart until they are used: any arithmetic on a loaded
     // value makes the compiler wait for it on the spot, and the wait covers every store issued before.
@@ -769,7 +818,10 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                 if (burst >= wg_groups) break;
                 int lane_p = lane0, first_p = (wg_g0 + burst) * kGroupBoards;      // opaque copies: what the passes derive from them is computed here
                 asm volatile("" : "+v"(lane_p), "+s"(first_p));
-                density_planes_out(planes, n_boards, first_p, lane_p, s_wtab, out_density, s_lut, (phase_mask & 512) ? 0 : (phase_mask & 256) ? 256 : kCells);
+                const int plane_stride = (phase_mask & 512) ? 0 : (phase_mask & 256) ? 256 : kCells;
+                // (the queue is free here: phase 4 has read it, the next board's phase 0 fills it again)
+                if (first_p + kGroupBoards <= n_boards && plane_stride > 0) density_planes_out<true>(planes, n_boards, first_p, lane_p, s_wtab, s_queue, out_density, s_lut, plane_stride);
+                else density_planes_out<false>(planes, n_boards, first_p, lane_p, s_wtab, s_queue, out_density, s_lut, plane_stride);
                 GMK_STAMP(8);
                 if (live) break;
             }
@@ -855,6 +907,22 @@ int upload_lane_jobs() {
     for (int i = 0; i < 15; ++i) init[i] = init[kColBase + i] = 0x3FFFFFFFu;
     // (a diagonal's cells sit at bits 2 x, an anti-diagonal's at bits 2 y: the line starts at x = max(0, x - y) resp. y = max(0, x + y - 14))
     for (int d = 0; d <= 28; ++d) init[kDiagBase + d] = init[kAntiBase + d] = ((1u << (2 * (15 - std::abs(d - 14)))) - 1u) << (2 * std::max(0, d - 14));
+    uint32_t consts[64][4];
+    for (int lane = 0; lane < 64; ++lane) {
+        uint32_t row4 = 0, col = 0;
+        for (int pass = 0; pass < 4; ++pass) {
+            const int c = std::min(64 * pass + lane, kCells - 1);
+            row4 |= static_cast<uint32_t>(4 * (c / 15)) << (8 * pass);
+            col |= static_cast<uint32_t>(c % 15) << (8 * pass);
+        }
+        consts[lane][0] = row4;
+        consts[lane][1] = col;
+        for (int k = 0; k < 2; ++k) {
+            const uint32_t job = jobs[lane * 2 + k], dir = (job >> 5) & 3u, first = (job >> 12) & 255u;
+            consts[lane][2 + k] = dir == 2u ? 2u * (first % 15u) : dir == 3u ? 2u * (first / 15u) : 0u;
+        }
+    }
+    GMK_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_lane_consts), consts, sizeof consts));
     GMK_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_line_init), init, sizeof init));
     GMK_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_lane_jobs), jobs, sizeof jobs));
     if (steps != kScanSteps) { gmk::set_error("lane jobs: %d scan steps, the kernel is built for %d", steps, kScanSteps); return GMK_ERR_STATE; }
