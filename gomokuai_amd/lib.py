@@ -44,6 +44,7 @@ EXPORTS = [
     "gmk_evalstate_create", "gmk_evalstate_destroy", "gmk_evalstate_reset", "gmk_evalstate_update", "gmk_evalstate_update_host", "gmk_evalstate_read",
     "gmk_az_create", "gmk_az_destroy", "gmk_az_set_roots", "gmk_az_select", "gmk_az_expand", "gmk_az_select_host", "gmk_az_expand_host", "gmk_az_read_node_host", "gmk_az_read_children_host", "gmk_az_set_leaf_host", "gmk_az_rollout_host", "gmk_az_expand_stages_host", "gmk_az_write_stats_host", "gmk_az_step", "gmk_az_advance", "gmk_az_set_slots", "gmk_az_live_games", "gmk_az_set_game_ids", "gmk_az_add_root_noise", "gmk_az_set_option", "gmk_az_root_stats",
     "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_run_rave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
+    "gmk_pattern_policy", "gmk_pattern_policy_host", "gmk_pattern_play",
 ]
 
 
@@ -149,6 +150,9 @@ def load():
     L.gmk_records_pack.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, C.c_uint64, vp, vp]
     L.gmk_records_unpack.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.gmk_samples_from_packed.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.gmk_pattern_policy.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    L.gmk_pattern_policy_host.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.gmk_pattern_play.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -447,6 +451,35 @@ class EvaluatorStates:
         _check(load().gmk_evalstate_read(self.h, out["scores"].ctypes.data, out["density"].ctypes.data, out["pattern_dist"].ctypes.data,
                                          out["compound_dist"].ctypes.data, out["meta"].ctypes.data, out["record"].ctypes.data))
         return out
+
+
+# ---------------- K10: the pattern heuristic on its own (EvaluationProbs, DecisiveFilter, EvaluationValue) ----------------
+PATTERN_OVER, PATTERN_EVALUATOR_ERROR, PATTERN_ILLEGAL, PATTERN_STALLED = 1, 2, 4, 8      # status bits of gmk_pattern_policy / gmk_pattern_play
+
+
+def pattern_policy(moves, lens, filter=True):
+    """moves u8[n, stride] (host), lens i32[n]: one move list per position, black first -> {"probs" f32[n,225], "value" f32[n], "best" i32[n],
+    "status" i32[n]} for the player to move: what PatternEvalAgent (filter=True) or MaxEvaluatedRollout (filter=False) sees there.
+    Runs on the GPU through gmk_pattern_policy_host; raises without one."""
+    init()
+    moves = np.ascontiguousarray(moves, dtype=np.uint8)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    assert moves.ndim == 2 and lens.shape == (moves.shape[0],)
+    n, stride = moves.shape
+    out = {"probs": np.zeros((n, N), np.float32), "value": np.zeros(n, np.float32), "best": np.zeros(n, np.int32), "status": np.zeros(n, np.int32)}
+    _check(load().gmk_pattern_policy_host(moves.ctypes.data, stride, lens.ctypes.data, n, int(bool(filter)),
+                                          out["probs"].ctypes.data, out["value"].ctypes.data, out["best"].ctypes.data, out["status"].ctypes.data))
+    return out
+
+
+def pattern_policy_device(d_moves, stride, d_lens, n, filter=True, d_probs=None, d_value=None, d_best=None, d_status=None, stream=None):
+    """Device-pointer form (ints, e.g. torch.Tensor.data_ptr()) of gmk_pattern_policy; asynchronous on `stream`."""
+    _check(load().gmk_pattern_policy(d_moves, int(stride), d_lens, int(n), int(bool(filter)), d_probs, d_value, d_best, d_status, stream))
+
+
+def pattern_play(d_moves, d_lens, n, filter=True, max_moves=0, d_winner=None, d_values=None, d_status=None, stream=None):
+    """gmk_pattern_play: the n openings in d_moves u8[n,225] / d_lens i32[n] (device pointers) are played out greedily in one launch."""
+    _check(load().gmk_pattern_play(d_moves, d_lens, int(n), int(bool(filter)), int(max_moves), d_winner, d_values, d_status, stream))
 
 
 # ---------------- K6: pattern-guided search (TraditionalPolicy), one tree + one evaluator per game ----------------

@@ -713,6 +713,38 @@ def play_match_games(n_games, supervisor, candidate, playouts=400, seed=G.DEFAUL
     return rec, sup_black
 
 
+def play_pattern_games(n_games, opening_plies=4, seed=G.DEFAULT_SEED, first_game_id=0, filter=True, max_moves=N, device=None):
+    """n_games whole games of the search-free pattern policy against itself (K10, gmk_pattern_play): every ply is the first maximum of
+    Heuristic::EvaluationProbs -- after DecisiveFilter with filter=True (PatternEvalAgent), without it Heuristic::MaxEvaluatedRollout -- on the
+    game's live evaluator, all games in ONE launch on the current stream; nothing comes back to the host between plies.  The policy is
+    deterministic: variety comes from the openings (synthetic generator, `opening_plies` plies of game first_game_id + g), so a game's record
+    depends only on its global id.  max_moves < 225: at most that many plies are added to an opening.
+    Returns (GameRecords without visit counts, values float32[n, 225] on the device: entry i of a row = the EvaluationValue the player of
+    move i saw, 0 for opening plies and past the end); the records carry the kernel's status words as `.status` (int32[n], lib.PATTERN_*)."""
+    if max_moves < 1:
+        raise ValueError("play_pattern_games: max_moves must be at least 1")
+    G.init(torch.cuda.current_device() if device is None else device.index)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    moves = np.zeros((n_games, N), dtype=np.uint8)
+    lens = np.zeros(n_games, dtype=np.int32)
+    if opening_plies > 0 and n_games > 0:
+        m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
+        lens = np.minimum(l, opening_plies).astype(np.int32)
+        keep = min(int(opening_plies), m.shape[1])
+        moves[:, :keep] = np.where(np.arange(keep)[None, :] < lens[:, None], m[:, :keep], 0)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        d_moves, d_lens = torch.from_numpy(moves).to(dev), torch.from_numpy(lens).to(dev)
+        d_winner = torch.zeros(n_games, dtype=torch.int8, device=dev)
+        d_values = torch.zeros((n_games, N), dtype=torch.float32, device=dev)
+        d_status = torch.zeros(n_games, dtype=torch.int32, device=dev)
+        G.pattern_play(d_moves.data_ptr(), d_lens.data_ptr(), n_games, filter, max_moves if max_moves < N else 0,
+                       d_winner.data_ptr(), d_values.data_ptr(), d_status.data_ptr(), stream.cuda_stream)
+    rec = GameRecords(d_moves, d_lens, d_winner, None, first_game_id)
+    rec.status = d_status
+    return rec, d_values
+
+
 def dump_batches(samples, path, batch_size=512):
     """The reference appends mini-batches to `latest.train.hdf5` as three growing datasets `state_batch`, `value_batch`,
     `probs_batch` of shape (batches, batch_size, ...) (network/data_helper.py:176-194).  h5py is written when it can be

@@ -441,6 +441,36 @@ int gmk_pvnet_set_dense(gmk_pvnet* net, const float* w_policy, const float* b_po
                         const float* w_out, float b_out);
 int gmk_pvnet_evaluate(gmk_pvnet* net, const float* d_states, int n, float* d_value, float* d_probs, void* stream);
 
+/* ---- K10: the pattern heuristic on its own, per position and for whole greedy games ----
+ * Heuristic::EvaluationProbs, DecisiveFilter and EvaluationValue (core/lib/include/algorithms/Heuristic.hpp:16-45, 94-161) for a batch, outside
+ * any tree.  filter: 1 = EvaluationProbs + DecisiveFilter (PatternEvalAgent::getAction, core/interface/src/Agent.h:107-160, and
+ * TraditionalPolicy::hybridSimulate); 0 = EvaluationProbs alone (Heuristic::MaxEvaluatedRollout, Heuristic.hpp:61-83).
+ * gmk_pattern_policy: position g is the move list d_moves[g*stride .. + d_lens[g]), black first and alternating, replayed in order on a fresh
+ *   evaluator (Evaluator::applyMove, as gmk_evalstate_update: the heuristic reads the order-dependent flag words).  For the player to move:
+ *   d_probs float32[n][225] (an empty list: 1.0 on the centre cell, Heuristic.hpp:22-25), d_value float32[n] = EvaluationValue, d_best int32[n] =
+ *   the first maximum of probs (maxCoeff).  Any output pointer may be NULL.  d_status int32[n]:
+ *     bit 0  the game is over at this position: probs all zero, value 0, best -1 (the reference never asks)
+ *     bit 1  evaluator error, as in K1 and K2
+ *     bit 2  not a position: a cell >= 225, an occupied cell, a move after the end or a length outside [0, 225]; outputs as for bit 0, and
+ *            nothing outside the list is read
+ *   Asynchronous on `stream`; n = 0 does nothing.  The work counter of a launch comes from a ring the first call allocates: let that call
+ *   happen outside a stream capture.
+ * gmk_pattern_policy_host: the same with host buffers (allocates, copies in, runs, copies out, synchronises).
+ * gmk_pattern_play: whole games in ONE launch.  On entry d_moves uint8[n][225] / d_lens int32[n] hold every game's opening (0 .. 225 moves), on
+ *   exit the whole game: every ply is the policy above on the live evaluator and applyMove of `best`, until Evaluator::checkGameEnd
+ *   (Pattern.cpp:344-354) or until max_moves > 0 plies were added (0: no limit).  d_winner int8[n] = -1, 0 or 1; d_values float32[n][225] (or NULL):
+ *   entry i = the EvaluationValue the player of move i saw, 0 for the opening's plies and past the end.  d_status: bits 0 (the game is finished), 1
+ *   and 2 as above -- an opening that is not a position is left as it was given, winner 0 -- and
+ *     bit 3  stalled: the chosen cell was not empty, where the reference would ask again for ever (Heuristic.hpp:65-68); the game stops where
+ *            it stands, winner 0.
+ *   d_winner, d_values and d_status may be NULL. */
+int gmk_pattern_policy(const uint8_t* d_moves, int stride, const int32_t* d_lens, int n, int filter,
+                       float* d_probs, float* d_value, int32_t* d_best, int32_t* d_status, void* stream);
+int gmk_pattern_policy_host(const uint8_t* h_moves, int stride, const int32_t* h_lens, int n, int filter,
+                            float* h_probs, float* h_value, int32_t* h_best, int32_t* h_status);
+int gmk_pattern_play(uint8_t* d_moves, int32_t* d_lens, int n, int filter, int max_moves,
+                     int8_t* d_winner, float* d_values, int32_t* d_status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
