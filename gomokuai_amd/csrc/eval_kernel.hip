@@ -133,6 +133,15 @@ __device__ __forceinline__ void store_saddr(uint32_t byte_offset, int32_t value,
     asm volatile("global_store_dword %0, %1, %2" : : "v"(byte_offset), "v"(value), "s"(base) : "memory");
 }
 
+// The same with an immediate byte offset (13 bits, signed, on gfx950: -4096 .. 4095) and, for kNt, the non-temporal bit: a board's whole 3 600-byte
+// score block lies within reach of ONE scalar base and ONE lane offset, so its sixteen stores need no address arithmetic between them.
+template <int kImm, bool kNt>
+__device__ __forceinline__ void store_saddr_imm(uint32_t byte_offset, int32_t value, unsigned long long base) {
+    static_assert(kImm >= 0 && kImm < 4096, "the immediate offset of a global store has 13 bits, signed");
+    if (kNt) asm volatile("global_store_dword %0, %1, %2 offset:%3 nt" : : "v"(byte_offset), "v"(value), "s"(base), "n"(kImm) : "memory");
+    else asm volatile("global_store_dword %0, %1, %2 offset:%3" : : "v"(byte_offset), "v"(value), "s"(base), "n"(kImm) : "memory");
+}
+
 __device__ __forceinline__ void wave_phase_fence() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -375,7 +384,11 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
 #else
     constexpr int phase_mask = 0x7F;
     (void)phase_mask_arg; (void)prof;
+#ifdef GMK_K1_MARKERS
+#define GMK_STAMP(k) asm volatile("; gmk_mark " #k)      // (tools/k1_frame_counts.py counts the assembly between two marks)
+#else
 #define GMK_STAMP(k) do { } while (0)
+#endif
 #endif
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     // layout: [trans (LDS address 0)][records (16-byte aligned)][lane jobs 128][line pads 96][boards: kBoardsPerBlock * kBoardWords]
@@ -433,7 +446,7 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
         next_black = p[0];
         next_white = p[16];
     };
-    auto take_row = [&](int b) -> uint32_t { return lane < 16 && b < n_boards ? cur_black | (cur_white << 16) : 0u; };
+    auto take_row = [&](int lane_m, int b) -> uint32_t { return lane_m < 16 && b < n_boards ? cur_black | (cur_white << 16) : 0u; };
 
     // The workgroup owns one contiguous run of groups (what a CU writes at any time lies within a few hundred kilobytes) and hands its
     // boards out one at a time from a counter in LDS: the sixteen wavefronts -- four per SIMD, and a SIMD's vector unit is what the kernel
@@ -458,6 +471,9 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
     asm volatile("" : "+v"(next_black), "+v"(next_white));        // (once: wait for them here)
 #pragma unroll 1
     for (;;) {
+#ifdef GMK_K1_MARKERS
+        GMK_STAMP(10);                                          // (the loop's top: what lies in front of it is the prologue, not the loop head)
+#endif
         const bool live = idx < wg_boards;
         const int board = wg_first + idx;
         cur_black = next_black; cur_white = next_white;
@@ -474,9 +490,13 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                 for (int i = 0; i < kCntWords / 4; i += 64)
                     if (i + 64 <= kCntWords / 4 || lane < kCntWords / 4 - i) z[i] = make_uint4(0u, 0u, 0u, 0u);
             }
+            // The lane masks of this phase come from a copy of the lane number that the compiler cannot see through: a compare per board each.  Hoisted
+            // out of the board loop they are scalar register pairs that do not fit and come back by two v_readlane each, per board.
+            int lane_m = lane;
+            asm volatile("" : "+v"(lane_m));
             s_lines[lane] = line_init_lo;                       // (the all-blank line words wait in two registers, not in LDS: no read before the write)
-            if (lane < kLineWords - 64) s_lines[64 + lane] = line_init_hi;
-            if (lane < kMiscWords) s_misc[lane] = 0;
+            if (lane_m < kLineWords - 64) s_lines[64 + lane] = line_init_hi;
+            if (lane_m < kMiscWords) s_misc[lane] = 0;
 #ifndef GMK_K1_TOTALS_HOT
             // Per-type totals: one atomic per match on eight addresses is 64 lanes on eight LDS words -- up to ~25 of them on the same one, served
             // one after the other (phase 2 is 41 % of the LDS pipe's cycles, profiles/r04_k1_lds_phases.txt).  kTotalsCopies copies, a lane adds to copy
@@ -484,7 +504,7 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
             // summed behind phase 2.
             if (lane < 8 * kTotalsCopies) s_queue[kQueueCap - 8 * kTotalsCopies + lane] = 0;
 #endif
-            const uint32_t my_row = take_row(board);
+            const uint32_t my_row = take_row(lane_m, board);
             wave_phase_fence();
             {
                 // stones per colour: a row reduction in registers (an atomicAdd of fifteen lanes on one word is turned by the compiler
@@ -494,7 +514,7 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                 cnt += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(cnt), 0x114, 0xF, 0xF, false));       // row_shr:4
                 cnt += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(cnt), 0x112, 0xF, 0xF, false));       // row_shr:2
                 cnt += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(cnt), 0x111, 0xF, 0xF, false));       // row_shr:1
-                if (lane == 15) s_misc[0] = cnt;                // lane 15 holds the sum of lanes 0 .. 15 (my_row is zero in lane 15)
+                if (lane_m == 15) s_misc[0] = cnt;                // lane 15 holds the sum of lanes 0 .. 15 (my_row is zero in lane 15)
             }
             {
                 // Where is a colour's density count positive (<=> its weight positive: the +160 of Pattern.cpp:268)?  Wherever a stone
@@ -520,7 +540,8 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                 for (int pass = 0; pass < 4; ++pass) {
                     const uint32_t gw = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(static_cast<int>((cell_row4 >> (8 * pass)) & 0xFFu), gate)) >> ((cell_col >> (8 * pass)) & 0xFFu);
                     if (pass < 3 || lane < kCells - 192)
-                        reinterpret_cast<uint4*>(s_scores)[64 * pass + lane] = make_uint4(((gw >> 16) & 1u) * 160u, 0u, 0u, (gw & 1u) * 160u);
+                        reinterpret_cast<uint4*>(s_scores)[64 * pass + lane] = make_uint4(static_cast<uint32_t>(__builtin_amdgcn_sbfe(static_cast<int>(gw), 16, 1)) & 160u, 0u, 0u,
+                                                                                          static_cast<uint32_t>(__builtin_amdgcn_sbfe(static_cast<int>(gw), 0, 1)) & 160u);
                 }
             }
             {
@@ -529,14 +550,19 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                 const int y = lane >> 2, part = lane & 3;
                 const uint32_t row = __shfl(my_row, min(y, 14));
                 uint32_t row_sym = 0;
+                // (what the loop needs of y, worked out in front of it: left to itself the compiler recomputes both for every stone)
+                uint32_t y2 = 2u * static_cast<uint32_t>(y), y4 = 4u * static_cast<uint32_t>(y);
+                asm volatile("" : "+v"(y2), "+v"(y4));
                 for (uint32_t m = lane < 60 ? (row | (row >> 16)) & (0xFu << (4 * part)) & 0x7FFFu : 0u; m; m &= m - 1u) {
                     const int x = __ffs(m) - 1;
-                    const uint32_t code = ((row >> x) & 1u) ? 3u : 2u;
-                    const uint32_t at_x = code << (2 * x), at_y = code << (2 * y);
+                    const uint32_t code = ((row >> x) & 1u) | 2u;                      // black 3, white 2
+                    const uint32_t at_x = code << (2 * x), at_y = code << y2;
                     row_sym |= at_x;
-                    atomicXor(&s_lines[kColBase + x], at_y);
-                    atomicXor(&s_lines[kDiagBase + x - y + 14], at_x);
-                    atomicXor(&s_lines[kAntiBase + x + y], at_y);
+                    // (the three words lie at the column's word -+ y: one shift-add and two adds, the bases are immediate offsets)
+                    char* const col = reinterpret_cast<char*>(s_lines + x);
+                    atomicXor(reinterpret_cast<uint32_t*>(col) + kColBase, at_y);
+                    atomicXor(reinterpret_cast<uint32_t*>(col - y4) + (kDiagBase + 14), at_x);
+                    atomicXor(reinterpret_cast<uint32_t*>(col + y4) + kAntiBase, at_y);
                 }
                 if (row_sym) atomicXor(&s_lines[y], row_sym);
             }
@@ -828,39 +854,55 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
         }
         if (!live) break;
         // ---- phase 5: results leave LDS ----
+#ifdef GMK_K1_MARKERS
+        GMK_STAMP(12);
+#endif
         if (live && (phase_mask & 32)) {
             int lane_b = lane;                                  // (a copy the compiler cannot see through: the store addresses are computed here,
             asm volatile("" : "+v"(lane_b));                    // not kept in registers across the density pass)
+            // Every store of the phase is global_store_dword <lane * 4>, <value>, s[base] offset:<immediate>: the board is wave-uniform, so its
+            // blocks' addresses are worked out on the scalar unit, and what differs between the stores of a block is an immediate.
+            const uint32_t lane_off = 4u * static_cast<uint32_t>(lane_b);
             if (out_scores) {
                 // the block is [cell][group] in LDS and [group][cell] in memory: a lane reads the sixteen bytes of its cell and writes one
                 // word into each group's plane, 256 contiguous bytes per store instruction
-                int32_t* dst = out_scores + static_cast<size_t>(board) * kScoreWords + lane_b;
+                const unsigned long long dst = reinterpret_cast<unsigned long long>(out_scores + static_cast<size_t>(board) * kScoreWords);
                 const int4* src = reinterpret_cast<const int4*>(s_scores);
                 // (all reads first: one LDS round trip instead of four)
                 const int4 v0 = src[lane_b], v1 = src[lane_b + 64], v2 = src[lane_b + 128], v3 = src[min(lane_b + 192, kCells - 1)];
 #ifdef GMK_K1_PLAIN_SCORES
-#define GMK_STORE(p, v) (*(p) = (v))
+                constexpr bool kNt = false;
 #else
-#define GMK_STORE(p, v) __builtin_nontemporal_store(v, p)       // (non-temporal: 0.1575 -> 0.1543 ms)
+                constexpr bool kNt = true;                          // (non-temporal: 0.1575 -> 0.1543 ms)
 #endif
+#define GMK_STORE(words, v) store_saddr_imm<4 * (words), kNt>(lane_off, v, dst)
                 // in ADDRESS order (the board's 3 600 bytes are one contiguous run: piece after piece, so that the two parts of a cache line that two
                 // pieces share reach the L2 back to back)
                 const bool tail = lane_b + 192 < kCells;
-                GMK_STORE(dst, v0.x); GMK_STORE(dst + 64, v1.x); GMK_STORE(dst + 128, v2.x); if (tail) GMK_STORE(dst + 192, v3.x);
-                GMK_STORE(dst + kCells, v0.y); GMK_STORE(dst + kCells + 64, v1.y); GMK_STORE(dst + kCells + 128, v2.y); if (tail) GMK_STORE(dst + kCells + 192, v3.y);
-                GMK_STORE(dst + 2 * kCells, v0.z); GMK_STORE(dst + 2 * kCells + 64, v1.z); GMK_STORE(dst + 2 * kCells + 128, v2.z); if (tail) GMK_STORE(dst + 2 * kCells + 192, v3.z);
-                GMK_STORE(dst + 3 * kCells, v0.w); GMK_STORE(dst + 3 * kCells + 64, v1.w); GMK_STORE(dst + 3 * kCells + 128, v2.w); if (tail) GMK_STORE(dst + 3 * kCells + 192, v3.w);
+                GMK_STORE(0, v0.x); GMK_STORE(64, v1.x); GMK_STORE(128, v2.x); if (tail) GMK_STORE(192, v3.x);
+                GMK_STORE(kCells, v0.y); GMK_STORE(kCells + 64, v1.y); GMK_STORE(kCells + 128, v2.y); if (tail) GMK_STORE(kCells + 192, v3.y);
+                GMK_STORE(2 * kCells, v0.z); GMK_STORE(2 * kCells + 64, v1.z); GMK_STORE(2 * kCells + 128, v2.z); if (tail) GMK_STORE(2 * kCells + 192, v3.z);
+                GMK_STORE(3 * kCells, v0.w); GMK_STORE(3 * kCells + 64, v1.w); GMK_STORE(3 * kCells + 128, v2.w); if (tail) GMK_STORE(3 * kCells + 192, v3.w);
 #undef GMK_STORE
             }
-            if (out_totals && lane_b < 11) out_totals[static_cast<size_t>(board) * 11 + lane_b] = s_misc[4 + lane_b];
-            if (out_status && lane_b == 0) {
-                const uint32_t wbits = s_misc[1], stones = s_misc[0];
+            if (out_totals) {
+                const unsigned long long dst = reinterpret_cast<unsigned long long>(out_totals + static_cast<size_t>(board) * 11);
+                if (lane_b < 11) store_saddr_imm<0, false>(lane_off, static_cast<int32_t>(s_misc[4 + lane_b]), dst);
+            }
+            if (out_status) {
+                // stones, winner bits and the error flag are one value per board: every lane reads them (one broadcast read each), the
+                // scalar unit does the arithmetic, lane 0 stores the word
+                const uint32_t stones = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(s_misc[0])));
+                const uint32_t wbits = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(s_misc[1])));
+                const uint32_t flagged = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(s_misc[2])));
                 const int stones_b = stones & 0xFFFFu, stones_w = stones >> 16;
                 // the side that completed five is the only one that can own a Five (the game stops there)
                 const int winner = (wbits & 1u) ? 1 : (wbits & 2u) ? -1 : 0;
                 const bool over = winner != 0 || stones_b + stones_w == kCells;
                 const int to_move = over ? 0 : (stones_b == stones_w ? 1 : -1);
-                out_status[board] = (over ? 1 : 0) | ((s_misc[2] || phase_mask != 0x7F) ? 2 : 0) | ((winner & 0xFF) << 8) | ((to_move & 0xFF) << 16);
+                const int word = (over ? 1 : 0) | ((flagged || phase_mask != 0x7F) ? 2 : 0) | ((winner & 0xFF) << 8) | ((to_move & 0xFF) << 16);
+                const unsigned long long dst = reinterpret_cast<unsigned long long>(out_status + board);
+                if (lane_b == 0) store_saddr_imm<0, false>(lane_off, word, dst);
             }
         }
         wave_phase_fence();
