@@ -61,7 +61,8 @@ constexpr int kMaxBlocksPerCu = 1;
 constexpr int kScoreWords = 4 * kCells;          // 900, 16-byte aligned block.  In LDS the block is [cell][4 groups]: a colour's own and opponent view of a
                                                  // cell are the halves of one 64-bit word (white: groups 0, 1; black: 2, 3), so a deposit into both is ONE ds_add_u64
 constexpr int kCntWords = 3 * kCells + 1;        // [LiveThree, DeadThree, LiveTwo][cell]: eight 4-bit counters per word, field = colour * 4 + direction:
-                                                 // how many '_' pieces of matches of that type lie on the cell (<= 15: at most 8 transitions x 2 matches reach a cell)
+                                                 // how many '_' pieces of matches of that type lie on the cell (<= 15: at most 8 transitions x 2 matches reach a cell;
+                                                 // the most any board of the test sets or of the saturation search reaches is 2)
 constexpr int kZeroWords = kScoreWords + kCntWords;                   // cleared for every board (a multiple of 4)
 constexpr int kLineWords = 96;                   // line words, 2 bits per cell = its DFA symbol (0 black, 1 white, 3 blank): rows [0,15) cell x at bits 2x,
                                                  // columns [20,35) cell y at bits 2y, diagonals x-y+14 at [36,65) at bits 2x, anti-diagonals x+y at [65,94) at bits 2y
@@ -621,7 +622,8 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                 }
                 push(tw, kScanSteps - 1);
                 n_queued = static_cast<int>((q_at - q_base) >> 2);
-                if (q_at >= q_full) s_misc[2] = 1;                  // (flagged at kQueueCap - 64 entries: 2.5 x the most a board of the test sets queues)
+                if (q_at >= q_full) s_misc[2] = 1;                  // (flagged at kQueueCap - 64 = 384 entries: 2.0 x the 192 of the synthetic and dense test boards,
+                                                                    //  1.14 x the 338 of the heaviest legal position a search found, DESIGN.md "K1's fixed capacities")
             }
             wave_phase_fence();
             GMK_STAMP(2);
@@ -703,8 +705,15 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
 
             // ---- phase 3b: one lane per candidate cell and colour: the compound decision (Pattern.cpp:440-486), critical-point deposits,
             //      counter-move rescans queued in the upper half of the queue ----
+            // (an empty cell is a candidate at most once and a board with a counter has a stone: n_cand <= 224 = kQueueCap / 2, the list cannot overflow)
             if (n_cand > kQueueCap / 2) { s_misc[2] = 1; n_cand = kQueueCap / 2; }
             if (phase_mask & 2048) n_cand = 0;
+            // The rescan queue works in ROUNDS: a round of phase 3b queues at most 64 x 2 entries, and phase 4 empties the queue once the next
+            // round's might not fit, and behind the last round.  (Legal positions queue more than the upper half holds -- 116 compounds of this
+            // kind = 232 entries on a position of tests/golden/k1_saturated.npz -- and used to be flagged with their rescans dropped.)  The
+            // benchmark's boards have at most 32 candidates: one round, phase 4 once, as before; a board without candidates skips both.
+            constexpr int kRescanFlush = kQueueCap / 2 - 2 * 64;    // fill level above which another round might not fit
+            static_assert(kRescanFlush > 0 && kRescanFlush + 2 * 64 <= kQueueCap / 2, "a round of phase 3b fits behind the flush level");
             int n_comp_q = 0;                                       // components queued for phase 4 (wave-uniform: slots by ballot prefix)
             if (phase_mask & 8)
             for (int v0 = 0; v0 < 2 * n_cand; v0 += 64) {           // one lane per (candidate cell, colour): 0 white, 1 black
@@ -777,11 +786,12 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                 if (queue) {
                     const uint32_t slot = static_cast<uint32_t>(n_comp_q) + 2u * __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(queuers >> 32),
                                                                                                           __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(queuers), 0u));
-                    if (slot < kQueueCap / 2) { s_queue[kQueueCap / 2 + slot] = ent1; s_queue[kQueueCap / 2 + slot + 1] = ent2; }      // (slots are even)
-                    else s_misc[2] = 1;
+                    // (slots are even, and slot + 1 <= kRescanFlush + 2 * 63 + 1 < kQueueCap / 2: no bounds check)
+                    s_queue[kQueueCap / 2 + slot] = ent1;
+                    s_queue[kQueueCap / 2 + slot + 1] = ent2;
                 }
                 n_comp_q += 2 * __popcll(queuers);
-            }
+                if (v0 + 64 < 2 * n_cand && n_comp_q <= kRescanFlush) continue;      // more candidates and room for their round: on with phase 3b
             wave_phase_fence();
             GMK_STAMP(5);
 
@@ -791,7 +801,7 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
             //      per round, lane 63 idle), lane kk looks at the transition at index 6 + kk only (the automaton forgets its start
             //      state after 7 symbols, so <= 8 lookups from the root bring it to the right state), and the lowest lane with a hit applies it ----
             if (phase_mask & 16) {
-                const int n_comp = min(n_comp_q, kQueueCap / 2);
+                const int n_comp = n_comp_q;
                 int lane_4 = lane;                                  // (an opaque copy: the lane's place is derived here, not kept in registers
                 asm volatile("" : "+v"(lane_4));                    //  across the whole board loop)
                 const int grp = lane_4 / 7, kk = lane_4 - 7 * grp, k = 6 + kk, start = k > 7 ? k - 7 : 0;
@@ -828,8 +838,10 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                     if (hit_back >= 0 && (mine & ((1u << kk) - 1u)) == 0u) add_counter_cells(hit_w0, hit_back, q, stride, s_scores + (c ? 2 : 1));
                 }
             }
+            n_comp_q = 0;                                           // the queue is empty again (its entries are read before the next round writes: LDS runs in order)
             wave_phase_fence();
             GMK_STAMP(6);
+            }                                                       // (the rounds of phases 3b and 4)
 
         }
 

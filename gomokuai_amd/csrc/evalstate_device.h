@@ -261,8 +261,7 @@ __device__ inline void queue_compound(const Ctx& c, int cell, int pb /* player i
         const int count_i = count0 + i * delta;
         const uint32_t item = static_cast<uint32_t>(cell) | (static_cast<uint32_t>(pb) << 8) | (static_cast<uint32_t>(ctype) << 9) |
                               (((comps >> (4 * i)) & 15u) << 11) | ((!triple && l3 == 0) ? 1u << 15 : 0u) | ((2 * count_i + delta == 3) ? 1u << 16 : 0u);
-        if (slot0 + i < static_cast<uint32_t>(kCompoundCap)) c.scratch[oItems + slot0 + i] = item;
-        else c.st[oMeta + 3] |= 8u;
+        if (slot0 + i < static_cast<uint32_t>(kCompoundCap)) c.scratch[oItems + slot0 + i] = item;      // (past the end: update_compounds sees the count and starts over in rounds)
     }
 }
 
@@ -340,29 +339,42 @@ __device__ inline void apply_compound_items(const Ctx& c, int delta) {
 }
 
 // Updater::updateCompound for the four directions (Pattern.cpp:167-197): lane = direction * 13 + window index finds the
-// compounds, then one lane per component applies them
+// compounds, then one lane per component applies them.
+// The component queue holds kCompoundCap items.  All 52 lanes queue at once first (round -1); a move whose windows hold more components
+// than that -- legal positions do: tests/golden/k1_saturated.npz has games with more than 64 around one move, which used to be flagged
+// with the surplus dropped -- is done again four lanes at a time: 4 cells x 2 colours x at most 8 components fit the queue whatever the
+// board.  Nothing is applied before the count is known, and a compound's items depend on nothing another compound's application writes
+// (its own-view count field of its own cell; applications write other cells' opponent-view fields and their own cell), so the rounds
+// give what the one pass gives -- and what the reference's compound-after-compound loop gives.
 __device__ inline void update_compounds(const Ctx& c, int move, int delta) {
-    if (c.lane == 0) c.scratch[oItemCount] = 0u;
-    wave_phase_fence();
-    if (c.lane < 52) {
-        const int dir = c.lane / 13, i = c.lane % 13;
-        const uint64_t syms = window_symbols(c.st + oLines, move, dir);
-        // only blanks; the centre lies on all four lines and is handled once (findCompound)
-        if (!(i == 6 && dir != 0) && ((syms >> (2 * i)) & 3u) == 3u) {
-            const int cell = move + (i - 6) * dir_stride(dir);
-            const uint32_t* density = c.st + oDensity;
-            const uint32_t* pd = c.st + oPdist + pdist_index(cell, 0);
-            const uint32_t any = pd[5] | pd[4] | pd[3];
-            for (int pb = 0; pb < 2; ++pb) {                    // { White, Black }
-                if (density_count(density[pb * kCells + cell]) < 2) continue;
-                const uint32_t bits = (any >> (8 * group2(pb, pb))) & 0xFFu;           // Compound::Test (Pattern.cpp:424-433)
-                if (!(bits & (bits - 1u))) continue;
-                queue_compound(c, cell, pb, delta);
+    static_assert(4 * 2 * 8 <= kCompoundCap, "a round of four lanes fits the component queue");
+    for (int round = -1; round < 13; ++round) {
+        if (c.lane == 0) c.scratch[oItemCount] = 0u;
+        wave_phase_fence();
+        if (c.lane < 52 && (round < 0 || (c.lane >> 2) == round)) {
+            const int dir = c.lane / 13, i = c.lane % 13;
+            const uint64_t syms = window_symbols(c.st + oLines, move, dir);
+            // only blanks; the centre lies on all four lines and is handled once (findCompound)
+            if (!(i == 6 && dir != 0) && ((syms >> (2 * i)) & 3u) == 3u) {
+                const int cell = move + (i - 6) * dir_stride(dir);
+                const uint32_t* density = c.st + oDensity;
+                const uint32_t* pd = c.st + oPdist + pdist_index(cell, 0);
+                const uint32_t any = pd[5] | pd[4] | pd[3];
+                for (int pb = 0; pb < 2; ++pb) {                    // { White, Black }
+                    if (density_count(density[pb * kCells + cell]) < 2) continue;
+                    const uint32_t bits = (any >> (8 * group2(pb, pb))) & 0xFFu;           // Compound::Test (Pattern.cpp:424-433)
+                    if (!(bits & (bits - 1u))) continue;
+                    queue_compound(c, cell, pb, delta);
+                }
             }
         }
+        wave_phase_fence();
+        // (one value for the wavefront: every lane reads the same word)
+        if (__builtin_amdgcn_readfirstlane(static_cast<int>(c.scratch[oItemCount])) > kCompoundCap) continue;      // round -1 only: again, in rounds
+        apply_compound_items(c, delta);
+        if (round < 0) break;
+        wave_phase_fence();
     }
-    wave_phase_fence();
-    apply_compound_items(c, delta);
 }
 
 // Updater::updateBlock (Pattern.cpp:236-272): lanes 0..48 = the 7x7 block around the move

@@ -95,7 +95,8 @@ int gmk_moves_to_planes(const uint8_t *h_moves, int stride, const int32_t *h_len
  *   totals  uint32[n][11]        m_patternDist[225][0..7] then m_compoundDist[225][0..2]: white count in the low,
  *                                black in the high 16 bits (Pattern.cpp:390-393)
  *   status  int32[n]             bit0 game over, bit1 evaluator error (the reference would read out of bounds,
- *                                Pattern.cpp:484-485, or overflow a queue), bits 8..15 winner, bits 16..23 player to move
+ *                                Pattern.cpp:484-485, or the board queues 384 or more emitting transitions: no legal position
+ *                                found so far does, DESIGN.md "K1's fixed capacities"), bits 8..15 winner, bits 16..23 player to move
  * Any output pointer may be NULL.  All pointers are device pointers; n boards; asynchronous on stream. */
 int gmk_eval_batch(const uint16_t *d_planes, int n,
                    int32_t *d_scores, int32_t *d_density, uint32_t *d_totals, int32_t *d_status,

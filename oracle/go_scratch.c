@@ -30,12 +30,14 @@ static int sym(const int8_t *cell, int x, int y) {
 
 /* lead / trail: number of '?' symbols put before / after the cells of every line.  The reference uses 6/6
    (Mapping.cpp:61-77); the kernel uses 1/2, which this model lets the tests prove equivalent. */
-int go_scratch_eval(const int8_t *cell /*[225] -1/0/+1*/, int lead, int trail,
-                    int32_t *scores /*[4][225]*/, int32_t *density /*[2][2][225]*/,
-                    uint32_t *totals /*[11]*/, int32_t *status) {
+/* load (optional, int32[GO_LOAD_FIELDS]): how much of each fixed-size structure of K1 the position asks for, see go_scratch_load */
+static int scratch_core(const int8_t *cell /*[225] -1/0/+1*/, int lead, int trail,
+                        int32_t *scores /*[4][225]*/, int32_t *density /*[2][2][225]*/,
+                        uint32_t *totals /*[11]*/, int32_t *status, int32_t *load) {
     const go_ac *ac = go_default_ac();
-    static int cnt[GO_N][3][2][4];                 /* '_' pieces of L3 / D3 / L2 per cell, colour, direction */
+    int cnt[GO_N][3][2][4];                        /* '_' pieces of L3 / D3 / L2 per cell, colour, direction */
     int winner = GO_NONE, err = 0, n_black = 0, n_white = 0;
+    int n_trans = 0, n_match = 0, n_cand = 0, n_compound = 0, n_queued = 0, max_cnt = 0, type_err = 0, n_five = 0;
     memset(scores, 0, sizeof(int32_t) * 4 * GO_N);
     memset(density, 0, sizeof(int32_t) * 4 * GO_N);
     memset(totals, 0, sizeof(uint32_t) * 11);
@@ -58,9 +60,12 @@ int go_scratch_eval(const int8_t *cell /*[225] -1/0/+1*/, int lead, int trail,
             int32_t pat[64], off[64];
             int m = go_ac_match(ac, codes, n, pat, off, 64);
             if (m > 64) { err = 1; m = 64; }
+            uint64_t ends = 0;                      /* end offsets with a match: the automaton's emitting transitions on this line */
+            n_match += m;
             for (int k = 0; k < m; ++k) {
                 const go_pattern *p = &ac->patterns[pat[k]];
-                if (p->type == GO_FIVE) { winner = p->favour; continue; }
+                if (!((ends >> off[k]) & 1)) { ends |= 1ull << off[k]; ++n_trans; }
+                if (p->type == GO_FIVE) { winner = p->favour; ++n_five; continue; }
                 int end = (y0 * GO_W + x0) + (off[k] - lead) * k_stride[dir];
                 totals[p->type] += (p->favour == GO_BLACK) ? 0x10000u : 1u;
                 int s = (dir >= 2) ? (int)(1.2 * p->score) : p->score;
@@ -98,7 +103,10 @@ int go_scratch_eval(const int8_t *cell /*[225] -1/0/+1*/, int lead, int trail,
 
     /* 4: compounds (A.8 step 4; Pattern.cpp:167-197, 420-550) */
     for (int q = 0; q < GO_N; ++q) {
+        for (int t = 0; t < 3; ++t) for (int c = 0; c < 2; ++c) for (int d = 0; d < 4; ++d)
+            if (cnt[q][t][c][d] > max_cnt) max_cnt = cnt[q][t][c][d];
         if (cell[q] != GO_NONE) continue;
+        int is_cand = 0;
         for (int c = 0; c < 2; ++c) {
             int colour = c ? GO_BLACK : GO_WHITE;
             int k[3][4], bits = 0;
@@ -107,6 +115,7 @@ int go_scratch_eval(const int8_t *cell /*[225] -1/0/+1*/, int lead, int trail,
                 bits |= (k[t][d] == 1 ? 1 : k[t][d] == 2 ? 3 : 0) << (2 * d);
             }
             if (!(bits & (bits - 1))) continue;
+            if (!is_cand) { is_cand = 1; ++n_cand; }
             if (density[(c * 2 + 0) * GO_N + q] < 2) continue;
             enum { S0, L2, LD3, To33, To43, To44 };
             int state = S0, l3 = 0, triple = 0, ncomp = 0, cdir[8], ctype[8];
@@ -123,7 +132,9 @@ int go_scratch_eval(const int8_t *cell /*[225] -1/0/+1*/, int lead, int trail,
                 }
             }
             int type = state - To33;
-            if (type < 0 || type > 2) { err = 1; continue; }      /* reference: out-of-bounds read */
+            if (type < 0 || type > 2) { err = 1; type_err = 1; continue; }      /* reference: out-of-bounds read */
+            ++n_compound;
+            if (!triple && !l3) ++n_queued;             /* its two components' counter moves are looked up again */
             totals[8 + type] += c ? 0x10000u : 1u;
             for (int i = 0; i < ncomp; ++i) {
                 scores[grp(colour, colour) * GO_N + q] += 600;
@@ -154,15 +165,48 @@ int go_scratch_eval(const int8_t *cell /*[225] -1/0/+1*/, int lead, int trail,
     int end = winner != GO_NONE || n_black + n_white == GO_N;
     int cur = end ? GO_NONE : (n_black == n_white ? GO_BLACK : GO_WHITE);
     if (status) *status = (end ? 1 : 0) | (err ? 2 : 0) | ((int)(uint8_t)(int8_t)winner << 8) | ((int)(uint8_t)(int8_t)cur << 16);
+    if (load) {
+        load[GO_LOAD_TRANSITIONS] = n_trans; load[GO_LOAD_MATCHES] = n_match; load[GO_LOAD_CANDIDATES] = n_cand;
+        load[GO_LOAD_COMPOUNDS] = n_compound; load[GO_LOAD_QUEUED] = n_queued; load[GO_LOAD_MAX_COUNTER] = max_cnt;
+        load[GO_LOAD_TYPE_ERROR] = type_err; load[GO_LOAD_FIVES] = n_five;
+    }
     return err;
+}
+
+int go_scratch_eval(const int8_t *cell, int lead, int trail, int32_t *scores, int32_t *density, uint32_t *totals, int32_t *status) {
+    return scratch_core(cell, lead, trail, scores, density, totals, status, NULL);
+}
+
+/* What a position asks of K1's fixed-size on-chip structures, counted with the oracle's own matcher on the kernel's line
+   padding (1 leading, 2 trailing '?'): see GO_LOAD_* in gomoku_oracle.h.  A model of loads, not of kernel code. */
+int go_scratch_load(const int8_t *cell, int32_t *load /*[GO_LOAD_FIELDS]*/) {
+    int32_t scores[4 * GO_N], density[4 * GO_N], status;
+    uint32_t totals[11];
+    return scratch_core(cell, 1, 2, scores, density, totals, &status, load);
+}
+
+static void cells_of(const uint8_t *moves, int len, int8_t *cell) {
+    memset(cell, 0, GO_N);
+    for (int i = 0; i < len; ++i) cell[moves[i]] = (i & 1) ? GO_WHITE : GO_BLACK;
+}
+
+void go_scratch_load_cells_batch(const int8_t *cells /*[n][225]*/, int n, int32_t *load /*[n][GO_LOAD_FIELDS]*/) {
+    for (int b = 0; b < n; ++b) go_scratch_load(cells + (size_t)b * GO_N, load + (size_t)b * GO_LOAD_FIELDS);
+}
+
+void go_scratch_load_batch(const uint8_t *moves, const int32_t *lens, int stride, int n, int32_t *load /*[n][GO_LOAD_FIELDS]*/) {
+    for (int b = 0; b < n; ++b) {
+        int8_t cell[GO_N];
+        cells_of(moves + (size_t)b * stride, lens[b], cell);
+        go_scratch_load(cell, load + (size_t)b * GO_LOAD_FIELDS);
+    }
 }
 
 void go_scratch_eval_batch(const uint8_t *moves, const int32_t *lens, int stride, int n, int lead, int trail,
                            int32_t *scores, int32_t *density, uint32_t *totals, int32_t *status) {
     for (int b = 0; b < n; ++b) {
         int8_t cell[GO_N];
-        memset(cell, 0, sizeof cell);
-        for (int i = 0; i < lens[b]; ++i) cell[moves[(size_t)b * stride + i]] = (i & 1) ? GO_WHITE : GO_BLACK;
+        cells_of(moves + (size_t)b * stride, lens[b], cell);
         go_scratch_eval(cell, lead, trail, scores + (size_t)b * 4 * GO_N, density + (size_t)b * 4 * GO_N,
                         totals + (size_t)b * 11, status + b);
     }

@@ -124,6 +124,21 @@ int  go_scratch_eval(const int8_t *cell, int lead, int trail, int32_t *scores, i
 void go_scratch_eval_batch(const uint8_t *moves, const int32_t *lens, int stride, int n, int lead, int trail,
                            int32_t *scores, int32_t *density, uint32_t *totals, int32_t *status);
 
+/* What a position asks of the fixed-size structures of K1 (eval_kernel.hip), counted by the same formulation:
+     TRANSITIONS  (line, end offset) pairs with at least one match, Fives included, on lines padded 1 + 2 (the transition queue)
+     MATCHES      matches, Fives included
+     CANDIDATES   empty cells where either colour's 2-bit direction flags have two or more bits set (the candidate list)
+     COMPOUNDS    (cell, colour) compounds: candidates past the density gate with a type in range
+     QUEUED       of those, the ones with exactly two components and no LiveThree (the counter-move rescan queue)
+     MAX_COUNTER  the largest unclipped '_' counter of a (cell, type, colour, direction) (the kernel keeps it in 4 bits)
+     TYPE_ERROR   1 if a candidate's compound type is out of range (Pattern.cpp:484-485 reads out of bounds; status bit 1)
+     FIVES        Five matches (a position in play has none, a finished one those of the last stone) */
+enum { GO_LOAD_TRANSITIONS, GO_LOAD_MATCHES, GO_LOAD_CANDIDATES, GO_LOAD_COMPOUNDS, GO_LOAD_QUEUED, GO_LOAD_MAX_COUNTER,
+       GO_LOAD_TYPE_ERROR, GO_LOAD_FIVES, GO_LOAD_FIELDS };
+int  go_scratch_load(const int8_t *cell, int32_t *load);
+void go_scratch_load_batch(const uint8_t *moves, const int32_t *lens, int stride, int n, int32_t *load);
+void go_scratch_load_cells_batch(const int8_t *cells, int n, int32_t *load);   /* cells int8[n][225]: any stone counts (search tools) */
+
 /* ---------------- Philox4x32-10 (counter-based RNG shared with the GPU path) ---------------- */
 void go_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 

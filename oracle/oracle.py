@@ -88,6 +88,10 @@ def lib():
     L.go_eval_replay_batch.restype = None
     L.go_scratch_eval_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.go_scratch_eval_batch.restype = None
+    L.go_scratch_load_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.go_scratch_load_batch.restype = None
+    L.go_scratch_load_cells_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.go_scratch_load_cells_batch.restype = None
     L.go_philox4x32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.go_philox4x32.restype = None
     L.go_trad_new.argtypes = [C.c_double]
@@ -295,6 +299,27 @@ def scratch_batch(moves, lens, lead=6, trail=6):
     lib().go_scratch_eval_batch(moves.ctypes.data, lens.ctypes.data, stride, n, lead, trail,
                                 scores.ctypes.data, density.ctypes.data, totals.ctypes.data, status.ctypes.data)
     return scores, density, totals, status
+
+
+LOAD_FIELDS = ("transitions", "matches", "candidates", "compounds", "queued", "max_counter", "type_error", "fives")
+
+
+def scratch_load(moves, lens):
+    """What the final positions of the move lists ask of K1's fixed-size structures (go_scratch_load): i32[n, 8], columns LOAD_FIELDS."""
+    moves = np.ascontiguousarray(moves, dtype=np.uint8)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    n, stride = moves.shape
+    load = np.zeros((n, len(LOAD_FIELDS)), dtype=np.int32)
+    lib().go_scratch_load_batch(moves.ctypes.data, lens.ctypes.data, stride, n, load.ctypes.data)
+    return load
+
+
+def scratch_load_cells(cells):
+    """The same for positions given as cells, i8[n, 225] (-1 white, 0 empty, +1 black), whatever their stone counts."""
+    cells = np.ascontiguousarray(cells, dtype=np.int8).reshape(-1, N)
+    load = np.zeros((len(cells), len(LOAD_FIELDS)), dtype=np.int32)
+    lib().go_scratch_load_cells_batch(cells.ctypes.data, len(cells), load.ctypes.data)
+    return load
 
 
 def philox(ctr, key):

@@ -90,6 +90,12 @@ def test_long_games(oracle):
     keep = np.nonzero((ref[3] & 2) == 0)[0]
     got = G.eval_batch_host(planes)
     _compare([r[keep] for r in ref], [g[keep] for g in got])
+    # ... and on ALL of them the kernel's error bit is the position's own (the oracle's from-scratch evaluation, the kernel's line padding):
+    # the replay's bit also remembers errors of earlier positions of the game, which a kernel that sees the stones only cannot know
+    pure = oracle.scratch_batch(moves, lens, 1, 2)
+    print("long games: %d boards, %d flagged by the replay, %d by the position alone, %d by the kernel" %
+          (len(lens), ((ref[3] & 2) != 0).sum(), ((pure[3] & 2) != 0).sum(), ((got[3] & 2) != 0).sum()))
+    assert ((got[3] & 2) == (pure[3] & 2)).all()
 
 
 def test_properties_at_full_size(oracle):
