@@ -45,6 +45,8 @@ EXPORTS = [
     "gmk_az_create", "gmk_az_destroy", "gmk_az_set_roots", "gmk_az_select", "gmk_az_expand", "gmk_az_select_host", "gmk_az_expand_host", "gmk_az_read_node_host", "gmk_az_read_children_host", "gmk_az_set_leaf_host", "gmk_az_rollout_host", "gmk_az_expand_stages_host", "gmk_az_write_stats_host", "gmk_az_step", "gmk_az_advance", "gmk_az_set_slots", "gmk_az_live_games", "gmk_az_set_game_ids", "gmk_az_add_root_noise", "gmk_az_set_option", "gmk_az_root_stats",
     "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_run_rave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
     "gmk_pattern_policy", "gmk_pattern_policy_host", "gmk_pattern_play",
+    "gmk_replay_create", "gmk_replay_destroy", "gmk_replay_reset", "gmk_replay_append", "gmk_replay_append_packed", "gmk_replay_size",
+    "gmk_replay_sample", "gmk_replay_draw_host",
 ]
 
 
@@ -153,6 +155,14 @@ def load():
     L.gmk_pattern_policy.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.gmk_pattern_policy_host.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.gmk_pattern_play.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.gmk_replay_create.argtypes = [C.c_int64, C.c_int64, C.c_uint64, C.POINTER(vp)]
+    L.gmk_replay_destroy.argtypes = [vp]
+    L.gmk_replay_reset.argtypes = [vp, vp]
+    L.gmk_replay_append.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    L.gmk_replay_append_packed.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp]
+    L.gmk_replay_size.argtypes = [vp] + [C.POINTER(C.c_int64)] * 4 + [vp]
+    L.gmk_replay_sample.argtypes = [vp, C.c_int, C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.gmk_replay_draw_host.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, vp]
     _lib = L
     return L
 
@@ -413,6 +423,53 @@ def samples_from_packed(d_buf, n, d_offsets, d_sample_game, d_sample_move, n_sam
     """Device-pointer form of gmk_samples_from_packed (K4 + K5 on the wire form)."""
     _check(load().gmk_samples_from_packed(d_buf, int(n), d_offsets, d_sample_game, d_sample_move, int(n_samples), int(augment),
                                           d_states, d_values, d_pi, stream))
+
+
+# ---------------- replay buffer (device pointers; include/gomoku_hip.h) ----------------
+REPLAY_BAD_LENGTH, REPLAY_TOO_FEW = 1, 2      # the *d_status codes of replay append / sample
+
+
+def replay_draw_host(seed, step, population, batch):
+    """gmk_replay_draw_host: the population indices perm(0 .. batch-1) of the batch of (seed, step), int64[batch]; needs no GPU."""
+    out = np.zeros(int(batch) if batch > 0 else 0, dtype=np.int64)
+    _check(load().gmk_replay_draw_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), int(population), int(batch), out.ctypes.data))
+    return out
+
+
+class ReplayHandle:
+    """A gmk_replay handle: game records in HBM (ring of plies, ring of visit rows, ring of game descriptors); device pointers as ints."""
+
+    def __init__(self, capacity_plies, max_games, seed=DEFAULT_SEED):
+        init()
+        h = C.c_void_p()
+        _check(load().gmk_replay_create(int(capacity_plies), int(max_games), int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and load is not None:
+            load().gmk_replay_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def reset(self, stream=None):
+        _check(load().gmk_replay_reset(self.h, stream))
+
+    def append(self, d_moves, d_lens, d_winner, d_visits, n, first_move, d_status, stream=None):
+        _check(load().gmk_replay_append(self.h, d_moves, d_lens, d_winner, d_visits, int(n), int(first_move), d_status, stream))
+
+    def append_packed(self, d_buf, n, d_offsets, first_move, d_status, stream=None):
+        _check(load().gmk_replay_append_packed(self.h, d_buf, int(n), d_offsets, int(first_move), d_status, stream))
+
+    def size(self, stream=None):
+        """-> (games, stored plies, sampled plies, evicted games); synchronises `stream`."""
+        v = [C.c_int64() for _ in range(4)]
+        _check(load().gmk_replay_size(self.h, *[C.byref(x) for x in v], stream))
+        return tuple(x.value for x in v)
+
+    def sample(self, batch, step, augment, states_float, d_states, d_values, d_pi, d_picked, d_status, stream=None):
+        _check(load().gmk_replay_sample(self.h, int(batch), int(step), int(bool(augment)), int(bool(states_float)), d_states, d_values, d_pi,
+                                        d_picked, d_status, stream))
 
 
 # ---------------- K2: incrementally maintained evaluator states ----------------

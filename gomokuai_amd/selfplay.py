@@ -900,6 +900,116 @@ def samples_from_packed(buf, n, augment=False, first_move=0):
     return states, values, pi
 
 
+class ReplayBuffer:
+    """The trainer's side of self-play: DataHelper.buffer + DataHelper.generate_batch (network/data_helper.py:67-83, 97-139) in HBM
+    (gmk_replay_*, replay_kernel.hip).  It keeps game RECORDS -- a byte per stored ply, a 450-byte visit row per sampled ply -- and builds
+    the tuples of a minibatch when it is drawn: `batch_size` distinct samples per step (random.sample), a sample = one sampled ply under
+    one of the eight symmetries.  At most capacity_plies stored plies and max_games games are held; an append makes the oldest whole
+    games leave until the new ones fit (the reference trims before it extends and may overshoot; this capacity is an allocation).
+    extend / extend_packed / sample are asynchronous on the current stream of the buffer's device; len(), stats() and status() synchronise it."""
+
+    def __init__(self, capacity_plies, max_games=None, seed=G.DEFAULT_SEED, device=None):
+        capacity_plies = int(capacity_plies)
+        if capacity_plies < N:
+            raise ValueError("ReplayBuffer: capacity_plies must be at least 225 (one full game)")
+        if max_games is None:
+            max_games = max(1, capacity_plies // 8)          # (32 bytes per game: no game of self-play is shorter than nine plies)
+        max_games = int(max_games)
+        if not 1 <= max_games <= capacity_plies:
+            raise ValueError("ReplayBuffer: max_games must be in [1, capacity_plies]")
+        G.init(torch.cuda.current_device() if device is None else torch.device(device).index or 0)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.capacity_plies, self.max_games, self.seed = capacity_plies, max_games, int(seed)
+        self._h = G.ReplayHandle(capacity_plies, max_games, seed)
+        self._status = torch.zeros(2, dtype=torch.int32, device=self.device)      # [0] the last append's code, [1] the last draw's
+        self._step = 0
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            self._h.close()
+            self._h = None
+
+    def reset(self):
+        self._h.reset(_stream(self.device))
+
+    def extend(self, records, first_move=0):
+        """Appends the games of a GameRecords on this device (with visits).  Plies below first_move are kept for the positions after them
+        but are never drawn.  A length outside [0, 225] appends nothing and leaves lib.REPLAY_BAD_LENGTH in status()[0]."""
+        if records.visits is None:
+            raise ValueError("ReplayBuffer.extend: the records carry no visit counts")
+        if not 0 <= int(first_move) <= N:
+            raise ValueError("ReplayBuffer.extend: first_move must be in [0, 225]")
+        n = len(records)
+        if n == 0:
+            return
+        if not records.moves.is_cuda or records.moves.device != self.device:
+            raise ValueError("ReplayBuffer.extend: the records must be on %s" % (self.device,))
+        moves = records.moves.contiguous().view(torch.uint8)
+        lens = records.lens.to(torch.int32).contiguous()
+        winner = records.winner.to(torch.int8).contiguous()
+        visits = records.visits.contiguous()
+        assert moves.shape == (n, N) and winner.shape == (n,) and visits.shape == (n, N, N) and visits.element_size() == 2
+        self._h.append(moves.data_ptr(), lens.data_ptr(), winner.data_ptr(), visits.data_ptr(), n, first_move, self._status.data_ptr(),
+                       _stream(self.device))
+
+    def extend_packed(self, buf, n, first_move=0):
+        """Appends the n games of a wire-form block with visits (pack_records / pack_records_device; what a rank sends to gather_records)."""
+        if not 0 <= int(first_move) <= N:
+            raise ValueError("ReplayBuffer.extend_packed: first_move must be in [0, 225]")
+        n = int(n)
+        if n == 0:
+            return
+        if not buf.is_cuda or buf.device != self.device or buf.dtype != torch.uint8 or buf.numel() < 5 * n:
+            raise ValueError("ReplayBuffer.extend_packed: buf must be a uint8 tensor of at least 5 n bytes on %s" % (self.device,))
+        buf = buf.contiguous()
+        stream = _stream(self.device)
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        G.records_scan(buf.data_ptr(), n, offsets.data_ptr(), stream)
+        self._h.append_packed(buf.data_ptr(), n, offsets.data_ptr(), first_move, self._status[0:].data_ptr(), stream)
+
+    def sample(self, batch_size, step=None, augment=True, dtype=torch.float32, return_picked=False):
+        """-> (states [B,6,15,15] of `dtype` (torch.float32 or torch.uint8), values float32[B], pi float32[B,225][, picked int64[B,3] =
+        (game serial, ply, symmetry)]): the batch of (seed, step), B distinct samples; the same (seed, step) and contents give the same
+        batch.  step=None counts the draws of this object.  With fewer than B samples held nothing is written and status()[1] is
+        lib.REPLAY_TOO_FEW (the tensors are returned uninitialised): ask len() first, as batches() does."""
+        if dtype not in (torch.float32, torch.uint8):
+            raise ValueError("ReplayBuffer.sample: dtype must be torch.float32 or torch.uint8")
+        batch_size = int(batch_size)
+        if batch_size < 0:
+            raise ValueError("ReplayBuffer.sample: batch_size must not be negative")
+        if step is None:
+            step = self._step
+            self._step += 1
+        dev = self.device
+        states = torch.empty((batch_size, 6, 15, 15), dtype=dtype, device=dev)
+        values = torch.empty(batch_size, dtype=torch.float32, device=dev)
+        pi = torch.empty((batch_size, N), dtype=torch.float32, device=dev)
+        picked = torch.empty((batch_size, 3), dtype=torch.int64, device=dev) if return_picked else None
+        self._h.sample(batch_size, step, augment, dtype == torch.float32, states.data_ptr(), values.data_ptr(), pi.data_ptr(),
+                       None if picked is None else picked.data_ptr(), self._status[1:].data_ptr(), _stream(dev))
+        return (states, values, pi, picked) if return_picked else (states, values, pi)
+
+    def stats(self):
+        """{"games", "plies", "population" (sampled plies held), "evicted_games", "capacity_plies", "max_games"}; synchronises."""
+        games, plies, population, evicted = self._h.size(_stream(self.device))
+        return {"games": games, "plies": plies, "population": population, "evicted_games": evicted,
+                "capacity_plies": self.capacity_plies, "max_games": self.max_games}
+
+    def status(self):
+        """(code of the last append, code of the last draw): 0, lib.REPLAY_BAD_LENGTH, lib.REPLAY_TOO_FEW; synchronises."""
+        a, d = self._status.tolist()
+        return a, d
+
+    def __len__(self):
+        """The population of an augmented draw: 8 x the sampled plies held -- what len(DataHelper.buffer) counts."""
+        return 8 * self._h.size(_stream(self.device))[2]
+
+    def batches(self, batch_size):
+        """generate_batch (data_helper.py:133-139): yields augmented float32 minibatches while len(self) > batch_size."""
+        while len(self) > batch_size:
+            yield self.sample(batch_size)
+
+
 class GatherError(RuntimeError):
     """Raised on EVERY rank when any rank could not contribute to gather_records."""
 

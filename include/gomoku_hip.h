@@ -264,6 +264,61 @@ int gmk_samples_from_packed(const uint8_t *d_buf, int n, const int64_t *d_offset
                             const int32_t *d_sample_move, int n_samples, int augment, uint8_t *d_states, float *d_values,
                             float *d_pi, void *stream);
 
+/* ---- replay buffer: game records kept in HBM, training minibatches drawn from them ----
+ * Takes the place of DataHelper.buffer + DataHelper.generate_batch (network/data_helper.py:67-83, 97-139).  The handle keeps RECORDS, not
+ * tuples: one byte per stored ply, one 450-byte visit row per sampled ply, 32 bytes per game; a minibatch is built from them when it is
+ * drawn (K4 + K5 for one sample and one symmetry per wavefront; states, value and pi are the bits gmk_samples_from_records writes).
+ * Append and draw are asynchronous on `stream` and make no host round trip; only gmk_replay_size synchronises.  One handle serves one
+ * stream at a time.  The device memory comes from the library's block pool (gmk_pool_release) and is not cleared.
+ *
+ * Capacity and eviction.  The buffer holds at most capacity_plies stored plies and max_games games.  An append of n games gives them the
+ * serial numbers tail .. tail + n - 1 (tail = games appended since create / reset), then the oldest whole games leave until everything
+ * held fits both limits; if the n games alone exceed a limit, the oldest of THEM leave too (the buffer keeps the newest games that fit).
+ * The reference trims its list to maxlen BEFORE it extends it (data_helper.py:79-81), so its buffer may overshoot maxlen by one
+ * extension; here the capacity is an allocation, so it is hard: the trim comes with the append.
+ * first_move (per append): plies below it are stored -- the position before a later ply contains them -- but they are not in the
+ * population and carry no visit row; a game with len <= first_move adds nothing to the population.  A length outside [0, 225] sets
+ * *d_status = GMK_REPLAY_BAD_LENGTH and appends nothing (no byte of the buffer's state changes); otherwise *d_status = 0.
+ * gmk_replay_append reads the fixed-stride records of gmk_samples_from_records, gmk_replay_append_packed a wire block with visits and the
+ * d_offsets that gmk_records_scan made of its lens.  An append that brings more games than any before it (and more than
+ * min(max_games, 65536)) drains `stream` once and regrows a scratch row; no other append waits for the device.
+ *
+ * Population order.  P = sampled plies held.  Sampled ply s in [0, P), oldest first: the held games in serial order, within a game the
+ * plies first_move .. len - 1.  Without augmentation M = P and sample p is ply p, symmetry 0; with augmentation M = 8 P and sample p is
+ * ply p / 8 under symmetry a = p % 8 = 2 k + flip, the numbering of gmk_samples_from_records (np.rot90 k times, then np.fliplr if flip):
+ * the tuple is row 8 s + a of that call's augmented output.
+ *
+ * Draw rule.  Element i of the batch of (seed, step), 0 <= i < batch <= M, is sample perm(i); perm is a bijection of [0, M), so a
+ * batch holds distinct samples (random.sample, data_helper.py:137-139).  Let k be the integer with 4^(k-1) < M <= 4^k (k = 0 for M = 1)
+ * and mask = 2^k - 1.  E is a balanced Feistel network on 2k-bit numbers x:  L = x >> k, R = x & mask;  four rounds r = 0, 1, 2, 3 of
+ *       F = philox4x32_10(counter = {R, r, step & 0xFFFFFFFF, step >> 32}, key = {seed & 0xFFFFFFFF, seed >> 32}).v[0] & mask
+ *       (L, R) <- (R, L ^ F)
+ * then E(x) = (L << k) | R.  (philox4x32_10 is Philox4x32 with ten rounds, gomokuai_amd/csrc/philox.h; v[0] is its first output word;
+ * step is taken as an unsigned 64-bit number.)  perm(i) = E applied to i once, and again while the result is >= M (cycle walking).
+ * gmk_replay_draw_host evaluates perm(0 .. batch-1) on the host: it needs no GPU and no gmk_init, and no compute entry uses it.
+ *
+ * gmk_replay_sample writes the batch: d_states [B][6][225], uint8 (states_float = 0) or float32 0.0 / 1.0 (states_float != 0: what
+ * gmk_pvnet_forward and the PyTorch module take), d_values float[B], d_pi float[B][225], and, unless NULL, d_picked int64[B][3] =
+ * (game serial, ply, symmetry).  If M < batch, *d_status = GMK_REPLAY_TOO_FEW and no output byte is written; otherwise *d_status = 0.
+ * gmk_replay_size: games and stored plies held, population = P (sampled plies held, not multiplied by 8), evicted_games = games that have
+ * left or never fitted = the serial of the oldest game held; any of the four pointers may be NULL.  gmk_replay_reset empties the buffer
+ * (serials start at 0 again).  GMK_ERR_ARG: a NULL handle or pointer, a misaligned pointer (d_lens, d_buf, d_status and float outputs
+ * 4 bytes; d_offsets and d_picked 8; d_visits 2), n < 0, batch < 0, first_move outside [0, 225], capacity_plies outside [225, 2^40],
+ * max_games outside [1, capacity_plies]; in gmk_replay_draw_host also batch > population.  n = 0 and batch = 0 are no-ops. */
+enum { GMK_REPLAY_BAD_LENGTH = 1, GMK_REPLAY_TOO_FEW = 2 };
+typedef struct gmk_replay gmk_replay;
+int gmk_replay_create(int64_t capacity_plies, int64_t max_games, uint64_t seed, gmk_replay **out);
+int gmk_replay_destroy(gmk_replay *h);
+int gmk_replay_reset(gmk_replay *h, void *stream);
+int gmk_replay_append(gmk_replay *h, const uint8_t *d_moves, const int32_t *d_lens, const int8_t *d_winner, const uint16_t *d_visits,
+                      int n, int first_move, int32_t *d_status, void *stream);
+int gmk_replay_append_packed(gmk_replay *h, const uint8_t *d_buf, int n, const int64_t *d_offsets, int first_move, int32_t *d_status,
+                             void *stream);
+int gmk_replay_size(gmk_replay *h, int64_t *games, int64_t *plies, int64_t *population, int64_t *evicted_games, void *stream);
+int gmk_replay_sample(gmk_replay *h, int batch, int64_t step, int augment, int states_float, void *d_states, float *d_values, float *d_pi,
+                      int64_t *d_picked, int32_t *d_status, void *stream);
+int gmk_replay_draw_host(uint64_t seed, int64_t step, int64_t population, int64_t batch, int64_t *h_index);
+
 /* ---- K6: pattern-guided tree search, the reference's self-play supervisor ("traditional_mcts", config.py:9-12) ----
  * Replaces MCTS(policy = TraditionalPolicy(c_puct)) : core/lib/include/policies/Traditional.h:17-69 on top of
  * Heuristic (core/lib/include/algorithms/Heuristic.hpp:16-45, 94-200), RAVE::Select / BackPropogate<false>
