@@ -33,14 +33,14 @@
 //     v_alignbit of the line word with its '?' pads);
 //   * phase 5: the 3.6 KB score block leaves LDS transposed to [group][cell]: sixteen non-temporal dword stores of 256 contiguous bytes, in
 //     ADDRESS order (the two parts of a cache line that two pieces share reach the L2 back to back);
-//   * phase D, once per group, in the board iteration that is the wavefront's turn within its workgroup: the density planes of the
+//   * phase D, once per group, by the wavefront that is handed board 12 k of its workgroup's run for the run's k-th group: the density planes of the
 //     sixteen boards on the matrix cores -- Out[board, colour][cell] = Stone[board, colour][cell'] * W[cell'][cell], the stones as
 //     the A operand and the constant banded weight matrix (rows of a 6 KB table in LDS) as the B operand of
 //     v_mfma_i32_32x32x32_i8 (14 passes of 3-5 MFMAs, small integers: exact), stored as 2 x 128 contiguous bytes per instruction.  A group whose
 //     sixteen boards all exist (every group but the last of a launch whose board count is not a multiple of sixteen) stores without guards, one
 //     straight-line block per pass: per pair of stores three vector instructions (the occupied bit, two XORs) and two scalar ones (the board's
 //     block added to a 64-bit scalar base: global_store_dword offset, value, s[base]); the occupied bits come from 7 x 16 words the burst puts
-//     in LDS once (two 16-byte reads per pass).  The per-lane constants of the prologue are one 16-byte read of a table the host uploads once.
+//     in LDS once (two 16-byte reads per pass).  Everything the prologue reads is one image the host builds once: 23 KB staged 16 bytes per lane, 32 bytes of constants per lane, all loads issued at once.
 // HBM traffic per board: 64 B in, 7 248 B out (7 312 B algorithmic); everything else stays on chip.
 #include <algorithm>
 #include <cstdlib>
@@ -56,6 +56,10 @@ constexpr int kThreads = 64 * kBoardsPerBlock;
 constexpr int kCells = 225;
 constexpr int kQueueCap = 448;
 constexpr int kMaxBlocksPerCu = 1;
+constexpr int kBurstEvery = 12;                    // a workgroup's k-th density burst goes with board kBurstEvery * k of its run (<= kGroupBoards; measured: 16 -0.9 %, 14 -2.8 %,
+                                                  // 12 -3.3 % of the step against the bursts taken in turns, profiles/r09_k1_ab.txt)
+static_assert(kBurstEvery >= 1 && kBurstEvery <= kGroupBoards, "every burst of a run needs a board of the run to go with");
+[[maybe_unused]] constexpr int kTimelineSlots = 8;  // clock values per wavefront of the profiling flavour's timeline (the kernel says which)
 
 // per-board LDS region (32-bit words)
 constexpr int kScoreWords = 4 * kCells;          // 900, 16-byte aligned block.  In LDS the block is [cell][4 groups]: a colour's own and opponent view of a
@@ -78,17 +82,20 @@ constexpr int kMiscWords = 48;                   // [0] stones black | white << 
 constexpr int kBoardWords = kZeroWords + kLineWords + kQueueCap + kMiscWords;
 static_assert(kZeroWords % 4 == 0 && kBoardWords % 4 == 0, "16-byte alignment of the per-board blocks");
 constexpr int kStaticTableWords = 128 + kLineWords + 512 + 1560 + 4;   // lane jobs, the lines' '?' pads (phase 4), the bits-to-bytes table, the weight table of phase D,
-                                                                        // and the workgroup's two hand-out counters (boards, density bursts)
+                                                                        // and the workgroup's hand-out counter (four words: one used)
 
 // Lane -> line jobs.  A job word holds what the scan and the deposits need of a line, ready to use: bits 0..4 symbols in its stream
 // segment (len + 3: one leading and two trailing pads), 5..6 dir, 7..11 cell stride, 12..19 its first cell, 20..26 line word index.
-__constant__ uint32_t c_lane_jobs[64 * 2];
-__constant__ uint32_t c_line_init[kLineWords];   // all cells blank: (1 << 2 len) - 1
-// What else the kernel's prologue would derive from the lane number alone (upload_lane_jobs): [0] row * 4 and [1] column of the lane's cell in each of
-// the four passes over the board (cell = 64 pass + lane, the last one clamped to 224), a byte per pass; [2], [3] where the first cell of the lane's
-// two lines sits in its line word (bit 2 x0 for a diagonal, 2 y0 for an anti-diagonal, 0 for rows and columns)
-__constant__ uint4 c_lane_consts[64];
-constexpr int kScanSteps = 19;                    // symbols in the longest lane stream (upload_lane_jobs checks it)
+// Everything a launch reads besides the boards is ONE image in device memory that the host builds once (build_stage_image): first what every workgroup
+// stages in LDS, in LDS order and ready to use -- the automaton, the emission records, the lane jobs, the lines' '?' pads, the bits-to-bytes table, the
+// weight table of phase D, the hand-out counter's start value -- copied 16 bytes per lane; behind it a 32-byte record per lane with what the prologue
+// would otherwise derive from the lane number: its two jobs, its two all-blank line words ((1 << 2 len) - 1: words lane and 64 + lane), then [0] row * 4
+// and [1] column of the lane's cell in each of the four passes over the board (cell = 64 pass + lane, the last one clamped to 224), a byte per pass, and
+// [2], [3] where the first cell of the lane's two lines sits in its line word (bit 2 x0 for a diagonal, 2 y0 for an anti-diagonal, 0 for rows and columns).
+// Every load of the prologue is issued before the first of them is waited for: their latencies overlap.  (They used to be a dozen loops and
+// constant-memory reads, each waiting for its own load: a dozen memory latencies in a row at the head of every launch.)
+constexpr int kLaneRecordVecs = 2;
+constexpr int kScanSteps = 19;                    // symbols in the longest lane stream (lane_tables checks it)
 
 __device__ __forceinline__ int dir_stride(int dir) { return (0x0E100F01u >> (8 * dir)) & 0xFFu; }      // 1, 15, 16, 14: a shift, not three branches
 
@@ -296,8 +303,8 @@ __device__ __forceinline__ void density_tile_pass(const uint32_t (&own_rows)[8],
 // within a few microseconds by one wavefront they reach DRAM as whole cache lines, row after row.  (One pass per board iteration --
 // each line written in two pieces a board's work apart, each board's block in fourteen -- ran into the DRAM controller's write
 // credits: TCC_EA0_WRREQ 9.7 M per launch instead of 3.9 M for the scores alone, a fifth of them 32-byte pieces.)
-// The sixteen wavefronts of a workgroup take turns (the caller runs this in board iteration `wavefront number`), so that at any time
-// one wavefront per CU is storing planes while fifteen evaluate boards.
+// The bursts of a workgroup are spread over its run (the caller takes burst k with board kBurstEvery * k of the run), so that most of the time
+// one or two wavefronts per CU are storing planes while the others evaluate boards.
 // s_occ: 7 x 16 words of this wavefront's LDS that nothing else uses at this point (the caller passes its transition queue).
 template <bool kFull>
 __device__ __forceinline__ void density_planes_out(const uint16_t* __restrict__ planes, int n_boards, int first_board, int lane,
@@ -368,23 +375,31 @@ __device__ __forceinline__ void density_planes_out(const uint16_t* __restrict__ 
 }
 
 __global__ __launch_bounds__(kThreads)
-void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, int n_groups,
+void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, int groups_each, int groups_extra,
                            int32_t* __restrict__ out_scores, int32_t* __restrict__ out_density,
                            uint32_t* __restrict__ out_totals, int32_t* __restrict__ out_status,
-                           const uint32_t* __restrict__ g_trans, const uint32_t* __restrict__ g_records,
-                           int trans_words, int record_words, const uint32_t* __restrict__ g_wtab,
-                           int phase_mask_arg, unsigned long long* __restrict__ prof) {
+                           const uint4* __restrict__ g_stage, int stage_vecs, int trans_words, int record_words,
+                           int phase_mask_arg, unsigned long long* __restrict__ prof, unsigned long long* __restrict__ timeline) {
     // Profiling aids, -DGMK_PROFILE build only (the production build runs every phase and reads no clock): phase_mask bit p runs
     // phase p, bit 6 phase D (bit 8: its planes 1 KB apart, bit 9: passes without stores, bit 10: no passes; bit 11: no compounds =
     // phases 3b and 4 skipped; bit 12: consecutive groups to different workgroups), any mask but 0x7F sets the error bit of every
-    // board's status word; prof != nullptr: s_memtime cycles per phase, summed over the wavefronts.
+    // board's status word; prof != nullptr: s_memtime cycles per phase, summed over the wavefronts; timeline != nullptr: eight clock values per
+    // wavefront (kTimelineSlots, tools/k1_timeline.py), each written by lane 0 with an ordinary vector store.
 #ifdef GMK_PROFILE
+    // [0] entry, [1] end of the prologue, [2] arrival at the barrier, [3] leaving it, [4] end of the wavefront's last board, [5] exit,
+    // [6] density bursts taken in or behind the last board's iteration | boards done << 16, [7] the clocks those bursts took
+    unsigned long long* const tl_row = timeline ? timeline + (static_cast<size_t>(blockIdx.x) * kBoardsPerBlock + (threadIdx.x >> 6)) * kTimelineSlots : nullptr;
+#define GMK_TL(slot, value) do { if (tl_row && (threadIdx.x & 63) == 0) tl_row[slot] = (value); } while (0)
+    GMK_TL(0, __builtin_amdgcn_s_memtime());
+    unsigned long long tl_last_board = 0, tl_burst_clocks = 0;
+    int tl_bursts = 0;
     const int phase_mask = phase_mask_arg;
     unsigned long long t_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t_prev = __builtin_amdgcn_s_memtime();
 #define GMK_STAMP(k) do { if (prof) { const unsigned long long t_now_ = __builtin_amdgcn_s_memtime(); t_acc[k] += t_now_ - t_prev; t_prev = t_now_; } } while (0)
 #else
     constexpr int phase_mask = 0x7F;
-    (void)phase_mask_arg; (void)prof;
+    (void)phase_mask_arg; (void)prof; (void)timeline;
+#define GMK_TL(slot, value) do { } while (0)
 #ifdef GMK_K1_MARKERS
 #define GMK_STAMP(k) asm volatile("; gmk_mark " #k)      // (tools/k1_frame_counts.py counts the assembly between two marks)
 #else
@@ -396,20 +411,18 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
     const uint4* s_rec = reinterpret_cast<const uint4*>(lds + trans_words);
     uint32_t* s_jobs = lds + trans_words + record_words;
 
-    for (int i = threadIdx.x; i < trans_words; i += kThreads) lds[i] = g_trans[i];
-    for (int i = threadIdx.x; i < record_words; i += kThreads) lds[trans_words + i] = g_records[i];
-    if (threadIdx.x < 128) s_jobs[threadIdx.x] = c_lane_jobs[threadIdx.x];
-    // a line word's '?' pads: symbol 2 in every 2-bit slot of the word that is not one of the line's cells (phase 4 ORs them in: its
-    // window then reads '?' off the line wherever the line starts in its word)
-    uint32_t* s_pads = s_jobs + 128;
-    if (threadIdx.x < kLineWords) s_pads[threadIdx.x] = ~c_line_init[threadIdx.x] & 0xAAAAAAAAu;
+    // the loads of the prologue, all of them in front of their first use: the staged image (two pieces of 16 bytes per lane cover 32 KB; the
+    // automaton's image is 23 KB) and this lane's record
+    const int tid = threadIdx.x;
+    const uint4 stage_a = g_stage[min(tid, stage_vecs - 1)], stage_b = g_stage[min(tid + kThreads, stage_vecs - 1)];
+    const uint4* lane_record = g_stage + stage_vecs + kLaneRecordVecs * (tid & 63);
+    const uint4 lane_lines = lane_record[0], lane_consts = lane_record[1];
+    uint32_t* s_pads = s_jobs + 128;                                         // a line word's '?' pads: symbol 2 in every 2-bit slot of the word that is not one of the
+                                                                             // line's cells (phase 4 ORs them in: its window then reads '?' off the line wherever the line starts in its word)
     uint2* s_lut = reinterpret_cast<uint2*>(s_jobs + 128 + kLineWords);      // byte -> its eight bits as bytes (the stone operands of phase D)
-    if (threadIdx.x < 256) s_lut[threadIdx.x] = make_uint2(((threadIdx.x & 15u) * 0x204081u) & 0x01010101u, ((threadIdx.x >> 4) * 0x204081u) & 0x01010101u);
     uint32_t* s_wtab_words = s_jobs + 128 + kLineWords + 512;
-    for (int i = threadIdx.x; i < kWtabWords; i += kThreads) s_wtab_words[i] = g_wtab[i];
     const v4i* s_wtab = reinterpret_cast<const v4i*>(s_wtab_words);
-    uint32_t* s_handout = s_wtab_words + kWtabWords;        // [0] boards handed out, [1] density bursts handed out
-    if (threadIdx.x < 4) s_handout[threadIdx.x] = threadIdx.x == 0 ? 2u * kBoardsPerBlock : 0u;      // (every wavefront's first two boards are its own: see below)
+    uint32_t* s_handout = s_wtab_words + kWtabWords;        // [0] boards handed out: starts at 2 x kBoardsPerBlock (every wavefront's first two boards are its own: see below)
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane0 = threadIdx.x & 63;
     uint32_t* s_scores = lds + trans_words + record_words + kStaticTableWords + wave * kBoardWords;      // int32 scores, accumulated with ds_add
@@ -427,14 +440,12 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
     // barrier of the kernel stands in front of that board's phase 1)
     GMK_STAMP(0);
 
-    // ---- work distribution: see the hand-out counters below ----
+    // ---- work distribution: see the hand-out counter below ----
     const bool planes_out = out_density != nullptr && (phase_mask & 64) && !(phase_mask & 1024);
     int lane = lane0;
-    // (from constant memory, not from their staged copies: those are not there yet)
-    const uint32_t job_a = c_lane_jobs[lane * 2], job_b = c_lane_jobs[lane * 2 + 1];
-    const uint32_t line_init_lo = c_line_init[lane], line_init_hi = c_line_init[min(64 + lane, kLineWords - 1)];
-    // (one 16-byte read instead of ~100 vector instructions of multiply-shift divisions in every wavefront of every launch)
-    const uint4 lane_consts = c_lane_consts[lane];
+    // (from the lane's record, not from the staged copies: those are not there yet)
+    const uint32_t job_a = lane_lines.x, job_b = lane_lines.y;
+    const uint32_t line_init_lo = lane_lines.z, line_init_hi = lane_lines.w;
     const uint32_t cell_row4 = lane_consts.x, cell_col = lane_consts.y, norm_a = lane_consts.z, norm_b = lane_consts.w;
     uint32_t* s_rows = s_misc + 16;                      // row y at [3 + y]
     // a board's 64 B are fetched while the board before it is evaluated.  No branch around the loads (every lane reads some valid
@@ -452,24 +463,35 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
     // The workgroup owns one contiguous run of groups (what a CU writes at any time lies within a few hundred kilobytes) and hands its
     // boards out one at a time from a counter in LDS: the sixteen wavefronts -- four per SIMD, and a SIMD's vector unit is what the kernel
     // is bound by -- finish within one board of each other instead of 16 boards x (the spread of a board's work, ~ +-25 %) apart.
-    // The density bursts of its groups are handed out the same way, one per wavefront and sixteen boards, wavefront w in its w-th board.
+    // The density bursts of its groups go with boards of the run that are fixed in advance (phase D below).
     // (Round 2 measured a dynamic hand-out -- chunks of four, stealing round a ring of workgroups -- as no gain and concluded the wavefronts'
     // waits were the limit.  They are not: tools/valu_probe.hip shows a wave-instruction costs a SIMD 4 cycles whatever its type, K1's ~950
     // per board make the vector unit ~90 % busy while all sixteen wavefronts run, and what the static hand-out lost was whole SIMDs idling
     // behind the slowest one: 0.1544 -> 0.1402 ms.)
-    const int wg_g0 = static_cast<int>(static_cast<long long>(n_groups) * blockIdx.x / gridDim.x);
-    const int wg_groups = static_cast<int>(static_cast<long long>(n_groups) * (blockIdx.x + 1) / gridDim.x) - wg_g0;
+    // (groups_each = groups / grid and groups_extra = groups % grid come from the host: the first groups_extra workgroups own one group more.  Worked
+    // out here as floor(groups * block / grid) it was two 64-bit divisions, ~200 scalar instructions per wavefront and launch.)
+    const int wg_block = static_cast<int>(blockIdx.x);
+    const int wg_g0 = groups_each * wg_block + min(wg_block, groups_extra);
+    const int wg_groups = groups_each + (wg_block < groups_extra ? 1 : 0);
     const int wg_first = wg_g0 * kGroupBoards, wg_boards = min(wg_groups * kGroupBoards, n_boards - wg_first);
-    auto hand_out = [&](int which) -> int {
+    auto hand_out = [&]() -> int {
         uint32_t v = 0;
-        if (lane0 == 0) v = atomicAdd(&s_handout[which], 1u);
+        if (lane0 == 0) v = atomicAdd(s_handout, 1u);
         return __builtin_amdgcn_readfirstlane(static_cast<int>(v));
     };
     // A wavefront's first two boards are fixed (boards w and 16 + w of the workgroup's run; the counter starts behind them): the first dynamic hand-out
     // then comes after the kernel's one barrier.
     int idx = wave, boards_done = 0;
     if (idx < wg_boards) fetch_row(wg_first + idx);
+    // the image goes to LDS (address 0 on) once every load of the prologue is on its way
+    {
+        uint4* s_stage = reinterpret_cast<uint4*>(lds);
+        if (tid < stage_vecs) s_stage[tid] = stage_a;
+        if (tid + kThreads < stage_vecs) s_stage[tid + kThreads] = stage_b;
+        for (int i = tid + 2 * kThreads; i < stage_vecs; i += kThreads) s_stage[i] = g_stage[i];
+    }
     asm volatile("" : "+v"(next_black), "+v"(next_white));        // (once: wait for them here)
+    GMK_TL(1, __builtin_amdgcn_s_memtime());
 #pragma unroll 1
     for (;;) {
 #ifdef GMK_K1_MARKERS
@@ -479,7 +501,7 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
         const int board = wg_first + idx;
         cur_black = next_black; cur_white = next_white;
         int idx_next = idx;
-        if (live) { idx_next = boards_done == 0 ? kBoardsPerBlock + wave : hand_out(0); fetch_row(wg_first + min(idx_next, wg_boards - 1)); }
+        if (live) { idx_next = boards_done == 0 ? kBoardsPerBlock + wave : hand_out(); fetch_row(wg_first + min(idx_next, wg_boards - 1)); }
         GMK_STAMP(11);
 
         if (live) {
@@ -570,8 +592,15 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
             wave_phase_fence();
             GMK_STAMP(1);
         }
+#ifdef GMK_PROFILE
+        if (boards_done == 0) GMK_TL(2, __builtin_amdgcn_s_memtime());
+#endif
         if (boards_done == 0) __syncthreads();                  // the tables are staged (the automaton at LDS address 0, the records, jobs, the tables of phase D,
-                                                                // the hand-out counters): from here on the wavefronts never wait for each other
+                                                                // the hand-out counter): from here on the wavefronts never wait for each other
+#ifdef GMK_PROFILE
+        if (boards_done == 0) GMK_TL(3, __builtin_amdgcn_s_memtime());
+        if (live) { tl_bursts = 0; tl_burst_clocks = 0; }
+#endif
         if (live) {
             // ---- phase 1: walk the DFA along this lane's lines; transitions that emit go to the queue ----
             // The lane's one or two lines become ONE stream of 2-bit DFA symbols:
@@ -848,23 +877,29 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
         asm volatile("" : "+v"(next_black), "+v"(next_white));    // the wait for the next board's planes (a use the compiler must honour)
         GMK_STAMP(7);
 
-        // ---- phase D: density planes of the workgroup's groups: one burst in this wavefront's turn (its w-th board of every sixteen),
-        //      and whatever is left once the boards have run out ----
-        if (planes_out && (!live || (boards_done & 15) == wave)) {
-            for (;;) {
-                const int burst = hand_out(1);
-                if (burst >= wg_groups) break;
-                int lane_p = lane0, first_p = (wg_g0 + burst) * kGroupBoards;      // opaque copies: what the passes derive from them is computed here
-                asm volatile("" : "+v"(lane_p), "+s"(first_p));
-                const int plane_stride = (phase_mask & 512) ? 0 : (phase_mask & 256) ? 256 : kCells;
-                // (the queue is free here: phase 4 has read it, the next board's phase 0 fills it again)
-                if (first_p + kGroupBoards <= n_boards && plane_stride > 0) density_planes_out<true>(planes, n_boards, first_p, lane_p, s_wtab, s_queue, out_density, s_lut, plane_stride);
-                else density_planes_out<false>(planes, n_boards, first_p, lane_p, s_wtab, s_queue, out_density, s_lut, plane_stride);
-                GMK_STAMP(8);
-                if (live) break;
-            }
-        }
+        // ---- phase D: density planes of the workgroup's groups.  The burst of the run's k-th group belongs to the run's board kBurstEvery * k: whichever
+        //      wavefront is handed that board takes the burst with it.  Every board is handed out once, so every burst is taken once, without a counter;
+        //      a run of G groups has more than 16 (G - 1) >= kBurstEvery (G - 1) boards, so every burst has its board.  On a run of sixteen groups the last
+        //      burst starts 76 boards -- almost five board times, a burst takes one and a half -- before the run's end: no wavefront is left with a burst
+        //      when the boards have run out.  (Taken in turns, wavefront w in its w-th board, two bursts per workgroup were left for the end, and each
+        //      held the launch's end back.)  A burst reads the boards' planes and nothing of their evaluation: it may run ahead of its group's boards. ----
         if (!live) break;
+        const int burst = idx / kBurstEvery;
+        if (planes_out && burst * kBurstEvery == idx && burst < wg_groups) {
+#ifdef GMK_PROFILE
+            const unsigned long long tl_burst_from = __builtin_amdgcn_s_memtime();
+#endif
+            int lane_p = lane0, first_p = (wg_g0 + burst) * kGroupBoards;      // opaque copies: what the passes derive from them is computed here
+            asm volatile("" : "+v"(lane_p), "+s"(first_p));
+            const int plane_stride = (phase_mask & 512) ? 0 : (phase_mask & 256) ? 256 : kCells;
+            // (the queue is free here: phase 4 has read it, the next board's phase 0 fills it again)
+            if (first_p + kGroupBoards <= n_boards && plane_stride > 0) density_planes_out<true>(planes, n_boards, first_p, lane_p, s_wtab, s_queue, out_density, s_lut, plane_stride);
+            else density_planes_out<false>(planes, n_boards, first_p, lane_p, s_wtab, s_queue, out_density, s_lut, plane_stride);
+            GMK_STAMP(8);
+#ifdef GMK_PROFILE
+            ++tl_bursts; tl_burst_clocks += __builtin_amdgcn_s_memtime() - tl_burst_from;
+#endif
+        }
         // ---- phase 5: results leave LDS ----
 #ifdef GMK_K1_MARKERS
         GMK_STAMP(12);
@@ -919,9 +954,16 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
         }
         wave_phase_fence();
         GMK_STAMP(9);
+#ifdef GMK_PROFILE
+        tl_last_board = __builtin_amdgcn_s_memtime();
+#endif
         idx = idx_next; ++boards_done;
     }
 #ifdef GMK_PROFILE
+    GMK_TL(4, tl_last_board);
+    GMK_TL(6, static_cast<unsigned long long>(tl_bursts) | static_cast<unsigned long long>(boards_done) << 16);
+    GMK_TL(7, tl_burst_clocks);
+    GMK_TL(5, __builtin_amdgcn_s_memtime());
     // [0] table staging, [1] phase 0, [2] scan, [3] deposits, [4] phase 3, [5] phase 3b, [6] rescans, [7] wait for the next planes,
     // [8] phase D, [9] phase 5, [11] loop head; [15] wavefronts
     if (prof && lane0 == 0) {
@@ -930,12 +972,14 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
     }
 #endif
 #undef GMK_STAMP
+#undef GMK_TL
 }
 
 // ---- host side ----
 struct LineJob { int len, x0, y0, dir; };
 
-int upload_lane_jobs() {
+// The lane jobs and '?' pads as they lie in LDS (jobs_out: 128 words, pads_out: kLineWords) and the 64 lane records (records_out: 8 words each).
+int lane_tables(uint32_t* jobs_out, uint32_t* pads_out, uint32_t* records_out) {
     std::vector<LineJob> lines;
     for (int i = 0; i < 15; ++i) lines.push_back({15, 0, i, 0});
     for (int i = 0; i < 15; ++i) lines.push_back({15, i, 0, 1});
@@ -976,17 +1020,21 @@ int upload_lane_jobs() {
             consts[lane][2 + k] = dir == 2u ? 2u * (first % 15u) : dir == 3u ? 2u * (first / 15u) : 0u;
         }
     }
-    GMK_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_lane_consts), consts, sizeof consts));
-    GMK_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_line_init), init, sizeof init));
-    GMK_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_lane_jobs), jobs, sizeof jobs));
+    for (int i = 0; i < 128; ++i) jobs_out[i] = jobs[i];
+    for (int i = 0; i < kLineWords; ++i) pads_out[i] = ~init[i] & 0xAAAAAAAAu;
+    for (int lane = 0; lane < 64; ++lane) {
+        uint32_t* r = records_out + 8 * lane;
+        r[0] = jobs[lane * 2]; r[1] = jobs[lane * 2 + 1];
+        r[2] = init[lane]; r[3] = init[std::min(64 + lane, kLineWords - 1)];
+        for (int k = 0; k < 4; ++k) r[4 + k] = consts[lane][k];
+    }
     if (steps != kScanSteps) { gmk::set_error("lane jobs: %d scan steps, the kernel is built for %d", steps, kScanSteps); return GMK_ERR_STATE; }
     return GMK_OK;
 }
 
 // The weight table of phase D (kWtab*): [plane kind: count, weight][dy + 6][xo] x 16 bytes, byte j = the tap from column j of a row
 // dy below the cell's to a cell in column xo: BlockWeights (Pattern.cpp:598-609) at (dy, j - xo), its non-zero mask for the count planes.
-int upload_density_weights(uint32_t** d_out) {
-    std::vector<int8_t> t(static_cast<size_t>(kWtabWords) * 4, 0);
+int density_weights(int8_t* t /* kWtabWords * 4 bytes, zeroed */) {
     for (int kind = 0; kind < 2; ++kind)
         for (int dy = -3; dy <= 3; ++dy)
             for (int xo = 0; xo < 15; ++xo)
@@ -1009,23 +1057,48 @@ int upload_density_weights(uint32_t** d_out) {
             if (y < 0 || y > 14) continue;
             if (y / 2 < dens_kt_lo(m) || y / 2 > dens_kt_hi(m)) { gmk::set_error("density weight table: row %d of cell %d is not covered", y, cell); return GMK_ERR_STATE; }
         }
-    GMK_HIP_CHECK(hipMalloc(d_out, t.size()));
-    GMK_HIP_CHECK(hipMemcpy(*d_out, t.data(), t.size(), hipMemcpyHostToDevice));
     return GMK_OK;
 }
 
-struct Launch { int grid, n_groups; size_t lds; };
+// The image of the kernel's tables (see kLaneRecordVecs): [automaton][records][lane jobs 128][pads][bits-to-bytes 512][weights][hand-out 4], then the lane
+// records.  Built once; the automaton and the records are copied from the device state's tables.
+int build_stage_image(const gmk::DeviceState& st, uint4** d_out, int* stage_vecs) {
+    const size_t trans_words = static_cast<size_t>(st.n_states) * 4, record_words = static_cast<size_t>(st.n_records) * 4;
+    std::vector<uint32_t> rest(kStaticTableWords + 64 * 4 * kLaneRecordVecs, 0u);
+    uint32_t* jobs = rest.data(), *pads = jobs + 128, *lut = pads + kLineWords, *wtab = lut + 512, *handout = wtab + kWtabWords, *records = handout + 4;
+    int rc = lane_tables(jobs, pads, records);
+    if (rc != GMK_OK) return rc;
+    for (uint32_t b = 0; b < 256; ++b) { lut[2 * b] = ((b & 15u) * 0x204081u) & 0x01010101u; lut[2 * b + 1] = ((b >> 4) * 0x204081u) & 0x01010101u; }
+    rc = density_weights(reinterpret_cast<int8_t*>(wtab));
+    if (rc != GMK_OK) return rc;
+    handout[0] = 2u * kBoardsPerBlock;
+    const size_t staged_words = trans_words + record_words + kStaticTableWords;
+    if (staged_words % 4 != 0) { gmk::set_error("K1 tables: %zu staged words are not whole 16-byte pieces", staged_words); return GMK_ERR_STATE; }
+    uint32_t* d = nullptr;
+    GMK_HIP_CHECK(hipMalloc(&d, (trans_words + record_words + rest.size()) * sizeof(uint32_t)));
+    GMK_HIP_CHECK(hipMemcpy(d, st.d_trans, trans_words * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+    GMK_HIP_CHECK(hipMemcpy(d + trans_words, st.d_records, record_words * sizeof(uint32_t), hipMemcpyDeviceToDevice));
+    GMK_HIP_CHECK(hipMemcpy(d + trans_words + record_words, rest.data(), rest.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    *d_out = reinterpret_cast<uint4*>(d);
+    *stage_vecs = static_cast<int>(staged_words / 4);
+    return GMK_OK;
+}
+
+struct Launch { int grid, n_groups, groups_each, groups_extra; size_t lds; };
 
 Launch plan_launch(int n, const gmk::DeviceState& st) {
     Launch l;
     l.n_groups = (n + kGroupBoards - 1) / kGroupBoards;
     l.grid = std::max(1, std::min(l.n_groups, st.cu_count * kMaxBlocksPerCu));
+    l.groups_each = l.n_groups / l.grid;                      // a workgroup's run: groups_each groups, one more in the first groups_extra workgroups
+    l.groups_extra = l.n_groups % l.grid;
     l.lds = static_cast<size_t>(kBoardsPerBlock * kBoardWords + st.n_states * 4 + st.n_records * 4 + kStaticTableWords) * 4;
     return l;
 }
 
 bool g_jobs_uploaded = false;
-uint32_t* g_wtab = nullptr;
+uint4* g_stage = nullptr;
+int g_stage_vecs = 0;
 }  // namespace
 
 extern "C" int gmk_eval_batch(const uint16_t* d_planes, int n, int32_t* d_scores, int32_t* d_density,
@@ -1035,9 +1108,7 @@ extern "C" int gmk_eval_batch(const uint16_t* d_planes, int n, int32_t* d_scores
     if (n < 0 || (n > 0 && !d_planes)) { gmk::set_error("gmk_eval_batch: bad arguments"); return GMK_ERR_ARG; }
     if (n == 0) return GMK_OK;
     if (!g_jobs_uploaded) {
-        int rc = upload_lane_jobs();
-        if (rc != GMK_OK) return rc;
-        rc = upload_density_weights(&g_wtab);
+        const int rc = build_stage_image(st, &g_stage, &g_stage_vecs);
         if (rc != GMK_OK) return rc;
         GMK_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(eval_positions_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         g_jobs_uploaded = true;
@@ -1051,10 +1122,35 @@ extern "C" int gmk_eval_batch(const uint16_t* d_planes, int n, int32_t* d_scores
         GMK_HIP_CHECK(hipMalloc(&d_prof, 16 * sizeof(unsigned long long)));
         GMK_HIP_CHECK(hipMemset(d_prof, 0, 16 * sizeof(unsigned long long)));
     }
+    // (profile build only) GMK_EVAL_TIMELINE=<file>: every launch leaves its wavefronts' clock values there (tools/k1_timeline.py reads them)
+    static const char* const timeline_path = gmk::profile_env("GMK_EVAL_TIMELINE");
+    unsigned long long* d_timeline = nullptr;
+    const size_t timeline_words = static_cast<size_t>(l.grid) * kBoardsPerBlock * kTimelineSlots;
+    hipEvent_t tl_from = nullptr, tl_to = nullptr;
+    if (timeline_path) {
+        GMK_HIP_CHECK(hipMalloc(&d_timeline, timeline_words * sizeof(unsigned long long)));
+        GMK_HIP_CHECK(hipMemset(d_timeline, 0, timeline_words * sizeof(unsigned long long)));
+        GMK_HIP_CHECK(hipEventCreate(&tl_from));
+        GMK_HIP_CHECK(hipEventCreate(&tl_to));
+        GMK_HIP_CHECK(hipDeviceSynchronize());
+        GMK_HIP_CHECK(hipEventRecord(tl_from, static_cast<hipStream_t>(stream)));
+    }
     hipLaunchKernelGGL(eval_positions_kernel, dim3(l.grid), dim3(kThreads), l.lds, static_cast<hipStream_t>(stream),
-                       d_planes, n, l.n_groups, d_scores, d_density, d_totals, d_status,
-                       st.d_trans, st.d_records, st.n_states * 4, st.n_records * 4, g_wtab, phase_mask, d_prof);
+                       d_planes, n, l.groups_each, l.groups_extra, d_scores, d_density, d_totals, d_status,
+                       g_stage, g_stage_vecs, st.n_states * 4, st.n_records * 4, phase_mask, d_prof, d_timeline);
     GMK_HIP_CHECK(hipGetLastError());
+    if (timeline_path) {
+        // the file: grid, wavefronts per workgroup, slots per wavefront, the launch's time between two events in nanoseconds; then the slots
+        GMK_HIP_CHECK(hipEventRecord(tl_to, static_cast<hipStream_t>(stream)));
+        GMK_HIP_CHECK(hipEventSynchronize(tl_to));
+        float wall_ms = 0.f;
+        GMK_HIP_CHECK(hipEventElapsedTime(&wall_ms, tl_from, tl_to));
+        std::vector<unsigned long long> h(4 + timeline_words);
+        h[0] = static_cast<unsigned long long>(l.grid); h[1] = kBoardsPerBlock; h[2] = kTimelineSlots; h[3] = static_cast<unsigned long long>(wall_ms * 1e6);
+        GMK_HIP_CHECK(hipMemcpy(h.data() + 4, d_timeline, timeline_words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        (void)hipFree(d_timeline); (void)hipEventDestroy(tl_from); (void)hipEventDestroy(tl_to);
+        if (std::FILE* f = std::fopen(timeline_path, "wb")) { std::fwrite(h.data(), sizeof(unsigned long long), h.size(), f); std::fclose(f); }
+    }
     if (stamps) {                                               // (profile build only) cycles per phase and board, mean over the wavefronts
         unsigned long long h[16];
         GMK_HIP_CHECK(hipDeviceSynchronize());

@@ -2,14 +2,14 @@
 """K1's frame, static instruction counts (a recipe, not a test: they move with the compiler): compiles eval_kernel.hip as the production
 build does plus -DGMK_K1_MARKERS, which turns every GMK_STAMP(k) of the board loop into an assembly comment `; gmk_mark k`, and counts the
 vector, scalar, LDS and global-memory instructions in the text from a mark to the next mark (or the kernel's end); two more marks exist in
-this build only: 10 at the top of the board loop, 12 in front of phase 5.  A region is named by what the source holds behind its opening
+this build only: 10 at the top of the board loop, 12 in front of phase 5; what lies between the kernel's entry and mark 0 is counted as region -1.  A region is named by what the source holds behind its opening
 mark.  The text is counted as it lies: a block the compiler moved out of line counts where it was put (the density bursts lie behind
 mark 8, phase 5 behind them), and a loop's body counts once, so the figures are good for the straight-line frame regions (loop head,
 phase 0 with ONE pass of its stone loop, phase 5) and for comparing two builds of the same source, not as per-board dynamic counts.  A mark is a scheduling barrier, so the marked build is not the production one instruction for instruction.
 usage: k1_frame_counts.py [file.s | file.hip] ...   (default: gomokuai_amd/csrc/eval_kernel.hip; needs hipcc for a .hip)"""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {0: "prologue", 9: "loop tail", 10: "loop head", 11: "phase 0", 1: "scan", 2: "deposits", 3: "phase 3", 4: "phase 3b", 5: "rescans", 6: "planes wait", 7: "burst hand-out",
+NAMES = {-1: "entry, staging", 0: "prologue", 9: "loop tail", 10: "loop head", 11: "phase 0", 1: "scan", 2: "deposits", 3: "phase 3", 4: "phase 3b", 5: "rescans", 6: "planes wait", 7: "burst hand-out",
          8: "phase D bursts", 12: "phase 5"}
 FRAME = (10, 11, 12)
 
@@ -44,6 +44,10 @@ def report(src):
         print("%s %s" % (key, m.group(1) if m else "?"))
     order, cur = [], None
     for line in (l.strip() for l in text.splitlines()):
+        if re.match(r"^_Z\w*eval_positions_kernel\w*:", line):         # the kernel's entry: what lies in front of mark 0 (the tables' staging)
+            cur = {"valu": 0, "salu": 0, "lds": 0, "vmem": 0, "lanes": 0, "opens": -1}
+            order.append(cur)
+            continue
         m = re.match(r"^; gmk_mark (\d+)", line)
         if m:
             cur = {"valu": 0, "salu": 0, "lds": 0, "vmem": 0, "lanes": 0, "opens": int(m.group(1))}
