@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "capi_common.h"
+#include "pvnet_pack.h"
 
 namespace {
 
@@ -58,9 +59,7 @@ __device__ __forceinline__ int padded_index(int p) { return (p / 15 + 1) * 17 + 
 // row of the 32 x 32 C/D tile that register r of this lane holds (cdna_hip_programming.md, fragment layout)
 __device__ __forceinline__ int cd_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
-// The order in which a layer's k-pairs are walked (and packed): chunks of 2 * CP input channels; inside a chunk the nine taps; inside a tap
-// ("step") the chunk's CP channel pairs.
-__host__ __device__ inline void step_chunk_tap(int step, int& chunk, int& tap) { chunk = step / 9; tap = step - 9 * chunk; }
+// (the order in which a layer's k-pairs are walked and packed: pvnet_pack.h, step_chunk_tap)
 
 // One convolution layer for NP pixel tiles and one tile of 32 output channels: acc[t] += W^T * Act over all k-pairs (in pack_layer()'s order).
 // `in` points at the layer's input activations in LDS, base[t] is this lane's byte offset for tile t:
@@ -564,37 +563,13 @@ void pvnet_dense_kernel(DenseParams prm) {
     }
 }
 
-// A operands of one layer in lane order, four consecutive k-pairs of a lane side by side: [cout tile][k-pair / 4][64 lanes][4]; k-pair order as
-// conv_tiles() walks it (layer 1's 27 k-pairs: seven groups, the last one padded)
-void pack_layer(const float* w /* [cout][cin][3][3] */, int cin, int cout, std::vector<float>& out) {
-    const int CP = cin >= 16 ? 8 : cin / 2, chunks = cin / 2 / CP, steps = chunks * 9, kps = steps * CP, groups = (kps + 3) / 4;
-    out.assign((static_cast<size_t>(cout / 32) * groups + 2 * CP / 4 + 1) * 256, 0.0f);      // + the two steps conv_tiles() fetches past the last tile's end
-    for (int tile = 0; tile < cout / 32; ++tile)
-        for (int step = 0; step < steps; ++step) {
-            int chunk, tap;
-            step_chunk_tap(step, chunk, tap);
-            for (int cp = 0; cp < CP; ++cp) {
-                const int kp = step * CP + cp;
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int co = tile * 32 + (lane & 31), ci = chunk * 2 * CP + 2 * cp + (lane >> 5);
-                    out[((static_cast<size_t>(tile) * groups + kp / 4) * 64 + lane) * 4 + (kp & 3)] = w[(static_cast<size_t>(co) * cin + ci) * 9 + tap];
-                }
-            }
-        }
-}
+// The packers of the weights (pack_layer, pack_heads, pack_bias, pack_dense) and the handle live in pvnet_pack.h: the trainer derives its repack
+// table from the same functions.
+using gmk::pvpack::pack_layer;
+static_assert(gmk::pvpack::kPix == kPix && gmk::pvpack::kHeadRows == kHeadRows && gmk::pvpack::kDenseBody == kDenseBody &&
+              gmk::pvpack::kDenseBodies == kDenseBodies && gmk::pvpack::kPolicySteps == kPolicySteps, "pvnet_pack.h packs for these kernels");
 
 }  // namespace
-
-struct gmk_pvnet {
-    float *d_w1 = nullptr, *d_w2 = nullptr, *d_w3 = nullptr, *d_wh = nullptr, *d_b = nullptr;
-    bool attr_set = false;
-    // the dense layers (gmk_pvnet_set_dense): packed weights, biases (policy [256] | hidden [64] | output weights [64]), the output bias, and the
-    // head activations between the two kernels of gmk_pvnet_evaluate ([capacity][900 + 450], grown on demand)
-    float *d_wp = nullptr, *d_dense = nullptr, *d_flat = nullptr;
-    float b_out = 0.0f;
-    bool has_dense = false, dense_attr_set = false;
-    int flat_capacity = 0;
-};
 
 extern "C" int gmk_pvnet_destroy(gmk_pvnet* net) {
     if (!net) return GMK_OK;
@@ -609,22 +584,12 @@ extern "C" int gmk_pvnet_create(const float* w1, const float* b1, const float* w
     gmk::DeviceState& st = gmk::device_state();
     if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
     if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !wp || !bp || !wv || !bv || !out) { gmk::set_error("gmk_pvnet_create: bad arguments"); return GMK_ERR_ARG; }
-    std::vector<float> p1, p2, p3, ph(4 * 32 * 64 + 4 * kHeadRows * 32, 0.0f), bias(32 + 64 + 128 + 8, 0.0f);
+    std::vector<float> p1, p2, p3, ph, bias;
     pack_layer(w1, 6, 32, p1);
     pack_layer(w2, 32, 64, p2);
     pack_layer(w3, 64, 128, p3);
-    for (int wave = 0; wave < 4; ++wave)                         // 4x4x1 A operands: lane l carries row l % 4 of its block, for the channel that accumulator
-        for (int r = 0; r < 16; ++r)                             // register r of wave `wave` holds on that lane half
-            for (int lane = 0; lane < 64; ++lane) {
-                const int c = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), j = lane & 3;
-                ph[(wave * 32 + r) * 64 + lane] = wp[j * 128 + c];
-                ph[(wave * 32 + 16 + r) * 64 + lane] = j < 2 ? wv[j * 128 + c] : 0.0f;
-            }
-    for (int wave = 0; wave < 4; ++wave)                         // ... and per channel for the corner pixel
-        for (int j = 0; j < kHeadRows; ++j)
-            for (int c = 0; c < 32; ++c) ph[4 * 32 * 64 + (wave * kHeadRows + j) * 32 + c] = j < 4 ? wp[j * 128 + 32 * wave + c] : wv[(j - 4) * 128 + 32 * wave + c];
-    std::memcpy(&bias[0], b1, 32 * 4); std::memcpy(&bias[32], b2, 64 * 4); std::memcpy(&bias[96], b3, 128 * 4);
-    std::memcpy(&bias[224], bp, 4 * 4); std::memcpy(&bias[228], bv, 2 * 4);
+    gmk::pvpack::pack_heads(wp, wv, ph);
+    gmk::pvpack::pack_bias(b1, b2, b3, bp, bv, bias);
     gmk_pvnet* net = new gmk_pvnet;
     const bool ok = hipMalloc(&net->d_w1, p1.size() * 4) == hipSuccess && hipMalloc(&net->d_w2, p2.size() * 4) == hipSuccess &&
                     hipMalloc(&net->d_w3, p3.size() * 4) == hipSuccess && hipMalloc(&net->d_wh, ph.size() * 4) == hipSuccess &&
@@ -688,20 +653,8 @@ extern "C" int gmk_pvnet_set_dense(gmk_pvnet* net, const float* w_policy, const 
     gmk::DeviceState& st = gmk::device_state();
     if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
     if (!net || !w_policy || !b_policy || !w_hidden || !b_hidden || !w_out) { gmk::set_error("gmk_pvnet_set_dense: bad arguments"); return GMK_ERR_ARG; }
-    // B operands of v_mfma_f32_16x16x4_f32 in lane order: lane l carries W[output = 16 tile + (l & 15)][k = 4 step + (l >> 4)]; per wave and body
-    // the nine steps' four policy tiles and hidden tile side by side (zeros: the 16th policy tile, k >= 450 of the hidden layer, the pad body)
-    std::vector<float> wp(static_cast<size_t>(4) * (kDenseBodies + 1) * kDenseBody * 5 * 64, 0.0f), dense(256 + 64 + 64, 0.0f);
-    for (int wave = 0; wave < 4; ++wave)
-        for (int step = 0; step < kPolicySteps; ++step)
-            for (int q = 0; q < 5; ++q)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int k = 4 * step + (lane >> 4), body = step / kDenseBody, g = (step % kDenseBody) / 4;
-                    float v = 0.0f;
-                    if (q < 4) { const int o = 16 * (wave + 4 * q) + (lane & 15); if (o < kPix) v = w_policy[static_cast<size_t>(o) * 900 + k]; }
-                    else if (k < 450) v = w_hidden[static_cast<size_t>(16 * wave + (lane & 15)) * 450 + k];
-                    wp[((((static_cast<size_t>(wave) * (kDenseBodies + 1) + body) * 5 + q) * 3 + g) * 64 + lane) * 4 + (step & 3)] = v;
-                }
-    std::memcpy(&dense[0], b_policy, kPix * 4); std::memcpy(&dense[256], b_hidden, 64 * 4); std::memcpy(&dense[320], w_out, 64 * 4);
+    std::vector<float> wp, dense;                               // the layouts: pvnet_pack.h, pack_dense
+    gmk::pvpack::pack_dense(w_policy, b_policy, w_hidden, b_hidden, w_out, wp, dense);
     if (!net->d_wp) {
         const bool ok = hipMalloc(&net->d_wp, wp.size() * 4) == hipSuccess && hipMalloc(&net->d_dense, dense.size() * 4) == hipSuccess;
         if (!ok) { gmk::set_error("gmk_pvnet_set_dense: device allocation failed"); return GMK_ERR_HIP; }

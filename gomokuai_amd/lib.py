@@ -47,6 +47,8 @@ EXPORTS = [
     "gmk_pattern_policy", "gmk_pattern_policy_host", "gmk_pattern_play",
     "gmk_replay_create", "gmk_replay_destroy", "gmk_replay_reset", "gmk_replay_append", "gmk_replay_append_packed", "gmk_replay_size",
     "gmk_replay_sample", "gmk_replay_draw_host",
+    "gmk_train_create", "gmk_train_destroy", "gmk_train_forward", "gmk_train_grads", "gmk_train_step", "gmk_train_params", "gmk_train_set_params",
+    "gmk_train_get_block", "gmk_train_set_block", "gmk_train_set_step_count", "gmk_train_export", "gmk_train_info",
 ]
 
 
@@ -163,6 +165,18 @@ def load():
     L.gmk_replay_size.argtypes = [vp] + [C.POINTER(C.c_int64)] * 4 + [vp]
     L.gmk_replay_sample.argtypes = [vp, C.c_int, C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     L.gmk_replay_draw_host.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, vp]
+    L.gmk_train_create.argtypes = [vp] * 16 + [C.c_int, C.POINTER(vp)]
+    L.gmk_train_destroy.argtypes = [vp]
+    L.gmk_train_forward.argtypes = [vp, vp, C.c_int, vp, vp, vp]
+    L.gmk_train_grads.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp]
+    L.gmk_train_step.argtypes = [vp, vp, vp, vp, C.c_int, C.c_float, vp, vp, vp, vp]
+    L.gmk_train_params.argtypes = [vp] * 17
+    L.gmk_train_set_params.argtypes = [vp] * 17
+    L.gmk_train_get_block.argtypes = [vp, C.c_int, vp]
+    L.gmk_train_set_block.argtypes = [vp, C.c_int, vp]
+    L.gmk_train_set_step_count.argtypes = [vp, C.c_int64]
+    L.gmk_train_export.argtypes = [vp, vp, vp]
+    L.gmk_train_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     _lib = L
     return L
 
@@ -470,6 +484,107 @@ class ReplayHandle:
     def sample(self, batch, step, augment, states_float, d_states, d_values, d_pi, d_picked, d_status, stream=None):
         _check(load().gmk_replay_sample(self.h, int(batch), int(step), int(bool(augment)), int(bool(states_float)), d_states, d_values, d_pi,
                                         d_picked, d_status, stream))
+
+
+# ---------------- K11: the trainer (device pointers; include/gomoku_hip.h) ----------------
+# the sixteen tensors: (name, shape) in the ARGUMENT order of gmk_train_create / gmk_train_params (gmk_pvnet_create's ten, gmk_pvnet_set_dense's six)
+TRAIN_TENSORS = (("w1", (32, 6, 3, 3)), ("b1", (32,)), ("w2", (64, 32, 3, 3)), ("b2", (64,)), ("w3", (128, 64, 3, 3)), ("b3", (128,)),
+                 ("w_policy_conv", (4, 128)), ("b_policy_conv", (4,)), ("w_value_conv", (2, 128)), ("b_value_conv", (2,)),
+                 ("w_policy", (225, 900)), ("b_policy", (225,)), ("w_hidden", (64, 450)), ("b_hidden", (64,)), ("w_out", (64,)), ("b_out", (1,)))
+# ... and their order inside a block (d_grads, the moments): the two 1x1 heads side by side
+TRAIN_BLOCK_ORDER = ("w1", "b1", "w2", "b2", "w3", "b3", "w_policy_conv", "w_value_conv", "b_policy_conv", "b_value_conv",
+                     "w_policy", "b_policy", "w_hidden", "b_hidden", "w_out", "b_out")
+TRAIN_BIASES = tuple(name for name, _ in TRAIN_TENSORS if name.startswith("b"))
+TRAIN_PARAMS = sum(int(np.prod(shape)) for _, shape in TRAIN_TENSORS)
+BLOCK_PARAMS, BLOCK_M, BLOCK_V, BLOCK_UPDATE = 0, 1, 2, 3
+
+
+def split_block(block):
+    """A block in TRAIN_BLOCK_ORDER (numpy or torch, 1-D) -> {name: view of the tensor's shape}."""
+    shapes, out, at = dict(TRAIN_TENSORS), {}, 0
+    for name in TRAIN_BLOCK_ORDER:
+        size = int(np.prod(shapes[name]))
+        out[name] = block[at:at + size].reshape(shapes[name])
+        at += size
+    assert at == TRAIN_PARAMS == block.shape[0]
+    return out
+
+
+def join_block(tensors):
+    """{name: array} -> one float32 numpy block in TRAIN_BLOCK_ORDER."""
+    shapes = dict(TRAIN_TENSORS)
+    parts = [np.ascontiguousarray(np.asarray(tensors[name], dtype=np.float32)).reshape(-1) for name in TRAIN_BLOCK_ORDER]
+    assert all(p.size == int(np.prod(shapes[name])) for p, name in zip(parts, TRAIN_BLOCK_ORDER))
+    return np.concatenate(parts)
+
+
+class TrainerHandle:
+    """A gmk_trainer handle: the parameters, Adam's moments and the activations of up to max_batch positions in HBM; device pointers as ints."""
+
+    def __init__(self, arrays, max_batch):
+        """arrays: {name: float32 array} for every name of TRAIN_TENSORS."""
+        init()
+        host = self._host(arrays)
+        h = C.c_void_p()
+        _check(load().gmk_train_create(*[a.ctypes.data for a in host], int(max_batch), C.byref(h)))
+        self.h, self.max_batch = h, int(max_batch)
+
+    @staticmethod
+    def _host(arrays):
+        host = [np.ascontiguousarray(np.asarray(arrays[name], dtype=np.float32)) for name, _ in TRAIN_TENSORS]
+        for a, (name, shape) in zip(host, TRAIN_TENSORS):
+            if a.size != int(np.prod(shape)):
+                raise ValueError("TrainerHandle: %s must hold %d floats" % (name, int(np.prod(shape))))
+        return host
+
+    def close(self):
+        if getattr(self, "h", None) and load is not None:
+            load().gmk_train_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def forward(self, d_states, n, d_value, d_probs, stream=None):
+        _check(load().gmk_train_forward(self.h, d_states, int(n), d_value, d_probs, stream))
+
+    def grads(self, d_states, d_values, d_pi, n, d_grads, d_metrics, stream=None):
+        _check(load().gmk_train_grads(self.h, d_states, d_values, d_pi, int(n), d_grads, d_metrics, stream))
+
+    def step(self, d_states, d_values, d_pi, n, lr, d_old_probs, d_probs_out, d_metrics, stream=None):
+        _check(load().gmk_train_step(self.h, d_states, d_values, d_pi, int(n), float(lr), d_old_probs, d_probs_out, d_metrics, stream))
+
+    def params(self):
+        """-> {name: float32 array}; synchronises the device."""
+        out = {name: np.empty(shape, dtype=np.float32) for name, shape in TRAIN_TENSORS}
+        _check(load().gmk_train_params(self.h, *[out[name].ctypes.data for name, _ in TRAIN_TENSORS]))
+        return out
+
+    def set_params(self, arrays):
+        host = self._host(arrays)
+        _check(load().gmk_train_set_params(self.h, *[a.ctypes.data for a in host]))
+
+    def get_block(self, which):
+        out = np.empty(TRAIN_PARAMS, dtype=np.float32)
+        _check(load().gmk_train_get_block(self.h, int(which), out.ctypes.data))
+        return out
+
+    def set_block(self, which, block):
+        block = np.ascontiguousarray(np.asarray(block, dtype=np.float32)).reshape(-1)
+        if block.size != TRAIN_PARAMS:
+            raise ValueError("TrainerHandle.set_block: a block holds %d floats" % TRAIN_PARAMS)
+        _check(load().gmk_train_set_block(self.h, int(which), block.ctypes.data))
+
+    def set_step_count(self, step):
+        _check(load().gmk_train_set_step_count(self.h, int(step)))
+
+    def export(self, pvnet_handle, stream=None):
+        _check(load().gmk_train_export(self.h, pvnet_handle, stream))
+
+    def info(self):
+        """-> {"step", "scratch_bytes", "max_batch", "param_floats"}"""
+        step, scratch, mb, pf = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
+        _check(load().gmk_train_info(self.h, C.byref(step), C.byref(scratch), C.byref(mb), C.byref(pf)))
+        return {"step": step.value, "scratch_bytes": scratch.value, "max_batch": mb.value, "param_floats": pf.value}
 
 
 # ---------------- K2: incrementally maintained evaluator states ----------------

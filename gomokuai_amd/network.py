@@ -1,6 +1,7 @@
 """PolicyValueNetwork in PyTorch-ROCm: the architecture of the reference's TF1 graph (network/model_tf.py:28-66), for
-inference at the leaves of the network-guided search (K7, lib.AlphaZeroMCTS).  Training is out of scope;
-weights are randomly initialised like `tf.global_variables_initializer()` does when no checkpoint exists
+inference at the leaves of the network-guided search (K7, lib.AlphaZeroMCTS: FusedPolicyValueNetwork, K9) and for training on
+the device (Trainer, K11: the loss, the optimiser and the multi-pass train_step of model_tf.py:73-135 as HIP kernels).
+Weights are randomly initialised like `tf.global_variables_initializer()` does when no checkpoint exists
 (model_tf.py:165-172: glorot-uniform kernels, zero biases), or loaded from a state dict.
 
     inputs   float32 [B, 6, 15, 15]   Board.encoded_states() (core/py_ext/src/game_ext.hpp:87-104)
@@ -84,6 +85,12 @@ class FusedPolicyValueNetwork:
 
     __del__ = close
 
+    def load_from(self, trainer):
+        """Takes the weights a Trainer holds now (gmk_train_export: one repack kernel on the current stream, no trip through the host).  `self.net`
+        keeps the weights it had: call trainer.sync_to(self.net) as well where dense_reference() or the module itself is used afterwards."""
+        trainer.export(self)
+        return self
+
     @torch.no_grad()
     def trunk(self, states):
         """states float32 [B, 6, 15, 15] on the GPU -> (relu(policy conv) [B, 900], relu(value conv) [B, 450]), flattened (pixel, channel)."""
@@ -122,3 +129,139 @@ class FusedPolicyValueNetwork:
         states = torch.from_numpy(np.asarray(board.encoded_states(), dtype=np.float32)[None]).to(dev)
         value, probs = self(states)
         return float(value[0]), probs[0].cpu().numpy()
+
+
+# the trainer's tensor names (lib.TRAIN_TENSORS) -> how a PolicyValueNetwork holds them
+_MODULE_TENSORS = (("w1", "conv.0.weight"), ("b1", "conv.0.bias"), ("w2", "conv.1.weight"), ("b2", "conv.1.bias"), ("w3", "conv.2.weight"), ("b3", "conv.2.bias"),
+                   ("w_policy_conv", "policy_conv.weight"), ("b_policy_conv", "policy_conv.bias"), ("w_value_conv", "value_conv.weight"), ("b_value_conv", "value_conv.bias"),
+                   ("w_policy", "policy_dense.weight"), ("b_policy", "policy_dense.bias"), ("w_hidden", "value_hidden.weight"), ("b_hidden", "value_hidden.bias"),
+                   ("w_out", "value_out.weight"), ("b_out", "value_out.bias"))
+
+
+def module_arrays(net):
+    """{trainer tensor name: float32 numpy array in the trainer's shape} of a PolicyValueNetwork."""
+    from . import lib as G
+    sd, shapes = net.state_dict(), dict(G.TRAIN_TENSORS)
+    return {name: np.ascontiguousarray(sd[key].detach().float().cpu().numpy()).reshape(shapes[name]) for name, key in _MODULE_TENSORS}
+
+
+class Trainer:
+    """The network's training step on the device (gmk_train_*, train_kernel.hip; K11): compile() and train_step() of the reference's
+    PolicyValueNetwork (model_tf.py:73-135).  Holds its own float32 copy of `net`'s parameters, Adam's moments and the activations of up
+    to max_batch positions in HBM; float32 throughout and bit-reproducible.  All inputs are contiguous float32 CUDA tensors -- what
+    selfplay.ReplayBuffer.sample returns -- and every kernel goes to torch's current stream."""
+
+    def __init__(self, net, max_batch=512):
+        from . import lib as G
+        G.init()
+        self.G, self.max_batch = G, int(max_batch)
+        self.device = next(net.parameters()).device
+        if self.device.type != "cuda":
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._h = G.TrainerHandle(module_arrays(net), max_batch)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            self._h.close()
+            self._h = None
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _batch(self, states, values=None, pi=None):
+        n = states.shape[0]
+        if not (states.is_cuda and states.dtype == torch.float32 and states.is_contiguous() and tuple(states.shape[1:]) == (6, 15, 15)):
+            raise ValueError("Trainer: states must be a contiguous float32 CUDA tensor [n, 6, 15, 15]")
+        if not 1 <= n <= self.max_batch:
+            raise ValueError("Trainer: the batch must hold 1 .. max_batch = %d positions" % self.max_batch)
+        if values is not None and not (values.is_cuda and values.dtype == torch.float32 and values.is_contiguous() and tuple(values.shape) == (n,)):
+            raise ValueError("Trainer: values must be a contiguous float32 CUDA tensor [n]")
+        if pi is not None and not (pi.is_cuda and pi.dtype == torch.float32 and pi.is_contiguous() and tuple(pi.shape) == (n, 225)):
+            raise ValueError("Trainer: pi must be a contiguous float32 CUDA tensor [n, 225]")
+        return n
+
+    def forward(self, states):
+        """-> (value [n], probs [n, 225]) with the trainer's current parameters."""
+        n = self._batch(states)
+        value = torch.empty((n,), dtype=torch.float32, device=states.device)
+        probs = torch.empty((n, 225), dtype=torch.float32, device=states.device)
+        self._h.forward(states.data_ptr(), n, value.data_ptr(), probs.data_ptr(), self._stream())
+        return value, probs
+
+    def grads(self, states, values, pi):
+        """Forward, loss and backward without an update -> ({name: gradient of the data loss, no L2 term}, metrics float32[4] on the device =
+        loss including L2, entropy, value loss, policy loss).  The gradients are views of one block in lib.TRAIN_BLOCK_ORDER."""
+        n = self._batch(states, values, pi)
+        block = torch.empty(self.G.TRAIN_PARAMS, dtype=torch.float32, device=states.device)
+        metrics = torch.empty(4, dtype=torch.float32, device=states.device)
+        self._h.grads(states.data_ptr(), values.data_ptr(), pi.data_ptr(), n, block.data_ptr(), metrics.data_ptr(), self._stream())
+        return self.G.split_block(block), metrics
+
+    def step(self, states, values, pi, lr, old_probs=None):
+        """One optimiser step -> (probs [n, 225] from BEFORE the update, metrics float32[5] on the device = loss, entropy, value loss, policy
+        loss, KL against old_probs (0 without))."""
+        n = self._batch(states, values, pi)
+        if old_probs is not None and not (old_probs.is_cuda and old_probs.dtype == torch.float32 and old_probs.is_contiguous() and tuple(old_probs.shape) == (n, 225)):
+            raise ValueError("Trainer.step: old_probs must be a contiguous float32 CUDA tensor [n, 225]")
+        probs = torch.empty((n, 225), dtype=torch.float32, device=states.device)
+        metrics = torch.empty(5, dtype=torch.float32, device=states.device)
+        self._h.step(states.data_ptr(), values.data_ptr(), pi.data_ptr(), n, lr, None if old_probs is None else old_probs.data_ptr(),
+                     probs.data_ptr(), metrics.data_ptr(), self._stream())
+        return probs, metrics
+
+    def train_step(self, states, values, pi, lr, kl_target, num_epoches=5):
+        """PolicyValueNetwork.train_step (model_tf.py:111-135): up to num_epoches optimiser steps on one minibatch.  The first pass's
+        probabilities are `old`; every later pass reports its KL against them and the passes stop once kl > 4 kl_target.  One four-byte
+        read-back per pass (the KL) decides that; loss and entropy are read once at the end.  -> (loss, entropy, kl, epochs)."""
+        old, kl, metrics, done = None, 0.0, None, 0
+        for i in range(int(num_epoches)):
+            probs, metrics = self.step(states, values, pi, lr, old)
+            done = i + 1
+            if i == 0:
+                old, kl = probs, 0.0                      # "KL divergence is apparently zero"; the one read-back of this pass is skipped with it
+            else:
+                kl = float(metrics[4])
+            if kl > 4 * kl_target:
+                break
+        if metrics is None:
+            return 0.0, 0.0, 0.0, 0
+        loss, entropy = metrics[:2].tolist()
+        return loss, entropy, kl, done
+
+    def params(self):
+        """{name: float32 numpy array} of the current parameters (lib.TRAIN_TENSORS); synchronises."""
+        return self._h.params()
+
+    def sync_to(self, module):
+        """The trainer's parameters back into a PolicyValueNetwork (on whichever device it lives)."""
+        arrays = self._h.params()
+        sd = module.state_dict()
+        with torch.no_grad():
+            for name, key in _MODULE_TENSORS:
+                sd[key].copy_(torch.from_numpy(arrays[name]).reshape(sd[key].shape))
+        return module
+
+    def last_update(self):
+        """{name: what the last step subtracted from the tensor}: w_new = w_old - update exactly, in float32."""
+        return self.G.split_block(self._h.get_block(self.G.BLOCK_UPDATE))
+
+    def state_dict(self):
+        """Parameters, both moments (blocks in lib.TRAIN_BLOCK_ORDER, split by name) and Adam's step count."""
+        G = self.G
+        return {"params": self._h.params(), "m": dict(G.split_block(self._h.get_block(G.BLOCK_M))), "v": dict(G.split_block(self._h.get_block(G.BLOCK_V))),
+                "step": self._h.info()["step"]}
+
+    def load_state_dict(self, state):
+        G = self.G
+        self._h.set_params(state["params"])
+        self._h.set_block(G.BLOCK_M, G.join_block(state["m"]))
+        self._h.set_block(G.BLOCK_V, G.join_block(state["v"]))
+        self._h.set_step_count(state["step"])
+
+    @property
+    def steps(self):
+        return self._h.info()["step"]
+
+    def export(self, fused):
+        """The current parameters into an existing FusedPolicyValueNetwork's device buffers (gmk_train_export), ordered on the current stream."""
+        self._h.export(fused.h, self._stream())

@@ -527,6 +527,65 @@ int gmk_pattern_policy_host(const uint8_t* h_moves, int stride, const int32_t* h
 int gmk_pattern_play(uint8_t* d_moves, int32_t* d_lens, int n, int filter, int max_moves,
                      int8_t* d_winner, float* d_values, int32_t* d_status, void* stream);
 
+/* ---- K11: training the policy-value network on the device (network/train.py:62-86, network/model_tf.py:73-135) ----
+ * A gmk_trainer holds the network's sixteen parameter tensors in float32 in their canonical layouts (those gmk_pvnet_create and
+ * gmk_pvnet_set_dense take), Adam's two moments, a gradient block and the activations of up to max_batch positions.  One step = forward
+ * with kept activations, loss, backward, TF1's Adam (tf.train.AdamOptimizer: lr_t = lr sqrt(1 - 0.999^t) / (1 - 0.9^t),
+ * w -= lr_t m / (sqrt(v) + 1e-8)); float32 parameters, activations, gradients and moments (Adam's few operations per element run in
+ * float64 between float32 loads and stores), no floating-point atomics: the same inputs give the same bits.
+ * loss = mean (value - z)^2 + mean softmax cross-entropy(pi, logits) + 1e-4 sum(w^2) / 2 over every tensor that is not a bias.
+ * All pointers are device pointers unless named h_; n in [1, max_batch]; everything is asynchronous on `stream` unless said otherwise.
+ *
+ * The host arrays h_w1 .. h_b_out are gmk_pvnet_create's ten followed by gmk_pvnet_set_dense's six (h_b_out points at one float).
+ * BLOCK ORDER -- the order of d_grads and of gmk_train_get_block / gmk_train_set_block, 326 540 floats:
+ *   w1 [32][6][3][3], b1 [32], w2 [64][32][3][3], b2 [64], w3 [128][64][3][3], b3 [128], w_policy_conv [4][128], w_value_conv [2][128],
+ *   b_policy_conv [4], b_value_conv [2], w_policy [225][900], b_policy [225], w_hidden [64][450], b_hidden [64], w_out [64], b_out [1]
+ *   (the two 1x1 heads sit side by side because they run as one GEMM).
+ *
+ * gmk_train_create: moments zero, step count 0.  max_batch in [1, 4096].
+ * gmk_train_forward: d_states float32 [n][6][225] -> d_value [n], d_probs [n][225] (the training path's forward; activations are kept).
+ * gmk_train_grads: forward, loss and backward, no update.  d_grads: one block in BLOCK ORDER, the gradient of the data loss (WITHOUT the L2
+ *   term).  d_metrics float[4] = loss including L2, entropy mean(-sum p log(p + 1e-10)), value loss, policy loss.
+ * gmk_train_step: the same, then Adam on every tensor (weights with the L2 gradient 1e-4 w).  d_probs_out (or NULL) [n][225]: the policy
+ *   output from BEFORE the update, as session.run([policy_output, loss, entropy, opt]) fetches it.  d_metrics float[5]: the four above and
+ *   [4] = mean sum (old + 1e-10) log((old + 1e-10) / (p + 1e-10)) against d_old_probs [n][225], or 0 if d_old_probs is NULL.
+ * gmk_train_params / gmk_train_set_params: the sixteen tensors to / from host arrays (blocking; they synchronise the device).
+ * gmk_train_get_block / gmk_train_set_block: a whole block in BLOCK ORDER to / from the host (blocking): which = 0 parameters, 1 first
+ *   moments, 2 second moments, 3 (get only) the update the last step applied: w_new = w_old - update, exactly.  Block 3 is a diagnostic: the
+ *   difference of two stored float32 parameters carries half an ulp of the PARAMETER, several 1e-6 of a step of lr, so the optimiser's
+ *   arithmetic can be checked to 1e-6 only against the update itself (tests/test_train_gpu.py).  It costs a fifth parameter-sized block
+ *   (1.3 MB) and one 4-byte store per element and step; nothing in the training path reads it.
+ * gmk_train_set_step_count: Adam's t (what a restored state continues from).
+ * gmk_train_export: writes the parameters into an existing gmk_pvnet's device buffers, in the layouts gmk_pvnet_create / gmk_pvnet_set_dense
+ *   give them, with one kernel on `stream` (GMK_ERR_STATE before gmk_pvnet_set_dense).  The network's output bias is a host scalar in the
+ *   handle: its four bytes are read back, so this call returns after `stream` has reached it.  It must not run while a
+ *   gmk_pvnet_evaluate of `net` is in flight on another stream.
+ * gmk_train_info: the number of steps taken, the scratch bytes (activations, columns, split-K slabs), max_batch, the floats of a block; any
+ *   pointer may be NULL. */
+typedef struct gmk_trainer gmk_trainer;
+int gmk_train_create(const float* h_w1, const float* h_b1, const float* h_w2, const float* h_b2, const float* h_w3, const float* h_b3,
+                     const float* h_w_policy_conv, const float* h_b_policy_conv, const float* h_w_value_conv, const float* h_b_value_conv,
+                     const float* h_w_policy, const float* h_b_policy, const float* h_w_hidden, const float* h_b_hidden,
+                     const float* h_w_out, const float* h_b_out, int max_batch, gmk_trainer** out);
+int gmk_train_destroy(gmk_trainer* trainer);
+int gmk_train_forward(gmk_trainer* trainer, const float* d_states, int n, float* d_value, float* d_probs, void* stream);
+int gmk_train_grads(gmk_trainer* trainer, const float* d_states, const float* d_values, const float* d_pi, int n, float* d_grads,
+                    float* d_metrics, void* stream);
+int gmk_train_step(gmk_trainer* trainer, const float* d_states, const float* d_values, const float* d_pi, int n, float lr,
+                   const float* d_old_probs, float* d_probs_out, float* d_metrics, void* stream);
+int gmk_train_params(gmk_trainer* trainer, float* h_w1, float* h_b1, float* h_w2, float* h_b2, float* h_w3, float* h_b3,
+                     float* h_w_policy_conv, float* h_b_policy_conv, float* h_w_value_conv, float* h_b_value_conv,
+                     float* h_w_policy, float* h_b_policy, float* h_w_hidden, float* h_b_hidden, float* h_w_out, float* h_b_out);
+int gmk_train_set_params(gmk_trainer* trainer, const float* h_w1, const float* h_b1, const float* h_w2, const float* h_b2, const float* h_w3,
+                         const float* h_b3, const float* h_w_policy_conv, const float* h_b_policy_conv, const float* h_w_value_conv,
+                         const float* h_b_value_conv, const float* h_w_policy, const float* h_b_policy, const float* h_w_hidden,
+                         const float* h_b_hidden, const float* h_w_out, const float* h_b_out);
+int gmk_train_get_block(gmk_trainer* trainer, int which, float* h_block);
+int gmk_train_set_block(gmk_trainer* trainer, int which, const float* h_block);
+int gmk_train_set_step_count(gmk_trainer* trainer, int64_t step);
+int gmk_train_export(gmk_trainer* trainer, gmk_pvnet* net, void* stream);
+int gmk_train_info(gmk_trainer* trainer, int64_t* h_step, int64_t* h_scratch_bytes, int32_t* h_max_batch, int32_t* h_param_floats);
+
 #ifdef __cplusplus
 }
 #endif
