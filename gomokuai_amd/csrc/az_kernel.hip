@@ -470,6 +470,94 @@ void az_root_noise_kernel(AzTree t, const int32_t* __restrict__ slot_game, const
     }
 }
 
+// The cell MCTS::stepForward() would play for every game, left ON THE DEVICE for the match referee (match_kernel.hip): the most visited root
+// child, first maximum in child (= cell) order, exactly az_advance_kernel's choice; -1 for a root without a visited child.  visits (may be
+// null): the root children's visit counts by cell, saturated like the records' rows.  One wavefront per game.
+__global__ __launch_bounds__(64)
+void az_root_choice_kernel(AzTree t, int16_t* __restrict__ cells, uint16_t* __restrict__ visits) {
+    const int game = blockIdx.x, lane = threadIdx.x;
+    if (game >= t.n_games) return;
+    const size_t base = static_cast<size_t>(game) * t.cap;
+    const uint2 rk = t.kids[base];
+    const uint32_t first = rk.x, n = rk.y & 0xFFu;
+    uint32_t best_v = 0, best_i = 0xFFFFFFFFu;
+    for (uint32_t i = lane; i < n; i += 64) {
+        const uint32_t v = t.stat[base + first + i].x;
+        if (v > best_v) { best_v = v; best_i = i; }
+    }
+    for (int s = 32; s > 0; s >>= 1) {
+        const uint32_t ov = __shfl_down(best_v, s), oi = __shfl_down(best_i, s);
+        if (ov > best_v || (ov == best_v && ov != 0u && oi < best_i)) { best_v = ov; best_i = oi; }
+    }
+    if (lane == 0) cells[game] = best_v == 0u ? static_cast<int16_t>(-1) : static_cast<int16_t>((t.kids[base + first + best_i].y >> 8) & 0xFFu);
+    if (visits) {
+        uint16_t* rv = visits + static_cast<size_t>(game) * kCells;
+        for (int i = lane; i < kCells; i += 64) rv[i] = 0;
+        __syncthreads();
+        for (uint32_t i = lane; i < n; i += 64) rv[(t.kids[base + first + i].y >> 8) & 0xFFu] = static_cast<uint16_t>(min(t.stat[base + first + i].x, 65535u));
+    }
+}
+
+// gmk_az_step with the cells and the referee's verdicts (GMK_MATCH_*) read from device memory.  A game that moved follows the move -- the
+// child's subtree into the other arena (fresh == 0, as az_step_kernel) or a new root in place (fresh != 0, what gmk_az_set_roots makes for
+// the position after the move); a game that ended on this ply is closed as az_advance_kernel closes one (status bit 0, a childless root in
+// both arenas); a game that did not move or was over before keeps its tree (copied over as it is when the arenas flip: a closed game's
+// childless root is in both already).  One wavefront per game.
+__global__ __launch_bounds__(64)
+void az_step_device_kernel(AzTree t, AzArena b, const int16_t* __restrict__ cells, const int32_t* __restrict__ verdict, int fresh) {
+    const int game = blockIdx.x, lane = threadIdx.x;
+    if (game >= t.n_games) return;
+    AzHeader& hdr = t.hdr[game];
+    const size_t base = static_cast<size_t>(game) * t.cap;
+    const int v = verdict[game];
+    if (hdr.status & kStatusOver) return;                        // closed on an earlier ply
+    const uint32_t cell = static_cast<uint32_t>(static_cast<int>(cells[game]));
+    const uint32_t stones = hdr.stones;
+    bool moved = v == GMK_MATCH_MOVED || v == GMK_MATCH_ENDED;
+    if (moved) {                                                 // the referee judged the RECORD; the handle's own position must agree
+        const uint32_t row = cell < 225u ? hdr.rows[cell / 15u] >> (cell % 15u) : 0x10001u;
+        if (row & 0x10001u) { moved = false; if (lane == 0) hdr.status |= 4u; }
+    }
+    if (!moved) {
+        if (!fresh) az_keep_subtree(t, b, base, 0u, lane, hdr);
+        return;
+    }
+    uint32_t best_i = 0xFFFFFFFFu;                               // the child of that cell (children are in ascending cell order: at most one)
+    if (!fresh && v == GMK_MATCH_MOVED) {
+        const uint2 rk = t.kids[base];
+        const uint32_t first = rk.x, n = rk.y & 0xFFu;
+        for (uint32_t i = lane; i < n; i += 64)
+            if (((t.kids[base + first + i].y >> 8) & 0xFFu) == cell) best_i = first + i;
+        for (int s = 32; s > 0; s >>= 1) best_i = min(best_i, static_cast<uint32_t>(__shfl_xor(best_i, s)));
+    }
+    __syncthreads();                                             // every lane has read the old header
+    if (lane == 0) {
+        hdr.rows[cell / 15u] |= 1u << (cell % 15u + ((stones & 1u) ? 16 : 0));
+        hdr.stones = stones + 1u;
+        hdr.last_move2 = hdr.last_move;
+        hdr.last_move = cell;
+        hdr.leaf_pending = 0;
+    }
+    if (v == GMK_MATCH_ENDED) {
+        if (lane == 0) {
+            hdr.status |= kStatusOver;
+            hdr.n_nodes = 1;
+            t.stat[base] = make_uint2(0u, 0u); t.kids[base] = make_uint2(0u, 0u); t.prior[base] = 1.0f; t.parent[base] = kNoNode;
+            if (!fresh) { b.stat[base] = make_uint2(0u, 0u); b.kids[base] = make_uint2(0u, 0u); b.prior[base] = 1.0f; b.parent[base] = kNoNode; }
+        }
+        return;
+    }
+    if (fresh) {                                                 // a new root, as az_init_roots_kernel makes it
+        if (lane == 0) { t.stat[base] = make_uint2(0u, 0u); t.kids[base] = make_uint2(0u, cell << 8); t.prior[base] = 1.0f; t.parent[base] = kNoNode; hdr.n_nodes = 1; }
+        return;
+    }
+    if (best_i == 0xFFFFFFFFu) {                                 // stepForward(move) without such a child: a new node (MCTS.cpp:140-145)
+        if (lane == 0) { b.stat[base] = make_uint2(0u, 0u); b.kids[base] = make_uint2(0u, cell << 8); b.prior[base] = 1.0f; b.parent[base] = kNoNode; hdr.n_nodes = 1; }
+        return;
+    }
+    az_keep_subtree(t, b, base, best_i, lane, hdr);
+}
+
 __global__ void az_init_roots_kernel(AzTree t) {
     const int game = blockIdx.x * blockDim.x + threadIdx.x;
     if (game >= t.n_games) return;
@@ -713,6 +801,34 @@ extern "C" int gmk_az_step(gmk_az* a, const int16_t* h_moves) {
     GMK_HIP_CHECK(hipGetLastError());
     GMK_HIP_CHECK(hipDeviceSynchronize());
     std::swap(a->t.stat, a->other.stat); std::swap(a->t.kids, a->other.kids); std::swap(a->t.prior, a->other.prior); std::swap(a->t.parent, a->other.parent);
+    return GMK_OK;
+}
+
+extern "C" int gmk_az_root_choice(gmk_az* a, int16_t* d_cells, uint16_t* d_visits, void* stream) {
+    if (!a || !d_cells) { gmk::set_error("gmk_az_root_choice: bad arguments"); return GMK_ERR_ARG; }
+    if (!a->rooted) { gmk::set_error("gmk_az_root_choice: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
+    hipLaunchKernelGGL(az_root_choice_kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_cells, d_visits);
+    GMK_HIP_CHECK(hipGetLastError());
+    return GMK_OK;
+}
+
+// gmk_az_step from device memory, on the caller's stream (az_step_device_kernel), then the leaf batch is compacted as gmk_az_advance
+// compacts it.  The one synchronisation of a match ply is here: the number of live games (4 bytes) and, if asked for, the referee's count.
+extern "C" int gmk_az_step_device(gmk_az* a, const int16_t* d_cells, const int32_t* d_verdict, int fresh_root, const int32_t* d_unfinished, int32_t* h_unfinished,
+                                  void* stream) {
+    if (!a || !d_cells || !d_verdict || (h_unfinished && !d_unfinished)) { gmk::set_error("gmk_az_step_device: bad arguments"); return GMK_ERR_ARG; }
+    if (!a->rooted) { gmk::set_error("gmk_az_step_device: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
+    if (a->slots.slot_game) { gmk::set_error("gmk_az_step_device: the handle plays through slots (gmk_az_set_slots): a match wants one game per slot"); return GMK_ERR_STATE; }
+    if (!fresh_root)
+        if (const int rc = az_second_arena(a); rc != GMK_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(az_step_device_kernel, dim3(a->t.n_games), dim3(64), 0, s, a->t, a->other, d_cells, d_verdict, fresh_root ? 1 : 0);
+    GMK_HIP_CHECK(hipGetLastError());
+    int32_t unfinished = 0;
+    if (h_unfinished) GMK_HIP_CHECK(hipMemcpyAsync(&unfinished, d_unfinished, 4, hipMemcpyDeviceToHost, s));
+    if (const int rc = az_compact(a, s); rc != GMK_OK) return rc;   // (synchronises)
+    if (!fresh_root) { std::swap(a->t.stat, a->other.stat); std::swap(a->t.kids, a->other.kids); std::swap(a->t.prior, a->other.prior); std::swap(a->t.parent, a->other.parent); }
+    if (h_unfinished) *h_unfinished = unfinished;
     return GMK_OK;
 }
 

@@ -877,6 +877,104 @@ void trad_root_stats_kernel(const uint2* stat, const uint2* info, const uint32_t
     }
 }
 
+// trad_root_stats_kernel's `best` and visit counts, left ON THE DEVICE for the match referee (match_kernel.hip): the cell as int16 (-1: a
+// root without children), the counts by cell saturated like the records' rows (visits may be null).  One wavefront per game.
+__global__ __launch_bounds__(64)
+void trad_root_choice_kernel(TradArena a, const TradHeader* hdrs, int cap, int n_games, int16_t* __restrict__ cells, uint16_t* __restrict__ visits) {
+    const int game = blockIdx.x, lane = threadIdx.x;
+    if (game >= n_games) return;
+    const size_t base = static_cast<size_t>(game) * cap;
+    const bool no_root = hdrs[game].fresh == 1u;                // the position was set but never searched
+    const uint32_t lk = no_root ? 0u : a.link[base], first = lk & 0xFFFFFFu, n = lk >> 24;
+    uint16_t* rv = visits ? visits + static_cast<size_t>(game) * 225 : nullptr;
+    if (rv) {
+        for (int i = lane; i < 225; i += 64) rv[i] = 0;
+        __syncthreads();
+    }
+    uint32_t best_visits = 0, best_ord = 0xFFFFFFFFu, best_cell = 0;
+    for (uint32_t i = lane; i < n; i += 64) {
+        const uint32_t v = a.stat[base + first + i].x, cell = a.info[base + first + i].x >> 24, o = a.ord[base + first + i];
+        if (rv && cell < 225u) rv[cell] = static_cast<uint16_t>(min(v, 65535u));
+        if (best_ord == 0xFFFFFFFFu || v > best_visits || (v == best_visits && o < best_ord)) { best_visits = v; best_ord = o; best_cell = cell; }
+    }
+    for (int s = 32; s > 0; s >>= 1) {
+        const uint32_t ov = __shfl_down(best_visits, s), oo = __shfl_down(best_ord, s), oc = __shfl_down(best_cell, s);
+        if (oo != 0xFFFFFFFFu && (best_ord == 0xFFFFFFFFu || ov > best_visits || (ov == best_visits && oo < best_ord))) { best_visits = ov; best_ord = oo; best_cell = oc; }
+    }
+    if (lane == 0) cells[game] = best_ord == 0xFFFFFFFFu ? static_cast<int16_t>(-1) : static_cast<int16_t>(best_cell);
+}
+
+// gmk_trad_step with the cells and the referee's verdicts (GMK_MATCH_*) read from device memory.  A game that moved appends the move to its
+// position and follows it: the child's subtree into the other arena (fresh == 0, as trad_step_kernel) or a new root at the next search
+// (fresh != 0, as gmk_trad_set_positions leaves the game).  A game that ended on this ply takes the move and goes idle (status bit 4: the
+// searches skip it) behind a childless root; one that did not move or was over before keeps its tree -- copied over as it is when the
+// arenas flip (an idle game's childless root is in both already).  One wavefront per game.
+__global__ __launch_bounds__(64)
+void trad_step_device_kernel(TradArena a, TradArena b, TradHeader* hdrs, int cap, int n_games, const int16_t* __restrict__ cells, const int32_t* __restrict__ verdict,
+                             int fresh, uint8_t* moves, int32_t* lens) {
+    const int game = blockIdx.x, lane = threadIdx.x;
+    if (game >= n_games) return;
+    TradHeader& hdr = hdrs[game];
+    if (hdr.status & kStatusIdleSlot) return;                   // closed on an earlier ply
+    const size_t base = static_cast<size_t>(game) * cap;
+    uint8_t* mv = moves + static_cast<size_t>(game) * 225;
+    const int len = lens[game], v = verdict[game];
+    const uint32_t cell = static_cast<uint32_t>(static_cast<int>(cells[game]));
+    bool moved = v == GMK_MATCH_MOVED || v == GMK_MATCH_ENDED;
+    if (moved) {                                                // the referee judged the RECORD; the handle's own position must agree
+        bool legal = cell < 225u && len < 225;
+        for (int i = lane; i < len; i += 64) legal &= mv[i] != cell;
+        if (!__all(legal)) { moved = false; if (lane == 0) hdr.status |= 8u; }
+    }
+    if (fresh) {
+        if (moved && lane == 0) {
+            mv[len] = static_cast<uint8_t>(cell); lens[game] = len + 1;
+            hdr.fresh = 1; hdr.playouts_done = 0;
+            if (v == GMK_MATCH_ENDED) hdr.status |= kStatusIdleSlot;
+        }
+        return;
+    }
+    if (hdr.fresh == 1u) {                                      // the position was set but never searched: its root node does not exist yet
+        if (lane == 0) {
+            a.stat[base] = make_uint2(0u, 0u);
+            a.info[base] = make_uint2(kNoParent | ((len ? mv[len - 1] : 255u) << 24), __float_as_uint(1.0f));
+            a.link[base] = 0u;
+            if (a.amaf) a.amaf[base] = make_uint2(0u, 0u);
+            hdr.n_nodes = 1; hdr.status = 0; hdr.root_black = static_cast<uint32_t>(len & 1); hdr.fresh = 2;
+        }
+        __syncthreads();
+    }
+    if (!moved) {
+        const uint32_t kept = copy_subtree<false>(a, b, base, 0u, lane);
+        if (lane == 0) hdr.n_nodes = kept;
+        return;
+    }
+    uint32_t best_id = 0xFFFFFFFFu;                             // the child of that cell (a cell has at most one)
+    if (v == GMK_MATCH_MOVED) {
+        const uint32_t lk = a.link[base], first = lk & 0xFFFFFFu, n = lk >> 24;
+        for (uint32_t i = lane; i < n; i += 64)
+            if ((a.info[base + first + i].x >> 24) == cell) best_id = first + i;
+        for (int s = 32; s > 0; s >>= 1) best_id = min(best_id, static_cast<uint32_t>(__shfl_xor(best_id, s)));
+    }
+    __syncthreads();                                            // every lane has read the old move list
+    if (lane == 0) { mv[len] = static_cast<uint8_t>(cell); lens[game] = len + 1; hdr.fresh = 2; hdr.root_black ^= 1u; }
+    if (best_id == 0xFFFFFFFFu) {                               // stepForward(move) without such a child (MCTS.cpp:140-145), or the end of the game: a new node
+        if (lane == 0) {
+            const uint2 st = make_uint2(0u, 0u), inf = make_uint2(kNoParent | (cell << 24), __float_as_uint(1.0f));
+            b.stat[base] = st; b.info[base] = inf; b.link[base] = 0u; b.ord[base] = 0; hdr.n_nodes = 1;
+            if (a.amaf) b.amaf[base] = make_uint2(0u, 0u);
+            if (v == GMK_MATCH_ENDED) {
+                a.stat[base] = st; a.info[base] = inf; a.link[base] = 0u; a.ord[base] = 0;
+                if (a.amaf) a.amaf[base] = make_uint2(0u, 0u);
+                hdr.status |= kStatusIdleSlot;
+            }
+        }
+        return;
+    }
+    const uint32_t kept = copy_subtree<false>(a, b, base, best_id, lane);
+    if (lane == 0) hdr.n_nodes = kept;
+}
+
 }  // namespace
 
 
@@ -1105,9 +1203,8 @@ extern "C" int gmk_trad_root_stats(gmk_trad* t, uint32_t* h_visits, float* h_val
                                    uint32_t* h_root_visits, float* h_root_value, int32_t* h_n_nodes, int32_t* h_status,
                                    uint64_t* h_evaluator_updates);
 
-extern "C" int gmk_trad_step(gmk_trad* t, const int16_t* h_moves) {
-    if (!t) { gmk::set_error("gmk_trad_step: bad arguments"); return GMK_ERR_ARG; }
-    if (!t->positioned) { gmk::set_error("gmk_trad_step: gmk_trad_set_positions has not been called"); return GMK_ERR_STATE; }
+// the second arena of gmk_trad_step / gmk_trad_step_device (and d_forced), allocated by the first call; the AMAF block follows the first one
+static int trad_second_arena(gmk_trad* t, const char* name) {
     const size_t n = static_cast<size_t>(t->n_games), nodes = n * static_cast<size_t>(t->cap);
     if (!t->second_arena) {
         const bool ok = gmk::device_malloc(&t->d_stat2, nodes * 8) == hipSuccess && gmk::device_malloc(&t->d_info2, nodes * 8) == hipSuccess &&
@@ -1117,11 +1214,19 @@ extern "C" int gmk_trad_step(gmk_trad* t, const int16_t* h_moves) {
             (void)gmk::device_free(t->d_stat2); (void)gmk::device_free(t->d_info2); (void)gmk::device_free(t->d_link2); (void)gmk::device_free(t->d_front2); (void)gmk::device_free(t->d_ord2); (void)gmk::device_free(t->d_forced);
             t->d_stat2 = t->d_info2 = t->d_front2 = nullptr; t->d_link2 = nullptr; t->d_ord2 = nullptr; t->d_forced = nullptr;
             (void)hipGetLastError();
-            gmk::set_error("gmk_trad_step: hipMalloc of the second arena (%zu nodes) failed", nodes);
+            gmk::set_error("%s: hipMalloc of the second arena (%zu nodes) failed", name, nodes);
             return GMK_ERR_HIP;
         }
         t->second_arena = true;
     }
+    return GMK_OK;
+}
+
+extern "C" int gmk_trad_step(gmk_trad* t, const int16_t* h_moves) {
+    if (!t) { gmk::set_error("gmk_trad_step: bad arguments"); return GMK_ERR_ARG; }
+    if (!t->positioned) { gmk::set_error("gmk_trad_step: gmk_trad_set_positions has not been called"); return GMK_ERR_STATE; }
+    const size_t n = static_cast<size_t>(t->n_games), nodes = n * static_cast<size_t>(t->cap);
+    if (const int rc = trad_second_arena(t, "gmk_trad_step"); rc != GMK_OK) return rc;
     GMK_HIP_CHECK(hipDeviceSynchronize());
     if (h_moves) GMK_HIP_CHECK(hipMemcpy(t->d_forced, h_moves, n * 2, hipMemcpyHostToDevice));
     if (t->d_amaf && !t->d_amaf2 && gmk::device_malloc(&t->d_amaf2, nodes * 8) != hipSuccess) { gmk::set_error("gmk_trad_step: hipMalloc of the second arena (%zu nodes) failed", nodes); return GMK_ERR_HIP; }
@@ -1132,6 +1237,33 @@ extern "C" int gmk_trad_step(gmk_trad* t, const int16_t* h_moves) {
     GMK_HIP_CHECK(hipDeviceSynchronize());
     std::swap(t->d_stat, t->d_stat2); std::swap(t->d_info, t->d_info2); std::swap(t->d_link, t->d_link2);
     std::swap(t->d_front, t->d_front2); std::swap(t->d_ord, t->d_ord2); std::swap(t->d_amaf, t->d_amaf2);
+    return GMK_OK;
+}
+
+extern "C" int gmk_trad_root_choice(gmk_trad* t, int16_t* d_cells, uint16_t* d_visits, void* stream) {
+    if (!t || !d_cells) { gmk::set_error("gmk_trad_root_choice: bad arguments"); return GMK_ERR_ARG; }
+    if (!t->positioned) { gmk::set_error("gmk_trad_root_choice: gmk_trad_set_positions has not been called"); return GMK_ERR_STATE; }
+    hipLaunchKernelGGL(trad_root_choice_kernel, dim3(t->n_games), dim3(64), 0, static_cast<hipStream_t>(stream), t->arena(), t->d_hdr, t->cap, t->n_games, d_cells, d_visits);
+    GMK_HIP_CHECK(hipGetLastError());
+    return GMK_OK;
+}
+
+// gmk_trad_step from device memory, on the caller's stream (trad_step_device_kernel): nothing is copied and nothing is waited for
+extern "C" int gmk_trad_step_device(gmk_trad* t, const int16_t* d_cells, const int32_t* d_verdict, int fresh_root, void* stream) {
+    if (!t || !d_cells || !d_verdict) { gmk::set_error("gmk_trad_step_device: bad arguments"); return GMK_ERR_ARG; }
+    if (!t->positioned) { gmk::set_error("gmk_trad_step_device: gmk_trad_set_positions has not been called"); return GMK_ERR_STATE; }
+    if (!fresh_root) {
+        const size_t nodes = static_cast<size_t>(t->n_games) * static_cast<size_t>(t->cap);
+        if (const int rc = trad_second_arena(t, "gmk_trad_step_device"); rc != GMK_OK) return rc;
+        if (t->d_amaf && !t->d_amaf2 && gmk::device_malloc(&t->d_amaf2, nodes * 8) != hipSuccess) { gmk::set_error("gmk_trad_step_device: hipMalloc of the second arena (%zu nodes) failed", nodes); return GMK_ERR_HIP; }
+    }
+    hipLaunchKernelGGL(trad_step_device_kernel, dim3(t->n_games), dim3(64), 0, static_cast<hipStream_t>(stream), t->arena(), t->arena2(), t->d_hdr, t->cap, t->n_games,
+                       d_cells, d_verdict, fresh_root ? 1 : 0, t->d_moves, t->d_lens);
+    GMK_HIP_CHECK(hipGetLastError());
+    if (!fresh_root) {
+        std::swap(t->d_stat, t->d_stat2); std::swap(t->d_info, t->d_info2); std::swap(t->d_link, t->d_link2);
+        std::swap(t->d_front, t->d_front2); std::swap(t->d_ord, t->d_ord2); std::swap(t->d_amaf, t->d_amaf2);
+    }
     return GMK_OK;
 }
 

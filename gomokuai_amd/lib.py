@@ -42,9 +42,10 @@ EXPORTS = [
     "gmk_mcts_alg_bytes", "gmk_mcts_launch_info", "gmk_visits_to_pi", "gmk_mcts_advance", "gmk_mcts_step", "gmk_mcts_step_host", "gmk_mcts_add_root_noise", "gmk_mcts_set_option", "gmk_mcts_reserve", "gmk_selfplay_run", "gmk_samples_from_records",
     "gmk_records_scan", "gmk_records_packed_bytes", "gmk_records_pack", "gmk_records_unpack", "gmk_samples_from_packed",
     "gmk_evalstate_create", "gmk_evalstate_destroy", "gmk_evalstate_reset", "gmk_evalstate_update", "gmk_evalstate_update_host", "gmk_evalstate_read",
-    "gmk_az_create", "gmk_az_destroy", "gmk_az_set_roots", "gmk_az_select", "gmk_az_expand", "gmk_az_select_host", "gmk_az_expand_host", "gmk_az_read_node_host", "gmk_az_read_children_host", "gmk_az_set_leaf_host", "gmk_az_rollout_host", "gmk_az_expand_stages_host", "gmk_az_write_stats_host", "gmk_az_step", "gmk_az_advance", "gmk_az_set_slots", "gmk_az_live_games", "gmk_az_set_game_ids", "gmk_az_add_root_noise", "gmk_az_set_option", "gmk_az_root_stats",
-    "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_run_rave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
+    "gmk_az_create", "gmk_az_destroy", "gmk_az_set_roots", "gmk_az_select", "gmk_az_expand", "gmk_az_select_host", "gmk_az_expand_host", "gmk_az_read_node_host", "gmk_az_read_children_host", "gmk_az_set_leaf_host", "gmk_az_rollout_host", "gmk_az_expand_stages_host", "gmk_az_write_stats_host", "gmk_az_step", "gmk_az_root_choice", "gmk_az_step_device", "gmk_az_advance", "gmk_az_set_slots", "gmk_az_live_games", "gmk_az_set_game_ids", "gmk_az_add_root_noise", "gmk_az_set_option", "gmk_az_root_stats",
+    "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_root_choice", "gmk_trad_step_device", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_run_rave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
     "gmk_pattern_policy", "gmk_pattern_policy_host", "gmk_pattern_play",
+    "gmk_match_referee",
     "gmk_replay_create", "gmk_replay_destroy", "gmk_replay_reset", "gmk_replay_append", "gmk_replay_append_packed", "gmk_replay_size",
     "gmk_replay_sample", "gmk_replay_draw_host",
     "gmk_train_create", "gmk_train_destroy", "gmk_train_forward", "gmk_train_grads", "gmk_train_step", "gmk_train_params", "gmk_train_set_params",
@@ -121,6 +122,8 @@ def load():
     L.gmk_az_expand.argtypes = [vp, vp, vp, vp]
     L.gmk_az_select_host.argtypes = [vp, vp, vp]
     L.gmk_az_step.argtypes = [vp, vp]
+    L.gmk_az_root_choice.argtypes = [vp, vp, vp, vp]
+    L.gmk_az_step_device.argtypes = [vp, vp, vp, C.c_int, vp, C.POINTER(C.c_int32), vp]
     L.gmk_az_live_games.argtypes = [vp, C.POINTER(C.c_int32)]
     L.gmk_az_set_slots.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     L.gmk_az_advance.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_int32), vp]
@@ -134,6 +137,9 @@ def load():
     L.gmk_trad_set_positions.argtypes = [vp, vp, vp]
     L.gmk_trad_run.argtypes = [vp, C.c_int, C.c_double, vp]
     L.gmk_trad_step.argtypes = [vp, vp]
+    L.gmk_trad_root_choice.argtypes = [vp, vp, vp, vp]
+    L.gmk_trad_step_device.argtypes = [vp, vp, vp, C.c_int, vp]
+    L.gmk_match_referee.argtypes = [C.c_int, C.c_int] + [vp] * 11
     L.gmk_trad_add_root_noise.argtypes = [vp, C.c_float, C.c_float, C.c_uint64, C.c_uint32]
     L.gmk_trad_set_option.argtypes = [vp, C.c_int, C.c_int]
     L.gmk_trad_root_stats.argtypes = [vp] * 10
@@ -654,6 +660,47 @@ def pattern_play(d_moves, d_lens, n, filter=True, max_moves=0, d_winner=None, d_
     _check(load().gmk_pattern_play(d_moves, d_lens, int(n), int(bool(filter)), int(max_moves), d_winner, d_values, d_status, stream))
 
 
+# ---------------- K12: the referee of a match between two search handles (gmk_match_referee) and what its callers share ----------------
+MATCH_MOVED, MATCH_REFUSED, MATCH_ENDED, MATCH_OVER = 0, 1, 2, 3      # the referee's verdicts (include/gomoku_hip.h)
+MATCH_STATUS_REFUSED, MATCH_STATUS_BAD_ROW = 1, 2                      # bits of the referee's status words
+
+
+def _current_stream(stream):
+    import torch
+    return torch.cuda.current_stream().cuda_stream if stream is None else stream
+
+
+def _root_choice(entry, tree, cells, visits, stream):
+    import torch
+    assert cells.is_cuda and cells.dtype == torch.int16 and cells.shape == (tree.n,) and cells.is_contiguous()
+    assert visits is None or (visits.is_cuda and visits.element_size() == 2 and visits.shape == (tree.n, N) and visits.is_contiguous())
+    _check(entry(tree.h, cells.data_ptr(), None if visits is None else visits.data_ptr(), _current_stream(stream)))
+
+
+def _check_step_device(tree, cells, verdict):
+    import torch
+    assert cells.is_cuda and cells.dtype == torch.int16 and cells.shape == (tree.n,) and cells.is_contiguous()
+    assert verdict.is_cuda and verdict.dtype == torch.int32 and verdict.shape == (tree.n,) and verdict.is_contiguous()
+
+
+def match_referee(cells, visit_rows, row_of, moves, lens, winner, visits, verdict, status, unfinished, stream=None):
+    """gmk_match_referee: one ply of n games on the device.  cells int16[n], visit_rows 2-byte [n, 225] or None, row_of int32[n] or None
+    (slot -> record row), the records moves uint8[rows, 225] / lens int32[rows] / winner int8[rows] / visits 2-byte [rows, 225, 225] or None,
+    verdict int32[n] (MATCH_*, in and out), status int32[n], unfinished int32[1]: torch tensors on the GPU."""
+    import torch
+    n, rows = int(cells.shape[0]), int(lens.shape[0])
+    assert cells.dtype == torch.int16 and cells.is_contiguous() and verdict.dtype == torch.int32 and verdict.shape == (n,) and status.dtype == torch.int32 and status.shape == (n,)
+    assert unfinished.dtype == torch.int32 and unfinished.numel() == 1
+    assert moves.dtype == torch.uint8 and moves.shape == (rows, N) and moves.is_contiguous() and lens.dtype == torch.int32 and winner.dtype == torch.int8 and winner.shape == (rows,)
+    assert visit_rows is None or (visit_rows.element_size() == 2 and visit_rows.shape == (n, N) and visit_rows.is_contiguous())
+    assert visits is None or (visits.element_size() == 2 and visits.shape == (rows, N, N) and visits.is_contiguous())
+    assert row_of is None or (row_of.dtype == torch.int32 and row_of.shape == (n,) and row_of.is_contiguous())
+    assert all(t is None or t.is_cuda for t in (cells, visit_rows, row_of, moves, lens, winner, visits, verdict, status, unfinished))
+    opt = lambda t: None if t is None else t.data_ptr()
+    _check(load().gmk_match_referee(n, rows, cells.data_ptr(), opt(visit_rows), opt(row_of), moves.data_ptr(), lens.data_ptr(), winner.data_ptr(), opt(visits),
+                                    verdict.data_ptr(), status.data_ptr(), unfinished.data_ptr(), _current_stream(stream)))
+
+
 # ---------------- K6: pattern-guided search (TraditionalPolicy), one tree + one evaluator per game ----------------
 class TraditionalMCTS:
     """n_games searches of MCTS(policy=TraditionalPolicy(c_puct)) run side by side on the GPU (gmk_trad_*).
@@ -713,6 +760,16 @@ class TraditionalMCTS:
             m = np.ascontiguousarray(moves, dtype=np.int16)
             assert m.shape == (self.n,)
             _check(load().gmk_trad_step(self.h, m.ctypes.data))
+
+    def root_choice(self, cells, visits=None, stream=None):
+        """gmk_trad_root_choice: root_stats()["best"] into cells (torch int16[n] on the GPU) and the root children's visit counts by cell,
+        saturated at 65 535, into visits (2-byte torch [n, 225], or None); nothing comes to the host."""
+        _root_choice(load().gmk_trad_root_choice, self, cells, visits, stream)
+
+    def step_device(self, cells, verdict, fresh_root=False, stream=None):
+        """gmk_trad_step_device: step() with the cells (torch int16[n]) and the referee's verdicts (torch int32[n], MATCH_*) on the GPU."""
+        _check_step_device(self, cells, verdict)
+        _check(load().gmk_trad_step_device(self.h, cells.data_ptr(), verdict.data_ptr(), int(bool(fresh_root)), _current_stream(stream)))
 
     def add_root_noise(self, alpha=0.05, epsilon=0.25, seed=DEFAULT_SEED, first_game_id=0):
         _check(load().gmk_trad_add_root_noise(self.h, alpha, epsilon, seed, first_game_id))
@@ -878,6 +935,21 @@ class AlphaZeroMCTS:
             m = np.ascontiguousarray(moves, dtype=np.int16)
             assert m.shape == (self.n,)
             _check(load().gmk_az_step(self.h, m.ctypes.data))
+
+    def root_choice(self, cells, visits=None, stream=None):
+        """gmk_az_root_choice: the most visited root child (first maximum in cell order, -1 without one) into cells (torch int16[n] on the
+        GPU) and the root children's visit counts by cell, saturated at 65 535, into visits (2-byte torch [n, 225], or None)."""
+        _root_choice(load().gmk_az_root_choice, self, cells, visits, stream)
+
+    def step_device(self, cells, verdict, fresh_root=False, unfinished=None, stream=None):
+        """gmk_az_step_device: step() with the cells (torch int16[n]) and the referee's verdicts (torch int32[n], MATCH_*) on the GPU; games that
+        ended leave the leaf batch.  unfinished: the referee's counter (torch int32[1]); its value is returned (else None)."""
+        _check_step_device(self, cells, verdict)
+        count = C.c_int32(0)
+        _check(load().gmk_az_step_device(self.h, cells.data_ptr(), verdict.data_ptr(), int(bool(fresh_root)), None if unfinished is None else unfinished.data_ptr(),
+                                         None if unfinished is None else C.byref(count), _current_stream(stream)))
+        self._refresh_live()
+        return None if unfinished is None else count.value
 
     def set_slots(self, n_total, open_moves=None, open_lens=None):
         """Continuous batching (gmk_az_set_slots): the n slots of this handle play n_total games between them, from their openings

@@ -713,6 +713,184 @@ def play_match_games(n_games, supervisor, candidate, playouts=400, seed=G.DEFAUL
     return rec, sup_black
 
 
+def evaluation_sides(n_games):
+    """network_is_black bool[n]: eval_agents exchanges the start player after every game (agents/utils.py:82-93), so the first agent --
+    the network -- has black in game i iff i is even."""
+    return np.arange(int(n_games)) % 2 == 0
+
+
+def evaluation_scores(winner, network_is_black):
+    """eval_agents' count (agents/utils.py:84-89) per game: 1 for a win of the network, 0 for a loss, 0.5 for a tie; winner +1 black, -1 white,
+    0 tie.  The win rate is their mean."""
+    winner, black = np.asarray(winner).astype(np.int64), np.asarray(network_is_black, dtype=bool)
+    return np.where(winner == 0, 0.5, np.where((winner > 0) == black, 1.0, 0.0))
+
+
+_EVAL_OPPONENTS = ("traditional_mcts", "rave_mcts", "random_mcts")
+
+
+class _EvalOpponent:
+    """The opponent's side of one group of play_evaluation_games: a K6 / K8 handle that keeps its trees (or gets fresh roots), or -- on the
+    host loop only -- the K3 searcher of play_match_games, which starts every search from fresh roots."""
+
+    def __init__(self, spec, idx, moves, lens, seed, first_game_id, reuse_subtree):
+        kind, kw = spec
+        self.kind, self.idx, self.reuse, self.seed, self.first = kind, idx, reuse_subtree, seed, first_game_id
+        self.playouts = int(kw.get("c_iterations", 400))
+        k, c_puct = len(idx), float(kw.get("c_puct", 5.0))
+        if kind == "random_mcts":
+            self.searcher, self.tree = _Searcher(spec, k, self.playouts, seed, first_game_id), None
+            return
+        cap = min((3 if reuse_subtree else 1) * self.playouts * 226 + 256, (1 << 24) - 1)
+        if kind == "rave_mcts":
+            self.tree = G.PoolRAVEMCTS(k, node_capacity=cap, c_puct=c_puct, seed=seed, first_game_id=first_game_id)
+        elif kw.get("use_rave"):
+            self.tree = G.TraditionalRAVEMCTS(k, node_capacity=cap, c_puct=c_puct, c_bias=float(kw.get("c_bias", 0.0)))
+        else:
+            self.tree = G.TraditionalMCTS(k, node_capacity=cap, c_puct=c_puct)
+        self.tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS["counter"])
+        self.tree.set_game_ids(np.asarray(idx, dtype=np.uint32))
+        self.tree.set_positions(moves, lens)
+
+    def add_root_noise(self, root_noise):
+        if root_noise is not None and self.tree is not None:
+            self.tree.add_root_noise(root_noise[0], root_noise[1], seed=self.seed, first_game_id=self.first)
+
+    def overflow(self):
+        return self.tree is not None and bool((self.tree.root_stats()["status"] & G.TraditionalMCTS.STATUS_ARENA_FULL).any())
+
+    def close(self):
+        (self.tree if self.tree is not None else self.searcher).close()
+
+
+def play_evaluation_games(n_games, network, opponent, playouts=400, c_puct=5.0, seed=G.DEFAULT_SEED, first_game_id=0, opening_plies=0, max_moves=N,
+                          reuse_subtree=True, root_noise=(0.05, 0.25), device_loop=None, device=None):
+    """The reference's evaluation match (network/train.py:88-126 evaluate_network -> agents/utils.py:66-100 eval_agents): n_games games of the
+    network-guided searcher (K7 with `network` = network.FusedPolicyValueNetwork at the leaves, `playouts` playouts a move) against
+    `opponent` = (name, kwargs) as in DATA_CONFIG["schedule"] ("traditional_mcts" -- with {"use_rave": True} TraditionalPolicy + RAVE --,
+    "rave_mcts" or "random_mcts"; kwargs["c_iterations"] is its playout budget).  The network has black in game i iff i is even.  The games
+    with the network as black and the others form two groups, each with one K7 handle and one opponent handle; every ply of a group is one
+    search by the side to move, whose choice both trees follow.  reuse_subtree: each agent keeps its own tree through the game and follows the
+    opponent's move by stepForward(move) (MCTS.cpp:119-147), and root_noise = (alpha, epsilon) is mixed into the mover's root priors before
+    every search (MCTS.cpp:182) by the counter-based sampler keyed by first_game_id + i; otherwise every search starts from a fresh root.
+    device_loop=True: root choice, referee (K12: the record, the end-of-game test) and both steps are kernels on the current stream and the
+    host sees the count of unfinished games per ply; False: the same match through the host (root_stats down, numpy boards, moves up);
+    None: the device loop, except for "random_mcts" (the gmk_mcts handle), which the host loop serves, from fresh roots at every move.
+    A mover whose root has no child to play leaves its game where it stands (it cannot happen on a board with an empty cell).
+    Returns (GameRecords, network_is_black bool[n], scores float[n]); the records' visit counts at move i are the mover's, and
+    records.groups lists per group the games, the unfinished count and the K7 handle's live games after the loop."""
+    kind = opponent[0]
+    if kind not in _EVAL_OPPONENTS:
+        raise ValueError("play_evaluation_games: unknown opponent '%s' (%s)" % (kind, ", ".join(_EVAL_OPPONENTS)))
+    if device_loop and kind == "random_mcts":
+        raise ValueError("play_evaluation_games: random_mcts (the gmk_mcts handle) is served by the host loop only: device_loop=False or None")
+    if device_loop is None:
+        device_loop = kind != "random_mcts"
+    if opening_plies > 8:
+        raise ValueError("play_evaluation_games: openings of at most 8 plies (an opening cannot be a finished game)")
+    G.init(torch.cuda.current_device() if device is None else device.index)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    black = evaluation_sides(n_games)
+    games = _HostGames(n_games)
+    if opening_plies > 0:
+        m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
+        games.open_with(m, l, opening_plies)
+    start = int(games.lens[0]) if n_games else 0
+    assert (games.lens == start).all() and not games.over.any()
+    if device_loop:
+        d_moves, d_lens = torch.from_numpy(games.moves).to(dev), torch.from_numpy(games.lens).to(dev)
+        d_winner = torch.zeros(n_games, dtype=torch.int8, device=dev)
+        d_visits = torch.zeros((n_games, N, N), dtype=torch.int16, device=dev)
+    else:
+        visits = np.zeros((n_games, N, N), dtype=np.uint16)
+    overflow, groups = False, []
+    net_cap = min((3 if reuse_subtree else 1) * playouts * N + 1, (1 << 24) - 1)
+    for gi, idx in enumerate((np.nonzero(black)[0], np.nonzero(~black)[0])):
+        k = len(idx)
+        if k == 0:
+            groups.append({"games": idx, "unfinished": 0, "live_games": 0})
+            continue
+        net = G.AlphaZeroMCTS(k, node_capacity=net_cap, c_puct=c_puct)
+        net.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS["counter"])
+        net.set_game_ids(np.asarray(idx, dtype=np.uint32))
+        net.set_roots(G.moves_to_planes(games.moves[idx], games.lens[idx]), games.last_two()[idx])
+        opp = _EvalOpponent(opponent, idx, games.moves[idx], games.lens[idx], seed, first_game_id, reuse_subtree)
+        unfinished = k
+        with torch.no_grad():
+            if device_loop:
+                d_idx = torch.from_numpy(idx.astype(np.int32)).to(dev)
+                d_cells, d_rows = torch.full((k,), -1, dtype=torch.int16, device=dev), torch.zeros((k, N), dtype=torch.int16, device=dev)
+                d_verdict, d_status, d_unfinished = torch.zeros(k, dtype=torch.int32, device=dev), torch.zeros(k, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+                for ply in range(max_moves):
+                    net_moves = ((start + ply) % 2 == 0) == (gi == 0)         # group 0: the network has black, i.e. it moves on even stone counts
+                    if net_moves:
+                        if root_noise is not None:
+                            net.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id)
+                        net.search(network, playouts)
+                        net.root_choice(d_cells, d_rows)
+                    else:
+                        opp.add_root_noise(root_noise)
+                        opp.tree.run(opp.playouts, stream)
+                        opp.tree.root_choice(d_cells, d_rows)
+                    G.match_referee(d_cells, d_rows, d_idx, d_moves, d_lens, d_winner, d_visits, d_verdict, d_status, d_unfinished)
+                    opp.tree.step_device(d_cells, d_verdict, fresh_root=not reuse_subtree)
+                    unfinished = net.step_device(d_cells, d_verdict, fresh_root=not reuse_subtree, unfinished=d_unfinished)
+                    if unfinished == 0:
+                        break
+                overflow |= bool((net.root_stats()["status"] & G.AlphaZeroMCTS.STATUS_ARENA_FULL).any())
+            else:
+                for ply in range(max_moves):
+                    if games.over[idx].all():
+                        break
+                    net_moves = ((start + ply) % 2 == 0) == (gi == 0)
+                    if net_moves:
+                        if ply > 0 and not reuse_subtree:
+                            net.set_roots(G.moves_to_planes(games.moves[idx], games.lens[idx]), games.last_two()[idx])
+                        if root_noise is not None:
+                            net.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id)
+                        net.search(network, playouts)
+                        st = net.root_stats()
+                        overflow |= bool((st["status"] & G.AlphaZeroMCTS.STATUS_ARENA_FULL).any())
+                        v, best = st["visits"], np.where(st["visits"].max(1) > 0, st["visits"].argmax(1), -1)      # max_element: the first maximum in cell order
+                    elif opp.tree is None:
+                        v, best, full = opp.searcher.search(games.moves[idx], games.lens[idx], idx, stream)
+                        overflow |= full
+                    else:
+                        if ply > 0 and not reuse_subtree:
+                            opp.tree.set_positions(games.moves[idx], games.lens[idx])
+                        opp.add_root_noise(root_noise)
+                        opp.tree.run(opp.playouts, stream)
+                        st = opp.tree.root_stats()
+                        v, best = st["visits"], st["best"]
+                    step = np.where(games.over[idx], -1, best).astype(np.int16)
+                    played = np.full(n_games, -1, dtype=np.int64)
+                    played[idx] = step
+                    at = games.lens.copy()
+                    moved = games.apply(played)
+                    slot_of = np.full(n_games, -1, dtype=np.int64)
+                    slot_of[idx] = np.arange(k)
+                    visits[moved, at[moved]] = np.minimum(v[slot_of[moved]], 65535)
+                    if reuse_subtree:
+                        net.step(step)
+                        if opp.tree is not None:
+                            opp.tree.step(step)
+                unfinished = int((~games.over[idx]).sum())
+            overflow |= opp.overflow()
+        groups.append({"games": idx, "unfinished": unfinished, "live_games": net.live})
+        opp.close()
+        net.close()
+    if device_loop:
+        rec = GameRecords(d_moves, d_lens, d_winner, d_visits, first_game_id, overflow)
+        winner = d_winner.cpu().numpy()
+    else:
+        rec = GameRecords(torch.from_numpy(games.moves).to(dev), torch.from_numpy(games.lens).to(dev), torch.from_numpy(games.winner).to(dev),
+                          torch.from_numpy(visits.view(np.int16)).to(dev), first_game_id, overflow)
+        winner = games.winner
+    rec.groups = groups
+    return rec, black, evaluation_scores(winner, black)
+
+
 def play_pattern_games(n_games, opening_plies=4, seed=G.DEFAULT_SEED, first_game_id=0, filter=True, max_moves=N, device=None):
     """n_games whole games of the search-free pattern policy against itself (K10, gmk_pattern_play): every ply is the first maximum of
     Heuristic::EvaluationProbs -- after DecisiveFilter with filter=True (PatternEvalAgent), without it Heuristic::MaxEvaluatedRollout -- on the

@@ -8,13 +8,65 @@ Play, keep, draw, learn, hand the new weights to the searcher -- all in HBM on o
     loop = TrainingLoop(replay, trainer, fused, export_every=1)
     loop.run(100, play=lambda: selfplay.play_network_games(32, fused, playouts=400))
 
-`play` returns a GameRecords with visit counts on the buffer's device (or None); the loop appends it before every step.  The win-rate
-schedule of the reference (evaluate_network / eval_agents, train.py:88-126) is not part of this loop.
+`play` returns a GameRecords with visit counts on the buffer's device (or None); the loop appends it before every step.
+
+The win-rate schedule of the reference (evaluate_network / eval_agents, train.py:88-126) is EvaluationSchedule; with eval_period the loop
+plays its match every eval_period steps (selfplay.play_evaluation_games: K7 + K9 against the current opponent, refereed on the device):
+
+    loop = TrainingLoop(replay, trainer, fused, eval_period=100, on_best=save, on_checkpoint=save)
 """
+
+# DATA_CONFIG["schedule"] of the reference (config.py:8-20) without its two botzone programs, which do not exist here
+SUPERVISOR = ("traditional_mcts", {"c_puct": 5.0, "c_iterations": 20000})
+CANDIDATES = (("random_mcts", {"c_puct": 5.0, "c_iterations": 400}), ("rave_mcts", {"c_puct": 5.0, "c_iterations": 400}), None)
+
+
+class EvaluationSchedule:
+    """The state evaluate_network keeps (train.py:30-32) and its rules (:93-123): the network meets candidates[schedule_level] (None = the
+    supervisor) at ref_iterations playouts; a win rate above best_win_rate is a new best, and one that reaches 1 - 0.05 * level powers an
+    MCTS opponent up by 2 * c_iterations or, past 20 000, moves on to the next candidate."""
+
+    def __init__(self, supervisor=SUPERVISOR, candidates=CANDIDATES, eval_rounds=11, c_iterations=400):
+        if not candidates:
+            raise ValueError("EvaluationSchedule: at least one candidate (None = the supervisor)")
+        self.supervisor, self.candidates = supervisor, list(candidates)
+        self.eval_rounds, self.c_iterations = int(eval_rounds), int(c_iterations)
+        self.schedule_level, self.ref_iterations, self.best_win_rate = 0, self.c_iterations, 0.0
+
+    def opponent(self):
+        """(name, kwargs) of the agent to play now; an MCTS agent is powered up to ref_iterations (train.py:93-99)."""
+        spec = self.candidates[self.schedule_level]
+        name, kwargs = spec if spec is not None else self.supervisor
+        kwargs = dict(kwargs)
+        if "mcts" in name:
+            kwargs["c_iterations"] = self.ref_iterations
+        return name, kwargs
+
+    def update(self, win_rate):
+        """train.py:105-123 for one evaluation's win rate.  -> {"new_best", "level_up", "next_candidate"}; the opponent that was played is
+        the one opponent() named BEFORE the call."""
+        events = {"new_best": False, "level_up": False, "next_candidate": False}
+        if win_rate > self.best_win_rate:
+            events["new_best"] = True
+            if win_rate >= 1.0 - 0.05 * self.schedule_level:        # levelup threshold decay
+                events["level_up"] = True
+                is_mcts = "mcts" in self.opponent()[0]
+                if is_mcts:
+                    self.ref_iterations += 2 * self.c_iterations
+                if not is_mcts or self.ref_iterations > 20000:
+                    self.ref_iterations = self.c_iterations
+                    if self.schedule_level + 1 < len(self.candidates):      # (the reference would index past its list: the last level stays)
+                        self.schedule_level += 1
+                        events["next_candidate"] = True
+                self.best_win_rate = 0.0
+            else:
+                self.best_win_rate = win_rate
+        return events
 
 
 class TrainingLoop:
-    def __init__(self, replay, trainer, fused=None, batch_size=512, lr=2e-3, kl_target=0.02, num_epoches=5, export_every=1):
+    def __init__(self, replay, trainer, fused=None, batch_size=512, lr=2e-3, kl_target=0.02, num_epoches=5, export_every=1,
+                 eval_period=None, schedule=None, eval_playouts=400, eval_options=None, on_best=None, on_checkpoint=None):
         if batch_size < 1 or batch_size > trainer.max_batch:
             raise ValueError("TrainingLoop: batch_size must be in [1, trainer.max_batch]")
         if export_every < 1:
@@ -24,6 +76,13 @@ class TrainingLoop:
         self.lr_multiplier = 1.0
         self.total_steps = 0
         self.history = []                         # one dict per step: loss, entropy, kl, epochs, lr (the rate the step used), exported
+        if eval_period is not None and eval_period < 1:
+            raise ValueError("TrainingLoop: eval_period must be at least 1 (None: no evaluation)")
+        # every eval_period steps: schedule.eval_rounds games of `fused` (eval_playouts playouts a move) against schedule.opponent();
+        # eval_options: further keywords of selfplay.play_evaluation_games; on_best(name) / on_checkpoint(name) are where a caller saves the model
+        self.eval_period = None if eval_period is None else int(eval_period)
+        self.schedule = schedule if schedule is not None or eval_period is None else EvaluationSchedule()
+        self.eval_playouts, self.eval_options, self.on_best, self.on_checkpoint = int(eval_playouts), dict(eval_options or {}), on_best, on_checkpoint
 
     def step(self):
         """One train_network: draw a minibatch, train_step on it, tune the learning-rate multiplier by the KL (train.py:73-77), and every
@@ -40,6 +99,36 @@ class TrainingLoop:
         if exported:
             self.trainer.export(self.fused)
         record = {"loss": loss, "entropy": entropy, "kl": kl, "epochs": epochs, "lr": lr, "exported": exported}
+        self.history.append(record)
+        if self.eval_period is not None and self.total_steps % self.eval_period == 0:
+            if self.fused is None:
+                raise ValueError("TrainingLoop: eval_period needs `fused`, the network the evaluation plays with")
+            if not exported:
+                self.trainer.export(self.fused)
+            self.evaluate(self.fused)
+        return record
+
+    def evaluate(self, network):
+        """evaluate_network (train.py:88-126): eval_rounds games of `network` against the schedule's current opponent, the schedule's update,
+        on_best("best_model-<opponent>-<ref_iterations>") on a new best (:106-110, named before the level-up as the reference names it) and
+        on_checkpoint("current_model-<steps>-<level>-<ref_iterations>-<best win rate, two decimals>") after every evaluation (:126-134).
+        -> the evaluation's record (also appended to self.history)."""
+        from . import selfplay
+        if self.schedule is None:
+            self.schedule = EvaluationSchedule()
+        sch = self.schedule
+        name, kwargs = sch.opponent()
+        played_at = sch.ref_iterations
+        rec, network_is_black, scores = selfplay.play_evaluation_games(sch.eval_rounds, network, (name, kwargs), playouts=self.eval_playouts, **self.eval_options)
+        win_rate = float(scores.mean())
+        events = sch.update(win_rate)
+        if events["new_best"] and self.on_best is not None:
+            self.on_best("best_model-{}-{}".format(name, played_at))
+        checkpoint = "current_model-{}-{}-{}-{:.2f}".format(self.total_steps, sch.schedule_level, sch.ref_iterations, sch.best_win_rate)
+        if self.on_checkpoint is not None:
+            self.on_checkpoint(checkpoint)
+        record = {"evaluation": True, "step": self.total_steps, "opponent": name, "ref_iterations": played_at, "win_rate": win_rate, "scores": scores,
+                  "network_is_black": network_is_black, "schedule_level": sch.schedule_level, "best_win_rate": sch.best_win_rate, "checkpoint": checkpoint, **events}
         self.history.append(record)
         return record
 

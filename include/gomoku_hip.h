@@ -348,6 +348,16 @@ int gmk_trad_root_stats(gmk_trad* t, uint32_t* h_visits, float* h_values, float*
  * subtree is kept (compacted into a second arena), a move without a child starts a new node; the move is appended to the
  * game's position and the next gmk_trad_run synchronises the evaluator (Policy::prepare).  Status bit 3 = not a legal move. */
 int gmk_trad_step(gmk_trad* t, const int16_t* h_moves);
+/* The two calls a device-resident match makes of a K6 / K8 handle (K12, see gmk_match_referee below).
+ * gmk_trad_root_choice: what gmk_trad_root_stats reports as `best` -- the cell MCTS::stepForward() would play, -1 for a root without
+ * children -- as d_cells int16[n], and the root children's visit counts by cell saturated at 65 535 as d_visits uint16[n][225] (may be
+ * NULL), both in device memory, on `stream`; nothing is copied to the host.
+ * gmk_trad_step_device: gmk_trad_step with the cells read from d_cells and the launch on `stream`, steered by the referee's verdicts
+ * d_verdict int32[n] (GMK_MATCH_*): a game that MOVED follows the move, one that ENDED takes the move and goes idle (status bit 4: the
+ * searches skip it), one that was REFUSED or OVER keeps its tree and status.  fresh_root = 0 keeps the subtree as gmk_trad_step does;
+ * fresh_root != 0 leaves a moved game as gmk_trad_set_positions would leave it for the position after the move (a new root at the next search). */
+int gmk_trad_root_choice(gmk_trad* t, int16_t* d_cells, uint16_t* d_visits, void* stream);
+int gmk_trad_step_device(gmk_trad* t, const int16_t* d_cells, const int32_t* d_verdict, int fresh_root, void* stream);
 /* Default::AddNoise on every root with children (the reference does this at the start of every search, MCTS.cpp:182) */
 int gmk_trad_add_root_noise(gmk_trad* t, float alpha, float epsilon, uint64_t seed, uint32_t first_game_id);
 /* TraditionalPolicy(c_puct, use_rave = true) (agents/mcts.py:44-47): gmk_trad_run's playout with RAVE::BackPropogate<true> in place of
@@ -425,6 +435,19 @@ int gmk_az_expand(gmk_az* a, const float* d_values, const float* d_probs, void* 
 /* MCTS::stepForward() / stepForward(move) (core/lib/src/MCTS.cpp:129-147) for every game, subtree kept (as gmk_trad_step): h_moves
  * int16[n] = the cell to step to, -1 = the most visited child, NULL = -1 for all; status bit 2 = not a legal move. */
 int gmk_az_step(gmk_az* a, const int16_t* h_moves);
+/* The two calls a device-resident match makes of a K7 handle (K12, see gmk_match_referee below).
+ * gmk_az_root_choice: the most visited root child, first maximum in cell order as gmk_az_advance picks it (-1: no visited child), as
+ * d_cells int16[n], and the root children's visit counts by cell saturated at 65 535 as d_visits uint16[n][225] (may be NULL), both in
+ * device memory, on `stream`; nothing is copied to the host.
+ * gmk_az_step_device: gmk_az_step with the cells read from d_cells and the launch on `stream`, steered by the referee's verdicts
+ * d_verdict int32[n] (GMK_MATCH_*): a game that MOVED follows the move, one that ENDED is closed as gmk_az_advance closes one (status
+ * bit 0; the leaf batch is compacted, so gmk_az_live_games drops), one that was REFUSED or OVER keeps its tree and status.  fresh_root = 0
+ * keeps the subtree as gmk_az_step does; fresh_root != 0 makes the root gmk_az_set_roots makes for the position after the move.
+ * The call waits for the stream once, for the number of live games; with h_unfinished it brings the referee's count d_unfinished
+ * (int32[1], device) along in the same wait -- the four bytes the host sees of a match ply. */
+int gmk_az_root_choice(gmk_az* a, int16_t* d_cells, uint16_t* d_visits, void* stream);
+int gmk_az_step_device(gmk_az* a, const int16_t* d_cells, const int32_t* d_verdict, int fresh_root, const int32_t* d_unfinished, int32_t* h_unfinished,
+                       void* stream);
 /* One self-play move for every game still played, on the device (replaces the per-ply host work of the reference's self-play loop,
  * network/data_helper.py:56-83 with agents/alphazero.py:5-9 on both sides, as gmk_mcts_advance does for K3): the most visited child of
  * the root (first maximum in cell order, MCTS.cpp:129-134) is appended to the game's record with the root's visit counts, played on the
@@ -472,6 +495,28 @@ int gmk_az_write_stats_host(gmk_az* a, int game, const uint32_t* h_nodes, const 
 /* host outputs, any may be NULL; status bit 0 = the game is over (gmk_az_advance), bit 1 = node arena full (playouts of that game were dropped) */
 int gmk_az_root_stats(gmk_az* a, uint32_t* h_visits, float* h_values, float* h_priors, uint32_t* h_root_visits,
                       float* h_root_value, int32_t* h_n_nodes, int32_t* h_status);
+
+/* ---- K12: the referee of a match between two search handles, on the device (match_kernel.hip) ----
+ * One ply of n two-agent games without the host in the loop (agents/utils.py:13-63 dual_play, :66-100 eval_agents): the side to move has
+ * searched; gmk_az_root_choice or gmk_trad_root_choice leaves its cells and visit rows in device memory; gmk_match_referee plays them on
+ * the game records; gmk_trad_step_device and gmk_az_step_device make both trees follow.
+ * The referee, one wavefront per game: slot g plays the record row d_row_of[g] (int32[n], NULL: row g; rows = the records' row count) of
+ * d_moves uint8[rows][225], d_lens int32[rows], d_winner int8[rows], d_visits uint16[rows][225][225] (may be NULL).  For every game that
+ * is still running it rebuilds the position from the record, refuses a cell that is off the board or occupied (the record stays as it is
+ * and bit 0 of d_status[g] is set; bit 1: d_row_of[g] is not a row), and otherwise plays it with Board::applyMove's end test (Game.cpp:37-49,
+ * 88-136: five or more through the new stone, or a full board as a tie), appends the move and the visit row d_visit_rows[g] (uint16[n][225],
+ * NULL: zeros) to the record and writes the winner of a game that ended.
+ * d_verdict int32[n] is the state of the games and the referee's word to the step calls; the caller zeroes it (GMK_MATCH_MOVED) before
+ * the first ply, or sets GMK_MATCH_OVER for a game that is not to be played, and zeroes d_status:
+ *   GMK_MATCH_MOVED 0    the cell was played, the game goes on          GMK_MATCH_REFUSED 1   the game did not move and goes on
+ *   GMK_MATCH_ENDED 2    the cell was played and ended the game         GMK_MATCH_OVER 3      the game was over before this ply
+ * d_unfinished int32[1]: the games that go on (MOVED or REFUSED) after this ply. */
+#define GMK_MATCH_MOVED 0
+#define GMK_MATCH_REFUSED 1
+#define GMK_MATCH_ENDED 2
+#define GMK_MATCH_OVER 3
+int gmk_match_referee(int n, int rows, const int16_t* d_cells, const uint16_t* d_visit_rows, const int32_t* d_row_of, uint8_t* d_moves, int32_t* d_lens,
+                      int8_t* d_winner, uint16_t* d_visits, int32_t* d_verdict, int32_t* d_status, int32_t* d_unfinished, void* stream);
 
 /* ---- K9: the convolutional trunk of the policy-value network (the evaluator K7 calls at every leaf) as one fused kernel ----
  * Replaces the convolution layers of PolicyValueNetwork (network/model_tf.py:28-66: conv3x3 6->32->64->128 with ReLU, the 1x1
