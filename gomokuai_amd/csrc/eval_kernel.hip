@@ -26,7 +26,8 @@
 //   * phase 2: one lane per queued transition: one 16-byte record read gives the (<= 2) matches, each with a
 //     compact list of <= 4 score deposits -- a colour's own and opponent view of a cell are the halves of one 64-bit word, so a deposit is ONE
 //     ds_add_u64 whose value decides -- and 4-bit per-(cell, colour, direction, type) counters;
-//   * phase 3: one lane per cell: compound candidates from the counters; phase 3b: one lane per (candidate, colour):
+//   * phase 3: one lane per cell: compound candidates from the counters -- a colour's half word h of the OR-ed counters makes one iff
+//     h & ((h - 1) | 0xEEEE): v_or3, v_pk_add_u16, v_bitop3, v_cmp per pass in front of the ballot (the static listing, profiles/r10_k1_frame_counts.txt); phase 3b: one lane per (candidate, colour):
 //     the density gate "count >= 2" from seven row popcounts, the compound decision in closed form (components n, threes s), +-600 deposits,
 //     components queued by ballot prefix with their line word and slot in the entry;
 //   * phase 4: seven lanes per compound component, nine per round: its counter-move cells from the 13-symbol window around it (one
@@ -126,12 +127,11 @@ __device__ __forceinline__ uint32_t dfa_address(uint32_t table_word, uint32_t fo
     return addr;
 }
 
-// v_mul_u32_u24, written out: once the compiler has proved that only low bits of a product are used it drops the mask that made the factor 24 bits
-// wide and then has to take the full 32-bit multiply, which runs at a quarter of the rate
-__device__ __forceinline__ uint32_t mul24(uint32_t a, uint32_t b) {
-    uint32_t r;
-    asm("v_mul_u32_u24 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b));
-    return r;
+// both 16-bit halves of a word decremented, no borrow from the low half into the high one: one v_pk_sub_u16
+typedef unsigned short v2u16 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pk_dec_u16(uint32_t word) {
+    const v2u16 ones = {1, 1};
+    return __builtin_bit_cast(uint32_t, static_cast<v2u16>(__builtin_bit_cast(v2u16, word) - ones));
 }
 
 // global_store_dword with the address as a wave-uniform 64-bit base in scalar registers plus the lane's unsigned 32-bit byte offset, written out: from
@@ -455,7 +455,8 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
     uint32_t next_black = 0, next_white = 0, cur_black = 0, cur_white = 0;
     auto fetch_row = [&](int b) {
         const uint16_t* p = row_ptr + static_cast<size_t>(min(b, n_boards - 1)) * 32;
-        next_black = p[0];
+        next_black = p[0];                              // (bit 15 of a row is zero, the planes' contract in include/gomoku_hip.h: phase 0's packed gate shifts and the
+                                                        //  white stone count rely on it, nothing here clears it)
         next_white = p[16];
     };
     auto take_row = [&](int lane_m, int b) -> uint32_t { return lane_m < 16 && b < n_boards ? cur_black | (cur_white << 16) : 0u; };
@@ -544,10 +545,12 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                 // of the colour lies under the 7x7 BlockWeights mask (Pattern.cpp:598-609) around the cell: the rows, dilated by the
                 // mask's row patterns -- 1001001 three rows away, 0111110 one and two rows away, 1110111 in the row itself -- and OR-ed
                 // over the seven rows, for both colours at once (black in the low, white in the high half word), restricted to empty cells.
-                // (a shift must not carry bits from one half word into the other: they are cut off first)
                 const uint32_t r = my_row;
-                const uint32_t l1 = (r & 0x3FFF3FFFu) << 1, l2 = (r & 0x1FFF1FFFu) << 2, l3 = (r & 0x0FFF0FFFu) << 3;
-                const uint32_t r1 = (r & 0x7FFE7FFEu) >> 1, r2 = (r & 0x7FFC7FFCu) >> 2, r3 = (r & 0x7FF87FF8u) >> 3;
+                // packed 16-bit shifts: nothing crosses from one half word into the other, so no masks.  Bit 15 of a row is zero (the planes'
+                // contract, include/gomoku_hip.h), so nothing comes down from it; what a left shift leaves there is cut off by `empty` below.
+                const v2u16 rr = __builtin_bit_cast(v2u16, r);
+                const uint32_t l1 = __builtin_bit_cast(uint32_t, static_cast<v2u16>(rr << 1)), l2 = __builtin_bit_cast(uint32_t, static_cast<v2u16>(rr << 2)), l3 = __builtin_bit_cast(uint32_t, static_cast<v2u16>(rr << 3));
+                const uint32_t r1 = __builtin_bit_cast(uint32_t, static_cast<v2u16>(rr >> 1)), r2 = __builtin_bit_cast(uint32_t, static_cast<v2u16>(rr >> 2)), r3 = __builtin_bit_cast(uint32_t, static_cast<v2u16>(rr >> 3));
                 const int far = static_cast<int>(r | l3 | r3), near = static_cast<int>(r | l1 | l2 | r1 | r2);
                 uint32_t g = l1 | l2 | l3 | r1 | r2 | r3;
                 g |= static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, near, 0x111, 0xF, 0xF, true)) | static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, near, 0x101, 0xF, 0xF, true));     // rows y -+ 1
@@ -708,22 +711,20 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                     // clipped to 2 (the reference's 2-bit shift flags), OR-ed over the types, sum to two or more over the directions (only
                     // empty cells have counters: a '_' piece is a blank).  Decided in phase 3b, with the density gate of Pattern.cpp:182.
                     const uint32_t any = any_cnt[pass];
-                    const uint32_t upper = (any >> 1) | (any >> 2) | (any >> 3);
-                    // one nibble per (colour, direction): 0, 1 or 2 = the clipped count; the nibbles of a colour summed by one multiplication
-                    const uint32_t clipped = ((any | upper) & 0x11111111u) + (upper & 0x11111111u);
-                    // (24-bit multiplies: bits 12..15 of the product depend on the low sixteen bits of the factor only, and a full 32-bit multiply --
-                    // which the compiler picks once it has dropped the mask -- runs at a quarter of the rate)
-                    // The sums land at bits 12..15 (white) and 16..19 (black); "two or more" is then bits 13..15 resp. 17..19 non-zero, and those
-                    // bits ARE the entry's colour flags (no selects to turn them into two flag bits)
-                    uint32_t cand = mul24(clipped, 0x1111u) & 0xE000u;
-                    cand |= mul24(clipped >> 16, 0x11110u) & 0xE0000u;
-                    if (pass == 3 && q >= kCells) cand = 0u;
-                    const unsigned long long pushers = __ballot(cand != 0u);
+                    // A colour's half word h holds its four direction nibbles; "the clipped counts sum to two or more" is "a nibble is >= 2 or two
+                    // nibbles are non-zero", and that is h & ((h - 1) | 0xEEEE) != 0: a nibble >= 2 has one of its upper three bits set; with every
+                    // nibble 0 or 1, h & (h - 1) is h without its lowest set bit.  Both colours at once: a packed 16-bit decrement (no borrow
+                    // from white's half into black's) and one three-operand bit operation.  The exact sums are not needed: phase 3b works
+                    // everything out from the counters again and only asks which colour made the cell a candidate.
+                    const uint32_t hot = any & (pk_dec_u16(any) | 0xEEEEEEEEu);
+                    // (the last pass has 33 cells: the lanes behind them read cell 224 again and are cut out of the ballot on the scalar unit)
+                    const unsigned long long pushers = __ballot(hot != 0u) & (pass < 3 ? ~0ull : (1ull << (kCells - 192)) - 1ull);
                     if (pushers) {
-                        if (cand) {
+                        if (hot != 0u && (pass < 3 || lane < kCells - 192)) {
                             const int slot = n_cand + static_cast<int>(__builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(pushers >> 32),
                                                                        __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(pushers), 0u)));
-                            if (slot < kQueueCap / 2) s_queue[slot] = static_cast<uint32_t>(q) | cand;
+                            // the entry: the cell, bit 8: white's counters made it a candidate, bit 9: black's
+                            if (slot < kQueueCap / 2) s_queue[slot] = static_cast<uint32_t>(q) | ((hot & 0xFFFFu) ? 0x100u : 0u) | ((hot >> 16) ? 0x200u : 0u);
                         }
                         n_cand += __popcll(pushers);
                     }
@@ -747,12 +748,12 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
             if (phase_mask & 8)
             for (int v0 = 0; v0 < 2 * n_cand; v0 += 64) {           // one lane per (candidate cell, colour): 0 white, 1 black
                 const int v = v0 + lane;
-                const int flag_shift = 13 + 4 * (v & 1);           // this lane's colour flags in a candidate entry (bits 13..15 white, 17..19 black)
+                const int flag_shift = 8 + (v & 1);                // this lane's colour flag in a candidate entry (bit 8 white, bit 9 black)
                 const uint32_t ce = s_queue[v >> 1];                // (< n_cand + 32 <= 256: inside the queue; lanes past the end are masked below)
                 const int q = ce & 255, c = v & 1;
                 bool queue = false;
                 uint32_t ent1 = 0, ent2 = 0;
-                if (v < 2 * n_cand && ((ce >> flag_shift) & 7u)) {
+                if (v < 2 * n_cand && ((ce >> flag_shift) & 1u)) {
                     // this colour's four direction nibbles of the three counter words (read together with the rows below: one round trip)
                     const uint32_t f3 = (s_cnt[q] >> (16 * c)) & 0xFFFFu, fd = (s_cnt[kCells + q] >> (16 * c)) & 0xFFFFu, f2 = (s_cnt[2 * kCells + q] >> (16 * c)) & 0xFFFFu;
                     // the density gate (Pattern.cpp:182): the colour's density COUNT at the cell must be two or more: its stones under the
