@@ -11,6 +11,8 @@
 //     the network           any callable on that batch (PyTorch-ROCm PolicyValueNetwork, network/model_tf.py:28-66)
 //     az_expand_kernel      children with the returned priors, value backed up to the root
 // all on one HIP stream (the three steps can be captured in a hipGraph and replayed per playout).
+// With GMK_OPT_AZ_LEAVES = L > 1 a step takes up to L leaves from every game, steered apart by virtual loss, and the batch has live x L rows:
+// az_select_leaves_kernel / az_expand_leaves_kernel below, for searches of few games.
 // Mapping: one wavefront per game, lanes over the (<= 225) children; the tree is an SoA arena per game in HBM.
 #include <algorithm>
 #include <cmath>
@@ -40,7 +42,9 @@ struct AzHeader {                                // 256 B per game, in HBM
     uint32_t status;                             // bit 0: the game is over (az_advance_kernel), bit 1: node arena full, bit 2: a forced step was not a move of the game
     uint32_t leaf, leaf_pending;                 // node waiting for the network's answer (leaf_pending = 1)
     uint32_t leaf_stones;
-    uint32_t pad[24];
+    uint32_t quota;                              // several leaves per step: the playouts the game still owes (gmk_az_add_playouts)
+    uint32_t n_pending;                          //   leaves waiting for the network's answer (AzLeaves::pend), 0 between steps
+    uint32_t pad[22];
 };
 static_assert(sizeof(AzHeader) == 256, "AzHeader layout");
 
@@ -201,6 +205,216 @@ void az_expand_kernel(AzTree t, const float* __restrict__ values, const float* _
         if (stages & 2) backup(t.stat + arena, t.parent + arena, leaf, -values[row]);  // node_value = -state_value (MCTS.cpp:166-168)
         hdr->leaf_pending = 0;
     }
+}
+
+// ---- Several leaves per game per step, with virtual loss (GMK_OPT_AZ_LEAVES = L > 1) ----
+// A search of few games gives the network a batch of few rows; with L leaves per game a step carries live x L rows and a search of P playouts
+// takes about P / L steps.  The descents of one step are steered apart by a per-node in-flight count v (a side array, all zero between
+// steps): a child with real statistics (N, Q) and v descents in flight below it is scored as if each of them had already come back lost,
+//     q_eff = v == 0 ? Q : (Q N - v) / (N + v)      n_i = N + v + 1      sqrt_n = sqrt(N_parent + v_parent)      (all in double)
+// in the expression of az_select_kernel; with every v zero it is that kernel's formula.  Every game owes `quota` playouts
+// (gmk_az_add_playouts); a step makes min(L, quota) descents, one after the other:
+//     the game is over at the leaf   the real value is backed up at once, quota - 1, no row; the next descent sees the new statistics
+//     a childless leaf with v > 0    it waits for the network already (a collision): the step's descents end here, nothing is counted
+//     otherwise                      v + 1 from the root to the leaf, the leaf is the k-th pending leaf, its planes are row row_of * L + k,
+//                                    quota - 1
+// and the rows k >= n_pending of the game's L rows are zeros.  The first descent of a step cannot collide, so a game that owes playouts
+// completes at least one per step.  az_expand_leaves_kernel answers the pending leaves in their order (which fixes the node numbering):
+// Default::Expand from row k, -value[row] backed up -- or status bit 1 and no backup where the children do not fit --, v - 1 from the leaf up.
+// Lane 0 writes the marks, the backups and the row words; the 64 lanes read them in the next descent: a workgroup-scope fence and a barrier
+// stand between the two (nothing is shared between games).  One wavefront per game, no synchronisation with the host.
+struct AzPending {                               // 80 B
+    uint32_t node, stones, pad[2];
+    uint32_t rows[16];                           // the leaf's position
+};
+struct AzLeaves {
+    uint16_t* inflight;                          // [n_games][cap] v: descents that passed through the node and wait for the network
+    AzPending* pend;                             // [n_games][GMK_AZ_MAX_LEAVES]
+    int leaves;                                  // L
+};
+
+__global__ __launch_bounds__(64)
+void az_select_leaves_kernel(AzTree t, AzLeaves lv, float* out_states) {
+    __shared__ uint32_t s_rows[16];
+    const int game = blockIdx.x, lane = threadIdx.x;
+    if (game >= t.n_games) return;
+    AzHeader* hdr = t.hdr + game;
+    if (hdr->status & kStatusOver) return;                       // the game is over: it owes nothing and has no rows
+    const size_t row0 = static_cast<size_t>(t.row_of[game]) * lv.leaves;
+    const size_t arena = static_cast<size_t>(game) * t.cap;
+    uint2* stat = t.stat + arena;
+    const uint2* kids = t.kids + arena;
+    const float* prior = t.prior + arena;
+    const uint32_t* parent = t.parent + arena;
+    uint16_t* inflight = lv.inflight + arena;
+    AzPending* pend = lv.pend + static_cast<size_t>(game) * GMK_AZ_MAX_LEAVES;
+    uint32_t quota = hdr->quota;
+    const int descents = static_cast<int>(min(static_cast<uint32_t>(lv.leaves), quota));
+    const int root_stones = static_cast<int>(hdr->stones);
+    const uint32_t root_last = hdr->last_move, root_last2 = hdr->last_move2;
+    int k = 0;                                                   // pending leaves so far
+    for (int d = 0; d < descents; ++d) {
+        if (lane < 16) s_rows[lane] = hdr->rows[lane];
+        __syncthreads();
+        uint32_t node = 0;
+        int stones = root_stones;
+        uint32_t last = root_last, last2 = root_last2;
+        // ---- Default::Select with the in-flight descents counted as losses ----
+        for (;;) {
+            const uint2 kd = kids[node];
+            const uint32_t first = kd.x, n = kd.y & 0xFFu;
+            if (n == 0) break;
+            const double sqrt_n = sqrt(static_cast<double>(stat[node].x + static_cast<uint32_t>(inflight[node])));
+            double best_score = -1.0;
+            uint32_t best_i = 0xFFFFFFFFu;
+            for (uint32_t i = lane; i < n; i += 64) {
+                const uint2 cs = stat[first + i];
+                const uint32_t v_i = inflight[first + i];
+                const double q = static_cast<double>(__uint_as_float(cs.y));
+                const double q_eff = v_i == 0u ? q : (q * static_cast<double>(cs.x) - static_cast<double>(v_i)) / static_cast<double>(cs.x + v_i);
+                const double p_i = prior[first + i], n_i = static_cast<double>(cs.x + v_i + 1u);
+                const double score = q_eff + t.c_puct * p_i * sqrt_n / n_i;
+                if (score > best_score) { best_score = score; best_i = i; }
+            }
+#pragma unroll
+            for (int s = 32; s > 0; s >>= 1) {                                         // first maximum, strict '>'
+                const double os = __shfl_down(best_score, s);
+                const uint32_t oi = __shfl_down(best_i, s);
+                if (os > best_score || (os == best_score && oi < best_i)) { best_score = os; best_i = oi; }
+            }
+            best_i = __shfl(best_i, 0);
+            if (best_i == 0xFFFFFFFFu) best_i = 0;
+            node = first + best_i;
+            const uint32_t cell = (kids[node].y >> 8) & 0xFFu;
+            if (lane == 0) s_rows[cell / 15] |= 1u << (cell % 15 + ((stones & 1) ? 16 : 0));
+            __syncthreads();
+            ++stones;
+            last2 = last;
+            last = cell;
+        }
+        // ---- Board::checkGameEnd, as az_select_kernel ----
+        bool ended = false;
+        int winner = 0;
+        if (stones > 0 && last < 225u) {
+            const int mover_white = (stones - 1) & 1;
+            if (five_through<1>(s_rows, last % 15, last / 15, mover_white ? 16 : 0)) { ended = true; winner = mover_white ? -1 : 1; }
+        }
+        if (!ended && stones == kCells) ended = true;
+        bool collided = false;
+        if (ended) {
+            const int node_player = (stones & 1) ? 1 : -1;
+            if (lane == 0) backup(stat, parent, node, static_cast<float>(node_player * winner));
+            --quota;
+        } else if (inflight[node] != 0) {
+            collided = true;
+        } else {
+            if (lane == 0) {
+                for (uint32_t up = node; up != kNoNode; up = parent[up]) inflight[up] = static_cast<uint16_t>(inflight[up] + 1u);
+                pend[k].node = node;
+                pend[k].stones = static_cast<uint32_t>(stones);
+            }
+            if (lane < 16) pend[k].rows[lane] = s_rows[lane];
+            const int cur_white = stones & 1;
+            float* out = out_states + (row0 + static_cast<size_t>(k)) * 6 * kCells;
+            for (int i = lane; i < kCells; i += 64) {
+                const uint32_t row = s_rows[i / 15] >> (i % 15);
+                const bool black = row & 1u, white = (row >> 16) & 1u;
+                out[0 * kCells + i] = (cur_white ? white : black) ? 1.0f : 0.0f;
+                out[1 * kCells + i] = (cur_white ? black : white) ? 1.0f : 0.0f;
+                out[2 * kCells + i] = (!black && !white) ? 1.0f : 0.0f;
+                out[3 * kCells + i] = static_cast<uint32_t>(i) == last ? 1.0f : 0.0f;
+                out[4 * kCells + i] = static_cast<uint32_t>(i) == last2 ? 1.0f : 0.0f;
+                out[5 * kCells + i] = cur_white ? 0.0f : 1.0f;
+            }
+            ++k;
+            --quota;
+        }
+        __threadfence_block();                                   // lane 0's marks and backups, before the next descent reads them
+        __syncthreads();                                         // (and every lane is done with s_rows)
+        if (collided) break;
+    }
+    for (int r = k; r < lv.leaves; ++r) {
+        float* out = out_states + (row0 + static_cast<size_t>(r)) * 6 * kCells;
+        for (int i = lane; i < 6 * kCells; i += 64) out[i] = 0.0f;
+    }
+    if (lane == 0) { hdr->quota = quota; hdr->n_pending = static_cast<uint32_t>(k); hdr->leaf_pending = 0; }
+}
+
+__global__ __launch_bounds__(64)
+void az_expand_leaves_kernel(AzTree t, AzLeaves lv, const float* values, const float* probs) {
+    const int game = blockIdx.x, lane = threadIdx.x;
+    if (game >= t.n_games) return;
+    AzHeader* hdr = t.hdr + game;
+    const int n_pending = static_cast<int>(hdr->n_pending);
+    if (n_pending == 0) return;
+    const size_t row0 = static_cast<size_t>(t.row_of[game]) * lv.leaves;
+    const size_t arena = static_cast<size_t>(game) * t.cap;
+    uint16_t* inflight = lv.inflight + arena;
+    const AzPending* pend = lv.pend + static_cast<size_t>(game) * GMK_AZ_MAX_LEAVES;
+    uint32_t n_nodes = hdr->n_nodes;
+    bool full = false;
+    for (int k = 0; k < n_pending; ++k) {
+        const uint32_t leaf = pend[k].node;
+        // ---- Default::Expand with extraCheck, as az_expand_kernel: probability not 0 and the cell is free; ascending cell id ----
+        const float* p = probs + (row0 + static_cast<size_t>(k)) * kCells;
+        float pv[4];
+        bool take[4];
+        int rank[4], total = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = lane + 64 * j;
+            pv[j] = i < kCells ? p[i] : 0.0f;
+            const uint32_t row = i < kCells ? pend[k].rows[i / 15] >> (i % 15) : 0x10001u;
+            take[j] = i < kCells && pv[j] != 0.0f && !(row & 0x10001u);
+            const unsigned long long b = __ballot(take[j]);
+            rank[j] = total + static_cast<int>(__builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(b >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(b), 0u)));
+            total += __popcll(b);
+        }
+        bool dropped = false;
+        if (total > 0) {
+            if (n_nodes + total > static_cast<uint32_t>(t.cap)) {
+                dropped = full = true;                           // arena full: this playout is dropped, its marks are taken back below
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (take[j]) {
+                        const uint32_t child = n_nodes + rank[j];
+                        t.stat[arena + child] = make_uint2(0u, 0u);
+                        t.kids[arena + child] = make_uint2(0u, static_cast<uint32_t>(lane + 64 * j) << 8);
+                        t.prior[arena + child] = pv[j];
+                        t.parent[arena + child] = leaf;
+                    }
+                if (lane == 0) {
+                    const uint32_t cell_bits = t.kids[arena + leaf].y & 0xFF00u;
+                    t.kids[arena + leaf] = make_uint2(n_nodes, static_cast<uint32_t>(total) | cell_bits);
+                }
+                n_nodes += total;
+            }
+        }
+        __threadfence_block();
+        if (lane == 0) {
+            if (!dropped) backup(t.stat + arena, t.parent + arena, leaf, -values[row0 + k]);
+            for (uint32_t up = leaf; up != kNoNode; up = t.parent[arena + up]) inflight[up] = static_cast<uint16_t>(inflight[up] - 1u);
+        }
+    }
+    if (lane == 0) {
+        hdr->n_nodes = n_nodes;
+        if (full) hdr->status |= 2u;
+        hdr->n_pending = 0;
+    }
+}
+
+__global__ void az_add_playouts_kernel(AzTree t, uint32_t playouts) {
+    const int game = blockIdx.x * blockDim.x + threadIdx.x;
+    if (game >= t.n_games) return;
+    if (!(t.hdr[game].status & kStatusOver)) t.hdr[game].quota += playouts;
+}
+
+__global__ void az_playouts_owed_kernel(AzTree t, int32_t* owed) {
+    const int game = blockIdx.x * blockDim.x + threadIdx.x;
+    if (game >= t.n_games) return;
+    const uint32_t quota = t.hdr[game].quota;
+    if (quota != 0u && !(t.hdr[game].status & kStatusOver)) atomicMax(owed, static_cast<int32_t>(min(quota, 0x7FFFFFFFu)));
 }
 
 // MCTS::stepForward() / stepForward(move) (MCTS.cpp:129-147): the chosen child's subtree becomes the tree, copied level by
@@ -378,6 +592,7 @@ void az_advance_kernel(AzTree t, AzArena b, uint8_t* __restrict__ rec_moves, uin
                 hdr.status |= kStatusOver;
             }
             hdr.leaf_pending = 0;
+            hdr.quota = 0;                                       // a refilled slot owes nothing until the next gmk_az_add_playouts
             hdr.n_nodes = 1;
             t.stat[base] = make_uint2(0u, 0u); t.kids[base] = make_uint2(0u, root_cell); t.prior[base] = 1.0f; t.parent[base] = kNoNode;
             if (reuse) { b.stat[base] = make_uint2(0u, 0u); b.kids[base] = make_uint2(0u, root_cell); b.prior[base] = 1.0f; b.parent[base] = kNoNode; }
@@ -541,6 +756,7 @@ void az_step_device_kernel(AzTree t, AzArena b, const int16_t* __restrict__ cell
     if (v == GMK_MATCH_ENDED) {
         if (lane == 0) {
             hdr.status |= kStatusOver;
+            hdr.quota = 0;
             hdr.n_nodes = 1;
             t.stat[base] = make_uint2(0u, 0u); t.kids[base] = make_uint2(0u, 0u); t.prior[base] = 1.0f; t.parent[base] = kNoNode;
             if (!fresh) { b.stat[base] = make_uint2(0u, 0u); b.kids[base] = make_uint2(0u, 0u); b.prior[base] = 1.0f; b.parent[base] = kNoNode; }
@@ -604,6 +820,9 @@ struct gmk_az {
     bool second_arena = false;
     int noise_sampler = GMK_NOISE_SAMPLER_STD;                   // gmk_az_set_option
     uint32_t* d_game_ids = nullptr;                              // the device copy of game_ids for az_root_noise_kernel
+    AzLeaves lv{nullptr, nullptr, 1};                            // GMK_OPT_AZ_LEAVES; the side buffers come with the first L > 1
+    int32_t* d_owed = nullptr;                                   // gmk_az_playouts_owed's word
+    bool select_issued = false;                                  // L > 1: gmk_az_select has marked its leaves, gmk_az_expand has not answered yet
     // device scratch of the host-driven form (gmk_az_select_host / gmk_az_expand_host)
     float *h_states = nullptr, *h_values = nullptr, *h_probs = nullptr;
     int16_t* h_paths = nullptr;
@@ -617,6 +836,7 @@ extern "C" int gmk_az_destroy(gmk_az* a) {
     (void)gmk::device_free(a->d_forced); (void)gmk::device_free(a->d_game_ids); (void)gmk::device_free(a->d_noise_priors); (void)gmk::device_free(a->d_unfinished); (void)gmk::device_free(a->d_row_of);
     (void)gmk::device_free(a->slots.slot_game); (void)gmk::device_free(a->d_open_moves); (void)gmk::device_free(a->d_open_lens);
     (void)gmk::device_free(a->h_states); (void)gmk::device_free(a->h_values); (void)gmk::device_free(a->h_probs); (void)gmk::device_free(a->h_paths); (void)gmk::device_free(a->h_lens);
+    (void)gmk::device_free(a->lv.inflight); (void)gmk::device_free(a->lv.pend); (void)gmk::device_free(a->d_owed);
     delete a;
     return GMK_OK;
 }
@@ -647,6 +867,23 @@ static int az_compact(gmk_az* a, hipStream_t s) {
     GMK_HIP_CHECK(hipMemcpyAsync(&n, a->d_row_of + a->t.n_games, 4, hipMemcpyDeviceToHost, s));
     GMK_HIP_CHECK(hipStreamSynchronize(s));
     a->n_live = n;
+    return GMK_OK;
+}
+
+// L > 1 and a select is waiting for its expand: the in-flight marks are up, so nothing may move the trees or change how they are read
+static bool az_marks_up(const gmk_az* a, const char* who) {
+    if (a->lv.leaves > 1 && a->select_issued) { gmk::set_error("%s: gmk_az_select is waiting for its gmk_az_expand (GMK_OPT_AZ_LEAVES = %d)", who, a->lv.leaves); return true; }
+    return false;
+}
+// the host-driven entries serve one leaf per game
+static bool az_many_leaves(const gmk_az* a, const char* who) {
+    if (a->lv.leaves > 1) { gmk::set_error("%s: the host-driven form takes one leaf per step (GMK_OPT_AZ_LEAVES = %d)", who, a->lv.leaves); return true; }
+    return false;
+}
+// new roots: no leaf is pending and nothing is in flight (the headers are rewritten by the caller: quota 0, n_pending 0)
+static int az_reset_leaves(gmk_az* a) {
+    a->select_issued = false;
+    if (a->lv.inflight) GMK_HIP_CHECK(hipMemset(a->lv.inflight, 0, static_cast<size_t>(a->t.n_games) * static_cast<size_t>(a->t.cap) * 2));
     return GMK_OK;
 }
 
@@ -683,6 +920,7 @@ extern "C" int gmk_az_set_roots(gmk_az* a, const uint16_t* h_planes, const int16
     }
     GMK_HIP_CHECK(hipDeviceSynchronize());
     GMK_HIP_CHECK(hipMemcpy(a->t.hdr, hdr.data(), hdr.size() * sizeof(AzHeader), hipMemcpyHostToDevice));
+    if (const int rc = az_reset_leaves(a); rc != GMK_OK) return rc;
     hipLaunchKernelGGL(az_init_roots_kernel, dim3((a->t.n_games + 255) / 256), dim3(256), 0, nullptr, a->t);
     GMK_HIP_CHECK(hipGetLastError());
     GMK_HIP_CHECK(hipDeviceSynchronize());
@@ -746,6 +984,7 @@ extern "C" int gmk_az_set_slots(gmk_az* a, int n_total, const uint8_t* h_open_mo
     a->slots.n_total = n_total;
     a->slots.open_moves = a->d_open_moves; a->slots.open_lens = a->d_open_lens; a->slots.open_stride = open_stride;
     GMK_HIP_CHECK(hipMemcpy(a->t.hdr, hdr.data(), hdr.size() * sizeof(AzHeader), hipMemcpyHostToDevice));
+    if (const int rc = az_reset_leaves(a); rc != GMK_OK) return rc;
     hipLaunchKernelGGL(az_init_roots_kernel, dim3((a->t.n_games + 255) / 256), dim3(256), 0, nullptr, a->t);
     GMK_HIP_CHECK(hipGetLastError());
     GMK_HIP_CHECK(hipDeviceSynchronize());
@@ -757,6 +996,13 @@ extern "C" int gmk_az_set_slots(gmk_az* a, int n_total, const uint8_t* h_open_mo
 extern "C" int gmk_az_select(gmk_az* a, float* d_states, void* stream) {
     if (!a || !d_states) { gmk::set_error("gmk_az_select: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_select: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
+    if (a->lv.leaves > 1) {                                      // d_states has gmk_az_live_games x L rows
+        if (az_marks_up(a, "gmk_az_select")) return GMK_ERR_STATE;
+        hipLaunchKernelGGL(az_select_leaves_kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_states);
+        GMK_HIP_CHECK(hipGetLastError());
+        a->select_issued = true;
+        return GMK_OK;
+    }
     hipLaunchKernelGGL(az_select_kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_states);
     GMK_HIP_CHECK(hipGetLastError());
     return GMK_OK;
@@ -765,8 +1011,39 @@ extern "C" int gmk_az_select(gmk_az* a, float* d_states, void* stream) {
 extern "C" int gmk_az_expand(gmk_az* a, const float* d_values, const float* d_probs, void* stream) {
     if (!a || !d_values || !d_probs) { gmk::set_error("gmk_az_expand: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_expand: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
+    if (a->lv.leaves > 1) {                                      // d_values and d_probs have gmk_az_live_games x L rows
+        hipLaunchKernelGGL(az_expand_leaves_kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs);
+        GMK_HIP_CHECK(hipGetLastError());
+        a->select_issued = false;
+        return GMK_OK;
+    }
     hipLaunchKernelGGL(az_expand_kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3);
     GMK_HIP_CHECK(hipGetLastError());
+    return GMK_OK;
+}
+
+// Every game that is not over owes `playouts` more (several leaves per step: az_select_leaves_kernel takes them off as it completes them)
+extern "C" int gmk_az_add_playouts(gmk_az* a, int playouts, void* stream) {
+    if (!a || playouts < 0) { gmk::set_error("gmk_az_add_playouts: bad arguments"); return GMK_ERR_ARG; }
+    if (!a->rooted) { gmk::set_error("gmk_az_add_playouts: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
+    hipLaunchKernelGGL(az_add_playouts_kernel, dim3((a->t.n_games + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), a->t, static_cast<uint32_t>(playouts));
+    GMK_HIP_CHECK(hipGetLastError());
+    return GMK_OK;
+}
+
+// The largest number of playouts a game of the handle still owes (synchronises the stream)
+extern "C" int gmk_az_playouts_owed(gmk_az* a, int32_t* h_max, void* stream) {
+    if (!a || !h_max) { gmk::set_error("gmk_az_playouts_owed: bad arguments"); return GMK_ERR_ARG; }
+    if (!a->rooted) { gmk::set_error("gmk_az_playouts_owed: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
+    if (!a->d_owed) GMK_HIP_CHECK(gmk::device_malloc(&a->d_owed, 4));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    GMK_HIP_CHECK(hipMemsetAsync(a->d_owed, 0, 4, s));
+    hipLaunchKernelGGL(az_playouts_owed_kernel, dim3((a->t.n_games + 255) / 256), dim3(256), 0, s, a->t, a->d_owed);
+    GMK_HIP_CHECK(hipGetLastError());
+    int32_t owed = 0;
+    GMK_HIP_CHECK(hipMemcpyAsync(&owed, a->d_owed, 4, hipMemcpyDeviceToHost, s));
+    GMK_HIP_CHECK(hipStreamSynchronize(s));
+    *h_max = owed;
     return GMK_OK;
 }
 
@@ -793,6 +1070,7 @@ static int az_second_arena(gmk_az* a) {
 extern "C" int gmk_az_step(gmk_az* a, const int16_t* h_moves) {
     if (!a) { gmk::set_error("gmk_az_step: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_step: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
+    if (az_marks_up(a, "gmk_az_step")) return GMK_ERR_STATE;
     const size_t n = static_cast<size_t>(a->t.n_games);
     if (const int rc = az_second_arena(a); rc != GMK_OK) return rc;
     GMK_HIP_CHECK(hipDeviceSynchronize());
@@ -818,6 +1096,7 @@ extern "C" int gmk_az_step_device(gmk_az* a, const int16_t* d_cells, const int32
                                   void* stream) {
     if (!a || !d_cells || !d_verdict || (h_unfinished && !d_unfinished)) { gmk::set_error("gmk_az_step_device: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_step_device: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
+    if (az_marks_up(a, "gmk_az_step_device")) return GMK_ERR_STATE;
     if (a->slots.slot_game) { gmk::set_error("gmk_az_step_device: the handle plays through slots (gmk_az_set_slots): a match wants one game per slot"); return GMK_ERR_STATE; }
     if (!fresh_root)
         if (const int rc = az_second_arena(a); rc != GMK_OK) return rc;
@@ -837,6 +1116,7 @@ extern "C" int gmk_az_advance(gmk_az* a, uint8_t* d_moves, uint16_t* d_visits, i
                               void* stream) {
     if (!a || !d_moves || !d_lens || !d_winner) { gmk::set_error("gmk_az_advance: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_advance: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
+    if (az_marks_up(a, "gmk_az_advance")) return GMK_ERR_STATE;
     if (reuse_subtree)
         if (const int rc = az_second_arena(a); rc != GMK_OK) return rc;
     if (!a->d_unfinished) GMK_HIP_CHECK(gmk::device_malloc(&a->d_unfinished, 4));
@@ -853,6 +1133,24 @@ extern "C" int gmk_az_advance(gmk_az* a, uint8_t* d_moves, uint16_t* d_visits, i
 }
 
 extern "C" int gmk_az_set_option(gmk_az* a, int option, int value) {
+    if (a && az_marks_up(a, "gmk_az_set_option")) return GMK_ERR_STATE;
+    if (a && option == GMK_OPT_AZ_LEAVES && value >= 1 && value <= GMK_AZ_MAX_LEAVES) {
+        if (value > 1 && !a->lv.inflight) {                      // the side buffers: in-flight counts (all zero between steps) and the pending leaves
+            const size_t n = static_cast<size_t>(a->t.n_games), nodes = n * static_cast<size_t>(a->t.cap);
+            GMK_HIP_CHECK(hipDeviceSynchronize());
+            if (gmk::device_malloc(&a->lv.inflight, nodes * 2) != hipSuccess || gmk::device_malloc(&a->lv.pend, n * GMK_AZ_MAX_LEAVES * sizeof(AzPending)) != hipSuccess) {
+                (void)gmk::device_free(a->lv.inflight); (void)gmk::device_free(a->lv.pend);
+                a->lv.inflight = nullptr; a->lv.pend = nullptr;
+                (void)hipGetLastError();
+                gmk::set_error("gmk_az_set_option: hipMalloc of the in-flight counts (%zu nodes) failed", nodes);
+                return GMK_ERR_HIP;
+            }
+            GMK_HIP_CHECK(hipMemset(a->lv.inflight, 0, nodes * 2));
+            GMK_HIP_CHECK(hipMemset(a->lv.pend, 0, n * GMK_AZ_MAX_LEAVES * sizeof(AzPending)));
+        }
+        a->lv.leaves = value;
+        return GMK_OK;
+    }
     if (a && option == GMK_OPT_NOISE_SAMPLER && (value == GMK_NOISE_SAMPLER_STD || value == GMK_NOISE_SAMPLER_COUNTER)) { a->noise_sampler = value; return GMK_OK; }
     gmk::set_error("gmk_az_set_option: bad handle, unknown option %d or value %d", option, value);
     return GMK_ERR_ARG;
@@ -862,6 +1160,7 @@ extern "C" int gmk_az_set_option(gmk_az* a, int option, int value) {
 extern "C" int gmk_az_add_root_noise(gmk_az* a, float alpha, float epsilon, uint64_t seed, uint32_t first_game_id) {
     if (!a || !(alpha > 0.0f)) { gmk::set_error("gmk_az_add_root_noise: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_add_root_noise: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
+    if (az_marks_up(a, "gmk_az_add_root_noise")) return GMK_ERR_STATE;
     const size_t n = static_cast<size_t>(a->t.n_games);
     if (a->noise_sampler == GMK_NOISE_SAMPLER_COUNTER) {         // drawn on the device, one wavefront per game: nothing comes back to the host
         if (!a->slots.slot_game) {
@@ -928,6 +1227,7 @@ static bool az_host_scratch(gmk_az* a) {
 // (-1 = the playout ended at a finished game and is already backed up: nothing to evaluate)
 extern "C" int gmk_az_select_host(gmk_az* a, int16_t* h_paths, int32_t* h_lens) {
     if (!a || !h_paths || !h_lens) { gmk::set_error("gmk_az_select_host: bad arguments"); return GMK_ERR_ARG; }
+    if (az_many_leaves(a, "gmk_az_select_host")) return GMK_ERR_STATE;
     if (!az_host_scratch(a)) { gmk::set_error("gmk_az_select_host: device allocation failed"); return GMK_ERR_HIP; }
     const int rc = gmk_az_select(a, a->h_states, nullptr);
     if (rc != GMK_OK) return rc;
@@ -940,6 +1240,7 @@ extern "C" int gmk_az_select_host(gmk_az* a, int16_t* h_paths, int32_t* h_lens) 
 
 extern "C" int gmk_az_expand_host(gmk_az* a, const float* h_values, const float* h_probs) {
     if (!a || !h_values || !h_probs) { gmk::set_error("gmk_az_expand_host: bad arguments"); return GMK_ERR_ARG; }
+    if (az_many_leaves(a, "gmk_az_expand_host")) return GMK_ERR_STATE;
     if (!az_host_scratch(a)) { gmk::set_error("gmk_az_expand_host: device allocation failed"); return GMK_ERR_HIP; }
     GMK_HIP_CHECK(hipMemcpy(a->h_values, h_values, static_cast<size_t>(a->t.n_games) * 4, hipMemcpyHostToDevice));
     GMK_HIP_CHECK(hipMemcpy(a->h_probs, h_probs, static_cast<size_t>(a->t.n_games) * 225 * 4, hipMemcpyHostToDevice));
@@ -1029,6 +1330,7 @@ extern "C" int gmk_az_read_children_host(gmk_az* a, int game, uint32_t first_chi
 extern "C" int gmk_az_set_leaf_host(gmk_az* a, int game, uint32_t leaf, const int16_t* h_path, int depth) {
     if (!a || game < 0 || game >= a->t.n_games || depth < 0 || depth > 225 || (depth > 0 && !h_path) || leaf >= static_cast<uint32_t>(a->t.cap)) { gmk::set_error("gmk_az_set_leaf_host: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_set_leaf_host: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
+    if (az_many_leaves(a, "gmk_az_set_leaf_host")) return GMK_ERR_STATE;
     AzHeader h;
     GMK_HIP_CHECK(hipDeviceSynchronize());
     GMK_HIP_CHECK(hipMemcpy(&h, a->t.hdr + game, sizeof h, hipMemcpyDeviceToHost));
@@ -1049,6 +1351,7 @@ extern "C" int gmk_az_set_leaf_host(gmk_az* a, int game, uint32_t leaf, const in
 extern "C" int gmk_az_expand_stages_host(gmk_az* a, const float* h_values, const float* h_probs, int do_expand, int do_backup) {
     if (!a || (do_backup && !h_values) || (do_expand && !h_probs)) { gmk::set_error("gmk_az_expand_stages_host: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_expand_stages_host: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
+    if (az_many_leaves(a, "gmk_az_expand_stages_host")) return GMK_ERR_STATE;
     if (!az_host_scratch(a)) { gmk::set_error("gmk_az_expand_stages_host: device allocation failed"); return GMK_ERR_HIP; }
     if (h_values) GMK_HIP_CHECK(hipMemcpy(a->h_values, h_values, static_cast<size_t>(a->t.n_games) * 4, hipMemcpyHostToDevice));
     if (h_probs) GMK_HIP_CHECK(hipMemcpy(a->h_probs, h_probs, static_cast<size_t>(a->t.n_games) * 225 * 4, hipMemcpyHostToDevice));
@@ -1062,6 +1365,7 @@ extern "C" int gmk_az_expand_stages_host(gmk_az* a, const float* h_values, const
 // node statistics as a Python back_prop left them: h_nodes[i] gets {h_visits[i], h_values[i]}
 extern "C" int gmk_az_write_stats_host(gmk_az* a, int game, const uint32_t* h_nodes, const uint32_t* h_visits, const float* h_values, int n) {
     if (!a || game < 0 || game >= a->t.n_games || n < 0 || (n > 0 && (!h_nodes || !h_visits || !h_values))) { gmk::set_error("gmk_az_write_stats_host: bad arguments"); return GMK_ERR_ARG; }
+    if (az_many_leaves(a, "gmk_az_write_stats_host")) return GMK_ERR_STATE;
     GMK_HIP_CHECK(hipDeviceSynchronize());
     for (int i = 0; i < n; ++i) {
         if (h_nodes[i] >= static_cast<uint32_t>(a->t.cap)) { gmk::set_error("gmk_az_write_stats_host: node %u outside the arena", h_nodes[i]); return GMK_ERR_ARG; }
@@ -1079,6 +1383,7 @@ extern "C" int gmk_az_write_stats_host(gmk_az* a, int game, const uint32_t* h_no
 extern "C" int gmk_az_rollout_host(gmk_az* a, int game, uint64_t seed, uint32_t counter0, uint32_t counter1, uint32_t counter2, int32_t* h_winner) {
     if (!a || game < 0 || game >= a->t.n_games || !h_winner) { gmk::set_error("gmk_az_rollout_host: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_rollout_host: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
+    if (az_many_leaves(a, "gmk_az_rollout_host")) return GMK_ERR_STATE;
     if (!a->d_unfinished) GMK_HIP_CHECK(gmk::device_malloc(&a->d_unfinished, 4));
     hipLaunchKernelGGL(az_leaf_rollout_kernel, dim3(1), dim3(64), 0, nullptr, a->t, game, counter0, counter1, counter2, static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), a->d_unfinished);
     GMK_HIP_CHECK(hipGetLastError());

@@ -29,7 +29,8 @@ class TableInfo(C.Structure):
 _lib = None
 
 # gmk_*_set_option (include/gomoku_hip.h)
-OPT_NOISE_SAMPLER, OPT_LOCKSTEP = 1, 2
+OPT_NOISE_SAMPLER, OPT_LOCKSTEP, OPT_AZ_LEAVES = 1, 2, 3
+AZ_MAX_LEAVES = 8                              # GMK_AZ_MAX_LEAVES: leaves per game per step of a K7 handle (AlphaZeroMCTS(leaves=))
 NOISE_SAMPLERS = {"std": 0, "counter": 1}      # std::gamma_distribution on the host / the counter-based sampler of include/gomoku_noise.h on the device
 
 # every symbol include/gomoku_hip.h declares (checked by tests/test_cabi.py)
@@ -42,7 +43,7 @@ EXPORTS = [
     "gmk_mcts_alg_bytes", "gmk_mcts_launch_info", "gmk_visits_to_pi", "gmk_mcts_advance", "gmk_mcts_step", "gmk_mcts_step_host", "gmk_mcts_add_root_noise", "gmk_mcts_set_option", "gmk_mcts_reserve", "gmk_selfplay_run", "gmk_samples_from_records",
     "gmk_records_scan", "gmk_records_packed_bytes", "gmk_records_pack", "gmk_records_unpack", "gmk_samples_from_packed",
     "gmk_evalstate_create", "gmk_evalstate_destroy", "gmk_evalstate_reset", "gmk_evalstate_update", "gmk_evalstate_update_host", "gmk_evalstate_read",
-    "gmk_az_create", "gmk_az_destroy", "gmk_az_set_roots", "gmk_az_select", "gmk_az_expand", "gmk_az_select_host", "gmk_az_expand_host", "gmk_az_read_node_host", "gmk_az_read_children_host", "gmk_az_set_leaf_host", "gmk_az_rollout_host", "gmk_az_expand_stages_host", "gmk_az_write_stats_host", "gmk_az_step", "gmk_az_root_choice", "gmk_az_step_device", "gmk_az_advance", "gmk_az_set_slots", "gmk_az_live_games", "gmk_az_set_game_ids", "gmk_az_add_root_noise", "gmk_az_set_option", "gmk_az_root_stats",
+    "gmk_az_create", "gmk_az_destroy", "gmk_az_set_roots", "gmk_az_select", "gmk_az_expand", "gmk_az_select_host", "gmk_az_expand_host", "gmk_az_read_node_host", "gmk_az_read_children_host", "gmk_az_set_leaf_host", "gmk_az_rollout_host", "gmk_az_expand_stages_host", "gmk_az_write_stats_host", "gmk_az_step", "gmk_az_root_choice", "gmk_az_step_device", "gmk_az_advance", "gmk_az_set_slots", "gmk_az_live_games", "gmk_az_set_game_ids", "gmk_az_add_root_noise", "gmk_az_set_option", "gmk_az_add_playouts", "gmk_az_playouts_owed", "gmk_az_root_stats",
     "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_root_choice", "gmk_trad_step_device", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_run_rave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
     "gmk_pattern_policy", "gmk_pattern_policy_host", "gmk_pattern_play",
     "gmk_match_referee",
@@ -129,6 +130,8 @@ def load():
     L.gmk_az_advance.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_int32), vp]
     L.gmk_az_add_root_noise.argtypes = [vp, C.c_float, C.c_float, C.c_uint64, C.c_uint32]
     L.gmk_az_set_option.argtypes = [vp, C.c_int, C.c_int]
+    L.gmk_az_add_playouts.argtypes = [vp, C.c_int, vp]
+    L.gmk_az_playouts_owed.argtypes = [vp, C.POINTER(C.c_int32), vp]
     L.gmk_az_expand_host.argtypes = [vp, vp, vp]
     L.gmk_az_root_stats.argtypes = [vp] * 8
     L.gmk_trad_create.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]
@@ -872,17 +875,22 @@ class TraditionalRAVEMCTS(TraditionalMCTS):
 class AlphaZeroMCTS:
     """n_games searches of MCTS(policy=Policy(eval_state=network.eval_state, c_puct)) (agents/alphazero.py:5-9) advancing one
     playout per step: select() writes the leaves' feature planes into `states` (torch float32 [n, 6, 15, 15] on the GPU), the
-    caller's network maps them to (value [n], probs [n, 225]), expand() grows the trees and backs the values up."""
+    caller's network maps them to (value [n], probs [n, 225]), expand() grows the trees and backs the values up.
+    leaves = L > 1 (at most AZ_MAX_LEAVES): a step takes up to L leaves from every game, steered apart by virtual loss (OPT_AZ_LEAVES, see
+    gmk_az_set_option); the batch then has live x L rows, game g's k-th leaf in row g L + k, and search() takes about playouts / L steps."""
 
-    def __init__(self, n_games, node_capacity=1 << 16, c_puct=5.0):
+    def __init__(self, n_games, node_capacity=1 << 16, c_puct=5.0, leaves=1):
         import torch
         init()
         self.n = n_games
         h = C.c_void_p()
         _check(load().gmk_az_create(n_games, int(node_capacity), float(c_puct), C.byref(h)))
         self.h = h
+        self.leaves = 1
         self.states = torch.zeros((n_games, 6, 15, 15), dtype=torch.float32, device="cuda")
-        self.live = n_games                                        # rows of the leaf batch (see select)
+        self.live = n_games                                        # games with rows in the leaf batch (see select)
+        if leaves != 1:
+            self.set_option(OPT_AZ_LEAVES, leaves)
 
     def close(self):
         if getattr(self, "h", None) and load is not None:
@@ -918,12 +926,12 @@ class AlphaZeroMCTS:
         import torch
         stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
         _check(load().gmk_az_select(self.h, self.states.data_ptr(), stream))
-        return self.states[:self.live]                             # the games still played (all of them until advance() ends one)
+        return self.states[:self.live * self.leaves]               # the games still played (all of them until advance() ends one), `leaves` rows each
 
     def expand(self, values, probs, stream=None):
         import torch
         assert values.dtype == torch.float32 and probs.dtype == torch.float32 and values.is_contiguous() and probs.is_contiguous()
-        assert values.numel() == self.live and probs.numel() == self.live * N
+        assert values.numel() == self.live * self.leaves and probs.numel() == self.live * self.leaves * N
         stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
         _check(load().gmk_az_expand(self.h, values.data_ptr(), probs.data_ptr(), stream))
 
@@ -983,20 +991,58 @@ class AlphaZeroMCTS:
         _check(load().gmk_az_add_root_noise(self.h, alpha, epsilon, seed, first_game_id))
 
     def set_option(self, option, value):
-        """gmk_az_set_option: OPT_NOISE_SAMPLER -> NOISE_SAMPLERS["std" | "counter"]."""
+        """gmk_az_set_option: OPT_NOISE_SAMPLER -> NOISE_SAMPLERS["std" | "counter"]; OPT_AZ_LEAVES -> 1 .. AZ_MAX_LEAVES leaves per game per step."""
+        import torch
         _check(load().gmk_az_set_option(self.h, int(option), int(value)))
+        if int(option) == OPT_AZ_LEAVES:
+            self.leaves = int(value)
+            if self.states.shape[0] < self.n * self.leaves:
+                self.states = torch.zeros((self.n * self.leaves, 6, 15, 15), dtype=torch.float32, device="cuda")
+
+    def add_playouts(self, playouts, stream=None):
+        """gmk_az_add_playouts: every game that is not over owes `playouts` more (leaves > 1: select() takes them off as it completes them)."""
+        _check(load().gmk_az_add_playouts(self.h, int(playouts), _current_stream(stream)))
+
+    def playouts_owed(self, stream=None):
+        """gmk_az_playouts_owed: the largest number of playouts a game still owes (waits for the stream)."""
+        owed = C.c_int32(0)
+        _check(load().gmk_az_playouts_owed(self.h, C.byref(owed), _current_stream(stream)))
+        return owed.value
 
     def search(self, network, playouts, graph=False):
         """`playouts` lock-step playouts; network(states) -> (value [n], probs [n, 225]) on the GPU.  graph=True: the first playout
         runs eagerly, then ONE playout step (select kernel, the network's kernels, expand kernel) is captured into a hipGraph and
         replayed for the rest, which removes the launch gaps between the ~10 kernels of a step; the network must be capturable
-        (no host synchronisation; PolicyValueNetwork and FusedPolicyValueNetwork are)."""
+        (no host synchronisation; PolicyValueNetwork and FusedPolicyValueNetwork are).
+        leaves > 1: every game is given `playouts` more to complete (add_playouts), ceil(playouts / leaves) steps are taken without looking,
+        then steps until no game owes any (playouts_owed: collisions cut steps short); every game ends with exactly `playouts` more."""
         import torch
 
         def step():
             values, probs = network(self.select())
             self.expand(values.contiguous(), probs.contiguous())
 
+        if self.leaves > 1:
+            if playouts <= 0:
+                return
+            self.add_playouts(playouts)
+            blind = -(-playouts // self.leaves)
+            if not graph or blind < 3:
+                for _ in range(blind):
+                    step()
+                while self.playouts_owed() > 0:
+                    step()
+                return
+            step()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                step()
+            for _ in range(blind - 1):
+                g.replay()
+            while self.playouts_owed() > 0:
+                g.replay()
+            return
         if not graph or playouts < 3:
             for _ in range(playouts):
                 step()

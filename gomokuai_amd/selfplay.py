@@ -472,7 +472,7 @@ def _play_supervisor_slots(n_games, slots, playouts, c_puct, seed, first_game_id
 
 
 def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, first_game_id=0, opening_plies=0, max_moves=N,
-                       device=None, node_capacity=None, reuse_subtree=True, root_noise=(0.05, 0.25), slots=None, device_loop=True, noise_sampler="counter"):
+                       device=None, node_capacity=None, reuse_subtree=True, root_noise=(0.05, 0.25), slots=None, device_loop=True, noise_sampler="counter", leaves=1):
     """n_games complete games of the network-guided searcher against itself (agents/alphazero.py:5-9 on both sides: the
     reference's AlphaZero self-play), all games in lock step on the current GPU: every move = `playouts` lock-step playouts of
     K7 with `network(states [n,6,15,15]) -> (value [n], probs [n,225])` at the leaves (network.FusedPolicyValueNetwork = K9),
@@ -482,7 +482,9 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
     host-driven loop with fresh roots only).  device_loop (all games at once): the move, the record, the end-of-game check and the re-rooting are one
     kernel per ply (gmk_az_advance) and the host sees four bytes per move; noise_sampler "counter" (default) draws the root noise on the device
     (az_root_noise_kernel, include/gomoku_noise.h), "std" on the host with std::gamma_distribution (priors down and up every ply); False = the host-driven loop it replaced (numpy boards, root statistics down and moves up every ply), kept for the
-    tests that compare the two.  Returns GameRecords like play_games."""
+    tests that compare the two.  leaves > 1: every search step takes up to that many leaves from each game, with virtual loss
+    (lib.AlphaZeroMCTS(leaves=)): the network's batch is live games x leaves rows and a move takes about playouts / leaves steps; the games differ
+    from those of leaves = 1, and are the same games on every loop of this function.  Returns GameRecords like play_games."""
     if slots is not None and slots < n_games and (max_moves < N or (device_loop and opening_plies > 8)):
         # (the slot loops play whole games, the device-resident one from openings of at most 8 plies -- gmk_az_set_slots' limit: say so instead of
         # ignoring the cap or failing inside the library; ADVICE r3)
@@ -499,7 +501,7 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
             games.open_with(m, l, opening_plies)
         slots = int(slots)
         cap = node_capacity if node_capacity is not None else min((3 if reuse_subtree else 1) * playouts * N + 1, (1 << 24) - 1)
-        tree = G.AlphaZeroMCTS(slots, node_capacity=cap, c_puct=c_puct)
+        tree = G.AlphaZeroMCTS(slots, node_capacity=cap, c_puct=c_puct, leaves=leaves)
         tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS[noise_sampler])
         tree.set_slots(n_games, games.moves[:, :max(int(games.lens.max()), 1)], games.lens)
         d_moves, d_lens = torch.from_numpy(games.moves).to(dev), torch.from_numpy(games.lens).to(dev)
@@ -524,7 +526,7 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
             games.open_with(m, l, opening_plies)
         visits = np.zeros((n_games, N, N), dtype=np.uint16)
         slots = int(slots)
-        tree = G.AlphaZeroMCTS(slots, node_capacity=node_capacity if node_capacity is not None else min(playouts * N + 1, (1 << 24) - 1), c_puct=c_puct)
+        tree = G.AlphaZeroMCTS(slots, node_capacity=node_capacity if node_capacity is not None else min(playouts * N + 1, (1 << 24) - 1), c_puct=c_puct, leaves=leaves)
         active, next_game, overflow = np.arange(slots), slots, False
         with torch.no_grad():
             for _ in range((n_games // slots + 2) * N):
@@ -562,7 +564,7 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
         m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
         games.open_with(m, l, opening_plies)
     cap = node_capacity if node_capacity is not None else min((3 if reuse_subtree else 1) * playouts * N + 1, (1 << 24) - 1)
-    tree = G.AlphaZeroMCTS(n_games, node_capacity=cap, c_puct=c_puct)
+    tree = G.AlphaZeroMCTS(n_games, node_capacity=cap, c_puct=c_puct, leaves=leaves)
     tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS[noise_sampler])
     tree.set_roots(G.moves_to_planes(games.moves, games.lens), games.last_two())
     if device_loop:
@@ -764,7 +766,7 @@ class _EvalOpponent:
 
 
 def play_evaluation_games(n_games, network, opponent, playouts=400, c_puct=5.0, seed=G.DEFAULT_SEED, first_game_id=0, opening_plies=0, max_moves=N,
-                          reuse_subtree=True, root_noise=(0.05, 0.25), device_loop=None, device=None):
+                          reuse_subtree=True, root_noise=(0.05, 0.25), device_loop=None, device=None, leaves=1):
     """The reference's evaluation match (network/train.py:88-126 evaluate_network -> agents/utils.py:66-100 eval_agents): n_games games of the
     network-guided searcher (K7 with `network` = network.FusedPolicyValueNetwork at the leaves, `playouts` playouts a move) against
     `opponent` = (name, kwargs) as in DATA_CONFIG["schedule"] ("traditional_mcts" -- with {"use_rave": True} TraditionalPolicy + RAVE --,
@@ -777,6 +779,8 @@ def play_evaluation_games(n_games, network, opponent, playouts=400, c_puct=5.0, 
     host sees the count of unfinished games per ply; False: the same match through the host (root_stats down, numpy boards, moves up);
     None: the device loop, except for "random_mcts" (the gmk_mcts handle), which the host loop serves, from fresh roots at every move.
     A mover whose root has no child to play leaves its game where it stands (it cannot happen on a board with an empty cell).
+    leaves > 1: the network's searches take up to that many leaves per game per step, with virtual loss (lib.AlphaZeroMCTS(leaves=)) -- a
+    match has few games, so this is what fills the network's batch; both loops play the same games.
     Returns (GameRecords, network_is_black bool[n], scores float[n]); the records' visit counts at move i are the mover's, and
     records.groups lists per group the games, the unfinished count and the K7 handle's live games after the loop."""
     kind = opponent[0]
@@ -811,7 +815,7 @@ def play_evaluation_games(n_games, network, opponent, playouts=400, c_puct=5.0, 
         if k == 0:
             groups.append({"games": idx, "unfinished": 0, "live_games": 0})
             continue
-        net = G.AlphaZeroMCTS(k, node_capacity=net_cap, c_puct=c_puct)
+        net = G.AlphaZeroMCTS(k, node_capacity=net_cap, c_puct=c_puct, leaves=leaves)
         net.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS["counter"])
         net.set_game_ids(np.asarray(idx, dtype=np.uint32))
         net.set_roots(G.moves_to_planes(games.moves[idx], games.lens[idx]), games.last_two()[idx])

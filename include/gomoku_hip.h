@@ -204,7 +204,8 @@ int gmk_mcts_add_root_noise(gmk_mcts *m, float alpha, float epsilon, void *strea
  *                                      semantics -- kept subtree + noise before every search -- then run inside ONE persistent launch.
  * GMK_OPT_LOCKSTEP: 1 = gmk_selfplay_run / gmk_trad_selfplay_run alternate search and step launches even where one persistent launch could play
  *   the games (the second form the tests hold the persistent one to); 0 (default) = persistent wherever the configuration allows. */
-enum { GMK_OPT_NOISE_SAMPLER = 1, GMK_OPT_LOCKSTEP = 2 };
+enum { GMK_OPT_NOISE_SAMPLER = 1, GMK_OPT_LOCKSTEP = 2, GMK_OPT_AZ_LEAVES = 3 /* K7 only: see gmk_az_set_option */ };
+#define GMK_AZ_MAX_LEAVES 8
 enum { GMK_NOISE_SAMPLER_STD = 0, GMK_NOISE_SAMPLER_COUNTER = 1 };
 int gmk_mcts_set_option(gmk_mcts *m, int option, int value);
 /* The handle's tree arenas, now: one arena per game (what the first gmk_mcts_set_roots allocates) or, two_arenas != 0, the two arenas per game of
@@ -468,8 +469,27 @@ int gmk_az_advance(gmk_az* a, uint8_t* d_moves, uint16_t* d_visits, int32_t* d_l
  * by first_game_id + ids[g], ids as set by gmk_az_set_game_ids (uint32[n], host; default: the slot number) */
 int gmk_az_set_game_ids(gmk_az* a, const uint32_t* h_ids);
 int gmk_az_add_root_noise(gmk_az* a, float alpha, float epsilon, uint64_t seed, uint32_t first_game_id);
-/* GMK_OPT_NOISE_SAMPLER for a K7 handle (see gmk_mcts_set_option): GMK_NOISE_SAMPLER_COUNTER draws the noise on the device, one wavefront per game */
+/* GMK_OPT_NOISE_SAMPLER for a K7 handle (see gmk_mcts_set_option): GMK_NOISE_SAMPLER_COUNTER draws the noise on the device, one wavefront per game.
+ * GMK_OPT_AZ_LEAVES = L in 1 .. GMK_AZ_MAX_LEAVES (GMK_ERR_ARG otherwise; default 1): leaves per game per step, with virtual loss.
+ *   L = 1: gmk_az_select / gmk_az_expand are the one-leaf kernels, one playout per step.
+ *   L > 1: every game owes a quota of playouts (gmk_az_add_playouts).  gmk_az_select makes min(L, quota) descents per game, one after the
+ *   other; each counts the descents still in flight below a node as lost playouts (per child: mean (Q N - v) / (N + v), count N + v + 1,
+ *   parent count N + v under the square root, in double), so that they spread.  A descent that ends at a finished game is backed up at once;
+ *   one that reaches a leaf already waiting for the network ends the game's descents for this step and is not counted; any other marks its
+ *   path, becomes the game's k-th pending leaf and takes one off the quota.  d_states, d_values and d_probs then have
+ *   gmk_az_live_games x L rows: game g's k-th leaf is row row(g) * L + k, rows past the game's pending leaves are zeros on the way out and
+ *   ignored on the way in.  gmk_az_expand answers the pending leaves in that order and takes the marks back; a leaf whose children do not
+ *   fit the arena sets status bit 1 and its playout is dropped.  Neither call waits for the host: a step can be captured in a hipGraph.
+ *   The first L > 1 allocates two bytes per node and 640 bytes per game.  Between a gmk_az_select and its gmk_az_expand the marks are up:
+ *   gmk_az_select, gmk_az_step, gmk_az_step_device, gmk_az_advance, gmk_az_add_root_noise and gmk_az_set_option return GMK_ERR_STATE then.
+ *   The host-driven entries below (one game behind a Python evaluator) return GMK_ERR_STATE on a handle whose L > 1.
+ * gmk_az_add_playouts: every game that is not over owes `playouts` more (finished games keep 0); gmk_az_set_roots and gmk_az_set_slots
+ *   reset the quota, the pending leaves and the marks, and a slot refilled by gmk_az_advance starts with 0.
+ * gmk_az_playouts_owed: *h_max = the largest quota over the handle; synchronises `stream`.  A game that owes playouts completes at least
+ *   one per step, so `playouts` steps always suffice and about playouts / L do. */
 int gmk_az_set_option(gmk_az* a, int option, int value);
+int gmk_az_add_playouts(gmk_az* a, int playouts, void* stream);
+int gmk_az_playouts_owed(gmk_az* a, int32_t* h_max, void* stream);
 /* The same two steps for an evaluator that runs on the host and wants positions, not planes (the Python callable of
  * Policy(eval_state=...)): select, then the moves from the root to every pending leaf (h_paths int16[n][226], h_lens int32[n],
  * -1 = nothing to evaluate); expand from host memory.  Synchronous. */
