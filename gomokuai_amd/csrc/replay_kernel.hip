@@ -18,6 +18,7 @@
 #include "capi_common.h"
 #include "records_access.h"
 #include "replay_draw.h"
+#include "replay_image.h"
 
 namespace {
 
@@ -315,6 +316,107 @@ void replay_draw_kernel(const uint64_t* __restrict__ state, const GameDesc* __re
     }
 }
 
+// ---- the image (replay_image.h): the descriptors need a kernel each way, the plies and the visit rows are plain copies ----
+// out: one thread per held game compacts its GameDesc into the 8-byte record; thread 0 also writes the header and the sections' padding
+__global__ __launch_bounds__(kThreads)
+void replay_snapshot_kernel(const GameDesc* __restrict__ desc, uint64_t max_games, uint64_t head, uint64_t n, uint64_t T, uint64_t S,
+                            uint8_t* __restrict__ image, int32_t* __restrict__ status) {
+    const uint64_t g = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
+    uint64_t* words = reinterpret_cast<uint64_t*>(image);                 // (8-byte aligned: checked by the caller; the device is little-endian)
+    if (g < n) {
+        const GameDesc d = desc[(head + g) % max_games];
+        uint8_t rec[8];
+        gmk::replay_image_put_desc(rec, d.len, d.first, d.winner);
+        words[gmk::kImageHeaderBytes / 8 + g] = gmk::image_u64(rec);
+    }
+    if (g != 0) return;
+    const uint8_t magic[8] = {'G', 'M', 'K', 'R', 'P', 'L', 'Y', '1'};
+    words[0] = gmk::image_u64(magic);
+    words[1] = n;
+    words[2] = T;
+    words[3] = S;
+    words[4] = head;
+    words[5] = gmk::replay_image_size(n, T, S);
+    words[6] = words[7] = 0;
+    uint8_t* moves = image + gmk::kImageHeaderBytes + gmk::kImageDescBytes * n;
+    for (uint64_t i = T; i < gmk::image_roundup8(T); ++i) moves[i] = 0;
+    uint8_t* visits = moves + gmk::image_roundup8(T);
+    for (uint64_t i = gmk::kImageRowBytes * S; i < gmk::image_roundup8(gmk::kImageRowBytes * S); ++i) visits[i] = 0;
+    *status = 0;
+}
+
+// in (one workgroup, the chunked scan of replay_plan_kernel): every rule of replay_image.h but the host-only ones, then whether the games
+// fit; with commit, also the GameDesc of every game -- mstart / sstart rebased so that the oldest game starts both rings at 0 -- and the
+// state words.  A refusal writes *status and nothing else.  It runs twice per restore: commit = 0 before the rings are copied, commit = 1 after.
+__global__ __launch_bounds__(kThreads)
+void replay_restore_kernel(const uint8_t* __restrict__ image, uint64_t bytes, uint64_t cap, uint64_t max_games, int commit,
+                           uint64_t* __restrict__ state, GameDesc* __restrict__ desc, int32_t* __restrict__ status) {
+    __shared__ int64_t s_m[kThreads], s_s[kThreads];
+    __shared__ int s_bad;
+    const int tid = threadIdx.x;
+    gmk::ReplayImageHeader h;
+    if (gmk::replay_image_check_header(image, bytes, &h) != gmk::kImageOk) {      // (uniform: every thread reads the same 64 bytes)
+        if (tid == 0) *status = GMK_REPLAY_BAD_IMAGE;
+        return;
+    }
+    const uint8_t* recs = image + gmk::kImageHeaderBytes;                         // h.n of them lie inside the image: the header's formula
+    const int64_t n = static_cast<int64_t>(h.n);
+    const int64_t per = (n + kThreads - 1) / kThreads;
+    const int64_t lo = tid * per < n ? tid * per : n;
+    const int64_t hi = lo + per < n ? lo + per : n;
+    if (tid == 0) s_bad = 0;
+    __syncthreads();
+    int64_t m = 0, s = 0;
+    bool bad = false;
+    for (int64_t j = lo; j < hi; ++j) {
+        int len, first, winner;
+        if (gmk::replay_image_check_desc(recs + gmk::kImageDescBytes * j, &len, &first, &winner) != gmk::kImageOk) bad = true;
+        else { m += len; s += gmk::image_sampled(len, first); }
+    }
+    if (bad) atomicOr(&s_bad, 1);
+    s_m[tid] = m;
+    s_s[tid] = s;
+    __syncthreads();
+    for (int d = 1; d < kThreads; d <<= 1) {             // inclusive Hillis-Steele scan of both sums
+        const int64_t om = tid >= d ? s_m[tid - d] : 0, os = tid >= d ? s_s[tid - d] : 0;
+        __syncthreads();
+        s_m[tid] += om;
+        s_s[tid] += os;
+        __syncthreads();
+    }
+    int32_t code = 0;
+    if (s_bad || static_cast<uint64_t>(s_m[kThreads - 1]) != h.T || static_cast<uint64_t>(s_s[kThreads - 1]) != h.S) code = GMK_REPLAY_BAD_IMAGE;
+    else if (h.T > cap || h.n > max_games) code = GMK_REPLAY_NO_ROOM;
+    if (code || !commit) {
+        if (tid == 0) *status = code;
+        return;
+    }
+    uint64_t em = static_cast<uint64_t>(s_m[tid] - m), es = static_cast<uint64_t>(s_s[tid] - s);
+    for (int64_t j = lo; j < hi; ++j) {
+        int len, first, winner;
+        (void)gmk::replay_image_check_desc(recs + gmk::kImageDescBytes * j, &len, &first, &winner);
+        GameDesc d;
+        d.serial = h.head + static_cast<uint64_t>(j);
+        d.mstart = em;
+        d.sstart = es;
+        d.len = static_cast<int16_t>(len);
+        d.first = static_cast<int16_t>(first);
+        d.winner = static_cast<int8_t>(winner);
+        d.pad[0] = d.pad[1] = d.pad[2] = 0;
+        desc[d.serial % max_games] = d;
+        em += static_cast<uint64_t>(len);
+        es += static_cast<uint64_t>(gmk::image_sampled(len, first));
+    }
+    if (tid != 0) return;
+    state[kHead] = h.head;
+    state[kTail] = h.head + h.n;
+    state[kMHead] = 0;
+    state[kMTail] = h.T;
+    state[kSHead] = 0;
+    state[kSTail] = h.S;
+    *status = 0;
+}
+
 bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
 
 constexpr int64_t kMaxCapacityPlies = int64_t(1) << 40;
@@ -498,5 +600,114 @@ extern "C" int gmk_replay_draw_host(uint64_t seed, int64_t step, int64_t populat
     const uint64_t M = static_cast<uint64_t>(population);
     const int k = gmk::replay_half_bits(M);
     for (int64_t i = 0; i < batch; ++i) h_index[i] = static_cast<int64_t>(gmk::replay_perm(static_cast<uint64_t>(i), M, k, seed, static_cast<uint64_t>(step)));
+    return GMK_OK;
+}
+
+// ---- the image: snapshot, restore, and the host's check ----
+namespace {
+
+// the state words on the host; drains the stream
+int read_state(gmk_replay* h, uint64_t* w, hipStream_t s) {
+    GMK_HIP_CHECK(hipMemcpyAsync(w, h->d_state, kStateWords * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    GMK_HIP_CHECK(hipStreamSynchronize(s));
+    return GMK_OK;
+}
+
+// `count` units of `unit` bytes between a ring (unit `start` onwards, modulo cap units) and a linear run: at most two contiguous copies
+int copy_ring(uint8_t* ring, uint8_t* linear, bool to_ring, uint64_t start, uint64_t count, uint64_t cap, uint64_t unit, hipStream_t s) {
+    const uint64_t at = start % cap, one = count < cap - at ? count : cap - at;
+    const uint64_t part[2][3] = {{at, 0, one}, {0, one, count - one}};     // ring unit, linear unit, units
+    for (const auto& p : part) {
+        if (p[2] == 0) continue;
+        uint8_t *r = ring + p[0] * unit, *l = linear + p[1] * unit;
+        GMK_HIP_CHECK(hipMemcpyAsync(to_ring ? r : l, to_ring ? l : r, p[2] * unit, hipMemcpyDeviceToDevice, s));
+    }
+    return GMK_OK;
+}
+
+}  // namespace
+
+extern "C" int gmk_replay_image_bytes(gmk_replay* h, int64_t* bytes, void* stream) {
+    GMK_NEED_INIT();
+    if (!h || !bytes) { gmk::set_error("gmk_replay_image_bytes: no handle or no result pointer"); return GMK_ERR_ARG; }
+    uint64_t w[kStateWords];
+    const int rc = read_state(h, w, static_cast<hipStream_t>(stream));
+    if (rc != GMK_OK) return rc;
+    *bytes = static_cast<int64_t>(gmk::replay_image_size(w[kTail] - w[kHead], w[kMTail] - w[kMHead], w[kSTail] - w[kSHead]));
+    return GMK_OK;
+}
+
+extern "C" int gmk_replay_snapshot(gmk_replay* h, uint8_t* d_image, int64_t capacity_bytes, int32_t* d_status, void* stream) {
+    GMK_NEED_INIT();
+    if (!h || !d_image || !d_status || capacity_bytes < 0 || misaligned(d_image, 8) || misaligned(d_status, 4)) {
+        gmk::set_error("gmk_replay_snapshot: bad arguments (capacity_bytes >= 0; d_image 8-byte, d_status 4-byte aligned)");
+        return GMK_ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint64_t w[kStateWords];
+    const int rc = read_state(h, w, s);
+    if (rc != GMK_OK) return rc;
+    const uint64_t n = w[kTail] - w[kHead], T = w[kMTail] - w[kMHead], S = w[kSTail] - w[kSHead];
+    if (static_cast<uint64_t>(capacity_bytes) < gmk::replay_image_size(n, T, S)) {
+        GMK_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_status), GMK_REPLAY_NO_ROOM, 1, s));
+        return GMK_OK;
+    }
+    const unsigned blocks = static_cast<unsigned>(n / kThreads + 1);
+    hipLaunchKernelGGL(replay_snapshot_kernel, dim3(blocks), dim3(kThreads), 0, s, h->d_desc, h->max_games, w[kHead], n, T, S, d_image, d_status);
+    GMK_HIP_CHECK(hipGetLastError());
+    uint8_t* moves = d_image + gmk::kImageHeaderBytes + gmk::kImageDescBytes * n;
+    int rc2 = copy_ring(h->d_moves, moves, false, w[kMHead], T, h->cap, 1, s);
+    if (rc2 == GMK_OK)
+        rc2 = copy_ring(reinterpret_cast<uint8_t*>(h->d_visits), moves + gmk::image_roundup8(T), false, w[kSHead], S, h->cap, gmk::kImageRowBytes, s);
+    return rc2;
+}
+
+extern "C" int gmk_replay_restore(gmk_replay* h, const uint8_t* d_image, int64_t bytes, int32_t* d_status, void* stream) {
+    GMK_NEED_INIT();
+    if (!h || !d_image || !d_status || bytes < static_cast<int64_t>(gmk::kImageHeaderBytes) || misaligned(d_image, 8) || misaligned(d_status, 4)) {
+        gmk::set_error("gmk_replay_restore: bad arguments (bytes >= 64; d_image 8-byte, d_status 4-byte aligned)");
+        return GMK_ERR_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // 1. the whole check, on the device; nothing of the handle is written yet
+    hipLaunchKernelGGL(replay_restore_kernel, dim3(1), dim3(kThreads), 0, s, d_image, static_cast<uint64_t>(bytes), h->cap, h->max_games, 0, h->d_state,
+                       h->d_desc, d_status);
+    GMK_HIP_CHECK(hipGetLastError());
+    int32_t code = 0;
+    uint8_t header[gmk::kImageHeaderBytes];
+    GMK_HIP_CHECK(hipMemcpyAsync(&code, d_status, sizeof(code), hipMemcpyDeviceToHost, s));
+    GMK_HIP_CHECK(hipMemcpyAsync(header, d_image, sizeof(header), hipMemcpyDeviceToHost, s));
+    GMK_HIP_CHECK(hipStreamSynchronize(s));
+    if (code != 0) return GMK_OK;                                             // refused: *d_status says why
+    // 2. the rings, from their start (the restored games are rebased to ply 0 of both), 3. the descriptors and the state words
+    const uint64_t n = gmk::image_u64(header + 8), T = gmk::image_u64(header + 16), S = gmk::image_u64(header + 24);
+    uint8_t* moves = const_cast<uint8_t*>(d_image) + gmk::kImageHeaderBytes + gmk::kImageDescBytes * n;
+    int rc = copy_ring(h->d_moves, moves, true, 0, T, h->cap, 1, s);
+    if (rc == GMK_OK) rc = copy_ring(reinterpret_cast<uint8_t*>(h->d_visits), moves + gmk::image_roundup8(T), true, 0, S, h->cap, gmk::kImageRowBytes, s);
+    if (rc != GMK_OK) return rc;
+    hipLaunchKernelGGL(replay_restore_kernel, dim3(1), dim3(kThreads), 0, s, d_image, static_cast<uint64_t>(bytes), h->cap, h->max_games, 1, h->d_state,
+                       h->d_desc, d_status);
+    GMK_HIP_CHECK(hipGetLastError());
+    return GMK_OK;
+}
+
+extern "C" int gmk_replay_image_check_host(const uint8_t* image, int64_t bytes, int64_t info[5]) {
+    if (!image || bytes < static_cast<int64_t>(gmk::kImageHeaderBytes)) {
+        gmk::set_error("gmk_replay_image_check_host: bad arguments (an image of at least 64 bytes)");
+        return GMK_ERR_ARG;
+    }
+    gmk::ReplayImageHeader h;
+    const int fault = gmk::replay_image_check(image, static_cast<uint64_t>(bytes), &h);
+    if (fault != gmk::kImageOk) {
+        gmk::set_error("gmk_replay_image_check_host: %s", gmk::replay_image_fault_text(fault));
+        return GMK_REPLAY_BAD_IMAGE;
+    }
+    if (info) {
+        info[0] = static_cast<int64_t>(h.n);
+        info[1] = static_cast<int64_t>(h.T);
+        info[2] = static_cast<int64_t>(h.S);
+        info[3] = static_cast<int64_t>(h.head);
+        info[4] = 0;
+    }
     return GMK_OK;
 }

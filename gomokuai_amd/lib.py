@@ -48,7 +48,7 @@ EXPORTS = [
     "gmk_pattern_policy", "gmk_pattern_policy_host", "gmk_pattern_play",
     "gmk_match_referee",
     "gmk_replay_create", "gmk_replay_destroy", "gmk_replay_reset", "gmk_replay_append", "gmk_replay_append_packed", "gmk_replay_size",
-    "gmk_replay_sample", "gmk_replay_draw_host",
+    "gmk_replay_sample", "gmk_replay_draw_host", "gmk_replay_image_bytes", "gmk_replay_snapshot", "gmk_replay_restore", "gmk_replay_image_check_host",
     "gmk_train_create", "gmk_train_destroy", "gmk_train_forward", "gmk_train_grads", "gmk_train_step", "gmk_train_params", "gmk_train_set_params",
     "gmk_train_get_block", "gmk_train_set_block", "gmk_train_set_step_count", "gmk_train_export", "gmk_train_info",
 ]
@@ -174,6 +174,10 @@ def load():
     L.gmk_replay_size.argtypes = [vp] + [C.POINTER(C.c_int64)] * 4 + [vp]
     L.gmk_replay_sample.argtypes = [vp, C.c_int, C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     L.gmk_replay_draw_host.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, vp]
+    L.gmk_replay_image_bytes.argtypes = [vp, C.POINTER(C.c_int64), vp]
+    L.gmk_replay_snapshot.argtypes = [vp, vp, C.c_int64, vp, vp]
+    L.gmk_replay_restore.argtypes = [vp, vp, C.c_int64, vp, vp]
+    L.gmk_replay_image_check_host.argtypes = [vp, C.c_int64, vp]
     L.gmk_train_create.argtypes = [vp] * 16 + [C.c_int, C.POINTER(vp)]
     L.gmk_train_destroy.argtypes = [vp]
     L.gmk_train_forward.argtypes = [vp, vp, C.c_int, vp, vp, vp]
@@ -449,7 +453,7 @@ def samples_from_packed(d_buf, n, d_offsets, d_sample_game, d_sample_move, n_sam
 
 
 # ---------------- replay buffer (device pointers; include/gomoku_hip.h) ----------------
-REPLAY_BAD_LENGTH, REPLAY_TOO_FEW = 1, 2      # the *d_status codes of replay append / sample
+REPLAY_BAD_LENGTH, REPLAY_TOO_FEW, REPLAY_BAD_IMAGE, REPLAY_NO_ROOM = 1, 2, 3, 4      # the *d_status codes of replay append / sample / snapshot / restore
 
 
 def replay_draw_host(seed, step, population, batch):
@@ -457,6 +461,20 @@ def replay_draw_host(seed, step, population, batch):
     out = np.zeros(int(batch) if batch > 0 else 0, dtype=np.int64)
     _check(load().gmk_replay_draw_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), int(population), int(batch), out.ctypes.data))
     return out
+
+
+def replay_image_check_host(image):
+    """gmk_replay_image_check_host on a buffer image (bytes, or a uint8 numpy array): -> {"games", "plies", "population", "head"}.
+    Raises ValueError, naming the broken rule, if the image is not valid, and GmkError if it has fewer than 64 bytes; needs no GPU."""
+    image = np.ascontiguousarray(np.frombuffer(image, dtype=np.uint8) if isinstance(image, (bytes, bytearray, memoryview)) else image)
+    if image.dtype != np.uint8 or image.ndim != 1:
+        raise ValueError("replay_image_check_host: the image must be a flat uint8 array")
+    info = np.zeros(5, dtype=np.int64)
+    rc = load().gmk_replay_image_check_host(image.ctypes.data, int(image.size), info.ctypes.data)
+    if rc == REPLAY_BAD_IMAGE:
+        raise ValueError(load().gmk_last_error().decode())
+    _check(rc)
+    return {"games": int(info[0]), "plies": int(info[1]), "population": int(info[2]), "head": int(info[3])}
 
 
 class ReplayHandle:
@@ -493,6 +511,21 @@ class ReplayHandle:
     def sample(self, batch, step, augment, states_float, d_states, d_values, d_pi, d_picked, d_status, stream=None):
         _check(load().gmk_replay_sample(self.h, int(batch), int(step), int(bool(augment)), int(bool(states_float)), d_states, d_values, d_pi,
                                         d_picked, d_status, stream))
+
+    def image_bytes(self, stream=None):
+        """The size of the image of what is held now; synchronises `stream`."""
+        v = C.c_int64()
+        _check(load().gmk_replay_image_bytes(self.h, C.byref(v), stream))
+        return v.value
+
+    def snapshot(self, d_image, capacity_bytes, d_status, stream=None):
+        """gmk_replay_snapshot: the image into d_image (8-byte aligned); *d_status = REPLAY_NO_ROOM: nothing was written.  Drains `stream` once."""
+        _check(load().gmk_replay_snapshot(self.h, d_image, int(capacity_bytes), d_status, stream))
+
+    def restore(self, d_image, n_bytes, d_status, stream=None):
+        """gmk_replay_restore: the image's games replace what is held; *d_status = REPLAY_BAD_IMAGE / REPLAY_NO_ROOM: nothing changed.
+        Drains `stream` once."""
+        _check(load().gmk_replay_restore(self.h, d_image, int(n_bytes), d_status, stream))
 
 
 # ---------------- K11: the trainer (device pointers; include/gomoku_hip.h) ----------------

@@ -1182,6 +1182,54 @@ class ReplayBuffer:
         a, d = self._status.tolist()
         return a, d
 
+    def state_dict(self):
+        """What a checkpoint keeps of the buffer: {"image": the held games as a uint8 CPU tensor (gmk_replay_snapshot; the format is in
+        include/gomoku_hip.h), "seed", "step" (the draw counter of sample(step=None)), "capacity_plies", "max_games"}.  Synchronises."""
+        stream = _stream(self.device)
+        size = self._h.image_bytes(stream)
+        image = torch.empty(size, dtype=torch.uint8, device=self.device)
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._h.snapshot(image.data_ptr(), size, status.data_ptr(), stream)
+        code = int(status.item())
+        if code:
+            raise RuntimeError("ReplayBuffer.state_dict: gmk_replay_snapshot refused an image of its own size (status %d)" % code)
+        return {"image": image.cpu(), "seed": self.seed, "step": self._step, "capacity_plies": self.capacity_plies, "max_games": self.max_games}
+
+    def load_state_dict(self, state):
+        """The games, their serials and the draw counter of a state_dict() replace what this buffer holds, so that its draws and evictions
+        go on as the saved buffer's would have.  Raises ValueError -- and leaves the buffer as it was -- if the seeds differ (the draws
+        would silently differ), if the image is not valid, or if its games do not fit capacity_plies and max_games."""
+        mask = 0xFFFFFFFFFFFFFFFF
+        if int(state["seed"]) & mask != self.seed & mask:
+            raise ValueError("ReplayBuffer.load_state_dict: the state was saved with seed %d, this buffer draws with seed %d" % (int(state["seed"]), self.seed))
+        image = state["image"]
+        if not torch.is_tensor(image) or image.dtype != torch.uint8 or image.dim() != 1 or image.numel() < 64:
+            raise ValueError("ReplayBuffer.load_state_dict: the image must be a flat uint8 tensor of at least 64 bytes")
+        step = int(state["step"])
+        G.replay_image_check_host(image.cpu().contiguous().numpy())          # ValueError names the broken rule
+        d_image = image.to(self.device).contiguous()
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._h.restore(d_image.data_ptr(), d_image.numel(), status.data_ptr(), _stream(self.device))
+        code = int(status.item())
+        if code == G.REPLAY_NO_ROOM:
+            raise ValueError("ReplayBuffer.load_state_dict: the saved games do not fit capacity_plies = %d and max_games = %d"
+                             % (self.capacity_plies, self.max_games))
+        if code:
+            raise ValueError("ReplayBuffer.load_state_dict: the device refused the image (status %d)" % code)
+        self._step = step
+
+    @classmethod
+    def from_state_dict(cls, state, capacity_plies=None, max_games=None, device=None):
+        """A new buffer with the saved seed that holds the saved games; the sizes default to the saved ones."""
+        buf = cls(state["capacity_plies"] if capacity_plies is None else capacity_plies, state["max_games"] if max_games is None else max_games,
+                  seed=state["seed"], device=device)
+        try:
+            buf.load_state_dict(state)
+        except Exception:
+            buf.close()
+            raise
+        return buf
+
     def __len__(self):
         """The population of an augmented draw: 8 x the sampled plies held -- what len(DataHelper.buffer) counts."""
         return 8 * self._h.size(_stream(self.device))[2]

@@ -6,15 +6,26 @@ Play, keep, draw, learn, hand the new weights to the searcher -- all in HBM on o
     fused, trainer = FusedPolicyValueNetwork(net), Trainer(net, max_batch=512)
     replay = selfplay.ReplayBuffer(200_000)
     loop = TrainingLoop(replay, trainer, fused, export_every=1)
-    loop.run(100, play=lambda: selfplay.play_network_games(32, fused, playouts=400))
+    if os.path.exists("run.pt"):
+        loop.load("run.pt")                      # trainer, buffer, schedule and counters: the run goes on with the bits it would have had
+    play = lambda: selfplay.play_network_games(32, fused, playouts=400, seed=SEED + loop.total_steps, first_game_id=32 * loop.total_steps)
+    loop.run(100, play=play)
 
-`play` returns a GameRecords with visit counts on the buffer's device (or None); the loop appends it before every step.
+`play` returns a GameRecords with visit counts on the buffer's device (or None); the loop appends it before every step.  The loop does not
+save `play`: one that derives its seed and first_game_id from loop.total_steps, as above, plays after a resume what it would have played.
 
 The win-rate schedule of the reference (evaluate_network / eval_agents, train.py:88-126) is EvaluationSchedule; with eval_period the loop
-plays its match every eval_period steps (selfplay.play_evaluation_games: K7 + K9 against the current opponent, refereed on the device):
+plays its match every eval_period steps (selfplay.play_evaluation_games: K7 + K9 against the current opponent, refereed on the device),
+and on_checkpoint is where a run saves itself (save() replaces the file atomically: a job killed in the middle leaves the old one):
 
-    loop = TrainingLoop(replay, trainer, fused, eval_period=100, on_best=save, on_checkpoint=save)
+    loop = TrainingLoop(replay, trainer, fused, eval_period=100, on_best=save_model, on_checkpoint=lambda name: loop.save("run.pt"))
+
+parse_checkpoint_name reads the counters back from the name on_checkpoint gets, as TrainingPipeline.restore_model does (train.py:137-145).
 """
+import os
+
+import numpy as np
+import torch
 
 # DATA_CONFIG["schedule"] of the reference (config.py:8-20) without its two botzone programs, which do not exist here
 SUPERVISOR = ("traditional_mcts", {"c_puct": 5.0, "c_iterations": 20000})
@@ -66,6 +77,47 @@ class EvaluationSchedule:
             else:
                 self.best_win_rate = win_rate
         return events
+
+    def state_dict(self):
+        """The three numbers restore_model reads back (train.py:141-144).  The candidates and eval_rounds are configuration: not saved."""
+        return {"schedule_level": self.schedule_level, "ref_iterations": self.ref_iterations, "best_win_rate": self.best_win_rate}
+
+    def load_state_dict(self, state):
+        level = int(state["schedule_level"])
+        if not 0 <= level < len(self.candidates):
+            raise ValueError("EvaluationSchedule.load_state_dict: schedule_level %d, but there are %d candidates" % (level, len(self.candidates)))
+        self.schedule_level, self.ref_iterations, self.best_win_rate = level, int(state["ref_iterations"]), float(state["best_win_rate"])
+
+
+def parse_checkpoint_name(name):
+    """The counters in the name TrainingLoop.evaluate gives on_checkpoint, "current_model-<steps>-<level>-<ref_iterations>-<rate>", with or
+    without directories in front (restore_model, train.py:140-144) -> {"total_steps", "schedule_level", "ref_iterations", "best_win_rate"}.
+    Anything else raises ValueError."""
+    parts = os.path.basename(str(name)).split("-")
+    try:
+        if len(parts) != 5 or parts[0] != "current_model":
+            raise ValueError
+        out = {"total_steps": int(parts[1]), "schedule_level": int(parts[2]), "ref_iterations": int(parts[3]), "best_win_rate": float(parts[4])}
+        if min(out["total_steps"], out["schedule_level"], out["ref_iterations"]) < 0 or not 0.0 <= out["best_win_rate"] <= 1.0:
+            raise ValueError
+    except ValueError:
+        raise ValueError("parse_checkpoint_name: %r is not current_model-<steps>-<level>-<ref_iterations>-<rate>" % (name,)) from None
+    return out
+
+
+def _plain(value):
+    """A history value as Python numbers, strings, lists, dicts and tensors only -- what torch.load(weights_only=True) reads back."""
+    if isinstance(value, dict):
+        return {str(k): _plain(v) for k, v in value.items()}
+    if isinstance(value, (list, tuple)):
+        return [_plain(v) for v in value]
+    if isinstance(value, np.ndarray):
+        return value.tolist()
+    if isinstance(value, np.generic):
+        return value.item()
+    if torch.is_tensor(value):
+        return value.detach().cpu()
+    return value
 
 
 class TrainingLoop:
@@ -141,7 +193,9 @@ class TrainingLoop:
 
     def run(self, n_steps, play=None, first_move=0):
         """n_steps steps; before each, play() (if given) supplies new games for the buffer.  A step is skipped -- nothing is drawn -- while
-        the buffer holds no more samples than a batch (generate_batch, data_helper.py:133-139).  -> the records of the steps taken."""
+        the buffer holds no more samples than a batch (generate_batch, data_helper.py:133-139).  -> the records of the steps taken.
+        `play` stays the caller's business and is not part of a checkpoint: a resumable one derives its seed and first_game_id from
+        self.total_steps, so that a resumed run plays the games the uninterrupted one would have played."""
         taken = []
         for _ in range(int(n_steps)):
             if play is not None:
@@ -152,3 +206,53 @@ class TrainingLoop:
                 continue
             taken.append(self.step())
         return taken
+
+    # ---- checkpoint and resume: everything a run needs to go on with the bits it would have had ----
+    def config(self):
+        """The loop's hyperparameters, as a checkpoint keeps them under "config"."""
+        return {"batch_size": self.batch_size, "lr": self.lr, "kl_target": self.kl_target, "num_epoches": self.num_epoches,
+                "export_every": self.export_every, "eval_period": self.eval_period, "eval_playouts": self.eval_playouts}
+
+    def state_dict(self):
+        """{"total_steps", "lr_multiplier", "history", "config", "trainer", "replay", "schedule" (None without one)}: Python numbers, strings,
+        lists, dicts and torch tensors only, so torch.load(weights_only=True) reads it back.  Synchronises."""
+        t = self.trainer.state_dict()
+        trainer = {"step": int(t["step"]), **{k: {name: torch.from_numpy(np.array(a, dtype=np.float32)) for name, a in t[k].items()} for k in ("params", "m", "v")}}
+        return {"total_steps": self.total_steps, "lr_multiplier": self.lr_multiplier, "history": _plain(self.history), "config": self.config(),
+                "trainer": trainer, "replay": self.replay.state_dict(), "schedule": None if self.schedule is None else self.schedule.state_dict()}
+
+    def load_state_dict(self, state):
+        """Restores a state_dict() into this loop's own trainer, replay and schedule, and exports the restored parameters into `fused` if
+        there is one.  Raises ValueError, naming the keys, if the saved "config" differs from this loop's -- before anything is changed;
+        so does a buffer state that the replay refuses (ReplayBuffer.load_state_dict)."""
+        mine, saved = self.config(), dict(state["config"])
+        differ = sorted(k for k in set(mine) | set(saved) if k not in mine or k not in saved or mine[k] != saved[k])
+        if differ:
+            raise ValueError("TrainingLoop.load_state_dict: the saved config differs in " + ", ".join(
+                "%s (saved %r, here %r)" % (k, saved.get(k), mine.get(k)) for k in differ))
+        if state["schedule"] is not None and self.schedule is None:
+            self.schedule = EvaluationSchedule()
+        self.replay.load_state_dict(state["replay"])                  # the one part that can refuse: first
+        if state["schedule"] is not None:
+            self.schedule.load_state_dict(state["schedule"])
+        t = state["trainer"]
+        self.trainer.load_state_dict({"step": int(t["step"]), **{k: {name: a.numpy() for name, a in t[k].items()} for k in ("params", "m", "v")}})
+        self.total_steps, self.lr_multiplier, self.history = int(state["total_steps"]), float(state["lr_multiplier"]), list(state["history"])
+        if self.fused is not None:
+            self.trainer.export(self.fused)
+
+    def save(self, path):
+        """state_dict() to `path` with torch.save, through a temporary file beside it and os.replace: a job killed in the middle leaves the
+        old file."""
+        path = os.fspath(path)
+        tmp = "%s.tmp.%d" % (path, os.getpid())
+        try:
+            torch.save(self.state_dict(), tmp)
+            os.replace(tmp, path)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+
+    def load(self, path):
+        """load_state_dict() of a file save() wrote, read with weights_only=True.  A file that cannot be read leaves the loop as it was."""
+        self.load_state_dict(torch.load(os.fspath(path), map_location="cpu", weights_only=True))

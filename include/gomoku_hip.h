@@ -269,7 +269,7 @@ int gmk_samples_from_packed(const uint8_t *d_buf, int n, const int64_t *d_offset
  * Takes the place of DataHelper.buffer + DataHelper.generate_batch (network/data_helper.py:67-83, 97-139).  The handle keeps RECORDS, not
  * tuples: one byte per stored ply, one 450-byte visit row per sampled ply, 32 bytes per game; a minibatch is built from them when it is
  * drawn (K4 + K5 for one sample and one symmetry per wavefront; states, value and pi are the bits gmk_samples_from_records writes).
- * Append and draw are asynchronous on `stream` and make no host round trip; only gmk_replay_size synchronises.  One handle serves one
+ * Append and draw are asynchronous on `stream` and make no host round trip; gmk_replay_size and the image calls below synchronise.  One handle serves one
  * stream at a time.  The device memory comes from the library's block pool (gmk_pool_release) and is not cleared.
  *
  * Capacity and eviction.  The buffer holds at most capacity_plies stored plies and max_games games.  An append of n games gives them the
@@ -305,8 +305,45 @@ int gmk_samples_from_packed(const uint8_t *d_buf, int n, const int64_t *d_offset
  * left or never fitted = the serial of the oldest game held; any of the four pointers may be NULL.  gmk_replay_reset empties the buffer
  * (serials start at 0 again).  GMK_ERR_ARG: a NULL handle or pointer, a misaligned pointer (d_lens, d_buf, d_status and float outputs
  * 4 bytes; d_offsets and d_picked 8; d_visits 2), n < 0, batch < 0, first_move outside [0, 225], capacity_plies outside [225, 2^40],
- * max_games outside [1, capacity_plies]; in gmk_replay_draw_host also batch > population.  n = 0 and batch = 0 are no-ops. */
-enum { GMK_REPLAY_BAD_LENGTH = 1, GMK_REPLAY_TOO_FEW = 2 };
+ * max_games outside [1, capacity_plies]; in gmk_replay_draw_host also batch > population.  n = 0 and batch = 0 are no-ops.
+ *
+ * The image (checkpoints).  gmk_replay_snapshot writes, and gmk_replay_restore reads, a position-independent byte image of what the handle
+ * holds: the same bytes for the same held games, wherever the rings stand and whatever the capacities are.  Little-endian, every section
+ * 8-byte aligned:
+ *     0  8 bytes   "GMKRPLY1"
+ *     8  uint64    n      games held
+ *    16  uint64    T      stored plies  = sum len
+ *    24  uint64    S      sampled plies = sum max(0, len - first)
+ *    32  uint64    head   serial of the oldest game held (= evicted_games)
+ *    40  uint64    bytes  size of the whole image
+ *    48  uint64 0, uint64 0   (reserved, must be zero)
+ *    64  n descriptors, oldest game first, 8 bytes each: uint16 len, uint16 first, int8 winner, three zero bytes
+ *    ..  uint8  moves[T], the games back to back, zero bytes up to a multiple of 8
+ *    ..  uint16 visits[S][225], in population order, zero bytes up to a multiple of 8
+ *   bytes = 64 + 8 n + roundup8(T) + roundup8(450 S); an empty buffer is the 64-byte header.
+ * Valid (gomokuai_amd/csrc/replay_image.h, one text for the host and the device): the magic; the reserved words zero; the bytes field
+ * equal to the `bytes` argument and to the formula; n <= 2^40 and head <= 2^62; every len <= 225 and every first <= 225; the descriptors'
+ * pad bytes zero; the descriptors' sums equal to T and S.  The device checks all of that before it reads a move or a visit row, so a
+ * damaged image makes it neither read past `bytes` nor write past the rings; like gmk_replay_append it trusts the move bytes themselves.
+ * gmk_replay_image_check_host checks the same and also that every move byte is below 225 and that the sections' padding is zero; it
+ * needs no GPU and no gmk_init.  It returns GMK_OK and info = {n, T, S, head, 0} (info may be NULL), or GMK_REPLAY_BAD_IMAGE -- as its
+ * return value, the one positive one of this header -- with the broken rule in gmk_last_error.  The winner byte is copied, not judged.
+ * gmk_replay_image_bytes: the size of the image of what is held now.
+ * gmk_replay_snapshot writes that image to d_image and *d_status = 0; the handle does not change.  If capacity_bytes is too small,
+ * *d_status = GMK_REPLAY_NO_ROOM and no byte of d_image is written.
+ * gmk_replay_restore replaces whatever the handle holds by the image's games.  They keep their serials head .. head + n - 1: afterwards
+ * evicted_games = head, the next append gets serial head + n, and gmk_replay_size, every output of gmk_replay_sample (d_picked included)
+ * and which games every later append evicts are those of the handle the image was taken from (the same games leave when the capacities
+ * are equal).  Where the games stand in the rings is not kept: they are laid down from the rings' start.  *d_status = GMK_REPLAY_BAD_IMAGE
+ * if the image is not valid, else GMK_REPLAY_NO_ROOM if T > capacity_plies or n > max_games, else 0; a refusal changes no byte of the
+ * handle's state, descriptors or rings.
+ * Synchronisation: gmk_replay_image_bytes, gmk_replay_snapshot and gmk_replay_restore each drain `stream` once (a checkpoint is not a
+ * step); snapshot and restore then leave their copies queued on it.  The descriptors go through a kernel each way (restore: one workgroup
+ * that validates, takes the prefix sums and writes descriptors and state words last); the plies and the visit rows are one contiguous run
+ * of each ring modulo the capacity and move as at most two device-to-device copies each.
+ * GMK_ERR_ARG here: a NULL handle or pointer (info excepted), d_image not 8-byte or d_status not 4-byte aligned, bytes < 64,
+ * capacity_bytes < 0. */
+enum { GMK_REPLAY_BAD_LENGTH = 1, GMK_REPLAY_TOO_FEW = 2, GMK_REPLAY_BAD_IMAGE = 3, GMK_REPLAY_NO_ROOM = 4 };
 typedef struct gmk_replay gmk_replay;
 int gmk_replay_create(int64_t capacity_plies, int64_t max_games, uint64_t seed, gmk_replay **out);
 int gmk_replay_destroy(gmk_replay *h);
@@ -319,6 +356,10 @@ int gmk_replay_size(gmk_replay *h, int64_t *games, int64_t *plies, int64_t *popu
 int gmk_replay_sample(gmk_replay *h, int batch, int64_t step, int augment, int states_float, void *d_states, float *d_values, float *d_pi,
                       int64_t *d_picked, int32_t *d_status, void *stream);
 int gmk_replay_draw_host(uint64_t seed, int64_t step, int64_t population, int64_t batch, int64_t *h_index);
+int gmk_replay_image_bytes(gmk_replay *h, int64_t *bytes, void *stream);
+int gmk_replay_snapshot(gmk_replay *h, uint8_t *d_image, int64_t capacity_bytes, int32_t *d_status, void *stream);
+int gmk_replay_restore(gmk_replay *h, const uint8_t *d_image, int64_t bytes, int32_t *d_status, void *stream);
+int gmk_replay_image_check_host(const uint8_t *image, int64_t bytes, int64_t info[5]);
 
 /* ---- K6: pattern-guided tree search, the reference's self-play supervisor ("traditional_mcts", config.py:9-12) ----
  * Replaces MCTS(policy = TraditionalPolicy(c_puct)) : core/lib/include/policies/Traditional.h:17-69 on top of
