@@ -987,7 +987,7 @@ extern "C" int gmk_trad_destroy(gmk_trad* t) {
     }
     (void)gmk::device_free(t->d_states); (void)gmk::device_free(t->d_stat); (void)gmk::device_free(t->d_info); (void)gmk::device_free(t->d_link);
     (void)gmk::device_free(t->d_front); (void)gmk::device_free(t->d_ord); (void)gmk::device_free(t->d_stat2); (void)gmk::device_free(t->d_info2); (void)gmk::device_free(t->d_front2);
-    (void)gmk::device_free(t->d_link2); (void)gmk::device_free(t->d_ord2); (void)gmk::device_free(t->d_amaf); (void)gmk::device_free(t->d_amaf2); (void)gmk::device_free(t->d_forced); (void)gmk::device_free(t->d_priors); (void)gmk::device_free(t->d_hdr); (void)gmk::device_free(t->d_moves); (void)gmk::device_free(t->d_lens); (void)gmk::device_free(t->d_game_ids); (void)gmk::device_free(t->d_path_spill);
+    (void)gmk::device_free(t->d_link2); (void)gmk::device_free(t->d_ord2); (void)gmk::device_free(t->d_amaf); (void)gmk::device_free(t->d_amaf2); (void)gmk::device_free(t->d_forced); (void)gmk::device_free(t->d_priors); (void)gmk::device_free(t->d_hdr); (void)gmk::device_free(t->d_moves); (void)gmk::device_free(t->d_lens); (void)gmk::device_free(t->d_game_ids); (void)gmk::device_free(t->d_path_spill); (void)gmk::device_free(t->d_ensemble);
     delete t;
     return GMK_OK;
 }

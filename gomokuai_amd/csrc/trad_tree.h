@@ -119,6 +119,8 @@ struct gmk_trad {
     uint32_t* block_link = nullptr;
     uint8_t* block_ord = nullptr;
     uint2* block_amaf = nullptr;                                            // TraditionalPolicy + RAVE handles: the sixth block (ensure_amaf, trad_kernel.hip)
+    void* d_ensemble = nullptr;                                             // accumulators of gmk_trad_ensemble_merge (ensemble_kernel.hip), [ensemble_capacity] ensembles
+    int ensemble_capacity = 0;
     size_t arena_stride() const { return (paired && d_stat2 > d_stat) ? static_cast<size_t>(d_stat2 - d_stat) : 0; }
     int policy = 0;                                                          // 0 not searched yet, 1 TraditionalPolicy (gmk_trad_run), 2 PoolRAVEPolicy (gmk_trad_run_poolrave),
                                                                              // 3 TraditionalPolicy + RAVE (gmk_trad_run_rave): one per handle

@@ -6,6 +6,7 @@ is host-side interop only.
     python -m gomokuai_amd.interface botzone   --agent traditional:5 --ms 960        < request.json
     python -m gomokuai_amd.interface keepalive --agent random:5:5    --iterations 2000
     python -m gomokuai_amd.interface console   --agent traditional:5 --agent2 traditional:7 --ms 1000
+    python -m gomokuai_amd.interface botzone   --agent random-mcts:5:5 --replicas 1024 --ms 960     < request.json
 """
 import datetime
 import json
@@ -115,6 +116,63 @@ class MCTSAgent(Agent):
             self.mcts.reset()
 
 
+class EnsembleAgent(Agent):
+    """An MCTS agent whose search is an ensemble of `replicas` trees of the same root on one GPU (gomokuai_amd/ensemble.py, K13), merged on the
+    device; the move is the argmax of evalState's probabilities from the merged visits, as MCTSAgent plays it.  iterations = playouts per
+    REPLICA and move; milliseconds = launches of `chunk` playouts per replica until the time has passed (at least one, at most max_playouts
+    per move: the arenas are sized for that).  The trees are kept across moves (step) while the board advances by played moves; anything else
+    -- a revert, a new game -- starts them anew from the board."""
+
+    def __init__(self, policy, replicas, milliseconds=None, iterations=None, quiet=False, chunk=64, max_playouts=1024, **search_args):
+        from .ensemble import EnsembleSearch
+        self.ms, self.iterations, self.quiet, self.chunk = milliseconds, iterations, quiet, int(chunk)
+        self.max_playouts = int(iterations) if iterations is not None else int(max_playouts)
+        search_args.setdefault("playouts_capacity", 3 * self.max_playouts)      # a kept subtree and the new search
+        self.search = EnsembleSearch(policy, replicas, **search_args)
+        self.moves, self.playouts, self.seconds = None, 0, 0.0
+
+    def name(self):
+        return "EnsembleAgent:%s:%dx%s" % (self.search.policy, self.search.replicas, "%dms" % self.ms if self.iterations is None else "%dit" % self.iterations)
+
+    def sync_with_board(self, board):
+        moves = [int(p.id) for p in board.move_record]
+        known = self.moves
+        if known is not None and len(known) < len(moves) <= len(known) + 2 and moves[:len(known)] == known:
+            for cell in moves[len(known):]:                        # our own move and the opponent's reply: follow them, subtrees kept
+                self.search.step([cell])
+        elif known is None or moves != known:
+            self.search.set_positions([moves])
+        self.moves = moves
+
+    def get_action(self, board):
+        import time
+        import torch
+        t0 = time.perf_counter()
+        self.playouts = 0
+        if self.iterations is not None:
+            self.search.search(self.iterations)
+            self.playouts = int(self.iterations)
+        else:
+            while True:                                            # at least one chunk
+                self.search.search(self.chunk)
+                torch.cuda.current_stream().synchronize()
+                self.playouts += self.chunk
+                if (time.perf_counter() - t0) * 1000.0 >= self.ms or self.playouts + self.chunk > self.max_playouts:
+                    break
+        value, probs = self.search.eval_state()[0]
+        self.seconds = time.perf_counter() - t0
+        if not self.quiet:
+            print(value)
+        return _core().Position(int(np.argmax(probs)))             # maxCoeff: the first maximum
+
+    def debug_message(self):
+        return {"replicas": self.search.replicas, "playouts_per_replica": self.playouts, "total_playouts": self.playouts * self.search.replicas,
+                "duration": "%dms" % int(self.seconds * 1000)}
+
+    def reset(self):
+        self.moves = None
+
+
 class PatternEvalAgent(Agent):
     """Agent.h:108-161: no search, the move with the largest Heuristic::EvaluationProbs after DecisiveFilter on the agent's own
     incremental evaluator (Heuristic.hpp:16-28, 94-161); the centre on an empty board.  On the GPU that is the policy head of K6:
@@ -161,8 +219,10 @@ class PatternEvalAgent(Agent):
             self.tree.reset_evaluators()
 
 
-def make_agent(spec, milliseconds=960, iterations=None, quiet=False):
-    """'random', 'human', 'pattern', 'random-mcts[:c_puct[:c_rollouts]]', 'traditional[:c_puct]', 'poolrave[:c_puct[:c_bias]]'."""
+def make_agent(spec, milliseconds=960, iterations=None, quiet=False, replicas=1, seed=None):
+    """'random', 'human', 'pattern', 'random-mcts[:c_puct[:c_rollouts]]', 'traditional[:c_puct]', 'poolrave[:c_puct[:c_bias]]'.
+    replicas > 1 turns the three MCTS kinds into an EnsembleAgent of that many trees per position ('traditional' with the reference's root
+    noise, alpha 0.05 / epsilon 0.25: its search has no other source of difference); replicas = 1 builds the agents as ever."""
     core = _core()
     kind, *args = spec.split(":")
     num = [float(a) for a in args]
@@ -172,6 +232,13 @@ def make_agent(spec, milliseconds=960, iterations=None, quiet=False):
         return HumanAgent()
     if kind == "pattern":
         return PatternEvalAgent()
+    if replicas > 1 and kind in ("random-mcts", "traditional", "poolrave"):
+        extra = {} if seed is None else {"seed": int(seed)}
+        if kind == "random-mcts":
+            return EnsembleAgent("random", replicas, milliseconds, iterations, quiet, c_puct=num[0] if num else 5.0, c_rollouts=int(num[1]) if len(num) > 1 else 5, **extra)
+        if kind == "traditional":
+            return EnsembleAgent("traditional", replicas, milliseconds, iterations, quiet, c_puct=num[0] if num else 5.0, root_noise=(0.05, 0.25), **extra)
+        return EnsembleAgent("poolrave", replicas, milliseconds, iterations, quiet, c_puct=num[0] if num else 2.0, **extra)
     if kind == "random-mcts":
         policy = core.RandomPolicy(num[0] if num else 5.0, int(num[1]) if len(num) > 1 else 5)
     elif kind == "traditional":
@@ -300,17 +367,18 @@ def main(argv=None):
     ap.add_argument("--ms", type=int, default=960, help="search time per move (the reference's default constraint)")
     ap.add_argument("--iterations", type=int, default=None, help="playouts per move instead of a time budget")
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--replicas", type=int, default=1, help="trees per position for the MCTS agents (root-parallel ensemble, merged on the GPU); --iterations then counts playouts per replica")
     args = ap.parse_args(argv)
     if args.seed is not None:
         _core().set_seed(args.seed)
         random.seed(args.seed)
     quiet = args.mode != "console"                                  # a bot's stdout carries the protocol only
-    agent = make_agent(args.agent, args.ms, args.iterations, quiet)
+    agent = make_agent(args.agent, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed)
     if args.mode == "botzone":
         return botzone_interface(agent)
     if args.mode == "keepalive":
         return keep_alive_botzone_interface(agent)
-    return console_interface(agent, make_agent(args.agent2, args.ms, args.iterations, quiet))
+    return console_interface(agent, make_agent(args.agent2, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed))
 
 
 if __name__ == "__main__":

@@ -47,6 +47,7 @@ EXPORTS = [
     "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_root_choice", "gmk_trad_step_device", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_run_rave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
     "gmk_pattern_policy", "gmk_pattern_policy_host", "gmk_pattern_play",
     "gmk_match_referee",
+    "gmk_mcts_ensemble_merge", "gmk_trad_ensemble_merge", "gmk_ensemble_merge_host",
     "gmk_replay_create", "gmk_replay_destroy", "gmk_replay_reset", "gmk_replay_append", "gmk_replay_append_packed", "gmk_replay_size",
     "gmk_replay_sample", "gmk_replay_draw_host", "gmk_replay_image_bytes", "gmk_replay_snapshot", "gmk_replay_restore", "gmk_replay_image_check_host",
     "gmk_train_create", "gmk_train_destroy", "gmk_train_forward", "gmk_train_grads", "gmk_train_step", "gmk_train_params", "gmk_train_set_params",
@@ -143,6 +144,9 @@ def load():
     L.gmk_trad_root_choice.argtypes = [vp, vp, vp, vp]
     L.gmk_trad_step_device.argtypes = [vp, vp, vp, C.c_int, vp]
     L.gmk_match_referee.argtypes = [C.c_int, C.c_int] + [vp] * 11
+    L.gmk_mcts_ensemble_merge.argtypes = [vp, C.c_int] + [vp] * 8
+    L.gmk_trad_ensemble_merge.argtypes = [vp, C.c_int] + [vp] * 8
+    L.gmk_ensemble_merge_host.argtypes = [C.c_int, C.c_int] + [vp] * 10
     L.gmk_trad_add_root_noise.argtypes = [vp, C.c_float, C.c_float, C.c_uint64, C.c_uint32]
     L.gmk_trad_set_option.argtypes = [vp, C.c_int, C.c_int]
     L.gmk_trad_root_stats.argtypes = [vp] * 10
@@ -393,6 +397,12 @@ class BatchedMCTS:
                                        None if om is None else om.ctypes.data, stride, None if ol is None else ol.ctypes.data,
                                        d_moves, d_visits, d_lens, d_winner, C.byref(played), stream))
         return played.value
+
+    def ensemble_merge(self, group, visits=None, values=None, cells=None, cells_per_game=None, root_visits=None, root_value=None, status=None, stream=None):
+        """gmk_mcts_ensemble_merge: the games read as n // group ensembles of `group` replicas, their root tables merged on the device into
+        torch tensors on the GPU (any may be None): visits int32 / uint32 [E, 225], values float32 [E, 225], cells int16[E], cells_per_game
+        int16[n], root_visits int32[E], root_value float32[E], status int32[E] (ENSEMBLE_* bits).  Asynchronous on the stream."""
+        _ensemble_merge(load().gmk_mcts_ensemble_merge, self, group, visits, values, cells, cells_per_game, root_visits, root_value, status, stream)
 
     def alg_bytes(self):
         b = C.c_uint64()
@@ -719,6 +729,50 @@ def _check_step_device(tree, cells, verdict):
     assert verdict.is_cuda and verdict.dtype == torch.int32 and verdict.shape == (tree.n,) and verdict.is_contiguous()
 
 
+# ---------------- K13: root-parallel ensembles (gmk_*_ensemble_merge) ----------------
+ENSEMBLE_MISMATCH, ENSEMBLE_RANGE, ENSEMBLE_SATURATED = 1, 2, 4      # bits of the merge's status words
+ENSEMBLE_MAX_GROUP = 4096
+
+
+def _ensemble_merge(entry, tree, group, visits, values, cells, cells_per_game, root_visits, root_value, status, stream):
+    import torch
+    group = int(group)
+    n_ens = tree.n // group if group > 0 and tree.n % group == 0 else 0      # (a bad group: the library refuses it; no shape to hold the tensors to)
+    def ptr(t, size, shape):
+        if t is None:
+            return None
+        assert t.is_cuda and t.is_contiguous() and t.element_size() == size and (n_ens == 0 or tuple(t.shape) == shape), "ensemble_merge: a tensor of the wrong shape or type"
+        return t.data_ptr()
+    _check(entry(tree.h, group, ptr(visits, 4, (n_ens, N)), ptr(values, 4, (n_ens, N)), ptr(cells, 2, (n_ens,)), ptr(cells_per_game, 2, (tree.n,)),
+                 ptr(root_visits, 4, (n_ens,)), ptr(root_value, 4, (n_ens,)), ptr(status, 4, (n_ens,)), _current_stream(stream)))
+
+
+def ensemble_merge_host(group, visits, values, root_visits=None, root_values=None):
+    """gmk_ensemble_merge_host: the merge of gmk_*_ensemble_merge on host tables -- visits uint32[n, 225], values float32[n, 225], and
+    optionally root_visits uint32[n], root_values float32[n] of n = E * group replicas -> {"visits" u32[E,225], "values" f32[E,225],
+    "cells" i16[E], "root_visits" u32[E], "root_value" f32[E], "status" i32[E]}.  Needs no GPU."""
+    visits = np.ascontiguousarray(visits, dtype=np.uint32)
+    values = np.ascontiguousarray(values, dtype=np.float32)
+    group = int(group)
+    if visits.ndim != 2 or visits.shape[1] != N or values.shape != visits.shape:
+        raise ValueError("ensemble_merge_host: visits and values are [n, 225] tables")
+    n = visits.shape[0]
+    if group >= 1 and n % group != 0:
+        raise GmkError("ensemble_merge_host: group %d does not divide the %d games" % (group, n))
+    rv = rq = None
+    if root_visits is not None:
+        rv = np.ascontiguousarray(root_visits, dtype=np.uint32)
+        rq = np.ascontiguousarray(root_values, dtype=np.float32)
+        assert rv.shape == (n,) and rq.shape == (n,)
+    n_ens = n // group if group >= 1 else 0
+    out = {"visits": np.zeros((n_ens, N), np.uint32), "values": np.zeros((n_ens, N), np.float32), "cells": np.zeros(n_ens, np.int16),
+           "root_visits": np.zeros(n_ens, np.uint32), "root_value": np.zeros(n_ens, np.float32), "status": np.zeros(n_ens, np.int32)}
+    _check(load().gmk_ensemble_merge_host(n_ens, group, visits.ctypes.data, values.ctypes.data, None if rv is None else rv.ctypes.data,
+                                          None if rq is None else rq.ctypes.data, *[out[k].ctypes.data for k in
+                                          ("visits", "values", "cells", "root_visits", "root_value", "status")]))
+    return out
+
+
 def match_referee(cells, visit_rows, row_of, moves, lens, winner, visits, verdict, status, unfinished, stream=None):
     """gmk_match_referee: one ply of n games on the device.  cells int16[n], visit_rows 2-byte [n, 225] or None, row_of int32[n] or None
     (slot -> record row), the records moves uint8[rows, 225] / lens int32[rows] / winner int8[rows] / visits 2-byte [rows, 225, 225] or None,
@@ -806,6 +860,10 @@ class TraditionalMCTS:
         """gmk_trad_step_device: step() with the cells (torch int16[n]) and the referee's verdicts (torch int32[n], MATCH_*) on the GPU."""
         _check_step_device(self, cells, verdict)
         _check(load().gmk_trad_step_device(self.h, cells.data_ptr(), verdict.data_ptr(), int(bool(fresh_root)), _current_stream(stream)))
+
+    def ensemble_merge(self, group, visits=None, values=None, cells=None, cells_per_game=None, root_visits=None, root_value=None, status=None, stream=None):
+        """gmk_trad_ensemble_merge: BatchedMCTS.ensemble_merge for a K6 / K6 + RAVE / K8 handle."""
+        _ensemble_merge(load().gmk_trad_ensemble_merge, self, group, visits, values, cells, cells_per_game, root_visits, root_value, status, stream)
 
     def add_root_noise(self, alpha=0.05, epsilon=0.25, seed=DEFAULT_SEED, first_game_id=0):
         _check(load().gmk_trad_add_root_noise(self.h, alpha, epsilon, seed, first_game_id))

@@ -579,6 +579,42 @@ int gmk_az_root_stats(gmk_az* a, uint32_t* h_visits, float* h_values, float* h_p
 int gmk_match_referee(int n, int rows, const int16_t* d_cells, const uint16_t* d_visit_rows, const int32_t* d_row_of, uint8_t* d_moves, int32_t* d_lens,
                       int8_t* d_winner, uint16_t* d_visits, int32_t* d_verdict, int32_t* d_status, int32_t* d_unfinished, void* stream);
 
+/* ---- K13: root-parallel tree ensembles: one position searched by many replicas, their root tables merged on the device ----
+ * The n_games of a K3 handle (gmk_mcts) or a K6 / K6 + RAVE / K8 handle (gmk_trad) are read as E = n_games / group ensembles of `group`
+ * consecutive games: ensemble e = games e*group .. e*group + group - 1, the REPLICAS of one position, each with its own arena and its own
+ * random streams (its game id).  The merge calls read the replicas' roots after a search and write one table per ensemble; they touch no
+ * tree, so the searches can go on afterwards.  Outputs are device memory, written on `stream`; nothing is copied to the host and the call
+ * does not wait; any output may be NULL:
+ *   d_visits uint32[E][225], d_values float[E][225], d_cells int16[E], d_cells_per_game int16[n_games] (the ensemble's cell once per
+ *   replica: what gmk_mcts_step takes as d_forced_moves and gmk_trad_step_device as d_cells), d_root_visits uint32[E], d_root_value
+ *   float[E], d_status int32[E].
+ * The merge.  With n_r[c], q_r[c] replica r's root child visits and value at cell c (zero without a child) and N_r, V_r its root's, as the
+ * root statistics calls report them:
+ *   visits[c] = sum_r n_r[c]
+ *   S[c]      = sum_r llrint(double(n_r[c]) * double(q_r[c]) * 2^24)     int64; every product rounded on its own, no fused multiply-add
+ *   values[c] = float(double(S[c]) / 2^24 / double(visits[c])), 0 where visits[c] = 0
+ *   root_visits, root_value: the same over (N_r, V_r)
+ *   cell      = the first maximum of visits in ascending cell order (MCTS::stepForward, core/lib/src/MCTS.cpp:129-134), -1 without a visit.
+ * Every sum is a sum of integers, so the result is the same bits for any launch geometry and any order of the replicas.
+ * Status bits: GMK_ENSEMBLE_MISMATCH -- a replica does not stand at the position of replica 0 of its ensemble (the same stones, hence the
+ *   same player to move): the ensemble's visit and value rows and root pair are zeros and its cell is -1 in both cell outputs; other
+ *   ensembles are unaffected.  GMK_ENSEMBLE_RANGE -- a replica holds a count of 2^24 or more: it adds nothing (so |S| < 2^60 always).
+ *   GMK_ENSEMBLE_SATURATED -- a sum of counts passed 2^32 - 1 (possible from 257 replicas on): that uint32 output holds 2^32 - 1; the sums
+ *   themselves are kept in 64 bits, so values, root_value and the cell are those of the exact sums.
+ * A finished or idle replica adds nothing (K3: status bit 0; K6 / K8: status bit 4), nor does one that was positioned and never searched.
+ * GMK_ERR_ARG unless 1 <= group <= 4096 and group divides n_games.
+ * gmk_ensemble_merge_host: the same merge of host tables h_visits uint32[E*group][225], h_values float[E*group][225], h_root_visits
+ *   uint32[E*group], h_root_values float[E*group] (the root pair may be NULL: zeros) into host outputs (any may be NULL); there are no
+ *   positions to compare, so GMK_ENSEMBLE_MISMATCH is never set.  Needs no GPU and no gmk_init. */
+enum { GMK_ENSEMBLE_MISMATCH = 1, GMK_ENSEMBLE_RANGE = 2, GMK_ENSEMBLE_SATURATED = 4 };
+int gmk_mcts_ensemble_merge(gmk_mcts* m, int group, uint32_t* d_visits, float* d_values, int16_t* d_cells, int16_t* d_cells_per_game,
+                            uint32_t* d_root_visits, float* d_root_value, int32_t* d_status, void* stream);
+int gmk_trad_ensemble_merge(gmk_trad* t, int group, uint32_t* d_visits, float* d_values, int16_t* d_cells, int16_t* d_cells_per_game,
+                            uint32_t* d_root_visits, float* d_root_value, int32_t* d_status, void* stream);
+int gmk_ensemble_merge_host(int n_ensembles, int group, const uint32_t* h_visits, const float* h_values, const uint32_t* h_root_visits,
+                            const float* h_root_values, uint32_t* out_visits, float* out_values, int16_t* out_cells,
+                            uint32_t* out_root_visits, float* out_root_value, int32_t* out_status);
+
 /* ---- K9: the convolutional trunk of the policy-value network (the evaluator K7 calls at every leaf) as one fused kernel ----
  * Replaces the convolution layers of PolicyValueNetwork (network/model_tf.py:28-66: conv3x3 6->32->64->128 with ReLU, the 1x1
  * policy head 128->4 and the 1x1 value head 128->2, both with ReLU) for a batch of positions, in float32 on the f32 matrix cores.
