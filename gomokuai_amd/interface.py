@@ -7,6 +7,7 @@ is host-side interop only.
     python -m gomokuai_amd.interface keepalive --agent random:5:5    --iterations 2000
     python -m gomokuai_amd.interface console   --agent traditional:5 --agent2 traditional:7 --ms 1000
     python -m gomokuai_amd.interface botzone   --agent random-mcts:5:5 --replicas 1024 --ms 960     < request.json
+    python -m gomokuai_amd.interface botzone   --agent traditional:5 --vcf 16 --ms 960              < request.json
 """
 import datetime
 import json
@@ -219,10 +220,59 @@ class PatternEvalAgent(Agent):
             self.tree.reset_evaluators()
 
 
-def make_agent(spec, milliseconds=960, iterations=None, quiet=False, replicas=1, seed=None):
+class VCFAgent(Agent):
+    """Any agent with the exact solver for forced wins by continuous fours in front of it (K14, lib.vcf_solve): when the side to move has such
+    a win within `depth` own moves and `budget` candidates, its first move is played and the inner agent is not asked; otherwise the inner agent
+    decides.  The debug message adds both verdicts, the own one and the opponent's ("what threatens me?", reported only)."""
+
+    def __init__(self, inner, depth=16, budget=100000):
+        self.inner, self.depth, self.budget = inner, int(depth), int(budget)
+        self.moves, self.own, self.threat = [], None, None
+
+    def name(self):
+        return "VCF(" + self.inner.name() + ")"
+
+    def sync_with_board(self, board):
+        self.moves = [int(p.id) for p in board.move_record]
+        self.inner.sync_with_board(board)
+
+    def reset(self):
+        self.inner.reset()
+
+    def _solve(self, opponent):
+        from . import lib as G
+        moves = np.zeros((1, max(1, len(self.moves))), np.uint8)
+        moves[0, :len(self.moves)] = self.moves
+        out = G.vcf_solve(moves, np.array([len(self.moves)], np.int32), self.depth, self.budget, opponent=opponent)
+        status, length = int(out["status"][0]), int(out["length"][0])
+        return {"status": G.VCF_STATUS_NAMES[status], "move": int(out["move"][0]), "length": length, "nodes": int(out["nodes"][0]),
+                "pv": [int(c) for c in out["pv"][0][:max(0, 2 * length - 1)]]}
+
+    def get_action(self, board):
+        self.moves = [int(p.id) for p in board.move_record]
+        self.own, self.threat = self._solve(False), None
+        if self.own["status"] == "WIN":
+            return _core().Position(self.own["move"])
+        return self.inner.get_action(board)
+
+    def debug_message(self):
+        if self.own is None:
+            return self.inner.debug_message()
+        if self.threat is None:
+            self.threat = self._solve(True)
+        inner = None if self.own["status"] == "WIN" else self.inner.debug_message()      # a forced win was played: the inner agent was not asked
+        message = dict(inner) if isinstance(inner, dict) else {"inner": inner}
+        message["vcf"], message["vcf_opponent"] = self.own, self.threat
+        return message
+
+
+def make_agent(spec, milliseconds=960, iterations=None, quiet=False, replicas=1, seed=None, vcf=0):
     """'random', 'human', 'pattern', 'random-mcts[:c_puct[:c_rollouts]]', 'traditional[:c_puct]', 'poolrave[:c_puct[:c_bias]]'.
     replicas > 1 turns the three MCTS kinds into an EnsembleAgent of that many trees per position ('traditional' with the reference's root
-    noise, alpha 0.05 / epsilon 0.25: its search has no other source of difference); replicas = 1 builds the agents as ever."""
+    noise, alpha 0.05 / epsilon 0.25: its search has no other source of difference); replicas = 1 builds the agents as ever.
+    vcf = D > 0 puts the forced-win solver in front of the agent (VCFAgent, depth D); 'human' and 'random' stay as they are."""
+    if vcf > 0 and spec.split(":")[0] not in ("human", "random"):
+        return VCFAgent(make_agent(spec, milliseconds, iterations, quiet, replicas, seed), depth=vcf)
     core = _core()
     kind, *args = spec.split(":")
     num = [float(a) for a in args]
@@ -368,17 +418,18 @@ def main(argv=None):
     ap.add_argument("--iterations", type=int, default=None, help="playouts per move instead of a time budget")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--replicas", type=int, default=1, help="trees per position for the MCTS agents (root-parallel ensemble, merged on the GPU); --iterations then counts playouts per replica")
+    ap.add_argument("--vcf", type=int, default=0, metavar="DEPTH", help="put the exact forced-win solver (continuous fours, up to DEPTH own moves) in front of the agents; 0: off")
     args = ap.parse_args(argv)
     if args.seed is not None:
         _core().set_seed(args.seed)
         random.seed(args.seed)
     quiet = args.mode != "console"                                  # a bot's stdout carries the protocol only
-    agent = make_agent(args.agent, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed)
+    agent = make_agent(args.agent, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed, vcf=args.vcf)
     if args.mode == "botzone":
         return botzone_interface(agent)
     if args.mode == "keepalive":
         return keep_alive_botzone_interface(agent)
-    return console_interface(agent, make_agent(args.agent2, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed))
+    return console_interface(agent, make_agent(args.agent2, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed, vcf=args.vcf))
 
 
 if __name__ == "__main__":

@@ -46,6 +46,7 @@ EXPORTS = [
     "gmk_az_create", "gmk_az_destroy", "gmk_az_set_roots", "gmk_az_select", "gmk_az_expand", "gmk_az_select_host", "gmk_az_expand_host", "gmk_az_read_node_host", "gmk_az_read_children_host", "gmk_az_set_leaf_host", "gmk_az_rollout_host", "gmk_az_expand_stages_host", "gmk_az_write_stats_host", "gmk_az_step", "gmk_az_root_choice", "gmk_az_step_device", "gmk_az_advance", "gmk_az_set_slots", "gmk_az_live_games", "gmk_az_set_game_ids", "gmk_az_add_root_noise", "gmk_az_set_option", "gmk_az_add_playouts", "gmk_az_playouts_owed", "gmk_az_root_stats",
     "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_root_choice", "gmk_trad_step_device", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_run_rave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
     "gmk_pattern_policy", "gmk_pattern_policy_host", "gmk_pattern_play",
+    "gmk_vcf_solve", "gmk_vcf_solve_host",
     "gmk_match_referee",
     "gmk_mcts_ensemble_merge", "gmk_trad_ensemble_merge", "gmk_ensemble_merge_host",
     "gmk_replay_create", "gmk_replay_destroy", "gmk_replay_reset", "gmk_replay_append", "gmk_replay_append_packed", "gmk_replay_size",
@@ -170,6 +171,8 @@ def load():
     L.gmk_pattern_policy.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.gmk_pattern_policy_host.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.gmk_pattern_play.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.gmk_vcf_solve.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.gmk_vcf_solve_host.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp, vp]
     L.gmk_replay_create.argtypes = [C.c_int64, C.c_int64, C.c_uint64, C.POINTER(vp)]
     L.gmk_replay_destroy.argtypes = [vp]
     L.gmk_replay_reset.argtypes = [vp, vp]
@@ -704,6 +707,43 @@ def pattern_policy_device(d_moves, stride, d_lens, n, filter=True, d_probs=None,
 def pattern_play(d_moves, d_lens, n, filter=True, max_moves=0, d_winner=None, d_values=None, d_status=None, stream=None):
     """gmk_pattern_play: the n openings in d_moves u8[n,225] / d_lens i32[n] (device pointers) are played out greedily in one launch."""
     _check(load().gmk_pattern_play(d_moves, d_lens, int(n), int(bool(filter)), int(max_moves), d_winner, d_values, d_status, stream))
+
+
+# ---------------- K14: the forced-win solver by continuous fours (gmk_vcf_solve) ----------------
+VCF_NONE, VCF_WIN, VCF_DEPTH, VCF_BUDGET, VCF_OVER, VCF_BAD = 0, 1, 2, 3, 4, 5      # the status of a position (include/gomoku_hip.h)
+VCF_STATUS_NAMES = ("NONE", "WIN", "DEPTH", "BUDGET", "OVER", "BAD")
+VCF_OPPONENT, VCF_ITERATIVE = 1, 2                                                 # flags
+VCF_MAX_DEPTH, VCF_PV = 32, 64
+
+
+def _vcf_flags(opponent, iterative):
+    return (VCF_OPPONENT if opponent else 0) | (VCF_ITERATIVE if iterative else 0)
+
+
+def vcf_solve(moves, lens, max_depth=16, budget=100000, opponent=False, iterative=False):
+    """moves u8[n, stride] (host), lens i32[n]: one move list per position, black first -> {"status" i32[n], "move" i32[n], "length" i32[n],
+    "nodes" u32[n], "pv" u8[n, 64]}: is there a forced win by continuous fours for the side to move (opponent=True: for the other side, moving
+    first), within max_depth attacker moves and `budget` four-making candidates?  Exact; the contract is in include/gomoku_hip.h.
+    Runs on the GPU through gmk_vcf_solve_host; raises without one."""
+    init()
+    moves = np.ascontiguousarray(moves, dtype=np.uint8)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    assert moves.ndim == 2 and lens.shape == (moves.shape[0],)
+    n, stride = moves.shape
+    out = {"status": np.zeros(n, np.int32), "move": np.zeros(n, np.int32), "length": np.zeros(n, np.int32), "nodes": np.zeros(n, np.uint32),
+           "pv": np.full((n, VCF_PV), 255, np.uint8)}
+    if n:
+        _check(load().gmk_vcf_solve_host(moves.ctypes.data, stride, lens.ctypes.data, n, int(max_depth), int(budget), _vcf_flags(opponent, iterative),
+                                         out["status"].ctypes.data, out["move"].ctypes.data, out["length"].ctypes.data, out["nodes"].ctypes.data,
+                                         out["pv"].ctypes.data))
+    return out
+
+
+def vcf_solve_device(d_moves, stride, d_lens, n, max_depth=16, budget=100000, opponent=False, iterative=False,
+                     d_status=None, d_move=None, d_length=None, d_nodes=None, d_pv=None, stream=None):
+    """Device-pointer form (ints, e.g. torch.Tensor.data_ptr()) of gmk_vcf_solve; asynchronous on `stream`, allocates nothing."""
+    _check(load().gmk_vcf_solve(d_moves, int(stride), d_lens, int(n), int(max_depth), int(budget), _vcf_flags(opponent, iterative),
+                                d_status, d_move, d_length, d_nodes, d_pv, stream))
 
 
 # ---------------- K12: the referee of a match between two search handles (gmk_match_referee) and what its callers share ----------------

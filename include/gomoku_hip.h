@@ -669,6 +669,51 @@ int gmk_pattern_policy_host(const uint8_t* h_moves, int stride, const int32_t* h
 int gmk_pattern_play(uint8_t* d_moves, int32_t* d_lens, int n, int filter, int max_moves,
                      int8_t* d_winner, float* d_values, int32_t* d_status, void* stream);
 
+/* ---- K14: the forced-win solver by continuous fours (VCF), exact, per position and in batch ----
+ * No counterpart in the reference; the contract is this block.  All of it is geometry on the 15 x 15 board, the pattern automaton is not involved.
+ * Position g is the move list d_moves[g*stride .. + d_lens[g]), black first and alternating; a cell is y * 15 + x.  The ATTACKER is the side to
+ * move, or with GMK_VCF_OPPONENT the other side, moving first as if the side to move had passed ("what threatens me?"); the defender is the
+ * other colour.  completing(S) = the empty cells whose occupation by colour S makes a run of five OR MORE through that cell (freestyle, as
+ * Board::checkGameEnd; runs do not wrap from one row into the next).  L limits the attacker's moves, the one that makes five included.
+ *
+ *   attack(depth):                                  the attacker is to move and has made `depth` moves
+ *     W = completing(attacker);  if W: pv += [min W]; return WIN
+ *     T = completing(defender);  if |T| >= 2: return FAIL
+ *     if depth + 2 > L: cut = true; return FAIL
+ *     for c in (T if T else all empty cells), ascending:
+ *         F = completing(attacker) with c played;  if F is empty: continue            (not a four: no candidate, no node)
+ *         if nodes == budget: stop everything with BUDGET
+ *         nodes += 1
+ *         if |F| >= 2: pv += [c, F's lowest, F's second lowest]; return WIN
+ *         r = F's only cell; play c and r
+ *         if attack(depth + 1) == WIN: pv = [c, r] + the rest; return WIN
+ *         undo both
+ *     return FAIL
+ *
+ * Plain mode runs attack(0) with L = max_depth.  GMK_VCF_ITERATIVE runs L = 1, 2, .. max_depth in turn, `cut` cleared before each, and stops
+ * at the first WIN or at the first limit that fails without a cut; nodes add up over the limits and the budget is on the total.
+ * Per position (any output pointer may be NULL): d_status int32[n], d_move int32[n], d_length int32[n], d_nodes uint32[n],
+ * d_pv uint8[n][GMK_VCF_PV]:
+ *     GMK_VCF_NONE    FAIL with cut false: no forced win by fours at any depth
+ *     GMK_VCF_WIN     move = pv[0], length = the attacker's moves in pv, which has 2 * length - 1 cells, attacker and defender alternating
+ *     GMK_VCF_DEPTH   no win found and some branch was cut by the limit
+ *     GMK_VCF_BUDGET  nodes == budget and another candidate was due
+ *     GMK_VCF_OVER    a colour already has five or more; nothing is searched
+ *     GMK_VCF_BAD     not a position: a length outside [0, 225] or above stride, a cell >= 225 or a repeated cell; nothing is searched and
+ *                     nothing outside the list is read
+ *   move is -1 and length 0 unless WIN; nodes is 0 for OVER and BAD, else the count when the search stopped; pv cells past the end are 255.
+ *   Every output is an exact function of the list, max_depth, budget and flags.
+ * gmk_vcf_solve: asynchronous on `stream`, allocates nothing; n = 0 does nothing.  GMK_ERR_ARG: a NULL input with n > 0, n < 0, stride < 1,
+ *   max_depth outside [1, GMK_VCF_MAX_DEPTH], unknown flag bits, d_lens or an int32 output not 4-byte aligned.  GMK_ERR_STATE without a device.
+ * gmk_vcf_solve_host: the same with host buffers (allocates, copies in, runs on the GPU, copies out, synchronises). */
+enum { GMK_VCF_MAX_DEPTH = 32, GMK_VCF_PV = 64 };
+enum { GMK_VCF_OPPONENT = 1, GMK_VCF_ITERATIVE = 2 };
+enum { GMK_VCF_NONE = 0, GMK_VCF_WIN = 1, GMK_VCF_DEPTH = 2, GMK_VCF_BUDGET = 3, GMK_VCF_OVER = 4, GMK_VCF_BAD = 5 };
+int gmk_vcf_solve(const uint8_t* d_moves, int stride, const int32_t* d_lens, int n, int max_depth, uint32_t budget, int flags,
+                  int32_t* d_status, int32_t* d_move, int32_t* d_length, uint32_t* d_nodes, uint8_t* d_pv, void* stream);
+int gmk_vcf_solve_host(const uint8_t* h_moves, int stride, const int32_t* h_lens, int n, int max_depth, uint32_t budget, int flags,
+                       int32_t* h_status, int32_t* h_move, int32_t* h_length, uint32_t* h_nodes, uint8_t* h_pv);
+
 /* ---- K11: training the policy-value network on the device (network/train.py:62-86, network/model_tf.py:73-135) ----
  * A gmk_trainer holds the network's sixteen parameter tensors in float32 in their canonical layouts (those gmk_pvnet_create and
  * gmk_pvnet_set_dense take), Adam's two moments, a gradient block and the activations of up to max_batch positions.  One step = forward
