@@ -8,6 +8,7 @@ is host-side interop only.
     python -m gomokuai_amd.interface console   --agent traditional:5 --agent2 traditional:7 --ms 1000
     python -m gomokuai_amd.interface botzone   --agent random-mcts:5:5 --replicas 1024 --ms 960     < request.json
     python -m gomokuai_amd.interface botzone   --agent traditional:5 --vcf 16 --ms 960              < request.json
+    python -m gomokuai_amd.interface botzone   --agent traditional:5 --vcf 16 --vcf-defend --ms 960 < request.json
 """
 import datetime
 import json
@@ -223,11 +224,15 @@ class PatternEvalAgent(Agent):
 class VCFAgent(Agent):
     """Any agent with the exact solver for forced wins by continuous fours in front of it (K14, lib.vcf_solve): when the side to move has such
     a win within `depth` own moves and `budget` candidates, its first move is played and the inner agent is not asked; otherwise the inner agent
-    decides.  The debug message adds both verdicts, the own one and the opponent's ("what threatens me?", reported only)."""
+    decides.  The debug message adds both verdicts, the own one and the opponent's ("what threatens me?", reported only).
+    defend=True acts on the opponent's verdict as well (K15, lib.vcf_defend): when the side to move has no forced win and the opponent has one,
+    the inner agent is still asked, so that its tree stays in step, but its move stands only if it lies in the best class of cells there is:
+    those that HOLD, else those UNKNOWN, else those that LOSE in the greatest number of moves.  Otherwise the cell of that class with the highest
+    lib.pattern_policy(filter=False) probability is played, the lowest cell on a tie.  The debug message then adds `vcf_defence`."""
 
-    def __init__(self, inner, depth=16, budget=100000):
-        self.inner, self.depth, self.budget = inner, int(depth), int(budget)
-        self.moves, self.own, self.threat = [], None, None
+    def __init__(self, inner, depth=16, budget=100000, defend=False):
+        self.inner, self.depth, self.budget, self.defend = inner, int(depth), int(budget), bool(defend)
+        self.moves, self.own, self.threat, self.defence = [], None, None, None
 
     def name(self):
         return "VCF(" + self.inner.name() + ")"
@@ -239,21 +244,56 @@ class VCFAgent(Agent):
     def reset(self):
         self.inner.reset()
 
-    def _solve(self, opponent):
-        from . import lib as G
+    def _lists(self):
         moves = np.zeros((1, max(1, len(self.moves))), np.uint8)
         moves[0, :len(self.moves)] = self.moves
-        out = G.vcf_solve(moves, np.array([len(self.moves)], np.int32), self.depth, self.budget, opponent=opponent)
-        status, length = int(out["status"][0]), int(out["length"][0])
-        return {"status": G.VCF_STATUS_NAMES[status], "move": int(out["move"][0]), "length": length, "nodes": int(out["nodes"][0]),
-                "pv": [int(c) for c in out["pv"][0][:max(0, 2 * length - 1)]]}
+        return moves, np.array([len(self.moves)], np.int32)
+
+    @staticmethod
+    def _verdict(status, move, length, nodes, pv):
+        from . import lib as G
+        return {"status": G.VCF_STATUS_NAMES[int(status)], "move": int(move), "length": int(length), "nodes": int(nodes),
+                "pv": [int(c) for c in pv[:max(0, 2 * int(length) - 1)]]}
+
+    def _solve(self, opponent):
+        from . import lib as G
+        out = G.vcf_solve(*self._lists(), self.depth, self.budget, opponent=opponent)
+        return self._verdict(out["status"][0], out["move"][0], out["length"][0], out["nodes"][0], out["pv"][0])
+
+    def _defend(self, inner_move):
+        """The threat and, where it is a WIN, (the cell to play, the report for the debug message); else (None, None)."""
+        from . import lib as G
+        moves, lens = self._lists()
+        out = G.vcf_defend(moves, lens, self.depth, self.budget)
+        length = int(out["threat_length"][0])
+        self.threat = self._verdict(out["threat_status"][0], out["threat_pv"][0][0] if length else -1, length, out["threat_nodes"][0], out["threat_pv"][0])
+        if self.threat["status"] != "WIN":
+            return None, None
+        verdict, lengths, nodes = out["verdict"][0], out["length"][0].astype(np.int64), out["nodes"][0]
+        holds, unknown, loses = (np.flatnonzero(verdict == v) for v in (G.VCF_CELL_HOLDS, G.VCF_CELL_UNKNOWN, G.VCF_CELL_LOSES))
+        # a cell was searched unless the threat's own line settled it: such a cell LOSES without a node, and a search that finds a win has one
+        report = {"holds": [int(c) for c in holds], "unknown": len(unknown), "loses": len(loses),
+                  "searched": len(holds) + len(unknown) + int(np.count_nonzero(nodes[loses])), "overruled": False}
+        # no cell is FIVE here: the side to move has no forced win, so it has no completing cell
+        longest = loses[lengths[loses] == lengths[loses].max()] if len(loses) else loses
+        best = next((cells for cells in (holds, unknown, longest) if len(cells)), None)
+        if best is None or inner_move in best:
+            return inner_move, report
+        probs = G.pattern_policy(moves, lens, filter=False)["probs"][0]
+        report["overruled"] = True
+        return int(best[int(np.argmax(probs[best]))]), report      # argmax takes the first of equals: the lowest cell
 
     def get_action(self, board):
         self.moves = [int(p.id) for p in board.move_record]
-        self.own, self.threat = self._solve(False), None
+        self.own, self.threat, self.defence = self._solve(False), None, None
         if self.own["status"] == "WIN":
             return _core().Position(self.own["move"])
-        return self.inner.get_action(board)
+        action = self.inner.get_action(board)
+        if self.defend:
+            cell, self.defence = self._defend(int(action.id))
+            if self.defence is not None and self.defence["overruled"]:
+                return _core().Position(cell)
+        return action
 
     def debug_message(self):
         if self.own is None:
@@ -263,16 +303,21 @@ class VCFAgent(Agent):
         inner = None if self.own["status"] == "WIN" else self.inner.debug_message()      # a forced win was played: the inner agent was not asked
         message = dict(inner) if isinstance(inner, dict) else {"inner": inner}
         message["vcf"], message["vcf_opponent"] = self.own, self.threat
+        if self.defence is not None:
+            message["vcf_defence"] = self.defence
         return message
 
 
-def make_agent(spec, milliseconds=960, iterations=None, quiet=False, replicas=1, seed=None, vcf=0):
+def make_agent(spec, milliseconds=960, iterations=None, quiet=False, replicas=1, seed=None, vcf=0, vcf_defend=False):
     """'random', 'human', 'pattern', 'random-mcts[:c_puct[:c_rollouts]]', 'traditional[:c_puct]', 'poolrave[:c_puct[:c_bias]]'.
     replicas > 1 turns the three MCTS kinds into an EnsembleAgent of that many trees per position ('traditional' with the reference's root
     noise, alpha 0.05 / epsilon 0.25: its search has no other source of difference); replicas = 1 builds the agents as ever.
-    vcf = D > 0 puts the forced-win solver in front of the agent (VCFAgent, depth D); 'human' and 'random' stay as they are."""
+    vcf = D > 0 puts the forced-win solver in front of the agent (VCFAgent, depth D); 'human' and 'random' stay as they are.
+    vcf_defend=True (with vcf > 0 only) lets that agent also refuse moves that lose to the opponent's forced win (VCFAgent(defend=True))."""
+    if vcf_defend and vcf <= 0:
+        raise ValueError("vcf_defend needs vcf > 0")
     if vcf > 0 and spec.split(":")[0] not in ("human", "random"):
-        return VCFAgent(make_agent(spec, milliseconds, iterations, quiet, replicas, seed), depth=vcf)
+        return VCFAgent(make_agent(spec, milliseconds, iterations, quiet, replicas, seed), depth=vcf, defend=vcf_defend)
     core = _core()
     kind, *args = spec.split(":")
     num = [float(a) for a in args]
@@ -419,17 +464,20 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--replicas", type=int, default=1, help="trees per position for the MCTS agents (root-parallel ensemble, merged on the GPU); --iterations then counts playouts per replica")
     ap.add_argument("--vcf", type=int, default=0, metavar="DEPTH", help="put the exact forced-win solver (continuous fours, up to DEPTH own moves) in front of the agents; 0: off")
+    ap.add_argument("--vcf-defend", action="store_true", help="with --vcf: also refuse moves that lose to the opponent's forced win by fours, as far as any cell holds")
     args = ap.parse_args(argv)
+    if args.vcf_defend and args.vcf <= 0:
+        ap.error("--vcf-defend needs --vcf DEPTH")
     if args.seed is not None:
         _core().set_seed(args.seed)
         random.seed(args.seed)
     quiet = args.mode != "console"                                  # a bot's stdout carries the protocol only
-    agent = make_agent(args.agent, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed, vcf=args.vcf)
+    agent = make_agent(args.agent, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed, vcf=args.vcf, vcf_defend=args.vcf_defend)
     if args.mode == "botzone":
         return botzone_interface(agent)
     if args.mode == "keepalive":
         return keep_alive_botzone_interface(agent)
-    return console_interface(agent, make_agent(args.agent2, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed, vcf=args.vcf))
+    return console_interface(agent, make_agent(args.agent2, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed, vcf=args.vcf, vcf_defend=args.vcf_defend))
 
 
 if __name__ == "__main__":

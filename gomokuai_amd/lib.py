@@ -46,7 +46,7 @@ EXPORTS = [
     "gmk_az_create", "gmk_az_destroy", "gmk_az_set_roots", "gmk_az_select", "gmk_az_expand", "gmk_az_select_host", "gmk_az_expand_host", "gmk_az_read_node_host", "gmk_az_read_children_host", "gmk_az_set_leaf_host", "gmk_az_rollout_host", "gmk_az_expand_stages_host", "gmk_az_write_stats_host", "gmk_az_step", "gmk_az_root_choice", "gmk_az_step_device", "gmk_az_advance", "gmk_az_set_slots", "gmk_az_live_games", "gmk_az_set_game_ids", "gmk_az_add_root_noise", "gmk_az_set_option", "gmk_az_add_playouts", "gmk_az_playouts_owed", "gmk_az_root_stats",
     "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_root_choice", "gmk_trad_step_device", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_run_rave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
     "gmk_pattern_policy", "gmk_pattern_policy_host", "gmk_pattern_play",
-    "gmk_vcf_solve", "gmk_vcf_solve_host",
+    "gmk_vcf_solve", "gmk_vcf_solve_host", "gmk_vcf_defend", "gmk_vcf_defend_host",
     "gmk_match_referee",
     "gmk_mcts_ensemble_merge", "gmk_trad_ensemble_merge", "gmk_ensemble_merge_host",
     "gmk_replay_create", "gmk_replay_destroy", "gmk_replay_reset", "gmk_replay_append", "gmk_replay_append_packed", "gmk_replay_size",
@@ -173,6 +173,8 @@ def load():
     L.gmk_pattern_play.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.gmk_vcf_solve.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp]
     L.gmk_vcf_solve_host.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp, vp]
+    L.gmk_vcf_defend.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.gmk_vcf_defend_host.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.gmk_replay_create.argtypes = [C.c_int64, C.c_int64, C.c_uint64, C.POINTER(vp)]
     L.gmk_replay_destroy.argtypes = [vp]
     L.gmk_replay_reset.argtypes = [vp, vp]
@@ -744,6 +746,41 @@ def vcf_solve_device(d_moves, stride, d_lens, n, max_depth=16, budget=100000, op
     """Device-pointer form (ints, e.g. torch.Tensor.data_ptr()) of gmk_vcf_solve; asynchronous on `stream`, allocates nothing."""
     _check(load().gmk_vcf_solve(d_moves, int(stride), d_lens, int(n), int(max_depth), int(budget), _vcf_flags(opponent, iterative),
                                 d_status, d_move, d_length, d_nodes, d_pv, stream))
+
+
+# ---------------- K15: the moves that refute a forced win by continuous fours (gmk_vcf_defend) ----------------
+VCF_CELL_NONE, VCF_CELL_HOLDS, VCF_CELL_LOSES, VCF_CELL_UNKNOWN, VCF_CELL_FIVE = 0, 1, 2, 3, 4      # the verdict of a cell (include/gomoku_hip.h)
+VCF_CELL_NAMES = ("NONE", "HOLDS", "LOSES", "UNKNOWN", "FIVE")
+
+
+def vcf_defend(moves, lens, max_depth=16, budget=100000, iterative=False):
+    """moves u8[n, stride] (host), lens i32[n]: one move list per position, black first -> the threat against the side to move, which is
+    vcf_solve(opponent=True) ("threat_status" i32[n], "threat_length" i32[n], "threat_pv" u8[n, 64], "threat_nodes" u32[n]), and for each of
+    the 225 cells what a stone of the side to move there does about it: "verdict" u8[n, 225] (VCF_CELL_*), "length" u8[n, 225] (the
+    attacker's moves where the cell LOSES) and "nodes" u32[n, 225] (the candidates tried where the cell was searched).  Exact; the contract is
+    in include/gomoku_hip.h ("K15").  Runs on the GPU through gmk_vcf_defend_host; raises without one."""
+    init()
+    moves = np.ascontiguousarray(moves, dtype=np.uint8)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    assert moves.ndim == 2 and lens.shape == (moves.shape[0],)
+    n, stride = moves.shape
+    out = {"threat_status": np.zeros(n, np.int32), "threat_length": np.zeros(n, np.int32), "threat_pv": np.full((n, VCF_PV), 255, np.uint8),
+           "threat_nodes": np.zeros(n, np.uint32), "verdict": np.zeros((n, 225), np.uint8), "length": np.zeros((n, 225), np.uint8),
+           "nodes": np.zeros((n, 225), np.uint32)}
+    if n:
+        _check(load().gmk_vcf_defend_host(moves.ctypes.data, stride, lens.ctypes.data, n, int(max_depth), int(budget), _vcf_flags(False, iterative),
+                                          out["threat_status"].ctypes.data, out["threat_length"].ctypes.data, out["threat_pv"].ctypes.data,
+                                          out["threat_nodes"].ctypes.data, out["verdict"].ctypes.data, out["length"].ctypes.data,
+                                          out["nodes"].ctypes.data))
+    return out
+
+
+def vcf_defend_device(d_moves, stride, d_lens, n, max_depth=16, budget=100000, iterative=False, d_threat_status=None, d_threat_length=None,
+                      d_threat_pv=None, d_threat_nodes=None, d_verdict=None, d_cell_length=None, d_cell_nodes=None, stream=None):
+    """Device-pointer form (ints, e.g. torch.Tensor.data_ptr()) of gmk_vcf_defend; asynchronous on `stream`, allocates nothing.  The threat's
+    status, length and pv and the verdicts are required."""
+    _check(load().gmk_vcf_defend(d_moves, int(stride), d_lens, int(n), int(max_depth), int(budget), _vcf_flags(False, iterative),
+                                 d_threat_status, d_threat_length, d_threat_pv, d_threat_nodes, d_verdict, d_cell_length, d_cell_nodes, stream))
 
 
 # ---------------- K12: the referee of a match between two search handles (gmk_match_referee) and what its callers share ----------------

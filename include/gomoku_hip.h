@@ -714,6 +714,54 @@ int gmk_vcf_solve(const uint8_t* d_moves, int stride, const int32_t* d_lens, int
 int gmk_vcf_solve_host(const uint8_t* h_moves, int stride, const int32_t* h_lens, int n, int max_depth, uint32_t budget, int flags,
                        int32_t* h_status, int32_t* h_move, int32_t* h_length, uint32_t* h_nodes, uint8_t* h_pv);
 
+/* ---- K15: the moves that refute a forced win by continuous fours, exact, per position and in batch ----
+ * No counterpart in the reference; the contract is this block, on top of K14's.  A position is the move list, as for K14.  D is the side to
+ * move, A the other colour: the threat's attacker.  attack, completing, L and budget are K14's; solve(list, flags) is gmk_vcf_solve's result
+ * for that list with the same max_depth and budget.  flags: 0 or GMK_VCF_ITERATIVE.
+ *
+ *   1. threat = solve(P, GMK_VCF_OPPONENT | (flags & GMK_VCF_ITERATIVE)): d_threat_status int32[n], d_threat_length int32[n],
+ *      d_threat_pv uint8[n][GMK_VCF_PV], d_threat_nodes uint32[n], equal bit for bit to what gmk_vcf_solve writes.
+ *   2. threat OVER or BAD: every cell's verdict is GMK_VCF_CELL_NONE; nothing is searched.
+ *   3. Otherwise each cell c has a verdict (d_verdict uint8[n][225]), a length (d_cell_length uint8[n][225]) and nodes (d_cell_nodes
+ *      uint32[n][225]); length and nodes are 0 unless said otherwise:
+ *        c occupied                                   GMK_VCF_CELL_NONE
+ *        c in completing(D) on P                      GMK_VCF_CELL_FIVE     D wins at once
+ *        else, threat NONE                            GMK_VCF_CELL_HOLDS    not searched: a defender stone never gives the attacker a line of
+ *                                                                           fours he did not have
+ *        else, threat DEPTH or BUDGET                 GMK_VCF_CELL_UNKNOWN  not searched: the caller raises the limits
+ *        else (threat WIN with pv): follow(0) on P with a D stone on c -- the walk of attack with exactly one candidate per level, pv's
+ *        attacker move of that level:
+ *
+ *          follow(i):                       the board is P, the D stone on c, then i attacker moves of pv and their i forced replies
+ *            if completing(A): return LOSES, length i + 1
+ *            T = completing(D);  if |T| >= 2: return FAIL
+ *            if 2 i >= |pv|: return FAIL
+ *            a = pv[2 i];  if a is occupied, or T is not empty and a is not in T: return FAIL
+ *            F = completing(A) with a played;  if F is empty: return FAIL
+ *            if |F| >= 2: return LOSES, length i + 2
+ *            play a and F's only cell;  return follow(i + 1)
+ *
+ *          LOSES                                      GMK_VCF_CELL_LOSES with that length, nodes 0
+ *          FAIL: s = solve(P + [c], flags & GMK_VCF_ITERATIVE), each such cell with the whole budget; nodes = s.nodes
+ *            s WIN                                    GMK_VCF_CELL_LOSES, length = s.length
+ *            s NONE                                   GMK_VCF_CELL_HOLDS
+ *            s DEPTH or BUDGET                        GMK_VCF_CELL_UNKNOWN
+ *   4. Every output is an exact function of the list, max_depth, budget and flags.
+ *
+ * gmk_vcf_defend: asynchronous on `stream` (two launches), allocates nothing; n = 0 does nothing.  d_threat_nodes, d_cell_length and
+ *   d_cell_nodes may be NULL; the other four outputs are required, and the second launch reads the three required threat outputs.
+ *   GMK_ERR_ARG as for gmk_vcf_solve, and for a NULL required output with n > 0, GMK_VCF_OPPONENT or an unknown bit in flags, a 4-byte output
+ *   that is not 4-byte aligned.  GMK_ERR_STATE without a device.  Nothing outside a list's len cells is read; the stone on c is added in
+ *   registers, never written to the list.
+ * gmk_vcf_defend_host: the same with host buffers (allocates, copies in, runs on the GPU, copies out, synchronises). */
+enum { GMK_VCF_CELL_NONE = 0, GMK_VCF_CELL_HOLDS = 1, GMK_VCF_CELL_LOSES = 2, GMK_VCF_CELL_UNKNOWN = 3, GMK_VCF_CELL_FIVE = 4 };
+int gmk_vcf_defend(const uint8_t* d_moves, int stride, const int32_t* d_lens, int n, int max_depth, uint32_t budget, int flags,
+                   int32_t* d_threat_status, int32_t* d_threat_length, uint8_t* d_threat_pv, uint32_t* d_threat_nodes,
+                   uint8_t* d_verdict, uint8_t* d_cell_length, uint32_t* d_cell_nodes, void* stream);
+int gmk_vcf_defend_host(const uint8_t* h_moves, int stride, const int32_t* h_lens, int n, int max_depth, uint32_t budget, int flags,
+                        int32_t* h_threat_status, int32_t* h_threat_length, uint8_t* h_threat_pv, uint32_t* h_threat_nodes,
+                        uint8_t* h_verdict, uint8_t* h_cell_length, uint32_t* h_cell_nodes);
+
 /* ---- K11: training the policy-value network on the device (network/train.py:62-86, network/model_tf.py:73-135) ----
  * A gmk_trainer holds the network's sixteen parameter tensors in float32 in their canonical layouts (those gmk_pvnet_create and
  * gmk_pvnet_set_dense take), Adam's two moments, a gradient block and the activations of up to max_batch positions.  One step = forward
