@@ -13,6 +13,8 @@
 // all on one HIP stream (the three steps can be captured in a hipGraph and replayed per playout).
 // With GMK_OPT_AZ_LEAVES = L > 1 a step takes up to L leaves from every game, steered apart by virtual loss, and the batch has live x L rows:
 // az_select_leaves_kernel / az_expand_leaves_kernel below, for searches of few games.
+// With GMK_OPT_AZ_VCF_DEPTH = D > 0 the pending leaves are also handed to K14's exact solver of forced wins by fours (az_vcf_leaves_kernel, right
+// behind the select kernel), and the expand kernels answer a solved leaf themselves: include/gomoku_hip.h, "K7 + K14".
 // Mapping: one wavefront per game, lanes over the (<= 225) children; the tree is an SoA arena per game in HBM.
 #include <algorithm>
 #include <cmath>
@@ -26,6 +28,7 @@
 #include "rollout_device.h"
 #include "root_noise.h"
 #include "noise_device.h"
+#include "vcf_device.h"
 
 namespace {
 
@@ -44,9 +47,12 @@ struct AzHeader {                                // 256 B per game, in HBM
     uint32_t leaf_stones;
     uint32_t quota;                              // several leaves per step: the playouts the game still owes (gmk_az_add_playouts)
     uint32_t n_pending;                          //   leaves waiting for the network's answer (AzLeaves::pend), 0 between steps
-    uint32_t pad[22];
+    uint32_t vcf_leaves, vcf_wins, vcf_cut;      // K7 + K14 (GMK_OPT_AZ_VCF_DEPTH > 0): pending leaves solved, answered WIN, cut by BUDGET or DEPTH
+    uint32_t pad0;
+    unsigned long long vcf_nodes;                //   and the nodes their walks counted
+    uint32_t pad[16];
 };
-static_assert(sizeof(AzHeader) == 256, "AzHeader layout");
+static_assert(sizeof(AzHeader) == 256 && offsetof(AzHeader, vcf_nodes) % 8 == 0, "AzHeader layout");
 
 struct AzTree {
     AzHeader* hdr;
@@ -68,6 +74,21 @@ __device__ __forceinline__ void backup(uint2* stat, const uint32_t* parent, uint
         const float q = __uint_as_float(s.y);
         stat[node] = make_uint2(visits, __float_as_uint(q + (value - q) / static_cast<float>(visits)));
     }
+}
+
+// K7 + K14: one verdict per row of the leaf batch, written by az_vcf_leaves_kernel and read by the <true> instantiations of the expand kernels
+struct AzVcf {
+    int4* verdict;                               // [n_games * GMK_AZ_MAX_LEAVES] {status, move, length, nodes}, owned by the handle
+    int max_depth;                               // D
+    uint32_t budget;                             // B
+};
+
+// lane 0 of the game's expand wavefront: the leaf's verdict goes into the game's counters
+__device__ __forceinline__ void count_verdict(AzHeader* hdr, const int4& v) {
+    hdr->vcf_leaves += 1u;
+    hdr->vcf_wins += v.x == GMK_VCF_WIN ? 1u : 0u;
+    hdr->vcf_cut += (v.x == GMK_VCF_BUDGET || v.x == GMK_VCF_DEPTH) ? 1u : 0u;
+    hdr->vcf_nodes += static_cast<uint32_t>(v.w);
 }
 
 __global__ __launch_bounds__(64)
@@ -155,8 +176,10 @@ void az_select_kernel(AzTree t, float* __restrict__ out_states) {
     }
 }
 
+// kVcf: the leaf's verdict comes first (GMK_OPT_AZ_VCF_DEPTH > 0) -- on WIN the answer is (1.0f, one-hot(move)) instead of the network's row
+template <bool kVcf>
 __global__ __launch_bounds__(64)
-void az_expand_kernel(AzTree t, const float* __restrict__ values, const float* __restrict__ probs, int stages /* bit 0: expand, bit 1: back up */) {
+void az_expand_kernel(AzTree t, const float* __restrict__ values, const float* __restrict__ probs, int stages /* bit 0: expand, bit 1: back up */, AzVcf vc) {
     const int game = blockIdx.x, lane = threadIdx.x;
     if (game >= t.n_games) return;
     AzHeader* hdr = t.hdr + game;
@@ -165,6 +188,14 @@ void az_expand_kernel(AzTree t, const float* __restrict__ values, const float* _
     const size_t arena = static_cast<size_t>(game) * t.cap;
     const uint32_t leaf = hdr->leaf;
     uint32_t n_nodes = hdr->n_nodes;
+    bool win = false;
+    int win_cell = -1;
+    if constexpr (kVcf) {
+        const int4 v = vc.verdict[row];
+        win = v.x == GMK_VCF_WIN;
+        win_cell = v.y;
+        if (lane == 0) count_verdict(hdr, v);
+    }
     // ---- Default::Expand with extraCheck (MonteCarlo.hpp:71-80): probability not 0 and the cell is free; ascending cell id ----
     const float* p = probs + row * kCells;
     float pv[4];
@@ -174,6 +205,7 @@ void az_expand_kernel(AzTree t, const float* __restrict__ values, const float* _
     for (int j = 0; j < 4; ++j) {
         const int i = lane + 64 * j;
         pv[j] = i < kCells ? p[i] : 0.0f;
+        if constexpr (kVcf) { if (win) pv[j] = i == win_cell ? 1.0f : 0.0f; }
         const uint32_t row = i < kCells ? hdr->leaf_rows[i / 15] >> (i % 15) : 0x10001u;
         take[j] = i < kCells && pv[j] != 0.0f && !(row & 0x10001u);
         const unsigned long long b = __ballot(take[j]);
@@ -202,7 +234,7 @@ void az_expand_kernel(AzTree t, const float* __restrict__ values, const float* _
     }
     __threadfence_block();
     if (lane == 0) {
-        if (stages & 2) backup(t.stat + arena, t.parent + arena, leaf, -values[row]);  // node_value = -state_value (MCTS.cpp:166-168)
+        if (stages & 2) backup(t.stat + arena, t.parent + arena, leaf, win ? -1.0f : -values[row]);      // node_value = -state_value (MCTS.cpp:166-168)
         hdr->leaf_pending = 0;
     }
 }
@@ -340,8 +372,9 @@ void az_select_leaves_kernel(AzTree t, AzLeaves lv, float* out_states) {
     if (lane == 0) { hdr->quota = quota; hdr->n_pending = static_cast<uint32_t>(k); hdr->leaf_pending = 0; }
 }
 
+template <bool kVcf>
 __global__ __launch_bounds__(64)
-void az_expand_leaves_kernel(AzTree t, AzLeaves lv, const float* values, const float* probs) {
+void az_expand_leaves_kernel(AzTree t, AzLeaves lv, const float* values, const float* probs, AzVcf vc) {
     const int game = blockIdx.x, lane = threadIdx.x;
     if (game >= t.n_games) return;
     AzHeader* hdr = t.hdr + game;
@@ -355,6 +388,14 @@ void az_expand_leaves_kernel(AzTree t, AzLeaves lv, const float* values, const f
     bool full = false;
     for (int k = 0; k < n_pending; ++k) {
         const uint32_t leaf = pend[k].node;
+        bool win = false;
+        int win_cell = -1;
+        if constexpr (kVcf) {
+            const int4 v = vc.verdict[row0 + static_cast<size_t>(k)];
+            win = v.x == GMK_VCF_WIN;
+            win_cell = v.y;
+            if (lane == 0) count_verdict(hdr, v);
+        }
         // ---- Default::Expand with extraCheck, as az_expand_kernel: probability not 0 and the cell is free; ascending cell id ----
         const float* p = probs + (row0 + static_cast<size_t>(k)) * kCells;
         float pv[4];
@@ -364,6 +405,7 @@ void az_expand_leaves_kernel(AzTree t, AzLeaves lv, const float* values, const f
         for (int j = 0; j < 4; ++j) {
             const int i = lane + 64 * j;
             pv[j] = i < kCells ? p[i] : 0.0f;
+            if constexpr (kVcf) { if (win) pv[j] = i == win_cell ? 1.0f : 0.0f; }
             const uint32_t row = i < kCells ? pend[k].rows[i / 15] >> (i % 15) : 0x10001u;
             take[j] = i < kCells && pv[j] != 0.0f && !(row & 0x10001u);
             const unsigned long long b = __ballot(take[j]);
@@ -393,7 +435,7 @@ void az_expand_leaves_kernel(AzTree t, AzLeaves lv, const float* values, const f
         }
         __threadfence_block();
         if (lane == 0) {
-            if (!dropped) backup(t.stat + arena, t.parent + arena, leaf, -values[row0 + k]);
+            if (!dropped) backup(t.stat + arena, t.parent + arena, leaf, win ? -1.0f : -values[row0 + k]);
             for (uint32_t up = leaf; up != kNoNode; up = t.parent[arena + up]) inflight[up] = static_cast<uint16_t>(inflight[up] - 1u);
         }
     }
@@ -401,6 +443,143 @@ void az_expand_leaves_kernel(AzTree t, AzLeaves lv, const float* values, const f
         hdr->n_nodes = n_nodes;
         if (full) hdr->status |= 2u;
         hdr->n_pending = 0;
+    }
+}
+
+// ---- K7 + K14: forced wins by fours at the pending leaves (GMK_OPT_AZ_VCF_DEPTH = D > 0) ----
+// K14's walk (vcf_kernel.hip, the contract in include/gomoku_hip.h "K14") in plain mode with the side to move attacking, restated around another
+// loader and another finish; the row gather and the geometry of fours are vcf_device.h's.  One board ROW per lane, sixteen lanes per leaf, four
+// leaves per wavefront, one wavefront per workgroup.  Group i of the launch takes game i / L's leaf i % L: a finished game or a k >= n_pending
+// (L = 1: a leaf that is not pending) leaves the group idle, so the live games' leaves are found by skipping, which is row_of read forwards, and
+// the verdict goes to row row_of[game] * L + k of the leaf batch.  Lane y reads ONE word of the leaf's sixteen (black | white << 16; word 15 is
+// zero) and splits it into attacker and defender by the leaf's stone count: no move list exists and none is built.  A pending leaf is a position
+// the select kernel built from legal moves, so K14's BAD cannot arise; OVER can, from a root given with a five on it.  No principal variation is
+// kept beyond the first move.  No float, no atomics, no barrier, nothing allocated.
+__global__ __launch_bounds__(64)
+void az_vcf_leaves_kernel(AzTree t, AzLeaves lv, AzVcf vc) {
+    namespace V = gmk::vcf;
+    __shared__ uint32_t stack[V::kLevels][64];                   // per level and lane: candidates left 0..14, "the level has more" 15, c 16..23, r 24..31
+    const int lane = threadIdx.x, y = lane & 15, group = lane >> 4, gbase = lane & 48;
+    const uint32_t board_row = y < 15 ? V::kRowMask : 0u;
+    const int limit = vc.max_depth;
+
+    int state = V::kIdle, depth = 0;
+    size_t out_row = 0;
+    bool cut = false, more = false;
+    uint32_t nodes = 0, att = 0, def = 0, mask = 0;
+
+    // ---- the loader ----
+    const long long item = static_cast<long long>(blockIdx.x) * 4 + group;
+    if (item < static_cast<long long>(t.n_games) * lv.leaves) {
+        const int game = static_cast<int>(item / lv.leaves), k = static_cast<int>(item - static_cast<long long>(game) * lv.leaves);
+        const AzHeader* hdr = t.hdr + game;
+        if (!(hdr->status & kStatusOver)) {
+            out_row = static_cast<size_t>(t.row_of[game]) * lv.leaves + static_cast<size_t>(k);
+            const bool many = lv.leaves > 1;
+            const bool pending = many ? static_cast<uint32_t>(k) < hdr->n_pending : hdr->leaf_pending != 0u;
+            if (pending) {
+                const AzPending* pd = lv.pend + static_cast<size_t>(game) * GMK_AZ_MAX_LEAVES + (many ? k : 0);
+                const uint32_t word = many ? pd->rows[y] : hdr->leaf_rows[y];
+                const uint32_t stones = many ? pd->stones : hdr->leaf_stones;
+                const uint32_t black = word & V::kRowMask, white = (word >> 16) & V::kRowMask;
+                att = (stones & 1u) ? white : black;             // white is to move on odd stone counts
+                def = (stones & 1u) ? black : white;
+                state = V::kInit;
+            } else if (y == 0) {
+                vc.verdict[out_row] = make_int4(GMK_VCF_NONE, -1, 0, 0);
+            }
+        }
+    }
+
+    // The group's verdict.  first = the cell that ends a winning line at the root (depth 0), else the first move is on the stack.
+    const auto finish = [&](int status, int first, int tail) {
+        const bool win = status == GMK_VCF_WIN;
+        if (y == 0)
+            vc.verdict[out_row] = make_int4(status, !win ? -1 : depth > 0 ? static_cast<int>((stack[0][lane] >> 16) & 255u) : first, !win ? 0 : depth + tail,
+                                            static_cast<int>(nodes));
+        state = V::kIdle;
+    };
+    // The walk has failed at the root, with every move undone.
+    const auto failed = [&]() { finish(cut ? GMK_VCF_DEPTH : GMK_VCF_NONE, -1, 0); };
+
+    while (__ballot(state != V::kIdle) != 0ull) {
+        // ---- the pass: every group in the same instructions ----
+        const bool trying = state == V::kRun;                      // such a group has a candidate: `mask` is not empty
+        uint32_t popped = trying ? mask : 0u;
+        const int c = V::take_lowest(popped, y, gbase);
+        const uint32_t left = V::group_rows(popped != 0, gbase);
+        const int cy = trying ? c / 15 : 0;
+        const uint32_t cbit = trying ? 1u << (c - 15 * cy) : 0u;
+        if (trying) {
+            mask = popped;
+            more = left != 0;
+            if (y == cy) att |= cbit;
+        }
+        uint32_t A[9], D[9], N[9];
+        V::gather_rows(att, A);
+        uint32_t F = V::completing(A, board_row & ~(att | def));
+        const int f1 = V::take_lowest(F, y, gbase), f2 = V::take_lowest(F, y, gbase);
+        const bool replied = trying && f1 >= 0 && f2 < 0;          // the forced reply goes on the board
+        const int ry = replied ? f1 / 15 : 0;
+        const uint32_t rbit = replied ? 1u << (f1 - 15 * ry) : 0u;
+        if (replied && y == ry) def |= rbit;
+        const uint32_t empty = board_row & ~(att | def);
+        V::gather_rows(def, D);
+        V::gather_rows(empty | att, N);
+        uint32_t T = V::completing(D, empty);
+        uint32_t C = V::four_making(A, N, empty);
+        if (V::group_rows(T != 0, gbase)) C &= T;                  // a defender four: only its blocking cell is a candidate
+        const int t1 = V::take_lowest(T, y, gbase), t2 = V::take_lowest(T, y, gbase);
+        (void)t1;
+        const bool child_has = V::group_rows(C != 0, gbase) != 0;
+        bool over = false;
+        if (__ballot(state == V::kInit) != 0ull) over = V::group_rows((V::five(A) | V::five(D)) != 0, gbase) != 0;
+
+        // ---- decisions, the same in all sixteen lanes of a group ----
+        if (state == V::kInit) {
+            if (over) finish(GMK_VCF_OVER, -1, 0);
+            else if (f1 >= 0) finish(GMK_VCF_WIN, f1, 1);
+            else {
+                bool fail = t2 >= 0;
+                if (!fail && 2 > limit) { cut = true; fail = true; }
+                if (!fail && !child_has) fail = true;
+                if (fail) failed();
+                else { mask = C; more = true; state = V::kRun; }
+            }
+        } else if (trying) {
+            bool retract = true;
+            if (f1 < 0) {
+                // not a four: no candidate and no node (as vcf_kernel: the plane-wide mask does not offer such a cell)
+            } else if (nodes == vc.budget) {
+                finish(GMK_VCF_BUDGET, -1, 0);
+            } else {
+                ++nodes;
+                if (f2 >= 0) finish(GMK_VCF_WIN, c, 2);
+                else {
+                    bool fail = t2 >= 0;
+                    if (!fail && depth + 3 > limit) { cut = true; fail = true; }
+                    if (!fail && !child_has) fail = true;
+                    if (!fail) {
+                        stack[depth][lane] = mask | (more ? 0x8000u : 0u) | (static_cast<uint32_t>(c) << 16) | (static_cast<uint32_t>(f1) << 24);
+                        ++depth;
+                        mask = C; more = true; retract = false;
+                    } else if (y == ry) def ^= rbit;
+                }
+            }
+            if (state == V::kRun && retract) {
+                if (y == cy) att ^= cbit;
+                while (!more) {                                    // climb while the level has nothing left
+                    if (depth == 0) { failed(); break; }
+                    --depth;
+                    const uint32_t w = stack[depth][lane];
+                    mask = w & V::kRowMask;
+                    more = (w & 0x8000u) != 0;
+                    const int uc = static_cast<int>((w >> 16) & 255u), ur = static_cast<int>(w >> 24);
+                    if (y == uc / 15) att ^= 1u << (uc % 15);
+                    if (y == ur / 15) def ^= 1u << (ur % 15);
+                }
+            }
+        }
     }
 }
 
@@ -823,6 +1002,8 @@ struct gmk_az {
     AzLeaves lv{nullptr, nullptr, 1};                            // GMK_OPT_AZ_LEAVES; the side buffers come with the first L > 1
     int32_t* d_owed = nullptr;                                   // gmk_az_playouts_owed's word
     bool select_issued = false;                                  // L > 1: gmk_az_select has marked its leaves, gmk_az_expand has not answered yet
+    bool leaf_waiting = false;                                   // any L: a gmk_az_select has not been answered yet (asked by the GMK_OPT_AZ_VCF_* options only)
+    AzVcf vcf{nullptr, 0, 64u};                                  // GMK_OPT_AZ_VCF_DEPTH / _BUDGET; the verdict buffer comes with the first D > 0
     // device scratch of the host-driven form (gmk_az_select_host / gmk_az_expand_host)
     float *h_states = nullptr, *h_values = nullptr, *h_probs = nullptr;
     int16_t* h_paths = nullptr;
@@ -837,6 +1018,7 @@ extern "C" int gmk_az_destroy(gmk_az* a) {
     (void)gmk::device_free(a->slots.slot_game); (void)gmk::device_free(a->d_open_moves); (void)gmk::device_free(a->d_open_lens);
     (void)gmk::device_free(a->h_states); (void)gmk::device_free(a->h_values); (void)gmk::device_free(a->h_probs); (void)gmk::device_free(a->h_paths); (void)gmk::device_free(a->h_lens);
     (void)gmk::device_free(a->lv.inflight); (void)gmk::device_free(a->lv.pend); (void)gmk::device_free(a->d_owed);
+    (void)gmk::device_free(a->vcf.verdict);
     delete a;
     return GMK_OK;
 }
@@ -875,14 +1057,16 @@ static bool az_marks_up(const gmk_az* a, const char* who) {
     if (a->lv.leaves > 1 && a->select_issued) { gmk::set_error("%s: gmk_az_select is waiting for its gmk_az_expand (GMK_OPT_AZ_LEAVES = %d)", who, a->lv.leaves); return true; }
     return false;
 }
-// the host-driven entries serve one leaf per game
+// the host-driven entries serve one leaf per game, evaluated by the host alone
 static bool az_many_leaves(const gmk_az* a, const char* who) {
+    if (a->vcf.max_depth > 0) { gmk::set_error("%s: the host-driven form does not solve its leaves (GMK_OPT_AZ_VCF_DEPTH = %d)", who, a->vcf.max_depth); return true; }
     if (a->lv.leaves > 1) { gmk::set_error("%s: the host-driven form takes one leaf per step (GMK_OPT_AZ_LEAVES = %d)", who, a->lv.leaves); return true; }
     return false;
 }
 // new roots: no leaf is pending and nothing is in flight (the headers are rewritten by the caller: quota 0, n_pending 0)
 static int az_reset_leaves(gmk_az* a) {
     a->select_issued = false;
+    a->leaf_waiting = false;
     if (a->lv.inflight) GMK_HIP_CHECK(hipMemset(a->lv.inflight, 0, static_cast<size_t>(a->t.n_games) * static_cast<size_t>(a->t.cap) * 2));
     return GMK_OK;
 }
@@ -993,6 +1177,16 @@ extern "C" int gmk_az_set_slots(gmk_az* a, int n_total, const uint8_t* h_open_mo
     return az_compact(a, nullptr);
 }
 
+// D > 0: the pending leaves go through the solver, on the same stream, right behind the select kernel
+static int az_vcf_leaves(gmk_az* a, void* stream) {
+    a->leaf_waiting = true;
+    if (a->vcf.max_depth == 0) return GMK_OK;
+    const long long groups = static_cast<long long>(a->t.n_games) * a->lv.leaves;
+    hipLaunchKernelGGL(az_vcf_leaves_kernel, dim3(static_cast<unsigned>((groups + 3) / 4)), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, a->vcf);
+    GMK_HIP_CHECK(hipGetLastError());
+    return GMK_OK;
+}
+
 extern "C" int gmk_az_select(gmk_az* a, float* d_states, void* stream) {
     if (!a || !d_states) { gmk::set_error("gmk_az_select: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_select: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
@@ -1001,24 +1195,28 @@ extern "C" int gmk_az_select(gmk_az* a, float* d_states, void* stream) {
         hipLaunchKernelGGL(az_select_leaves_kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_states);
         GMK_HIP_CHECK(hipGetLastError());
         a->select_issued = true;
-        return GMK_OK;
+        return az_vcf_leaves(a, stream);
     }
     hipLaunchKernelGGL(az_select_kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_states);
     GMK_HIP_CHECK(hipGetLastError());
-    return GMK_OK;
+    return az_vcf_leaves(a, stream);
 }
 
 extern "C" int gmk_az_expand(gmk_az* a, const float* d_values, const float* d_probs, void* stream) {
     if (!a || !d_values || !d_probs) { gmk::set_error("gmk_az_expand: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_expand: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
     if (a->lv.leaves > 1) {                                      // d_values and d_probs have gmk_az_live_games x L rows
-        hipLaunchKernelGGL(az_expand_leaves_kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs);
+        if (a->vcf.max_depth > 0) hipLaunchKernelGGL(az_expand_leaves_kernel<true>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf);
+        else hipLaunchKernelGGL(az_expand_leaves_kernel<false>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf);
         GMK_HIP_CHECK(hipGetLastError());
         a->select_issued = false;
+        a->leaf_waiting = false;
         return GMK_OK;
     }
-    hipLaunchKernelGGL(az_expand_kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3);
+    if (a->vcf.max_depth > 0) hipLaunchKernelGGL(az_expand_kernel<true>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf);
+    else hipLaunchKernelGGL(az_expand_kernel<false>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf);
     GMK_HIP_CHECK(hipGetLastError());
+    a->leaf_waiting = false;
     return GMK_OK;
 }
 
@@ -1149,6 +1347,29 @@ extern "C" int gmk_az_set_option(gmk_az* a, int option, int value) {
             GMK_HIP_CHECK(hipMemset(a->lv.pend, 0, n * GMK_AZ_MAX_LEAVES * sizeof(AzPending)));
         }
         a->lv.leaves = value;
+        return GMK_OK;
+    }
+    if (a && (option == GMK_OPT_AZ_VCF_DEPTH || option == GMK_OPT_AZ_VCF_BUDGET)) {
+        const bool depth = option == GMK_OPT_AZ_VCF_DEPTH;
+        if (depth ? (value < 0 || value > GMK_VCF_MAX_DEPTH) : (value < 1 || value > (1 << 20))) {
+            gmk::set_error("gmk_az_set_option: GMK_OPT_AZ_VCF_DEPTH takes 0 .. %d and GMK_OPT_AZ_VCF_BUDGET 1 .. 2^20, not %d", GMK_VCF_MAX_DEPTH, value);
+            return GMK_ERR_ARG;
+        }
+        if (a->leaf_waiting) { gmk::set_error("gmk_az_set_option: gmk_az_select is waiting for its gmk_az_expand; the leaves' verdicts belong to the old setting"); return GMK_ERR_STATE; }
+        if (!depth) { a->vcf.budget = static_cast<uint32_t>(value); return GMK_OK; }
+        if (value > 0 && !a->vcf.verdict) {                      // one verdict per row of the largest leaf batch; every row reads "no leaf" until a select writes it
+            const size_t rows = static_cast<size_t>(a->t.n_games) * GMK_AZ_MAX_LEAVES;
+            const std::vector<int4> none(rows, make_int4(GMK_VCF_NONE, -1, 0, 0));
+            GMK_HIP_CHECK(hipDeviceSynchronize());
+            if (gmk::device_malloc(&a->vcf.verdict, rows * sizeof(int4)) != hipSuccess) {
+                a->vcf.verdict = nullptr;
+                (void)hipGetLastError();
+                gmk::set_error("gmk_az_set_option: hipMalloc of the verdict buffer (%zu rows) failed", rows);
+                return GMK_ERR_HIP;
+            }
+            GMK_HIP_CHECK(hipMemcpy(a->vcf.verdict, none.data(), rows * sizeof(int4), hipMemcpyHostToDevice));
+        }
+        a->vcf.max_depth = value;
         return GMK_OK;
     }
     if (a && option == GMK_OPT_NOISE_SAMPLER && (value == GMK_NOISE_SAMPLER_STD || value == GMK_NOISE_SAMPLER_COUNTER)) { a->noise_sampler = value; return GMK_OK; }
@@ -1356,8 +1577,9 @@ extern "C" int gmk_az_expand_stages_host(gmk_az* a, const float* h_values, const
     if (h_values) GMK_HIP_CHECK(hipMemcpy(a->h_values, h_values, static_cast<size_t>(a->t.n_games) * 4, hipMemcpyHostToDevice));
     if (h_probs) GMK_HIP_CHECK(hipMemcpy(a->h_probs, h_probs, static_cast<size_t>(a->t.n_games) * 225 * 4, hipMemcpyHostToDevice));
     else GMK_HIP_CHECK(hipMemset(a->h_probs, 0, static_cast<size_t>(a->t.n_games) * 225 * 4));
-    hipLaunchKernelGGL(az_expand_kernel, dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, a->h_values, a->h_probs, (do_expand ? 1 : 0) | (do_backup ? 2 : 0));
+    hipLaunchKernelGGL(az_expand_kernel<false>, dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, a->h_values, a->h_probs, (do_expand ? 1 : 0) | (do_backup ? 2 : 0), a->vcf);
     GMK_HIP_CHECK(hipGetLastError());
+    a->leaf_waiting = false;
     GMK_HIP_CHECK(hipDeviceSynchronize());
     return GMK_OK;
 }
@@ -1420,5 +1642,40 @@ extern "C" int gmk_az_root_stats(gmk_az* a, uint32_t* h_visits, float* h_values,
         if (h_status) h_status[g] = static_cast<int32_t>(hdr[g].status);
     }
     cleanup();
+    return GMK_OK;
+}
+
+// ---- K7 + K14: the read-out ----
+extern "C" int gmk_az_vcf_stats(gmk_az* a, uint32_t* h_leaves, uint32_t* h_wins, uint32_t* h_cut, uint64_t* h_nodes) {
+    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    if (!a) { gmk::set_error("gmk_az_vcf_stats: bad arguments"); return GMK_ERR_ARG; }
+    if (!a->rooted) { gmk::set_error("gmk_az_vcf_stats: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
+    const size_t n = static_cast<size_t>(a->t.n_games);
+    std::vector<AzHeader> hdr(n);
+    GMK_HIP_CHECK(hipDeviceSynchronize());
+    GMK_HIP_CHECK(hipMemcpy(hdr.data(), a->t.hdr, n * sizeof(AzHeader), hipMemcpyDeviceToHost));
+    for (size_t g = 0; g < n; ++g) {
+        if (h_leaves) h_leaves[g] = hdr[g].vcf_leaves;
+        if (h_wins) h_wins[g] = hdr[g].vcf_wins;
+        if (h_cut) h_cut[g] = hdr[g].vcf_cut;
+        if (h_nodes) h_nodes[g] = hdr[g].vcf_nodes;
+    }
+    return GMK_OK;
+}
+
+extern "C" int gmk_az_vcf_verdicts_host(gmk_az* a, int32_t* h_status, int32_t* h_move, int32_t* h_length, uint32_t* h_nodes) {
+    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    if (!a) { gmk::set_error("gmk_az_vcf_verdicts_host: bad arguments"); return GMK_ERR_ARG; }
+    if (a->vcf.max_depth == 0 || !a->vcf.verdict) { gmk::set_error("gmk_az_vcf_verdicts_host: the leaves are not solved (GMK_OPT_AZ_VCF_DEPTH = 0)"); return GMK_ERR_STATE; }
+    const size_t rows = static_cast<size_t>(a->n_live) * static_cast<size_t>(a->lv.leaves);
+    std::vector<int4> v(rows);
+    GMK_HIP_CHECK(hipDeviceSynchronize());
+    if (rows) GMK_HIP_CHECK(hipMemcpy(v.data(), a->vcf.verdict, rows * sizeof(int4), hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < rows; ++r) {
+        if (h_status) h_status[r] = v[r].x;
+        if (h_move) h_move[r] = v[r].y;
+        if (h_length) h_length[r] = v[r].z;
+        if (h_nodes) h_nodes[r] = static_cast<uint32_t>(v[r].w);
+    }
     return GMK_OK;
 }

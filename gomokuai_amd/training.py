@@ -36,14 +36,18 @@ class EvaluationSchedule:
     """The state evaluate_network keeps (train.py:30-32) and its rules (:93-123): the network meets candidates[schedule_level] (None = the
     supervisor) at ref_iterations playouts; a win rate above best_win_rate is a new best, and one that reaches 1 - 0.05 * level powers an
     MCTS opponent up by 2 * c_iterations or, past 20 000, moves on to the next candidate.  leaves: the leaves per game per step of the
-    network's searches in the match (selfplay.play_evaluation_games(leaves=); 1 = the reference's search, one leaf at a time)."""
+    network's searches in the match (selfplay.play_evaluation_games(leaves=); 1 = the reference's search, one leaf at a time).  vcf: (depth,
+    budget) of the forced-win solver at the leaves of those searches (selfplay.play_evaluation_games(vcf=)), None = off."""
 
-    def __init__(self, supervisor=SUPERVISOR, candidates=CANDIDATES, eval_rounds=11, c_iterations=400, leaves=1):
+    def __init__(self, supervisor=SUPERVISOR, candidates=CANDIDATES, eval_rounds=11, c_iterations=400, leaves=1, vcf=None):
         if not candidates:
             raise ValueError("EvaluationSchedule: at least one candidate (None = the supervisor)")
         if not 1 <= int(leaves) <= 8:
             raise ValueError("EvaluationSchedule: leaves must be in [1, 8]")
         self.leaves = int(leaves)
+        if vcf is not None and not (len(vcf) == 2 and 1 <= int(vcf[0]) <= 32 and 1 <= int(vcf[1]) <= 1 << 20):
+            raise ValueError("EvaluationSchedule: vcf is (depth in [1, 32], budget in [1, 2^20]) or None")
+        self.vcf = None if vcf is None else (int(vcf[0]), int(vcf[1]))
         self.supervisor, self.candidates = supervisor, list(candidates)
         self.eval_rounds, self.c_iterations = int(eval_rounds), int(c_iterations)
         self.schedule_level, self.ref_iterations, self.best_win_rate = 0, self.c_iterations, 0.0
@@ -178,6 +182,8 @@ class TrainingLoop:
         options = dict(self.eval_options)
         if getattr(sch, "leaves", 1) != 1:
             options.setdefault("leaves", sch.leaves)              # (eval_options may name its own)
+        if getattr(sch, "vcf", None) is not None:
+            options.setdefault("vcf", sch.vcf)
         rec, network_is_black, scores = selfplay.play_evaluation_games(sch.eval_rounds, network, (name, kwargs), playouts=self.eval_playouts, **options)
         win_rate = float(scores.mean())
         events = sch.update(win_rate)

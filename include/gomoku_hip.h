@@ -204,7 +204,8 @@ int gmk_mcts_add_root_noise(gmk_mcts *m, float alpha, float epsilon, void *strea
  *                                      semantics -- kept subtree + noise before every search -- then run inside ONE persistent launch.
  * GMK_OPT_LOCKSTEP: 1 = gmk_selfplay_run / gmk_trad_selfplay_run alternate search and step launches even where one persistent launch could play
  *   the games (the second form the tests hold the persistent one to); 0 (default) = persistent wherever the configuration allows. */
-enum { GMK_OPT_NOISE_SAMPLER = 1, GMK_OPT_LOCKSTEP = 2, GMK_OPT_AZ_LEAVES = 3 /* K7 only: see gmk_az_set_option */ };
+enum { GMK_OPT_NOISE_SAMPLER = 1, GMK_OPT_LOCKSTEP = 2, GMK_OPT_AZ_LEAVES = 3 /* K7 only: see gmk_az_set_option */,
+       GMK_OPT_AZ_VCF_DEPTH = 4, GMK_OPT_AZ_VCF_BUDGET = 5 /* K7 only: see "K7 + K14" */ };
 #define GMK_AZ_MAX_LEAVES 8
 enum { GMK_NOISE_SAMPLER_STD = 0, GMK_NOISE_SAMPLER_COUNTER = 1 };
 int gmk_mcts_set_option(gmk_mcts *m, int option, int value);
@@ -556,6 +557,33 @@ int gmk_az_write_stats_host(gmk_az* a, int game, const uint32_t* h_nodes, const 
 /* host outputs, any may be NULL; status bit 0 = the game is over (gmk_az_advance), bit 1 = node arena full (playouts of that game were dropped) */
 int gmk_az_root_stats(gmk_az* a, uint32_t* h_visits, float* h_values, float* h_priors, uint32_t* h_root_visits,
                       float* h_root_value, int32_t* h_n_nodes, int32_t* h_status);
+/* ---- K7 + K14: forced wins by fours solved at the leaves of the network search (az_vcf_leaves_kernel) ----
+ * Two options of gmk_az_set_option:
+ *   GMK_OPT_AZ_VCF_DEPTH  = D in 0 .. GMK_VCF_MAX_DEPTH, default 0 = off
+ *   GMK_OPT_AZ_VCF_BUDGET = B in 1 .. 2^20, default 64 (not tuned; DESIGN.md K16 has the timing table)
+ * GMK_ERR_ARG outside these ranges; GMK_ERR_STATE while a gmk_az_select waits for its gmk_az_expand.  The first D > 0 allocates the verdict
+ * buffer, 16 bytes x n_games x GMK_AZ_MAX_LEAVES.  With D = 0 every entry launches exactly the kernels it launches without this block.
+ * With D > 0 a step is the same step with another evaluator.  For every pending leaf -- its stones and its side to move, white when the
+ * leaf's stone count is odd -- gmk_az_select computes, in a kernel of its own right behind the select kernel on the same stream,
+ *     r = K14's walk (below, "K14") on that position, max_depth = D, budget = B, plain mode (flags 0), the side to move attacks
+ * and gmk_az_expand answers the leaf
+ *     r.status == GMK_VCF_WIN     as if the network had returned value = +1.0f and probs = one-hot(r.move): one child, cell pv[0], prior 1.0f,
+ *                                 and -1.0f is backed up
+ *     NONE, DEPTH, BUDGET, OVER   from its row of d_values / d_probs, unchanged
+ * so the search equals the search with the evaluator E'(pos) = WIN ? (1, one-hot) : E(pos), bit for bit.  Default::Expand's legality check, the
+ * arena-full rule (status bit 1, the playout dropped), virtual loss, quota and the order of the pending leaves are as they are.  Terminal
+ * leaves, collided descents and rows k >= n_pending have no leaf and are not solved.  d_values and d_probs are read, never written.  Nothing
+ * waits for the host: a captured step stays one chain of kernels.
+ * Per game the handle counts the leaves solved, those answered WIN, those cut by BUDGET or DEPTH, and the nodes the walks counted;
+ * gmk_az_set_roots and gmk_az_set_slots clear the counters (a slot refilled by gmk_az_advance keeps them: they belong to the slot).
+ * gmk_az_vcf_stats: the counters, per-game host arrays uint32[n_games] x 3 and uint64[n_games]; any pointer may be NULL.  Synchronises.
+ * gmk_az_vcf_verdicts_host: the verdicts of the last gmk_az_select for the gmk_az_live_games x L rows of the leaf batch: status, move, length
+ *   (int32 each) and nodes (uint32), as gmk_vcf_solve writes them; a row without a pending leaf reads GMK_VCF_NONE / -1 / 0 / 0.
+ *   GMK_ERR_STATE when D = 0.  Synchronises.
+ * The host-driven one-leaf entries gmk_az_select_host, gmk_az_expand_host, gmk_az_set_leaf_host and gmk_az_expand_stages_host return
+ * GMK_ERR_STATE on a handle whose D > 0, as they do when L > 1. */
+int gmk_az_vcf_stats(gmk_az* a, uint32_t* h_leaves, uint32_t* h_wins, uint32_t* h_cut, uint64_t* h_nodes);
+int gmk_az_vcf_verdicts_host(gmk_az* a, int32_t* h_status, int32_t* h_move, int32_t* h_length, uint32_t* h_nodes);
 
 /* ---- K12: the referee of a match between two search handles, on the device (match_kernel.hip) ----
  * One ply of n two-agent games without the host in the loop (agents/utils.py:13-63 dual_play, :66-100 eval_agents): the side to move has
