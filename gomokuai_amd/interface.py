@@ -9,6 +9,7 @@ is host-side interop only.
     python -m gomokuai_amd.interface botzone   --agent random-mcts:5:5 --replicas 1024 --ms 960     < request.json
     python -m gomokuai_amd.interface botzone   --agent traditional:5 --vcf 16 --ms 960              < request.json
     python -m gomokuai_amd.interface botzone   --agent traditional:5 --vcf 16 --vcf-defend --ms 960 < request.json
+    python -m gomokuai_amd.interface botzone   --agent traditional:5 --vcf 16 --vct 2 --ms 960        < request.json
 """
 import datetime
 import json
@@ -228,11 +229,21 @@ class VCFAgent(Agent):
     defend=True acts on the opponent's verdict as well (K15, lib.vcf_defend): when the side to move has no forced win and the opponent has one,
     the inner agent is still asked, so that its tree stays in step, but its move stands only if it lies in the best class of cells there is:
     those that HOLD, else those UNKNOWN, else those that LOSE in the greatest number of moves.  Otherwise the cell of that class with the highest
-    lib.pattern_policy(filter=False) probability is played, the lowest cell on a tie.  The debug message then adds `vcf_defence`."""
+    lib.pattern_policy(filter=False) probability is played, the lowest cell on a tie.  The debug message then adds `vcf_defence`.
+    threats=T > 0 adds the forced win by continuous threats (K17, lib.vct_solve: at most T moves that threaten a win by fours, every reply
+    that holds answered, then a win by fours).  It is tried last, after the own win by fours and after the defence: only when the inner
+    agent's move stands, a WIN's first move is played in its place.  The debug message then adds `vct`, the verdict and `positions`.
+    That search comes after the inner agent has spent its time and is bounded by its own limits only, not by a clock: `threats`, `depth`,
+    `budget` and `max_positions`, the cap per level (default 512, the setting tools/vct_time.py measured: tens of milliseconds at T <= 3 with
+    depth 8 and budget 1000; a root that runs into the cap ends VCT_BUDGET and the inner move is played)."""
 
-    def __init__(self, inner, depth=16, budget=100000, defend=False):
+    def __init__(self, inner, depth=16, budget=100000, defend=False, threats=0, max_positions=512):
+        from . import lib as G
+        if not 0 <= int(threats) <= G.VCT_MAX_THREATS:
+            raise ValueError("threats must be in 0 .. %d" % G.VCT_MAX_THREATS)
         self.inner, self.depth, self.budget, self.defend = inner, int(depth), int(budget), bool(defend)
-        self.moves, self.own, self.threat, self.defence = [], None, None, None
+        self.threats, self.max_positions = int(threats), int(max_positions)
+        self.moves, self.own, self.threat, self.defence, self.vct = [], None, None, None, None
 
     def name(self):
         return "VCF(" + self.inner.name() + ")"
@@ -283,9 +294,17 @@ class VCFAgent(Agent):
         report["overruled"] = True
         return int(best[int(np.argmax(probs[best]))]), report      # argmax takes the first of equals: the lowest cell
 
+    def _threats(self):
+        """The verdict of lib.vct_solve for the side to move, as the debug message carries it."""
+        from . import lib as G
+        out = G.vct_solve(*self._lists(), self.depth, self.budget, max_threats=self.threats, max_positions=self.max_positions)
+        cells = [int(c) for c in out["pv"][0]]
+        return {"status": G.VCT_STATUS_NAMES[int(out["status"][0])], "move": int(out["move"][0]), "threats": int(out["threats"][0]),
+                "positions": int(out["positions"][0]), "pv": cells[:cells.index(255)] if 255 in cells else cells}
+
     def get_action(self, board):
         self.moves = [int(p.id) for p in board.move_record]
-        self.own, self.threat, self.defence = self._solve(False), None, None
+        self.own, self.threat, self.defence, self.vct = self._solve(False), None, None, None
         if self.own["status"] == "WIN":
             return _core().Position(self.own["move"])
         action = self.inner.get_action(board)
@@ -293,6 +312,10 @@ class VCFAgent(Agent):
             cell, self.defence = self._defend(int(action.id))
             if self.defence is not None and self.defence["overruled"]:
                 return _core().Position(cell)
+        if self.threats > 0:
+            self.vct = self._threats()
+            if self.vct["status"] == "WIN":
+                return _core().Position(self.vct["move"])
         return action
 
     def debug_message(self):
@@ -305,19 +328,28 @@ class VCFAgent(Agent):
         message["vcf"], message["vcf_opponent"] = self.own, self.threat
         if self.defence is not None:
             message["vcf_defence"] = self.defence
+        if self.vct is not None:
+            message["vct"] = self.vct
         return message
 
 
-def make_agent(spec, milliseconds=960, iterations=None, quiet=False, replicas=1, seed=None, vcf=0, vcf_defend=False):
+def make_agent(spec, milliseconds=960, iterations=None, quiet=False, replicas=1, seed=None, vcf=0, vcf_defend=False, vct=0):
     """'random', 'human', 'pattern', 'random-mcts[:c_puct[:c_rollouts]]', 'traditional[:c_puct]', 'poolrave[:c_puct[:c_bias]]'.
     replicas > 1 turns the three MCTS kinds into an EnsembleAgent of that many trees per position ('traditional' with the reference's root
     noise, alpha 0.05 / epsilon 0.25: its search has no other source of difference); replicas = 1 builds the agents as ever.
     vcf = D > 0 puts the forced-win solver in front of the agent (VCFAgent, depth D); 'human' and 'random' stay as they are.
-    vcf_defend=True (with vcf > 0 only) lets that agent also refuse moves that lose to the opponent's forced win (VCFAgent(defend=True))."""
+    vcf_defend=True (with vcf > 0 only) lets that agent also refuse moves that lose to the opponent's forced win (VCFAgent(defend=True)).
+    vct = T in 1 .. lib.VCT_MAX_THREATS (with vcf > 0 only) lets it also play a forced win by at most T threat moves (VCFAgent(threats=T)); that
+    search runs after the agent's own and is not bounded by `milliseconds`.  0 builds today's agents."""
     if vcf_defend and vcf <= 0:
         raise ValueError("vcf_defend needs vcf > 0")
+    if vct and vcf <= 0:
+        raise ValueError("vct needs vcf > 0")
+    from . import lib as G
+    if not 0 <= vct <= G.VCT_MAX_THREATS:
+        raise ValueError("vct must be in 0 .. %d" % G.VCT_MAX_THREATS)
     if vcf > 0 and spec.split(":")[0] not in ("human", "random"):
-        return VCFAgent(make_agent(spec, milliseconds, iterations, quiet, replicas, seed), depth=vcf, defend=vcf_defend)
+        return VCFAgent(make_agent(spec, milliseconds, iterations, quiet, replicas, seed), depth=vcf, defend=vcf_defend, threats=vct)
     core = _core()
     kind, *args = spec.split(":")
     num = [float(a) for a in args]
@@ -465,19 +497,25 @@ def main(argv=None):
     ap.add_argument("--replicas", type=int, default=1, help="trees per position for the MCTS agents (root-parallel ensemble, merged on the GPU); --iterations then counts playouts per replica")
     ap.add_argument("--vcf", type=int, default=0, metavar="DEPTH", help="put the exact forced-win solver (continuous fours, up to DEPTH own moves) in front of the agents; 0: off")
     ap.add_argument("--vcf-defend", action="store_true", help="with --vcf: also refuse moves that lose to the opponent's forced win by fours, as far as any cell holds")
+    ap.add_argument("--vct", type=int, default=0, metavar="T", help="with --vcf: also play a forced win by at most T moves that threaten a win by fours (fours and threes); 0: off.  This search runs after the agent's own and is not bounded by --ms")
     args = ap.parse_args(argv)
     if args.vcf_defend and args.vcf <= 0:
         ap.error("--vcf-defend needs --vcf DEPTH")
+    if args.vct and args.vcf <= 0:
+        ap.error("--vct needs --vcf DEPTH")
+    from . import lib as G
+    if not 0 <= args.vct <= G.VCT_MAX_THREATS:
+        ap.error("--vct takes 0 .. %d" % G.VCT_MAX_THREATS)
     if args.seed is not None:
         _core().set_seed(args.seed)
         random.seed(args.seed)
     quiet = args.mode != "console"                                  # a bot's stdout carries the protocol only
-    agent = make_agent(args.agent, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed, vcf=args.vcf, vcf_defend=args.vcf_defend)
+    agent = make_agent(args.agent, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed, vcf=args.vcf, vcf_defend=args.vcf_defend, vct=args.vct)
     if args.mode == "botzone":
         return botzone_interface(agent)
     if args.mode == "keepalive":
         return keep_alive_botzone_interface(agent)
-    return console_interface(agent, make_agent(args.agent2, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed, vcf=args.vcf, vcf_defend=args.vcf_defend))
+    return console_interface(agent, make_agent(args.agent2, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed, vcf=args.vcf, vcf_defend=args.vcf_defend, vct=args.vct))
 
 
 if __name__ == "__main__":

@@ -48,6 +48,7 @@ EXPORTS = [
     "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_root_choice", "gmk_trad_step_device", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_run_rave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
     "gmk_pattern_policy", "gmk_pattern_policy_host", "gmk_pattern_play",
     "gmk_vcf_solve", "gmk_vcf_solve_host", "gmk_vcf_defend", "gmk_vcf_defend_host",
+    "gmk_vcf_threats", "gmk_vcf_threats_host", "gmk_vct_solve", "gmk_vct_solve_host",
     "gmk_match_referee",
     "gmk_mcts_ensemble_merge", "gmk_trad_ensemble_merge", "gmk_ensemble_merge_host",
     "gmk_replay_create", "gmk_replay_destroy", "gmk_replay_reset", "gmk_replay_append", "gmk_replay_append_packed", "gmk_replay_size",
@@ -178,6 +179,10 @@ def load():
     L.gmk_vcf_solve_host.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp, vp]
     L.gmk_vcf_defend.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gmk_vcf_defend_host.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.gmk_vcf_threats.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.gmk_vcf_threats_host.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.gmk_vct_solve.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.gmk_vct_solve_host.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.gmk_replay_create.argtypes = [C.c_int64, C.c_int64, C.c_uint64, C.POINTER(vp)]
     L.gmk_replay_destroy.argtypes = [vp]
     L.gmk_replay_reset.argtypes = [vp, vp]
@@ -784,6 +789,70 @@ def vcf_defend_device(d_moves, stride, d_lens, n, max_depth=16, budget=100000, i
     status, length and pv and the verdicts are required."""
     _check(load().gmk_vcf_defend(d_moves, int(stride), d_lens, int(n), int(max_depth), int(budget), _vcf_flags(False, iterative),
                                  d_threat_status, d_threat_length, d_threat_pv, d_threat_nodes, d_verdict, d_cell_length, d_cell_nodes, stream))
+
+
+# ---------------- K17: what a stone of the side to move threatens (gmk_vcf_threats), and the forced win by threats (gmk_vct_solve) ----------------
+VCF_THREAT_NONE, VCF_THREAT_QUIET, VCF_THREAT_WINS, VCF_THREAT_UNKNOWN, VCF_THREAT_FIVE, VCF_THREAT_FOUR, VCF_THREAT_IGNORES = 0, 1, 2, 3, 4, 5, 6
+VCF_THREAT_NAMES = ("NONE", "QUIET", "WINS", "UNKNOWN", "FIVE", "FOUR", "IGNORES")
+VCT_MAX_THREATS, VCT_PV = 8, 80
+VCT_BUDGET = 6                                                                      # a status of vct_solve beside the VCF_* ones
+VCT_STATUS_NAMES = VCF_STATUS_NAMES + ("VCT_BUDGET",)
+
+
+def vcf_threats(moves, lens, max_depth=16, budget=100000, iterative=False):
+    """moves u8[n, stride] (host), lens i32[n]: one move list per position, black first -> the own verdict of the side to move, which is
+    vcf_solve's ("own_status" i32[n], "own_move" i32[n], "own_length" i32[n], "own_nodes" u32[n], "own_pv" u8[n, 64]), and for each of the 225
+    cells what a stone of the side to move there threatens: "verdict" u8[n, 225] (VCF_THREAT_*), "length" u8[n, 225] (the moves of the win by
+    fours that a WINS cell threatens; 1 or 2 for a FOUR) and "nodes" u32[n, 225] (the candidates tried where the cell was searched).  Exact;
+    the contract is in include/gomoku_hip.h ("K17").  Runs on the GPU through gmk_vcf_threats_host; raises without one."""
+    init()
+    moves = np.ascontiguousarray(moves, dtype=np.uint8)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    assert moves.ndim == 2 and lens.shape == (moves.shape[0],)
+    n, stride = moves.shape
+    out = {"own_status": np.zeros(n, np.int32), "own_move": np.zeros(n, np.int32), "own_length": np.zeros(n, np.int32),
+           "own_nodes": np.zeros(n, np.uint32), "own_pv": np.full((n, VCF_PV), 255, np.uint8), "verdict": np.zeros((n, 225), np.uint8),
+           "length": np.zeros((n, 225), np.uint8), "nodes": np.zeros((n, 225), np.uint32)}
+    if n:
+        _check(load().gmk_vcf_threats_host(moves.ctypes.data, stride, lens.ctypes.data, n, int(max_depth), int(budget), _vcf_flags(False, iterative),
+                                           *[out[k].ctypes.data for k in ("own_status", "own_move", "own_length", "own_nodes", "own_pv", "verdict",
+                                                                          "length", "nodes")]))
+    return out
+
+
+def vcf_threats_device(d_moves, stride, d_lens, n, max_depth=16, budget=100000, iterative=False, d_own_status=None, d_own_move=None,
+                       d_own_length=None, d_own_nodes=None, d_own_pv=None, d_verdict=None, d_cell_length=None, d_cell_nodes=None, stream=None):
+    """Device-pointer form (ints, e.g. torch.Tensor.data_ptr()) of gmk_vcf_threats; asynchronous on `stream`, allocates nothing.  The own
+    status and the verdicts are required."""
+    _check(load().gmk_vcf_threats(d_moves, int(stride), d_lens, int(n), int(max_depth), int(budget), _vcf_flags(False, iterative),
+                                  d_own_status, d_own_move, d_own_length, d_own_nodes, d_own_pv, d_verdict, d_cell_length, d_cell_nodes, stream))
+
+
+def vct_solve(moves, lens, max_depth=16, budget=100000, iterative=False, max_threats=1, max_positions=4096):
+    """moves u8[n, stride] (host), lens i32[n]: one move list per root, black first -> {"status" i32[n] (VCF_* or VCT_BUDGET), "move" i32[n],
+    "threats" i32[n], "positions" u32[n], "pv" u8[n, 80]}: does the side to move have a forced win by continuous threats, at most max_threats
+    moves that threaten a win by fours (each answered by every reply that holds) and then a win by fours?  max_depth, budget and iterative are
+    those of every inner vcf_solve; max_positions caps the positions of one root on one level.  Exact; the contract is in
+    include/gomoku_hip.h ("K17").  Runs on the GPU through gmk_vct_solve_host; raises without one."""
+    init()
+    moves = np.ascontiguousarray(moves, dtype=np.uint8)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    assert moves.ndim == 2 and lens.shape == (moves.shape[0],)
+    n, stride = moves.shape
+    out = {"status": np.zeros(n, np.int32), "move": np.full(n, -1, np.int32), "threats": np.zeros(n, np.int32), "positions": np.zeros(n, np.uint32),
+           "pv": np.full((n, VCT_PV), 255, np.uint8)}
+    if n:
+        _check(load().gmk_vct_solve_host(moves.ctypes.data, stride, lens.ctypes.data, n, int(max_depth), int(budget), _vcf_flags(False, iterative),
+                                         int(max_threats), int(max_positions), *[out[k].ctypes.data for k in ("status", "move", "threats", "positions", "pv")]))
+    return out
+
+
+def vct_solve_device(d_moves, stride, d_lens, n, max_depth=16, budget=100000, iterative=False, max_threats=1, max_positions=4096,
+                     d_status=None, d_move=None, d_threats=None, d_positions=None, d_pv=None, stream=None):
+    """Device-pointer form (ints, e.g. torch.Tensor.data_ptr()) of gmk_vct_solve.  It allocates its workspace and synchronises `stream`
+    between the levels: when it returns, the outputs are written."""
+    _check(load().gmk_vct_solve(d_moves, int(stride), d_lens, int(n), int(max_depth), int(budget), _vcf_flags(False, iterative), int(max_threats),
+                                int(max_positions), d_status, d_move, d_threats, d_positions, d_pv, stream))
 
 
 # ---------------- K12: the referee of a match between two search handles (gmk_match_referee) and what its callers share ----------------

@@ -790,6 +790,86 @@ int gmk_vcf_defend_host(const uint8_t* h_moves, int stride, const int32_t* h_len
                         int32_t* h_threat_status, int32_t* h_threat_length, uint8_t* h_threat_pv, uint32_t* h_threat_nodes,
                         uint8_t* h_verdict, uint8_t* h_cell_length, uint32_t* h_cell_nodes);
 
+/* ---- K17: what a stone of the side to move threatens, for every cell, exact, per position and in batch ----
+ * No counterpart in the reference; the contract is this block, on top of K14's.  A position is the move list, as for K14.  A is the side to
+ * move, D the other colour.  attack, completing, L and budget are K14's; solve(list, flags) is gmk_vcf_solve's result for that list with the
+ * same max_depth and budget.  flags: 0 or GMK_VCF_ITERATIVE.
+ *
+ *   1. own = solve(P, flags & GMK_VCF_ITERATIVE): d_own_status int32[n], d_own_move int32[n], d_own_length int32[n], d_own_nodes uint32[n],
+ *      d_own_pv uint8[n][GMK_VCF_PV], equal bit for bit to what gmk_vcf_solve writes.
+ *   2. own OVER or BAD: every cell's verdict is GMK_VCF_THREAT_NONE; nothing is searched.
+ *   3. Otherwise (own WIN, NONE, DEPTH or BUDGET alike) each cell c has a verdict (d_verdict uint8[n][225]), a length (d_cell_length
+ *      uint8[n][225]) and nodes (d_cell_nodes uint32[n][225]); length and nodes are 0 unless said otherwise.  Tested in this order:
+ *        c occupied                                   GMK_VCF_THREAT_NONE
+ *        c in completing(A) on P                      GMK_VCF_THREAT_FIVE     A wins at once
+ *        completing(D) on P + [c] is not empty        GMK_VCF_THREAT_IGNORES  D makes five next
+ *        completing(A) on P + [c] is not empty        GMK_VCF_THREAT_FOUR     length = 1 with one completing cell, 2 with several; not searched
+ *        else s = solve(P + [c], GMK_VCF_OPPONENT | (flags & GMK_VCF_ITERATIVE)): A, having played c, attacks again as if D had passed;
+ *        each such cell with the whole budget; nodes = s.nodes
+ *          s WIN                                      GMK_VCF_THREAT_WINS, length = s.length: c threatens a win by fours in that many moves
+ *          s NONE                                     GMK_VCF_THREAT_QUIET
+ *          s DEPTH or BUDGET                          GMK_VCF_THREAT_UNKNOWN  the caller raises the limits
+ *   4. Every output is an exact function of the list, max_depth, budget and flags.
+ *
+ * gmk_vcf_threats: asynchronous on `stream` (two launches), allocates nothing; n = 0 does nothing.  d_own_status and d_verdict are required
+ *   (the second launch reads the first); the other own outputs, d_cell_length and d_cell_nodes may be NULL.  GMK_ERR_ARG as for
+ *   gmk_vcf_defend.  GMK_ERR_STATE without a device.  Nothing outside a list's len cells is read; the stone on c is added in registers, never
+ *   written to the list.
+ * gmk_vcf_threats_host: the same with host buffers (allocates, copies in, runs on the GPU, copies out, synchronises). */
+enum { GMK_VCF_THREAT_NONE = 0, GMK_VCF_THREAT_QUIET = 1, GMK_VCF_THREAT_WINS = 2, GMK_VCF_THREAT_UNKNOWN = 3, GMK_VCF_THREAT_FIVE = 4,
+       GMK_VCF_THREAT_FOUR = 5, GMK_VCF_THREAT_IGNORES = 6 };
+int gmk_vcf_threats(const uint8_t* d_moves, int stride, const int32_t* d_lens, int n, int max_depth, uint32_t budget, int flags,
+                    int32_t* d_own_status, int32_t* d_own_move, int32_t* d_own_length, uint32_t* d_own_nodes, uint8_t* d_own_pv,
+                    uint8_t* d_verdict, uint8_t* d_cell_length, uint32_t* d_cell_nodes, void* stream);
+int gmk_vcf_threats_host(const uint8_t* h_moves, int stride, const int32_t* h_lens, int n, int max_depth, uint32_t budget, int flags,
+                         int32_t* h_own_status, int32_t* h_own_move, int32_t* h_own_length, uint32_t* h_own_nodes, uint8_t* h_own_pv,
+                         uint8_t* h_verdict, uint8_t* h_cell_length, uint32_t* h_cell_nodes);
+
+/* ---- K17: the forced win by continuous threats (fours and threes, VCT), exact, per position and in batch ----
+ * No counterpart in the reference; the contract is this block, on top of K14's, K15's and the one above.  A root is a move list; A is its
+ * side to move, D the other colour.  solve, threats and defend are gmk_vcf_solve, gmk_vcf_threats and gmk_vcf_defend with this call's
+ * max_depth, budget and flags (0 or GMK_VCF_ITERATIVE).  max_threats = T in 1 .. GMK_VCT_MAX_THREATS limits A's threat moves, the moves that
+ * are answered by a reply of D's choice; max_positions = M >= 1 caps the positions of one root on one level.
+ * The search is level-synchronous.  Level 0 is the root; the positions of level t have A to move after t threat moves and their replies.
+ *
+ *   for t = 0, 1, .. T:
+ *     every position Q of level t: o = solve(Q).  At the root OVER and BAD are the result.  o WIN: Q is won, with depth 0 and line o.pv.
+ *       o DEPTH or BUDGET: cut = true.  t = T and Q not won: cut = true (level T is never expanded).
+ *     resolve, levels t - 1 .. 0: depth(Q) = 0 if Q is won, else 1 + min over Q's candidates c of (max over c's children of their depth,
+ *       0 without children), over the candidates whose children all have a depth; none: no depth yet.
+ *     the root has a depth: WIN.  Nothing of it is expanded further.
+ *     t < T, every Q of the level that is not won, in order:
+ *       the candidates are the cells of threats(Q) with verdict WINS or FOUR, ascending.  A cell UNKNOWN: cut = true; it is no candidate.
+ *       candidate c: d = defend(Q + [c]).  A cell UNKNOWN: cut = true and c is dropped.  A cell FIVE: c is dropped (the IGNORES verdict
+ *       already excludes it).  Otherwise c's children are the positions Q + [c, r], r over the HOLDS cells, ascending; they join level t + 1.
+ *     level t + 1 has more than M positions: GMK_VCT_BUDGET, and the level is discarded.
+ *   no win when the levels run out: GMK_VCF_DEPTH if cut, else GMK_VCF_NONE.
+ *
+ * Nothing is pruned: a position is expanded whether or not its branch can still win, so `positions` is a function of the contract alone.
+ * Per root (any output pointer may be NULL): d_status int32[n] (GMK_VCF_NONE, WIN, DEPTH, OVER, BAD, or GMK_VCT_BUDGET), d_move int32[n],
+ * d_threats int32[n], d_positions uint32[n], d_pv uint8[n][GMK_VCT_PV]:
+ *     move       WIN: pv[0] -- o.move at depth 0, else the lowest cell among the candidates of minimal depth; -1 otherwise
+ *     threats    WIN: the root's depth, A's threat moves before the win by fours; 0 otherwise
+ *     positions  the sizes of the root's levels added up, the root itself included, up to the level it ended at; a discarded level is not counted
+ *     pv         WIN: c, the lowest candidate of minimal depth, then its child r of greatest depth (the lowest r on ties), and so on down; the
+ *                line ends with the o.pv of a won position, or with c alone when no reply holds.  Cells past the end, and every cell of
+ *                another status, are 255.
+ * A root's outputs are an exact function of its list and the six parameters; they do not depend on the other roots of the batch.
+ * gmk_vct_solve: the driver is host code.  It allocates its workspace on the device (and frees it), launches the three solvers and small
+ *   kernels of its own on `stream`, and SYNCHRONISES `stream` several times per level to read per-root counts; when it returns the outputs are
+ *   written.  n = 0 does nothing.  GMK_ERR_ARG: as gmk_vcf_solve, GMK_VCF_OPPONENT in flags, max_threats or max_positions out of range.
+ *   GMK_ERR_HIP when a level does not fit in device or host memory; GMK_ERR_CAPACITY when a level, the roots' (n) included, has more than 2^22
+ *   positions over the batch.  The workspace is a few blocks per level.
+ * gmk_vct_solve_host: the same with host buffers. */
+enum { GMK_VCT_MAX_THREATS = 8, GMK_VCT_PV = 80 };
+enum { GMK_VCT_BUDGET = 6 };
+int gmk_vct_solve(const uint8_t* d_moves, int stride, const int32_t* d_lens, int n, int max_depth, uint32_t budget, int flags,
+                  int max_threats, int max_positions, int32_t* d_status, int32_t* d_move, int32_t* d_threats, uint32_t* d_positions,
+                  uint8_t* d_pv, void* stream);
+int gmk_vct_solve_host(const uint8_t* h_moves, int stride, const int32_t* h_lens, int n, int max_depth, uint32_t budget, int flags,
+                       int max_threats, int max_positions, int32_t* h_status, int32_t* h_move, int32_t* h_threats, uint32_t* h_positions,
+                       uint8_t* h_pv);
+
 /* ---- K11: training the policy-value network on the device (network/train.py:62-86, network/model_tf.py:73-135) ----
  * A gmk_trainer holds the network's sixteen parameter tensors in float32 in their canonical layouts (those gmk_pvnet_create and
  * gmk_pvnet_set_dense take), Adam's two moments, a gradient block and the activations of up to max_batch positions.  One step = forward
