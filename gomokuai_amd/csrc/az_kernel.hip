@@ -50,7 +50,8 @@ struct AzHeader {                                // 256 B per game, in HBM
     uint32_t vcf_leaves, vcf_wins, vcf_cut;      // K7 + K14 (GMK_OPT_AZ_VCF_DEPTH > 0): pending leaves solved, answered WIN, cut by BUDGET or DEPTH
     uint32_t pad0;
     unsigned long long vcf_nodes;                //   and the nodes their walks counted
-    uint32_t pad[16];
+    uint32_t proof_proved, proof_stops;          // K7 + proofs (GMK_OPT_AZ_PROOF): nodes given a proof, descents ended at a node already proven
+    uint32_t pad[14];
 };
 static_assert(sizeof(AzHeader) == 256 && offsetof(AzHeader, vcf_nodes) % 8 == 0, "AzHeader layout");
 
@@ -91,6 +92,83 @@ __device__ __forceinline__ void count_verdict(AzHeader* hdr, const int4& v) {
     hdr->vcf_nodes += static_cast<uint32_t>(v.w);
 }
 
+// ---- K7 + proofs (GMK_OPT_AZ_PROOF; the contract is in include/gomoku_hip.h, "K7 + proofs") ----
+// A node's proof (GMK_AZ_PROOF_*) lives in bits 16..17 of its kids.y word, above the child count and the cell: every reader masks the word, and
+// az_keep_subtree copies it whole, so the bits travel through re-rooting.  Only the <true> instantiations below read or write them.
+constexpr uint32_t kProofShift = 16u, kProofBits = 3u << kProofShift;
+__device__ __forceinline__ uint32_t proof_of(uint32_t kids_y) { return (kids_y >> kProofShift) & 3u; }
+
+// prove(X, s), called by all 64 lanes of the game's wavefront with uniform arguments; stones = the stone count of X's position.  Lane 0 writes
+// the bit, a workgroup-scope fence and a barrier stand before the lanes read bits again (the next level's children, the next descent).  LOSES
+// makes the parent WINS; WINS makes the parent LOSES only when the parent has a child for every free cell and all of them are WINS -- a ballot
+// over the children, as select walks them.  Returns the number of nodes that were given a proof.
+__device__ uint32_t az_prove(uint2* kids, const uint32_t* parent, uint32_t x, uint32_t s, int stones, int lane) {
+    uint32_t proved = 0;
+    for (;;) {
+        const uint32_t ky = kids[x].y;
+        if (ky & kProofBits) break;
+        if (lane == 0) kids[x].y = ky | (s << kProofShift);
+        ++proved;
+        __threadfence_block();
+        __syncthreads();
+        const uint32_t p = parent[x];
+        if (p == kNoNode) break;
+        --stones;                                                // of P's position
+        if (s == GMK_AZ_PROOF_WINS) {
+            const uint2 pk = kids[p];
+            const uint32_t n = pk.y & 0xFFu;
+            if (n != static_cast<uint32_t>(kCells - stones)) break;                    // Default::Expand dropped a free cell: an untried reply
+            bool all = true;
+            for (uint32_t i = lane; i < n; i += 64) all = all && proof_of(kids[pk.x + i].y) == GMK_AZ_PROOF_WINS;
+            if (__ballot(!all) != 0ull) break;
+        }
+        s = s == GMK_AZ_PROOF_WINS ? GMK_AZ_PROOF_LOSES : GMK_AZ_PROOF_WINS;
+        x = p;
+    }
+    return proved;
+}
+
+// The children of a node for a descent: the first child marked LOSES in child order (lose_i, 0xFFFFFFFF: none), and whether children marked
+// WINS are left out of the PUCB maximum (some child is not marked WINS).  pb: this lane's children's proofs, two bits per round of 64.
+__device__ __forceinline__ void proof_children(const uint2* kids, uint32_t first, uint32_t n, int lane, uint32_t& pb, uint32_t& lose_i, bool& filter) {
+    pb = 0u;
+    lose_i = 0xFFFFFFFFu;
+    bool open = false;
+    int j = 0;
+    for (uint32_t i = lane; i < n; i += 64, ++j) {
+        const uint32_t pr = proof_of(kids[first + i].y);
+        pb |= pr << (2 * j);
+        if (pr == GMK_AZ_PROOF_LOSES) lose_i = min(lose_i, i);
+        open = open || pr != GMK_AZ_PROOF_WINS;
+    }
+    filter = __ballot(open) != 0ull;
+    if (__ballot(lose_i != 0xFFFFFFFFu) != 0ull) {
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) lose_i = min(lose_i, static_cast<uint32_t>(__shfl_xor(lose_i, s)));
+    }
+}
+
+// The root choice with proofs, after the old rule has left (best_v, best_i): the first child marked LOSES; otherwise the most visited child
+// among those not marked WINS that have a visit, first maximum in child order; otherwise the old rule's.  The same in every lane.
+__device__ __forceinline__ void proof_choice(const uint2* kids, const uint2* stat, uint32_t first, uint32_t n, int lane, uint32_t& best_v, uint32_t& best_i) {
+    uint32_t lose_i = 0xFFFFFFFFu, pv = 0u, pi = 0xFFFFFFFFu;
+    for (uint32_t i = lane; i < n; i += 64) {
+        const uint32_t pr = proof_of(kids[first + i].y), v = stat[first + i].x;
+        if (pr == GMK_AZ_PROOF_LOSES) lose_i = min(lose_i, i);
+        else if (pr != GMK_AZ_PROOF_WINS && v > pv) { pv = v; pi = i; }
+    }
+    for (int s = 32; s > 0; s >>= 1) {
+        lose_i = min(lose_i, static_cast<uint32_t>(__shfl_xor(lose_i, s)));
+        const uint32_t ov = __shfl_xor(pv, s), oi = __shfl_xor(pi, s);
+        if (ov > pv || (ov == pv && oi < pi)) { pv = ov; pi = oi; }
+    }
+    if (lose_i != 0xFFFFFFFFu) { best_v = 1u; best_i = lose_i; }
+    else if (pv != 0u) { best_v = pv; best_i = pi; }
+}
+
+// kProof (here and in az_select_leaves_kernel): a descent stops at a proven node below the root and backs the exact value up, children marked
+// LOSES are taken and children marked WINS avoided, and a five at the leaf starts a proof.  <false> is the search without the proof bits.
+template <bool kProof>
 __global__ __launch_bounds__(64)
 void az_select_kernel(AzTree t, float* __restrict__ out_states) {
     __shared__ uint32_t s_rows[16];
@@ -110,14 +188,23 @@ void az_select_kernel(AzTree t, float* __restrict__ out_states) {
     uint32_t last = hdr->last_move, last2 = hdr->last_move2;
 
     // ---- Default::Select (MonteCarlo.hpp:57-68) down to a leaf ----
+    uint32_t stopped = GMK_AZ_PROOF_NONE;                        // kProof: the proof of the node the descent ended at
     for (;;) {
         const uint2 k = kids[node];
+        if constexpr (kProof) {
+            if (node != 0u && (k.y & kProofBits)) { stopped = proof_of(k.y); break; }
+        }
         const uint32_t first = k.x, n = k.y & 0xFFu;
         if (n == 0) break;
+        uint32_t pb = 0u, lose_i = 0xFFFFFFFFu;
+        bool filter = false;
+        if constexpr (kProof) proof_children(kids, first, n, lane, pb, lose_i, filter);
         const double sqrt_n = sqrt(static_cast<double>(stat[node].x));
         double best_score = -1.0;
         uint32_t best_i = 0xFFFFFFFFu;
-        for (uint32_t i = lane; i < n; i += 64) {
+        int j = 0;
+        for (uint32_t i = lane; i < n; i += 64, ++j) {
+            if constexpr (kProof) { if (filter && ((pb >> (2 * j)) & 3u) == GMK_AZ_PROOF_WINS) continue; }
             const uint2 cs = stat[first + i];
             const double p_i = prior[first + i], n_i = static_cast<double>(cs.x + 1u);
             const double score = static_cast<double>(__uint_as_float(cs.y)) + t.c_puct * p_i * sqrt_n / n_i;       // Q + PUCB (:23-28)
@@ -131,6 +218,7 @@ void az_select_kernel(AzTree t, float* __restrict__ out_states) {
         }
         best_i = __shfl(best_i, 0);
         if (best_i == 0xFFFFFFFFu) best_i = 0;                                          // nothing beat the initial -1.0: the first child
+        if constexpr (kProof) { if (lose_i != 0xFFFFFFFFu) best_i = lose_i; }
         node = first + best_i;
         const uint32_t cell = (kids[node].y >> 8) & 0xFFu;
         if (lane == 0) s_rows[cell / 15] |= 1u << (cell % 15 + ((stones & 1) ? 16 : 0));                            // Policy::applyMove: black moves on even counts
@@ -140,6 +228,18 @@ void az_select_kernel(AzTree t, float* __restrict__ out_states) {
         last = cell;
     }
 
+    if constexpr (kProof) {
+        if (stopped != GMK_AZ_PROOF_NONE) {                      // the value is known: no network row
+            if (lane == 0) {
+                backup(stat, t.parent + arena, node, stopped == GMK_AZ_PROOF_LOSES ? 1.0f : -1.0f);
+                hdr->leaf_pending = 0;
+                hdr->proof_stops += 1u;
+            }
+            if (out_states)
+                for (int i = lane; i < 6 * kCells; i += 64) out_states[row * 6 * kCells + i] = 0.0f;
+            return;
+        }
+    }
     // ---- Board::checkGameEnd (Game.cpp:88-136): five through the last stone, or a full board ----
     bool ended = false;
     int winner = 0;
@@ -154,6 +254,12 @@ void az_select_kernel(AzTree t, float* __restrict__ out_states) {
         if (lane == 0) {
             backup(stat, t.parent + arena, node, static_cast<float>(node_player * winner));
             hdr->leaf_pending = 0;
+        }
+        if constexpr (kProof) {
+            if (winner != 0) {                                   // a five: the side to move at the node has lost
+                const uint32_t proved = az_prove(t.kids + arena, t.parent + arena, node, GMK_AZ_PROOF_LOSES, stones, lane);
+                if (lane == 0) hdr->proof_proved += proved;
+            }
         }
         if (out_states)
             for (int i = lane; i < 6 * kCells; i += 64) out_states[row * 6 * kCells + i] = 0.0f;
@@ -177,7 +283,8 @@ void az_select_kernel(AzTree t, float* __restrict__ out_states) {
 }
 
 // kVcf: the leaf's verdict comes first (GMK_OPT_AZ_VCF_DEPTH > 0) -- on WIN the answer is (1.0f, one-hot(move)) instead of the network's row
-template <bool kVcf>
+// kProof (with kVcf): a leaf answered WIN whose child was created is proven WINS
+template <bool kVcf, bool kProof>
 __global__ __launch_bounds__(64)
 void az_expand_kernel(AzTree t, const float* __restrict__ values, const float* __restrict__ probs, int stages /* bit 0: expand, bit 1: back up */, AzVcf vc) {
     const int game = blockIdx.x, lane = threadIdx.x;
@@ -233,6 +340,13 @@ void az_expand_kernel(AzTree t, const float* __restrict__ values, const float* _
         }
     }
     __threadfence_block();
+    if constexpr (kProof) {
+        __syncthreads();                                         // the leaf's new kids word, before the 64 lanes read it
+        if (win && total > 0 && (stages & 1)) {
+            const uint32_t proved = az_prove(t.kids + arena, t.parent + arena, leaf, GMK_AZ_PROOF_WINS, static_cast<int>(hdr->leaf_stones), lane);
+            if (lane == 0) hdr->proof_proved += proved;
+        }
+    }
     if (lane == 0) {
         if (stages & 2) backup(t.stat + arena, t.parent + arena, leaf, win ? -1.0f : -values[row]);      // node_value = -state_value (MCTS.cpp:166-168)
         hdr->leaf_pending = 0;
@@ -265,6 +379,7 @@ struct AzLeaves {
     int leaves;                                  // L
 };
 
+template <bool kProof>
 __global__ __launch_bounds__(64)
 void az_select_leaves_kernel(AzTree t, AzLeaves lv, float* out_states) {
     __shared__ uint32_t s_rows[16];
@@ -292,14 +407,23 @@ void az_select_leaves_kernel(AzTree t, AzLeaves lv, float* out_states) {
         int stones = root_stones;
         uint32_t last = root_last, last2 = root_last2;
         // ---- Default::Select with the in-flight descents counted as losses ----
+        uint32_t stopped = GMK_AZ_PROOF_NONE;                    // kProof: the proof of the node the descent ended at
         for (;;) {
             const uint2 kd = kids[node];
+            if constexpr (kProof) {
+                if (node != 0u && (kd.y & kProofBits)) { stopped = proof_of(kd.y); break; }
+            }
             const uint32_t first = kd.x, n = kd.y & 0xFFu;
             if (n == 0) break;
+            uint32_t pb = 0u, lose_i = 0xFFFFFFFFu;
+            bool filter = false;
+            if constexpr (kProof) proof_children(kids, first, n, lane, pb, lose_i, filter);
             const double sqrt_n = sqrt(static_cast<double>(stat[node].x + static_cast<uint32_t>(inflight[node])));
             double best_score = -1.0;
             uint32_t best_i = 0xFFFFFFFFu;
-            for (uint32_t i = lane; i < n; i += 64) {
+            int j = 0;
+            for (uint32_t i = lane; i < n; i += 64, ++j) {
+                if constexpr (kProof) { if (filter && ((pb >> (2 * j)) & 3u) == GMK_AZ_PROOF_WINS) continue; }
                 const uint2 cs = stat[first + i];
                 const uint32_t v_i = inflight[first + i];
                 const double q = static_cast<double>(__uint_as_float(cs.y));
@@ -316,6 +440,7 @@ void az_select_leaves_kernel(AzTree t, AzLeaves lv, float* out_states) {
             }
             best_i = __shfl(best_i, 0);
             if (best_i == 0xFFFFFFFFu) best_i = 0;
+            if constexpr (kProof) { if (lose_i != 0xFFFFFFFFu) best_i = lose_i; }
             node = first + best_i;
             const uint32_t cell = (kids[node].y >> 8) & 0xFFu;
             if (lane == 0) s_rows[cell / 15] |= 1u << (cell % 15 + ((stones & 1) ? 16 : 0));
@@ -327,15 +452,24 @@ void az_select_leaves_kernel(AzTree t, AzLeaves lv, float* out_states) {
         // ---- Board::checkGameEnd, as az_select_kernel ----
         bool ended = false;
         int winner = 0;
-        if (stones > 0 && last < 225u) {
+        if (stopped == GMK_AZ_PROOF_NONE && stones > 0 && last < 225u) {
             const int mover_white = (stones - 1) & 1;
             if (five_through<1>(s_rows, last % 15, last / 15, mover_white ? 16 : 0)) { ended = true; winner = mover_white ? -1 : 1; }
         }
         if (!ended && stones == kCells) ended = true;
         bool collided = false;
-        if (ended) {
+        if (kProof && stopped != GMK_AZ_PROOF_NONE) {            // the value is known: as a game that is over at the leaf
+            if (lane == 0) { backup(stat, parent, node, stopped == GMK_AZ_PROOF_LOSES ? 1.0f : -1.0f); hdr->proof_stops += 1u; }
+            --quota;
+        } else if (ended) {
             const int node_player = (stones & 1) ? 1 : -1;
             if (lane == 0) backup(stat, parent, node, static_cast<float>(node_player * winner));
+            if constexpr (kProof) {
+                if (winner != 0) {                               // a five: the side to move at the node has lost
+                    const uint32_t proved = az_prove(t.kids + arena, parent, node, GMK_AZ_PROOF_LOSES, stones, lane);
+                    if (lane == 0) hdr->proof_proved += proved;
+                }
+            }
             --quota;
         } else if (inflight[node] != 0) {
             collided = true;
@@ -372,7 +506,7 @@ void az_select_leaves_kernel(AzTree t, AzLeaves lv, float* out_states) {
     if (lane == 0) { hdr->quota = quota; hdr->n_pending = static_cast<uint32_t>(k); hdr->leaf_pending = 0; }
 }
 
-template <bool kVcf>
+template <bool kVcf, bool kProof>
 __global__ __launch_bounds__(64)
 void az_expand_leaves_kernel(AzTree t, AzLeaves lv, const float* values, const float* probs, AzVcf vc) {
     const int game = blockIdx.x, lane = threadIdx.x;
@@ -434,6 +568,13 @@ void az_expand_leaves_kernel(AzTree t, AzLeaves lv, const float* values, const f
             }
         }
         __threadfence_block();
+        if constexpr (kProof) {
+            __syncthreads();                                     // the leaf's new kids word, before the 64 lanes read it
+            if (win && total > 0 && !dropped) {
+                const uint32_t proved = az_prove(t.kids + arena, t.parent + arena, leaf, GMK_AZ_PROOF_WINS, static_cast<int>(pend[k].stones), lane);
+                if (lane == 0) hdr->proof_proved += proved;
+            }
+        }
         if (lane == 0) {
             if (!dropped) backup(t.stat + arena, t.parent + arena, leaf, win ? -1.0f : -values[row0 + k]);
             for (uint32_t up = leaf; up != kNoNode; up = t.parent[arena + up]) inflight[up] = static_cast<uint16_t>(inflight[up] - 1u);
@@ -640,6 +781,8 @@ __device__ void az_keep_subtree(const AzTree& t, const AzArena& b, size_t base, 
     if (lane == 0) hdr.n_nodes = next;
 }
 
+// kProof (here, in az_advance_kernel and in az_root_choice_kernel): where the kernel chooses, proof_choice has the last word
+template <bool kProof>
 __global__ __launch_bounds__(64)
 void az_step_kernel(AzTree t, AzArena b, const int16_t* forced) {
     const int game = blockIdx.x, lane = threadIdx.x;
@@ -661,6 +804,7 @@ void az_step_kernel(AzTree t, AzArena b, const int16_t* forced) {
     }
     best_v = __shfl(best_v, 0);
     best_i = __shfl(best_i, 0);
+    if constexpr (kProof) { if (want < 0) proof_choice(t.kids + base, t.stat + base, first, n, lane, best_v, best_i); }
     const bool found = best_v != 0u;
     const uint32_t stones = hdr.stones;
     const uint32_t cell = found ? (t.kids[base + first + best_i].y >> 8) & 0xFFu : static_cast<uint32_t>(want);
@@ -690,6 +834,7 @@ void az_step_kernel(AzTree t, AzArena b, const int16_t* forced) {
 // game goes on, and the tree is re-rooted: the child's subtree into the other arena (reuse) or a new root.  A root without a visited
 // child ends the game where it stands.  Finished games leave a childless root behind in both arenas, so that no kernel ever walks a
 // stale tree.  One wavefront per game.
+template <bool kProof>
 __global__ __launch_bounds__(64)
 void az_advance_kernel(AzTree t, AzArena b, uint8_t* __restrict__ rec_moves, uint16_t* __restrict__ rec_visits, int32_t* __restrict__ rec_lens,
                        int8_t* __restrict__ rec_winner, int32_t* __restrict__ unfinished, int reuse, AzSlots sl) {
@@ -716,6 +861,7 @@ void az_advance_kernel(AzTree t, AzArena b, uint8_t* __restrict__ rec_moves, uin
     }
     best_v = __shfl(best_v, 0);
     best_i = __shfl(best_i, 0);
+    if constexpr (kProof) proof_choice(t.kids + base, t.stat + base, first, n, lane, best_v, best_i);
     const uint32_t stones = hdr.stones;
     const int len = rec_lens[game];
     bool over = best_v == 0u || stones >= 225u || len >= 225;    // nothing the search wants to play
@@ -867,6 +1013,7 @@ void az_root_noise_kernel(AzTree t, const int32_t* __restrict__ slot_game, const
 // The cell MCTS::stepForward() would play for every game, left ON THE DEVICE for the match referee (match_kernel.hip): the most visited root
 // child, first maximum in child (= cell) order, exactly az_advance_kernel's choice; -1 for a root without a visited child.  visits (may be
 // null): the root children's visit counts by cell, saturated like the records' rows.  One wavefront per game.
+template <bool kProof>
 __global__ __launch_bounds__(64)
 void az_root_choice_kernel(AzTree t, int16_t* __restrict__ cells, uint16_t* __restrict__ visits) {
     const int game = blockIdx.x, lane = threadIdx.x;
@@ -883,6 +1030,7 @@ void az_root_choice_kernel(AzTree t, int16_t* __restrict__ cells, uint16_t* __re
         const uint32_t ov = __shfl_down(best_v, s), oi = __shfl_down(best_i, s);
         if (ov > best_v || (ov == best_v && ov != 0u && oi < best_i)) { best_v = ov; best_i = oi; }
     }
+    if constexpr (kProof) proof_choice(t.kids + base, t.stat + base, first, n, lane, best_v, best_i);
     if (lane == 0) cells[game] = best_v == 0u ? static_cast<int16_t>(-1) : static_cast<int16_t>((t.kids[base + first + best_i].y >> 8) & 0xFFu);
     if (visits) {
         uint16_t* rv = visits + static_cast<size_t>(game) * kCells;
@@ -981,6 +1129,23 @@ void az_root_stats_kernel(AzTree t, uint32_t* visits, float* values, float* prio
     }
 }
 
+// K7 + proofs: the root's proof and its children's by cell (0 where there is no child)
+__global__ __launch_bounds__(64)
+void az_root_proofs_kernel(AzTree t, int8_t* __restrict__ root, int8_t* __restrict__ children) {
+    const int game = blockIdx.x, lane = threadIdx.x;
+    if (game >= t.n_games) return;
+    const size_t arena = static_cast<size_t>(game) * t.cap;
+    const uint2 k = t.kids[arena];
+    int8_t* out = children + static_cast<size_t>(game) * kCells;
+    for (int i = lane; i < kCells; i += 64) out[i] = 0;
+    __syncthreads();
+    for (uint32_t i = lane; i < (k.y & 0xFFu); i += 64) {
+        const uint32_t ky = t.kids[arena + k.x + i].y;
+        out[(ky >> 8) & 0xFFu] = static_cast<int8_t>(proof_of(ky));
+    }
+    if (lane == 0) root[game] = static_cast<int8_t>(proof_of(k.y));
+}
+
 }  // namespace
 
 struct gmk_az {
@@ -1004,6 +1169,7 @@ struct gmk_az {
     bool select_issued = false;                                  // L > 1: gmk_az_select has marked its leaves, gmk_az_expand has not answered yet
     bool leaf_waiting = false;                                   // any L: a gmk_az_select has not been answered yet (asked by the GMK_OPT_AZ_VCF_* options only)
     AzVcf vcf{nullptr, 0, 64u};                                  // GMK_OPT_AZ_VCF_DEPTH / _BUDGET; the verdict buffer comes with the first D > 0
+    bool proof = false;                                          // GMK_OPT_AZ_PROOF: the <true> proof instantiations are launched
     // device scratch of the host-driven form (gmk_az_select_host / gmk_az_expand_host)
     float *h_states = nullptr, *h_values = nullptr, *h_probs = nullptr;
     int16_t* h_paths = nullptr;
@@ -1060,6 +1226,7 @@ static bool az_marks_up(const gmk_az* a, const char* who) {
 // the host-driven entries serve one leaf per game, evaluated by the host alone
 static bool az_many_leaves(const gmk_az* a, const char* who) {
     if (a->vcf.max_depth > 0) { gmk::set_error("%s: the host-driven form does not solve its leaves (GMK_OPT_AZ_VCF_DEPTH = %d)", who, a->vcf.max_depth); return true; }
+    if (a->proof) { gmk::set_error("%s: the host-driven form does not carry proofs (GMK_OPT_AZ_PROOF = 1)", who); return true; }
     if (a->lv.leaves > 1) { gmk::set_error("%s: the host-driven form takes one leaf per step (GMK_OPT_AZ_LEAVES = %d)", who, a->lv.leaves); return true; }
     return false;
 }
@@ -1192,12 +1359,14 @@ extern "C" int gmk_az_select(gmk_az* a, float* d_states, void* stream) {
     if (!a->rooted) { gmk::set_error("gmk_az_select: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
     if (a->lv.leaves > 1) {                                      // d_states has gmk_az_live_games x L rows
         if (az_marks_up(a, "gmk_az_select")) return GMK_ERR_STATE;
-        hipLaunchKernelGGL(az_select_leaves_kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_states);
+        if (a->proof) hipLaunchKernelGGL(az_select_leaves_kernel<true>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_states);
+        else hipLaunchKernelGGL(az_select_leaves_kernel<false>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_states);
         GMK_HIP_CHECK(hipGetLastError());
         a->select_issued = true;
         return az_vcf_leaves(a, stream);
     }
-    hipLaunchKernelGGL(az_select_kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_states);
+    if (a->proof) hipLaunchKernelGGL(az_select_kernel<true>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_states);
+    else hipLaunchKernelGGL(az_select_kernel<false>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_states);
     GMK_HIP_CHECK(hipGetLastError());
     return az_vcf_leaves(a, stream);
 }
@@ -1206,15 +1375,18 @@ extern "C" int gmk_az_expand(gmk_az* a, const float* d_values, const float* d_pr
     if (!a || !d_values || !d_probs) { gmk::set_error("gmk_az_expand: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_expand: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
     if (a->lv.leaves > 1) {                                      // d_values and d_probs have gmk_az_live_games x L rows
-        if (a->vcf.max_depth > 0) hipLaunchKernelGGL(az_expand_leaves_kernel<true>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf);
-        else hipLaunchKernelGGL(az_expand_leaves_kernel<false>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf);
+        // proofs start in the expand kernels only at a leaf answered WIN: without the solver the proof option launches what it launches when off
+        if (a->vcf.max_depth > 0 && a->proof) hipLaunchKernelGGL((az_expand_leaves_kernel<true, true>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf);
+        else if (a->vcf.max_depth > 0) hipLaunchKernelGGL((az_expand_leaves_kernel<true, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf);
+        else hipLaunchKernelGGL((az_expand_leaves_kernel<false, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf);
         GMK_HIP_CHECK(hipGetLastError());
         a->select_issued = false;
         a->leaf_waiting = false;
         return GMK_OK;
     }
-    if (a->vcf.max_depth > 0) hipLaunchKernelGGL(az_expand_kernel<true>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf);
-    else hipLaunchKernelGGL(az_expand_kernel<false>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf);
+    if (a->vcf.max_depth > 0 && a->proof) hipLaunchKernelGGL((az_expand_kernel<true, true>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf);
+    else if (a->vcf.max_depth > 0) hipLaunchKernelGGL((az_expand_kernel<true, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf);
+    else hipLaunchKernelGGL((az_expand_kernel<false, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf);
     GMK_HIP_CHECK(hipGetLastError());
     a->leaf_waiting = false;
     return GMK_OK;
@@ -1273,7 +1445,8 @@ extern "C" int gmk_az_step(gmk_az* a, const int16_t* h_moves) {
     if (const int rc = az_second_arena(a); rc != GMK_OK) return rc;
     GMK_HIP_CHECK(hipDeviceSynchronize());
     if (h_moves) GMK_HIP_CHECK(hipMemcpy(a->d_forced, h_moves, n * 2, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(az_step_kernel, dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, a->other, h_moves ? a->d_forced : nullptr);
+    if (a->proof) hipLaunchKernelGGL(az_step_kernel<true>, dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, a->other, h_moves ? a->d_forced : nullptr);
+    else hipLaunchKernelGGL(az_step_kernel<false>, dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, a->other, h_moves ? a->d_forced : nullptr);
     GMK_HIP_CHECK(hipGetLastError());
     GMK_HIP_CHECK(hipDeviceSynchronize());
     std::swap(a->t.stat, a->other.stat); std::swap(a->t.kids, a->other.kids); std::swap(a->t.prior, a->other.prior); std::swap(a->t.parent, a->other.parent);
@@ -1283,7 +1456,8 @@ extern "C" int gmk_az_step(gmk_az* a, const int16_t* h_moves) {
 extern "C" int gmk_az_root_choice(gmk_az* a, int16_t* d_cells, uint16_t* d_visits, void* stream) {
     if (!a || !d_cells) { gmk::set_error("gmk_az_root_choice: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_root_choice: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
-    hipLaunchKernelGGL(az_root_choice_kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_cells, d_visits);
+    if (a->proof) hipLaunchKernelGGL(az_root_choice_kernel<true>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_cells, d_visits);
+    else hipLaunchKernelGGL(az_root_choice_kernel<false>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_cells, d_visits);
     GMK_HIP_CHECK(hipGetLastError());
     return GMK_OK;
 }
@@ -1320,7 +1494,8 @@ extern "C" int gmk_az_advance(gmk_az* a, uint8_t* d_moves, uint16_t* d_visits, i
     if (!a->d_unfinished) GMK_HIP_CHECK(gmk::device_malloc(&a->d_unfinished, 4));
     hipStream_t s = static_cast<hipStream_t>(stream);
     GMK_HIP_CHECK(hipMemsetAsync(a->d_unfinished, 0, 4, s));
-    hipLaunchKernelGGL(az_advance_kernel, dim3(a->t.n_games), dim3(64), 0, s, a->t, a->other, d_moves, d_visits, d_lens, d_winner, a->d_unfinished, reuse_subtree ? 1 : 0, a->slots);
+    if (a->proof) hipLaunchKernelGGL(az_advance_kernel<true>, dim3(a->t.n_games), dim3(64), 0, s, a->t, a->other, d_moves, d_visits, d_lens, d_winner, a->d_unfinished, reuse_subtree ? 1 : 0, a->slots);
+    else hipLaunchKernelGGL(az_advance_kernel<false>, dim3(a->t.n_games), dim3(64), 0, s, a->t, a->other, d_moves, d_visits, d_lens, d_winner, a->d_unfinished, reuse_subtree ? 1 : 0, a->slots);
     GMK_HIP_CHECK(hipGetLastError());
     int32_t unfinished = 0;
     GMK_HIP_CHECK(hipMemcpyAsync(&unfinished, a->d_unfinished, 4, hipMemcpyDeviceToHost, s));
@@ -1370,6 +1545,11 @@ extern "C" int gmk_az_set_option(gmk_az* a, int option, int value) {
             GMK_HIP_CHECK(hipMemcpy(a->vcf.verdict, none.data(), rows * sizeof(int4), hipMemcpyHostToDevice));
         }
         a->vcf.max_depth = value;
+        return GMK_OK;
+    }
+    if (a && option == GMK_OPT_AZ_PROOF && (value == 0 || value == 1)) {
+        if (a->leaf_waiting) { gmk::set_error("gmk_az_set_option: gmk_az_select is waiting for its gmk_az_expand; GMK_OPT_AZ_PROOF changes how it is answered"); return GMK_ERR_STATE; }
+        a->proof = value == 1;                                   // the bits stay where they are: facts about positions, ignored while the option is off
         return GMK_OK;
     }
     if (a && option == GMK_OPT_NOISE_SAMPLER && (value == GMK_NOISE_SAMPLER_STD || value == GMK_NOISE_SAMPLER_COUNTER)) { a->noise_sampler = value; return GMK_OK; }
@@ -1577,7 +1757,7 @@ extern "C" int gmk_az_expand_stages_host(gmk_az* a, const float* h_values, const
     if (h_values) GMK_HIP_CHECK(hipMemcpy(a->h_values, h_values, static_cast<size_t>(a->t.n_games) * 4, hipMemcpyHostToDevice));
     if (h_probs) GMK_HIP_CHECK(hipMemcpy(a->h_probs, h_probs, static_cast<size_t>(a->t.n_games) * 225 * 4, hipMemcpyHostToDevice));
     else GMK_HIP_CHECK(hipMemset(a->h_probs, 0, static_cast<size_t>(a->t.n_games) * 225 * 4));
-    hipLaunchKernelGGL(az_expand_kernel<false>, dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, a->h_values, a->h_probs, (do_expand ? 1 : 0) | (do_backup ? 2 : 0), a->vcf);
+    hipLaunchKernelGGL((az_expand_kernel<false, false>), dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, a->h_values, a->h_probs, (do_expand ? 1 : 0) | (do_backup ? 2 : 0), a->vcf);
     GMK_HIP_CHECK(hipGetLastError());
     a->leaf_waiting = false;
     GMK_HIP_CHECK(hipDeviceSynchronize());
@@ -1676,6 +1856,40 @@ extern "C" int gmk_az_vcf_verdicts_host(gmk_az* a, int32_t* h_status, int32_t* h
         if (h_move) h_move[r] = v[r].y;
         if (h_length) h_length[r] = v[r].z;
         if (h_nodes) h_nodes[r] = static_cast<uint32_t>(v[r].w);
+    }
+    return GMK_OK;
+}
+
+// ---- K7 + proofs: the read-outs ----
+extern "C" int gmk_az_root_proofs(gmk_az* a, int8_t* h_root, int8_t* h_children) {
+    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    if (!a) { gmk::set_error("gmk_az_root_proofs: bad arguments"); return GMK_ERR_ARG; }
+    if (!a->rooted) { gmk::set_error("gmk_az_root_proofs: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
+    const size_t n = static_cast<size_t>(a->t.n_games);
+    int8_t* d_out = nullptr;
+    GMK_HIP_CHECK(hipDeviceSynchronize());
+    GMK_HIP_CHECK(gmk::device_malloc(&d_out, n * 226));
+    hipLaunchKernelGGL(az_root_proofs_kernel, dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, d_out + n * 225, d_out);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess && h_children) e = hipMemcpy(h_children, d_out, n * 225, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && h_root) e = hipMemcpy(h_root, d_out + n * 225, n, hipMemcpyDeviceToHost);
+    (void)gmk::device_free(d_out);
+    GMK_HIP_CHECK(e);
+    return GMK_OK;
+}
+
+extern "C" int gmk_az_proof_stats(gmk_az* a, uint32_t* h_proved, uint32_t* h_stops) {
+    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    if (!a) { gmk::set_error("gmk_az_proof_stats: bad arguments"); return GMK_ERR_ARG; }
+    if (!a->rooted) { gmk::set_error("gmk_az_proof_stats: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
+    const size_t n = static_cast<size_t>(a->t.n_games);
+    std::vector<AzHeader> hdr(n);
+    GMK_HIP_CHECK(hipDeviceSynchronize());
+    GMK_HIP_CHECK(hipMemcpy(hdr.data(), a->t.hdr, n * sizeof(AzHeader), hipMemcpyDeviceToHost));
+    for (size_t g = 0; g < n; ++g) {
+        if (h_proved) h_proved[g] = hdr[g].proof_proved;
+        if (h_stops) h_stops[g] = hdr[g].proof_stops;
     }
     return GMK_OK;
 }

@@ -479,9 +479,23 @@ def _vcf_options(vcf):
     return {"vcf_depth": int(depth), "vcf_budget": int(budget)}
 
 
+def _root_choice(visits, proofs=None):
+    """The cell every game plays from its root's visit counts [n, 225] (-1: none): the most visited child, first maximum in cell order
+    (MCTS::stepForward()'s max_element).  proofs int8[n, 225] (lib.AlphaZeroMCTS.root_proofs()["children"]): the root-choice rule of "K7 + proofs",
+    as the kernels apply it -- the first child that is a proven loss for its mover; otherwise the most visited child that is not a proven win
+    for its mover and has a visit; otherwise the rule above."""
+    best = np.where(visits.max(1) > 0, visits.argmax(1), -1)
+    if proofs is not None:
+        unproven = np.where(proofs == G.AZ_PROOF_WINS, 0, visits)
+        best = np.where(unproven.max(1) > 0, unproven.argmax(1), best)
+        loses = proofs == G.AZ_PROOF_LOSES
+        best = np.where(loses.any(1), loses.argmax(1), best)
+    return best
+
+
 def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, first_game_id=0, opening_plies=0, max_moves=N,
                        device=None, node_capacity=None, reuse_subtree=True, root_noise=(0.05, 0.25), slots=None, device_loop=True, noise_sampler="counter", leaves=1,
-                       vcf=None):
+                       vcf=None, proof=False):
     """n_games complete games of the network-guided searcher against itself (agents/alphazero.py:5-9 on both sides: the
     reference's AlphaZero self-play), all games in lock step on the current GPU: every move = `playouts` lock-step playouts of
     K7 with `network(states [n,6,15,15]) -> (value [n], probs [n,225])` at the leaves (network.FusedPolicyValueNetwork = K9),
@@ -494,7 +508,8 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
     tests that compare the two.  leaves > 1: every search step takes up to that many leaves from each game, with virtual loss
     (lib.AlphaZeroMCTS(leaves=)): the network's batch is live games x leaves rows and a move takes about playouts / leaves steps; the games differ
     from those of leaves = 1, and are the same games on every loop of this function.  vcf = (depth, budget): the searches solve forced wins by
-    fours at their leaves (lib.AlphaZeroMCTS(vcf_depth=, vcf_budget=)); None: they do not.  Returns GameRecords like play_games."""
+    fours at their leaves (lib.AlphaZeroMCTS(vcf_depth=, vcf_budget=)); None: they do not.  proof: the searches carry proven wins and losses up
+    their trees and every loop chooses its moves by them (lib.AlphaZeroMCTS(proof=), _root_choice).  Returns GameRecords like play_games."""
     if slots is not None and slots < n_games and (max_moves < N or (device_loop and opening_plies > 8)):
         # (the slot loops play whole games, the device-resident one from openings of at most 8 plies -- gmk_az_set_slots' limit: say so instead of
         # ignoring the cap or failing inside the library; ADVICE r3)
@@ -511,7 +526,7 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
             games.open_with(m, l, opening_plies)
         slots = int(slots)
         cap = node_capacity if node_capacity is not None else min((3 if reuse_subtree else 1) * playouts * N + 1, (1 << 24) - 1)
-        tree = G.AlphaZeroMCTS(slots, node_capacity=cap, c_puct=c_puct, leaves=leaves, **_vcf_options(vcf))
+        tree = G.AlphaZeroMCTS(slots, node_capacity=cap, c_puct=c_puct, leaves=leaves, proof=proof, **_vcf_options(vcf))
         tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS[noise_sampler])
         tree.set_slots(n_games, games.moves[:, :max(int(games.lens.max()), 1)], games.lens)
         d_moves, d_lens = torch.from_numpy(games.moves).to(dev), torch.from_numpy(games.lens).to(dev)
@@ -536,7 +551,7 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
             games.open_with(m, l, opening_plies)
         visits = np.zeros((n_games, N, N), dtype=np.uint16)
         slots = int(slots)
-        tree = G.AlphaZeroMCTS(slots, node_capacity=node_capacity if node_capacity is not None else min(playouts * N + 1, (1 << 24) - 1), c_puct=c_puct, leaves=leaves, **_vcf_options(vcf))
+        tree = G.AlphaZeroMCTS(slots, node_capacity=node_capacity if node_capacity is not None else min(playouts * N + 1, (1 << 24) - 1), c_puct=c_puct, leaves=leaves, proof=proof, **_vcf_options(vcf))
         active, next_game, overflow = np.arange(slots), slots, False
         with torch.no_grad():
             for _ in range((n_games // slots + 2) * N):
@@ -557,7 +572,7 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
                 st = tree.root_stats()
                 overflow |= bool((st["status"] & G.AlphaZeroMCTS.STATUS_ARENA_FULL).any())
                 visited = st["visits"].max(1) > 0
-                best = np.where(games.over[active] | ~visited, -1, st["visits"].argmax(1))
+                best = np.where(games.over[active] | ~visited, -1, _root_choice(st["visits"], tree.root_proofs()["children"] if proof else None))
                 games.over[active[(best < 0) & ~games.over[active]]] = True
                 played = np.full(n_games, -1, dtype=np.int64)
                 played[active] = best
@@ -574,7 +589,7 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
         m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
         games.open_with(m, l, opening_plies)
     cap = node_capacity if node_capacity is not None else min((3 if reuse_subtree else 1) * playouts * N + 1, (1 << 24) - 1)
-    tree = G.AlphaZeroMCTS(n_games, node_capacity=cap, c_puct=c_puct, leaves=leaves, **_vcf_options(vcf))
+    tree = G.AlphaZeroMCTS(n_games, node_capacity=cap, c_puct=c_puct, leaves=leaves, proof=proof, **_vcf_options(vcf))
     tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS[noise_sampler])
     tree.set_roots(G.moves_to_planes(games.moves, games.lens), games.last_two())
     if device_loop:
@@ -605,7 +620,7 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
             st = tree.root_stats()
             overflow |= bool((st["status"] & G.AlphaZeroMCTS.STATUS_ARENA_FULL).any())
             visited = st["visits"].max(1) > 0                    # no child was visited: nothing to play (cannot happen on a live board)
-            played = np.where(games.over | ~visited, -1, st["visits"].argmax(1)).astype(np.int16)      # max_element: the first maximum in child (= cell) order
+            played = np.where(games.over | ~visited, -1, _root_choice(st["visits"], tree.root_proofs()["children"] if proof else None)).astype(np.int16)
             games.over |= played < 0
             at = games.lens.copy()
             moved = games.apply(played)
@@ -776,7 +791,7 @@ class _EvalOpponent:
 
 
 def play_evaluation_games(n_games, network, opponent, playouts=400, c_puct=5.0, seed=G.DEFAULT_SEED, first_game_id=0, opening_plies=0, max_moves=N,
-                          reuse_subtree=True, root_noise=(0.05, 0.25), device_loop=None, device=None, leaves=1, vcf=None):
+                          reuse_subtree=True, root_noise=(0.05, 0.25), device_loop=None, device=None, leaves=1, vcf=None, proof=False):
     """The reference's evaluation match (network/train.py:88-126 evaluate_network -> agents/utils.py:66-100 eval_agents): n_games games of the
     network-guided searcher (K7 with `network` = network.FusedPolicyValueNetwork at the leaves, `playouts` playouts a move) against
     `opponent` = (name, kwargs) as in DATA_CONFIG["schedule"] ("traditional_mcts" -- with {"use_rave": True} TraditionalPolicy + RAVE --,
@@ -792,7 +807,8 @@ def play_evaluation_games(n_games, network, opponent, playouts=400, c_puct=5.0, 
     leaves > 1: the network's searches take up to that many leaves per game per step, with virtual loss (lib.AlphaZeroMCTS(leaves=)) -- a
     match has few games, so this is what fills the network's batch; both loops play the same games.
     vcf = (depth, budget): the network's searches -- not the opponent's -- solve forced wins by fours at their leaves
-    (lib.AlphaZeroMCTS(vcf_depth=, vcf_budget=)); None: they do not.
+    (lib.AlphaZeroMCTS(vcf_depth=, vcf_budget=)); None: they do not.  proof: they carry proven wins and losses up their trees, and the
+    network's moves are chosen by them on both loops (lib.AlphaZeroMCTS(proof=)).
     Returns (GameRecords, network_is_black bool[n], scores float[n]); the records' visit counts at move i are the mover's, and
     records.groups lists per group the games, the unfinished count and the K7 handle's live games after the loop."""
     kind = opponent[0]
@@ -827,7 +843,7 @@ def play_evaluation_games(n_games, network, opponent, playouts=400, c_puct=5.0, 
         if k == 0:
             groups.append({"games": idx, "unfinished": 0, "live_games": 0})
             continue
-        net = G.AlphaZeroMCTS(k, node_capacity=net_cap, c_puct=c_puct, leaves=leaves, **_vcf_options(vcf))
+        net = G.AlphaZeroMCTS(k, node_capacity=net_cap, c_puct=c_puct, leaves=leaves, proof=proof, **_vcf_options(vcf))
         net.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS["counter"])
         net.set_game_ids(np.asarray(idx, dtype=np.uint32))
         net.set_roots(G.moves_to_planes(games.moves[idx], games.lens[idx]), games.last_two()[idx])
@@ -868,7 +884,7 @@ def play_evaluation_games(n_games, network, opponent, playouts=400, c_puct=5.0, 
                         net.search(network, playouts)
                         st = net.root_stats()
                         overflow |= bool((st["status"] & G.AlphaZeroMCTS.STATUS_ARENA_FULL).any())
-                        v, best = st["visits"], np.where(st["visits"].max(1) > 0, st["visits"].argmax(1), -1)      # max_element: the first maximum in cell order
+                        v, best = st["visits"], _root_choice(st["visits"], net.root_proofs()["children"] if proof else None)
                     elif opp.tree is None:
                         v, best, full = opp.searcher.search(games.moves[idx], games.lens[idx], idx, stream)
                         overflow |= full

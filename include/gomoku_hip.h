@@ -205,7 +205,8 @@ int gmk_mcts_add_root_noise(gmk_mcts *m, float alpha, float epsilon, void *strea
  * GMK_OPT_LOCKSTEP: 1 = gmk_selfplay_run / gmk_trad_selfplay_run alternate search and step launches even where one persistent launch could play
  *   the games (the second form the tests hold the persistent one to); 0 (default) = persistent wherever the configuration allows. */
 enum { GMK_OPT_NOISE_SAMPLER = 1, GMK_OPT_LOCKSTEP = 2, GMK_OPT_AZ_LEAVES = 3 /* K7 only: see gmk_az_set_option */,
-       GMK_OPT_AZ_VCF_DEPTH = 4, GMK_OPT_AZ_VCF_BUDGET = 5 /* K7 only: see "K7 + K14" */ };
+       GMK_OPT_AZ_VCF_DEPTH = 4, GMK_OPT_AZ_VCF_BUDGET = 5 /* K7 only: see "K7 + K14" */,
+       GMK_OPT_AZ_PROOF = 6 /* K7 only: see "K7 + proofs" */ };
 #define GMK_AZ_MAX_LEAVES 8
 enum { GMK_NOISE_SAMPLER_STD = 0, GMK_NOISE_SAMPLER_COUNTER = 1 };
 int gmk_mcts_set_option(gmk_mcts *m, int option, int value);
@@ -584,6 +585,42 @@ int gmk_az_root_stats(gmk_az* a, uint32_t* h_visits, float* h_values, float* h_p
  * GMK_ERR_STATE on a handle whose D > 0, as they do when L > 1. */
 int gmk_az_vcf_stats(gmk_az* a, uint32_t* h_leaves, uint32_t* h_wins, uint32_t* h_cut, uint64_t* h_nodes);
 int gmk_az_vcf_verdicts_host(gmk_az* a, int32_t* h_status, int32_t* h_move, int32_t* h_length, uint32_t* h_nodes);
+/* ---- K7 + proofs: proven wins and losses carried up the tree (MCTS-Solver, Winands et al. 2008) ----
+ * GMK_OPT_AZ_PROOF of gmk_az_set_option: 0 (default) or 1, anything else GMK_ERR_ARG; GMK_ERR_STATE while the marks are up (L > 1) or a
+ * gmk_az_select waits for its gmk_az_expand.  With 0 every entry launches exactly the kernels it launches without this block.
+ * A node carries a proof in bits 16..17 of its child word (no memory of its own; the bits travel through re-rooting with the word):
+ *     GMK_AZ_PROOF_NONE  = 0   no proof
+ *     GMK_AZ_PROOF_WINS  = 1   the side to move at the node has a forced win
+ *     GMK_AZ_PROOF_LOSES = 2   the side to move at the node loses against every move
+ * A node whose last stone completed a five is LOSES.  A full board is not a proof.  Switching the option off leaves the bits where they are and
+ * the off-path ignores them; they are facts about positions, so switching it on again may use them.  gmk_az_set_roots, gmk_az_set_slots, a slot
+ * refilled by gmk_az_advance and every fresh root start with NONE.
+ * prove(X, s), run by the game's own wavefront; stones(X) = the stone count of X's position:
+ *     1. if X already has a proof, stop          2. proof(X) = s, and the game's `proved` counter + 1
+ *     3. P = X's parent; none: stop              4. s == LOSES: prove(P, WINS)
+ *     5. s == WINS: prove(P, LOSES) only when children(P) == 225 - stones(P) (Default::Expand dropped no free cell for a zero probability)
+ *        and every child of P is WINS; otherwise stop
+ * Proofs start (a) in gmk_az_select, at a descent that ends at a terminal node with a five: prove(node, LOSES), the +1 backed up as before;
+ * (b) in gmk_az_expand, at a pending leaf whose "K7 + K14" verdict is WIN and whose child was created (not dropped by a full arena):
+ * prove(leaf, WINS), the -1.0f backup and the one-hot child as before.  (b) needs GMK_OPT_AZ_VCF_DEPTH > 0; without it only (a) starts proofs.
+ * Descent (every descent of a step, any L).  On arriving at a node that is not the root and has a proof, before its children are read, the
+ * descent ends: +1.0f is backed up from it for LOSES, -1.0f for WINS, and the game's `stops` counter + 1.  With L > 1 this is the "game is
+ * over at the leaf" case (quota - 1, no mark, no row, no collision test); with L = 1 nothing is pending and the game's row is zeros.  The root
+ * always descends.  Among the children of a node: if any is LOSES the first such in child order (ascending cell) is taken; otherwise children
+ * marked WINS are left out of the PUCB maximum unless all are marked, then none is.  The expression, the double arithmetic, the strict '>' from
+ * -1.0 (nothing beats it: the first child, marked or not) and the virtual-loss terms are as they are.
+ * Root choice (gmk_az_advance, gmk_az_root_choice, and gmk_az_step for a game whose move is not forced; gmk_az_step_device chooses nothing):
+ *     1. the first child marked LOSES, if there is one
+ *     2. otherwise the most visited child among those not marked WINS that have at least one visit, first maximum in cell order
+ *     3. otherwise the old rule
+ * The recorded visit rows and gmk_az_root_stats are the raw counts, unchanged.
+ * gmk_az_root_proofs: the root's proof int8[n_games] and its children's by cell int8[n_games][225], 0 where there is no child; either may be
+ *   NULL.  gmk_az_proof_stats: per game, uint32[n_games] each, either may be NULL: nodes given a proof, and descents ended at a node already
+ *   proven; cleared where the "K7 + K14" counters are cleared.  Both synchronise.
+ * The host-driven one-leaf entries that refuse a handle whose D > 0 refuse one whose GMK_OPT_AZ_PROOF is 1 in the same way. */
+enum { GMK_AZ_PROOF_NONE = 0, GMK_AZ_PROOF_WINS = 1, GMK_AZ_PROOF_LOSES = 2 };
+int gmk_az_root_proofs(gmk_az* a, int8_t* h_root, int8_t* h_children);
+int gmk_az_proof_stats(gmk_az* a, uint32_t* h_proved, uint32_t* h_stops);
 
 /* ---- K12: the referee of a match between two search handles, on the device (match_kernel.hip) ----
  * One ply of n two-agent games without the host in the loop (agents/utils.py:13-63 dual_play, :66-100 eval_agents): the side to move has
