@@ -15,6 +15,9 @@
 // az_select_leaves_kernel / az_expand_leaves_kernel below, for searches of few games.
 // With GMK_OPT_AZ_VCF_DEPTH = D > 0 the pending leaves are also handed to K14's exact solver of forced wins by fours (az_vcf_leaves_kernel, right
 // behind the select kernel), and the expand kernels answer a solved leaf themselves: include/gomoku_hip.h, "K7 + K14".
+// With GMK_OPT_AZ_VCF_DEFEND on top of that and of GMK_OPT_AZ_PROOF the leaves the solver did not answer are asked what the opponent threatens
+// (az_threat_leaves_kernel) and which replies lose to it (az_defend_leaves_kernel, K15's table), and the expand kernels mark those children as the
+// opponent's proven wins: include/gomoku_hip.h, "K7 + K15".
 // Mapping: one wavefront per game, lanes over the (<= 225) children; the tree is an SoA arena per game in HBM.
 #include <algorithm>
 #include <cmath>
@@ -51,9 +54,12 @@ struct AzHeader {                                // 256 B per game, in HBM
     uint32_t pad0;
     unsigned long long vcf_nodes;                //   and the nodes their walks counted
     uint32_t proof_proved, proof_stops;          // K7 + proofs (GMK_OPT_AZ_PROOF): nodes given a proof, descents ended at a node already proven
-    uint32_t pad[14];
+    uint32_t def_threatened, def_marked;         // K7 + K15 (GMK_OPT_AZ_VCF_DEFEND): pending leaves under a WIN threat, children marked WINS
+    unsigned long long def_nodes;                //   the nodes of the cells' full solves
+    uint32_t def_searched;                       //   and the cells solved in full
+    uint32_t pad[9];
 };
-static_assert(sizeof(AzHeader) == 256 && offsetof(AzHeader, vcf_nodes) % 8 == 0, "AzHeader layout");
+static_assert(sizeof(AzHeader) == 256 && offsetof(AzHeader, vcf_nodes) % 8 == 0 && offsetof(AzHeader, def_nodes) % 8 == 0, "AzHeader layout");
 
 struct AzTree {
     AzHeader* hdr;
@@ -91,6 +97,17 @@ __device__ __forceinline__ void count_verdict(AzHeader* hdr, const int4& v) {
     hdr->vcf_cut += (v.x == GMK_VCF_BUDGET || v.x == GMK_VCF_DEPTH) ? 1u : 0u;
     hdr->vcf_nodes += static_cast<uint32_t>(v.w);
 }
+
+// K7 + K15: per row of the leaf batch, written by az_threat_leaves_kernel and az_defend_leaves_kernel and read by the <true, true, true>
+// instantiations of the expand kernels
+struct AzDefend {
+    int4* threat;                                // [n_games * GMK_AZ_MAX_LEAVES] {status, length, nodes, 1 when the leaf was asked}
+    uint8_t* pv;                                 // [rows][GMK_VCF_PV] the threat's line, written for a WIN only
+    uint16_t* occupied;                          // [rows][16] the leaf's stones of either colour per board row (the read-out's)
+    uint32_t* cells;                             // [rows][225] verdict 0..2, "solved in full" 3, nodes 4..: written for the rows under a WIN threat only
+};
+constexpr uint32_t kCellVerdict = 7u, kCellSearched = 8u;
+constexpr int kCellNodesShift = 4;
 
 // ---- K7 + proofs (GMK_OPT_AZ_PROOF; the contract is in include/gomoku_hip.h, "K7 + proofs") ----
 // A node's proof (GMK_AZ_PROOF_*) lives in bits 16..17 of its kids.y word, above the child count and the cell: every reader masks the word, and
@@ -164,6 +181,54 @@ __device__ __forceinline__ void proof_choice(const uint2* kids, const uint2* sta
     }
     if (lose_i != 0xFFFFFFFFu) { best_v = 1u; best_i = lose_i; }
     else if (pv != 0u) { best_v = pv; best_i = pi; }
+}
+
+// K7 + K15 in the expand kernels, called by all 64 lanes for a pending leaf that is not answered WIN, after the leaf's children were written
+// (created: they exist; a leaf whose playout was dropped for a full arena does not get here): the row's threat is WIN -> the game's counters, every child whose
+// cell is GMK_VCF_CELL_LOSES gets GMK_AZ_PROOF_WINS with its own word -- the lane that made the child rewrites it --, and when the leaf has a
+// child for every free cell and all are marked: prove(leaf, LOSES).  Returns whether the leaf was proven LOSES (+1.0f is then backed up).
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v += static_cast<uint32_t>(__shfl_xor(static_cast<int>(v), s));
+    return v;
+}
+__device__ bool az_defend_marks(const AzTree& t, size_t arena, AzHeader* hdr, const AzDefend& df, size_t row, uint32_t leaf, int leaf_stones,
+                                uint32_t first_child, const bool (&take)[4], const int (&rank)[4], int total, bool created, int lane) {
+    const int4 th = df.threat[row];
+    if (th.x != GMK_VCF_WIN || th.w == 0) return false;          // the same in every lane
+    const uint32_t* words = df.cells + row * kCells;
+    uint32_t searched = 0, nodes = 0, marked = 0;
+    bool all = true;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = lane + 64 * j;
+        const uint32_t w = i < kCells ? words[i] : 0u;
+        searched += (w & kCellSearched) ? 1u : 0u;
+        nodes += w >> kCellNodesShift;
+        if (created && take[j]) {
+            if ((w & kCellVerdict) == GMK_VCF_CELL_LOSES) {
+                t.kids[arena + first_child + rank[j]] = make_uint2(0u, (static_cast<uint32_t>(i) << 8) | (static_cast<uint32_t>(GMK_AZ_PROOF_WINS) << kProofShift));
+                ++marked;
+            } else all = false;
+        }
+    }
+    searched = wave_sum(searched);
+    nodes = wave_sum(nodes);
+    marked = wave_sum(marked);
+    if (lane == 0) {
+        hdr->def_threatened += 1u;
+        hdr->def_searched += searched;
+        hdr->def_nodes += nodes;
+        hdr->def_marked += marked;
+        hdr->proof_proved += marked;
+    }
+    if (!created) return false;
+    __threadfence_block();
+    __syncthreads();                                             // the children's words, before prove's ballot reads them one level up
+    if (total != kCells - leaf_stones || __ballot(!all) != 0ull) return false;
+    const uint32_t proved = az_prove(t.kids + arena, t.parent + arena, leaf, GMK_AZ_PROOF_LOSES, leaf_stones, lane);
+    if (lane == 0) hdr->proof_proved += proved;
+    return true;
 }
 
 // kProof (here and in az_select_leaves_kernel): a descent stops at a proven node below the root and backs the exact value up, children marked
@@ -284,9 +349,11 @@ void az_select_kernel(AzTree t, float* __restrict__ out_states) {
 
 // kVcf: the leaf's verdict comes first (GMK_OPT_AZ_VCF_DEPTH > 0) -- on WIN the answer is (1.0f, one-hot(move)) instead of the network's row
 // kProof (with kVcf): a leaf answered WIN whose child was created is proven WINS
-template <bool kVcf, bool kProof>
+// kDefend (with both): the children that lose to the opponent's forced win are marked, and a leaf without a holding reply is proven LOSES
+template <bool kVcf, bool kProof, bool kDefend>
 __global__ __launch_bounds__(64)
-void az_expand_kernel(AzTree t, const float* __restrict__ values, const float* __restrict__ probs, int stages /* bit 0: expand, bit 1: back up */, AzVcf vc) {
+void az_expand_kernel(AzTree t, const float* __restrict__ values, const float* __restrict__ probs, int stages /* bit 0: expand, bit 1: back up */, AzVcf vc,
+                      AzDefend df) {
     const int game = blockIdx.x, lane = threadIdx.x;
     if (game >= t.n_games) return;
     AzHeader* hdr = t.hdr + game;
@@ -347,8 +414,12 @@ void az_expand_kernel(AzTree t, const float* __restrict__ values, const float* _
             if (lane == 0) hdr->proof_proved += proved;
         }
     }
+    bool lost = false;
+    if constexpr (kDefend) {
+        if (!win) lost = az_defend_marks(t, arena, hdr, df, row, leaf, static_cast<int>(hdr->leaf_stones), n_nodes, take, rank, total, total > 0 && (stages & 1), lane);
+    }
     if (lane == 0) {
-        if (stages & 2) backup(t.stat + arena, t.parent + arena, leaf, win ? -1.0f : -values[row]);      // node_value = -state_value (MCTS.cpp:166-168)
+        if (stages & 2) backup(t.stat + arena, t.parent + arena, leaf, lost ? 1.0f : win ? -1.0f : -values[row]);      // node_value = -state_value (MCTS.cpp:166-168)
         hdr->leaf_pending = 0;
     }
 }
@@ -506,9 +577,9 @@ void az_select_leaves_kernel(AzTree t, AzLeaves lv, float* out_states) {
     if (lane == 0) { hdr->quota = quota; hdr->n_pending = static_cast<uint32_t>(k); hdr->leaf_pending = 0; }
 }
 
-template <bool kVcf, bool kProof>
+template <bool kVcf, bool kProof, bool kDefend>
 __global__ __launch_bounds__(64)
-void az_expand_leaves_kernel(AzTree t, AzLeaves lv, const float* values, const float* probs, AzVcf vc) {
+void az_expand_leaves_kernel(AzTree t, AzLeaves lv, const float* values, const float* probs, AzVcf vc, AzDefend df) {
     const int game = blockIdx.x, lane = threadIdx.x;
     if (game >= t.n_games) return;
     AzHeader* hdr = t.hdr + game;
@@ -547,6 +618,7 @@ void az_expand_leaves_kernel(AzTree t, AzLeaves lv, const float* values, const f
             total += __popcll(b);
         }
         bool dropped = false;
+        const uint32_t first_child = n_nodes;
         if (total > 0) {
             if (n_nodes + total > static_cast<uint32_t>(t.cap)) {
                 dropped = full = true;                           // arena full: this playout is dropped, its marks are taken back below
@@ -575,8 +647,12 @@ void az_expand_leaves_kernel(AzTree t, AzLeaves lv, const float* values, const f
                 if (lane == 0) hdr->proof_proved += proved;
             }
         }
+        bool lost = false;
+        if constexpr (kDefend) {
+            if (!win && !dropped) lost = az_defend_marks(t, arena, hdr, df, row0 + static_cast<size_t>(k), leaf, static_cast<int>(pend[k].stones), first_child, take, rank, total, total > 0, lane);
+        }
         if (lane == 0) {
-            if (!dropped) backup(t.stat + arena, t.parent + arena, leaf, win ? -1.0f : -values[row0 + k]);
+            if (!dropped) backup(t.stat + arena, t.parent + arena, leaf, lost ? 1.0f : win ? -1.0f : -values[row0 + k]);
             for (uint32_t up = leaf; up != kNoNode; up = t.parent[arena + up]) inflight[up] = static_cast<uint16_t>(inflight[up] - 1u);
         }
     }
@@ -696,6 +772,336 @@ void az_vcf_leaves_kernel(AzTree t, AzLeaves lv, AzVcf vc) {
             } else {
                 ++nodes;
                 if (f2 >= 0) finish(GMK_VCF_WIN, c, 2);
+                else {
+                    bool fail = t2 >= 0;
+                    if (!fail && depth + 3 > limit) { cut = true; fail = true; }
+                    if (!fail && !child_has) fail = true;
+                    if (!fail) {
+                        stack[depth][lane] = mask | (more ? 0x8000u : 0u) | (static_cast<uint32_t>(c) << 16) | (static_cast<uint32_t>(f1) << 24);
+                        ++depth;
+                        mask = C; more = true; retract = false;
+                    } else if (y == ry) def ^= rbit;
+                }
+            }
+            if (state == V::kRun && retract) {
+                if (y == cy) att ^= cbit;
+                while (!more) {                                    // climb while the level has nothing left
+                    if (depth == 0) { failed(); break; }
+                    --depth;
+                    const uint32_t w = stack[depth][lane];
+                    mask = w & V::kRowMask;
+                    more = (w & 0x8000u) != 0;
+                    const int uc = static_cast<int>((w >> 16) & 255u), ur = static_cast<int>(w >> 24);
+                    if (y == uc / 15) att ^= 1u << (uc % 15);
+                    if (y == ur / 15) def ^= 1u << (ur % 15);
+                }
+            }
+        }
+    }
+}
+
+// ---- K7 + K15: the replies that lose to a forced win by fours, at the pending leaves (GMK_OPT_AZ_VCF_DEFEND; include/gomoku_hip.h "K7 + K15") ----
+// Two further links of gmk_az_select's chain behind az_vcf_leaves_kernel, for a handle whose solver and proofs are on.
+// az_threat_leaves_kernel is that kernel's walk with the colours swapped -- the side that is NOT to move attacks, as if the side to move had
+// passed (K14's GMK_VCF_OPPONENT) -- and the line kept: on WIN every lane writes its four cells of the pv, the levels' (c, r) from the LDS stack
+// and the cells that end the line, as vcf_kernel's finish does.  A row whose own verdict (the kernel before, in stream order) is WIN or OVER,
+// or that has no pending leaf, reads {NONE, 0, 0, not asked}.  Lane y also leaves the leaf's occupied cells of row y for the read-out.
+__global__ __launch_bounds__(64)
+void az_threat_leaves_kernel(AzTree t, AzLeaves lv, AzVcf vc, AzDefend df) {
+    namespace V = gmk::vcf;
+    __shared__ uint32_t stack[V::kLevels][64];                   // as az_vcf_leaves_kernel
+    const int lane = threadIdx.x, y = lane & 15, group = lane >> 4, gbase = lane & 48;
+    const uint32_t board_row = y < 15 ? V::kRowMask : 0u;
+    const int limit = vc.max_depth;
+
+    int state = V::kIdle, depth = 0;
+    size_t out_row = 0;
+    bool cut = false, more = false;
+    uint32_t nodes = 0, att = 0, def = 0, mask = 0;
+
+    // ---- the loader ----
+    const long long item = static_cast<long long>(blockIdx.x) * 4 + group;
+    if (item < static_cast<long long>(t.n_games) * lv.leaves) {
+        const int game = static_cast<int>(item / lv.leaves), k = static_cast<int>(item - static_cast<long long>(game) * lv.leaves);
+        const AzHeader* hdr = t.hdr + game;
+        if (!(hdr->status & kStatusOver)) {
+            out_row = static_cast<size_t>(t.row_of[game]) * lv.leaves + static_cast<size_t>(k);
+            const bool many = lv.leaves > 1;
+            bool pending = many ? static_cast<uint32_t>(k) < hdr->n_pending : hdr->leaf_pending != 0u;
+            if (pending) {
+                const int own = vc.verdict[out_row].x;
+                pending = own != GMK_VCF_WIN && own != GMK_VCF_OVER;
+            }
+            if (pending) {
+                const AzPending* pd = lv.pend + static_cast<size_t>(game) * GMK_AZ_MAX_LEAVES + (many ? k : 0);
+                const uint32_t word = many ? pd->rows[y] : hdr->leaf_rows[y];
+                const uint32_t stones = many ? pd->stones : hdr->leaf_stones;
+                const uint32_t black = word & V::kRowMask, white = (word >> 16) & V::kRowMask;
+                att = (stones & 1u) ? black : white;             // white is to move on odd stone counts: black threatens
+                def = (stones & 1u) ? white : black;
+                df.occupied[out_row * 16 + y] = static_cast<uint16_t>(black | white);
+                state = V::kInit;
+            } else if (y == 0) {
+                df.threat[out_row] = make_int4(GMK_VCF_NONE, 0, 0, 0);
+            }
+        }
+    }
+
+    // The group's threat.  t0 .. t2 are the cells that end a winning line after the 2 * depth cells on the stack (255: none).
+    const auto finish = [&](int status, int t0, int t1, int t2) {
+        const bool win = status == GMK_VCF_WIN;
+        if (y == 0) df.threat[out_row] = make_int4(status, !win ? 0 : depth + (t1 == 255 ? 1 : 2), static_cast<int>(nodes), 1);
+        if (win) {
+            uint32_t line = 0u;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int k = 4 * y + i, tail = k - 2 * depth;
+                uint32_t v = 255u;
+                if (tail < 0) { const uint32_t w = stack[k >> 1][lane]; v = (k & 1) ? w >> 24 : (w >> 16) & 255u; }
+                else if (tail < 3) v = static_cast<uint32_t>(tail == 0 ? t0 : tail == 1 ? t1 : t2);
+                line |= v << (8 * i);
+            }
+            reinterpret_cast<uint32_t*>(df.pv + out_row * GMK_VCF_PV)[y] = line;
+        }
+        state = V::kIdle;
+    };
+    const auto failed = [&]() { finish(cut ? GMK_VCF_DEPTH : GMK_VCF_NONE, 255, 255, 255); };
+
+    while (__ballot(state != V::kIdle) != 0ull) {
+        // ---- the pass: every group in the same instructions ----
+        const bool trying = state == V::kRun;
+        uint32_t popped = trying ? mask : 0u;
+        const int c = V::take_lowest(popped, y, gbase);
+        const uint32_t left = V::group_rows(popped != 0, gbase);
+        const int cy = trying ? c / 15 : 0;
+        const uint32_t cbit = trying ? 1u << (c - 15 * cy) : 0u;
+        if (trying) {
+            mask = popped;
+            more = left != 0;
+            if (y == cy) att |= cbit;
+        }
+        uint32_t A[9], D[9], N[9];
+        V::gather_rows(att, A);
+        uint32_t F = V::completing(A, board_row & ~(att | def));
+        const int f1 = V::take_lowest(F, y, gbase), f2 = V::take_lowest(F, y, gbase);
+        const bool replied = trying && f1 >= 0 && f2 < 0;
+        const int ry = replied ? f1 / 15 : 0;
+        const uint32_t rbit = replied ? 1u << (f1 - 15 * ry) : 0u;
+        if (replied && y == ry) def |= rbit;
+        const uint32_t empty = board_row & ~(att | def);
+        V::gather_rows(def, D);
+        V::gather_rows(empty | att, N);
+        uint32_t T = V::completing(D, empty);
+        uint32_t C = V::four_making(A, N, empty);
+        if (V::group_rows(T != 0, gbase)) C &= T;
+        const int t1 = V::take_lowest(T, y, gbase), t2 = V::take_lowest(T, y, gbase);
+        (void)t1;
+        const bool child_has = V::group_rows(C != 0, gbase) != 0;
+        bool over = false;
+        if (__ballot(state == V::kInit) != 0ull) over = V::group_rows((V::five(A) | V::five(D)) != 0, gbase) != 0;
+
+        // ---- decisions, the same in all sixteen lanes of a group ----
+        if (state == V::kInit) {
+            if (over) finish(GMK_VCF_OVER, 255, 255, 255);
+            else if (f1 >= 0) finish(GMK_VCF_WIN, f1, 255, 255);
+            else {
+                bool fail = t2 >= 0;
+                if (!fail && 2 > limit) { cut = true; fail = true; }
+                if (!fail && !child_has) fail = true;
+                if (fail) failed();
+                else { mask = C; more = true; state = V::kRun; }
+            }
+        } else if (trying) {
+            bool retract = true;
+            if (f1 < 0) {
+                // not a four: no candidate and no node
+            } else if (nodes == vc.budget) {
+                finish(GMK_VCF_BUDGET, 255, 255, 255);
+            } else {
+                ++nodes;
+                if (f2 >= 0) finish(GMK_VCF_WIN, c, f1, f2);
+                else {
+                    bool fail = t2 >= 0;
+                    if (!fail && depth + 3 > limit) { cut = true; fail = true; }
+                    if (!fail && !child_has) fail = true;
+                    if (!fail) {
+                        stack[depth][lane] = mask | (more ? 0x8000u : 0u) | (static_cast<uint32_t>(c) << 16) | (static_cast<uint32_t>(f1) << 24);
+                        ++depth;
+                        mask = C; more = true; retract = false;
+                    } else if (y == ry) def ^= rbit;
+                }
+            }
+            if (state == V::kRun && retract) {
+                if (y == cy) att ^= cbit;
+                while (!more) {
+                    if (depth == 0) { failed(); break; }
+                    --depth;
+                    const uint32_t w = stack[depth][lane];
+                    mask = w & V::kRowMask;
+                    more = (w & 0x8000u) != 0;
+                    const int uc = static_cast<int>((w >> 16) & 255u), ur = static_cast<int>(w >> 24);
+                    if (y == uc / 15) att ^= 1u << (uc % 15);
+                    if (y == ur / 15) def ^= 1u << (ur % 15);
+                }
+            }
+        }
+    }
+}
+
+// az_defend_leaves_kernel is vcf_defend_kernel's launch two around the leaf loader: one job per (row, cell), one 16-lane group per job, follow
+// against the threat's line first and K14's full walk of P + c with the whole budget only after FAIL.  Jobs are handed out by ROW: kDefendWaves
+// wavefronts per row of the leaf batch, each with a slice of kDefendSlice consecutive cells whose four groups take the next cell of the slice as
+// they fall idle.  A wavefront reads its row's threat first and leaves unless it is WIN, so a leaf that is not threatened costs eight wavefronts
+// that load one word each; nothing is written for it (the expand kernels do not read its cells, the read-out fills them from the threat's status).
+// The position is read once per wavefront.  A leaf with a completing cell of its own is answered WIN by the kernel before the threat's, so
+// GMK_VCF_CELL_FIVE cannot arise: follow's init pass has no "over" test.  No float, no atomics, no barrier, nothing allocated.
+constexpr int kDefendWaves = 8, kDefendSlice = 29;
+static_assert(kDefendWaves * kDefendSlice >= kCells, "the slices cover a row");
+__global__ __launch_bounds__(64)
+void az_defend_leaves_kernel(AzTree t, AzLeaves lv, AzVcf vc, AzDefend df) {
+    namespace V = gmk::vcf;
+    enum : int { kSearch = 0, kFollow = 1 };
+    __shared__ uint32_t stack[V::kLevels][64];                   // K14's (search mode only)
+    const int lane = threadIdx.x, y = lane & 15, group = lane >> 4, gbase = lane & 48;
+    const uint32_t board_row = y < 15 ? V::kRowMask : 0u;
+
+    // ---- the loader: the same in all 64 lanes ----
+    const long long item = static_cast<long long>(blockIdx.x) / kDefendWaves;
+    const int slice = static_cast<int>(blockIdx.x % kDefendWaves);
+    if (item >= static_cast<long long>(t.n_games) * lv.leaves) return;
+    const int game = static_cast<int>(item / lv.leaves), k = static_cast<int>(item - static_cast<long long>(game) * lv.leaves);
+    const AzHeader* hdr = t.hdr + game;
+    if (hdr->status & kStatusOver) return;
+    const size_t out_row = static_cast<size_t>(t.row_of[game]) * lv.leaves + static_cast<size_t>(k);
+    const int4 th = df.threat[out_row];
+    if (th.x != GMK_VCF_WIN || th.w == 0) return;                // only a leaf that was pending and asked has a WIN here
+    const bool many = lv.leaves > 1;
+    const AzPending* pd = lv.pend + static_cast<size_t>(game) * GMK_AZ_MAX_LEAVES + (many ? k : 0);
+    const uint32_t word = many ? pd->rows[y] : hdr->leaf_rows[y];
+    const uint32_t stones = many ? pd->stones : hdr->leaf_stones;
+    const uint32_t black = word & V::kRowMask, white = (word >> 16) & V::kRowMask;
+    const uint32_t base_att = (stones & 1u) ? black : white, base_def = (stones & 1u) ? white : black;
+    const int tlen = th.y;
+    const uint32_t pvw = reinterpret_cast<const uint32_t*>(df.pv + out_row * GMK_VCF_PV)[y];     // this lane's four pv cells
+    uint32_t* out = df.cells + out_row * kCells;
+    int next_cell = slice * kDefendSlice;
+    int left = next_cell < kCells ? min(kDefendSlice, kCells - next_cell) : 0;
+
+    int state = V::kIdle, mode = kSearch, cell = 0, depth = 0;
+    const int limit = vc.max_depth;
+    bool cut = false, more = false;
+    uint32_t nodes = 0, att = 0, def = 0, mask = 0;
+
+    const auto settle = [&](int verdict, bool searched, uint32_t count) {
+        if (y == 0) out[cell] = static_cast<uint32_t>(verdict) | (searched ? kCellSearched : 0u) | (count << kCellNodesShift);
+        state = V::kIdle;
+    };
+    // P + c, nothing played: where follow starts, and where the search starts after it
+    const auto to_root = [&](int new_mode) {
+        const int jy = cell / 15;
+        att = base_att;
+        def = base_def | (y == jy ? 1u << (cell - 15 * jy) : 0u);
+        mode = new_mode;
+        nodes = 0; depth = 0; cut = false; more = false; mask = 0;
+        state = V::kInit;
+    };
+    // the search's result (K14's finish, without a pv)
+    const auto finish = [&](int status) {
+        settle(status == GMK_VCF_WIN ? GMK_VCF_CELL_LOSES : status == GMK_VCF_NONE ? GMK_VCF_CELL_HOLDS : GMK_VCF_CELL_UNKNOWN, true, nodes);
+    };
+    const auto failed = [&]() { finish(cut ? GMK_VCF_DEPTH : GMK_VCF_NONE); };
+
+    for (;;) {
+        // ---- groups without a job take the next cells of this wavefront's slice ----
+        const unsigned long long idle = __ballot(state == V::kIdle);
+        int rank = 0, takers = 0;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int is_idle = static_cast<int>((idle >> (16 * g)) & 1ull);
+            if (g < group) rank += is_idle;
+            takers += is_idle;
+        }
+        if (state == V::kIdle && rank < left) {
+            cell = next_cell + rank;
+            const int jy = cell / 15;
+            const bool taken = V::group_rows(y == jy && (((base_att | base_def) >> (cell - 15 * jy)) & 1u) != 0, gbase) != 0;
+            if (taken) settle(GMK_VCF_CELL_NONE, false, 0u);
+            else to_root(kFollow);
+        }
+        const int taken_jobs = takers < left ? takers : left;
+        left -= taken_jobs;
+        next_cell += taken_jobs;
+        if (__ballot(state != V::kIdle) == 0ull) {                 // nothing to walk: only occupied cells, or the slice is done
+            if (left == 0) break;
+            continue;
+        }
+
+        // ---- the pass (K14's): every group in the same instructions ----
+        const bool trying = state == V::kRun;
+        uint32_t popped = trying ? mask : 0u;
+        const int c = V::take_lowest(popped, y, gbase);
+        const uint32_t more_left = V::group_rows(popped != 0, gbase);
+        const int cy = trying ? c / 15 : 0;
+        const uint32_t cbit = trying ? 1u << (c - 15 * cy) : 0u;
+        if (trying) {
+            mask = popped;
+            more = more_left != 0;
+            if (y == cy) att |= cbit;
+        }
+        uint32_t A[9], D[9], N[9];
+        V::gather_rows(att, A);
+        uint32_t F = V::completing(A, board_row & ~(att | def));
+        const int f1 = V::take_lowest(F, y, gbase), f2 = V::take_lowest(F, y, gbase);
+        const bool replied = trying && f1 >= 0 && f2 < 0;          // the forced reply goes on the board
+        const int ry = replied ? f1 / 15 : 0;
+        const uint32_t rbit = replied ? 1u << (f1 - 15 * ry) : 0u;
+        if (replied && y == ry) def |= rbit;
+        const uint32_t empty = board_row & ~(att | def);
+        V::gather_rows(def, D);
+        V::gather_rows(empty | att, N);
+        uint32_t T = V::completing(D, empty);
+        uint32_t C = V::four_making(A, N, empty);
+        if (V::group_rows(T != 0, gbase)) C &= T;                  // a defender four: only its blocking cell is a candidate
+        const int t1 = V::take_lowest(T, y, gbase), t2 = V::take_lowest(T, y, gbase);
+        const bool child_has = V::group_rows(C != 0, gbase) != 0;
+        // follow's next level on this board: the threat's move there, which must be free and, against a defender four, its block
+        const int level = trying ? depth + 1 : depth;
+        const uint32_t pv_word = static_cast<uint32_t>(__shfl(static_cast<int>(pvw), gbase + ((level >> 1) & 15)));
+        const int a = static_cast<int>((pv_word >> (16 * (level & 1))) & 255u), ay = a / 15;     // 255 past the line's end: row 17, no lane's
+        const uint32_t abit = y == ay ? 1u << (a - 15 * ay) : 0u;
+        const bool a_free = V::group_rows((empty & abit) != 0, gbase) != 0;
+        const bool follows = t2 < 0 && level < tlen && a_free && (t1 < 0 || a == t1);
+
+        // ---- decisions, the same in all sixteen lanes of a group ----
+        if (state == V::kInit) {
+            if (mode == kFollow) {
+                if (f1 >= 0) settle(GMK_VCF_CELL_LOSES, false, 0u);
+                else if (follows) { mask = abit; state = V::kRun; }
+                else to_root(kSearch);
+            } else {
+                if (f1 >= 0) finish(GMK_VCF_WIN);                  // follow has settled these; kept so that the search is K14's walk whole
+                else {
+                    bool fail = t2 >= 0;
+                    if (!fail && 2 > limit) { cut = true; fail = true; }
+                    if (!fail && !child_has) fail = true;
+                    if (fail) failed();
+                    else { mask = C; more = true; state = V::kRun; }
+                }
+            }
+        } else if (trying && mode == kFollow) {
+            if (f1 < 0) to_root(kSearch);                          // the threat's move is no four any more
+            else if (f2 >= 0) settle(GMK_VCF_CELL_LOSES, false, 0u);
+            else if (follows) { ++depth; mask = abit; }            // a and its forced reply stay on the board
+            else to_root(kSearch);
+        } else if (trying) {
+            bool retract = true;
+            if (f1 < 0) {
+                // not a four: no candidate and no node (K14)
+            } else if (nodes == vc.budget) {
+                finish(GMK_VCF_BUDGET);
+            } else {
+                ++nodes;
+                if (f2 >= 0) finish(GMK_VCF_WIN);
                 else {
                     bool fail = t2 >= 0;
                     if (!fail && depth + 3 > limit) { cut = true; fail = true; }
@@ -1170,6 +1576,8 @@ struct gmk_az {
     bool leaf_waiting = false;                                   // any L: a gmk_az_select has not been answered yet (asked by the GMK_OPT_AZ_VCF_* options only)
     AzVcf vcf{nullptr, 0, 64u};                                  // GMK_OPT_AZ_VCF_DEPTH / _BUDGET; the verdict buffer comes with the first D > 0
     bool proof = false;                                          // GMK_OPT_AZ_PROOF: the <true> proof instantiations are launched
+    bool defend = false;                                         // GMK_OPT_AZ_VCF_DEFEND; it acts only with D > 0 and proof (az_defend_active)
+    AzDefend df{};                                               //   its buffers come when it first acts
     // device scratch of the host-driven form (gmk_az_select_host / gmk_az_expand_host)
     float *h_states = nullptr, *h_values = nullptr, *h_probs = nullptr;
     int16_t* h_paths = nullptr;
@@ -1185,6 +1593,7 @@ extern "C" int gmk_az_destroy(gmk_az* a) {
     (void)gmk::device_free(a->h_states); (void)gmk::device_free(a->h_values); (void)gmk::device_free(a->h_probs); (void)gmk::device_free(a->h_paths); (void)gmk::device_free(a->h_lens);
     (void)gmk::device_free(a->lv.inflight); (void)gmk::device_free(a->lv.pend); (void)gmk::device_free(a->d_owed);
     (void)gmk::device_free(a->vcf.verdict);
+    (void)gmk::device_free(a->df.threat); (void)gmk::device_free(a->df.pv); (void)gmk::device_free(a->df.occupied); (void)gmk::device_free(a->df.cells);
     delete a;
     return GMK_OK;
 }
@@ -1227,6 +1636,7 @@ static bool az_marks_up(const gmk_az* a, const char* who) {
 static bool az_many_leaves(const gmk_az* a, const char* who) {
     if (a->vcf.max_depth > 0) { gmk::set_error("%s: the host-driven form does not solve its leaves (GMK_OPT_AZ_VCF_DEPTH = %d)", who, a->vcf.max_depth); return true; }
     if (a->proof) { gmk::set_error("%s: the host-driven form does not carry proofs (GMK_OPT_AZ_PROOF = 1)", who); return true; }
+    if (a->defend) { gmk::set_error("%s: the host-driven form does not ask the defence solver (GMK_OPT_AZ_VCF_DEFEND = 1)", who); return true; }
     if (a->lv.leaves > 1) { gmk::set_error("%s: the host-driven form takes one leaf per step (GMK_OPT_AZ_LEAVES = %d)", who, a->lv.leaves); return true; }
     return false;
 }
@@ -1344,12 +1754,43 @@ extern "C" int gmk_az_set_slots(gmk_az* a, int n_total, const uint8_t* h_open_mo
     return az_compact(a, nullptr);
 }
 
-// D > 0: the pending leaves go through the solver, on the same stream, right behind the select kernel
+// K7 + K15 acts: the option, the solver and the proofs are all on, and its buffers are there (an option call whose allocation failed has
+// said so, and the block stays inert)
+static bool az_defend_wanted(const gmk_az* a) { return a->defend && a->proof && a->vcf.max_depth > 0; }
+static bool az_defend_active(const gmk_az* a) { return az_defend_wanted(a) && a->df.threat != nullptr; }
+
+// The buffers of K7 + K15, when an option call makes it act for the first time: per row of the largest leaf batch the threat (every row reads
+// "not asked" until a select writes it), its line, the occupied cells and one word per cell.
+static int az_defend_buffers(gmk_az* a) {
+    if (!az_defend_wanted(a) || a->df.threat) return GMK_OK;
+    const size_t rows = static_cast<size_t>(a->t.n_games) * GMK_AZ_MAX_LEAVES;
+    GMK_HIP_CHECK(hipDeviceSynchronize());
+    const bool ok = gmk::device_malloc(&a->df.threat, rows * sizeof(int4)) == hipSuccess && gmk::device_malloc(&a->df.pv, rows * GMK_VCF_PV) == hipSuccess &&
+                    gmk::device_malloc(&a->df.occupied, rows * 16 * 2) == hipSuccess && gmk::device_malloc(&a->df.cells, rows * kCells * 4) == hipSuccess &&
+                    hipMemset(a->df.threat, 0, rows * sizeof(int4)) == hipSuccess && hipMemset(a->df.pv, 0xFF, rows * GMK_VCF_PV) == hipSuccess &&
+                    hipMemset(a->df.occupied, 0, rows * 16 * 2) == hipSuccess && hipMemset(a->df.cells, 0, rows * kCells * 4) == hipSuccess;
+    if (!ok) {                                                   // all or nothing
+        (void)gmk::device_free(a->df.threat); (void)gmk::device_free(a->df.pv); (void)gmk::device_free(a->df.occupied); (void)gmk::device_free(a->df.cells);
+        a->df = AzDefend{};
+        (void)hipGetLastError();
+        gmk::set_error("gmk_az_set_option: hipMalloc of the defence buffers (%zu rows) failed", rows);
+        return GMK_ERR_HIP;
+    }
+    return GMK_OK;
+}
+
+// D > 0: the pending leaves go through the solver, on the same stream, right behind the select kernel; with K7 + K15 the threat against each
+// and the replies that lose to it follow, as two more links of the same chain
 static int az_vcf_leaves(gmk_az* a, void* stream) {
     a->leaf_waiting = true;
     if (a->vcf.max_depth == 0) return GMK_OK;
     const long long groups = static_cast<long long>(a->t.n_games) * a->lv.leaves;
     hipLaunchKernelGGL(az_vcf_leaves_kernel, dim3(static_cast<unsigned>((groups + 3) / 4)), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, a->vcf);
+    GMK_HIP_CHECK(hipGetLastError());
+    if (!az_defend_active(a)) return GMK_OK;
+    hipLaunchKernelGGL(az_threat_leaves_kernel, dim3(static_cast<unsigned>((groups + 3) / 4)), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, a->vcf, a->df);
+    GMK_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(az_defend_leaves_kernel, dim3(static_cast<unsigned>(groups * kDefendWaves)), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, a->vcf, a->df);
     GMK_HIP_CHECK(hipGetLastError());
     return GMK_OK;
 }
@@ -1376,17 +1817,19 @@ extern "C" int gmk_az_expand(gmk_az* a, const float* d_values, const float* d_pr
     if (!a->rooted) { gmk::set_error("gmk_az_expand: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
     if (a->lv.leaves > 1) {                                      // d_values and d_probs have gmk_az_live_games x L rows
         // proofs start in the expand kernels only at a leaf answered WIN: without the solver the proof option launches what it launches when off
-        if (a->vcf.max_depth > 0 && a->proof) hipLaunchKernelGGL((az_expand_leaves_kernel<true, true>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf);
-        else if (a->vcf.max_depth > 0) hipLaunchKernelGGL((az_expand_leaves_kernel<true, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf);
-        else hipLaunchKernelGGL((az_expand_leaves_kernel<false, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf);
+        if (az_defend_active(a)) hipLaunchKernelGGL((az_expand_leaves_kernel<true, true, true>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf, a->df);
+        else if (a->vcf.max_depth > 0 && a->proof) hipLaunchKernelGGL((az_expand_leaves_kernel<true, true, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf, a->df);
+        else if (a->vcf.max_depth > 0) hipLaunchKernelGGL((az_expand_leaves_kernel<true, false, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf, a->df);
+        else hipLaunchKernelGGL((az_expand_leaves_kernel<false, false, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf, a->df);
         GMK_HIP_CHECK(hipGetLastError());
         a->select_issued = false;
         a->leaf_waiting = false;
         return GMK_OK;
     }
-    if (a->vcf.max_depth > 0 && a->proof) hipLaunchKernelGGL((az_expand_kernel<true, true>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf);
-    else if (a->vcf.max_depth > 0) hipLaunchKernelGGL((az_expand_kernel<true, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf);
-    else hipLaunchKernelGGL((az_expand_kernel<false, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf);
+    if (az_defend_active(a)) hipLaunchKernelGGL((az_expand_kernel<true, true, true>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf, a->df);
+    else if (a->vcf.max_depth > 0 && a->proof) hipLaunchKernelGGL((az_expand_kernel<true, true, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf, a->df);
+    else if (a->vcf.max_depth > 0) hipLaunchKernelGGL((az_expand_kernel<true, false, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf, a->df);
+    else hipLaunchKernelGGL((az_expand_kernel<false, false, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf, a->df);
     GMK_HIP_CHECK(hipGetLastError());
     a->leaf_waiting = false;
     return GMK_OK;
@@ -1545,12 +1988,17 @@ extern "C" int gmk_az_set_option(gmk_az* a, int option, int value) {
             GMK_HIP_CHECK(hipMemcpy(a->vcf.verdict, none.data(), rows * sizeof(int4), hipMemcpyHostToDevice));
         }
         a->vcf.max_depth = value;
-        return GMK_OK;
+        return az_defend_buffers(a);
     }
     if (a && option == GMK_OPT_AZ_PROOF && (value == 0 || value == 1)) {
         if (a->leaf_waiting) { gmk::set_error("gmk_az_set_option: gmk_az_select is waiting for its gmk_az_expand; GMK_OPT_AZ_PROOF changes how it is answered"); return GMK_ERR_STATE; }
         a->proof = value == 1;                                   // the bits stay where they are: facts about positions, ignored while the option is off
-        return GMK_OK;
+        return az_defend_buffers(a);
+    }
+    if (a && option == GMK_OPT_AZ_VCF_DEFEND && (value == 0 || value == 1)) {
+        if (a->leaf_waiting) { gmk::set_error("gmk_az_set_option: gmk_az_select is waiting for its gmk_az_expand; GMK_OPT_AZ_VCF_DEFEND changes how it is answered"); return GMK_ERR_STATE; }
+        a->defend = value == 1;                                  // inert unless the solver and the proofs are on as well
+        return az_defend_buffers(a);
     }
     if (a && option == GMK_OPT_NOISE_SAMPLER && (value == GMK_NOISE_SAMPLER_STD || value == GMK_NOISE_SAMPLER_COUNTER)) { a->noise_sampler = value; return GMK_OK; }
     gmk::set_error("gmk_az_set_option: bad handle, unknown option %d or value %d", option, value);
@@ -1757,7 +2205,7 @@ extern "C" int gmk_az_expand_stages_host(gmk_az* a, const float* h_values, const
     if (h_values) GMK_HIP_CHECK(hipMemcpy(a->h_values, h_values, static_cast<size_t>(a->t.n_games) * 4, hipMemcpyHostToDevice));
     if (h_probs) GMK_HIP_CHECK(hipMemcpy(a->h_probs, h_probs, static_cast<size_t>(a->t.n_games) * 225 * 4, hipMemcpyHostToDevice));
     else GMK_HIP_CHECK(hipMemset(a->h_probs, 0, static_cast<size_t>(a->t.n_games) * 225 * 4));
-    hipLaunchKernelGGL((az_expand_kernel<false, false>), dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, a->h_values, a->h_probs, (do_expand ? 1 : 0) | (do_backup ? 2 : 0), a->vcf);
+    hipLaunchKernelGGL((az_expand_kernel<false, false, false>), dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, a->h_values, a->h_probs, (do_expand ? 1 : 0) | (do_backup ? 2 : 0), a->vcf, a->df);
     GMK_HIP_CHECK(hipGetLastError());
     a->leaf_waiting = false;
     GMK_HIP_CHECK(hipDeviceSynchronize());
@@ -1890,6 +2338,54 @@ extern "C" int gmk_az_proof_stats(gmk_az* a, uint32_t* h_proved, uint32_t* h_sto
     for (size_t g = 0; g < n; ++g) {
         if (h_proved) h_proved[g] = hdr[g].proof_proved;
         if (h_stops) h_stops[g] = hdr[g].proof_stops;
+    }
+    return GMK_OK;
+}
+
+// ---- K7 + K15: the read-outs ----
+extern "C" int gmk_az_defend_stats(gmk_az* a, uint32_t* h_threatened, uint32_t* h_marked, uint32_t* h_searched, uint64_t* h_nodes) {
+    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    if (!a) { gmk::set_error("gmk_az_defend_stats: bad arguments"); return GMK_ERR_ARG; }
+    if (!a->rooted) { gmk::set_error("gmk_az_defend_stats: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
+    const size_t n = static_cast<size_t>(a->t.n_games);
+    std::vector<AzHeader> hdr(n);
+    GMK_HIP_CHECK(hipDeviceSynchronize());
+    GMK_HIP_CHECK(hipMemcpy(hdr.data(), a->t.hdr, n * sizeof(AzHeader), hipMemcpyDeviceToHost));
+    for (size_t g = 0; g < n; ++g) {
+        if (h_threatened) h_threatened[g] = hdr[g].def_threatened;
+        if (h_marked) h_marked[g] = hdr[g].def_marked;
+        if (h_searched) h_searched[g] = hdr[g].def_searched;
+        if (h_nodes) h_nodes[g] = hdr[g].def_nodes;
+    }
+    return GMK_OK;
+}
+
+extern "C" int gmk_az_defend_verdicts_host(gmk_az* a, int32_t* h_threat_status, int32_t* h_threat_length, int8_t* h_verdict, uint32_t* h_nodes) {
+    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    if (!a) { gmk::set_error("gmk_az_defend_verdicts_host: bad arguments"); return GMK_ERR_ARG; }
+    if (!az_defend_active(a) || !a->df.threat) { gmk::set_error("gmk_az_defend_verdicts_host: the defence solver is not asked (GMK_OPT_AZ_VCF_DEFEND with GMK_OPT_AZ_VCF_DEPTH > 0 and GMK_OPT_AZ_PROOF)"); return GMK_ERR_STATE; }
+    const size_t rows = static_cast<size_t>(a->n_live) * static_cast<size_t>(a->lv.leaves);
+    std::vector<int4> th(rows);
+    std::vector<uint16_t> occupied(rows * 16);
+    std::vector<uint32_t> cells(rows * kCells);
+    GMK_HIP_CHECK(hipDeviceSynchronize());
+    if (rows) {
+        GMK_HIP_CHECK(hipMemcpy(th.data(), a->df.threat, rows * sizeof(int4), hipMemcpyDeviceToHost));
+        GMK_HIP_CHECK(hipMemcpy(occupied.data(), a->df.occupied, rows * 16 * 2, hipMemcpyDeviceToHost));
+        GMK_HIP_CHECK(hipMemcpy(cells.data(), a->df.cells, rows * kCells * 4, hipMemcpyDeviceToHost));
+    }
+    for (size_t r = 0; r < rows; ++r) {
+        const bool asked = th[r].w != 0, win = asked && th[r].x == GMK_VCF_WIN;
+        if (h_threat_status) h_threat_status[r] = th[r].x;
+        if (h_threat_length) h_threat_length[r] = th[r].y;
+        // the cells of a row that is not under a WIN threat were never written: K15's table for them follows from the threat's status alone
+        const int other = !asked || th[r].x == GMK_VCF_OVER ? GMK_VCF_CELL_NONE : th[r].x == GMK_VCF_NONE ? GMK_VCF_CELL_HOLDS : GMK_VCF_CELL_UNKNOWN;
+        for (int c = 0; c < kCells; ++c) {
+            const uint32_t w = cells[r * kCells + c];
+            const bool taken = (occupied[r * 16 + c / 15] >> (c % 15)) & 1u;
+            if (h_verdict) h_verdict[r * kCells + c] = static_cast<int8_t>(win ? (w & kCellVerdict) : taken ? GMK_VCF_CELL_NONE : other);
+            if (h_nodes) h_nodes[r * kCells + c] = win ? w >> kCellNodesShift : 0u;
+        }
     }
     return GMK_OK;
 }

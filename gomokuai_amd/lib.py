@@ -33,6 +33,7 @@ OPT_NOISE_SAMPLER, OPT_LOCKSTEP, OPT_AZ_LEAVES = 1, 2, 3
 OPT_AZ_VCF_DEPTH, OPT_AZ_VCF_BUDGET = 4, 5     # K7 + K14: forced wins by fours solved at the leaves (AlphaZeroMCTS(vcf_depth=, vcf_budget=))
 OPT_AZ_PROOF = 6                               # K7 + proofs: proven wins and losses carried up the tree (AlphaZeroMCTS(proof=))
 AZ_PROOF_NONE, AZ_PROOF_WINS, AZ_PROOF_LOSES = 0, 1, 2
+OPT_AZ_VCF_DEFEND = 7                          # K7 + K15: the replies that lose to a forced win by fours, proven at the leaves (AlphaZeroMCTS(vcf_defend=))
 AZ_MAX_LEAVES = 8                              # GMK_AZ_MAX_LEAVES: leaves per game per step of a K7 handle (AlphaZeroMCTS(leaves=))
 NOISE_SAMPLERS = {"std": 0, "counter": 1}      # std::gamma_distribution on the host / the counter-based sampler of include/gomoku_noise.h on the device
 
@@ -46,7 +47,7 @@ EXPORTS = [
     "gmk_mcts_alg_bytes", "gmk_mcts_launch_info", "gmk_visits_to_pi", "gmk_mcts_advance", "gmk_mcts_step", "gmk_mcts_step_host", "gmk_mcts_add_root_noise", "gmk_mcts_set_option", "gmk_mcts_reserve", "gmk_selfplay_run", "gmk_samples_from_records",
     "gmk_records_scan", "gmk_records_packed_bytes", "gmk_records_pack", "gmk_records_unpack", "gmk_samples_from_packed",
     "gmk_evalstate_create", "gmk_evalstate_destroy", "gmk_evalstate_reset", "gmk_evalstate_update", "gmk_evalstate_update_host", "gmk_evalstate_read",
-    "gmk_az_create", "gmk_az_destroy", "gmk_az_set_roots", "gmk_az_select", "gmk_az_expand", "gmk_az_select_host", "gmk_az_expand_host", "gmk_az_read_node_host", "gmk_az_read_children_host", "gmk_az_set_leaf_host", "gmk_az_rollout_host", "gmk_az_expand_stages_host", "gmk_az_write_stats_host", "gmk_az_step", "gmk_az_root_choice", "gmk_az_step_device", "gmk_az_advance", "gmk_az_set_slots", "gmk_az_live_games", "gmk_az_set_game_ids", "gmk_az_add_root_noise", "gmk_az_set_option", "gmk_az_add_playouts", "gmk_az_playouts_owed", "gmk_az_root_stats", "gmk_az_vcf_stats", "gmk_az_vcf_verdicts_host", "gmk_az_root_proofs", "gmk_az_proof_stats",
+    "gmk_az_create", "gmk_az_destroy", "gmk_az_set_roots", "gmk_az_select", "gmk_az_expand", "gmk_az_select_host", "gmk_az_expand_host", "gmk_az_read_node_host", "gmk_az_read_children_host", "gmk_az_set_leaf_host", "gmk_az_rollout_host", "gmk_az_expand_stages_host", "gmk_az_write_stats_host", "gmk_az_step", "gmk_az_root_choice", "gmk_az_step_device", "gmk_az_advance", "gmk_az_set_slots", "gmk_az_live_games", "gmk_az_set_game_ids", "gmk_az_add_root_noise", "gmk_az_set_option", "gmk_az_add_playouts", "gmk_az_playouts_owed", "gmk_az_root_stats", "gmk_az_vcf_stats", "gmk_az_vcf_verdicts_host", "gmk_az_defend_stats", "gmk_az_defend_verdicts_host", "gmk_az_root_proofs", "gmk_az_proof_stats",
     "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_root_choice", "gmk_trad_step_device", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_run_rave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
     "gmk_pattern_policy", "gmk_pattern_policy_host", "gmk_pattern_play",
     "gmk_vcf_solve", "gmk_vcf_solve_host", "gmk_vcf_defend", "gmk_vcf_defend_host",
@@ -144,6 +145,8 @@ def load():
     L.gmk_az_root_proofs.argtypes = [vp] * 3
     L.gmk_az_proof_stats.argtypes = [vp] * 3
     L.gmk_az_vcf_verdicts_host.argtypes = [vp] * 5
+    L.gmk_az_defend_stats.argtypes = [vp] * 5
+    L.gmk_az_defend_verdicts_host.argtypes = [vp] * 5
     L.gmk_trad_create.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]
     L.gmk_trad_destroy.argtypes = [vp]
     L.gmk_trad_reset_evaluators.argtypes = [vp]
@@ -1127,9 +1130,13 @@ class AlphaZeroMCTS:
     the winning move (OPT_AZ_VCF_DEPTH / OPT_AZ_VCF_BUDGET; include/gomoku_hip.h, "K7 + K14").  vcf_stats() and vcf_verdicts() read it out.
     proof = True: nodes carry proven wins and losses (a five on the board, a leaf the solver answers WIN) up the tree, descents stop at proven
     nodes without a network row, and the root plays a proven win and avoids proven losses (OPT_AZ_PROOF; include/gomoku_hip.h, "K7 + proofs").
-    root_proofs() and proof_stats() read it out."""
+    root_proofs() and proof_stats() read it out.
+    vcf_defend = True (it acts only with vcf_depth > 0 and proof): select() also asks what the opponent threatens at every pending leaf the solver
+    did not answer, and under a forced win by fours which replies lose to it (vcf_defend's table); expand() marks those children as the
+    opponent's proven wins and proves a leaf without a holding reply lost (OPT_AZ_VCF_DEFEND; include/gomoku_hip.h, "K7 + K15").
+    defend_stats() and defend_verdicts() read it out."""
 
-    def __init__(self, n_games, node_capacity=1 << 16, c_puct=5.0, leaves=1, vcf_depth=0, vcf_budget=64, proof=False):
+    def __init__(self, n_games, node_capacity=1 << 16, c_puct=5.0, leaves=1, vcf_depth=0, vcf_budget=64, proof=False, vcf_defend=False):
         import torch
         init()
         self.n = n_games
@@ -1146,6 +1153,8 @@ class AlphaZeroMCTS:
             self.set_option(OPT_AZ_VCF_DEPTH, vcf_depth)
         if proof:
             self.set_option(OPT_AZ_PROOF, 1)
+        if vcf_defend:
+            self.set_option(OPT_AZ_VCF_DEFEND, 1)
 
     def close(self):
         if getattr(self, "h", None) and load is not None:
@@ -1247,7 +1256,8 @@ class AlphaZeroMCTS:
 
     def set_option(self, option, value):
         """gmk_az_set_option: OPT_NOISE_SAMPLER -> NOISE_SAMPLERS["std" | "counter"]; OPT_AZ_LEAVES -> 1 .. AZ_MAX_LEAVES leaves per game per step;
-        OPT_AZ_VCF_DEPTH -> 0 (off) .. VCF_MAX_DEPTH and OPT_AZ_VCF_BUDGET -> 1 .. 2^20 for the solver at the leaves; OPT_AZ_PROOF -> 0 / 1."""
+        OPT_AZ_VCF_DEPTH -> 0 (off) .. VCF_MAX_DEPTH and OPT_AZ_VCF_BUDGET -> 1 .. 2^20 for the solver at the leaves; OPT_AZ_PROOF -> 0 / 1;
+        OPT_AZ_VCF_DEFEND -> 0 / 1."""
         import torch
         _check(load().gmk_az_set_option(self.h, int(option), int(value)))
         if int(option) == OPT_AZ_LEAVES:
@@ -1328,6 +1338,22 @@ class AlphaZeroMCTS:
         """gmk_az_proof_stats: per game, since set_roots / set_slots: nodes given a proof, and descents ended at a node already proven."""
         out = {"proved": np.zeros(self.n, np.uint32), "stops": np.zeros(self.n, np.uint32)}
         _check(load().gmk_az_proof_stats(self.h, out["proved"].ctypes.data, out["stops"].ctypes.data))
+        return out
+
+    def defend_stats(self):
+        """gmk_az_defend_stats: per game, since set_roots / set_slots: leaves expanded under a forced win by fours of the opponent, children marked
+        as his proven wins, cells that were solved in full, and the nodes of those solves."""
+        out = {"threatened": np.zeros(self.n, np.uint32), "marked": np.zeros(self.n, np.uint32), "searched": np.zeros(self.n, np.uint32), "nodes": np.zeros(self.n, np.uint64)}
+        _check(load().gmk_az_defend_stats(self.h, *[out[k].ctypes.data for k in ("threatened", "marked", "searched", "nodes")]))
+        return out
+
+    def defend_verdicts(self):
+        """gmk_az_defend_verdicts_host: for the live x leaves rows of the last select(), the threat against the leaf ("threat_status" i32[rows] as
+        vcf_solve names it, "threat_length" i32[rows]) and vcf_defend's table for it ("verdict" i8[rows, 225] VCF_CELL_*, "nodes" u32[rows, 225]); a
+        row without a pending leaf, or one the solver answered itself, reads VCF_NONE / 0 and zeros."""
+        rows = self.live * self.leaves
+        out = {"threat_status": np.zeros(rows, np.int32), "threat_length": np.zeros(rows, np.int32), "verdict": np.zeros((rows, N), np.int8), "nodes": np.zeros((rows, N), np.uint32)}
+        _check(load().gmk_az_defend_verdicts_host(self.h, *[out[k].ctypes.data for k in ("threat_status", "threat_length", "verdict", "nodes")]))
         return out
 
     def vcf_verdicts(self):

@@ -495,7 +495,7 @@ def _root_choice(visits, proofs=None):
 
 def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, first_game_id=0, opening_plies=0, max_moves=N,
                        device=None, node_capacity=None, reuse_subtree=True, root_noise=(0.05, 0.25), slots=None, device_loop=True, noise_sampler="counter", leaves=1,
-                       vcf=None, proof=False):
+                       vcf=None, proof=False, vcf_defend=False):
     """n_games complete games of the network-guided searcher against itself (agents/alphazero.py:5-9 on both sides: the
     reference's AlphaZero self-play), all games in lock step on the current GPU: every move = `playouts` lock-step playouts of
     K7 with `network(states [n,6,15,15]) -> (value [n], probs [n,225])` at the leaves (network.FusedPolicyValueNetwork = K9),
@@ -509,7 +509,10 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
     (lib.AlphaZeroMCTS(leaves=)): the network's batch is live games x leaves rows and a move takes about playouts / leaves steps; the games differ
     from those of leaves = 1, and are the same games on every loop of this function.  vcf = (depth, budget): the searches solve forced wins by
     fours at their leaves (lib.AlphaZeroMCTS(vcf_depth=, vcf_budget=)); None: they do not.  proof: the searches carry proven wins and losses up
-    their trees and every loop chooses its moves by them (lib.AlphaZeroMCTS(proof=), _root_choice).  Returns GameRecords like play_games."""
+    their trees and every loop chooses its moves by them (lib.AlphaZeroMCTS(proof=), _root_choice).  vcf_defend (with vcf and proof): the replies
+    that lose to the opponent's forced win by fours are proven at the leaves (lib.AlphaZeroMCTS(vcf_defend=)); such a search spends its playouts
+    below the few replies that hold, so a kept subtree stays nearly whole while the replies are forced: give node_capacity room (the records'
+    overflow says when an arena filled).  Returns GameRecords like play_games."""
     if slots is not None and slots < n_games and (max_moves < N or (device_loop and opening_plies > 8)):
         # (the slot loops play whole games, the device-resident one from openings of at most 8 plies -- gmk_az_set_slots' limit: say so instead of
         # ignoring the cap or failing inside the library; ADVICE r3)
@@ -526,7 +529,7 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
             games.open_with(m, l, opening_plies)
         slots = int(slots)
         cap = node_capacity if node_capacity is not None else min((3 if reuse_subtree else 1) * playouts * N + 1, (1 << 24) - 1)
-        tree = G.AlphaZeroMCTS(slots, node_capacity=cap, c_puct=c_puct, leaves=leaves, proof=proof, **_vcf_options(vcf))
+        tree = G.AlphaZeroMCTS(slots, node_capacity=cap, c_puct=c_puct, leaves=leaves, proof=proof, vcf_defend=vcf_defend, **_vcf_options(vcf))
         tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS[noise_sampler])
         tree.set_slots(n_games, games.moves[:, :max(int(games.lens.max()), 1)], games.lens)
         d_moves, d_lens = torch.from_numpy(games.moves).to(dev), torch.from_numpy(games.lens).to(dev)
@@ -551,7 +554,7 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
             games.open_with(m, l, opening_plies)
         visits = np.zeros((n_games, N, N), dtype=np.uint16)
         slots = int(slots)
-        tree = G.AlphaZeroMCTS(slots, node_capacity=node_capacity if node_capacity is not None else min(playouts * N + 1, (1 << 24) - 1), c_puct=c_puct, leaves=leaves, proof=proof, **_vcf_options(vcf))
+        tree = G.AlphaZeroMCTS(slots, node_capacity=node_capacity if node_capacity is not None else min(playouts * N + 1, (1 << 24) - 1), c_puct=c_puct, leaves=leaves, proof=proof, vcf_defend=vcf_defend, **_vcf_options(vcf))
         active, next_game, overflow = np.arange(slots), slots, False
         with torch.no_grad():
             for _ in range((n_games // slots + 2) * N):
@@ -589,7 +592,7 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
         m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
         games.open_with(m, l, opening_plies)
     cap = node_capacity if node_capacity is not None else min((3 if reuse_subtree else 1) * playouts * N + 1, (1 << 24) - 1)
-    tree = G.AlphaZeroMCTS(n_games, node_capacity=cap, c_puct=c_puct, leaves=leaves, proof=proof, **_vcf_options(vcf))
+    tree = G.AlphaZeroMCTS(n_games, node_capacity=cap, c_puct=c_puct, leaves=leaves, proof=proof, vcf_defend=vcf_defend, **_vcf_options(vcf))
     tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS[noise_sampler])
     tree.set_roots(G.moves_to_planes(games.moves, games.lens), games.last_two())
     if device_loop:
@@ -791,7 +794,7 @@ class _EvalOpponent:
 
 
 def play_evaluation_games(n_games, network, opponent, playouts=400, c_puct=5.0, seed=G.DEFAULT_SEED, first_game_id=0, opening_plies=0, max_moves=N,
-                          reuse_subtree=True, root_noise=(0.05, 0.25), device_loop=None, device=None, leaves=1, vcf=None, proof=False):
+                          reuse_subtree=True, root_noise=(0.05, 0.25), device_loop=None, device=None, leaves=1, vcf=None, proof=False, vcf_defend=False, node_capacity=None):
     """The reference's evaluation match (network/train.py:88-126 evaluate_network -> agents/utils.py:66-100 eval_agents): n_games games of the
     network-guided searcher (K7 with `network` = network.FusedPolicyValueNetwork at the leaves, `playouts` playouts a move) against
     `opponent` = (name, kwargs) as in DATA_CONFIG["schedule"] ("traditional_mcts" -- with {"use_rave": True} TraditionalPolicy + RAVE --,
@@ -808,7 +811,10 @@ def play_evaluation_games(n_games, network, opponent, playouts=400, c_puct=5.0, 
     match has few games, so this is what fills the network's batch; both loops play the same games.
     vcf = (depth, budget): the network's searches -- not the opponent's -- solve forced wins by fours at their leaves
     (lib.AlphaZeroMCTS(vcf_depth=, vcf_budget=)); None: they do not.  proof: they carry proven wins and losses up their trees, and the
-    network's moves are chosen by them on both loops (lib.AlphaZeroMCTS(proof=)).
+    network's moves are chosen by them on both loops (lib.AlphaZeroMCTS(proof=)).  vcf_defend (with vcf and proof): they also prove the
+    replies that lose to the opponent's forced win by fours (lib.AlphaZeroMCTS(vcf_defend=)); it applies to the K7 handle only.  Such a search
+    spends its playouts below the few replies that hold, so a kept subtree stays nearly whole while the replies are forced: node_capacity (the K7
+    handle's nodes per game; None: three searches' worth with kept subtrees) makes room, and the records' overflow says when an arena filled.
     Returns (GameRecords, network_is_black bool[n], scores float[n]); the records' visit counts at move i are the mover's, and
     records.groups lists per group the games, the unfinished count and the K7 handle's live games after the loop."""
     kind = opponent[0]
@@ -837,13 +843,13 @@ def play_evaluation_games(n_games, network, opponent, playouts=400, c_puct=5.0, 
     else:
         visits = np.zeros((n_games, N, N), dtype=np.uint16)
     overflow, groups = False, []
-    net_cap = min((3 if reuse_subtree else 1) * playouts * N + 1, (1 << 24) - 1)
+    net_cap = node_capacity if node_capacity is not None else min((3 if reuse_subtree else 1) * playouts * N + 1, (1 << 24) - 1)
     for gi, idx in enumerate((np.nonzero(black)[0], np.nonzero(~black)[0])):
         k = len(idx)
         if k == 0:
             groups.append({"games": idx, "unfinished": 0, "live_games": 0})
             continue
-        net = G.AlphaZeroMCTS(k, node_capacity=net_cap, c_puct=c_puct, leaves=leaves, proof=proof, **_vcf_options(vcf))
+        net = G.AlphaZeroMCTS(k, node_capacity=net_cap, c_puct=c_puct, leaves=leaves, proof=proof, vcf_defend=vcf_defend, **_vcf_options(vcf))
         net.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS["counter"])
         net.set_game_ids(np.asarray(idx, dtype=np.uint32))
         net.set_roots(G.moves_to_planes(games.moves[idx], games.lens[idx]), games.last_two()[idx])

@@ -38,9 +38,10 @@ class EvaluationSchedule:
     MCTS opponent up by 2 * c_iterations or, past 20 000, moves on to the next candidate.  leaves: the leaves per game per step of the
     network's searches in the match (selfplay.play_evaluation_games(leaves=); 1 = the reference's search, one leaf at a time).  vcf: (depth,
     budget) of the forced-win solver at the leaves of those searches (selfplay.play_evaluation_games(vcf=)), None = off.  proof: those searches
-    carry proven wins and losses up their trees (selfplay.play_evaluation_games(proof=))."""
+    carry proven wins and losses up their trees (selfplay.play_evaluation_games(proof=)).  vcf_defend: with vcf and proof, they prove the replies
+    that lose to the opponent's forced win by fours (selfplay.play_evaluation_games(vcf_defend=))."""
 
-    def __init__(self, supervisor=SUPERVISOR, candidates=CANDIDATES, eval_rounds=11, c_iterations=400, leaves=1, vcf=None, proof=False):
+    def __init__(self, supervisor=SUPERVISOR, candidates=CANDIDATES, eval_rounds=11, c_iterations=400, leaves=1, vcf=None, proof=False, vcf_defend=False):
         if not candidates:
             raise ValueError("EvaluationSchedule: at least one candidate (None = the supervisor)")
         if not 1 <= int(leaves) <= 8:
@@ -50,6 +51,7 @@ class EvaluationSchedule:
             raise ValueError("EvaluationSchedule: vcf is (depth in [1, 32], budget in [1, 2^20]) or None")
         self.vcf = None if vcf is None else (int(vcf[0]), int(vcf[1]))
         self.proof = bool(proof)
+        self.vcf_defend = bool(vcf_defend)
         self.supervisor, self.candidates = supervisor, list(candidates)
         self.eval_rounds, self.c_iterations = int(eval_rounds), int(c_iterations)
         self.schedule_level, self.ref_iterations, self.best_win_rate = 0, self.c_iterations, 0.0
@@ -188,6 +190,8 @@ class TrainingLoop:
             options.setdefault("vcf", sch.vcf)
         if getattr(sch, "proof", False):
             options.setdefault("proof", True)
+        if getattr(sch, "vcf_defend", False):
+            options.setdefault("vcf_defend", True)
         rec, network_is_black, scores = selfplay.play_evaluation_games(sch.eval_rounds, network, (name, kwargs), playouts=self.eval_playouts, **options)
         win_rate = float(scores.mean())
         events = sch.update(win_rate)

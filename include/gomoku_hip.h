@@ -206,7 +206,8 @@ int gmk_mcts_add_root_noise(gmk_mcts *m, float alpha, float epsilon, void *strea
  *   the games (the second form the tests hold the persistent one to); 0 (default) = persistent wherever the configuration allows. */
 enum { GMK_OPT_NOISE_SAMPLER = 1, GMK_OPT_LOCKSTEP = 2, GMK_OPT_AZ_LEAVES = 3 /* K7 only: see gmk_az_set_option */,
        GMK_OPT_AZ_VCF_DEPTH = 4, GMK_OPT_AZ_VCF_BUDGET = 5 /* K7 only: see "K7 + K14" */,
-       GMK_OPT_AZ_PROOF = 6 /* K7 only: see "K7 + proofs" */ };
+       GMK_OPT_AZ_PROOF = 6 /* K7 only: see "K7 + proofs" */,
+       GMK_OPT_AZ_VCF_DEFEND = 7 /* K7 only: see "K7 + K15" */ };
 #define GMK_AZ_MAX_LEAVES 8
 enum { GMK_NOISE_SAMPLER_STD = 0, GMK_NOISE_SAMPLER_COUNTER = 1 };
 int gmk_mcts_set_option(gmk_mcts *m, int option, int value);
@@ -621,6 +622,43 @@ int gmk_az_vcf_verdicts_host(gmk_az* a, int32_t* h_status, int32_t* h_move, int3
 enum { GMK_AZ_PROOF_NONE = 0, GMK_AZ_PROOF_WINS = 1, GMK_AZ_PROOF_LOSES = 2 };
 int gmk_az_root_proofs(gmk_az* a, int8_t* h_root, int8_t* h_children);
 int gmk_az_proof_stats(gmk_az* a, uint32_t* h_proved, uint32_t* h_stops);
+/* ---- K7 + K15: the replies that lose to a forced win by fours, proven at the leaves of the network search ----
+ * GMK_OPT_AZ_VCF_DEFEND of gmk_az_set_option: 0 (default) or 1, anything else GMK_ERR_ARG; GMK_ERR_STATE in the states in which options 4 to 6
+ * are refused (the marks are up, or a gmk_az_select waits for its gmk_az_expand).  The option ACTS only on a handle that also has
+ * GMK_OPT_AZ_VCF_DEPTH = D > 0 and GMK_OPT_AZ_PROOF = 1; with either of them off it is accepted and inert: every entry launches exactly the
+ * kernels it launches without this block and the search is bit for bit that handle's without the option.  The option call that makes it act
+ * for the first time allocates, per row of the largest leaf batch (n_games x GMK_AZ_MAX_LEAVES), 16 + GMK_VCF_PV + 32 + 900 bytes; nothing is
+ * allocated inside a step.  If that allocation fails the call returns GMK_ERR_HIP and the block stays inert.
+ * While it acts, gmk_az_select computes for every pending leaf P whose "K7 + K14" verdict is neither WIN nor OVER, in two more kernels behind
+ * that block's on the same stream (one linear chain):
+ *   1. threat = K14's walk on P with the side that is NOT to move attacking (GMK_VCF_OPPONENT), plain mode, max_depth = D, budget = B, the
+ *      handle's "K7 + K14" settings; its principal variation is kept.
+ *   2. threat.status == GMK_VCF_WIN: for every cell c the verdict of "K15"'s table (below) in plain mode for P: occupied NONE; otherwise
+ *      follow(0) against the threat's pv with a stone of the side to move on c, and only on FAIL solve(P + [c]) with the whole budget B.
+ *      GMK_VCF_CELL_FIVE cannot occur: a leaf with a completing cell of its own is a "K7 + K14" WIN (K14 answers it before any limit).
+ *   3. Any other threat status (NONE, DEPTH, BUDGET) marks nothing.
+ * The threat and the table equal gmk_vcf_defend's for the leaf's move list with (D, B, flags 0), bit for bit: threat status and length, and
+ * verdict and nodes per cell.
+ * gmk_az_expand then, for such a leaf under a WIN threat, once its children exist and unless the playout was dropped for a full arena:
+ *   every child whose cell is GMK_VCF_CELL_LOSES gets GMK_AZ_PROOF_WINS -- the opponent, to move there, has a forced win.  The bit is written
+ *   with the child's word, not through prove: one WINS child proves nothing about its parent.  Each such child counts once in `proved`.
+ *   If the leaf has a child for every free cell (children == 225 - stones) and every child is now WINS: prove(leaf, GMK_AZ_PROOF_LOSES), which
+ *   climbs by "K7 + proofs"'s rule, and +1.0f is backed up from the leaf in place of -value.
+ *   Otherwise the network's value and row are used as they are.  Priors are never changed: the descent already leaves WINS children out of
+ *   the maximum and stops at a marked child without a network row.
+ * A dropped leaf gets no mark and counts nowhere.  Virtual loss, quota, the order of the pending leaves, d_values and d_probs are untouched.
+ * Everything is exact integer work: no float, no atomics; a captured step stays one chain of kernels.
+ * gmk_az_defend_stats: per game, uint32[n_games] x 3 and uint64[n_games], any pointer may be NULL: the leaves expanded under a WIN threat, the
+ *   children marked, the cells solved in full (step 2's solve) and the nodes of those solves; cleared where the "K7 + K14" counters are
+ *   cleared.  Synchronises.
+ * gmk_az_defend_verdicts_host: for the gmk_az_live_games x L rows of the last gmk_az_select: h_threat_status int32[rows], h_threat_length
+ *   int32[rows], h_verdict int8[rows][225] (GMK_VCF_CELL_*), h_nodes uint32[rows][225]; any pointer may be NULL.  A row without a pending leaf,
+ *   or whose "K7 + K14" verdict is WIN or OVER, reads threat NONE, length 0 and all-zero cells; a pending leaf whose threat is NONE reads HOLDS
+ *   on its free cells, one whose threat is DEPTH or BUDGET reads UNKNOWN there, as K15's table has them.  GMK_ERR_STATE unless the option
+ *   acts.  Synchronises.
+ * The host-driven one-leaf entries that refuse a handle whose D > 0 refuse one whose GMK_OPT_AZ_VCF_DEFEND is 1 in the same way. */
+int gmk_az_defend_stats(gmk_az* a, uint32_t* h_threatened, uint32_t* h_marked, uint32_t* h_searched, uint64_t* h_nodes);
+int gmk_az_defend_verdicts_host(gmk_az* a, int32_t* h_threat_status, int32_t* h_threat_length, int8_t* h_verdict, uint32_t* h_nodes);
 
 /* ---- K12: the referee of a match between two search handles, on the device (match_kernel.hip) ----
  * One ply of n two-agent games without the host in the loop (agents/utils.py:13-63 dual_play, :66-100 eval_agents): the side to move has
