@@ -1,5 +1,6 @@
 """The float64 training-step reference (tests/train_reference.py) earns its trust on the CPU before the trainer's kernels are held to it."""
 import numpy as np
+import pytest
 import torch
 
 import train_reference as T
@@ -108,3 +109,76 @@ def test_adam_reproduces_a_scalar_worked_by_hand():
     vb = 0.999 * 0.00025 + 0.001 * 0.0625
     assert abs(p2["b_out"][0] - (b1 - lr2 * mb / (np.sqrt(vb) + 1e-8))) < 1e-15
     assert p2["w1"].max() == 0 and p2["w1"].min() == 0
+
+
+# ---------------- the five-order yardstick and the cases of tests/test_train_seams_gpu.py ----------------
+PARITY_CASES = ["seam-%d" % n for n in T.SEAM_BATCHES] + ["underflow", "not_distributions"]
+
+
+@pytest.mark.parametrize("name", PARITY_CASES)
+def test_five_order_yardstick_holds_float32_itself(name):
+    """torch float32 in a sixth and a seventh sample order, neither among the yardstick's five, stays within GRAD_LIMIT / 4 of it at every case the
+    kernel is held to GRAD_LIMIT on (largest seen with 1, 8 and 16 threads: 1.35); half a w2 gradient is still far outside.  A case that misses this gets another seed."""
+    ref = T.case_reference(name)
+    n = len(ref["batch"][0])
+    orders = [T.sample_order(n, i) for i in range(T.YARD_ORDERS + 2)]
+    if n > 4:                                              # 4! = 24 orders: two seeded draws may coincide there
+        assert len({tuple(o) for o in orders}) == len(orders)
+    for i in (T.YARD_ORDERS, T.YARD_ORDERS + 1):
+        g32, _, _ = T.gradients(ref["params"], T.reordered(ref["batch"], orders[i]), torch.float32)
+        ratios = T.sturdy_ratios(g32, ref["g64"], ref["yard"])
+        print("%s order %d: worst %.3f (%s)" % (name, i, max(ratios.values()), max(ratios, key=ratios.get)))
+        assert max(ratios.values()) <= T.GRAD_LIMIT / 4, ratios
+    broken = dict(ref["g64"])
+    broken["w2"] = ref["g64"]["w2"] * 0.5
+    assert T.sturdy_ratios(broken, ref["g64"], ref["yard"])["w2"] > 2 * T.GRAD_LIMIT
+    assert all(y > 0 for y in ref["yard"].values())
+
+
+def test_five_order_yardstick_is_the_largest_of_five_and_exact_where_float32_is():
+    ref = T.case_reference("dead_layer3")
+    errs = T.float32_errors(ref["params"], ref["batch"], ref["g64"])
+    g32, _, _ = T.gradients(ref["params"], ref["batch"], torch.float32)
+    for k in T.NAMES:
+        assert len(errs[k]) == T.YARD_ORDERS and ref["yard"][k] == max(errs[k])
+        assert errs[k][0] == float(np.abs(g32[k] - ref["g64"][k]).max())             # order 0 is the batch as given: gradient_ratios' yardstick
+    assert max(T.sturdy_ratios(ref["g64"], ref["g64"], ref["yard"]).values()) == 0.0
+    off = dict(ref["g64"])
+    off["w1"] = ref["g64"]["w1"] + 1e-30                                               # all five yardsticks are 0 there: nothing but 0 passes
+    assert ref["yard"]["w1"] == 0.0 and T.sturdy_ratios(off, ref["g64"], ref["yard"])["w1"] == float("inf")
+
+
+def _pre_activations(params, states):
+    with torch.no_grad():
+        logits, s = T.forward({k: torch.tensor(params[k], dtype=torch.float64) for k in T.NAMES}, torch.tensor(states, dtype=torch.float64))
+    return logits.numpy(), s.numpy()
+
+
+def test_degenerate_cases_are_what_they_claim():
+    """The premises of the exact-zero and degenerate GPU tests, in float64 and in torch float32, without a GPU."""
+    for kind, zeros in (("dead_layer3", T.DEAD_ZEROS), ("dead_layer2", T.DEAD2_ZEROS), ("saturated_tanh", T.SATURATED_ZEROS)):
+        ref = T.case_reference(kind)
+        g32, _, _ = T.gradients(ref["params"], ref["batch"], torch.float32)
+        for g in (ref["g64"], g32):
+            assert sorted(k for k in T.NAMES if not np.any(g[k])) == sorted(zeros), kind
+    sat = T.case_reference("saturated_tanh")
+    _, s = _pre_activations(sat["params"], sat["batch"][0])
+    assert (np.abs(s) >= 20).all(), s
+    want = float(np.mean((np.sign(s) - sat["batch"][1].astype(np.float64)) ** 2))
+    assert abs(sat["terms"]["value_loss"] - want) <= 1e-12 and abs(sat["terms32"]["value_loss"] - want) <= 1e-6
+
+    under = T.case_reference("underflow")
+    logits, _ = _pre_activations(under["params"], under["batch"][0])
+    assert ((logits.max(1) - logits.min(1)) >= 200).all(), logits.max(1) - logits.min(1)
+    pi = under["batch"][2]
+    assert ((pi == 1).sum(1) == 1).all() and ((pi == 0).sum(1) == 224).all() and (pi.argmax(1) == logits.argmin(1)).all()
+    assert (under["probs"].astype(np.float32) == 0).mean() > 0.25                      # float32 holds exact zeros where float64 holds 1e-60
+    assert all(np.isfinite(v) for v in under["terms"].values()) and all(np.isfinite(v) for v in under["terms32"].values())
+
+    pi = T.case_reference("not_distributions")["batch"][2]
+    sums = pi.sum(1)
+    assert sums[0] == 0 and abs(sums[1] - 0.5) < 1e-5 and sums[2] == 1 and (pi[2] == 1).sum() == 1 and abs(sums[3] - 1) < 1e-5
+
+    old = T.sparse_old_probs(4)
+    assert old.dtype == np.float32 and old.shape == (4, 225) and ((old == 0).sum(1) > 0).all() and ((old > 0).sum(1) > 0).all()
+    assert T.kl_divergence(old, under["probs"]) > 1.0                                  # mass where the underflowing net has none: a KL that matters
