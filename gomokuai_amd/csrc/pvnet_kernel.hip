@@ -574,7 +574,7 @@ static_assert(gmk::pvpack::kPix == kPix && gmk::pvpack::kHeadRows == kHeadRows &
 extern "C" int gmk_pvnet_destroy(gmk_pvnet* net) {
     if (!net) return GMK_OK;
     (void)hipFree(net->d_w1); (void)hipFree(net->d_w2); (void)hipFree(net->d_w3); (void)hipFree(net->d_wh); (void)hipFree(net->d_b);
-    (void)hipFree(net->d_wp); (void)hipFree(net->d_dense); (void)gmk::device_free(net->d_flat);
+    (void)hipFree(net->d_wp); (void)hipFree(net->d_dense); (void)gmk::device_free(net->d_flat); (void)hipFree(net->d_q);
     delete net;
     return GMK_OK;
 }
@@ -607,6 +607,7 @@ extern "C" int gmk_pvnet_create(const float* w1, const float* b1, const float* w
 namespace {
 
 int launch_trunk(gmk_pvnet* net, const float* d_states, int n, float* d_pflat, float* d_vflat, hipStream_t stream) {
+    if (net->precision == GMK_PVNET_BF16) return gmk::pvnet_bf16_launch(net, d_states, n, d_pflat, d_vflat, stream);   // "K9 in bf16": pvnet_bf16_kernel.hip
     gmk::DeviceState& st = gmk::device_state();
     const size_t lds = static_cast<size_t>(kLdsFloats) * 4;
     if (!net->attr_set) {

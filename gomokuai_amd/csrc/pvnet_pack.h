@@ -98,4 +98,15 @@ struct gmk_pvnet {
     float b_out = 0.0f;
     bool has_dense = false, dense_attr_set = false;
     int flat_capacity = 0;
+    // "K9 in bf16" (gmk_pvnet_set_precision): the bf16 weight buffer derived from d_w1 .. d_wh (pvnet_bf16_pack.h), allocated at the first
+    // switch to GMK_PVNET_BF16 and kept; `precision` picks the trunk kernel
+    int precision = 0;                               // GMK_PVNET_F32
+    unsigned short* d_q = nullptr;
+    bool bf16_attr_set = false;
 };
+
+namespace gmk {
+// pvnet_bf16_kernel.hip: the bf16 trunk in place of pvnet_trunk_kernel, and d_q refreshed from d_w1 .. d_wh by one kernel on `stream`
+int pvnet_bf16_launch(gmk_pvnet* net, const float* d_states, int n, float* d_pflat, float* d_vflat, void* stream);
+int pvnet_bf16_refresh(gmk_pvnet* net, void* stream);
+}  // namespace gmk

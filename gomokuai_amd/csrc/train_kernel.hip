@@ -636,6 +636,7 @@ extern "C" int gmk_train_export(gmk_trainer* T, gmk_pvnet* net, void* stream) {
     for (int b = 0; b <= kRepackBuffers; ++b) a.seg[b] = static_cast<int>(T->seg[b]);
     hipLaunchKernelGGL(pvnet_repack_kernel, dim3((a.seg[kRepackBuffers] + 255) / 256), dim3(256), 0, st, T->d_params, T->d_table, a);
     GMK_HIP_CHECK(hipGetLastError());
+    if (net->precision == GMK_PVNET_BF16) GMK_TRY(gmk::pvnet_bf16_refresh(net, stream));      // the bf16 trunk streams its own roundings of these weights
     // the output bias is a by-value kernel argument of K9's dense kernel, so it lives in the handle on the host: four bytes are read back here
     float b_out = 0.0f;
     GMK_HIP_CHECK(hipMemcpyAsync(&b_out, T->param(BOUT), sizeof(float), hipMemcpyDeviceToHost, st));

@@ -34,6 +34,8 @@ OPT_AZ_VCF_DEPTH, OPT_AZ_VCF_BUDGET = 4, 5     # K7 + K14: forced wins by fours 
 OPT_AZ_PROOF = 6                               # K7 + proofs: proven wins and losses carried up the tree (AlphaZeroMCTS(proof=))
 AZ_PROOF_NONE, AZ_PROOF_WINS, AZ_PROOF_LOSES = 0, 1, 2
 OPT_AZ_VCF_DEFEND = 7                          # K7 + K15: the replies that lose to a forced win by fours, proven at the leaves (AlphaZeroMCTS(vcf_defend=))
+PVNET_F32, PVNET_BF16 = 0, 1                   # GMK_PVNET_*: gmk_pvnet_set_precision (FusedPolicyValueNetwork(precision=))
+PVNET_PRECISIONS = {"f32": PVNET_F32, "bf16": PVNET_BF16}
 AZ_MAX_LEAVES = 8                              # GMK_AZ_MAX_LEAVES: leaves per game per step of a K7 handle (AlphaZeroMCTS(leaves=))
 NOISE_SAMPLERS = {"std": 0, "counter": 1}      # std::gamma_distribution on the host / the counter-based sampler of include/gomoku_noise.h on the device
 
@@ -49,6 +51,7 @@ EXPORTS = [
     "gmk_evalstate_create", "gmk_evalstate_destroy", "gmk_evalstate_reset", "gmk_evalstate_update", "gmk_evalstate_update_host", "gmk_evalstate_read",
     "gmk_az_create", "gmk_az_destroy", "gmk_az_set_roots", "gmk_az_select", "gmk_az_expand", "gmk_az_select_host", "gmk_az_expand_host", "gmk_az_read_node_host", "gmk_az_read_children_host", "gmk_az_set_leaf_host", "gmk_az_rollout_host", "gmk_az_expand_stages_host", "gmk_az_write_stats_host", "gmk_az_step", "gmk_az_root_choice", "gmk_az_step_device", "gmk_az_advance", "gmk_az_set_slots", "gmk_az_live_games", "gmk_az_set_game_ids", "gmk_az_add_root_noise", "gmk_az_set_option", "gmk_az_add_playouts", "gmk_az_playouts_owed", "gmk_az_root_stats", "gmk_az_vcf_stats", "gmk_az_vcf_verdicts_host", "gmk_az_defend_stats", "gmk_az_defend_verdicts_host", "gmk_az_root_proofs", "gmk_az_proof_stats",
     "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_root_choice", "gmk_trad_step_device", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_run_rave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
+    "gmk_pvnet_set_precision", "gmk_pvnet_get_precision", "gmk_bf16_round_host",
     "gmk_pattern_policy", "gmk_pattern_policy_host", "gmk_pattern_play",
     "gmk_vcf_solve", "gmk_vcf_solve_host", "gmk_vcf_defend", "gmk_vcf_defend_host",
     "gmk_vcf_threats", "gmk_vcf_threats_host", "gmk_vct_solve", "gmk_vct_solve_host",
@@ -173,6 +176,9 @@ def load():
     L.gmk_pvnet_forward.argtypes = [vp, vp, C.c_int, vp, vp, vp]
     L.gmk_pvnet_set_dense.argtypes = [vp] * 6 + [C.c_float]
     L.gmk_pvnet_evaluate.argtypes = [vp, vp, C.c_int, vp, vp, vp]
+    L.gmk_pvnet_set_precision.argtypes = [vp, C.c_int]
+    L.gmk_pvnet_get_precision.argtypes = [vp, C.POINTER(C.c_int)]
+    L.gmk_bf16_round_host.argtypes = [vp, C.c_size_t, vp]
     L.gmk_samples_from_records.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.gmk_records_scan.argtypes = [vp, C.c_int, vp, vp]
     L.gmk_records_packed_bytes.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_uint64), vp]

@@ -60,11 +60,17 @@ class FusedPolicyValueNetwork:
     """The same function as PolicyValueNetwork.forward in two HIP kernels on the f32 matrix cores (gmk_pvnet_evaluate): the convolutions (99 % of
     the arithmetic) as ONE fused kernel whose activations never leave LDS (K9), and the three dense layers with softmax / tanh as a second one.
     float32 throughout; sums run in a different order than MIOpen's / rocBLAS's, so outputs agree with the module's to rounding
-    (tests/test_pvnet_gpu.py: 2e-5), not bit for bit.  Takes the weights of `net` at construction."""
+    (tests/test_pvnet_gpu.py: 2e-5), not bit for bit.  Takes the weights of `net` at construction.
 
-    def __init__(self, net):
+    precision="bf16" runs the convolutions on the bf16 matrix cores instead ("K9 in bf16", include/gomoku_hip.h: weights, inputs and
+    activations rounded to bf16, float32 accumulation, the dense layers unchanged): faster, and within the rounding bound of
+    tests/pvnet_bf16_reference.py of the float64 network rather than float32's.  set_precision() switches an existing handle either way."""
+
+    def __init__(self, net, precision="f32"):
         import ctypes as C
         from . import lib as G
+        if precision not in G.PVNET_PRECISIONS:
+            raise ValueError("FusedPolicyValueNetwork: precision must be one of %s, not %r" % (sorted(G.PVNET_PRECISIONS), precision))
         G.init()
         self.net, self.G, self.h = net, G, C.c_void_p()
         host = lambda t: np.ascontiguousarray(t.detach().float().cpu().numpy())
@@ -77,6 +83,24 @@ class FusedPolicyValueNetwork:
                  host(net.value_out.weight).reshape(64)]
         assert dense[0].shape == (225, 900) and dense[2].shape == (64, 450)
         G._check(G.load().gmk_pvnet_set_dense(self.h, *[a.ctypes.data for a in dense], float(net.value_out.bias.detach().cpu().reshape(-1)[0])))
+        if precision != "f32":
+            self.set_precision(precision)
+
+    @property
+    def precision(self):
+        """"f32" or "bf16": what the handle's trunk runs in (gmk_pvnet_get_precision)"""
+        import ctypes as C
+        out = C.c_int(0)
+        self.G._check(self.G.load().gmk_pvnet_get_precision(self.h, C.byref(out)))
+        return {v: k for k, v in self.G.PVNET_PRECISIONS.items()}[out.value]
+
+    def set_precision(self, precision):
+        """Switches the trunk between "f32" and "bf16" (gmk_pvnet_set_precision: blocking, packs the bf16 weights from the handle's current ones;
+        not while a call on this network is in flight on another stream)."""
+        if precision not in self.G.PVNET_PRECISIONS:
+            raise ValueError("FusedPolicyValueNetwork: precision must be one of %s, not %r" % (sorted(self.G.PVNET_PRECISIONS), precision))
+        self.G._check(self.G.load().gmk_pvnet_set_precision(self.h, self.G.PVNET_PRECISIONS[precision]))
+        return self
 
     def close(self):
         if getattr(self, "h", None) and getattr(self, "G", None) is not None and self.G.load is not None:

@@ -742,6 +742,30 @@ int gmk_pvnet_set_dense(gmk_pvnet* net, const float* w_policy, const float* b_po
                         const float* w_out, float b_out);
 int gmk_pvnet_evaluate(gmk_pvnet* net, const float* d_states, int n, float* d_value, float* d_probs, void* stream);
 
+/* ---- K9 in bf16: the same trunk on the bf16 matrix cores, opt-in per handle ----
+ * A handle evaluates in GMK_PVNET_F32 (the default: exactly the kernels above) or GMK_PVNET_BF16.  Precision GMK_PVNET_BF16 evaluates the same
+ * network under these rules, and nothing else changes:
+ *   - the five convolution weight tensors (three 3x3 layers, two 1x1 heads) are rounded once to bf16, round to nearest, ties to even; biases
+ *     and the three dense layers stay float32;
+ *   - the input planes are rounded to bf16 on load (the 0/1 planes K7 feeds are exact);
+ *   - every convolution accumulates in float32 on the matrix cores (v_mfma_f32_32x32x16_bf16), the 3x3 layers starting from their float32 bias;
+ *   - after ReLU the activations of layers 1, 2 and 3 are rounded to bf16 (nearest even): they feed the next matrix instruction;
+ *   - the 1x1 heads take the bf16 layer-3 activations and bf16 weights; each of the four wavefronts sums its 32 channels, the four partial
+ *     sums are added in float32 in wavefront order, then the float32 head bias and ReLU: d_pflat / d_vflat are float32;
+ *   - the dense kernel is the float32 one, unchanged, on those rows;
+ *   - no float atomics: the same inputs give the same bits, and a row's outputs depend neither on the batch nor on where the row sits in it.
+ * gmk_pvnet_set_precision: blocking (it synchronises the device and, for GMK_PVNET_BF16, packs the bf16 weights from the handle's current ones);
+ *   not while a call on this handle is in flight on another stream, as for gmk_pvnet_set_dense.  GMK_ERR_ARG for a NULL handle or any other
+ *   precision.  gmk_pvnet_forward and gmk_pvnet_evaluate run the trunk of the handle's precision; gmk_train_export also refreshes the bf16
+ *   weights of a handle that is in GMK_PVNET_BF16, on its stream.  A handle switched back to GMK_PVNET_F32 gives the float32 bits again.
+ * gmk_pvnet_get_precision: *precision = the handle's.  GMK_ERR_ARG for a NULL argument.
+ * gmk_bf16_round_host: dst[i] = the bf16 bits of src[i] as the packer rounds them (nearest even; NaN -> 0x7FC0; beyond the largest bf16 -> Inf).
+ *   Needs no GPU and no gmk_init.  GMK_ERR_ARG for a NULL pointer with n > 0. */
+enum { GMK_PVNET_F32 = 0, GMK_PVNET_BF16 = 1 };
+int gmk_pvnet_set_precision(gmk_pvnet* net, int precision);
+int gmk_pvnet_get_precision(gmk_pvnet* net, int* precision);
+int gmk_bf16_round_host(const float* src, size_t n, uint16_t* dst);
+
 /* ---- K10: the pattern heuristic on its own, per position and for whole greedy games ----
  * Heuristic::EvaluationProbs, DecisiveFilter and EvaluationValue (core/lib/include/algorithms/Heuristic.hpp:16-45, 94-161) for a batch, outside
  * any tree.  filter: 1 = EvaluationProbs + DecisiveFilter (PatternEvalAgent::getAction, core/interface/src/Agent.h:107-160, and
