@@ -17,7 +17,8 @@
 // behind the select kernel), and the expand kernels answer a solved leaf themselves: include/gomoku_hip.h, "K7 + K14".
 // With GMK_OPT_AZ_VCF_DEFEND on top of that and of GMK_OPT_AZ_PROOF the leaves the solver did not answer are asked what the opponent threatens
 // (az_threat_leaves_kernel) and which replies lose to it (az_defend_leaves_kernel, K15's table), and the expand kernels mark those children as the
-// opponent's proven wins: include/gomoku_hip.h, "K7 + K15".
+// opponent's proven wins: include/gomoku_hip.h, "K7 + K15".  Those three kernels hold no walk of their own: K14's walk is vcf_device.h's, and
+// they are its loaders for a leaf and its endings.
 // Mapping: one wavefront per game, lanes over the (<= 225) children; the tree is an SoA arena per game in HBM.
 #include <algorithm>
 #include <cmath>
@@ -664,286 +665,142 @@ void az_expand_leaves_kernel(AzTree t, AzLeaves lv, const float* values, const f
 }
 
 // ---- K7 + K14: forced wins by fours at the pending leaves (GMK_OPT_AZ_VCF_DEPTH = D > 0) ----
-// K14's walk (vcf_kernel.hip, the contract in include/gomoku_hip.h "K14") in plain mode with the side to move attacking, restated around another
-// loader and another finish; the row gather and the geometry of fours are vcf_device.h's.  One board ROW per lane, sixteen lanes per leaf, four
-// leaves per wavefront, one wavefront per workgroup.  Group i of the launch takes game i / L's leaf i % L: a finished game or a k >= n_pending
-// (L = 1: a leaf that is not pending) leaves the group idle, so the live games' leaves are found by skipping, which is row_of read forwards, and
-// the verdict goes to row row_of[game] * L + k of the leaf batch.  Lane y reads ONE word of the leaf's sixteen (black | white << 16; word 15 is
-// zero) and splits it into attacker and defender by the leaf's stone count: no move list exists and none is built.  A pending leaf is a position
-// the select kernel built from legal moves, so K14's BAD cannot arise; OVER can, from a root given with a five on it.  No principal variation is
-// kept beyond the first move.  No float, no atomics, no barrier, nothing allocated.
+// The three kernels below run K14's walk (the contract in include/gomoku_hip.h "K14"), which is vcf_device.h's: pass, start and step, one board
+// ROW per lane, sixteen lanes per leaf.  What stands here is their loaders and their endings.  Lane y reads ONE word of the leaf's sixteen
+// (black | white << 16; word 15 is zero) and splits it into attacker and defender by the leaf's stone count: no move list exists and none is
+// built.  A pending leaf is a position the select kernel built from legal moves, so K14's BAD cannot arise; OVER can, from a root given with a
+// five on it.  The walks are in plain mode (no iterative deepening).  No float, no atomics, no barrier, nothing allocated.
+
+// Row `item` of a launch over n_games * L leaves is game item / L's leaf item % L.  False where there is no such leaf or the game is finished;
+// the live games' leaves are found by skipping, which is row_of read forwards: out_row = row_of[game] * L + k is the leaf's row of the batch.
+__device__ __forceinline__ bool leaf_of(const AzTree& t, const AzLeaves& lv, long long item, int& game, int& k, size_t& out_row) {
+    if (item >= static_cast<long long>(t.n_games) * lv.leaves) return false;
+    game = static_cast<int>(item / lv.leaves);
+    k = static_cast<int>(item - static_cast<long long>(game) * lv.leaves);
+    if (t.hdr[game].status & kStatusOver) return false;
+    out_row = static_cast<size_t>(t.row_of[game]) * lv.leaves + static_cast<size_t>(k);
+    return true;
+}
+// Leaf k of `game` waits for an answer (L = 1: the game's one leaf does).
+__device__ __forceinline__ bool leaf_pending(const AzTree& t, const AzLeaves& lv, int game, int k) {
+    const AzHeader* hdr = t.hdr + game;
+    return lv.leaves > 1 ? static_cast<uint32_t>(k) < hdr->n_pending : hdr->leaf_pending != 0u;
+}
+// This lane's word and the stone count of leaf k of `game`: the leaf's row y of black and of white; white is to move on odd stone counts.
+struct LeafRow {
+    uint32_t black, white;
+    bool white_to_move;
+};
+__device__ __forceinline__ LeafRow leaf_row(const AzTree& t, const AzLeaves& lv, int game, int k, int y) {
+    const AzHeader* hdr = t.hdr + game;
+    const bool many = lv.leaves > 1;
+    const AzPending* pd = lv.pend + static_cast<size_t>(game) * GMK_AZ_MAX_LEAVES + (many ? k : 0);
+    const uint32_t word = many ? pd->rows[y] : hdr->leaf_rows[y];
+    const uint32_t stones = many ? pd->stones : hdr->leaf_stones;
+    return {word & gmk::vcf::kRowMask, (word >> 16) & gmk::vcf::kRowMask, (stones & 1u) != 0};
+}
+
+// The side to move attacks.  Four leaves per wavefront, one wavefront per workgroup: group i of the launch takes row i (leaf_of); a leaf that
+// is not pending leaves the group idle.  The verdict goes to the leaf's row of the batch; no principal variation is kept beyond the first move.
 __global__ __launch_bounds__(64)
 void az_vcf_leaves_kernel(AzTree t, AzLeaves lv, AzVcf vc) {
     namespace V = gmk::vcf;
-    __shared__ uint32_t stack[V::kLevels][64];                   // per level and lane: candidates left 0..14, "the level has more" 15, c 16..23, r 24..31
-    const int lane = threadIdx.x, y = lane & 15, group = lane >> 4, gbase = lane & 48;
-    const uint32_t board_row = y < 15 ? V::kRowMask : 0u;
-    const int limit = vc.max_depth;
-
-    int state = V::kIdle, depth = 0;
+    __shared__ V::Stack stack;
+    const V::Lane ln;
+    V::Walk w;
+    w.limit = vc.max_depth;
+    int game = 0, k = 0;
     size_t out_row = 0;
-    bool cut = false, more = false;
-    uint32_t nodes = 0, att = 0, def = 0, mask = 0;
 
     // ---- the loader ----
-    const long long item = static_cast<long long>(blockIdx.x) * 4 + group;
-    if (item < static_cast<long long>(t.n_games) * lv.leaves) {
-        const int game = static_cast<int>(item / lv.leaves), k = static_cast<int>(item - static_cast<long long>(game) * lv.leaves);
-        const AzHeader* hdr = t.hdr + game;
-        if (!(hdr->status & kStatusOver)) {
-            out_row = static_cast<size_t>(t.row_of[game]) * lv.leaves + static_cast<size_t>(k);
-            const bool many = lv.leaves > 1;
-            const bool pending = many ? static_cast<uint32_t>(k) < hdr->n_pending : hdr->leaf_pending != 0u;
-            if (pending) {
-                const AzPending* pd = lv.pend + static_cast<size_t>(game) * GMK_AZ_MAX_LEAVES + (many ? k : 0);
-                const uint32_t word = many ? pd->rows[y] : hdr->leaf_rows[y];
-                const uint32_t stones = many ? pd->stones : hdr->leaf_stones;
-                const uint32_t black = word & V::kRowMask, white = (word >> 16) & V::kRowMask;
-                att = (stones & 1u) ? white : black;             // white is to move on odd stone counts
-                def = (stones & 1u) ? black : white;
-                state = V::kInit;
-            } else if (y == 0) {
-                vc.verdict[out_row] = make_int4(GMK_VCF_NONE, -1, 0, 0);
-            }
+    if (leaf_of(t, lv, static_cast<long long>(blockIdx.x) * 4 + ln.group, game, k, out_row)) {
+        if (leaf_pending(t, lv, game, k)) {
+            const LeafRow r = leaf_row(t, lv, game, k, ln.y);
+            w.reset(r.white_to_move ? r.white : r.black, r.white_to_move ? r.black : r.white, vc.max_depth);
+        } else if (ln.y == 0) {
+            vc.verdict[out_row] = make_int4(GMK_VCF_NONE, -1, 0, 0);
         }
     }
 
     // The group's verdict.  first = the cell that ends a winning line at the root (depth 0), else the first move is on the stack.
     const auto finish = [&](int status, int first, int tail) {
         const bool win = status == GMK_VCF_WIN;
-        if (y == 0)
-            vc.verdict[out_row] = make_int4(status, !win ? -1 : depth > 0 ? static_cast<int>((stack[0][lane] >> 16) & 255u) : first, !win ? 0 : depth + tail,
-                                            static_cast<int>(nodes));
-        state = V::kIdle;
+        if (ln.y == 0)
+            vc.verdict[out_row] = make_int4(status, !win ? -1 : w.depth > 0 ? V::level_c(stack[0][ln.lane]) : first, !win ? 0 : w.depth + tail,
+                                            static_cast<int>(w.nodes));
+        w.state = V::kIdle;
     };
     // The walk has failed at the root, with every move undone.
-    const auto failed = [&]() { finish(cut ? GMK_VCF_DEPTH : GMK_VCF_NONE, -1, 0); };
+    const auto failed = [&]() { finish(w.cut ? GMK_VCF_DEPTH : GMK_VCF_NONE, -1, 0); };
 
-    while (__ballot(state != V::kIdle) != 0ull) {
-        // ---- the pass: every group in the same instructions ----
-        const bool trying = state == V::kRun;                      // such a group has a candidate: `mask` is not empty
-        uint32_t popped = trying ? mask : 0u;
-        const int c = V::take_lowest(popped, y, gbase);
-        const uint32_t left = V::group_rows(popped != 0, gbase);
-        const int cy = trying ? c / 15 : 0;
-        const uint32_t cbit = trying ? 1u << (c - 15 * cy) : 0u;
-        if (trying) {
-            mask = popped;
-            more = left != 0;
-            if (y == cy) att |= cbit;
-        }
-        uint32_t A[9], D[9], N[9];
-        V::gather_rows(att, A);
-        uint32_t F = V::completing(A, board_row & ~(att | def));
-        const int f1 = V::take_lowest(F, y, gbase), f2 = V::take_lowest(F, y, gbase);
-        const bool replied = trying && f1 >= 0 && f2 < 0;          // the forced reply goes on the board
-        const int ry = replied ? f1 / 15 : 0;
-        const uint32_t rbit = replied ? 1u << (f1 - 15 * ry) : 0u;
-        if (replied && y == ry) def |= rbit;
-        const uint32_t empty = board_row & ~(att | def);
-        V::gather_rows(def, D);
-        V::gather_rows(empty | att, N);
-        uint32_t T = V::completing(D, empty);
-        uint32_t C = V::four_making(A, N, empty);
-        if (V::group_rows(T != 0, gbase)) C &= T;                  // a defender four: only its blocking cell is a candidate
-        const int t1 = V::take_lowest(T, y, gbase), t2 = V::take_lowest(T, y, gbase);
-        (void)t1;
-        const bool child_has = V::group_rows(C != 0, gbase) != 0;
-        bool over = false;
-        if (__ballot(state == V::kInit) != 0ull) over = V::group_rows((V::five(A) | V::five(D)) != 0, gbase) != 0;
-
-        // ---- decisions, the same in all sixteen lanes of a group ----
-        if (state == V::kInit) {
-            if (over) finish(GMK_VCF_OVER, -1, 0);
-            else if (f1 >= 0) finish(GMK_VCF_WIN, f1, 1);
-            else {
-                bool fail = t2 >= 0;
-                if (!fail && 2 > limit) { cut = true; fail = true; }
-                if (!fail && !child_has) fail = true;
-                if (fail) failed();
-                else { mask = C; more = true; state = V::kRun; }
-            }
-        } else if (trying) {
-            bool retract = true;
-            if (f1 < 0) {
-                // not a four: no candidate and no node (as vcf_kernel: the plane-wide mask does not offer such a cell)
-            } else if (nodes == vc.budget) {
-                finish(GMK_VCF_BUDGET, -1, 0);
-            } else {
-                ++nodes;
-                if (f2 >= 0) finish(GMK_VCF_WIN, c, 2);
-                else {
-                    bool fail = t2 >= 0;
-                    if (!fail && depth + 3 > limit) { cut = true; fail = true; }
-                    if (!fail && !child_has) fail = true;
-                    if (!fail) {
-                        stack[depth][lane] = mask | (more ? 0x8000u : 0u) | (static_cast<uint32_t>(c) << 16) | (static_cast<uint32_t>(f1) << 24);
-                        ++depth;
-                        mask = C; more = true; retract = false;
-                    } else if (y == ry) def ^= rbit;
-                }
-            }
-            if (state == V::kRun && retract) {
-                if (y == cy) att ^= cbit;
-                while (!more) {                                    // climb while the level has nothing left
-                    if (depth == 0) { failed(); break; }
-                    --depth;
-                    const uint32_t w = stack[depth][lane];
-                    mask = w & V::kRowMask;
-                    more = (w & 0x8000u) != 0;
-                    const int uc = static_cast<int>((w >> 16) & 255u), ur = static_cast<int>(w >> 24);
-                    if (y == uc / 15) att ^= 1u << (uc % 15);
-                    if (y == ur / 15) def ^= 1u << (ur % 15);
-                }
-            }
+    while (__ballot(w.state != V::kIdle) != 0ull) {
+        const V::Pass ps = V::pass(w, ln);
+        if (w.state == V::kInit) {
+            if (ps.over) finish(GMK_VCF_OVER, -1, 0);
+            else if (ps.f1 >= 0) finish(GMK_VCF_WIN, ps.f1, 1);
+            else V::start(w, ps, failed);
+        } else if (w.state == V::kRun) {
+            V::step(w, ln, ps, vc.budget, stack, [&](int c, int, int) { finish(GMK_VCF_WIN, c, 2); }, [&]() { finish(GMK_VCF_BUDGET, -1, 0); }, failed);
         }
     }
 }
 
 // ---- K7 + K15: the replies that lose to a forced win by fours, at the pending leaves (GMK_OPT_AZ_VCF_DEFEND; include/gomoku_hip.h "K7 + K15") ----
 // Two further links of gmk_az_select's chain behind az_vcf_leaves_kernel, for a handle whose solver and proofs are on.
-// az_threat_leaves_kernel is that kernel's walk with the colours swapped -- the side that is NOT to move attacks, as if the side to move had
-// passed (K14's GMK_VCF_OPPONENT) -- and the line kept: on WIN every lane writes its four cells of the pv, the levels' (c, r) from the LDS stack
-// and the cells that end the line, as vcf_kernel's finish does.  A row whose own verdict (the kernel before, in stream order) is WIN or OVER,
-// or that has no pending leaf, reads {NONE, 0, 0, not asked}.  Lane y also leaves the leaf's occupied cells of row y for the read-out.
+// az_threat_leaves_kernel is that kernel with the colours swapped -- the side that is NOT to move attacks, as if the side to move had passed
+// (K14's GMK_VCF_OPPONENT) -- and the line kept: on WIN every lane writes its four cells of the pv, the levels' (c, r) from the LDS stack and the
+// cells that end the line, as vcf_kernel's finish does.  A row whose own verdict (the kernel before, in stream order) is WIN or OVER, or that
+// has no pending leaf, reads {NONE, 0, 0, not asked}.  Lane y also leaves the leaf's occupied cells of row y for the read-out.
 __global__ __launch_bounds__(64)
 void az_threat_leaves_kernel(AzTree t, AzLeaves lv, AzVcf vc, AzDefend df) {
     namespace V = gmk::vcf;
-    __shared__ uint32_t stack[V::kLevels][64];                   // as az_vcf_leaves_kernel
-    const int lane = threadIdx.x, y = lane & 15, group = lane >> 4, gbase = lane & 48;
-    const uint32_t board_row = y < 15 ? V::kRowMask : 0u;
-    const int limit = vc.max_depth;
-
-    int state = V::kIdle, depth = 0;
+    __shared__ V::Stack stack;
+    const V::Lane ln;
+    const int y = ln.y;
+    V::Walk w;
+    w.limit = vc.max_depth;
+    int game = 0, k = 0;
     size_t out_row = 0;
-    bool cut = false, more = false;
-    uint32_t nodes = 0, att = 0, def = 0, mask = 0;
 
     // ---- the loader ----
-    const long long item = static_cast<long long>(blockIdx.x) * 4 + group;
-    if (item < static_cast<long long>(t.n_games) * lv.leaves) {
-        const int game = static_cast<int>(item / lv.leaves), k = static_cast<int>(item - static_cast<long long>(game) * lv.leaves);
-        const AzHeader* hdr = t.hdr + game;
-        if (!(hdr->status & kStatusOver)) {
-            out_row = static_cast<size_t>(t.row_of[game]) * lv.leaves + static_cast<size_t>(k);
-            const bool many = lv.leaves > 1;
-            bool pending = many ? static_cast<uint32_t>(k) < hdr->n_pending : hdr->leaf_pending != 0u;
-            if (pending) {
-                const int own = vc.verdict[out_row].x;
-                pending = own != GMK_VCF_WIN && own != GMK_VCF_OVER;
-            }
-            if (pending) {
-                const AzPending* pd = lv.pend + static_cast<size_t>(game) * GMK_AZ_MAX_LEAVES + (many ? k : 0);
-                const uint32_t word = many ? pd->rows[y] : hdr->leaf_rows[y];
-                const uint32_t stones = many ? pd->stones : hdr->leaf_stones;
-                const uint32_t black = word & V::kRowMask, white = (word >> 16) & V::kRowMask;
-                att = (stones & 1u) ? black : white;             // white is to move on odd stone counts: black threatens
-                def = (stones & 1u) ? white : black;
-                df.occupied[out_row * 16 + y] = static_cast<uint16_t>(black | white);
-                state = V::kInit;
-            } else if (y == 0) {
-                df.threat[out_row] = make_int4(GMK_VCF_NONE, 0, 0, 0);
-            }
+    if (leaf_of(t, lv, static_cast<long long>(blockIdx.x) * 4 + ln.group, game, k, out_row)) {
+        bool pending = leaf_pending(t, lv, game, k);
+        if (pending) {
+            const int own = vc.verdict[out_row].x;
+            pending = own != GMK_VCF_WIN && own != GMK_VCF_OVER;
+        }
+        if (pending) {
+            const LeafRow r = leaf_row(t, lv, game, k, y);
+            w.reset(r.white_to_move ? r.black : r.white, r.white_to_move ? r.white : r.black, vc.max_depth);      // the side that moved last threatens
+            df.occupied[out_row * 16 + y] = static_cast<uint16_t>(r.black | r.white);
+        } else if (y == 0) {
+            df.threat[out_row] = make_int4(GMK_VCF_NONE, 0, 0, 0);
         }
     }
 
     // The group's threat.  t0 .. t2 are the cells that end a winning line after the 2 * depth cells on the stack (255: none).
     const auto finish = [&](int status, int t0, int t1, int t2) {
         const bool win = status == GMK_VCF_WIN;
-        if (y == 0) df.threat[out_row] = make_int4(status, !win ? 0 : depth + (t1 == 255 ? 1 : 2), static_cast<int>(nodes), 1);
+        if (y == 0) df.threat[out_row] = make_int4(status, !win ? 0 : w.depth + (t1 == 255 ? 1 : 2), static_cast<int>(w.nodes), 1);
         if (win) {
             uint32_t line = 0u;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int k = 4 * y + i, tail = k - 2 * depth;
-                uint32_t v = 255u;
-                if (tail < 0) { const uint32_t w = stack[k >> 1][lane]; v = (k & 1) ? w >> 24 : (w >> 16) & 255u; }
-                else if (tail < 3) v = static_cast<uint32_t>(tail == 0 ? t0 : tail == 1 ? t1 : t2);
-                line |= v << (8 * i);
-            }
+            for (int i = 0; i < 4; ++i) line |= V::line_cell(stack, ln, w.depth, 4 * y + i, t0, t1, t2) << (8 * i);
             reinterpret_cast<uint32_t*>(df.pv + out_row * GMK_VCF_PV)[y] = line;
         }
-        state = V::kIdle;
+        w.state = V::kIdle;
     };
-    const auto failed = [&]() { finish(cut ? GMK_VCF_DEPTH : GMK_VCF_NONE, 255, 255, 255); };
+    const auto failed = [&]() { finish(w.cut ? GMK_VCF_DEPTH : GMK_VCF_NONE, 255, 255, 255); };
 
-    while (__ballot(state != V::kIdle) != 0ull) {
-        // ---- the pass: every group in the same instructions ----
-        const bool trying = state == V::kRun;
-        uint32_t popped = trying ? mask : 0u;
-        const int c = V::take_lowest(popped, y, gbase);
-        const uint32_t left = V::group_rows(popped != 0, gbase);
-        const int cy = trying ? c / 15 : 0;
-        const uint32_t cbit = trying ? 1u << (c - 15 * cy) : 0u;
-        if (trying) {
-            mask = popped;
-            more = left != 0;
-            if (y == cy) att |= cbit;
-        }
-        uint32_t A[9], D[9], N[9];
-        V::gather_rows(att, A);
-        uint32_t F = V::completing(A, board_row & ~(att | def));
-        const int f1 = V::take_lowest(F, y, gbase), f2 = V::take_lowest(F, y, gbase);
-        const bool replied = trying && f1 >= 0 && f2 < 0;
-        const int ry = replied ? f1 / 15 : 0;
-        const uint32_t rbit = replied ? 1u << (f1 - 15 * ry) : 0u;
-        if (replied && y == ry) def |= rbit;
-        const uint32_t empty = board_row & ~(att | def);
-        V::gather_rows(def, D);
-        V::gather_rows(empty | att, N);
-        uint32_t T = V::completing(D, empty);
-        uint32_t C = V::four_making(A, N, empty);
-        if (V::group_rows(T != 0, gbase)) C &= T;
-        const int t1 = V::take_lowest(T, y, gbase), t2 = V::take_lowest(T, y, gbase);
-        (void)t1;
-        const bool child_has = V::group_rows(C != 0, gbase) != 0;
-        bool over = false;
-        if (__ballot(state == V::kInit) != 0ull) over = V::group_rows((V::five(A) | V::five(D)) != 0, gbase) != 0;
-
-        // ---- decisions, the same in all sixteen lanes of a group ----
-        if (state == V::kInit) {
-            if (over) finish(GMK_VCF_OVER, 255, 255, 255);
-            else if (f1 >= 0) finish(GMK_VCF_WIN, f1, 255, 255);
-            else {
-                bool fail = t2 >= 0;
-                if (!fail && 2 > limit) { cut = true; fail = true; }
-                if (!fail && !child_has) fail = true;
-                if (fail) failed();
-                else { mask = C; more = true; state = V::kRun; }
-            }
-        } else if (trying) {
-            bool retract = true;
-            if (f1 < 0) {
-                // not a four: no candidate and no node
-            } else if (nodes == vc.budget) {
-                finish(GMK_VCF_BUDGET, 255, 255, 255);
-            } else {
-                ++nodes;
-                if (f2 >= 0) finish(GMK_VCF_WIN, c, f1, f2);
-                else {
-                    bool fail = t2 >= 0;
-                    if (!fail && depth + 3 > limit) { cut = true; fail = true; }
-                    if (!fail && !child_has) fail = true;
-                    if (!fail) {
-                        stack[depth][lane] = mask | (more ? 0x8000u : 0u) | (static_cast<uint32_t>(c) << 16) | (static_cast<uint32_t>(f1) << 24);
-                        ++depth;
-                        mask = C; more = true; retract = false;
-                    } else if (y == ry) def ^= rbit;
-                }
-            }
-            if (state == V::kRun && retract) {
-                if (y == cy) att ^= cbit;
-                while (!more) {
-                    if (depth == 0) { failed(); break; }
-                    --depth;
-                    const uint32_t w = stack[depth][lane];
-                    mask = w & V::kRowMask;
-                    more = (w & 0x8000u) != 0;
-                    const int uc = static_cast<int>((w >> 16) & 255u), ur = static_cast<int>(w >> 24);
-                    if (y == uc / 15) att ^= 1u << (uc % 15);
-                    if (y == ur / 15) def ^= 1u << (ur % 15);
-                }
-            }
+    while (__ballot(w.state != V::kIdle) != 0ull) {
+        const V::Pass ps = V::pass(w, ln);
+        if (w.state == V::kInit) {
+            if (ps.over) finish(GMK_VCF_OVER, 255, 255, 255);
+            else if (ps.f1 >= 0) finish(GMK_VCF_WIN, ps.f1, 255, 255);
+            else V::start(w, ps, failed);
+        } else if (w.state == V::kRun) {
+            V::step(w, ln, ps, vc.budget, stack, [&](int c, int f1, int f2) { finish(GMK_VCF_WIN, c, f1, f2); },
+                    [&]() { finish(GMK_VCF_BUDGET, 255, 255, 255); }, failed);
         }
     }
 }
@@ -961,171 +818,82 @@ __global__ __launch_bounds__(64)
 void az_defend_leaves_kernel(AzTree t, AzLeaves lv, AzVcf vc, AzDefend df) {
     namespace V = gmk::vcf;
     enum : int { kSearch = 0, kFollow = 1 };
-    __shared__ uint32_t stack[V::kLevels][64];                   // K14's (search mode only)
-    const int lane = threadIdx.x, y = lane & 15, group = lane >> 4, gbase = lane & 48;
-    const uint32_t board_row = y < 15 ? V::kRowMask : 0u;
+    __shared__ V::Stack stack;                                   // search mode only
+    const V::Lane ln;
+    const int y = ln.y;
 
     // ---- the loader: the same in all 64 lanes ----
-    const long long item = static_cast<long long>(blockIdx.x) / kDefendWaves;
     const int slice = static_cast<int>(blockIdx.x % kDefendWaves);
-    if (item >= static_cast<long long>(t.n_games) * lv.leaves) return;
-    const int game = static_cast<int>(item / lv.leaves), k = static_cast<int>(item - static_cast<long long>(game) * lv.leaves);
-    const AzHeader* hdr = t.hdr + game;
-    if (hdr->status & kStatusOver) return;
-    const size_t out_row = static_cast<size_t>(t.row_of[game]) * lv.leaves + static_cast<size_t>(k);
+    int game = 0, k = 0;
+    size_t out_row = 0;
+    if (!leaf_of(t, lv, static_cast<long long>(blockIdx.x) / kDefendWaves, game, k, out_row)) return;
     const int4 th = df.threat[out_row];
     if (th.x != GMK_VCF_WIN || th.w == 0) return;                // only a leaf that was pending and asked has a WIN here
-    const bool many = lv.leaves > 1;
-    const AzPending* pd = lv.pend + static_cast<size_t>(game) * GMK_AZ_MAX_LEAVES + (many ? k : 0);
-    const uint32_t word = many ? pd->rows[y] : hdr->leaf_rows[y];
-    const uint32_t stones = many ? pd->stones : hdr->leaf_stones;
-    const uint32_t black = word & V::kRowMask, white = (word >> 16) & V::kRowMask;
-    const uint32_t base_att = (stones & 1u) ? black : white, base_def = (stones & 1u) ? white : black;
+    const LeafRow r = leaf_row(t, lv, game, k, y);
+    const uint32_t base_att = r.white_to_move ? r.black : r.white, base_def = r.white_to_move ? r.white : r.black;
     const int tlen = th.y;
     const uint32_t pvw = reinterpret_cast<const uint32_t*>(df.pv + out_row * GMK_VCF_PV)[y];     // this lane's four pv cells
     uint32_t* out = df.cells + out_row * kCells;
     int next_cell = slice * kDefendSlice;
     int left = next_cell < kCells ? min(kDefendSlice, kCells - next_cell) : 0;
 
-    int state = V::kIdle, mode = kSearch, cell = 0, depth = 0;
-    const int limit = vc.max_depth;
-    bool cut = false, more = false;
-    uint32_t nodes = 0, att = 0, def = 0, mask = 0;
+    V::Walk w;
+    w.limit = vc.max_depth;
+    int mode = kSearch, cell = 0;
 
     const auto settle = [&](int verdict, bool searched, uint32_t count) {
         if (y == 0) out[cell] = static_cast<uint32_t>(verdict) | (searched ? kCellSearched : 0u) | (count << kCellNodesShift);
-        state = V::kIdle;
+        w.state = V::kIdle;
     };
     // P + c, nothing played: where follow starts, and where the search starts after it
     const auto to_root = [&](int new_mode) {
         const int jy = cell / 15;
-        att = base_att;
-        def = base_def | (y == jy ? 1u << (cell - 15 * jy) : 0u);
         mode = new_mode;
-        nodes = 0; depth = 0; cut = false; more = false; mask = 0;
-        state = V::kInit;
+        w.reset(base_att, base_def | (y == jy ? 1u << (cell - 15 * jy) : 0u), vc.max_depth);
     };
     // the search's result (K14's finish, without a pv)
     const auto finish = [&](int status) {
-        settle(status == GMK_VCF_WIN ? GMK_VCF_CELL_LOSES : status == GMK_VCF_NONE ? GMK_VCF_CELL_HOLDS : GMK_VCF_CELL_UNKNOWN, true, nodes);
+        settle(status == GMK_VCF_WIN ? GMK_VCF_CELL_LOSES : status == GMK_VCF_NONE ? GMK_VCF_CELL_HOLDS : GMK_VCF_CELL_UNKNOWN, true, w.nodes);
     };
-    const auto failed = [&]() { finish(cut ? GMK_VCF_DEPTH : GMK_VCF_NONE); };
+    const auto failed = [&]() { finish(w.cut ? GMK_VCF_DEPTH : GMK_VCF_NONE); };
 
     for (;;) {
         // ---- groups without a job take the next cells of this wavefront's slice ----
-        const unsigned long long idle = __ballot(state == V::kIdle);
-        int rank = 0, takers = 0;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int is_idle = static_cast<int>((idle >> (16 * g)) & 1ull);
-            if (g < group) rank += is_idle;
-            takers += is_idle;
-        }
-        if (state == V::kIdle && rank < left) {
-            cell = next_cell + rank;
+        const V::HandOut ho = V::hand_out(w.state, ln, left);
+        if (w.state == V::kIdle && ho.rank < left) {
+            cell = next_cell + ho.rank;
             const int jy = cell / 15;
-            const bool taken = V::group_rows(y == jy && (((base_att | base_def) >> (cell - 15 * jy)) & 1u) != 0, gbase) != 0;
+            const bool taken = V::group_rows(y == jy && (((base_att | base_def) >> (cell - 15 * jy)) & 1u) != 0, ln.gbase) != 0;
             if (taken) settle(GMK_VCF_CELL_NONE, false, 0u);
             else to_root(kFollow);
         }
-        const int taken_jobs = takers < left ? takers : left;
-        left -= taken_jobs;
-        next_cell += taken_jobs;
-        if (__ballot(state != V::kIdle) == 0ull) {                 // nothing to walk: only occupied cells, or the slice is done
+        left -= ho.taken;
+        next_cell += ho.taken;
+        if (__ballot(w.state != V::kIdle) == 0ull) {               // nothing to walk: only occupied cells, or the slice is done
             if (left == 0) break;
             continue;
         }
 
-        // ---- the pass (K14's): every group in the same instructions ----
-        const bool trying = state == V::kRun;
-        uint32_t popped = trying ? mask : 0u;
-        const int c = V::take_lowest(popped, y, gbase);
-        const uint32_t more_left = V::group_rows(popped != 0, gbase);
-        const int cy = trying ? c / 15 : 0;
-        const uint32_t cbit = trying ? 1u << (c - 15 * cy) : 0u;
-        if (trying) {
-            mask = popped;
-            more = more_left != 0;
-            if (y == cy) att |= cbit;
-        }
-        uint32_t A[9], D[9], N[9];
-        V::gather_rows(att, A);
-        uint32_t F = V::completing(A, board_row & ~(att | def));
-        const int f1 = V::take_lowest(F, y, gbase), f2 = V::take_lowest(F, y, gbase);
-        const bool replied = trying && f1 >= 0 && f2 < 0;          // the forced reply goes on the board
-        const int ry = replied ? f1 / 15 : 0;
-        const uint32_t rbit = replied ? 1u << (f1 - 15 * ry) : 0u;
-        if (replied && y == ry) def |= rbit;
-        const uint32_t empty = board_row & ~(att | def);
-        V::gather_rows(def, D);
-        V::gather_rows(empty | att, N);
-        uint32_t T = V::completing(D, empty);
-        uint32_t C = V::four_making(A, N, empty);
-        if (V::group_rows(T != 0, gbase)) C &= T;                  // a defender four: only its blocking cell is a candidate
-        const int t1 = V::take_lowest(T, y, gbase), t2 = V::take_lowest(T, y, gbase);
-        const bool child_has = V::group_rows(C != 0, gbase) != 0;
-        // follow's next level on this board: the threat's move there, which must be free and, against a defender four, its block
-        const int level = trying ? depth + 1 : depth;
-        const uint32_t pv_word = static_cast<uint32_t>(__shfl(static_cast<int>(pvw), gbase + ((level >> 1) & 15)));
-        const int a = static_cast<int>((pv_word >> (16 * (level & 1))) & 255u), ay = a / 15;     // 255 past the line's end: row 17, no lane's
-        const uint32_t abit = y == ay ? 1u << (a - 15 * ay) : 0u;
-        const bool a_free = V::group_rows((empty & abit) != 0, gbase) != 0;
-        const bool follows = t2 < 0 && level < tlen && a_free && (t1 < 0 || a == t1);
+        const V::Pass ps = V::pass(w, ln);
+        const V::Follow fo = V::follow_level(w, ln, ps, pvw, tlen);
 
         // ---- decisions, the same in all sixteen lanes of a group ----
-        if (state == V::kInit) {
+        if (w.state == V::kInit) {
             if (mode == kFollow) {
-                if (f1 >= 0) settle(GMK_VCF_CELL_LOSES, false, 0u);
-                else if (follows) { mask = abit; state = V::kRun; }
+                if (ps.f1 >= 0) settle(GMK_VCF_CELL_LOSES, false, 0u);
+                else if (fo.follows) { w.mask = fo.abit; w.state = V::kRun; }
                 else to_root(kSearch);
             } else {
-                if (f1 >= 0) finish(GMK_VCF_WIN);                  // follow has settled these; kept so that the search is K14's walk whole
-                else {
-                    bool fail = t2 >= 0;
-                    if (!fail && 2 > limit) { cut = true; fail = true; }
-                    if (!fail && !child_has) fail = true;
-                    if (fail) failed();
-                    else { mask = C; more = true; state = V::kRun; }
-                }
+                if (ps.f1 >= 0) finish(GMK_VCF_WIN);               // follow has settled these; kept so that the search is K14's walk whole
+                else V::start(w, ps, failed);
             }
-        } else if (trying && mode == kFollow) {
-            if (f1 < 0) to_root(kSearch);                          // the threat's move is no four any more
-            else if (f2 >= 0) settle(GMK_VCF_CELL_LOSES, false, 0u);
-            else if (follows) { ++depth; mask = abit; }            // a and its forced reply stay on the board
+        } else if (w.state == V::kRun && mode == kFollow) {
+            if (ps.f1 < 0) to_root(kSearch);                       // the threat's move is no four any more
+            else if (ps.f2 >= 0) settle(GMK_VCF_CELL_LOSES, false, 0u);
+            else if (fo.follows) { ++w.depth; w.mask = fo.abit; }  // a and its forced reply stay on the board
             else to_root(kSearch);
-        } else if (trying) {
-            bool retract = true;
-            if (f1 < 0) {
-                // not a four: no candidate and no node (K14)
-            } else if (nodes == vc.budget) {
-                finish(GMK_VCF_BUDGET);
-            } else {
-                ++nodes;
-                if (f2 >= 0) finish(GMK_VCF_WIN);
-                else {
-                    bool fail = t2 >= 0;
-                    if (!fail && depth + 3 > limit) { cut = true; fail = true; }
-                    if (!fail && !child_has) fail = true;
-                    if (!fail) {
-                        stack[depth][lane] = mask | (more ? 0x8000u : 0u) | (static_cast<uint32_t>(c) << 16) | (static_cast<uint32_t>(f1) << 24);
-                        ++depth;
-                        mask = C; more = true; retract = false;
-                    } else if (y == ry) def ^= rbit;
-                }
-            }
-            if (state == V::kRun && retract) {
-                if (y == cy) att ^= cbit;
-                while (!more) {                                    // climb while the level has nothing left
-                    if (depth == 0) { failed(); break; }
-                    --depth;
-                    const uint32_t w = stack[depth][lane];
-                    mask = w & V::kRowMask;
-                    more = (w & 0x8000u) != 0;
-                    const int uc = static_cast<int>((w >> 16) & 255u), ur = static_cast<int>(w >> 24);
-                    if (y == uc / 15) att ^= 1u << (uc % 15);
-                    if (y == ur / 15) def ^= 1u << (ur % 15);
-                }
-            }
+        } else if (w.state == V::kRun) {
+            V::step(w, ln, ps, vc.budget, stack, [&](int, int, int) { finish(GMK_VCF_WIN); }, [&]() { finish(GMK_VCF_BUDGET); }, failed);
         }
     }
 }

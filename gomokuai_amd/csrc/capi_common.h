@@ -24,6 +24,9 @@ struct DeviceState {
 };
 DeviceState& device_state();
 
+// The entry points' test of a pointer argument's alignment (NULL is aligned).
+inline bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
+
 // Profiling switches (phase masks, in-kernel timers, launch-shape overrides) exist in the -DGMK_PROFILE build only:
 // `python -m gomokuai_amd.build --profile` makes libgomoku_hip_prof.so, which tools/*.sh load with GMK_HIP_LIB=prof.
 // The production library never reads the environment, so a stray variable cannot change a result.

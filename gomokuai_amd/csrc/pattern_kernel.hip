@@ -234,7 +234,7 @@ int launch(PatternParams prm, hipStream_t stream) {
     return GMK_OK;
 }
 
-bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
+using gmk::misaligned;
 
 #define GMK_NEED_INIT()                                                                      \
     do {                                                                                     \

@@ -229,7 +229,7 @@ void records_unpack_kernel(const uint8_t* __restrict__ buf, uint64_t n_bytes, in
     }
 }
 
-bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
+using gmk::misaligned;
 
 // The three scan launches on `stream` (n > 0).
 int scan(const int32_t* d_lens, int n, int64_t* d_offsets, hipStream_t stream) {

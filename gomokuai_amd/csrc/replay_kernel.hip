@@ -417,7 +417,7 @@ void replay_restore_kernel(const uint8_t* __restrict__ image, uint64_t bytes, ui
     *status = 0;
 }
 
-bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
+using gmk::misaligned;
 
 constexpr int64_t kMaxCapacityPlies = int64_t(1) << 40;
 

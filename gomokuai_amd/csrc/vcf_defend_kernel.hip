@@ -1,9 +1,9 @@
 // vcf_defend_kernel.hip -- K15: the moves that refute a forced win by continuous fours, exact and batched.
 //
 // The contract is in include/gomoku_hip.h ("K15").  gmk_vcf_defend is two launches on the caller's stream: K14's kernel with GMK_VCF_OPPONENT
-// into the threat outputs, then the kernel below over jobs (position, cell), one 16-lane group per job, on K14's representation (vcf_device.h:
-// one board row per lane, DPP row shifts for the neighbours) and with K14's pass.  A job of a threatened position puts the defender's stone
-// on its cell in registers and walks in one of two modes:
+// into the threat outputs, then the kernel below over jobs (position, cell), one 16-lane group per job, on K14's representation and with K14's
+// walk, both vcf_device.h's (pass, start, step).  This file is what K15 puts around them: the jobs, the follow mode and the cells' verdicts.
+// A job of a threatened position puts the defender's stone on its cell in registers and walks in one of two modes:
 //     follow   the attacker's candidates of level i are reduced to pv[2 i], the threat's own move there: one pass per level, no stack, no
 //              node.  It ends in LOSES (the line still wins), in FIVE (the stone made five: the init pass's "over" test) or in FAIL;
 //     search   after FAIL the same group starts again from P + c as K14's full walk, with the whole budget.
@@ -18,6 +18,7 @@
 namespace {
 
 using namespace gmk::vcf;
+using gmk::misaligned;
 
 enum : int { kSearch = 0, kFollow = 1, kWhole = 2 };
 
@@ -35,18 +36,17 @@ struct DefendParams {
 };
 
 __global__ __launch_bounds__(64) void vcf_defend_kernel(DefendParams p) {
-    __shared__ uint32_t stack[kLevels][64];                    // K14's: candidates left 0..14, "the level has more" 15, c 16..23, r 24..31 (search mode only)
-    const int lane = threadIdx.x, y = lane & 15, group = lane >> 4, gbase = lane & 48;
-    const uint32_t board_row = y < 15 ? kRowMask : 0u;
+    __shared__ Stack stack;                                    // search mode only
+    const Lane ln;
+    const int y = ln.y, gbase = ln.gbase;
     const bool iterative = (p.flags & GMK_VCF_ITERATIVE) != 0;
     // this wavefront's slice of the n * 225 jobs: `left` jobs from (next_pos, next_cell) on; the grid covers exactly the jobs there are
     const long long total = static_cast<long long>(p.n) * kCells, first = static_cast<long long>(blockIdx.x) * p.per_wave;
     int next_pos = static_cast<int>(first / kCells), next_cell = static_cast<int>(first % kCells);
     int left = first < total ? static_cast<int>(std::min<long long>(p.per_wave, total - first)) : 0;
 
-    int state = kIdle, mode = kSearch, pos = -1, cell = 0, depth = 0, limit = 0;
-    bool cut = false, more = false;
-    uint32_t nodes = 0, att = 0, def = 0, mask = 0;
+    Walk w;
+    int mode = kSearch, pos = -1, cell = 0;
     // the position this group loaded last: its threat, and once `planes` is set its two planes (this lane's row) and this lane's four pv cells
     int held = -1, tstatus = GMK_VCF_BAD, tlen = 0;
     bool planes = false;
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(64) void vcf_defend_kernel(DefendParams p) {
             if (p.cell_length) p.cell_length[at] = static_cast<uint8_t>(length);
             if (p.cell_nodes) p.cell_nodes[at] = count;
         }
-        state = kIdle;
+        w.state = kIdle;
     };
     // every cell of the position at once: occupied cells and positions that are over or no positions NONE, the cells of `fives` FIVE, the rest `other`
     const auto settle_rows = [&](uint32_t occupied, uint32_t fives, int other) {
@@ -72,41 +72,26 @@ __global__ __launch_bounds__(64) void vcf_defend_kernel(DefendParams p) {
                 if (p.cell_nodes) p.cell_nodes[at + x] = 0u;
             }
         }
-        state = kIdle;
+        w.state = kIdle;
     };
     // P + c, nothing played: where follow starts, and where the search starts after it
     const auto to_root = [&](int new_mode) {
         const int jy = cell / 15;
-        att = base_att;
-        def = base_def | (y == jy ? 1u << (cell - 15 * jy) : 0u);
         mode = new_mode;
-        nodes = 0; depth = 0; cut = false; more = false; mask = 0;
-        limit = iterative ? 1 : p.max_depth;
-        state = kInit;
+        w.reset(base_att, base_def | (y == jy ? 1u << (cell - 15 * jy) : 0u), iterative ? 1 : p.max_depth);
     };
     // the search's result (K14's finish, without a pv)
     const auto finish = [&](int status, int length) {
-        settle(status == GMK_VCF_WIN ? GMK_VCF_CELL_LOSES : status == GMK_VCF_NONE ? GMK_VCF_CELL_HOLDS : GMK_VCF_CELL_UNKNOWN, length, nodes);
+        settle(status == GMK_VCF_WIN ? GMK_VCF_CELL_LOSES : status == GMK_VCF_NONE ? GMK_VCF_CELL_HOLDS : GMK_VCF_CELL_UNKNOWN, length, w.nodes);
     };
-    const auto limit_failed = [&]() {
-        if (!cut) finish(GMK_VCF_NONE, 0);
-        else if (iterative && limit < p.max_depth) { ++limit; cut = false; state = kInit; }
-        else finish(GMK_VCF_DEPTH, 0);
-    };
+    const auto failed = [&]() { limit_failed(w, iterative, p.max_depth, [&](int status) { finish(status, 0); }); };
 
     for (;;) {
         // ---- groups without a job take the next ones of this wavefront's slice ----
-        const unsigned long long idle = __ballot(state == kIdle);
-        int rank = 0, takers = 0;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int is_idle = static_cast<int>((idle >> (16 * g)) & 1ull);
-            if (g < group) rank += is_idle;
-            takers += is_idle;
-        }
-        if (state == kIdle && rank < left) {
+        const HandOut ho = hand_out(w.state, ln, left);
+        if (w.state == kIdle && ho.rank < left) {
             pos = next_pos;
-            cell = next_cell + rank;
+            cell = next_cell + ho.rank;
             if (cell >= kCells) { cell -= kCells; ++pos; }
             if (pos != held) {
                 held = pos;
@@ -116,23 +101,11 @@ __global__ __launch_bounds__(64) void vcf_defend_kernel(DefendParams p) {
             const bool win = tstatus == GMK_VCF_WIN;
             const bool searched = tstatus == GMK_VCF_NONE || tstatus == GMK_VCF_DEPTH || tstatus == GMK_VCF_BUDGET;
             if ((win || (searched && cell == 0)) && !planes) {
-                // the threat's status says that the list is a position; the tests stay, so that nothing outside it is read whatever the status says
-                const int len = p.lens[pos];
-                const bool bad = len < 0 || len > kCells || len > p.stride;
-                uint32_t black = 0, white = 0;
-                if (!bad) {
-                    const uint8_t* list = p.moves + static_cast<size_t>(pos) * static_cast<size_t>(p.stride);
-                    for (int i = 0; i < len; ++i) {
-                        const int stone = list[i];
-                        const int r = stone / 15;
-                        if (r != y) continue;
-                        const uint32_t bit = 1u << (stone - 15 * r);
-                        if (i & 1) white |= bit; else black |= bit;
-                    }
-                }
-                const bool black_attacks = !bad && (len & 1) != 0;   // the attacker is the side that is NOT to move
-                base_att = black_attacks ? black : white;
-                base_def = black_attacks ? white : black;
+                // the threat's status says that the list is a position; the length's tests stay, so that nothing outside it is read whatever it says
+                const Planes pl = load_moves<false>(p.moves, p.stride, p.lens, pos, ln);
+                const bool black_attacks = !pl.bad && (pl.len & 1) != 0;   // the attacker is the side that is NOT to move
+                base_att = black_attacks ? pl.black : pl.white;
+                base_def = black_attacks ? pl.white : pl.black;
                 tlen = p.threat_length[pos];
                 const uint8_t* line = p.threat_pv + static_cast<size_t>(pos) * GMK_VCF_PV + 4 * y;
                 pvw = static_cast<uint32_t>(line[0]) | static_cast<uint32_t>(line[1]) << 8 | static_cast<uint32_t>(line[2]) << 16 | static_cast<uint32_t>(line[3]) << 24;
@@ -145,124 +118,47 @@ __global__ __launch_bounds__(64) void vcf_defend_kernel(DefendParams p) {
                 else to_root(kFollow);
             } else if (cell == 0) {
                 if (searched) {
-                    att = base_att; def = base_def;
                     mode = kWhole;
-                    nodes = 0; depth = 0; cut = false; more = false; mask = 0;
-                    state = kInit;
+                    w.reset(base_att, base_def, 0);                // one pass and no walk: no limit is read
                 } else settle_rows(kRowMask, 0u, GMK_VCF_CELL_NONE);
             }
             // else: a cell of a position without a threat to follow, which the job of its cell 0 writes
         }
-        const int taken_jobs = takers < left ? takers : left;
-        left -= taken_jobs;
-        next_cell += taken_jobs;
+        left -= ho.taken;
+        next_cell += ho.taken;
         if (next_cell >= kCells) { next_cell -= kCells; ++next_pos; }
-        if (__ballot(state != kIdle) == 0ull) {                    // nothing to walk: only jobs that were settled as they were taken, or the slice is done
+        if (__ballot(w.state != kIdle) == 0ull) {                  // nothing to walk: only jobs that were settled as they were taken, or the slice is done
             if (left == 0) break;
             continue;
         }
 
-        // ---- the pass (K14's): every group in the same instructions ----
-        const bool trying = state == kRun;                         // such a group has a candidate: `mask` is not empty
-        uint32_t popped = trying ? mask : 0u;
-        const int c = take_lowest(popped, y, gbase);
-        const uint32_t more_left = group_rows(popped != 0, gbase);
-        const int cy = trying ? c / 15 : 0;
-        const uint32_t cbit = trying ? 1u << (c - 15 * cy) : 0u;
-        if (trying) {
-            mask = popped;
-            more = more_left != 0;
-            if (y == cy) att |= cbit;
-        }
-        uint32_t A[9], D[9], N[9];
-        gather_rows(att, A);
-        uint32_t F = completing(A, board_row & ~(att | def));
-        const int f1 = take_lowest(F, y, gbase), f2 = take_lowest(F, y, gbase);
-        const bool replied = trying && f1 >= 0 && f2 < 0;          // the forced reply goes on the board
-        const int ry = replied ? f1 / 15 : 0;
-        const uint32_t rbit = replied ? 1u << (f1 - 15 * ry) : 0u;
-        if (replied && y == ry) def |= rbit;
-        const uint32_t empty = board_row & ~(att | def);
-        gather_rows(def, D);
-        gather_rows(empty | att, N);
-        uint32_t T = completing(D, empty);
-        const uint32_t fives = T;                                  // completing(defender), whole
-        uint32_t C = four_making(A, N, empty);
-        if (group_rows(T != 0, gbase)) C &= T;                     // a defender four: only its blocking cell is a candidate
-        const int t1 = take_lowest(T, y, gbase), t2 = take_lowest(T, y, gbase);
-        const bool child_has = group_rows(C != 0, gbase) != 0;
-        bool over = false;
-        if (__ballot(state == kInit) != 0ull) over = group_rows((five(A) | five(D)) != 0, gbase) != 0;
-        // follow's next level on this board: the threat's move there, which must be free and, against a defender four, its block
-        const int level = trying ? depth + 1 : depth;
-        const uint32_t pv_word = static_cast<uint32_t>(__shfl(static_cast<int>(pvw), gbase + ((level >> 1) & 15)));
-        const int a = static_cast<int>((pv_word >> (16 * (level & 1))) & 255u), ay = a / 15;     // 255 past the line's end: row 17, no lane's
-        const uint32_t abit = y == ay ? 1u << (a - 15 * ay) : 0u;
-        const bool a_free = group_rows((empty & abit) != 0, gbase) != 0;
-        const bool follows = t2 < 0 && level < tlen && a_free && (t1 < 0 || a == t1);
+        const Pass ps = pass(w, ln);
+        const Follow fo = follow_level(w, ln, ps, pvw, tlen);
 
         // ---- decisions, the same in all sixteen lanes of a group ----
-        if (state == kInit) {
+        if (w.state == kInit) {
             if (mode == kWhole) {
-                settle_rows(att | def, fives, tstatus == GMK_VCF_NONE ? GMK_VCF_CELL_HOLDS : GMK_VCF_CELL_UNKNOWN);
+                settle_rows(w.att | w.def, ps.T, tstatus == GMK_VCF_NONE ? GMK_VCF_CELL_HOLDS : GMK_VCF_CELL_UNKNOWN);
             } else if (mode == kFollow) {
-                if (over) settle(GMK_VCF_CELL_FIVE, 0, 0u);
-                else if (f1 >= 0) settle(GMK_VCF_CELL_LOSES, 1, 0u);
-                else if (follows) { mask = abit; state = kRun; }
+                if (ps.over) settle(GMK_VCF_CELL_FIVE, 0, 0u);
+                else if (ps.f1 >= 0) settle(GMK_VCF_CELL_LOSES, 1, 0u);
+                else if (fo.follows) { w.mask = fo.abit; w.state = kRun; }
                 else to_root(kSearch);
             } else {
-                if (f1 >= 0) finish(GMK_VCF_WIN, 1);               // follow has settled these; kept so that the search is K14's walk whole
-                else {
-                    bool fail = t2 >= 0;
-                    if (!fail && 2 > limit) { cut = true; fail = true; }
-                    if (!fail && !child_has) fail = true;
-                    if (fail) limit_failed();
-                    else { mask = C; more = true; state = kRun; }
-                }
+                if (ps.f1 >= 0) finish(GMK_VCF_WIN, 1);            // follow has settled these; kept so that the search is K14's walk whole
+                else start(w, ps, failed);
             }
-        } else if (trying && mode == kFollow) {
-            if (f1 < 0) to_root(kSearch);                          // the threat's move is no four any more
-            else if (f2 >= 0) settle(GMK_VCF_CELL_LOSES, depth + 2, 0u);
-            else if (follows) { ++depth; mask = abit; }            // a and its forced reply stay on the board
+        } else if (w.state == kRun && mode == kFollow) {
+            if (ps.f1 < 0) to_root(kSearch);                       // the threat's move is no four any more
+            else if (ps.f2 >= 0) settle(GMK_VCF_CELL_LOSES, w.depth + 2, 0u);
+            else if (fo.follows) { ++w.depth; w.mask = fo.abit; }  // a and its forced reply stay on the board
             else to_root(kSearch);
-        } else if (trying) {
-            bool retract = true;
-            if (f1 < 0) {
-                // not a four: no candidate and no node (K14)
-            } else if (nodes == p.budget) {
-                finish(GMK_VCF_BUDGET, 0);
-            } else {
-                ++nodes;
-                if (f2 >= 0) finish(GMK_VCF_WIN, depth + 2);
-                else {
-                    bool fail = t2 >= 0;
-                    if (!fail && depth + 3 > limit) { cut = true; fail = true; }
-                    if (!fail && !child_has) fail = true;
-                    if (!fail) {
-                        stack[depth][lane] = mask | (more ? 0x8000u : 0u) | (static_cast<uint32_t>(c) << 16) | (static_cast<uint32_t>(f1) << 24);
-                        ++depth;
-                        mask = C; more = true; retract = false;
-                    } else if (y == ry) def ^= rbit;
-                }
-            }
-            if (state == kRun && retract) {
-                if (y == cy) att ^= cbit;
-                while (!more) {                                    // climb while the level has nothing left
-                    if (depth == 0) { limit_failed(); break; }
-                    --depth;
-                    const uint32_t w = stack[depth][lane];
-                    mask = w & kRowMask;
-                    more = (w & 0x8000u) != 0;
-                    const int uc = static_cast<int>((w >> 16) & 255u), ur = static_cast<int>(w >> 24);
-                    if (y == uc / 15) att ^= 1u << (uc % 15);
-                    if (y == ur / 15) def ^= 1u << (ur % 15);
-                }
-            }
+        } else if (w.state == kRun) {
+            step(w, ln, ps, p.budget, stack, [&](int, int, int) { finish(GMK_VCF_WIN, w.depth + 2); }, [&]() { finish(GMK_VCF_BUDGET, 0); }, failed);
         }
     }
 }
 
-bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
 
 bool bad_arguments(const void* moves, int stride, const void* lens, int n, int max_depth, int flags, const void* status, const void* length,
                    const void* pv, const void* verdict) {

@@ -2,20 +2,16 @@
 //
 // The contract is the walk in include/gomoku_hip.h ("K14"): the attacker makes a four, the defender's one reply is forced, and so on until a
 // double four or a five.  Everything is geometry on two 15 x 15 bit planes; the pattern automaton is not involved and there is no float.
-// Mapping: one board ROW per lane, sixteen lanes per position (lane 15 of a group is an off-board row of zeros), four positions per wavefront,
-// one wavefront per workgroup.  Horizontal neighbours are bit shifts; vertical and diagonal neighbours are the rows y-4 .. y+4, fetched with
-// DPP row shifts, which stay inside a 16-lane row and deliver zero from outside it -- exactly a board edge.  One pass of the loop is, for every
-// group at once and in the same instructions:
-//     take the lowest candidate c of the current level, play it, F = completing(attacker)                 (8 row shifts)
-//     if F is one cell r: play r, T = completing(defender), C = the four-making cells of the child       (16 row shifts)
-// and then a few group-uniform decisions: win, budget, descend (push mask, c, r: one LDS word per lane and level), or undo by XOR and climb
-// while the levels above have no candidate left.  A child never has a completing cell of its own (its parent's only one was just taken), so
-// completing(attacker) is evaluated once per node, for the candidate test that counts the node.  Four-making cells are found plane-wide: the
-// empties of a five-window with three attacker stones and no defender stone (with no completing cell on the board "at least three" is
-// "exactly three"); whatever that mask offers is still held to F != {} before it counts, so `nodes` is the contract's count.
-// Divergent trees cost idle passes, not divergent code; a group that has finished takes the next position of its wavefront's slice in the
-// same pass.  No atomics, no barrier, nothing allocated: the device entry is one launch.
-// The row gather and the geometry of fours are in vcf_device.h, which K15 (vcf_defend_kernel.hip) shares.
+// The walk itself is vcf_device.h's, where the mapping is told: one board ROW per lane, sixteen lanes per position, four positions per wavefront,
+// one wavefront per workgroup; a pass of the loop (gmk::vcf::pass) in the same instructions for every group, and then a few group-uniform
+// decisions (start, step): win, budget, descend (one LDS word per lane and level), or undo by XOR and climb.  A child never has a completing
+// cell of its own (its parent's only one was just taken), so completing(attacker) is evaluated once per node, for the candidate test that
+// counts the node.  Four-making cells are found plane-wide: the empties of a five-window with three attacker stones and no defender stone (with
+// no completing cell on the board "at least three" is "exactly three"); whatever that mask offers is still held to F != {} before it counts, so
+// `nodes` is the contract's count.
+// This file is K14's own around that walk: the move-list loader with its BAD verdicts, iterative deepening, and a finish that writes the whole
+// principal variation.  Divergent trees cost idle passes, not divergent code; a group that has finished takes the next position of its
+// wavefront's slice in the same pass.  No atomics, no barrier, nothing allocated: the device entry is one launch.
 #include <algorithm>
 
 #include "vcf_device.h"
@@ -23,6 +19,7 @@
 namespace {
 
 using namespace gmk::vcf;
+using gmk::misaligned;
 
 struct VcfParams {
     const uint8_t* moves;
@@ -37,173 +34,67 @@ struct VcfParams {
 };
 
 __global__ __launch_bounds__(64) void vcf_kernel(VcfParams p) {
-    __shared__ uint32_t stack[kLevels][64];                    // per level and lane: candidates left 0..14, "the level has more" 15, c 16..23, r 24..31
-    const int lane = threadIdx.x, y = lane & 15, group = lane >> 4, gbase = lane & 48;
-    const uint32_t board_row = y < 15 ? kRowMask : 0u;
+    __shared__ Stack stack;
+    const Lane ln;
+    const int y = ln.y;
     const bool iterative = (p.flags & GMK_VCF_ITERATIVE) != 0;
+    // this wavefront's slice of the batch: `left` positions from `next` on
     const long long first = static_cast<long long>(blockIdx.x) * p.per_wave;
     int next = first < p.n ? static_cast<int>(first) : p.n;
-    const int end = first + p.per_wave < p.n ? static_cast<int>(first + p.per_wave) : p.n;
+    int left = (first + p.per_wave < p.n ? static_cast<int>(first + p.per_wave) : p.n) - next;
 
-    int state = kIdle, pos = -1, depth = 0, limit = 0;
-    bool cut = false, more = false;
-    uint32_t nodes = 0, att = 0, def = 0, mask = 0;
+    Walk w;
+    int pos = -1;
 
     // The group's result.  t0 .. t2 are the cells that end a winning line after the 2 * depth cells on the stack (255: none).
     const auto finish = [&](int status, int t0, int t1, int t2) {
         const bool win = status == GMK_VCF_WIN;
         if (y == 0) {
             if (p.status) p.status[pos] = status;
-            if (p.move) p.move[pos] = !win ? -1 : depth > 0 ? static_cast<int>((stack[0][lane] >> 16) & 255u) : t0;
-            if (p.length) p.length[pos] = !win ? 0 : depth + (t1 == 255 ? 1 : 2);
-            if (p.nodes) p.nodes[pos] = nodes;
+            if (p.move) p.move[pos] = !win ? -1 : w.depth > 0 ? level_c(stack[0][ln.lane]) : t0;
+            if (p.length) p.length[pos] = !win ? 0 : w.depth + (t1 == 255 ? 1 : 2);
+            if (p.nodes) p.nodes[pos] = w.nodes;
         }
         if (p.pv) {
             uint8_t* out = p.pv + static_cast<size_t>(pos) * GMK_VCF_PV + 4 * y;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int k = 4 * y + i, tail = k - 2 * depth;
-                uint32_t v = 255u;
-                if (win) {
-                    if (tail < 0) { const uint32_t w = stack[k >> 1][lane]; v = (k & 1) ? w >> 24 : (w >> 16) & 255u; }
-                    else if (tail < 3) v = static_cast<uint32_t>(tail == 0 ? t0 : tail == 1 ? t1 : t2);
-                }
-                out[i] = static_cast<uint8_t>(v);
-            }
+            for (int i = 0; i < 4; ++i) out[i] = static_cast<uint8_t>(win ? line_cell(stack, ln, w.depth, 4 * y + i, t0, t1, t2) : 255u);
         }
-        state = kIdle;
+        w.state = kIdle;
     };
-    // The walk at this limit has failed at the root, with every move undone.
-    const auto limit_failed = [&]() {
-        if (!cut) finish(GMK_VCF_NONE, 255, 255, 255);
-        else if (iterative && limit < p.max_depth) { ++limit; cut = false; state = kInit; }
-        else finish(GMK_VCF_DEPTH, 255, 255, 255);
-    };
+    const auto failed = [&]() { limit_failed(w, iterative, p.max_depth, [&](int status) { finish(status, 255, 255, 255); }); };
 
     for (;;) {
         // ---- groups without a position take the next ones of this wavefront's slice ----
-        const unsigned long long idle = __ballot(state == kIdle);
-        int rank = 0, takers = 0;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int is_idle = static_cast<int>((idle >> (16 * g)) & 1ull);
-            if (g < group) rank += is_idle;
-            takers += is_idle;
+        const HandOut ho = hand_out(w.state, ln, left);
+        if (w.state == kIdle && ho.rank < left) {
+            pos = next + ho.rank;
+            const Planes pl = load_moves<true>(p.moves, p.stride, p.lens, pos, ln);
+            const bool black_attacks = ((pl.len & 1) == 0) != ((p.flags & GMK_VCF_OPPONENT) != 0);
+            w.reset(black_attacks ? pl.black : pl.white, black_attacks ? pl.white : pl.black, iterative ? 1 : p.max_depth);
+            if (pl.bad) finish(GMK_VCF_BAD, 255, 255, 255);
         }
-        if (state == kIdle && next + rank < end) {
-            pos = next + rank;
-            const int len = p.lens[pos];
-            bool bad = len < 0 || len > kCells || len > p.stride;
-            uint32_t black = 0, white = 0;
-            bool clash = false;
-            if (!bad) {
-                const uint8_t* list = p.moves + static_cast<size_t>(pos) * static_cast<size_t>(p.stride);
-                for (int i = 0; i < len; ++i) {
-                    const int cell = list[i];
-                    if (cell >= kCells) { bad = true; continue; }
-                    const int r = cell / 15;
-                    if (r != y) continue;
-                    const uint32_t bit = 1u << (cell - 15 * r);
-                    clash |= ((black | white) & bit) != 0;
-                    if (i & 1) white |= bit; else black |= bit;
-                }
-            }
-            bad |= group_rows(clash, gbase) != 0;
-            const bool black_attacks = ((len & 1) == 0) != ((p.flags & GMK_VCF_OPPONENT) != 0);
-            att = black_attacks ? black : white;
-            def = black_attacks ? white : black;
-            nodes = 0; depth = 0; cut = false; more = false; mask = 0;
-            limit = iterative ? 1 : p.max_depth;
-            state = kInit;
-            if (bad) finish(GMK_VCF_BAD, 255, 255, 255);
-        }
-        next = next + takers < end ? next + takers : end;
-        if (__ballot(state != kIdle) == 0ull) {                    // nothing to walk: only lists that were no positions, or the slice is done
-            if (next >= end) break;
+        left -= ho.taken;
+        next += ho.taken;
+        if (__ballot(w.state != kIdle) == 0ull) {                  // nothing to walk: only lists that were no positions, or the slice is done
+            if (left == 0) break;
             continue;
         }
 
-        // ---- the pass: every group in the same instructions ----
-        const bool trying = state == kRun;                         // such a group has a candidate: `mask` is not empty
-        uint32_t popped = trying ? mask : 0u;
-        const int c = take_lowest(popped, y, gbase);
-        const uint32_t left = group_rows(popped != 0, gbase);
-        const int cy = trying ? c / 15 : 0;
-        const uint32_t cbit = trying ? 1u << (c - 15 * cy) : 0u;
-        if (trying) {
-            mask = popped;
-            more = left != 0;
-            if (y == cy) att |= cbit;
-        }
-        uint32_t A[9], D[9], N[9];
-        gather_rows(att, A);
-        uint32_t F = completing(A, board_row & ~(att | def));
-        const int f1 = take_lowest(F, y, gbase), f2 = take_lowest(F, y, gbase);
-        const bool replied = trying && f1 >= 0 && f2 < 0;          // the forced reply goes on the board
-        const int ry = replied ? f1 / 15 : 0;
-        const uint32_t rbit = replied ? 1u << (f1 - 15 * ry) : 0u;
-        if (replied && y == ry) def |= rbit;
-        const uint32_t empty = board_row & ~(att | def);
-        gather_rows(def, D);
-        gather_rows(empty | att, N);
-        uint32_t T = completing(D, empty);
-        uint32_t C = four_making(A, N, empty);
-        if (group_rows(T != 0, gbase)) C &= T;                     // a defender four: only its blocking cell is a candidate
-        const int t1 = take_lowest(T, y, gbase), t2 = take_lowest(T, y, gbase);
-        (void)t1;
-        const bool child_has = group_rows(C != 0, gbase) != 0;
-        bool over = false;
-        if (__ballot(state == kInit) != 0ull) over = group_rows((five(A) | five(D)) != 0, gbase) != 0;
+        const Pass ps = pass(w, ln);
 
         // ---- decisions, the same in all sixteen lanes of a group ----
-        if (state == kInit) {
-            if (over) finish(GMK_VCF_OVER, 255, 255, 255);
-            else if (f1 >= 0) finish(GMK_VCF_WIN, f1, 255, 255);
-            else {
-                bool fail = t2 >= 0;
-                if (!fail && 2 > limit) { cut = true; fail = true; }
-                if (!fail && !child_has) fail = true;
-                if (fail) limit_failed();
-                else { mask = C; more = true; state = kRun; }
-            }
-        } else if (trying) {
-            bool retract = true;
-            if (f1 < 0) {
-                // not a four: no candidate and no node (the plane-wide mask does not offer such a cell; this keeps the count exact regardless)
-            } else if (nodes == p.budget) {
-                finish(GMK_VCF_BUDGET, 255, 255, 255);
-            } else {
-                ++nodes;
-                if (f2 >= 0) finish(GMK_VCF_WIN, c, f1, f2);
-                else {
-                    bool fail = t2 >= 0;
-                    if (!fail && depth + 3 > limit) { cut = true; fail = true; }
-                    if (!fail && !child_has) fail = true;
-                    if (!fail) {
-                        stack[depth][lane] = mask | (more ? 0x8000u : 0u) | (static_cast<uint32_t>(c) << 16) | (static_cast<uint32_t>(f1) << 24);
-                        ++depth;
-                        mask = C; more = true; retract = false;
-                    } else if (y == ry) def ^= rbit;
-                }
-            }
-            if (state == kRun && retract) {
-                if (y == cy) att ^= cbit;
-                while (!more) {                                    // climb while the level has nothing left
-                    if (depth == 0) { limit_failed(); break; }
-                    --depth;
-                    const uint32_t w = stack[depth][lane];
-                    mask = w & kRowMask;
-                    more = (w & 0x8000u) != 0;
-                    const int uc = static_cast<int>((w >> 16) & 255u), ur = static_cast<int>(w >> 24);
-                    if (y == uc / 15) att ^= 1u << (uc % 15);
-                    if (y == ur / 15) def ^= 1u << (ur % 15);
-                }
-            }
+        if (w.state == kInit) {
+            if (ps.over) finish(GMK_VCF_OVER, 255, 255, 255);
+            else if (ps.f1 >= 0) finish(GMK_VCF_WIN, ps.f1, 255, 255);
+            else start(w, ps, failed);
+        } else if (w.state == kRun) {
+            step(w, ln, ps, p.budget, stack, [&](int c, int f1, int f2) { finish(GMK_VCF_WIN, c, f1, f2); },
+                 [&]() { finish(GMK_VCF_BUDGET, 255, 255, 255); }, failed);
         }
     }
 }
 
-bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
 
 constexpr int kKnownFlags = GMK_VCF_OPPONENT | GMK_VCF_ITERATIVE;
 

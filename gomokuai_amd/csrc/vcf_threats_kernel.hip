@@ -1,11 +1,12 @@
 // vcf_threats_kernel.hip -- K17: what a stone of the side to move threatens, for every cell, exact and batched.
 //
 // The contract is in include/gomoku_hip.h ("K17").  gmk_vcf_threats is two launches on the caller's stream: K14's kernel for the side to move
-// into the own outputs, then the kernel below over jobs (position, cell), one 16-lane group per job, on K14's representation (vcf_device.h:
-// one board row per lane, DPP row shifts for the neighbours) and with K14's pass.  A job puts the attacker's stone on its cell in registers
-// and starts K14's walk for the attacker on that board, as if the defender had passed.  The walk's first pass already holds the three cheap
-// verdicts, in the contract's order: a five stands (the position itself has none, so the stone made it: FIVE), the defender has a completing
-// cell (IGNORES), the attacker has one (FOUR, one cell or several).  Only a cell with none of the three is searched, with the whole budget.
+// into the own outputs, then the kernel below over jobs (position, cell), one 16-lane group per job, on K14's representation and with K14's
+// walk, both vcf_device.h's (pass, start, step).  This file is what K17 puts around them: the jobs, the cheap verdicts at a root and the cells'
+// verdicts.  A job puts the attacker's stone on its cell in registers and starts K14's walk for the attacker on that board, as if the defender
+// had passed.  The walk's first pass already holds the three cheap verdicts, in the contract's order: a five stands (the position itself has
+// none, so the stone made it: FIVE), the defender has a completing cell (IGNORES), the attacker has one (FOUR, one cell or several).  Only a
+// cell with none of the three is searched, with the whole budget.
 // Occupied cells are settled when the job is taken.  A position that is over or no position is settled by the job of its cell 0 alone, every
 // lane writing its row; its other 224 jobs are nothing.  A group keeps the planes of the position it loaded last, so consecutive jobs of one
 // position read the list once.  A group that has finished takes the next job of its wavefront's slice in the same pass.  No float, no
@@ -17,6 +18,7 @@
 namespace {
 
 using namespace gmk::vcf;
+using gmk::misaligned;
 
 struct ThreatsParams {
     const uint8_t* moves;
@@ -30,18 +32,17 @@ struct ThreatsParams {
 };
 
 __global__ __launch_bounds__(64) void vcf_threats_kernel(ThreatsParams p) {
-    __shared__ uint32_t stack[kLevels][64];                    // K14's: candidates left 0..14, "the level has more" 15, c 16..23, r 24..31
-    const int lane = threadIdx.x, y = lane & 15, group = lane >> 4, gbase = lane & 48;
-    const uint32_t board_row = y < 15 ? kRowMask : 0u;
+    __shared__ Stack stack;
+    const Lane ln;
+    const int y = ln.y, gbase = ln.gbase;
     const bool iterative = (p.flags & GMK_VCF_ITERATIVE) != 0;
     // this wavefront's slice of the n * 225 jobs: `left` jobs from (next_pos, next_cell) on; the grid covers exactly the jobs there are
     const long long total = static_cast<long long>(p.n) * kCells, first = static_cast<long long>(blockIdx.x) * p.per_wave;
     int next_pos = static_cast<int>(first / kCells), next_cell = static_cast<int>(first % kCells);
     int left = first < total ? static_cast<int>(std::min<long long>(p.per_wave, total - first)) : 0;
 
-    int state = kIdle, pos = -1, cell = 0, depth = 0, limit = 0;
-    bool cut = false, more = false;
-    uint32_t nodes = 0, att = 0, def = 0, mask = 0;
+    Walk w;
+    int pos = -1, cell = 0;
     // the position this group loaded last: its own status, and once `planes` is set its two planes (this lane's row)
     int held = -1, ostatus = GMK_VCF_BAD;
     bool planes = false;
@@ -54,31 +55,20 @@ __global__ __launch_bounds__(64) void vcf_threats_kernel(ThreatsParams p) {
             if (p.cell_length) p.cell_length[at] = static_cast<uint8_t>(length);
             if (p.cell_nodes) p.cell_nodes[at] = count;
         }
-        state = kIdle;
+        w.state = kIdle;
     };
     // the search's result (K14's finish, without a pv)
     const auto finish = [&](int status, int length) {
-        settle(status == GMK_VCF_WIN ? GMK_VCF_THREAT_WINS : status == GMK_VCF_NONE ? GMK_VCF_THREAT_QUIET : GMK_VCF_THREAT_UNKNOWN, length, nodes);
+        settle(status == GMK_VCF_WIN ? GMK_VCF_THREAT_WINS : status == GMK_VCF_NONE ? GMK_VCF_THREAT_QUIET : GMK_VCF_THREAT_UNKNOWN, length, w.nodes);
     };
-    const auto limit_failed = [&]() {
-        if (!cut) finish(GMK_VCF_NONE, 0);
-        else if (iterative && limit < p.max_depth) { ++limit; cut = false; state = kInit; }
-        else finish(GMK_VCF_DEPTH, 0);
-    };
+    const auto failed = [&]() { limit_failed(w, iterative, p.max_depth, [&](int status) { finish(status, 0); }); };
 
     for (;;) {
         // ---- groups without a job take the next ones of this wavefront's slice ----
-        const unsigned long long idle = __ballot(state == kIdle);
-        int rank = 0, takers = 0;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int is_idle = static_cast<int>((idle >> (16 * g)) & 1ull);
-            if (g < group) rank += is_idle;
-            takers += is_idle;
-        }
-        if (state == kIdle && rank < left) {
+        const HandOut ho = hand_out(w.state, ln, left);
+        if (w.state == kIdle && ho.rank < left) {
             pos = next_pos;
-            cell = next_cell + rank;
+            cell = next_cell + ho.rank;
             if (cell >= kCells) { cell -= kCells; ++pos; }
             if (pos != held) {
                 held = pos;
@@ -87,23 +77,11 @@ __global__ __launch_bounds__(64) void vcf_threats_kernel(ThreatsParams p) {
             }
             const bool searched = ostatus == GMK_VCF_NONE || ostatus == GMK_VCF_WIN || ostatus == GMK_VCF_DEPTH || ostatus == GMK_VCF_BUDGET;
             if (searched && !planes) {
-                // the own status says that the list is a position; the tests stay, so that nothing outside it is read whatever the status says
-                const int len = p.lens[pos];
-                const bool bad = len < 0 || len > kCells || len > p.stride;
-                uint32_t black = 0, white = 0;
-                if (!bad) {
-                    const uint8_t* list = p.moves + static_cast<size_t>(pos) * static_cast<size_t>(p.stride);
-                    for (int i = 0; i < len; ++i) {
-                        const int stone = list[i];
-                        const int r = stone / 15;
-                        if (r != y) continue;
-                        const uint32_t bit = 1u << (stone - 15 * r);
-                        if (i & 1) white |= bit; else black |= bit;
-                    }
-                }
-                const bool black_attacks = bad || (len & 1) == 0;    // the attacker is the side to move
-                base_att = black_attacks ? black : white;
-                base_def = black_attacks ? white : black;
+                // the own status says that the list is a position; the length's tests stay, so that nothing outside it is read whatever it says
+                const Planes pl = load_moves<false>(p.moves, p.stride, p.lens, pos, ln);
+                const bool black_attacks = pl.bad || (pl.len & 1) == 0;    // the attacker is the side to move
+                base_att = black_attacks ? pl.black : pl.white;
+                base_def = black_attacks ? pl.white : pl.black;
                 planes = true;
             }
             if (searched) {
@@ -111,13 +89,7 @@ __global__ __launch_bounds__(64) void vcf_threats_kernel(ThreatsParams p) {
                 const uint32_t jbit = y == jy ? 1u << (cell - 15 * jy) : 0u;
                 const bool taken = group_rows(((base_att | base_def) & jbit) != 0, gbase) != 0;
                 if (taken) settle(GMK_VCF_THREAT_NONE, 0, 0u);
-                else {
-                    att = base_att | jbit;                         // P + [c], the defender passes: K14's root with GMK_VCF_OPPONENT
-                    def = base_def;
-                    nodes = 0; depth = 0; cut = false; more = false; mask = 0;
-                    limit = iterative ? 1 : p.max_depth;
-                    state = kInit;
-                }
+                else w.reset(base_att | jbit, base_def, iterative ? 1 : p.max_depth);      // P + [c], the defender passes: K14's root with GMK_VCF_OPPONENT
             } else if (cell == 0) {
                 // over, or no position: every cell at once
                 if (y < 15) {
@@ -131,97 +103,29 @@ __global__ __launch_bounds__(64) void vcf_threats_kernel(ThreatsParams p) {
             }
             // else: a cell of such a position, which the job of its cell 0 writes
         }
-        const int taken_jobs = takers < left ? takers : left;
-        left -= taken_jobs;
-        next_cell += taken_jobs;
+        left -= ho.taken;
+        next_cell += ho.taken;
         if (next_cell >= kCells) { next_cell -= kCells; ++next_pos; }
-        if (__ballot(state != kIdle) == 0ull) {                    // nothing to walk: only jobs that were settled as they were taken, or the slice is done
+        if (__ballot(w.state != kIdle) == 0ull) {                  // nothing to walk: only jobs that were settled as they were taken, or the slice is done
             if (left == 0) break;
             continue;
         }
 
-        // ---- the pass (K14's): every group in the same instructions ----
-        const bool trying = state == kRun;                         // such a group has a candidate: `mask` is not empty
-        uint32_t popped = trying ? mask : 0u;
-        const int c = take_lowest(popped, y, gbase);
-        const uint32_t more_left = group_rows(popped != 0, gbase);
-        const int cy = trying ? c / 15 : 0;
-        const uint32_t cbit = trying ? 1u << (c - 15 * cy) : 0u;
-        if (trying) {
-            mask = popped;
-            more = more_left != 0;
-            if (y == cy) att |= cbit;
-        }
-        uint32_t A[9], D[9], N[9];
-        gather_rows(att, A);
-        uint32_t F = completing(A, board_row & ~(att | def));
-        const int f1 = take_lowest(F, y, gbase), f2 = take_lowest(F, y, gbase);
-        const bool replied = trying && f1 >= 0 && f2 < 0;          // the forced reply goes on the board
-        const int ry = replied ? f1 / 15 : 0;
-        const uint32_t rbit = replied ? 1u << (f1 - 15 * ry) : 0u;
-        if (replied && y == ry) def |= rbit;
-        const uint32_t empty = board_row & ~(att | def);
-        gather_rows(def, D);
-        gather_rows(empty | att, N);
-        uint32_t T = completing(D, empty);
-        uint32_t C = four_making(A, N, empty);
-        if (group_rows(T != 0, gbase)) C &= T;                     // a defender four: only its blocking cell is a candidate
-        const int t1 = take_lowest(T, y, gbase), t2 = take_lowest(T, y, gbase);
-        const bool child_has = group_rows(C != 0, gbase) != 0;
-        bool over = false;
-        if (__ballot(state == kInit) != 0ull) over = group_rows((five(A) | five(D)) != 0, gbase) != 0;
+        const Pass ps = pass(w, ln);
 
         // ---- decisions, the same in all sixteen lanes of a group ----
-        if (state == kInit) {
+        if (w.state == kInit) {
             // the three cheap verdicts hold at every limit of an iterative walk alike, so only its first pass can meet them
-            if (over) settle(GMK_VCF_THREAT_FIVE, 0, 0u);
-            else if (t1 >= 0) settle(GMK_VCF_THREAT_IGNORES, 0, 0u);
-            else if (f1 >= 0) settle(GMK_VCF_THREAT_FOUR, f2 >= 0 ? 2 : 1, 0u);
-            else {
-                bool fail = false;                                 // K14's t2 >= 0 cannot be: the defender has no completing cell
-                if (2 > limit) { cut = true; fail = true; }
-                if (!fail && !child_has) fail = true;
-                if (fail) limit_failed();
-                else { mask = C; more = true; state = kRun; }
-            }
-        } else if (trying) {
-            bool retract = true;
-            if (f1 < 0) {
-                // not a four: no candidate and no node (K14)
-            } else if (nodes == p.budget) {
-                finish(GMK_VCF_BUDGET, 0);
-            } else {
-                ++nodes;
-                if (f2 >= 0) finish(GMK_VCF_WIN, depth + 2);
-                else {
-                    bool fail = t2 >= 0;
-                    if (!fail && depth + 3 > limit) { cut = true; fail = true; }
-                    if (!fail && !child_has) fail = true;
-                    if (!fail) {
-                        stack[depth][lane] = mask | (more ? 0x8000u : 0u) | (static_cast<uint32_t>(c) << 16) | (static_cast<uint32_t>(f1) << 24);
-                        ++depth;
-                        mask = C; more = true; retract = false;
-                    } else if (y == ry) def ^= rbit;
-                }
-            }
-            if (state == kRun && retract) {
-                if (y == cy) att ^= cbit;
-                while (!more) {                                    // climb while the level has nothing left
-                    if (depth == 0) { limit_failed(); break; }
-                    --depth;
-                    const uint32_t w = stack[depth][lane];
-                    mask = w & kRowMask;
-                    more = (w & 0x8000u) != 0;
-                    const int uc = static_cast<int>((w >> 16) & 255u), ur = static_cast<int>(w >> 24);
-                    if (y == uc / 15) att ^= 1u << (uc % 15);
-                    if (y == ur / 15) def ^= 1u << (ur % 15);
-                }
-            }
+            if (ps.over) settle(GMK_VCF_THREAT_FIVE, 0, 0u);
+            else if (ps.t1 >= 0) settle(GMK_VCF_THREAT_IGNORES, 0, 0u);
+            else if (ps.f1 >= 0) settle(GMK_VCF_THREAT_FOUR, ps.f2 >= 0 ? 2 : 1, 0u);
+            else start(w, ps, failed);                             // its t2 >= 0 cannot be: the defender has no completing cell
+        } else if (w.state == kRun) {
+            step(w, ln, ps, p.budget, stack, [&](int, int, int) { finish(GMK_VCF_WIN, w.depth + 2); }, [&]() { finish(GMK_VCF_BUDGET, 0); }, failed);
         }
     }
 }
 
-bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
 
 bool bad_arguments(const void* moves, int stride, const void* lens, int n, int max_depth, int flags, const void* status, const void* verdict) {
     return n < 0 || stride < 1 || max_depth < 1 || max_depth > GMK_VCF_MAX_DEPTH || (flags & ~GMK_VCF_ITERATIVE) != 0 ||

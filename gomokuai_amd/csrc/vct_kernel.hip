@@ -244,7 +244,7 @@ __global__ void vct_write_kernel(const LevelView* levels, int n, const int32_t* 
         for (int i = cells; i < GMK_VCT_PV; ++i) line[i] = 255;
 }
 
-bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
+using gmk::misaligned;
 
 bool bad_arguments(const void* moves, int stride, const void* lens, int n, int max_depth, int flags, int max_threats, int max_positions) {
     return n < 0 || stride < 1 || max_depth < 1 || max_depth > GMK_VCF_MAX_DEPTH || (flags & ~GMK_VCF_ITERATIVE) != 0 || max_threats < 1 ||

@@ -12,6 +12,7 @@ import az_defend_reference as Z
 import az_leaves_reference as R
 import az_proof_reference as P
 import az_vcf_reference as A
+import vcf_defend_reference as D
 from gomokuai_amd import lib as G
 from gomokuai_amd import selfplay
 from test_az_defend_reference import peaked
@@ -148,6 +149,28 @@ def test_root_tables_are_the_defence_solvers(n):
         seen |= _same_tables(tree, positions, depth, budget)
         tree.close()
     assert G.VCF_WIN in seen and (n < 3 or G.VCF_BUDGET in seen) and (n < 17 or G.VCF_NONE in seen)
+
+
+# Branches of the shared walk (vcf_device.h) that the positions above do not take in the two K7 + K15 kernels; found and confirmed on
+# tests/vcf_reference.py.  TANGLE at (8, 64): the threat's walk and a cell's search both meet a forced reply that makes two completing cells,
+# a search starts from a root where the defender's stone did, and one runs out of budget.  At depth 1 a walk is cut at its root: the threat's
+# on OPEN_THREE, and on CLOSED_FOUR the search of the one cell that blocks the four.
+TANGLE = [65, 128, 144, 115, 110, 67, 85, 66, 141, 111, 83, 154, 143, 140, 98, 100, 69, 126, 159, 156, 95, 130, 113, 94]
+CLOSED_FOUR = [110, 109, 111, 194, 112, 149, 113, 150, 210]      # black's four with one end closed, white to move
+
+
+def test_root_tables_on_the_walks_rarer_branches():
+    positions = [TANGLE, CLOSED_FOUR, Z.OPEN_THREE]
+    for depth, budget, threats in ((8, 64, [G.VCF_WIN, G.VCF_WIN, G.VCF_WIN]), (1, 64, [G.VCF_DEPTH, G.VCF_WIN, G.VCF_DEPTH])):
+        tree = _tree(positions, 1, 1.0, depth, budget)
+        tree.select()
+        _same_tables(tree, positions, depth, budget)
+        got = tree.defend_verdicts()
+        assert list(got["threat_status"]) == threats, (depth, budget)
+        if depth == 1:                                           # every other cell loses at once; the block's search is cut: UNKNOWN, no node
+            block = int(np.flatnonzero(got["verdict"][1] == D.CELL_UNKNOWN)[0])
+            assert block == 114 and got["nodes"][1][block] == 0 and (got["verdict"][1] == D.CELL_LOSES).sum() == N - len(CLOSED_FOUR) - 1
+        tree.close()
 
 
 def test_tables_at_eight_leaves_on_one_game():
