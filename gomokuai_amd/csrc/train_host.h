@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "../../include/gomoku_hip.h"
 #include "pvnet_pack.h"
 
 namespace gmk {
@@ -61,6 +62,103 @@ inline bool valid_batch(int n, int max_batch, const void* const* required, int n
     for (int i = 0; i < n_required; ++i) if (!required[i] || !aligned4(required[i])) return false;
     for (int i = 0; i < n_optional; ++i) if (optional[i] && !aligned4(optional[i])) return false;
     return true;
+}
+
+// ---- the kernel-level entries (gmk_train_kernel_*): the caller chooses strides and extents, so every index is worked out here, in int64, before
+// anything is launched.  Each check returns nullptr if the call fits and the name of the first field at fault otherwise.
+constexpr int64_t kStrideLimit = int64_t(1) << 31;     // strides and dimensions below 2^31: every product of two of them fits an int64
+constexpr int64_t kGridYZLimit = 65535;                // blocks along y (rows / 128) and z (k slabs) of one launch
+inline bool stride_ok(int64_t s) { return s >= 0 && s < kStrideLimit; }
+inline bool required_ptr(const void* p) { return p && aligned4(p); }
+
+inline const char* gemm_fits(const gmk_train_gemm_desc& d) {
+    if (d.M < 1) return "M";
+    if (d.N < 1) return "N";
+    if (d.K < 1) return "K";
+    if ((static_cast<int64_t>(d.M) + 127) / 128 > kGridYZLimit) return "M";
+    if (!required_ptr(d.A)) return "A";
+    if (!required_ptr(d.B)) return "B";
+    if (!stride_ok(d.sam)) return "sam";
+    if (!stride_ok(d.sak)) return "sak";
+    if (!stride_ok(d.sbk)) return "sbk";
+    if (!stride_ok(d.sbn)) return "sbn";
+    const int64_t M = d.M, N = d.N, K = d.K;
+    if ((M - 1) * d.sam + (K - 1) * d.sak >= d.a_floats) return "a_floats";
+    if ((K - 1) * d.sbk + (N - 1) * d.sbn >= d.b_floats) return "b_floats";
+    if (d.kslab < 1) return "kslab";
+    if (d.nz < 1 || d.nz > kGridYZLimit) return "nz";
+    const int64_t span = static_cast<int64_t>(d.nz) * d.kslab;
+    if (span < K || span >= kStrideLimit) return "nz";
+    // the optional operands are held to their extents in both forms, though the split-K form does not read them
+    if (d.bias && (!aligned4(d.bias) || N - 1 >= d.bias_floats)) return "bias";
+    if (d.mask) {
+        if (!aligned4(d.mask)) return "mask";
+        if (!stride_ok(d.ldm)) return "ldm";
+        if ((M - 1) * d.ldm + (N - 1) >= d.mask_floats) return "mask_floats";
+    }
+    if (d.relu != 0 && d.relu != 1) return "relu";
+    if (d.part) {                                      // split-K: nz slabs, each with at least one k
+        if (!aligned4(d.part)) return "part";
+        if ((static_cast<int64_t>(d.nz) - 1) * d.kslab >= K) return "nz";
+        if (d.z0 < 0) return "z0";
+        if (d.part_floats < M * N || static_cast<int64_t>(d.z0) + d.nz > d.part_floats / (M * N)) return "part_floats";
+        return nullptr;
+    }
+    if (d.nz != 1) return "nz";                        // direct: one slab that holds every k
+    if (d.kslab < K) return "kslab";
+    if (d.nsplit < 0) return "nsplit";
+    if (d.cq < 1) return "cq";
+    const int64_t nc = d.nsplit < N ? d.nsplit : N;    // columns 0 .. nc - 1 go to C, the rest to C2
+    if (nc > 0) {
+        if (!required_ptr(d.C)) return "C";
+        if (!stride_ok(d.ldc)) return "ldc";
+        int64_t row = nc;                              // one row's extent under the store map
+        if (d.cq < nc) {
+            if (!stride_ok(d.cs) || d.cs < d.cq) return "cs";          // groups of cq columns, cs apart: they must not overlap
+            row = ((nc - 1) / d.cq) * d.cs + (nc - 1) % d.cq + 1;
+        }
+        if (d.ldc < row) return "ldc";
+        if ((M - 1) * d.ldc + row > d.c_floats) return "c_floats";
+    }
+    if (nc < N) {
+        if (!required_ptr(d.C2)) return "C2";
+        if (!stride_ok(d.ldc2) || d.ldc2 < N - nc) return "ldc2";
+        if ((M - 1) * d.ldc2 + (N - nc) > d.c2_floats) return "c2_floats";
+    }
+    return nullptr;
+}
+
+inline const char* reduce_fits(const void* part, int nz, int64_t mn, const void* out) {
+    if (!required_ptr(part)) return "part";
+    if (!required_ptr(out)) return "out";
+    if (nz < 1) return "nz";
+    if (mn < 1 || mn >= kStrideLimit) return "mn";     // nz * mn fits an int64, (mn + 255) / 256 a grid
+    return nullptr;
+}
+
+// npos positions of C channels: 225 npos rows of 9 C columns, all of it below 2^31 floats
+inline const char* conv_fits(int C, int npos) {
+    if (C < 1) return "C";
+    if (npos < 1) return "npos";
+    if (static_cast<int64_t>(C) * npos > (kStrideLimit - 1) / (9 * kPix)) return "npos";
+    return nullptr;
+}
+inline const char* im2col_fits(const void* in, int64_t in_floats, int64_t sb, int64_t sp, int64_t sc, int C, int npos, const void* col) {
+    if (const char* bad = conv_fits(C, npos)) return bad;
+    if (!required_ptr(in)) return "in";
+    if (!required_ptr(col)) return "col";
+    if (!stride_ok(sb)) return "sb";
+    if (!stride_ok(sp)) return "sp";
+    if (!stride_ok(sc)) return "sc";
+    if ((npos - int64_t(1)) * sb + (kPix - 1) * sp + (C - int64_t(1)) * sc >= in_floats) return "in_floats";
+    return nullptr;
+}
+inline const char* col2im_fits(const void* dcol, int C, int npos, const void* mask, const void* out) {
+    if (const char* bad = conv_fits(C, npos)) return bad;
+    if (!required_ptr(dcol)) return "dcol";
+    if (!required_ptr(mask)) return "mask";
+    if (!required_ptr(out)) return "out";
+    return nullptr;
 }
 
 // ---- the repack table: for every float of a gmk_pvnet's seven device buffers, 1 + the index of the parameter it holds, or 0 for a zero ----

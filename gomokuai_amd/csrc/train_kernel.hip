@@ -359,11 +359,13 @@ int launch_gemm(const GemmArgs& g, int nz, hipStream_t stream) {
 
 #define GMK_TRY(expr) do { const int rc_ = (expr); if (rc_ != GMK_OK) return rc_; } while (0)
 
-int reduce_into(const gmk_trainer* T, int nz, long mn, float* out, hipStream_t stream) {
-    hipLaunchKernelGGL(train_reduce_kernel, dim3(static_cast<unsigned>((mn + 255) / 256)), dim3(256), 0, stream, T->splitk, nz, mn, out);
+int launch_reduce(const float* part, int nz, long mn, float* out, hipStream_t stream) {
+    hipLaunchKernelGGL(train_reduce_kernel, dim3(static_cast<unsigned>((mn + 255) / 256)), dim3(256), 0, stream, part, nz, mn, out);
     GMK_HIP_CHECK(hipGetLastError());
     return GMK_OK;
 }
+
+int reduce_into(const gmk_trainer* T, int nz, long mn, float* out, hipStream_t stream) { return launch_reduce(T->splitk, nz, mn, out, stream); }
 
 // out[N] = the column sums of X[rows][N], K slabs of kKSlabRows rows, added in slab order
 int column_sums(const gmk_trainer* T, const float* X, long rows, int N, float* out, hipStream_t stream) {
@@ -377,6 +379,13 @@ int column_sums(const gmk_trainer* T, const float* X, long rows, int N, float* o
 int launch_im2col(const float* in, long sb, long sp, long sc, int C, int npos, float* col, hipStream_t stream) {
     const long total = static_cast<long>(npos) * kPix * 9 * C;
     hipLaunchKernelGGL(im2col3x3_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, stream, in, sb, sp, sc, C, npos, col);
+    GMK_HIP_CHECK(hipGetLastError());
+    return GMK_OK;
+}
+
+int launch_col2im(const float* dcol, int C, int npos, const float* mask, float* out, hipStream_t stream) {
+    const long total = static_cast<long>(npos) * kPix * C;
+    hipLaunchKernelGGL(col2im3x3_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, stream, dcol, C, npos, mask, out);
     GMK_HIP_CHECK(hipGetLastError());
     return GMK_OK;
 }
@@ -483,11 +492,8 @@ int run_backward(const gmk_trainer* T, const float* d_states, int n, float* G, h
             z += nz;
             if (l > 0) {   // dcol takes the columns' place, then the gather
                 GMK_TRY(launch_gemm(gemm(dy, N, 1, T->param(kConv[l].w), K, 1, srows, K, N, T->col, K), 1, stream));
-                const long total = static_cast<long>(srows) * cin;
                 const long at = static_cast<long>(pos0) * kPix * cin;
-                hipLaunchKernelGGL(col2im3x3_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, stream, T->col, cin, ns,
-                                   (l == 1 ? T->act1 : T->act2) + at, dacts[l - 1] + at);
-                GMK_HIP_CHECK(hipGetLastError());
+                GMK_TRY(launch_col2im(T->col, cin, ns, (l == 1 ? T->act1 : T->act2) + at, dacts[l - 1] + at, stream));
             }
         }
         GMK_TRY(reduce_into(T, z, static_cast<long>(N) * K, T->grad(G, kConv[l].w), stream));
@@ -678,4 +684,36 @@ extern "C" int gmk_train_info(gmk_trainer* T, int64_t* h_step, int64_t* h_scratc
     if (h_max_batch) *h_max_batch = T->max_batch;
     if (h_param_floats) *h_param_floats = kParams;
     return GMK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// The kernels on their own (include/gomoku_hip.h): the trainer's launchers on the caller's operands, after train_host.h has held every index
+// the kernel can form to the extents the caller states.  Nothing is launched for a descriptor that does not fit.
+extern "C" int gmk_train_kernel_gemm(const gmk_train_gemm_desc* d, void* stream) {
+    if (not_ready()) return GMK_ERR_STATE;
+    if (!d) { gmk::set_error("gmk_train_kernel_gemm: desc is NULL"); return GMK_ERR_ARG; }
+    if (const char* bad = gemm_fits(*d)) { gmk::set_error("gmk_train_kernel_gemm: refused, field %s (addressing must stay inside the stated extents)", bad); return GMK_ERR_ARG; }
+    GemmArgs g = gemm(d->A, d->sam, d->sak, d->B, d->sbk, d->sbn, d->M, d->N, d->K, d->C, d->ldc);
+    g.kslab = d->kslab; g.part = d->part; g.z0 = d->z0;
+    g.cq = d->cq; g.cs = d->cs; g.nsplit = d->nsplit; g.C2 = d->C2; g.ldc2 = d->ldc2;
+    g.bias = d->bias; g.relu = d->relu; g.mask = d->mask; g.ldm = d->ldm;
+    return launch_gemm(g, d->nz, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int gmk_train_kernel_reduce(const float* part, int nz, int64_t mn, float* out, void* stream) {
+    if (not_ready()) return GMK_ERR_STATE;
+    if (const char* bad = reduce_fits(part, nz, mn, out)) { gmk::set_error("gmk_train_kernel_reduce: refused, argument %s", bad); return GMK_ERR_ARG; }
+    return launch_reduce(part, nz, static_cast<long>(mn), out, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int gmk_train_kernel_im2col(const float* in, int64_t in_floats, int64_t sb, int64_t sp, int64_t sc, int C, int npos, float* col, void* stream) {
+    if (not_ready()) return GMK_ERR_STATE;
+    if (const char* bad = im2col_fits(in, in_floats, sb, sp, sc, C, npos, col)) { gmk::set_error("gmk_train_kernel_im2col: refused, argument %s", bad); return GMK_ERR_ARG; }
+    return launch_im2col(in, static_cast<long>(sb), static_cast<long>(sp), static_cast<long>(sc), C, npos, col, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int gmk_train_kernel_col2im(const float* dcol, int C, int npos, const float* mask, float* out, void* stream) {
+    if (not_ready()) return GMK_ERR_STATE;
+    if (const char* bad = col2im_fits(dcol, C, npos, mask, out)) { gmk::set_error("gmk_train_kernel_col2im: refused, argument %s", bad); return GMK_ERR_ARG; }
+    return launch_col2im(dcol, C, npos, mask, out, static_cast<hipStream_t>(stream));
 }

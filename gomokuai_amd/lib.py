@@ -20,6 +20,21 @@ class GmkError(RuntimeError):
     pass
 
 
+class TrainGemmDesc(C.Structure):
+    """gmk_train_gemm_desc (include/gomoku_hip.h): train_gemm_kernel's argument block and the extent, in floats, of every buffer it names."""
+    _fields_ = [("A", C.c_void_p), ("sam", C.c_int64), ("sak", C.c_int64), ("a_floats", C.c_int64),
+                ("B", C.c_void_p), ("sbk", C.c_int64), ("sbn", C.c_int64), ("b_floats", C.c_int64),
+                ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+                ("kslab", C.c_int32), ("nz", C.c_int32), ("z0", C.c_int32),
+                ("part", C.c_void_p), ("part_floats", C.c_int64),
+                ("C", C.c_void_p), ("ldc", C.c_int64), ("cs", C.c_int64), ("c_floats", C.c_int64),
+                ("C2", C.c_void_p), ("ldc2", C.c_int64), ("c2_floats", C.c_int64),
+                ("cq", C.c_int32), ("nsplit", C.c_int32),
+                ("bias", C.c_void_p), ("bias_floats", C.c_int64),
+                ("mask", C.c_void_p), ("ldm", C.c_int64), ("mask_floats", C.c_int64),
+                ("relu", C.c_int32)]
+
+
 class TableInfo(C.Structure):
     _fields_ = [("n_patterns", C.c_int32), ("n_states", C.c_int32), ("dat_size", C.c_int32),
                 ("max_emissions", C.c_int32), ("trans_words", C.c_int32), ("emit_words", C.c_int32),
@@ -61,6 +76,7 @@ EXPORTS = [
     "gmk_replay_sample", "gmk_replay_draw_host", "gmk_replay_image_bytes", "gmk_replay_snapshot", "gmk_replay_restore", "gmk_replay_image_check_host",
     "gmk_train_create", "gmk_train_destroy", "gmk_train_forward", "gmk_train_grads", "gmk_train_step", "gmk_train_params", "gmk_train_set_params",
     "gmk_train_get_block", "gmk_train_set_block", "gmk_train_set_step_count", "gmk_train_export", "gmk_train_info",
+    "gmk_train_kernel_gemm", "gmk_train_kernel_reduce", "gmk_train_kernel_im2col", "gmk_train_kernel_col2im",
 ]
 
 
@@ -220,6 +236,10 @@ def load():
     L.gmk_train_set_step_count.argtypes = [vp, C.c_int64]
     L.gmk_train_export.argtypes = [vp, vp, vp]
     L.gmk_train_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.gmk_train_kernel_gemm.argtypes = [C.POINTER(TrainGemmDesc), vp]
+    L.gmk_train_kernel_reduce.argtypes = [vp, C.c_int, C.c_int64, vp, vp]
+    L.gmk_train_kernel_im2col.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, vp, vp]
+    L.gmk_train_kernel_col2im.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
     _lib = L
     return L
 
@@ -663,6 +683,50 @@ class TrainerHandle:
         step, scratch, mb, pf = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
         _check(load().gmk_train_info(self.h, C.byref(step), C.byref(scratch), C.byref(mb), C.byref(pf)))
         return {"step": step.value, "scratch_bytes": scratch.value, "max_batch": mb.value, "param_floats": pf.value}
+
+
+# K11's kernels on their own (gmk_train_kernel_*): a buffer is a float32 torch tensor on the device, or a device pointer as an int
+TRAIN_GEMM_NONE = 2 ** 31 - 1          # cq / nsplit: "no grouping" / "no split", as the trainer's own descriptors have them
+_GEMM_BUFFERS = {"A": "a_floats", "B": "b_floats", "part": "part_floats", "C": "c_floats", "C2": "c2_floats", "bias": "bias_floats", "mask": "mask_floats"}
+
+
+def _dev_ptr(buf):
+    if buf is None:
+        return None
+    return int(buf.data_ptr()) if hasattr(buf, "data_ptr") else int(buf)
+
+
+def train_gemm_desc(**fields):
+    """-> TrainGemmDesc.  Buffers (A, B, part, C, C2, bias, mask) are torch tensors -- the extent is then what is left of the tensor's storage
+    from its first element on -- or device pointers as ints with the `*_floats` field given.  Defaults: one k slab that holds every k, no
+    grouping, no split, no bias, no ReLU, no mask: the direct form as the trainer's gemm() sets it up."""
+    d = TrainGemmDesc()
+    d.kslab, d.nz, d.cq, d.nsplit = max(int(fields.get("K", 1)), 1), 1, TRAIN_GEMM_NONE, TRAIN_GEMM_NONE
+    for name, value in fields.items():
+        if name in _GEMM_BUFFERS:
+            setattr(d, name, _dev_ptr(value))
+            if hasattr(value, "data_ptr") and _GEMM_BUFFERS[name] not in fields:
+                setattr(d, _GEMM_BUFFERS[name], value.untyped_storage().nbytes() // 4 - value.storage_offset())
+        else:
+            setattr(d, name, int(value))
+    return d
+
+
+def train_kernel_gemm(desc, stream=None):
+    """train_gemm_kernel through the trainer's launcher; GmkError (status -3, the field named) if the descriptor's addressing does not fit."""
+    _check(load().gmk_train_kernel_gemm(C.byref(desc), stream))
+
+
+def train_kernel_reduce(part, nz, mn, out, stream=None):
+    _check(load().gmk_train_kernel_reduce(_dev_ptr(part), int(nz), int(mn), _dev_ptr(out), stream))
+
+
+def train_kernel_im2col(inp, in_floats, sb, sp, sc, channels, npos, col, stream=None):
+    _check(load().gmk_train_kernel_im2col(_dev_ptr(inp), int(in_floats), int(sb), int(sp), int(sc), int(channels), int(npos), _dev_ptr(col), stream))
+
+
+def train_kernel_col2im(dcol, channels, npos, mask, out, stream=None):
+    _check(load().gmk_train_kernel_col2im(_dev_ptr(dcol), int(channels), int(npos), _dev_ptr(mask), _dev_ptr(out), stream))
 
 
 # ---------------- K2: incrementally maintained evaluator states ----------------

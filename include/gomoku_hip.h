@@ -1028,6 +1028,57 @@ int gmk_train_set_step_count(gmk_trainer* trainer, int64_t step);
 int gmk_train_export(gmk_trainer* trainer, gmk_pvnet* net, void* stream);
 int gmk_train_info(gmk_trainer* trainer, int64_t* h_step, int64_t* h_scratch_bytes, int32_t* h_max_batch, int32_t* h_param_floats);
 
+/* ---- K11's kernels on their own: the GEMM, its split-K reduction, im2col and col2im on caller-supplied operands ----
+ * For tests of the kernels.  Each entry goes through the launcher the trainer itself uses, so the tile variant a shape gets (N <= 32,
+ * N <= 64, N > 64) is the trainer's choice.  All pointers are device pointers of float32, strides and extents count floats, everything is
+ * asynchronous on `stream`.  The strides are the caller's, so the host checks the addressing in 64-bit integers BEFORE the launch: a
+ * descriptor whose largest index leaves a buffer it names, or whose store map writes one float twice, returns GMK_ERR_ARG, nothing is
+ * launched and gmk_last_error() names the field.
+ *
+ * gmk_train_gemm_desc, field by field (the kernel's own argument block plus the extent of every buffer):
+ *   A, sam, sak, a_floats    A(m, k) = A[m * sam + k * sak], m < M, k < K.  Strides in [0, 2^31); 0 repeats one element along that axis.
+ *   B, sbk, sbn, b_floats    B(k, n) = B[k * sbk + n * sbn], n < N.  An operand whose k stride is 1 is loaded k-fastest; the sums are the same.
+ *   M, N, K                  all >= 1.  The result is S(m, n) = sum over k of A(m, k) B(k, n), float32 products accumulated in float32 in an
+ *                            order that depends on (M, N, K, kslab, the two "k stride is 1" facts) only, never on the data or on other rows.
+ *   kslab, nz, z0, part, part_floats
+ *                            part != NULL is the SPLIT-K form: slab z < nz holds the raw sums over k in [z * kslab, min(K, (z + 1) * kslab))
+ *                            at part[((z0 + z) * M + m) * N + n]; no epilogue -- bias, relu, mask, C and C2 are not read or written.
+ *                            kslab >= 1, z0 >= 0, (z0 + nz) * M * N <= part_floats, and nz is EXACTLY ceil(K / kslab): a slab that would hold
+ *                            no k at all is refused, not written as zeros.  nz * kslab < 2^31.
+ *                            part == NULL is the DIRECT form: nz must be 1 and kslab >= K (anything else would drop terms silently).
+ *   C, ldc, cq, cs, c_floats the direct form's output for columns n < min(N, nsplit): v = S(m, n) + bias[n], then max(v, 0) if relu, then 0
+ *                            unless mask(m, n) > 0, stored at C[m * ldc + (n / cq) * cs + n % cq].  cq >= N is "no grouping" (cs is then
+ *                            not used; the trainer passes cq = INT_MAX, cs = 0).  With cq < N, cs >= cq; ldc >= one row's extent under the map.
+ *   nsplit, C2, ldc2, c2_floats
+ *                            columns n >= nsplit go to C2[m * ldc2 + n - nsplit] instead (same epilogue); nsplit >= N is "no split"
+ *                            (INT_MAX in the trainer, C2 may be NULL); nsplit = 0 sends every column to C2 and C is not touched.
+ *   bias, bias_floats        NULL, or [N].
+ *   relu                     0 or 1.
+ *   mask, ldm, mask_floats   NULL, or mask(m, n) = mask[m * ldm + n]: only `> 0` keeps (0, -0, negatives and NaN all give 0).
+ * gmk_train_kernel_reduce: out[i] = part[0 * mn + i] + part[1 * mn + i] + ... + part[(nz - 1) * mn + i], float32, in that order, i < mn.
+ * gmk_train_kernel_im2col: 3x3 'same' columns of npos 15x15 positions of C channels: the input element (position b, pixel p, channel c) is
+ *   in[b * sb + p * sp + c * sc] (largest index < in_floats), col[(b * 225 + p) * 9 C + c * 9 + tap] is the pixel tap / 3 - 1 rows and
+ *   tap % 3 - 1 columns away, or 0.0f outside the board.  col holds npos * 225 * 9 C floats.
+ * gmk_train_kernel_col2im: out[row][c] (row = b * 225 + p, channels-last, npos * 225 * C floats) = the float32 sum, in tap order 0..8, of
+ *   the dcol[row'][c * 9 + tap] whose tap reads pixel p -- or 0 unless mask[row][c] > 0.  dcol holds npos * 225 * 9 C floats. */
+typedef struct gmk_train_gemm_desc {
+    const float* A; int64_t sam, sak, a_floats;
+    const float* B; int64_t sbk, sbn, b_floats;
+    int32_t M, N, K;
+    int32_t kslab, nz, z0;
+    float* part; int64_t part_floats;
+    float* C; int64_t ldc, cs, c_floats;
+    float* C2; int64_t ldc2, c2_floats;
+    int32_t cq, nsplit;
+    const float* bias; int64_t bias_floats;
+    const float* mask; int64_t ldm, mask_floats;
+    int32_t relu;
+} gmk_train_gemm_desc;
+int gmk_train_kernel_gemm(const gmk_train_gemm_desc* desc, void* stream);
+int gmk_train_kernel_reduce(const float* part, int nz, int64_t mn, float* out, void* stream);
+int gmk_train_kernel_im2col(const float* in, int64_t in_floats, int64_t sb, int64_t sp, int64_t sc, int C, int npos, float* col, void* stream);
+int gmk_train_kernel_col2im(const float* dcol, int C, int npos, const float* mask, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,8 @@ import pytest
 from gomokuai_amd import lib as G
 
 TRAIN_SYMBOLS = ("gmk_train_create", "gmk_train_destroy", "gmk_train_forward", "gmk_train_grads", "gmk_train_step", "gmk_train_params",
-                 "gmk_train_set_params", "gmk_train_get_block", "gmk_train_set_block", "gmk_train_set_step_count", "gmk_train_export", "gmk_train_info")
+                 "gmk_train_set_params", "gmk_train_get_block", "gmk_train_set_block", "gmk_train_set_step_count", "gmk_train_export", "gmk_train_info",
+                 "gmk_train_kernel_gemm", "gmk_train_kernel_reduce", "gmk_train_kernel_im2col", "gmk_train_kernel_col2im")
 
 
 def test_symbols_are_declared_and_exported():
@@ -41,6 +42,11 @@ def test_no_cpu_fallback_without_device():
     assert L.gmk_train_set_step_count(None, 0) == -4
     assert L.gmk_train_export(None, None, None) == -4
     assert L.gmk_train_info(None, None, None, None, None) == -4
+    assert L.gmk_train_kernel_gemm(C.byref(G.train_gemm_desc(M=1, N=1, K=1)), None) == -4
+    assert L.gmk_train_kernel_gemm(None, None) == -4
+    assert L.gmk_train_kernel_reduce(None, 1, 1, None, None) == -4
+    assert L.gmk_train_kernel_im2col(None, 0, 0, 0, 0, 1, 1, None, None) == -4
+    assert L.gmk_train_kernel_col2im(None, 1, 1, None, None, None) == -4
     assert L.gmk_train_destroy(None) == 0
     with pytest.raises(G.GmkError):
         G.TrainerHandle({name: __import__("numpy").zeros(shape, "float32") for name, shape in G.TRAIN_TENSORS}, 8)
