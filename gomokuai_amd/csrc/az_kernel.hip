@@ -12,7 +12,8 @@
 //     az_expand_kernel      children with the returned priors, value backed up to the root
 // all on one HIP stream (the three steps can be captured in a hipGraph and replayed per playout).
 // With GMK_OPT_AZ_LEAVES = L > 1 a step takes up to L leaves from every game, steered apart by virtual loss, and the batch has live x L rows:
-// az_select_leaves_kernel / az_expand_leaves_kernel below, for searches of few games.
+// az_select_leaves_kernel / az_expand_leaves_kernel, for searches of few games.  The two pairs of kernels are callers of one descent, one leaf
+// expansion and one view of a pending leaf (descend, leaf_candidates / write_children / leaf_proofs, pending_leaf).
 // With GMK_OPT_AZ_VCF_DEPTH = D > 0 the pending leaves are also handed to K14's exact solver of forced wins by fours (az_vcf_leaves_kernel, right
 // behind the select kernel), and the expand kernels answer a solved leaf themselves: include/gomoku_hip.h, "K7 + K14".
 // With GMK_OPT_AZ_VCF_DEFEND on top of that and of GMK_OPT_AZ_PROOF the leaves the solver did not answer are asked what the opponent threatens
@@ -24,6 +25,7 @@
 #include <cmath>
 #include <cstring>
 #include <random>
+#include <type_traits>
 #include <vector>
 
 #include "board_device.h"
@@ -145,6 +147,11 @@ __device__ uint32_t az_prove(uint2* kids, const uint32_t* parent, uint32_t x, ui
     }
     return proved;
 }
+// az_prove in the game's arena, with the nodes it proved added to the game's counter; called as az_prove is
+__device__ __forceinline__ void prove_counted(const AzTree& t, size_t arena, AzHeader* hdr, uint32_t x, uint32_t s, int stones, int lane) {
+    const uint32_t proved = az_prove(t.kids + arena, t.parent + arena, x, s, stones, lane);
+    if (lane == 0) hdr->proof_proved += proved;
+}
 
 // The children of a node for a descent: the first child marked LOSES in child order (lose_i, 0xFFFFFFFF: none), and whether children marked
 // WINS are left out of the PUCB maximum (some child is not marked WINS).  pb: this lane's children's proofs, two bits per round of 64.
@@ -184,6 +191,53 @@ __device__ __forceinline__ void proof_choice(const uint2* kids, const uint2* sta
     else if (pv != 0u) { best_v = pv; best_i = pi; }
 }
 
+// ---- The root's children, for the kernels that move the root or report it ----
+// The child MCTS::stepForward() plays (MCTS.cpp:129-134): the most visited one, first maximum in child order, i.e. ascending cells; under kProof
+// proof_choice has the last word.  The index among the root's n children, 0xFFFFFFFF when no child has a visit; the same in every lane.
+template <bool kProof>
+__device__ __forceinline__ uint32_t most_visited_child(const uint2* kids, const uint2* stat, uint32_t first, uint32_t n, int lane) {
+    uint32_t best_v = 0, best_i = 0xFFFFFFFFu;
+    for (uint32_t i = lane; i < n; i += 64) {
+        const uint32_t v = stat[first + i].x;
+        if (v > best_v) { best_v = v; best_i = i; }
+    }
+    for (int s = 32; s > 0; s >>= 1) {
+        const uint32_t ov = __shfl_down(best_v, s), oi = __shfl_down(best_i, s);
+        if (ov > best_v || (ov == best_v && ov != 0u && oi < best_i)) { best_v = ov; best_i = oi; }
+    }
+    best_v = __shfl(best_v, 0);
+    best_i = __shfl(best_i, 0);
+    if constexpr (kProof) proof_choice(kids, stat, first, n, lane, best_v, best_i);
+    return best_i;
+}
+// The root's child of `cell` (children are in ascending cell order: at most one), 0xFFFFFFFF when there is none; the same in every lane.
+__device__ __forceinline__ uint32_t child_of_cell(const uint2* kids, uint32_t first, uint32_t n, uint32_t cell, int lane) {
+    uint32_t found = 0xFFFFFFFFu;
+    for (uint32_t i = lane; i < n; i += 64)
+        if (((kids[first + i].y >> 8) & 0xFFu) == cell) found = i;
+    for (int s = 32; s > 0; s >>= 1) found = min(found, static_cast<uint32_t>(__shfl_xor(found, s)));
+    return found;
+}
+// The root children's visit counts by cell into rv[225], saturated to 65 535.  Called by all 64 lanes under uniform control flow: a barrier
+// stands between the zeros and the counts.
+__device__ __forceinline__ void visits_by_cell(uint16_t* rv, const uint2* kids, const uint2* stat, uint32_t first, uint32_t n, int lane) {
+    for (int i = lane; i < kCells; i += 64) rv[i] = 0;
+    __syncthreads();
+    for (uint32_t i = lane; i < n; i += 64) rv[(kids[first + i].y >> 8) & 0xFFu] = static_cast<uint16_t>(min(stat[first + i].x, 65535u));
+}
+// A new root at `base` of the arrays of an AzTree or an AzArena (one lane): no visit, no child, kids_y = the cell that led to it << 8, or 0
+template <class Arrays>
+__device__ __forceinline__ void new_root(const Arrays& a, size_t base, uint32_t kids_y) {
+    a.stat[base] = make_uint2(0u, 0u);
+    a.kids[base] = make_uint2(0u, kids_y);
+    a.prior[base] = 1.0f;
+    a.parent[base] = kNoNode;
+}
+
+// Default::Expand's candidates at a leaf (leaf_candidates below).  Lane l holds the cells l + 64 j: the probability, whether the cell becomes a
+// child, and its place among the children.  The same in every lane: total, the number of children, and win, the solver answered the leaf WIN.
+struct Candidates { float pv[4]; bool take[4]; int rank[4], total; bool win; };
+
 // K7 + K15 in the expand kernels, called by all 64 lanes for a pending leaf that is not answered WIN, after the leaf's children were written
 // (created: they exist; a leaf whose playout was dropped for a full arena does not get here): the row's threat is WIN -> the game's counters, every child whose
 // cell is GMK_VCF_CELL_LOSES gets GMK_AZ_PROOF_WINS with its own word -- the lane that made the child rewrites it --, and when the leaf has a
@@ -194,7 +248,7 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
     return v;
 }
 __device__ bool az_defend_marks(const AzTree& t, size_t arena, AzHeader* hdr, const AzDefend& df, size_t row, uint32_t leaf, int leaf_stones,
-                                uint32_t first_child, const bool (&take)[4], const int (&rank)[4], int total, bool created, int lane) {
+                                uint32_t first_child, const Candidates& c, bool created, int lane) {
     const int4 th = df.threat[row];
     if (th.x != GMK_VCF_WIN || th.w == 0) return false;          // the same in every lane
     const uint32_t* words = df.cells + row * kCells;
@@ -206,9 +260,9 @@ __device__ bool az_defend_marks(const AzTree& t, size_t arena, AzHeader* hdr, co
         const uint32_t w = i < kCells ? words[i] : 0u;
         searched += (w & kCellSearched) ? 1u : 0u;
         nodes += w >> kCellNodesShift;
-        if (created && take[j]) {
+        if (created && c.take[j]) {
             if ((w & kCellVerdict) == GMK_VCF_CELL_LOSES) {
-                t.kids[arena + first_child + rank[j]] = make_uint2(0u, (static_cast<uint32_t>(i) << 8) | (static_cast<uint32_t>(GMK_AZ_PROOF_WINS) << kProofShift));
+                t.kids[arena + first_child + c.rank[j]] = make_uint2(0u, (static_cast<uint32_t>(i) << 8) | (static_cast<uint32_t>(GMK_AZ_PROOF_WINS) << kProofShift));
                 ++marked;
             } else all = false;
         }
@@ -226,203 +280,9 @@ __device__ bool az_defend_marks(const AzTree& t, size_t arena, AzHeader* hdr, co
     if (!created) return false;
     __threadfence_block();
     __syncthreads();                                             // the children's words, before prove's ballot reads them one level up
-    if (total != kCells - leaf_stones || __ballot(!all) != 0ull) return false;
-    const uint32_t proved = az_prove(t.kids + arena, t.parent + arena, leaf, GMK_AZ_PROOF_LOSES, leaf_stones, lane);
-    if (lane == 0) hdr->proof_proved += proved;
+    if (c.total != kCells - leaf_stones || __ballot(!all) != 0ull) return false;
+    prove_counted(t, arena, hdr, leaf, GMK_AZ_PROOF_LOSES, leaf_stones, lane);
     return true;
-}
-
-// kProof (here and in az_select_leaves_kernel): a descent stops at a proven node below the root and backs the exact value up, children marked
-// LOSES are taken and children marked WINS avoided, and a five at the leaf starts a proof.  <false> is the search without the proof bits.
-template <bool kProof>
-__global__ __launch_bounds__(64)
-void az_select_kernel(AzTree t, float* __restrict__ out_states) {
-    __shared__ uint32_t s_rows[16];
-    const int game = blockIdx.x, lane = threadIdx.x;
-    if (game >= t.n_games) return;
-    AzHeader* hdr = t.hdr + game;
-    if (hdr->status & kStatusOver) return;                       // the game is over (az_advance_kernel): nothing to search, leaf_pending stays 0
-    const size_t row = static_cast<size_t>(t.row_of[game]);
-    const size_t arena = static_cast<size_t>(game) * t.cap;
-    uint2* stat = t.stat + arena;
-    const uint2* kids = t.kids + arena;
-    const float* prior = t.prior + arena;
-    if (lane < 16) s_rows[lane] = hdr->rows[lane];
-    __syncthreads();
-    uint32_t node = 0;
-    int stones = static_cast<int>(hdr->stones);
-    uint32_t last = hdr->last_move, last2 = hdr->last_move2;
-
-    // ---- Default::Select (MonteCarlo.hpp:57-68) down to a leaf ----
-    uint32_t stopped = GMK_AZ_PROOF_NONE;                        // kProof: the proof of the node the descent ended at
-    for (;;) {
-        const uint2 k = kids[node];
-        if constexpr (kProof) {
-            if (node != 0u && (k.y & kProofBits)) { stopped = proof_of(k.y); break; }
-        }
-        const uint32_t first = k.x, n = k.y & 0xFFu;
-        if (n == 0) break;
-        uint32_t pb = 0u, lose_i = 0xFFFFFFFFu;
-        bool filter = false;
-        if constexpr (kProof) proof_children(kids, first, n, lane, pb, lose_i, filter);
-        const double sqrt_n = sqrt(static_cast<double>(stat[node].x));
-        double best_score = -1.0;
-        uint32_t best_i = 0xFFFFFFFFu;
-        int j = 0;
-        for (uint32_t i = lane; i < n; i += 64, ++j) {
-            if constexpr (kProof) { if (filter && ((pb >> (2 * j)) & 3u) == GMK_AZ_PROOF_WINS) continue; }
-            const uint2 cs = stat[first + i];
-            const double p_i = prior[first + i], n_i = static_cast<double>(cs.x + 1u);
-            const double score = static_cast<double>(__uint_as_float(cs.y)) + t.c_puct * p_i * sqrt_n / n_i;       // Q + PUCB (:23-28)
-            if (score > best_score) { best_score = score; best_i = i; }
-        }
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) {                                             // first maximum, strict '>'
-            const double os = __shfl_down(best_score, s);
-            const uint32_t oi = __shfl_down(best_i, s);
-            if (os > best_score || (os == best_score && oi < best_i)) { best_score = os; best_i = oi; }
-        }
-        best_i = __shfl(best_i, 0);
-        if (best_i == 0xFFFFFFFFu) best_i = 0;                                          // nothing beat the initial -1.0: the first child
-        if constexpr (kProof) { if (lose_i != 0xFFFFFFFFu) best_i = lose_i; }
-        node = first + best_i;
-        const uint32_t cell = (kids[node].y >> 8) & 0xFFu;
-        if (lane == 0) s_rows[cell / 15] |= 1u << (cell % 15 + ((stones & 1) ? 16 : 0));                            // Policy::applyMove: black moves on even counts
-        __syncthreads();
-        ++stones;
-        last2 = last;
-        last = cell;
-    }
-
-    if constexpr (kProof) {
-        if (stopped != GMK_AZ_PROOF_NONE) {                      // the value is known: no network row
-            if (lane == 0) {
-                backup(stat, t.parent + arena, node, stopped == GMK_AZ_PROOF_LOSES ? 1.0f : -1.0f);
-                hdr->leaf_pending = 0;
-                hdr->proof_stops += 1u;
-            }
-            if (out_states)
-                for (int i = lane; i < 6 * kCells; i += 64) out_states[row * 6 * kCells + i] = 0.0f;
-            return;
-        }
-    }
-    // ---- Board::checkGameEnd (Game.cpp:88-136): five through the last stone, or a full board ----
-    bool ended = false;
-    int winner = 0;
-    if (stones > 0 && last < 225u) {
-        const int mover_white = (stones - 1) & 1;
-        if (five_through<1>(s_rows, last % 15, last / 15, mover_white ? 16 : 0)) { ended = true; winner = mover_white ? -1 : 1; }
-    }
-    if (!ended && stones == kCells) ended = true;
-    if (ended) {
-        // CalcScore(node.player, winner) (Game.h:34-36): the node's player is the one who made the last move
-        const int node_player = (stones & 1) ? 1 : -1;
-        if (lane == 0) {
-            backup(stat, t.parent + arena, node, static_cast<float>(node_player * winner));
-            hdr->leaf_pending = 0;
-        }
-        if constexpr (kProof) {
-            if (winner != 0) {                                   // a five: the side to move at the node has lost
-                const uint32_t proved = az_prove(t.kids + arena, t.parent + arena, node, GMK_AZ_PROOF_LOSES, stones, lane);
-                if (lane == 0) hdr->proof_proved += proved;
-            }
-        }
-        if (out_states)
-            for (int i = lane; i < 6 * kCells; i += 64) out_states[row * 6 * kCells + i] = 0.0f;
-        return;
-    }
-    if (lane == 0) { hdr->leaf = node; hdr->leaf_pending = 1; hdr->leaf_stones = static_cast<uint32_t>(stones); }
-    if (lane < 16) hdr->leaf_rows[lane] = s_rows[lane];
-    // ---- Board.encoded_states (game_ext.hpp:87-104): own stones, opponent's, empties, last move, the one before, colour to move ----
-    const int cur_white = stones & 1;
-    float* out = out_states + row * 6 * kCells;
-    for (int i = lane; i < kCells; i += 64) {
-        const uint32_t row = s_rows[i / 15] >> (i % 15);
-        const bool black = row & 1u, white = (row >> 16) & 1u;
-        out[0 * kCells + i] = (cur_white ? white : black) ? 1.0f : 0.0f;
-        out[1 * kCells + i] = (cur_white ? black : white) ? 1.0f : 0.0f;
-        out[2 * kCells + i] = (!black && !white) ? 1.0f : 0.0f;
-        out[3 * kCells + i] = static_cast<uint32_t>(i) == last ? 1.0f : 0.0f;
-        out[4 * kCells + i] = static_cast<uint32_t>(i) == last2 ? 1.0f : 0.0f;
-        out[5 * kCells + i] = cur_white ? 0.0f : 1.0f;
-    }
-}
-
-// kVcf: the leaf's verdict comes first (GMK_OPT_AZ_VCF_DEPTH > 0) -- on WIN the answer is (1.0f, one-hot(move)) instead of the network's row
-// kProof (with kVcf): a leaf answered WIN whose child was created is proven WINS
-// kDefend (with both): the children that lose to the opponent's forced win are marked, and a leaf without a holding reply is proven LOSES
-template <bool kVcf, bool kProof, bool kDefend>
-__global__ __launch_bounds__(64)
-void az_expand_kernel(AzTree t, const float* __restrict__ values, const float* __restrict__ probs, int stages /* bit 0: expand, bit 1: back up */, AzVcf vc,
-                      AzDefend df) {
-    const int game = blockIdx.x, lane = threadIdx.x;
-    if (game >= t.n_games) return;
-    AzHeader* hdr = t.hdr + game;
-    if (!hdr->leaf_pending) return;
-    const size_t row = static_cast<size_t>(t.row_of[game]);
-    const size_t arena = static_cast<size_t>(game) * t.cap;
-    const uint32_t leaf = hdr->leaf;
-    uint32_t n_nodes = hdr->n_nodes;
-    bool win = false;
-    int win_cell = -1;
-    if constexpr (kVcf) {
-        const int4 v = vc.verdict[row];
-        win = v.x == GMK_VCF_WIN;
-        win_cell = v.y;
-        if (lane == 0) count_verdict(hdr, v);
-    }
-    // ---- Default::Expand with extraCheck (MonteCarlo.hpp:71-80): probability not 0 and the cell is free; ascending cell id ----
-    const float* p = probs + row * kCells;
-    float pv[4];
-    bool take[4];
-    int rank[4], total = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int i = lane + 64 * j;
-        pv[j] = i < kCells ? p[i] : 0.0f;
-        if constexpr (kVcf) { if (win) pv[j] = i == win_cell ? 1.0f : 0.0f; }
-        const uint32_t row = i < kCells ? hdr->leaf_rows[i / 15] >> (i % 15) : 0x10001u;
-        take[j] = i < kCells && pv[j] != 0.0f && !(row & 0x10001u);
-        const unsigned long long b = __ballot(take[j]);
-        rank[j] = total + static_cast<int>(__builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(b >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(b), 0u)));
-        total += __popcll(b);
-    }
-    if (total > 0 && (stages & 1)) {
-        if (n_nodes + total > static_cast<uint32_t>(t.cap)) {
-            if (lane == 0) { hdr->status |= 2u; hdr->leaf_pending = 0; }               // arena full: this playout is dropped
-            return;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (take[j]) {
-                const uint32_t child = n_nodes + rank[j];
-                t.stat[arena + child] = make_uint2(0u, 0u);
-                t.kids[arena + child] = make_uint2(0u, static_cast<uint32_t>(lane + 64 * j) << 8);
-                t.prior[arena + child] = pv[j];
-                t.parent[arena + child] = leaf;
-            }
-        if (lane == 0) {
-            const uint32_t cell_bits = t.kids[arena + leaf].y & 0xFF00u;
-            t.kids[arena + leaf] = make_uint2(n_nodes, static_cast<uint32_t>(total) | cell_bits);
-            hdr->n_nodes = n_nodes + total;
-        }
-    }
-    __threadfence_block();
-    if constexpr (kProof) {
-        __syncthreads();                                         // the leaf's new kids word, before the 64 lanes read it
-        if (win && total > 0 && (stages & 1)) {
-            const uint32_t proved = az_prove(t.kids + arena, t.parent + arena, leaf, GMK_AZ_PROOF_WINS, static_cast<int>(hdr->leaf_stones), lane);
-            if (lane == 0) hdr->proof_proved += proved;
-        }
-    }
-    bool lost = false;
-    if constexpr (kDefend) {
-        if (!win) lost = az_defend_marks(t, arena, hdr, df, row, leaf, static_cast<int>(hdr->leaf_stones), n_nodes, take, rank, total, total > 0 && (stages & 1), lane);
-    }
-    if (lane == 0) {
-        if (stages & 2) backup(t.stat + arena, t.parent + arena, leaf, lost ? 1.0f : win ? -1.0f : -values[row]);      // node_value = -state_value (MCTS.cpp:166-168)
-        hdr->leaf_pending = 0;
-    }
 }
 
 // ---- Several leaves per game per step, with virtual loss (GMK_OPT_AZ_LEAVES = L > 1) ----
@@ -430,7 +290,7 @@ void az_expand_kernel(AzTree t, const float* __restrict__ values, const float* _
 // takes about P / L steps.  The descents of one step are steered apart by a per-node in-flight count v (a side array, all zero between
 // steps): a child with real statistics (N, Q) and v descents in flight below it is scored as if each of them had already come back lost,
 //     q_eff = v == 0 ? Q : (Q N - v) / (N + v)      n_i = N + v + 1      sqrt_n = sqrt(N_parent + v_parent)      (all in double)
-// in the expression of az_select_kernel; with every v zero it is that kernel's formula.  Every game owes `quota` playouts
+// which is descend<kProof, true> below; with every v zero it is the one-leaf formula.  Every game owes `quota` playouts
 // (gmk_az_add_playouts); a step makes min(L, quota) descents, one after the other:
 //     the game is over at the leaf   the real value is backed up at once, quota - 1, no row; the next descent sees the new statistics
 //     a childless leaf with v > 0    it waits for the network already (a collision): the step's descents end here, nothing is counted
@@ -451,6 +311,243 @@ struct AzLeaves {
     int leaves;                                  // L
 };
 
+// ---- What the one-leaf kernels and the L > 1 kernels share: a pending leaf, the descent, the game's end, the planes, the expansion ----
+// A pending leaf, wherever it is kept: the header's leaf words at L = 1, pend[k] otherwise.  waiting: it waits for an answer; rows: its sixteen words.
+struct PendingLeaf { bool waiting; uint32_t node, stones; const uint32_t* rows; };
+template <bool kMany>
+__device__ __forceinline__ PendingLeaf pending_leaf(const AzHeader* hdr, const AzPending* pend, int k) {
+    if constexpr (kMany) return {static_cast<uint32_t>(k) < hdr->n_pending, pend[k].node, pend[k].stones, pend[k].rows};
+    else return {hdr->leaf_pending != 0u, hdr->leaf, hdr->leaf_stones, hdr->leaf_rows};
+}
+__device__ __forceinline__ PendingLeaf pending_leaf(const AzTree& t, const AzLeaves& lv, int game, int k) {
+    const AzHeader* hdr = t.hdr + game;
+    return lv.leaves > 1 ? pending_leaf<true>(hdr, lv.pend + static_cast<size_t>(game) * GMK_AZ_MAX_LEAVES, k) : pending_leaf<false>(hdr, nullptr, 0);
+}
+
+// Default::Select (MonteCarlo.hpp:57-68) from the root down to a leaf.  Called by all 64 lanes of the game's wavefront under uniform control
+// flow: lane 0 puts every stone of the path into s_rows (which holds the root position) and a barrier stands behind each.
+// kProof: the descent stops at a proven node below the root (stopped: its proof), children marked LOSES are taken and children marked WINS
+// avoided.  kInflight: the in-flight counts steer it (the formula above); <.., false> neither loads nor adds them.
+struct Descent { uint32_t node; int stones; uint32_t last, last2, stopped; };     // where it ended, with the position's stone count and last two moves
+template <bool kProof, bool kInflight>
+__device__ __forceinline__ Descent descend(const uint2* stat, const uint2* kids, const float* prior, const uint16_t* inflight, uint32_t* s_rows, double c_puct,
+                                           int stones, uint32_t last, uint32_t last2, int lane) {
+    Descent d{0u, stones, last, last2, GMK_AZ_PROOF_NONE};
+    for (;;) {
+        const uint2 k = kids[d.node];
+        if constexpr (kProof) {
+            if (d.node != 0u && (k.y & kProofBits)) { d.stopped = proof_of(k.y); break; }
+        }
+        const uint32_t first = k.x, n = k.y & 0xFFu;
+        if (n == 0) break;
+        uint32_t pb = 0u, lose_i = 0xFFFFFFFFu;
+        bool filter = false;
+        if constexpr (kProof) proof_children(kids, first, n, lane, pb, lose_i, filter);
+        uint32_t n_node = stat[d.node].x;
+        if constexpr (kInflight) n_node += static_cast<uint32_t>(inflight[d.node]);
+        const double sqrt_n = sqrt(static_cast<double>(n_node));
+        double best_score = -1.0;
+        uint32_t best_i = 0xFFFFFFFFu;
+        int j = 0;
+        for (uint32_t i = lane; i < n; i += 64, ++j) {
+            if constexpr (kProof) { if (filter && ((pb >> (2 * j)) & 3u) == GMK_AZ_PROOF_WINS) continue; }
+            const uint2 cs = stat[first + i];
+            double q = static_cast<double>(__uint_as_float(cs.y));
+            uint32_t n_child = cs.x + 1u;
+            if constexpr (kInflight) {
+                const uint32_t v_i = inflight[first + i];
+                q = v_i == 0u ? q : (q * static_cast<double>(cs.x) - static_cast<double>(v_i)) / static_cast<double>(cs.x + v_i);
+                n_child = cs.x + v_i + 1u;
+            }
+            const double p_i = prior[first + i], n_i = static_cast<double>(n_child);
+            const double score = q + c_puct * p_i * sqrt_n / n_i;                      // Q + PUCB (:23-28)
+            if (score > best_score) { best_score = score; best_i = i; }
+        }
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) {                                             // first maximum, strict '>'
+            const double os = __shfl_down(best_score, s);
+            const uint32_t oi = __shfl_down(best_i, s);
+            if (os > best_score || (os == best_score && oi < best_i)) { best_score = os; best_i = oi; }
+        }
+        best_i = __shfl(best_i, 0);
+        if (best_i == 0xFFFFFFFFu) best_i = 0;                                          // nothing beat the initial -1.0: the first child
+        if constexpr (kProof) { if (lose_i != 0xFFFFFFFFu) best_i = lose_i; }
+        d.node = first + best_i;
+        const uint32_t cell = (kids[d.node].y >> 8) & 0xFFu;
+        if (lane == 0) s_rows[cell / 15] |= 1u << (cell % 15 + ((d.stones & 1) ? 16 : 0));                          // Policy::applyMove: black moves on even counts
+        __syncthreads();
+        ++d.stones;
+        d.last2 = d.last;
+        d.last = cell;
+    }
+    return d;
+}
+
+// Board::checkGameEnd (Game.cpp:88-136): five through the last stone (winner: +1 black, -1 white), or a full board
+__device__ __forceinline__ bool game_end(const uint32_t* s_rows, int stones, uint32_t last, int& winner) {
+    winner = 0;
+    if (stones > 0 && last < 225u) {
+        const int mover_white = (stones - 1) & 1;
+        if (five_through<1>(s_rows, last % 15, last / 15, mover_white ? 16 : 0)) { winner = mover_white ? -1 : 1; return true; }
+    }
+    return stones == kCells;
+}
+// Whether the descent's value is known without the network, all 64 lanes: it stopped at a proven node (the exact value is backed up), or the game
+// is over at the node: CalcScore(node.player, winner) (Game.h:34-36) is backed up -- the node's player is the one who made the last move --, and
+// under kProof a five proves that the side to move at the node has lost.  The proof stop comes before the game-end test.
+template <bool kProof>
+__device__ __forceinline__ bool settled_at_once(const AzTree& t, size_t arena, AzHeader* hdr, const uint32_t* s_rows, const Descent& d, int lane) {
+    if (kProof && d.stopped != GMK_AZ_PROOF_NONE) {
+        if (lane == 0) { backup(t.stat + arena, t.parent + arena, d.node, d.stopped == GMK_AZ_PROOF_LOSES ? 1.0f : -1.0f); hdr->proof_stops += 1u; }
+        return true;
+    }
+    int winner;
+    if (!game_end(s_rows, d.stones, d.last, winner)) return false;
+    const int node_player = (d.stones & 1) ? 1 : -1;
+    if (lane == 0) backup(t.stat + arena, t.parent + arena, d.node, static_cast<float>(node_player * winner));
+    if constexpr (kProof) { if (winner != 0) prove_counted(t, arena, hdr, d.node, GMK_AZ_PROOF_LOSES, d.stones, lane); }
+    return true;
+}
+
+// Board.encoded_states (game_ext.hpp:87-104), one row of the batch: own stones, opponent's, empties, last move, the one before, colour to move
+__device__ __forceinline__ void write_planes(float* out, const uint32_t* s_rows, int stones, uint32_t last, uint32_t last2, int lane) {
+    const int cur_white = stones & 1;
+    for (int i = lane; i < kCells; i += 64) {
+        const uint32_t row = s_rows[i / 15] >> (i % 15);
+        const bool black = row & 1u, white = (row >> 16) & 1u;
+        out[0 * kCells + i] = (cur_white ? white : black) ? 1.0f : 0.0f;
+        out[1 * kCells + i] = (cur_white ? black : white) ? 1.0f : 0.0f;
+        out[2 * kCells + i] = (!black && !white) ? 1.0f : 0.0f;
+        out[3 * kCells + i] = static_cast<uint32_t>(i) == last ? 1.0f : 0.0f;
+        out[4 * kCells + i] = static_cast<uint32_t>(i) == last2 ? 1.0f : 0.0f;
+        out[5 * kCells + i] = cur_white ? 0.0f : 1.0f;
+    }
+}
+// a row of the batch that no leaf fills
+__device__ __forceinline__ void zero_row(float* out, int lane) {
+    for (int i = lane; i < 6 * kCells; i += 64) out[i] = 0.0f;
+}
+
+// Default::Expand with extraCheck (MonteCarlo.hpp:71-80) for the leaf of batch row `row` at position `rows`: probability not 0 and the cell is
+// free; ascending cell id.  kVcf: the row's verdict comes first (lane 0 counts it) -- on WIN the answer is one-hot(move), not the network's row.
+template <bool kVcf>
+__device__ __forceinline__ Candidates leaf_candidates(const AzVcf& vc, AzHeader* hdr, const float* probs, size_t row, const uint32_t* rows, int lane) {
+    Candidates c;
+    c.win = false;
+    c.total = 0;
+    int win_cell = -1;
+    if constexpr (kVcf) {
+        const int4 v = vc.verdict[row];
+        c.win = v.x == GMK_VCF_WIN;
+        win_cell = v.y;
+        if (lane == 0) count_verdict(hdr, v);
+    }
+    const float* p = probs + row * kCells;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = lane + 64 * j;
+        c.pv[j] = i < kCells ? p[i] : 0.0f;
+        if constexpr (kVcf) { if (c.win) c.pv[j] = i == win_cell ? 1.0f : 0.0f; }
+        const uint32_t row = i < kCells ? rows[i / 15] >> (i % 15) : 0x10001u;
+        c.take[j] = i < kCells && c.pv[j] != 0.0f && !(row & 0x10001u);
+        const unsigned long long b = __ballot(c.take[j]);
+        c.rank[j] = c.total + static_cast<int>(__builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(b >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(b), 0u)));
+        c.total += __popcll(b);
+    }
+    return c;
+}
+// The candidates become the leaf's children at n_nodes .. n_nodes + total, and lane 0 writes the leaf's kids word: leaf_proofs' fence and barrier
+// stand before the 64 lanes read it.  The caller has checked that they fit.
+__device__ __forceinline__ void write_children(const AzTree& t, size_t arena, uint32_t leaf, uint32_t n_nodes, const Candidates& c, int lane) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (c.take[j]) {
+            const uint32_t child = n_nodes + c.rank[j];
+            t.stat[arena + child] = make_uint2(0u, 0u);
+            t.kids[arena + child] = make_uint2(0u, static_cast<uint32_t>(lane + 64 * j) << 8);
+            t.prior[arena + child] = c.pv[j];
+            t.parent[arena + child] = leaf;
+        }
+    if (lane == 0) {
+        const uint32_t cell_bits = t.kids[arena + leaf].y & 0xFF00u;
+        t.kids[arena + leaf] = make_uint2(n_nodes, static_cast<uint32_t>(c.total) | cell_bits);
+    }
+}
+// Between the children and the backup, called by all 64 lanes under uniform control flow: the fence behind the children's writes and, under kProof,
+// the barrier; kProof: a leaf answered WIN whose child exists is proven WINS; kDefend: the children that lose to the opponent's forced win are
+// marked (not for a leaf answered WIN or dropped for a full arena).  created: the children at first_child exist.  Returns whether the leaf was
+// proven LOSES: +1.0f is then the value to back up.
+template <bool kProof, bool kDefend>
+__device__ __forceinline__ bool leaf_proofs(const AzTree& t, size_t arena, AzHeader* hdr, const AzDefend& df, size_t row, const PendingLeaf& pl, uint32_t first_child,
+                                            const Candidates& c, bool created, bool dropped, int lane) {
+    __threadfence_block();
+    if constexpr (kProof) {
+        __syncthreads();                                         // the leaf's new kids word, before the 64 lanes read it
+        if (c.win && created) prove_counted(t, arena, hdr, pl.node, GMK_AZ_PROOF_WINS, static_cast<int>(pl.stones), lane);
+    }
+    if constexpr (kDefend) {
+        if (!c.win && !dropped) return az_defend_marks(t, arena, hdr, df, row, pl.node, static_cast<int>(pl.stones), first_child, c, created, lane);
+    }
+    return false;
+}
+
+// kProof: see descend; a five at the leaf starts a proof.  <false> is the search without the proof bits.
+template <bool kProof>
+__global__ __launch_bounds__(64)
+void az_select_kernel(AzTree t, float* __restrict__ out_states) {
+    __shared__ uint32_t s_rows[16];
+    const int game = blockIdx.x, lane = threadIdx.x;
+    if (game >= t.n_games) return;
+    AzHeader* hdr = t.hdr + game;
+    if (hdr->status & kStatusOver) return;                       // the game is over (az_advance_kernel): nothing to search, leaf_pending stays 0
+    const size_t row = static_cast<size_t>(t.row_of[game]);
+    const size_t arena = static_cast<size_t>(game) * t.cap;
+    if (lane < 16) s_rows[lane] = hdr->rows[lane];
+    __syncthreads();
+    const Descent d = descend<kProof, false>(t.stat + arena, t.kids + arena, t.prior + arena, nullptr, s_rows, t.c_puct, static_cast<int>(hdr->stones),
+                                             hdr->last_move, hdr->last_move2, lane);
+    if (settled_at_once<kProof>(t, arena, hdr, s_rows, d, lane)) {                     // no network row
+        if (lane == 0) hdr->leaf_pending = 0;
+        if (out_states) zero_row(out_states + row * 6 * kCells, lane);
+        return;
+    }
+    if (lane == 0) { hdr->leaf = d.node; hdr->leaf_pending = 1; hdr->leaf_stones = static_cast<uint32_t>(d.stones); }
+    if (lane < 16) hdr->leaf_rows[lane] = s_rows[lane];
+    write_planes(out_states + row * 6 * kCells, s_rows, d.stones, d.last, d.last2, lane);
+}
+
+// kVcf: the leaf's verdict comes first (GMK_OPT_AZ_VCF_DEPTH > 0) -- on WIN the answer is (1.0f, one-hot(move)) instead of the network's row
+// kProof (with kVcf): a leaf answered WIN whose child was created is proven WINS
+// kDefend (with both): the children that lose to the opponent's forced win are marked, and a leaf without a holding reply is proven LOSES
+template <bool kVcf, bool kProof, bool kDefend>
+__global__ __launch_bounds__(64)
+void az_expand_kernel(AzTree t, const float* __restrict__ values, const float* __restrict__ probs, int stages /* bit 0: expand, bit 1: back up */, AzVcf vc,
+                      AzDefend df) {
+    const int game = blockIdx.x, lane = threadIdx.x;
+    if (game >= t.n_games) return;
+    AzHeader* hdr = t.hdr + game;
+    const PendingLeaf pl = pending_leaf<false>(hdr, nullptr, 0);
+    if (!pl.waiting) return;
+    const size_t row = static_cast<size_t>(t.row_of[game]);
+    const size_t arena = static_cast<size_t>(game) * t.cap;
+    const uint32_t n_nodes = hdr->n_nodes;
+    const Candidates c = leaf_candidates<kVcf>(vc, hdr, probs, row, pl.rows, lane);
+    const bool created = c.total > 0 && (stages & 1);
+    if (created) {
+        if (n_nodes + c.total > static_cast<uint32_t>(t.cap)) {
+            if (lane == 0) { hdr->status |= 2u; hdr->leaf_pending = 0; }               // arena full: this playout is dropped
+            return;
+        }
+        write_children(t, arena, pl.node, n_nodes, c, lane);
+        if (lane == 0) hdr->n_nodes = n_nodes + c.total;
+    }
+    const bool lost = leaf_proofs<kProof, kDefend>(t, arena, hdr, df, row, pl, n_nodes, c, created, false, lane);
+    if (lane == 0) {
+        if (stages & 2) backup(t.stat + arena, t.parent + arena, pl.node, lost ? 1.0f : c.win ? -1.0f : -values[row]);  // node_value = -state_value (MCTS.cpp:166-168)
+        hdr->leaf_pending = 0;
+    }
+}
+
 template <bool kProof>
 __global__ __launch_bounds__(64)
 void az_select_leaves_kernel(AzTree t, AzLeaves lv, float* out_states) {
@@ -461,9 +558,6 @@ void az_select_leaves_kernel(AzTree t, AzLeaves lv, float* out_states) {
     if (hdr->status & kStatusOver) return;                       // the game is over: it owes nothing and has no rows
     const size_t row0 = static_cast<size_t>(t.row_of[game]) * lv.leaves;
     const size_t arena = static_cast<size_t>(game) * t.cap;
-    uint2* stat = t.stat + arena;
-    const uint2* kids = t.kids + arena;
-    const float* prior = t.prior + arena;
     const uint32_t* parent = t.parent + arena;
     uint16_t* inflight = lv.inflight + arena;
     AzPending* pend = lv.pend + static_cast<size_t>(game) * GMK_AZ_MAX_LEAVES;
@@ -472,98 +566,23 @@ void az_select_leaves_kernel(AzTree t, AzLeaves lv, float* out_states) {
     const int root_stones = static_cast<int>(hdr->stones);
     const uint32_t root_last = hdr->last_move, root_last2 = hdr->last_move2;
     int k = 0;                                                   // pending leaves so far
-    for (int d = 0; d < descents; ++d) {
+    for (int i = 0; i < descents; ++i) {
         if (lane < 16) s_rows[lane] = hdr->rows[lane];
         __syncthreads();
-        uint32_t node = 0;
-        int stones = root_stones;
-        uint32_t last = root_last, last2 = root_last2;
-        // ---- Default::Select with the in-flight descents counted as losses ----
-        uint32_t stopped = GMK_AZ_PROOF_NONE;                    // kProof: the proof of the node the descent ended at
-        for (;;) {
-            const uint2 kd = kids[node];
-            if constexpr (kProof) {
-                if (node != 0u && (kd.y & kProofBits)) { stopped = proof_of(kd.y); break; }
-            }
-            const uint32_t first = kd.x, n = kd.y & 0xFFu;
-            if (n == 0) break;
-            uint32_t pb = 0u, lose_i = 0xFFFFFFFFu;
-            bool filter = false;
-            if constexpr (kProof) proof_children(kids, first, n, lane, pb, lose_i, filter);
-            const double sqrt_n = sqrt(static_cast<double>(stat[node].x + static_cast<uint32_t>(inflight[node])));
-            double best_score = -1.0;
-            uint32_t best_i = 0xFFFFFFFFu;
-            int j = 0;
-            for (uint32_t i = lane; i < n; i += 64, ++j) {
-                if constexpr (kProof) { if (filter && ((pb >> (2 * j)) & 3u) == GMK_AZ_PROOF_WINS) continue; }
-                const uint2 cs = stat[first + i];
-                const uint32_t v_i = inflight[first + i];
-                const double q = static_cast<double>(__uint_as_float(cs.y));
-                const double q_eff = v_i == 0u ? q : (q * static_cast<double>(cs.x) - static_cast<double>(v_i)) / static_cast<double>(cs.x + v_i);
-                const double p_i = prior[first + i], n_i = static_cast<double>(cs.x + v_i + 1u);
-                const double score = q_eff + t.c_puct * p_i * sqrt_n / n_i;
-                if (score > best_score) { best_score = score; best_i = i; }
-            }
-#pragma unroll
-            for (int s = 32; s > 0; s >>= 1) {                                         // first maximum, strict '>'
-                const double os = __shfl_down(best_score, s);
-                const uint32_t oi = __shfl_down(best_i, s);
-                if (os > best_score || (os == best_score && oi < best_i)) { best_score = os; best_i = oi; }
-            }
-            best_i = __shfl(best_i, 0);
-            if (best_i == 0xFFFFFFFFu) best_i = 0;
-            if constexpr (kProof) { if (lose_i != 0xFFFFFFFFu) best_i = lose_i; }
-            node = first + best_i;
-            const uint32_t cell = (kids[node].y >> 8) & 0xFFu;
-            if (lane == 0) s_rows[cell / 15] |= 1u << (cell % 15 + ((stones & 1) ? 16 : 0));
-            __syncthreads();
-            ++stones;
-            last2 = last;
-            last = cell;
-        }
-        // ---- Board::checkGameEnd, as az_select_kernel ----
-        bool ended = false;
-        int winner = 0;
-        if (stopped == GMK_AZ_PROOF_NONE && stones > 0 && last < 225u) {
-            const int mover_white = (stones - 1) & 1;
-            if (five_through<1>(s_rows, last % 15, last / 15, mover_white ? 16 : 0)) { ended = true; winner = mover_white ? -1 : 1; }
-        }
-        if (!ended && stones == kCells) ended = true;
+        const Descent d = descend<kProof, true>(t.stat + arena, t.kids + arena, t.prior + arena, inflight, s_rows, t.c_puct, root_stones, root_last, root_last2, lane);
         bool collided = false;
-        if (kProof && stopped != GMK_AZ_PROOF_NONE) {            // the value is known: as a game that is over at the leaf
-            if (lane == 0) { backup(stat, parent, node, stopped == GMK_AZ_PROOF_LOSES ? 1.0f : -1.0f); hdr->proof_stops += 1u; }
+        if (settled_at_once<kProof>(t, arena, hdr, s_rows, d, lane)) {
             --quota;
-        } else if (ended) {
-            const int node_player = (stones & 1) ? 1 : -1;
-            if (lane == 0) backup(stat, parent, node, static_cast<float>(node_player * winner));
-            if constexpr (kProof) {
-                if (winner != 0) {                               // a five: the side to move at the node has lost
-                    const uint32_t proved = az_prove(t.kids + arena, parent, node, GMK_AZ_PROOF_LOSES, stones, lane);
-                    if (lane == 0) hdr->proof_proved += proved;
-                }
-            }
-            --quota;
-        } else if (inflight[node] != 0) {
+        } else if (inflight[d.node] != 0) {
             collided = true;
         } else {
             if (lane == 0) {
-                for (uint32_t up = node; up != kNoNode; up = parent[up]) inflight[up] = static_cast<uint16_t>(inflight[up] + 1u);
-                pend[k].node = node;
-                pend[k].stones = static_cast<uint32_t>(stones);
+                for (uint32_t up = d.node; up != kNoNode; up = parent[up]) inflight[up] = static_cast<uint16_t>(inflight[up] + 1u);
+                pend[k].node = d.node;
+                pend[k].stones = static_cast<uint32_t>(d.stones);
             }
             if (lane < 16) pend[k].rows[lane] = s_rows[lane];
-            const int cur_white = stones & 1;
-            float* out = out_states + (row0 + static_cast<size_t>(k)) * 6 * kCells;
-            for (int i = lane; i < kCells; i += 64) {
-                const uint32_t row = s_rows[i / 15] >> (i % 15);
-                const bool black = row & 1u, white = (row >> 16) & 1u;
-                out[0 * kCells + i] = (cur_white ? white : black) ? 1.0f : 0.0f;
-                out[1 * kCells + i] = (cur_white ? black : white) ? 1.0f : 0.0f;
-                out[2 * kCells + i] = (!black && !white) ? 1.0f : 0.0f;
-                out[3 * kCells + i] = static_cast<uint32_t>(i) == last ? 1.0f : 0.0f;
-                out[4 * kCells + i] = static_cast<uint32_t>(i) == last2 ? 1.0f : 0.0f;
-                out[5 * kCells + i] = cur_white ? 0.0f : 1.0f;
-            }
+            write_planes(out_states + (row0 + static_cast<size_t>(k)) * 6 * kCells, s_rows, d.stones, d.last, d.last2, lane);
             ++k;
             --quota;
         }
@@ -571,10 +590,7 @@ void az_select_leaves_kernel(AzTree t, AzLeaves lv, float* out_states) {
         __syncthreads();                                         // (and every lane is done with s_rows)
         if (collided) break;
     }
-    for (int r = k; r < lv.leaves; ++r) {
-        float* out = out_states + (row0 + static_cast<size_t>(r)) * 6 * kCells;
-        for (int i = lane; i < 6 * kCells; i += 64) out[i] = 0.0f;
-    }
+    for (int r = k; r < lv.leaves; ++r) zero_row(out_states + (row0 + static_cast<size_t>(r)) * 6 * kCells, lane);
     if (lane == 0) { hdr->quota = quota; hdr->n_pending = static_cast<uint32_t>(k); hdr->leaf_pending = 0; }
 }
 
@@ -593,68 +609,21 @@ void az_expand_leaves_kernel(AzTree t, AzLeaves lv, const float* values, const f
     uint32_t n_nodes = hdr->n_nodes;
     bool full = false;
     for (int k = 0; k < n_pending; ++k) {
-        const uint32_t leaf = pend[k].node;
-        bool win = false;
-        int win_cell = -1;
-        if constexpr (kVcf) {
-            const int4 v = vc.verdict[row0 + static_cast<size_t>(k)];
-            win = v.x == GMK_VCF_WIN;
-            win_cell = v.y;
-            if (lane == 0) count_verdict(hdr, v);
-        }
-        // ---- Default::Expand with extraCheck, as az_expand_kernel: probability not 0 and the cell is free; ascending cell id ----
-        const float* p = probs + (row0 + static_cast<size_t>(k)) * kCells;
-        float pv[4];
-        bool take[4];
-        int rank[4], total = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = lane + 64 * j;
-            pv[j] = i < kCells ? p[i] : 0.0f;
-            if constexpr (kVcf) { if (win) pv[j] = i == win_cell ? 1.0f : 0.0f; }
-            const uint32_t row = i < kCells ? pend[k].rows[i / 15] >> (i % 15) : 0x10001u;
-            take[j] = i < kCells && pv[j] != 0.0f && !(row & 0x10001u);
-            const unsigned long long b = __ballot(take[j]);
-            rank[j] = total + static_cast<int>(__builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(b >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(b), 0u)));
-            total += __popcll(b);
-        }
-        bool dropped = false;
+        const PendingLeaf pl = pending_leaf<true>(hdr, pend, k);
+        const size_t row = row0 + static_cast<size_t>(k);
+        const Candidates c = leaf_candidates<kVcf>(vc, hdr, probs, row, pl.rows, lane);
         const uint32_t first_child = n_nodes;
-        if (total > 0) {
-            if (n_nodes + total > static_cast<uint32_t>(t.cap)) {
-                dropped = full = true;                           // arena full: this playout is dropped, its marks are taken back below
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (take[j]) {
-                        const uint32_t child = n_nodes + rank[j];
-                        t.stat[arena + child] = make_uint2(0u, 0u);
-                        t.kids[arena + child] = make_uint2(0u, static_cast<uint32_t>(lane + 64 * j) << 8);
-                        t.prior[arena + child] = pv[j];
-                        t.parent[arena + child] = leaf;
-                    }
-                if (lane == 0) {
-                    const uint32_t cell_bits = t.kids[arena + leaf].y & 0xFF00u;
-                    t.kids[arena + leaf] = make_uint2(n_nodes, static_cast<uint32_t>(total) | cell_bits);
-                }
-                n_nodes += total;
-            }
+        const bool dropped = c.total > 0 && n_nodes + c.total > static_cast<uint32_t>(t.cap);
+        if (dropped) {
+            full = true;                                         // arena full: this playout is dropped, its marks are taken back below
+        } else if (c.total > 0) {
+            write_children(t, arena, pl.node, n_nodes, c, lane);
+            n_nodes += c.total;
         }
-        __threadfence_block();
-        if constexpr (kProof) {
-            __syncthreads();                                     // the leaf's new kids word, before the 64 lanes read it
-            if (win && total > 0 && !dropped) {
-                const uint32_t proved = az_prove(t.kids + arena, t.parent + arena, leaf, GMK_AZ_PROOF_WINS, static_cast<int>(pend[k].stones), lane);
-                if (lane == 0) hdr->proof_proved += proved;
-            }
-        }
-        bool lost = false;
-        if constexpr (kDefend) {
-            if (!win && !dropped) lost = az_defend_marks(t, arena, hdr, df, row0 + static_cast<size_t>(k), leaf, static_cast<int>(pend[k].stones), first_child, take, rank, total, total > 0, lane);
-        }
+        const bool lost = leaf_proofs<kProof, kDefend>(t, arena, hdr, df, row, pl, first_child, c, c.total > 0 && !dropped, dropped, lane);
         if (lane == 0) {
-            if (!dropped) backup(t.stat + arena, t.parent + arena, leaf, lost ? 1.0f : win ? -1.0f : -values[row0 + k]);
-            for (uint32_t up = leaf; up != kNoNode; up = t.parent[arena + up]) inflight[up] = static_cast<uint16_t>(inflight[up] - 1u);
+            if (!dropped) backup(t.stat + arena, t.parent + arena, pl.node, lost ? 1.0f : c.win ? -1.0f : -values[row]);
+            for (uint32_t up = pl.node; up != kNoNode; up = t.parent[arena + up]) inflight[up] = static_cast<uint16_t>(inflight[up] - 1u);
         }
     }
     if (lane == 0) {
@@ -663,6 +632,7 @@ void az_expand_leaves_kernel(AzTree t, AzLeaves lv, const float* values, const f
         hdr->n_pending = 0;
     }
 }
+
 
 // ---- K7 + K14: forced wins by fours at the pending leaves (GMK_OPT_AZ_VCF_DEPTH = D > 0) ----
 // The three kernels below run K14's walk (the contract in include/gomoku_hip.h "K14"), which is vcf_device.h's: pass, start and step, one board
@@ -681,23 +651,14 @@ __device__ __forceinline__ bool leaf_of(const AzTree& t, const AzLeaves& lv, lon
     out_row = static_cast<size_t>(t.row_of[game]) * lv.leaves + static_cast<size_t>(k);
     return true;
 }
-// Leaf k of `game` waits for an answer (L = 1: the game's one leaf does).
-__device__ __forceinline__ bool leaf_pending(const AzTree& t, const AzLeaves& lv, int game, int k) {
-    const AzHeader* hdr = t.hdr + game;
-    return lv.leaves > 1 ? static_cast<uint32_t>(k) < hdr->n_pending : hdr->leaf_pending != 0u;
-}
-// This lane's word and the stone count of leaf k of `game`: the leaf's row y of black and of white; white is to move on odd stone counts.
+// This lane's word of a pending leaf: the leaf's row y of black and of white; white is to move on odd stone counts.
 struct LeafRow {
     uint32_t black, white;
     bool white_to_move;
 };
-__device__ __forceinline__ LeafRow leaf_row(const AzTree& t, const AzLeaves& lv, int game, int k, int y) {
-    const AzHeader* hdr = t.hdr + game;
-    const bool many = lv.leaves > 1;
-    const AzPending* pd = lv.pend + static_cast<size_t>(game) * GMK_AZ_MAX_LEAVES + (many ? k : 0);
-    const uint32_t word = many ? pd->rows[y] : hdr->leaf_rows[y];
-    const uint32_t stones = many ? pd->stones : hdr->leaf_stones;
-    return {word & gmk::vcf::kRowMask, (word >> 16) & gmk::vcf::kRowMask, (stones & 1u) != 0};
+__device__ __forceinline__ LeafRow leaf_row(const PendingLeaf& pl, int y) {
+    const uint32_t word = pl.rows[y];
+    return {word & gmk::vcf::kRowMask, (word >> 16) & gmk::vcf::kRowMask, (pl.stones & 1u) != 0};
 }
 
 // The side to move attacks.  Four leaves per wavefront, one wavefront per workgroup: group i of the launch takes row i (leaf_of); a leaf that
@@ -714,8 +675,9 @@ void az_vcf_leaves_kernel(AzTree t, AzLeaves lv, AzVcf vc) {
 
     // ---- the loader ----
     if (leaf_of(t, lv, static_cast<long long>(blockIdx.x) * 4 + ln.group, game, k, out_row)) {
-        if (leaf_pending(t, lv, game, k)) {
-            const LeafRow r = leaf_row(t, lv, game, k, ln.y);
+        const PendingLeaf pl = pending_leaf(t, lv, game, k);
+        if (pl.waiting) {
+            const LeafRow r = leaf_row(pl, ln.y);
             w.reset(r.white_to_move ? r.white : r.black, r.white_to_move ? r.black : r.white, vc.max_depth);
         } else if (ln.y == 0) {
             vc.verdict[out_row] = make_int4(GMK_VCF_NONE, -1, 0, 0);
@@ -764,13 +726,14 @@ void az_threat_leaves_kernel(AzTree t, AzLeaves lv, AzVcf vc, AzDefend df) {
 
     // ---- the loader ----
     if (leaf_of(t, lv, static_cast<long long>(blockIdx.x) * 4 + ln.group, game, k, out_row)) {
-        bool pending = leaf_pending(t, lv, game, k);
+        const PendingLeaf pl = pending_leaf(t, lv, game, k);
+        bool pending = pl.waiting;
         if (pending) {
             const int own = vc.verdict[out_row].x;
             pending = own != GMK_VCF_WIN && own != GMK_VCF_OVER;
         }
         if (pending) {
-            const LeafRow r = leaf_row(t, lv, game, k, y);
+            const LeafRow r = leaf_row(pl, y);
             w.reset(r.white_to_move ? r.black : r.white, r.white_to_move ? r.white : r.black, vc.max_depth);      // the side that moved last threatens
             df.occupied[out_row * 16 + y] = static_cast<uint16_t>(r.black | r.white);
         } else if (y == 0) {
@@ -829,7 +792,7 @@ void az_defend_leaves_kernel(AzTree t, AzLeaves lv, AzVcf vc, AzDefend df) {
     if (!leaf_of(t, lv, static_cast<long long>(blockIdx.x) / kDefendWaves, game, k, out_row)) return;
     const int4 th = df.threat[out_row];
     if (th.x != GMK_VCF_WIN || th.w == 0) return;                // only a leaf that was pending and asked has a WIN here
-    const LeafRow r = leaf_row(t, lv, game, k, y);
+    const LeafRow r = leaf_row(pending_leaf(t, lv, game, k), y);
     const uint32_t base_att = r.white_to_move ? r.black : r.white, base_def = r.white_to_move ? r.white : r.black;
     const int tlen = th.y;
     const uint32_t pvw = reinterpret_cast<const uint32_t*>(df.pv + out_row * GMK_VCF_PV)[y];     // this lane's four pv cells
@@ -966,20 +929,14 @@ void az_step_kernel(AzTree t, AzArena b, const int16_t* forced) {
     const uint2 rk = t.kids[base];
     const uint32_t first = rk.x, n = rk.y & 0xFFu;
     const int want = forced ? forced[game] : -1;
-    uint32_t best_v = 0, best_i = 0xFFFFFFFFu;                   // visits + 1 (or "is the wanted cell"), first maximum in child order
-    for (uint32_t i = lane; i < n; i += 64) {
-        const uint32_t cell = (t.kids[base + first + i].y >> 8) & 0xFFu;
-        const uint32_t v = want >= 0 ? (cell == static_cast<uint32_t>(want) ? 1u : 0u) : t.stat[base + first + i].x + 1u;
-        if (v > best_v) { best_v = v; best_i = i; }
+    uint32_t best_i;
+    if (want >= 0) {
+        best_i = child_of_cell(t.kids + base, first, n, static_cast<uint32_t>(want), lane);
+    } else {
+        best_i = most_visited_child<kProof>(t.kids + base, t.stat + base, first, n, lane);
+        if (best_i == 0xFFFFFFFFu && n != 0u) best_i = 0u;       // no child has a visit: max_element's first, the first child
     }
-    for (int s = 32; s > 0; s >>= 1) {
-        const uint32_t ov = __shfl_down(best_v, s), oi = __shfl_down(best_i, s);
-        if (ov > best_v || (ov == best_v && ov != 0u && oi < best_i)) { best_v = ov; best_i = oi; }
-    }
-    best_v = __shfl(best_v, 0);
-    best_i = __shfl(best_i, 0);
-    if constexpr (kProof) { if (want < 0) proof_choice(t.kids + base, t.stat + base, first, n, lane, best_v, best_i); }
-    const bool found = best_v != 0u;
+    const bool found = best_i != 0xFFFFFFFFu;
     const uint32_t stones = hdr.stones;
     const uint32_t cell = found ? (t.kids[base + first + best_i].y >> 8) & 0xFFu : static_cast<uint32_t>(want);
     const uint32_t row = cell < 225u ? hdr.rows[cell / 15] >> (cell % 15) : 0x10001u;
@@ -995,7 +952,7 @@ void az_step_kernel(AzTree t, AzArena b, const int16_t* forced) {
     }
     const uint32_t src = !legal ? 0u : (found ? first + best_i : kNoNode);
     if (src == kNoNode) {                                       // stepForward(move) without such a child: a new node (MCTS.cpp:140-145)
-        if (lane == 0) { b.stat[base] = make_uint2(0u, 0u); b.kids[base] = make_uint2(0u, cell << 8); b.prior[base] = 1.0f; b.parent[base] = kNoNode; hdr.n_nodes = 1; }
+        if (lane == 0) { new_root(b, base, cell << 8); hdr.n_nodes = 1; }
         return;
     }
     az_keep_subtree(t, b, base, src, lane, hdr);
@@ -1019,36 +976,20 @@ void az_advance_kernel(AzTree t, AzArena b, uint8_t* __restrict__ rec_moves, uin
     const size_t base = static_cast<size_t>(slot) * t.cap;
     const int game = sl.slot_game ? sl.slot_game[slot] : slot;      // the rows of the records
     if ((hdr.status & kStatusOver) || game < 0) {
-        if (reuse && lane == 0) { b.stat[base] = make_uint2(0u, 0u); b.kids[base] = make_uint2(0u, 0u); b.prior[base] = 1.0f; b.parent[base] = kNoNode; }
+        if (reuse && lane == 0) new_root(b, base, 0u);
         return;
     }
     const uint2 rk = t.kids[base];
     const uint32_t first = rk.x, n = rk.y & 0xFFu;
-    uint32_t best_v = 0, best_i = 0xFFFFFFFFu;                   // visits, first maximum in child order
-    for (uint32_t i = lane; i < n; i += 64) {
-        const uint32_t v = t.stat[base + first + i].x;
-        if (v > best_v) { best_v = v; best_i = i; }
-    }
-    for (int s = 32; s > 0; s >>= 1) {
-        const uint32_t ov = __shfl_down(best_v, s), oi = __shfl_down(best_i, s);
-        if (ov > best_v || (ov == best_v && ov != 0u && oi < best_i)) { best_v = ov; best_i = oi; }
-    }
-    best_v = __shfl(best_v, 0);
-    best_i = __shfl(best_i, 0);
-    if constexpr (kProof) proof_choice(t.kids + base, t.stat + base, first, n, lane, best_v, best_i);
+    const uint32_t best_i = most_visited_child<kProof>(t.kids + base, t.stat + base, first, n, lane);
     const uint32_t stones = hdr.stones;
     const int len = rec_lens[game];
-    bool over = best_v == 0u || stones >= 225u || len >= 225;    // nothing the search wants to play
+    bool over = best_i == 0xFFFFFFFFu || stones >= 225u || len >= 225;                 // nothing the search wants to play
     int winner = 0;
     uint32_t cell = 255u;
     if (!over) {
         cell = (t.kids[base + first + best_i].y >> 8) & 0xFFu;
-        if (rec_visits) {
-            uint16_t* rv = rec_visits + (static_cast<size_t>(game) * kCells + static_cast<size_t>(len)) * kCells;
-            for (int i = lane; i < kCells; i += 64) rv[i] = 0;
-            __syncthreads();
-            for (uint32_t i = lane; i < n; i += 64) rv[(t.kids[base + first + i].y >> 8) & 0xFFu] = static_cast<uint16_t>(min(t.stat[base + first + i].x, 65535u));
-        }
+        if (rec_visits) visits_by_cell(rec_visits + (static_cast<size_t>(game) * kCells + static_cast<size_t>(len)) * kCells, t.kids + base, t.stat + base, first, n, lane);
         const int shift = (stones & 1u) ? 16 : 0;                // black moves on even stone counts
         if (lane < 16) s_rows[lane] = hdr.rows[lane] | ((lane == static_cast<int>(cell / 15u)) ? 1u << (cell % 15u + shift) : 0u);
         __syncthreads();
@@ -1093,8 +1034,8 @@ void az_advance_kernel(AzTree t, AzArena b, uint8_t* __restrict__ rec_moves, uin
             hdr.leaf_pending = 0;
             hdr.quota = 0;                                       // a refilled slot owes nothing until the next gmk_az_add_playouts
             hdr.n_nodes = 1;
-            t.stat[base] = make_uint2(0u, 0u); t.kids[base] = make_uint2(0u, root_cell); t.prior[base] = 1.0f; t.parent[base] = kNoNode;
-            if (reuse) { b.stat[base] = make_uint2(0u, 0u); b.kids[base] = make_uint2(0u, root_cell); b.prior[base] = 1.0f; b.parent[base] = kNoNode; }
+            new_root(t, base, root_cell);
+            if (reuse) new_root(b, base, root_cell);
         }
         return;
     }
@@ -1102,7 +1043,7 @@ void az_advance_kernel(AzTree t, AzArena b, uint8_t* __restrict__ rec_moves, uin
     if (reuse) {
         az_keep_subtree(t, b, base, first + best_i, lane, hdr);
     } else if (lane == 0) {                                      // a new root, as gmk_az_set_roots makes it
-        t.stat[base] = make_uint2(0u, 0u); t.kids[base] = make_uint2(0u, cell << 8); t.prior[base] = 1.0f; t.parent[base] = kNoNode;
+        new_root(t, base, cell << 8);
         hdr.n_nodes = 1;
     }
 }
@@ -1195,23 +1136,9 @@ void az_root_choice_kernel(AzTree t, int16_t* __restrict__ cells, uint16_t* __re
     const size_t base = static_cast<size_t>(game) * t.cap;
     const uint2 rk = t.kids[base];
     const uint32_t first = rk.x, n = rk.y & 0xFFu;
-    uint32_t best_v = 0, best_i = 0xFFFFFFFFu;
-    for (uint32_t i = lane; i < n; i += 64) {
-        const uint32_t v = t.stat[base + first + i].x;
-        if (v > best_v) { best_v = v; best_i = i; }
-    }
-    for (int s = 32; s > 0; s >>= 1) {
-        const uint32_t ov = __shfl_down(best_v, s), oi = __shfl_down(best_i, s);
-        if (ov > best_v || (ov == best_v && ov != 0u && oi < best_i)) { best_v = ov; best_i = oi; }
-    }
-    if constexpr (kProof) proof_choice(t.kids + base, t.stat + base, first, n, lane, best_v, best_i);
-    if (lane == 0) cells[game] = best_v == 0u ? static_cast<int16_t>(-1) : static_cast<int16_t>((t.kids[base + first + best_i].y >> 8) & 0xFFu);
-    if (visits) {
-        uint16_t* rv = visits + static_cast<size_t>(game) * kCells;
-        for (int i = lane; i < kCells; i += 64) rv[i] = 0;
-        __syncthreads();
-        for (uint32_t i = lane; i < n; i += 64) rv[(t.kids[base + first + i].y >> 8) & 0xFFu] = static_cast<uint16_t>(min(t.stat[base + first + i].x, 65535u));
-    }
+    const uint32_t best_i = most_visited_child<kProof>(t.kids + base, t.stat + base, first, n, lane);
+    if (lane == 0) cells[game] = best_i == 0xFFFFFFFFu ? static_cast<int16_t>(-1) : static_cast<int16_t>((t.kids[base + first + best_i].y >> 8) & 0xFFu);
+    if (visits) visits_by_cell(visits + static_cast<size_t>(game) * kCells, t.kids + base, t.stat + base, first, n, lane);
 }
 
 // gmk_az_step with the cells and the referee's verdicts (GMK_MATCH_*) read from device memory.  A game that moved follows the move -- the
@@ -1238,14 +1165,9 @@ void az_step_device_kernel(AzTree t, AzArena b, const int16_t* __restrict__ cell
         if (!fresh) az_keep_subtree(t, b, base, 0u, lane, hdr);
         return;
     }
-    uint32_t best_i = 0xFFFFFFFFu;                               // the child of that cell (children are in ascending cell order: at most one)
-    if (!fresh && v == GMK_MATCH_MOVED) {
-        const uint2 rk = t.kids[base];
-        const uint32_t first = rk.x, n = rk.y & 0xFFu;
-        for (uint32_t i = lane; i < n; i += 64)
-            if (((t.kids[base + first + i].y >> 8) & 0xFFu) == cell) best_i = first + i;
-        for (int s = 32; s > 0; s >>= 1) best_i = min(best_i, static_cast<uint32_t>(__shfl_xor(best_i, s)));
-    }
+    const uint2 rk = t.kids[base];
+    uint32_t best_i = 0xFFFFFFFFu;                               // the child of that cell
+    if (!fresh && v == GMK_MATCH_MOVED) best_i = child_of_cell(t.kids + base, rk.x, rk.y & 0xFFu, cell, lane);
     __syncthreads();                                             // every lane has read the old header
     if (lane == 0) {
         hdr.rows[cell / 15u] |= 1u << (cell % 15u + ((stones & 1u) ? 16 : 0));
@@ -1259,30 +1181,26 @@ void az_step_device_kernel(AzTree t, AzArena b, const int16_t* __restrict__ cell
             hdr.status |= kStatusOver;
             hdr.quota = 0;
             hdr.n_nodes = 1;
-            t.stat[base] = make_uint2(0u, 0u); t.kids[base] = make_uint2(0u, 0u); t.prior[base] = 1.0f; t.parent[base] = kNoNode;
-            if (!fresh) { b.stat[base] = make_uint2(0u, 0u); b.kids[base] = make_uint2(0u, 0u); b.prior[base] = 1.0f; b.parent[base] = kNoNode; }
+            new_root(t, base, 0u);
+            if (!fresh) new_root(b, base, 0u);
         }
         return;
     }
     if (fresh) {                                                 // a new root, as az_init_roots_kernel makes it
-        if (lane == 0) { t.stat[base] = make_uint2(0u, 0u); t.kids[base] = make_uint2(0u, cell << 8); t.prior[base] = 1.0f; t.parent[base] = kNoNode; hdr.n_nodes = 1; }
+        if (lane == 0) { new_root(t, base, cell << 8); hdr.n_nodes = 1; }
         return;
     }
     if (best_i == 0xFFFFFFFFu) {                                 // stepForward(move) without such a child: a new node (MCTS.cpp:140-145)
-        if (lane == 0) { b.stat[base] = make_uint2(0u, 0u); b.kids[base] = make_uint2(0u, cell << 8); b.prior[base] = 1.0f; b.parent[base] = kNoNode; hdr.n_nodes = 1; }
+        if (lane == 0) { new_root(b, base, cell << 8); hdr.n_nodes = 1; }
         return;
     }
-    az_keep_subtree(t, b, base, best_i, lane, hdr);
+    az_keep_subtree(t, b, base, rk.x + best_i, lane, hdr);
 }
 
 __global__ void az_init_roots_kernel(AzTree t) {
     const int game = blockIdx.x * blockDim.x + threadIdx.x;
     if (game >= t.n_games) return;
-    const size_t arena = static_cast<size_t>(game) * t.cap;
-    t.stat[arena] = make_uint2(0u, 0u);
-    t.kids[arena] = make_uint2(0u, (t.hdr[game].last_move & 0xFFu) << 8);
-    t.prior[arena] = 1.0f;
-    t.parent[arena] = kNoNode;
+    new_root(t, static_cast<size_t>(game) * t.cap, (t.hdr[game].last_move & 0xFFu) << 8);
 }
 
 __global__ __launch_bounds__(64)
@@ -1527,6 +1445,25 @@ extern "C" int gmk_az_set_slots(gmk_az* a, int n_total, const uint8_t* h_open_mo
 static bool az_defend_wanted(const gmk_az* a) { return a->defend && a->proof && a->vcf.max_depth > 0; }
 static bool az_defend_active(const gmk_az* a) { return az_defend_wanted(a) && a->df.threat != nullptr; }
 
+// The instantiation of a kernel for the handle's options: f is handed them as std::bool_constants and returns the kernel.  f(kVcf, kProof,
+// kDefend) for the expand kernels: proofs start there only at a leaf answered WIN, so without the solver the proof option launches what it
+// launches when off.  f(kProof) for the others.
+template <class F>
+static auto az_expand_variant(const gmk_az* a, F f) {
+    if (az_defend_active(a)) return f(std::true_type{}, std::true_type{}, std::true_type{});
+    if (a->vcf.max_depth > 0 && a->proof) return f(std::true_type{}, std::true_type{}, std::false_type{});
+    if (a->vcf.max_depth > 0) return f(std::true_type{}, std::false_type{}, std::false_type{});
+    return f(std::false_type{}, std::false_type{}, std::false_type{});
+}
+template <class F>
+static auto az_proof_variant(const gmk_az* a, F f) {
+    return a->proof ? f(std::true_type{}) : f(std::false_type{});
+}
+// the second arena holds the trees now
+static void az_flip_arenas(gmk_az* a) {
+    std::swap(a->t.stat, a->other.stat); std::swap(a->t.kids, a->other.kids); std::swap(a->t.prior, a->other.prior); std::swap(a->t.parent, a->other.parent);
+}
+
 // The buffers of K7 + K15, when an option call makes it act for the first time: per row of the largest leaf batch the threat (every row reads
 // "not asked" until a select writes it), its line, the occupied cells and one word per cell.
 static int az_defend_buffers(gmk_az* a) {
@@ -1568,14 +1505,14 @@ extern "C" int gmk_az_select(gmk_az* a, float* d_states, void* stream) {
     if (!a->rooted) { gmk::set_error("gmk_az_select: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
     if (a->lv.leaves > 1) {                                      // d_states has gmk_az_live_games x L rows
         if (az_marks_up(a, "gmk_az_select")) return GMK_ERR_STATE;
-        if (a->proof) hipLaunchKernelGGL(az_select_leaves_kernel<true>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_states);
-        else hipLaunchKernelGGL(az_select_leaves_kernel<false>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_states);
+        const auto kernel = az_proof_variant(a, [](auto proof) { return &az_select_leaves_kernel<proof>; });
+        hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_states);
         GMK_HIP_CHECK(hipGetLastError());
         a->select_issued = true;
         return az_vcf_leaves(a, stream);
     }
-    if (a->proof) hipLaunchKernelGGL(az_select_kernel<true>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_states);
-    else hipLaunchKernelGGL(az_select_kernel<false>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_states);
+    const auto kernel = az_proof_variant(a, [](auto proof) { return &az_select_kernel<proof>; });
+    hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_states);
     GMK_HIP_CHECK(hipGetLastError());
     return az_vcf_leaves(a, stream);
 }
@@ -1584,20 +1521,15 @@ extern "C" int gmk_az_expand(gmk_az* a, const float* d_values, const float* d_pr
     if (!a || !d_values || !d_probs) { gmk::set_error("gmk_az_expand: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_expand: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
     if (a->lv.leaves > 1) {                                      // d_values and d_probs have gmk_az_live_games x L rows
-        // proofs start in the expand kernels only at a leaf answered WIN: without the solver the proof option launches what it launches when off
-        if (az_defend_active(a)) hipLaunchKernelGGL((az_expand_leaves_kernel<true, true, true>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf, a->df);
-        else if (a->vcf.max_depth > 0 && a->proof) hipLaunchKernelGGL((az_expand_leaves_kernel<true, true, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf, a->df);
-        else if (a->vcf.max_depth > 0) hipLaunchKernelGGL((az_expand_leaves_kernel<true, false, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf, a->df);
-        else hipLaunchKernelGGL((az_expand_leaves_kernel<false, false, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf, a->df);
+        const auto kernel = az_expand_variant(a, [](auto vcf, auto proof, auto defend) { return &az_expand_leaves_kernel<vcf, proof, defend>; });
+        hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_values, d_probs, a->vcf, a->df);
         GMK_HIP_CHECK(hipGetLastError());
         a->select_issued = false;
         a->leaf_waiting = false;
         return GMK_OK;
     }
-    if (az_defend_active(a)) hipLaunchKernelGGL((az_expand_kernel<true, true, true>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf, a->df);
-    else if (a->vcf.max_depth > 0 && a->proof) hipLaunchKernelGGL((az_expand_kernel<true, true, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf, a->df);
-    else if (a->vcf.max_depth > 0) hipLaunchKernelGGL((az_expand_kernel<true, false, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf, a->df);
-    else hipLaunchKernelGGL((az_expand_kernel<false, false, false>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf, a->df);
+    const auto kernel = az_expand_variant(a, [](auto vcf, auto proof, auto defend) { return &az_expand_kernel<vcf, proof, defend>; });
+    hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_values, d_probs, 3, a->vcf, a->df);
     GMK_HIP_CHECK(hipGetLastError());
     a->leaf_waiting = false;
     return GMK_OK;
@@ -1656,19 +1588,19 @@ extern "C" int gmk_az_step(gmk_az* a, const int16_t* h_moves) {
     if (const int rc = az_second_arena(a); rc != GMK_OK) return rc;
     GMK_HIP_CHECK(hipDeviceSynchronize());
     if (h_moves) GMK_HIP_CHECK(hipMemcpy(a->d_forced, h_moves, n * 2, hipMemcpyHostToDevice));
-    if (a->proof) hipLaunchKernelGGL(az_step_kernel<true>, dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, a->other, h_moves ? a->d_forced : nullptr);
-    else hipLaunchKernelGGL(az_step_kernel<false>, dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, a->other, h_moves ? a->d_forced : nullptr);
+    const auto kernel = az_proof_variant(a, [](auto proof) { return &az_step_kernel<proof>; });
+    hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, a->other, h_moves ? a->d_forced : nullptr);
     GMK_HIP_CHECK(hipGetLastError());
     GMK_HIP_CHECK(hipDeviceSynchronize());
-    std::swap(a->t.stat, a->other.stat); std::swap(a->t.kids, a->other.kids); std::swap(a->t.prior, a->other.prior); std::swap(a->t.parent, a->other.parent);
+    az_flip_arenas(a);
     return GMK_OK;
 }
 
 extern "C" int gmk_az_root_choice(gmk_az* a, int16_t* d_cells, uint16_t* d_visits, void* stream) {
     if (!a || !d_cells) { gmk::set_error("gmk_az_root_choice: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_root_choice: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
-    if (a->proof) hipLaunchKernelGGL(az_root_choice_kernel<true>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_cells, d_visits);
-    else hipLaunchKernelGGL(az_root_choice_kernel<false>, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_cells, d_visits);
+    const auto kernel = az_proof_variant(a, [](auto proof) { return &az_root_choice_kernel<proof>; });
+    hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_cells, d_visits);
     GMK_HIP_CHECK(hipGetLastError());
     return GMK_OK;
 }
@@ -1689,7 +1621,7 @@ extern "C" int gmk_az_step_device(gmk_az* a, const int16_t* d_cells, const int32
     int32_t unfinished = 0;
     if (h_unfinished) GMK_HIP_CHECK(hipMemcpyAsync(&unfinished, d_unfinished, 4, hipMemcpyDeviceToHost, s));
     if (const int rc = az_compact(a, s); rc != GMK_OK) return rc;   // (synchronises)
-    if (!fresh_root) { std::swap(a->t.stat, a->other.stat); std::swap(a->t.kids, a->other.kids); std::swap(a->t.prior, a->other.prior); std::swap(a->t.parent, a->other.parent); }
+    if (!fresh_root) az_flip_arenas(a);
     if (h_unfinished) *h_unfinished = unfinished;
     return GMK_OK;
 }
@@ -1705,13 +1637,13 @@ extern "C" int gmk_az_advance(gmk_az* a, uint8_t* d_moves, uint16_t* d_visits, i
     if (!a->d_unfinished) GMK_HIP_CHECK(gmk::device_malloc(&a->d_unfinished, 4));
     hipStream_t s = static_cast<hipStream_t>(stream);
     GMK_HIP_CHECK(hipMemsetAsync(a->d_unfinished, 0, 4, s));
-    if (a->proof) hipLaunchKernelGGL(az_advance_kernel<true>, dim3(a->t.n_games), dim3(64), 0, s, a->t, a->other, d_moves, d_visits, d_lens, d_winner, a->d_unfinished, reuse_subtree ? 1 : 0, a->slots);
-    else hipLaunchKernelGGL(az_advance_kernel<false>, dim3(a->t.n_games), dim3(64), 0, s, a->t, a->other, d_moves, d_visits, d_lens, d_winner, a->d_unfinished, reuse_subtree ? 1 : 0, a->slots);
+    const auto kernel = az_proof_variant(a, [](auto proof) { return &az_advance_kernel<proof>; });
+    hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, s, a->t, a->other, d_moves, d_visits, d_lens, d_winner, a->d_unfinished, reuse_subtree ? 1 : 0, a->slots);
     GMK_HIP_CHECK(hipGetLastError());
     int32_t unfinished = 0;
     GMK_HIP_CHECK(hipMemcpyAsync(&unfinished, a->d_unfinished, 4, hipMemcpyDeviceToHost, s));
     if (const int rc = az_compact(a, s); rc != GMK_OK) return rc;   // (synchronises: both numbers are here now, and they agree)
-    if (reuse_subtree) { std::swap(a->t.stat, a->other.stat); std::swap(a->t.kids, a->other.kids); std::swap(a->t.prior, a->other.prior); std::swap(a->t.parent, a->other.parent); }
+    if (reuse_subtree) az_flip_arenas(a);
     if (h_unfinished) *h_unfinished = unfinished;
     return GMK_OK;
 }

@@ -30,6 +30,7 @@ class ProofSearch(A.VcfLeavesSearch):
     def reset_counters(self):
         super().reset_counters()
         self.proved, self.stops = 0, 0
+        self.floor_picks = 0                                     # descents' levels at which nothing beat -1.0 (not a counter of the handle)
 
     def _new_root(self):
         super()._new_root()
@@ -82,6 +83,7 @@ class ProofSearch(A.VcfLeavesSearch):
             best = int(np.argmax(score))                         # the first maximum
             if not score[best] > -1.0:
                 best = 0
+                self.floor_picks += 1
             if len(lose):
                 best = int(lose[0])
             node = a + best

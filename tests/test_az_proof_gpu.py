@@ -90,6 +90,31 @@ def test_an_open_four_between_the_descents_of_one_step(depth):
     tree.close()
 
 
+def faint_and_lost(states):
+    """every leaf is lost for the side that moved into it, and the priors are too small to lift a score off -1.0 in float64"""
+    return np.float32(1.0), np.full(N, np.float32(2.0) ** -100, dtype=np.float32)
+
+
+@pytest.mark.parametrize("leaves", [1, 4])
+@pytest.mark.parametrize("proof", [False, True])
+def test_nothing_beats_the_initial_score(leaves, proof):
+    """Boards with 2 .. 5 empty cells: once every child of a node has come back lost (Q = -1.0, or all in flight at L = 4) no score is
+    above the -1.0 the maximum starts from, and the descent takes the first child.  The proof option runs the same search here (no five is
+    met); it is the other instantiation of the descent."""
+    from test_az_leaves_gpu import _late_boards
+    refs = [P.ProofSearch(moves, faint_and_lost, 0, 64, proof=proof, c_puct=5.0, leaves=leaves) for moves in _late_boards()]
+    for ref in refs:
+        ref.search(40)
+    assert all(ref.floor_picks > 0 for ref in refs) and not any(ref.proved for ref in refs)
+    tree = _tree(_late_boards(), leaves, 5.0, 0, proof=proof)
+    tree.search(_host_network(faint_and_lost), 40)
+    st = tree.root_stats()
+    assert (st["root_visits"] == 40).all() and (st["status"] == 0).all()
+    _same(st, refs)
+    _same_proofs(tree, refs)
+    tree.close()
+
+
 # ---------------- 2. the arena ----------------
 @pytest.mark.parametrize("leaves", [1, 4])
 def test_a_win_leaf_that_does_not_fit_gets_no_bit(leaves):
@@ -139,6 +164,34 @@ def test_kept_subtrees_and_root_noise_across_three_moves(leaves):
         _same_proofs(tree, refs, "after step %d" % move)        # the bits travel with the subtree
         carried += sum(ref.proof[0] != P.NONE or any(ref.root_proofs()["children"]) for ref in refs)
     assert carried > 0 and sum(ref.stops for ref in refs) > 0
+    tree.close()
+
+
+@pytest.mark.parametrize("proof", [False, True])
+def test_step_from_unvisited_children_takes_the_first(proof):
+    """One playout expands the root and visits no child: the root choice has nothing to play, gmk_az_step(NULL) follows the first child
+    (max_element over equal counts), and the next search shows which cell it was."""
+    import torch
+    openings = [R.OPENINGS[1], R.OPENINGS[2]]
+    refs = [P.ProofSearch(moves, R.surrogate, 0, 64, proof=proof, c_puct=5.0) for moves in openings]
+    for ref in refs:
+        ref.search(1)
+    assert all(ref.nkids[0] > 1 and ref.choice() == P.NO_NODE for ref in refs)
+    tree = _tree(openings, 1, 5.0, 0, proof=proof)
+    network = _host_network(R.surrogate)
+    tree.search(network, 1)
+    cells = torch.full((len(refs),), -7, dtype=torch.int16, device="cuda")
+    tree.root_choice(cells)
+    assert cells.cpu().tolist() == [-1] * len(refs)
+    tree.step(None)
+    for ref in refs:
+        first = ref.cell[ref.first[0]]
+        assert ref.reroot() == first and ref.n_nodes == 1
+    _same(tree.root_stats(), refs, "after the step")
+    tree.search(network, 8)
+    for ref in refs:
+        ref.search(8)
+    _same(tree.root_stats(), refs, "the search after the step")
     tree.close()
 
 
