@@ -1298,7 +1298,19 @@ extern "C" int gmk_az_create(int n_games, int node_capacity, double c_puct, gmk_
     a->t.row_of = a->d_row_of;
     a->game_ids.resize(static_cast<size_t>(n_games));
     for (int g = 0; g < n_games; ++g) a->game_ids[static_cast<size_t>(g)] = static_cast<uint32_t>(g);
+    if (gmk::device_malloc(&a->d_game_ids, static_cast<size_t>(n_games) * 4) != hipSuccess ||
+        hipMemcpy(a->d_game_ids, a->game_ids.data(), static_cast<size_t>(n_games) * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        gmk_az_destroy(a); gmk::set_error("gmk_az_create: device allocation failed"); return GMK_ERR_HIP;
+    }
     *out = a;
+    return GMK_OK;
+}
+
+// d_game_ids mirrors game_ids, so that gmk_az_add_root_noise's kernel needs nothing from the host: after every change of game_ids, once the
+// device is idle (a noise kernel may still be reading the old ones on a stream of the caller's)
+static int az_upload_game_ids(gmk_az* a) {
+    GMK_HIP_CHECK(hipDeviceSynchronize());
+    GMK_HIP_CHECK(hipMemcpy(a->d_game_ids, a->game_ids.data(), a->game_ids.size() * 4, hipMemcpyHostToDevice));
     return GMK_OK;
 }
 
@@ -1343,7 +1355,7 @@ extern "C" int gmk_az_live_games(gmk_az* a, int32_t* n_live) {
 extern "C" int gmk_az_set_game_ids(gmk_az* a, const uint32_t* h_ids) {
     if (!a || !h_ids) { gmk::set_error("gmk_az_set_game_ids: bad arguments"); return GMK_ERR_ARG; }
     a->game_ids.assign(h_ids, h_ids + a->t.n_games);
-    return GMK_OK;
+    return az_upload_game_ids(a);
 }
 
 extern "C" int gmk_az_set_roots(gmk_az* a, const uint16_t* h_planes, const int16_t* h_last_moves) {
@@ -1436,6 +1448,7 @@ extern "C" int gmk_az_set_slots(gmk_az* a, int n_total, const uint8_t* h_open_mo
     GMK_HIP_CHECK(hipGetLastError());
     GMK_HIP_CHECK(hipDeviceSynchronize());
     for (size_t g = 0; g < ns; ++g) a->game_ids[g] = state[g] >= 0 ? static_cast<uint32_t>(state[g]) : 0u;
+    if (const int rc = az_upload_game_ids(a); rc != GMK_OK) return rc;
     a->rooted = true;
     return az_compact(a, nullptr);
 }
@@ -1705,26 +1718,26 @@ extern "C" int gmk_az_set_option(gmk_az* a, int option, int value) {
     return GMK_ERR_ARG;
 }
 
-// Default::AddNoise on every root with children, seeded like gmk_mcts_add_root_noise / gmk_trad_add_root_noise
-extern "C" int gmk_az_add_root_noise(gmk_az* a, float alpha, float epsilon, uint64_t seed, uint32_t first_game_id) {
+// Default::AddNoise on every root with children, seeded like gmk_mcts_add_root_noise / gmk_trad_add_root_noise.  The counter sampler is one
+// launch on `stream` and does not wait.  The std sampler draws on the host: it waits for `stream`, then for the device, and returns finished.
+extern "C" int gmk_az_add_root_noise(gmk_az* a, float alpha, float epsilon, uint64_t seed, uint32_t first_game_id, void* stream) {
     if (!a || !(alpha > 0.0f)) { gmk::set_error("gmk_az_add_root_noise: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_add_root_noise: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
     if (az_marks_up(a, "gmk_az_add_root_noise")) return GMK_ERR_STATE;
     const size_t n = static_cast<size_t>(a->t.n_games);
+    hipStream_t s = static_cast<hipStream_t>(stream);
     if (a->noise_sampler == GMK_NOISE_SAMPLER_COUNTER) {         // drawn on the device, one wavefront per game: nothing comes back to the host
-        if (!a->slots.slot_game) {
-            if (!a->d_game_ids) GMK_HIP_CHECK(gmk::device_malloc(&a->d_game_ids, n * 4));
-            GMK_HIP_CHECK(hipMemcpy(a->d_game_ids, a->game_ids.data(), n * 4, hipMemcpyHostToDevice));
-        }
-        hipLaunchKernelGGL(az_root_noise_kernel, dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, a->slots.slot_game, a->d_game_ids, first_game_id, alpha, epsilon,
+        hipLaunchKernelGGL(az_root_noise_kernel, dim3(a->t.n_games), dim3(64), 0, s, a->t, a->slots.slot_game, a->d_game_ids, first_game_id, alpha, epsilon,
                            static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32));
         GMK_HIP_CHECK(hipGetLastError());
         return GMK_OK;
     }
+    GMK_HIP_CHECK(hipStreamSynchronize(s));
     if (a->slots.slot_game) {                                    // continuous batching: the random stream belongs to the GAME a slot plays
         std::vector<int32_t> slot_game(n);
         GMK_HIP_CHECK(hipMemcpy(slot_game.data(), a->slots.slot_game, n * 4, hipMemcpyDeviceToHost));
         for (size_t g = 0; g < n; ++g) a->game_ids[g] = slot_game[g] >= 0 ? static_cast<uint32_t>(slot_game[g]) : 0u;
+        if (const int rc = az_upload_game_ids(a); rc != GMK_OK) return rc;
     }
     std::vector<float> priors(n * 225);
     int rc = gmk_az_root_stats(a, nullptr, nullptr, priors.data(), nullptr, nullptr, nullptr, nullptr);

@@ -376,7 +376,7 @@ private:
         }
         az_record_.assign(board.record_.begin(), board.record_.end());
         az_valid_ = true;
-        if (g_root_noise_alpha > 0.0f) throw_gmk(gmk_az_add_root_noise(az_handle_, g_root_noise_alpha, g_root_noise_epsilon, g_search_seed, game_id_));
+        if (g_root_noise_alpha > 0.0f) throw_gmk(gmk_az_add_root_noise(az_handle_, g_root_noise_alpha, g_root_noise_epsilon, g_search_seed, game_id_, nullptr));
         return budget;
     }
 
@@ -608,7 +608,7 @@ private:
         }
         trad_record_.assign(board.record_.begin(), board.record_.end());
         trad_valid_ = true;
-        if (g_root_noise_alpha > 0.0f) throw_gmk(gmk_trad_add_root_noise(trad_handle_, g_root_noise_alpha, g_root_noise_epsilon, g_search_seed, game_id_));
+        if (g_root_noise_alpha > 0.0f) throw_gmk(gmk_trad_add_root_noise(trad_handle_, g_root_noise_alpha, g_root_noise_epsilon, g_search_seed, game_id_, nullptr));
         std::vector<float> values(kN), priors(kN);
         uint32_t root_visits = 0;
         float q = 0.0f;

@@ -898,6 +898,7 @@ static int pair_arenas(gmk_mcts* m) {
     if (m->paired) {
         m->d_stats = m->block_stats; m->d_link = m->block_link; m->d_parent = m->block_parent;       // (the lock-step loop may have left them swapped)
         m->d_stats2 = m->block_stats + nodes; m->d_link2 = m->block_link + nodes; m->d_parent2 = m->block_parent + nodes;
+        m->rooted = false;                                          // the live trees may have been in the other half
         return GMK_OK;
     }
     (void)gmk::device_free(m->d_stats); (void)gmk::device_free(m->d_link); (void)gmk::device_free(m->d_parent);

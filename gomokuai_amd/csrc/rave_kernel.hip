@@ -386,6 +386,7 @@ extern "C" int gmk_trad_root_amaf(gmk_trad* t, uint32_t* h_amaf_visits, float* h
 #define GMK_TRY(expr) do { if ((expr) != hipSuccess) { gmk::set_error("%s failed", #expr); cleanup(); return GMK_ERR_HIP; } } while (0)
     GMK_TRY(gmk::device_malloc(&d_visits, n * 225 * 4)); GMK_TRY(gmk::device_malloc(&d_values, n * 225 * 4));
     GMK_TRY(hipMemset(d_visits, 0, n * 225 * 4)); GMK_TRY(hipMemset(d_values, 0, n * 225 * 4));
+    GMK_TRY(hipDeviceSynchronize());                             // a search may still be running on a stream of the caller's
     hipLaunchKernelGGL(rave_root_amaf_kernel, dim3(t->n_games), dim3(64), 0, nullptr, t->arena(), t->d_hdr, t->cap, d_visits, d_values);
     GMK_TRY(hipGetLastError());
     GMK_TRY(hipDeviceSynchronize());

@@ -1268,18 +1268,19 @@ extern "C" int gmk_trad_step_device(gmk_trad* t, const int16_t* d_cells, const i
 }
 
 // Default::AddNoise (MonteCarlo.hpp:97-108) on every root that has children (root_noise.h)
-extern "C" int gmk_trad_add_root_noise(gmk_trad* t, float alpha, float epsilon, uint64_t seed, uint32_t first_game_id) {
+// The counter sampler is one launch on `stream` and does not wait (d_game_ids mirrors game_ids: gmk_trad_set_game_ids and the end of
+// gmk_trad_selfplay_run keep it so).  The std sampler draws on the host: it waits for `stream`, then for the device, and returns finished.
+extern "C" int gmk_trad_add_root_noise(gmk_trad* t, float alpha, float epsilon, uint64_t seed, uint32_t first_game_id, void* stream) {
     if (!t || !(alpha > 0.0f)) { gmk::set_error("gmk_trad_add_root_noise: bad arguments"); return GMK_ERR_ARG; }
     if (!t->positioned) { gmk::set_error("gmk_trad_add_root_noise: gmk_trad_set_positions has not been called"); return GMK_ERR_STATE; }
     const size_t n = static_cast<size_t>(t->n_games);
     if (t->noise_sampler == GMK_NOISE_SAMPLER_COUNTER) {        // drawn on the device, one wavefront per game: nothing comes back to the host
-        GMK_HIP_CHECK(hipMemcpy(t->d_game_ids, t->game_ids.data(), n * 4, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(trad_root_noise_kernel, dim3(t->n_games), dim3(64), 0, nullptr, t->arena(), t->d_hdr, t->cap, t->d_lens, t->d_game_ids, first_game_id,
+        hipLaunchKernelGGL(trad_root_noise_kernel, dim3(t->n_games), dim3(64), 0, static_cast<hipStream_t>(stream), t->arena(), t->d_hdr, t->cap, t->d_lens, t->d_game_ids, first_game_id,
                            alpha, epsilon, static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32));
         GMK_HIP_CHECK(hipGetLastError());
-        GMK_HIP_CHECK(hipDeviceSynchronize());
         return GMK_OK;
     }
+    GMK_HIP_CHECK(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     std::vector<float> priors(n * 225);
     std::vector<int32_t> lens(n);
     int rc = gmk_trad_root_stats(t, nullptr, nullptr, priors.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
@@ -1314,6 +1315,7 @@ extern "C" int gmk_trad_root_stats(gmk_trad* t, uint32_t* h_visits, float* h_val
     GMK_TRY(gmk::device_malloc(&d_visits, n * 225 * 4)); GMK_TRY(gmk::device_malloc(&d_values, n * 225 * 4)); GMK_TRY(gmk::device_malloc(&d_priors, n * 225 * 4));
     GMK_TRY(gmk::device_malloc(&d_best, n * 4)); GMK_TRY(gmk::device_malloc(&d_root_visits, n * 4)); GMK_TRY(gmk::device_malloc(&d_root_value, n * 4));
     GMK_TRY(hipMemset(d_visits, 0, n * 225 * 4)); GMK_TRY(hipMemset(d_values, 0, n * 225 * 4)); GMK_TRY(hipMemset(d_priors, 0, n * 225 * 4));
+    GMK_TRY(hipDeviceSynchronize());                             // a search may still be running on a stream of the caller's
     hipLaunchKernelGGL(trad_root_stats_kernel, dim3(t->n_games), dim3(64), 0, nullptr, t->d_stat, t->d_info, t->d_link, t->d_ord, t->d_hdr, t->cap,
                        d_visits, d_values, d_priors, d_best, d_root_visits, d_root_value);
     GMK_TRY(hipGetLastError());
@@ -1488,7 +1490,7 @@ extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int policy, int n_total, uint3
         } else if (noise_alpha > 0.0f) {                        // Default::AddNoise at the start of every search (MCTS.cpp:182), keyed by the GAME a slot plays
             GMK_TRY(hipMemcpy(slot_game.data(), d_state, ns * 4, hipMemcpyDeviceToHost));
             for (size_t g = 0; g < ns; ++g) t->game_ids[g] = slot_game[g] >= 0 ? static_cast<uint32_t>(slot_game[g]) : 0u;
-            rc = gmk_trad_add_root_noise(t, noise_alpha, noise_epsilon, seed, first_game_id);
+            rc = gmk_trad_add_root_noise(t, noise_alpha, noise_epsilon, seed, first_game_id, s);
             if (rc != GMK_OK) break;
         }
         rc = policy == 1 ? gmk_trad_run_poolrave(t, playouts, c_puct, seed, first_game_id, s)
@@ -1511,6 +1513,7 @@ extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int policy, int n_total, uint3
     }
     int32_t overflow = 0;
     if (rc == GMK_OK) GMK_TRY(hipMemcpy(&overflow, sp.overflow, 4, hipMemcpyDeviceToHost));
+    if (rc == GMK_OK) GMK_TRY(hipMemcpy(t->d_game_ids, t->game_ids.data(), ns * 4, hipMemcpyHostToDevice));      // the loop's kernels wrote it: it mirrors game_ids again
 #undef GMK_TRY
     cleanup();
     if (h_overflow) *h_overflow = overflow;

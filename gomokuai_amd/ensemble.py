@@ -120,7 +120,7 @@ class EnsembleSearch:
         if self.policy == "random":
             self.tree.add_root_noise(alpha, eps, stream=self._stream())
         else:
-            self.tree.add_root_noise(alpha, eps, seed=self.seed, first_game_id=self.first_game_id)
+            self.tree.add_root_noise(alpha, eps, seed=self.seed, first_game_id=self.first_game_id, stream=self._stream())
 
     def search(self, playouts):
         """`playouts` more playouts for every replica, on the current stream (no wait).  With root_noise, the first search of a root draws it."""

@@ -154,7 +154,7 @@ def load():
     L.gmk_az_live_games.argtypes = [vp, C.POINTER(C.c_int32)]
     L.gmk_az_set_slots.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     L.gmk_az_advance.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_int32), vp]
-    L.gmk_az_add_root_noise.argtypes = [vp, C.c_float, C.c_float, C.c_uint64, C.c_uint32]
+    L.gmk_az_add_root_noise.argtypes = [vp, C.c_float, C.c_float, C.c_uint64, C.c_uint32, vp]
     L.gmk_az_set_option.argtypes = [vp, C.c_int, C.c_int]
     L.gmk_az_add_playouts.argtypes = [vp, C.c_int, vp]
     L.gmk_az_playouts_owed.argtypes = [vp, C.POINTER(C.c_int32), vp]
@@ -178,7 +178,7 @@ def load():
     L.gmk_mcts_ensemble_merge.argtypes = [vp, C.c_int] + [vp] * 8
     L.gmk_trad_ensemble_merge.argtypes = [vp, C.c_int] + [vp] * 8
     L.gmk_ensemble_merge_host.argtypes = [C.c_int, C.c_int] + [vp] * 10
-    L.gmk_trad_add_root_noise.argtypes = [vp, C.c_float, C.c_float, C.c_uint64, C.c_uint32]
+    L.gmk_trad_add_root_noise.argtypes = [vp, C.c_float, C.c_float, C.c_uint64, C.c_uint32, vp]
     L.gmk_trad_set_option.argtypes = [vp, C.c_int, C.c_int]
     L.gmk_trad_root_stats.argtypes = [vp] * 10
     L.gmk_trad_read_evaluators.argtypes = [vp, vp, vp, vp, vp, vp, vp]
@@ -1091,8 +1091,9 @@ class TraditionalMCTS:
         """gmk_trad_ensemble_merge: BatchedMCTS.ensemble_merge for a K6 / K6 + RAVE / K8 handle."""
         _ensemble_merge(load().gmk_trad_ensemble_merge, self, group, visits, values, cells, cells_per_game, root_visits, root_value, status, stream)
 
-    def add_root_noise(self, alpha=0.05, epsilon=0.25, seed=DEFAULT_SEED, first_game_id=0):
-        _check(load().gmk_trad_add_root_noise(self.h, alpha, epsilon, seed, first_game_id))
+    def add_root_noise(self, alpha=0.05, epsilon=0.25, seed=DEFAULT_SEED, first_game_id=0, stream=None):
+        """gmk_trad_add_root_noise on `stream` (default: torch's current stream): the counter sampler is one launch there, the std sampler waits for it."""
+        _check(load().gmk_trad_add_root_noise(self.h, alpha, epsilon, seed, first_game_id, _current_stream(stream)))
 
     _POOLRAVE = 0
 
@@ -1155,8 +1156,8 @@ class PoolRAVEMCTS(TraditionalMCTS):
     def run(self, playouts, stream=0):
         _check(load().gmk_trad_run_poolrave(self.h, int(playouts), self.c_puct, self.seed, self.first_game_id, stream))
 
-    def add_root_noise(self, alpha=0.05, epsilon=0.25, seed=None, first_game_id=None):
-        super().add_root_noise(alpha, epsilon, self.seed if seed is None else seed, self.first_game_id if first_game_id is None else first_game_id)
+    def add_root_noise(self, alpha=0.05, epsilon=0.25, seed=None, first_game_id=None, stream=None):
+        super().add_root_noise(alpha, epsilon, self.seed if seed is None else seed, self.first_game_id if first_game_id is None else first_game_id, stream)
 
     def root_stats(self):
         out = super().root_stats()
@@ -1321,8 +1322,9 @@ class AlphaZeroMCTS:
         self._refresh_live()
         return unfinished.value
 
-    def add_root_noise(self, alpha=0.05, epsilon=0.25, seed=DEFAULT_SEED, first_game_id=0):
-        _check(load().gmk_az_add_root_noise(self.h, alpha, epsilon, seed, first_game_id))
+    def add_root_noise(self, alpha=0.05, epsilon=0.25, seed=DEFAULT_SEED, first_game_id=0, stream=None):
+        """gmk_az_add_root_noise on `stream` (default: torch's current stream): the counter sampler is one launch there, the std sampler waits for it."""
+        _check(load().gmk_az_add_root_noise(self.h, alpha, epsilon, seed, first_game_id, _current_stream(stream)))
 
     def set_option(self, option, value):
         """gmk_az_set_option: OPT_NOISE_SAMPLER -> NOISE_SAMPLERS["std" | "counter"]; OPT_AZ_LEAVES -> 1 .. AZ_MAX_LEAVES leaves per game per step;

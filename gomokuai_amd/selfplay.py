@@ -402,7 +402,7 @@ def play_supervisor_games(n_games, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, fi
         if ply == 0 or not reuse_subtree:
             tree.set_positions(games.moves, games.lens)
         if root_noise is not None:
-            tree.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id)
+            tree.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id, stream=stream)
         tree.run(playouts, stream)
         st = tree.root_stats()
         overflow |= bool((st["status"] & G.TraditionalMCTS.STATUS_ARENA_FULL).any())
@@ -451,7 +451,7 @@ def _play_supervisor_slots(n_games, slots, playouts, c_puct, seed, first_game_id
             tree.set_positions(games.moves[active], np.where(fresh, games.lens[active], -1))
         fresh[:] = False
         if root_noise is not None:
-            tree.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id)
+            tree.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id, stream=stream)
         tree.run(playouts, stream)
         st = tree.root_stats()
         overflow |= bool((st["status"] & G.TraditionalMCTS.STATUS_ARENA_FULL).any())
@@ -782,9 +782,9 @@ class _EvalOpponent:
         self.tree.set_game_ids(np.asarray(idx, dtype=np.uint32))
         self.tree.set_positions(moves, lens)
 
-    def add_root_noise(self, root_noise):
+    def add_root_noise(self, root_noise, stream=None):
         if root_noise is not None and self.tree is not None:
-            self.tree.add_root_noise(root_noise[0], root_noise[1], seed=self.seed, first_game_id=self.first)
+            self.tree.add_root_noise(root_noise[0], root_noise[1], seed=self.seed, first_game_id=self.first, stream=stream)
 
     def overflow(self):
         return self.tree is not None and bool((self.tree.root_stats()["status"] & G.TraditionalMCTS.STATUS_ARENA_FULL).any())
@@ -868,7 +868,7 @@ def play_evaluation_games(n_games, network, opponent, playouts=400, c_puct=5.0, 
                         net.search(network, playouts)
                         net.root_choice(d_cells, d_rows)
                     else:
-                        opp.add_root_noise(root_noise)
+                        opp.add_root_noise(root_noise, stream)
                         opp.tree.run(opp.playouts, stream)
                         opp.tree.root_choice(d_cells, d_rows)
                     G.match_referee(d_cells, d_rows, d_idx, d_moves, d_lens, d_winner, d_visits, d_verdict, d_status, d_unfinished)
@@ -897,7 +897,7 @@ def play_evaluation_games(n_games, network, opponent, playouts=400, c_puct=5.0, 
                     else:
                         if ply > 0 and not reuse_subtree:
                             opp.tree.set_positions(games.moves[idx], games.lens[idx])
-                        opp.add_root_noise(root_noise)
+                        opp.add_root_noise(root_noise, stream)
                         opp.tree.run(opp.playouts, stream)
                         st = opp.tree.root_stats()
                         v, best = st["visits"], st["best"]

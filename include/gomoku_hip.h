@@ -10,7 +10,11 @@
  * Conventions
  *   - every function returns 0 on success, a negative gmk_status otherwise; gmk_last_error() has text;
  *   - `d_` pointers are DEVICE (HBM) pointers, `h_` pointers are host pointers;
- *   - `stream` is a hipStream_t passed as void* (NULL = the default stream); calls are asynchronous on it;
+ *   - `stream` is a hipStream_t passed as void* (NULL = the default stream); calls are asynchronous on it: an entry that takes a
+ *     `stream` does all of its device work on that stream, and one that returns host values waits for that stream first;
+ *   - an entry WITHOUT a `stream` that reads or writes a handle is ordered after everything already enqueued for that handle, on any
+ *     stream (it waits for the device at its head), and has finished when it returns (gmk_mcts_root_stats and gmk_mcts_alg_bytes
+ *     wait for the stream of the handle's last call instead);
  *   - there is no CPU fallback: without a usable HIP device every compute entry returns GMK_ERR_NO_DEVICE.
  *
  * Board encoding (replaces Board::m_moveStates, core/lib/include/Game.h:146-150)
@@ -214,7 +218,9 @@ int gmk_mcts_set_option(gmk_mcts *m, int option, int value);
 /* The handle's tree arenas, now: one arena per game (what the first gmk_mcts_set_roots allocates) or, two_arenas != 0, the two arenas per game of
  * the persistent loop with kept subtrees (what gmk_selfplay_run allocates).  Tens of GB, and the driver clears memory it has handed out before
  * (seconds per 24 GB): for callers that want that outside a region they time, or want the blocks in the library's pool before a batch starts
- * (create, reserve, destroy: the next handle of that shape finds them there). */
+ * (create, reserve, destroy: the next handle of that shape finds them there).  two_arenas != 0 loses the trees, also on a handle that has its
+ * two arenas already (a lock-step gmk_mcts_step with reuse_subtree may have left the live trees in the other half): gmk_mcts_run,
+ * gmk_mcts_root_stats and the other calls that want roots return GMK_ERR_STATE until the next gmk_mcts_set_roots. */
 int gmk_mcts_reserve(gmk_mcts *m, int two_arenas);
 /* Root statistics after a run (synchronises the stream used by the last run):
  *   h_visits uint32[n][225] child visit counts by cell (MCTS::evalState, MCTS.cpp:104-110),
@@ -403,8 +409,11 @@ int gmk_trad_step(gmk_trad* t, const int16_t* h_moves);
  * fresh_root != 0 leaves a moved game as gmk_trad_set_positions would leave it for the position after the move (a new root at the next search). */
 int gmk_trad_root_choice(gmk_trad* t, int16_t* d_cells, uint16_t* d_visits, void* stream);
 int gmk_trad_step_device(gmk_trad* t, const int16_t* d_cells, const int32_t* d_verdict, int fresh_root, void* stream);
-/* Default::AddNoise on every root with children (the reference does this at the start of every search, MCTS.cpp:182) */
-int gmk_trad_add_root_noise(gmk_trad* t, float alpha, float epsilon, uint64_t seed, uint32_t first_game_id);
+/* Default::AddNoise on every root with children (the reference does this at the start of every search, MCTS.cpp:182).
+ * GMK_NOISE_SAMPLER_COUNTER: one launch on `stream`, behind the search or step that made the root's children; the call does not wait.
+ * GMK_NOISE_SAMPLER_STD: the draws are the host's, so the call waits for `stream`, reads the priors back and returns with the new ones
+ * written (synchronises `stream` and the device). */
+int gmk_trad_add_root_noise(gmk_trad* t, float alpha, float epsilon, uint64_t seed, uint32_t first_game_id, void* stream);
 /* TraditionalPolicy(c_puct, use_rave = true) (agents/mcts.py:44-47): gmk_trad_run's playout with RAVE::BackPropogate<true> in place of
  * <false> (MonteCarlo.hpp:113-184).  At every level of the backup each child whose cell the LEAF position holds for the child's player
  * (the root position plus the path; there is no rollout) takes -value into its all-moves-as-first statistics, and the children are ranked
@@ -509,10 +518,14 @@ int gmk_az_step_device(gmk_az* a, const int16_t* d_cells, const int32_t* d_verdi
 int gmk_az_set_slots(gmk_az* a, int n_total, const uint8_t* h_open_moves, int open_stride, const int32_t* h_open_lens);
 int gmk_az_advance(gmk_az* a, uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int reuse_subtree, int32_t* h_unfinished,
                    void* stream);
-/* Default::AddNoise on every root with children (core/lib/include/algorithms/MonteCarlo.hpp:97-108); the stream of slot g is keyed
- * by first_game_id + ids[g], ids as set by gmk_az_set_game_ids (uint32[n], host; default: the slot number) */
+/* Default::AddNoise on every root with children (core/lib/include/algorithms/MonteCarlo.hpp:97-108); the random stream of slot g is keyed
+ * by first_game_id + ids[g], ids as set by gmk_az_set_game_ids (uint32[n], host; default: the slot number; the call waits for the device
+ * and uploads them).
+ * GMK_NOISE_SAMPLER_COUNTER: one launch on `stream`, behind the gmk_az_expand / gmk_az_advance that made the root's children and before
+ * the next gmk_az_select on it; the call does not wait.  GMK_NOISE_SAMPLER_STD: the draws are the host's, so the call waits for `stream`,
+ * reads the priors back and returns with the new ones written (synchronises `stream` and the device). */
 int gmk_az_set_game_ids(gmk_az* a, const uint32_t* h_ids);
-int gmk_az_add_root_noise(gmk_az* a, float alpha, float epsilon, uint64_t seed, uint32_t first_game_id);
+int gmk_az_add_root_noise(gmk_az* a, float alpha, float epsilon, uint64_t seed, uint32_t first_game_id, void* stream);
 /* GMK_OPT_NOISE_SAMPLER for a K7 handle (see gmk_mcts_set_option): GMK_NOISE_SAMPLER_COUNTER draws the noise on the device, one wavefront per game.
  * GMK_OPT_AZ_LEAVES = L in 1 .. GMK_AZ_MAX_LEAVES (GMK_ERR_ARG otherwise; default 1): leaves per game per step, with virtual loss.
  *   L = 1: gmk_az_select / gmk_az_expand are the one-leaf kernels, one playout per step.

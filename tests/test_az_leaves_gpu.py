@@ -246,7 +246,7 @@ def test_misuse_is_refused_and_the_handle_goes_on():
     assert L.gmk_az_step_device(tree.h, d_cells.data_ptr(), d_verdict.data_ptr(), 0, None, None, stream) == ERR_STATE
     assert L.gmk_az_set_option(tree.h, G.OPT_AZ_LEAVES, 2) == ERR_STATE
     assert L.gmk_az_set_option(tree.h, G.OPT_NOISE_SAMPLER, 1) == ERR_STATE
-    assert L.gmk_az_add_root_noise(tree.h, 0.05, 0.25, 1, 0) == ERR_STATE
+    assert L.gmk_az_add_root_noise(tree.h, 0.05, 0.25, 1, 0, stream) == ERR_STATE
     assert L.gmk_az_select(tree.h, tree.states.data_ptr(), stream) == ERR_STATE
     assert b"gmk_az_expand" in L.gmk_last_error()
     values, probs = network(states)

@@ -249,3 +249,42 @@ def test_reserved_arenas_serve_the_lock_step_calls_too():
     for other in out[1:]:
         for a, b in zip(out[0], other):
             assert (a == b).all()
+
+
+def test_reserve_on_a_paired_and_rooted_handle_unroots_it():
+    """gmk_mcts_reserve(two_arenas) on a handle that is already paired and rooted points the arenas back at the halves of the block; a lock-step
+    gmk_mcts_step with reuse_subtree has left the live trees in the other half, so the handle must not pass for rooted: gmk_mcts_run and
+    gmk_mcts_root_stats return GMK_ERR_STATE until gmk_mcts_set_roots, and a search after that is a fresh handle's, bit for bit."""
+    import torch
+    ERR_STATE = -4
+    L = G.load()
+    n, playouts = 6, 40
+    moves, lens, planes, last = _openings(n, 3, first=77)
+    dev = torch.device("cuda", 0)
+    d_moves = torch.zeros((n, 225), dtype=torch.uint8, device=dev); d_lens = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_winner = torch.zeros(n, dtype=torch.int8, device=dev); d_unfinished = torch.zeros(1, dtype=torch.int32, device=dev)
+    forced = torch.full((n,), -1, dtype=torch.int16, device=dev)
+    t = G.BatchedMCTS(n, node_capacity=3 * playouts * 225 + 1)
+    t.reserve(two_arenas=True)
+    t.set_roots(planes, last, first_game_id=5)
+    t.run(playouts)
+    t.step(forced.data_ptr(), d_moves.data_ptr(), None, d_lens.data_ptr(), d_winner.data_ptr(), d_unfinished.data_ptr(), reuse_subtree=True)
+    torch.cuda.synchronize()
+    t.reserve(two_arenas=True)                                   # the arenas are re-pointed: the trees of the step are in the other half
+    out = [np.zeros((n, 225), np.uint32), np.zeros(n, np.float32), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.int32)]
+    assert L.gmk_mcts_run(t.h, playouts, None) == ERR_STATE
+    assert b"gmk_mcts_set_roots" in L.gmk_last_error()
+    assert L.gmk_mcts_root_stats(t.h, *[a.ctypes.data for a in out]) == ERR_STATE
+    assert not any(a.any() for a in out)
+    t.set_roots(planes, last, first_game_id=5)
+    t.run(playouts)
+    got = t.root_stats()
+    t.close()
+    fresh = G.BatchedMCTS(n, node_capacity=3 * playouts * 225 + 1)
+    fresh.set_roots(planes, last, first_game_id=5)
+    fresh.run(playouts)
+    want = fresh.root_stats()
+    fresh.close()
+    for a, b in zip(got, want):
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+    assert (want[2] == playouts).all()
