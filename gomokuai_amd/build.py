@@ -24,7 +24,8 @@ def _stale(target, sources):
         return True
     t = os.path.getmtime(target)
     deps = list(sources) + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    deps.append(os.path.join(os.path.dirname(HERE), "include", "gomoku_hip.h"))
+    include = os.path.join(os.path.dirname(HERE), "include")
+    deps += [os.path.join(include, f) for f in ("gomoku_hip.h", "gomoku_noise.h", "gomoku_sample.h")]
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 

@@ -35,6 +35,7 @@
 #include "root_noise.h"
 #include "noise_device.h"
 #include "vcf_device.h"
+#include "../../include/gomoku_sample.h"
 
 namespace {
 
@@ -209,6 +210,74 @@ __device__ __forceinline__ uint32_t most_visited_child(const uint2* kids, const 
     best_i = __shfl(best_i, 0);
     if constexpr (kProof) proof_choice(kids, stat, first, n, lane, best_v, best_i);
     return best_i;
+}
+// K20: the first sample_plies plies of a self-play game are drawn in proportion to visits^power (include/gomoku_sample.h has the rule and its
+// serial statement, gmk_sample_choose225).  The kernels that take it are the instantiations with one AzSample among their arguments.
+struct AzSample {
+    const int32_t* slot_game;                    // [n_games] the game a slot plays under gmk_az_set_slots, otherwise null and
+    const uint32_t* game_ids;                    // [n_games] the game it plays by gmk_az_set_game_ids
+    uint32_t first_game_id, seed_lo, seed_hi;
+    uint32_t plies;                              // S > 0
+    int power;                                   // k in 1..3
+};
+// The game whose stream a slot draws from, as az_root_noise_kernel names it
+__device__ __forceinline__ uint32_t sample_game_id(const AzSample& sm, int slot) {
+    return sm.first_game_id + (sm.slot_game ? static_cast<uint32_t>(max(sm.slot_game[slot], 0)) : sm.game_ids[slot]);
+}
+// The child a sampled ply plays, called as most_visited_child is and with its result: on a root with `stones` >= S stones, or without weight, it
+// IS most_visited_child.  Lane l holds the children 4 l .. 4 l + 3, so child order is lane order: the weights stay in registers, one inclusive
+// scan of the lanes' 64-bit sums (six shuffles of two words) gives every lane the prefix before its first child, and the first lane with a
+// prefix above the target holds the choice.
+template <bool kProof>
+__device__ __forceinline__ uint32_t sampled_child(const uint2* kids, const uint2* stat, uint32_t first, uint32_t n, int lane, const AzSample& sm, uint32_t game_id,
+                                                  uint32_t stones) {
+    if (stones >= sm.plies) return most_visited_child<kProof>(kids, stat, first, n, lane);
+    uint64_t w[4], sum = 0;
+    uint32_t lose_i = 0xFFFFFFFFu;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t i = 4u * lane + j;
+        w[j] = 0;
+        if (i < n) {
+            w[j] = gmk_sample_weight(stat[first + i].x, sm.power);
+            if constexpr (kProof) {
+                const uint32_t pr = proof_of(kids[first + i].y);
+                if (pr == GMK_AZ_PROOF_LOSES) lose_i = min(lose_i, i);
+                if (pr == GMK_AZ_PROOF_WINS) w[j] = 0;
+            }
+        }
+        sum += w[j];
+    }
+    if constexpr (kProof) {                                      // a proven win is played, not drawn: the first one, which the first such lane holds
+        const unsigned long long lost = __ballot(lose_i != 0xFFFFFFFFu);
+        if (lost != 0ull) return __shfl(lose_i, __ffsll(static_cast<long long>(lost)) - 1);
+    }
+    uint64_t incl = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t below = __shfl_up(static_cast<unsigned long long>(incl), d);
+        if (lane >= d) incl += below;
+    }
+    const uint64_t total = __shfl(static_cast<unsigned long long>(incl), 63);
+    if (total == 0) return most_visited_child<kProof>(kids, stat, first, n, lane);
+    const uint64_t target = gmk_sample_target(total, game_id, stones, sm.seed_lo, sm.seed_hi);
+    uint64_t prefix = incl - sum;
+    uint32_t hit = 0xFFFFFFFFu;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        prefix += w[j];
+        if (hit == 0xFFFFFFFFu && prefix > target) hit = 4u * lane + j;
+    }
+    const unsigned long long hits = __ballot(hit != 0xFFFFFFFFu);                      // (never empty: target < total)
+    return __shfl(hit, __ffsll(static_cast<long long>(hits)) - 1);
+}
+// The root choice of a kernel instantiated without an AzSample (most_visited_child, and nothing more is read) or with one (sampled_child for
+// the game that slot `slot` plays, at the stones of its header)
+template <bool kProof, class... Sample>
+__device__ __forceinline__ uint32_t root_child(const uint2* kids, const uint2* stat, uint32_t first, uint32_t n, int lane, const AzHeader& hdr, int slot, const Sample&... sm) {
+    static_assert(sizeof...(Sample) <= 1 && (std::is_same_v<Sample, AzSample> && ...), "at most one AzSample");
+    if constexpr (sizeof...(Sample) == 1) return sampled_child<kProof>(kids, stat, first, n, lane, sm..., sample_game_id(sm..., slot), hdr.stones);
+    else return most_visited_child<kProof>(kids, stat, first, n, lane);
 }
 // The root's child of `cell` (children are in ascending cell order: at most one), 0xFFFFFFFF when there is none; the same in every lane.
 __device__ __forceinline__ uint32_t child_of_cell(const uint2* kids, uint32_t first, uint32_t n, uint32_t cell, int lane) {
@@ -965,10 +1034,11 @@ void az_step_kernel(AzTree t, AzArena b, const int16_t* forced) {
 // game goes on, and the tree is re-rooted: the child's subtree into the other arena (reuse) or a new root.  A root without a visited
 // child ends the game where it stands.  Finished games leave a childless root behind in both arenas, so that no kernel ever walks a
 // stale tree.  One wavefront per game.
-template <bool kProof>
+// Sample: nothing, or one AzSample (K20): the plies before its S are drawn by sampled_child, and nothing else changes.
+template <bool kProof, class... Sample>
 __global__ __launch_bounds__(64)
 void az_advance_kernel(AzTree t, AzArena b, uint8_t* __restrict__ rec_moves, uint16_t* __restrict__ rec_visits, int32_t* __restrict__ rec_lens,
-                       int8_t* __restrict__ rec_winner, int32_t* __restrict__ unfinished, int reuse, AzSlots sl) {
+                       int8_t* __restrict__ rec_winner, int32_t* __restrict__ unfinished, int reuse, AzSlots sl, Sample... sm) {
     __shared__ uint32_t s_rows[16];
     const int slot = blockIdx.x, lane = threadIdx.x;
     if (slot >= t.n_games) return;
@@ -981,7 +1051,7 @@ void az_advance_kernel(AzTree t, AzArena b, uint8_t* __restrict__ rec_moves, uin
     }
     const uint2 rk = t.kids[base];
     const uint32_t first = rk.x, n = rk.y & 0xFFu;
-    const uint32_t best_i = most_visited_child<kProof>(t.kids + base, t.stat + base, first, n, lane);
+    const uint32_t best_i = root_child<kProof>(t.kids + base, t.stat + base, first, n, lane, hdr, slot, sm...);
     const uint32_t stones = hdr.stones;
     const int len = rec_lens[game];
     bool over = best_i == 0xFFFFFFFFu || stones >= 225u || len >= 225;                 // nothing the search wants to play
@@ -1128,15 +1198,16 @@ void az_root_noise_kernel(AzTree t, const int32_t* __restrict__ slot_game, const
 // The cell MCTS::stepForward() would play for every game, left ON THE DEVICE for the match referee (match_kernel.hip): the most visited root
 // child, first maximum in child (= cell) order, exactly az_advance_kernel's choice; -1 for a root without a visited child.  visits (may be
 // null): the root children's visit counts by cell, saturated like the records' rows.  One wavefront per game.
-template <bool kProof>
+// Sample: nothing, or one AzSample (K20): az_advance_kernel's sampled choice.
+template <bool kProof, class... Sample>
 __global__ __launch_bounds__(64)
-void az_root_choice_kernel(AzTree t, int16_t* __restrict__ cells, uint16_t* __restrict__ visits) {
+void az_root_choice_kernel(AzTree t, int16_t* __restrict__ cells, uint16_t* __restrict__ visits, Sample... sm) {
     const int game = blockIdx.x, lane = threadIdx.x;
     if (game >= t.n_games) return;
     const size_t base = static_cast<size_t>(game) * t.cap;
     const uint2 rk = t.kids[base];
     const uint32_t first = rk.x, n = rk.y & 0xFFu;
-    const uint32_t best_i = most_visited_child<kProof>(t.kids + base, t.stat + base, first, n, lane);
+    const uint32_t best_i = root_child<kProof>(t.kids + base, t.stat + base, first, n, lane, t.hdr[game], game, sm...);
     if (lane == 0) cells[game] = best_i == 0xFFFFFFFFu ? static_cast<int16_t>(-1) : static_cast<int16_t>((t.kids[base + first + best_i].y >> 8) & 0xFFu);
     if (visits) visits_by_cell(visits + static_cast<size_t>(game) * kCells, t.kids + base, t.stat + base, first, n, lane);
 }
@@ -1609,13 +1680,41 @@ extern "C" int gmk_az_step(gmk_az* a, const int16_t* h_moves) {
     return GMK_OK;
 }
 
-extern "C" int gmk_az_root_choice(gmk_az* a, int16_t* d_cells, uint16_t* d_visits, void* stream) {
-    if (!a || !d_cells) { gmk::set_error("gmk_az_root_choice: bad arguments"); return GMK_ERR_ARG; }
-    if (!a->rooted) { gmk::set_error("gmk_az_root_choice: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
-    const auto kernel = az_proof_variant(a, [](auto proof) { return &az_root_choice_kernel<proof>; });
-    hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_cells, d_visits);
+// K20: the arguments of the two sampled entries, checked, as the kernels take them; plies == 0 when nothing is to be sampled
+static int az_sample_args(const gmk_az* a, const char* who, int sample_plies, int sample_power, uint64_t seed, uint32_t first_game_id, AzSample* sm) {
+    if (sample_plies < 0 || sample_plies > kCells || sample_power < 1 || sample_power > GMK_SAMPLE_MAX_POWER) {
+        gmk::set_error("%s: sample_plies takes 0 .. 225 and sample_power 1 .. %d, not %d and %d", who, GMK_SAMPLE_MAX_POWER, sample_plies, sample_power);
+        return GMK_ERR_ARG;
+    }
+    *sm = AzSample{a->slots.slot_game, a->d_game_ids, first_game_id, static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), static_cast<uint32_t>(sample_plies), sample_power};
+    return GMK_OK;
+}
+
+// gmk_az_root_choice and gmk_az_root_choice_sampled (sm: null, or what is to be sampled): one launch on `stream`
+static int az_root_choice(gmk_az* a, const char* who, int16_t* d_cells, uint16_t* d_visits, const AzSample* sm, void* stream) {
+    if (!a->rooted) { gmk::set_error("%s: gmk_az_set_roots has not been called", who); return GMK_ERR_STATE; }
+    if (sm && sm->plies != 0u) {
+        const auto kernel = az_proof_variant(a, [](auto proof) { return &az_root_choice_kernel<proof, AzSample>; });
+        hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_cells, d_visits, *sm);
+    } else {
+        const auto kernel = az_proof_variant(a, [](auto proof) { return &az_root_choice_kernel<proof>; });
+        hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_cells, d_visits);
+    }
     GMK_HIP_CHECK(hipGetLastError());
     return GMK_OK;
+}
+
+extern "C" int gmk_az_root_choice(gmk_az* a, int16_t* d_cells, uint16_t* d_visits, void* stream) {
+    if (!a || !d_cells) { gmk::set_error("gmk_az_root_choice: bad arguments"); return GMK_ERR_ARG; }
+    return az_root_choice(a, "gmk_az_root_choice", d_cells, d_visits, nullptr, stream);
+}
+
+extern "C" int gmk_az_root_choice_sampled(gmk_az* a, int16_t* d_cells, uint16_t* d_visits, int sample_plies, int sample_power, uint64_t seed, uint32_t first_game_id,
+                                          void* stream) {
+    if (!a || !d_cells) { gmk::set_error("gmk_az_root_choice_sampled: bad arguments"); return GMK_ERR_ARG; }
+    AzSample sm{};
+    if (const int rc = az_sample_args(a, "gmk_az_root_choice_sampled", sample_plies, sample_power, seed, first_game_id, &sm); rc != GMK_OK) return rc;
+    return az_root_choice(a, "gmk_az_root_choice_sampled", d_cells, d_visits, &sm, stream);
 }
 
 // gmk_az_step from device memory, on the caller's stream (az_step_device_kernel), then the leaf batch is compacted as gmk_az_advance
@@ -1639,25 +1738,63 @@ extern "C" int gmk_az_step_device(gmk_az* a, const int16_t* d_cells, const int32
     return GMK_OK;
 }
 
-// One self-play move of every game still played (az_advance_kernel).  h_unfinished: the games that go on.
-extern "C" int gmk_az_advance(gmk_az* a, uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int reuse_subtree, int32_t* h_unfinished,
-                              void* stream) {
-    if (!a || !d_moves || !d_lens || !d_winner) { gmk::set_error("gmk_az_advance: bad arguments"); return GMK_ERR_ARG; }
-    if (!a->rooted) { gmk::set_error("gmk_az_advance: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
-    if (az_marks_up(a, "gmk_az_advance")) return GMK_ERR_STATE;
+// One self-play move of every game still played (az_advance_kernel).  h_unfinished: the games that go on.  sm: null (gmk_az_advance), or what
+// gmk_az_advance_sampled is to sample.
+static int az_advance(gmk_az* a, const char* who, uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int reuse_subtree, const AzSample* sm,
+                      int32_t* h_unfinished, void* stream) {
+    if (!a->rooted) { gmk::set_error("%s: gmk_az_set_roots has not been called", who); return GMK_ERR_STATE; }
+    if (az_marks_up(a, who)) return GMK_ERR_STATE;
     if (reuse_subtree)
         if (const int rc = az_second_arena(a); rc != GMK_OK) return rc;
     if (!a->d_unfinished) GMK_HIP_CHECK(gmk::device_malloc(&a->d_unfinished, 4));
     hipStream_t s = static_cast<hipStream_t>(stream);
     GMK_HIP_CHECK(hipMemsetAsync(a->d_unfinished, 0, 4, s));
-    const auto kernel = az_proof_variant(a, [](auto proof) { return &az_advance_kernel<proof>; });
-    hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, s, a->t, a->other, d_moves, d_visits, d_lens, d_winner, a->d_unfinished, reuse_subtree ? 1 : 0, a->slots);
+    if (sm && sm->plies != 0u) {
+        const auto kernel = az_proof_variant(a, [](auto proof) { return &az_advance_kernel<proof, AzSample>; });
+        hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, s, a->t, a->other, d_moves, d_visits, d_lens, d_winner, a->d_unfinished, reuse_subtree ? 1 : 0, a->slots, *sm);
+    } else {
+        const auto kernel = az_proof_variant(a, [](auto proof) { return &az_advance_kernel<proof>; });
+        hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, s, a->t, a->other, d_moves, d_visits, d_lens, d_winner, a->d_unfinished, reuse_subtree ? 1 : 0, a->slots);
+    }
     GMK_HIP_CHECK(hipGetLastError());
     int32_t unfinished = 0;
     GMK_HIP_CHECK(hipMemcpyAsync(&unfinished, a->d_unfinished, 4, hipMemcpyDeviceToHost, s));
     if (const int rc = az_compact(a, s); rc != GMK_OK) return rc;   // (synchronises: both numbers are here now, and they agree)
     if (reuse_subtree) az_flip_arenas(a);
     if (h_unfinished) *h_unfinished = unfinished;
+    return GMK_OK;
+}
+
+extern "C" int gmk_az_advance(gmk_az* a, uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int reuse_subtree, int32_t* h_unfinished,
+                              void* stream) {
+    if (!a || !d_moves || !d_lens || !d_winner) { gmk::set_error("gmk_az_advance: bad arguments"); return GMK_ERR_ARG; }
+    return az_advance(a, "gmk_az_advance", d_moves, d_visits, d_lens, d_winner, reuse_subtree, nullptr, h_unfinished, stream);
+}
+
+extern "C" int gmk_az_advance_sampled(gmk_az* a, uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int reuse_subtree, int sample_plies,
+                                      int sample_power, uint64_t seed, uint32_t first_game_id, int32_t* h_unfinished, void* stream) {
+    if (!a || !d_moves || !d_lens || !d_winner) { gmk::set_error("gmk_az_advance_sampled: bad arguments"); return GMK_ERR_ARG; }
+    AzSample sm{};
+    if (const int rc = az_sample_args(a, "gmk_az_advance_sampled", sample_plies, sample_power, seed, first_game_id, &sm); rc != GMK_OK) return rc;
+    return az_advance(a, "gmk_az_advance_sampled", d_moves, d_visits, d_lens, d_winner, reuse_subtree, &sm, h_unfinished, stream);
+}
+
+// The rule of include/gomoku_sample.h for n roots given by rows, on the host: needs no GPU and no gmk_init
+extern "C" int gmk_move_sample_host(const uint32_t* h_visits, const int8_t* h_proofs, const int32_t* h_stones, const uint32_t* h_game_ids, int n, int sample_plies,
+                                    int sample_power, uint64_t seed, int16_t* h_cells) {
+    static_assert(GMK_SAMPLE_PROOF_WINS == GMK_AZ_PROOF_WINS && GMK_SAMPLE_PROOF_LOSES == GMK_AZ_PROOF_LOSES, "gomoku_sample.h reads the proofs of gomoku_hip.h");
+    if (n < 0 || (n > 0 && (!h_visits || !h_stones || !h_game_ids || !h_cells)) || sample_plies < 0 || sample_plies > kCells || sample_power < 1 ||
+        sample_power > GMK_SAMPLE_MAX_POWER) {
+        gmk::set_error("gmk_move_sample_host: bad arguments (sample_plies 0 .. 225, sample_power 1 .. %d)", GMK_SAMPLE_MAX_POWER);
+        return GMK_ERR_ARG;
+    }
+    for (int g = 0; g < n; ++g)
+        if (h_stones[g] < 0 || h_stones[g] > kCells) { gmk::set_error("gmk_move_sample_host: row %d has %d stones", g, h_stones[g]); return GMK_ERR_ARG; }
+    for (int g = 0; g < n; ++g) {
+        h_cells[g] = static_cast<int16_t>(gmk_sample_choose225(h_visits + static_cast<size_t>(g) * kCells, h_proofs ? h_proofs + static_cast<size_t>(g) * kCells : nullptr,
+                                                               static_cast<uint32_t>(h_stones[g]), h_game_ids[g], sample_plies, sample_power, static_cast<uint32_t>(seed),
+                                                               static_cast<uint32_t>(seed >> 32)));
+    }
     return GMK_OK;
 }
 

@@ -65,6 +65,7 @@ EXPORTS = [
     "gmk_records_scan", "gmk_records_packed_bytes", "gmk_records_pack", "gmk_records_unpack", "gmk_samples_from_packed",
     "gmk_evalstate_create", "gmk_evalstate_destroy", "gmk_evalstate_reset", "gmk_evalstate_update", "gmk_evalstate_update_host", "gmk_evalstate_read",
     "gmk_az_create", "gmk_az_destroy", "gmk_az_set_roots", "gmk_az_select", "gmk_az_expand", "gmk_az_select_host", "gmk_az_expand_host", "gmk_az_read_node_host", "gmk_az_read_children_host", "gmk_az_set_leaf_host", "gmk_az_rollout_host", "gmk_az_expand_stages_host", "gmk_az_write_stats_host", "gmk_az_step", "gmk_az_root_choice", "gmk_az_step_device", "gmk_az_advance", "gmk_az_set_slots", "gmk_az_live_games", "gmk_az_set_game_ids", "gmk_az_add_root_noise", "gmk_az_set_option", "gmk_az_add_playouts", "gmk_az_playouts_owed", "gmk_az_root_stats", "gmk_az_vcf_stats", "gmk_az_vcf_verdicts_host", "gmk_az_defend_stats", "gmk_az_defend_verdicts_host", "gmk_az_root_proofs", "gmk_az_proof_stats",
+    "gmk_az_advance_sampled", "gmk_az_root_choice_sampled", "gmk_move_sample_host",
     "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_root_choice", "gmk_trad_step_device", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_run_rave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
     "gmk_pvnet_set_precision", "gmk_pvnet_get_precision", "gmk_bf16_round_host",
     "gmk_pattern_policy", "gmk_pattern_policy_host", "gmk_pattern_play",
@@ -154,6 +155,9 @@ def load():
     L.gmk_az_live_games.argtypes = [vp, C.POINTER(C.c_int32)]
     L.gmk_az_set_slots.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     L.gmk_az_advance.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_int32), vp]
+    L.gmk_az_advance_sampled.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_int32), vp]
+    L.gmk_az_root_choice_sampled.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp]
+    L.gmk_move_sample_host.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64, vp]
     L.gmk_az_add_root_noise.argtypes = [vp, C.c_float, C.c_float, C.c_uint64, C.c_uint32, vp]
     L.gmk_az_set_option.argtypes = [vp, C.c_int, C.c_int]
     L.gmk_az_add_playouts.argtypes = [vp, C.c_int, vp]
@@ -949,6 +953,31 @@ def _root_choice(entry, tree, cells, visits, stream):
     _check(entry(tree.h, cells.data_ptr(), None if visits is None else visits.data_ptr(), _current_stream(stream)))
 
 
+def _sample_args(sample):
+    """sample = (plies, power, seed, first_game_id) -> the four arguments of the sampled entries"""
+    plies, power, seed, first_game_id = sample
+    return int(plies), int(power), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_game_id) & 0xFFFFFFFF
+
+
+def move_sample_host(visits, stones, game_ids, plies, power, seed, proofs=None):
+    """gmk_move_sample_host: the cell each of n roots plays under the sampling rule of include/gomoku_sample.h, int16[n] (-1: none); needs no
+    GPU.  visits uint32[n, 225] by cell, not saturated (root_stats()["visits"]); stones int32[n] on the root boards; game_ids uint32[n], GLOBAL
+    (first_game_id + the game's number); plies, power: a root with fewer than `plies` stones is drawn in proportion to visits^power (1..3), any
+    other plays the most visited child; proofs int8[n, 225] (AlphaZeroMCTS.root_proofs()["children"]) or None."""
+    visits = np.ascontiguousarray(visits, dtype=np.uint32)
+    n = visits.shape[0]
+    stones = np.ascontiguousarray(stones, dtype=np.int32)
+    game_ids = np.ascontiguousarray(game_ids, dtype=np.uint32)
+    assert visits.shape == (n, N) and stones.shape == (n,) and game_ids.shape == (n,)
+    if proofs is not None:
+        proofs = np.ascontiguousarray(proofs, dtype=np.int8)
+        assert proofs.shape == (n, N)
+    cells = np.zeros(n, dtype=np.int16)
+    _check(load().gmk_move_sample_host(visits.ctypes.data, None if proofs is None else proofs.ctypes.data, stones.ctypes.data, game_ids.ctypes.data, n,
+                                       int(plies), int(power), int(seed) & 0xFFFFFFFFFFFFFFFF, cells.ctypes.data))
+    return cells
+
+
 def _check_step_device(tree, cells, verdict):
     import torch
     assert cells.is_cuda and cells.dtype == torch.int16 and cells.shape == (tree.n,) and cells.is_contiguous()
@@ -1279,10 +1308,15 @@ class AlphaZeroMCTS:
             assert m.shape == (self.n,)
             _check(load().gmk_az_step(self.h, m.ctypes.data))
 
-    def root_choice(self, cells, visits=None, stream=None):
+    def root_choice(self, cells, visits=None, stream=None, sample=None):
         """gmk_az_root_choice: the most visited root child (first maximum in cell order, -1 without one) into cells (torch int16[n] on the
-        GPU) and the root children's visit counts by cell, saturated at 65 535, into visits (2-byte torch [n, 225], or None)."""
-        _root_choice(load().gmk_az_root_choice, self, cells, visits, stream)
+        GPU) and the root children's visit counts by cell, saturated at 65 535, into visits (2-byte torch [n, 225], or None).
+        sample = (plies, power, seed, first_game_id): gmk_az_root_choice_sampled, the choice advance(sample=) makes."""
+        if sample is None:
+            _root_choice(load().gmk_az_root_choice, self, cells, visits, stream)
+        else:
+            args = _sample_args(sample)
+            _root_choice(lambda h, c, v, s: load().gmk_az_root_choice_sampled(h, c, v, *args, s), self, cells, visits, stream)
 
     def step_device(self, cells, verdict, fresh_root=False, unfinished=None, stream=None):
         """gmk_az_step_device: step() with the cells (torch int16[n]) and the referee's verdicts (torch int32[n], MATCH_*) on the GPU; games that
@@ -1307,18 +1341,24 @@ class AlphaZeroMCTS:
             _check(load().gmk_az_set_slots(self.h, int(n_total), m.ctypes.data, m.shape[1], l.ctypes.data))
         self._refresh_live()
 
-    def advance(self, moves, visits, lens, winner, reuse_subtree=True, stream=None):
+    def advance(self, moves, visits, lens, winner, reuse_subtree=True, stream=None, sample=None):
         """One self-play move for every game still played, on the device (gmk_az_advance): moves uint8[n,225], visits int16/uint16
         [n,225,225] or None, lens int32[n], winner int8[n] are torch tensors on the GPU (the games' records, openings included);
-        returns the number of games that go on."""
+        returns the number of games that go on.  sample = (plies, power, seed, first_game_id): gmk_az_advance_sampled -- a game with fewer
+        than `plies` stones on its root board plays a child drawn in proportion to visits^power (power 1..3; include/gomoku_sample.h), keyed by
+        seed and the game's global id as add_root_noise keys its draws; None: every game plays its most visited child."""
         import torch
         stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
         rows = getattr(self, "n_total", None) or self.n
         assert moves.dtype == torch.uint8 and moves.shape == (rows, N) and lens.dtype == torch.int32 and lens.shape == (rows,) and winner.dtype == torch.int8 and winner.shape == (rows,)
         assert visits is None or (visits.element_size() == 2 and visits.shape == (rows, N, N))
         unfinished = C.c_int32(0)
-        _check(load().gmk_az_advance(self.h, moves.data_ptr(), visits.data_ptr() if visits is not None else None, lens.data_ptr(), winner.data_ptr(),
-                                     int(bool(reuse_subtree)), C.byref(unfinished), stream))
+        if sample is None:
+            _check(load().gmk_az_advance(self.h, moves.data_ptr(), visits.data_ptr() if visits is not None else None, lens.data_ptr(), winner.data_ptr(),
+                                         int(bool(reuse_subtree)), C.byref(unfinished), stream))
+        else:
+            _check(load().gmk_az_advance_sampled(self.h, moves.data_ptr(), visits.data_ptr() if visits is not None else None, lens.data_ptr(), winner.data_ptr(),
+                                                 int(bool(reuse_subtree)), *_sample_args(sample), C.byref(unfinished), stream))
         self._refresh_live()
         return unfinished.value
 

@@ -493,9 +493,19 @@ def _root_choice(visits, proofs=None):
     return best
 
 
+def _sampled_choice(visits, proofs, stones, games, sample):
+    """_root_choice for the host-driven loops of play_network_games: with sample = (plies, power, seed, first_game_id) the choice
+    gmk_az_advance_sampled makes on the device (lib.move_sample_host), for roots with `stones` stones that belong to the games numbered `games`."""
+    if sample is None:
+        return _root_choice(visits, proofs)
+    plies, power, seed, first_game_id = sample
+    ids = (first_game_id + np.asarray(games, dtype=np.int64)) & 0xFFFFFFFF
+    return G.move_sample_host(visits, stones, ids, plies, power, seed, proofs).astype(np.int64)
+
+
 def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, first_game_id=0, opening_plies=0, max_moves=N,
                        device=None, node_capacity=None, reuse_subtree=True, root_noise=(0.05, 0.25), slots=None, device_loop=True, noise_sampler="counter", leaves=1,
-                       vcf=None, proof=False, vcf_defend=False):
+                       vcf=None, proof=False, vcf_defend=False, sample_plies=0, sample_power=1):
     """n_games complete games of the network-guided searcher against itself (agents/alphazero.py:5-9 on both sides: the
     reference's AlphaZero self-play), all games in lock step on the current GPU: every move = `playouts` lock-step playouts of
     K7 with `network(states [n,6,15,15]) -> (value [n], probs [n,225])` at the leaves (network.FusedPolicyValueNetwork = K9),
@@ -512,7 +522,13 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
     their trees and every loop chooses its moves by them (lib.AlphaZeroMCTS(proof=), _root_choice).  vcf_defend (with vcf and proof): the replies
     that lose to the opponent's forced win by fours are proven at the leaves (lib.AlphaZeroMCTS(vcf_defend=)); such a search spends its playouts
     below the few replies that hold, so a kept subtree stays nearly whole while the replies are forced: give node_capacity room (the records'
-    overflow says when an arena filled).  Returns GameRecords like play_games."""
+    overflow says when an arena filled).  sample_plies = S > 0: a game plays its first S plies (openings count) in proportion to
+    visits^sample_power (1, 2, 3: temperature 1, 1/2, 1/3) and its most visited child afterwards, AlphaZero's self-play schedule
+    (lib.AlphaZeroMCTS.advance(sample=), include/gomoku_sample.h): the draw is keyed by seed, the game's global id and its stone count, so
+    these too are the same games on every loop, and a record's visit row gives its move again.  Returns GameRecords like play_games."""
+    if not (0 <= int(sample_plies) <= N and 1 <= int(sample_power) <= 3):
+        raise ValueError("play_network_games: sample_plies takes 0 .. 225 and sample_power 1, 2 or 3")
+    sample = (int(sample_plies), int(sample_power), seed, first_game_id) if int(sample_plies) > 0 else None
     if slots is not None and slots < n_games and (max_moves < N or (device_loop and opening_plies > 8)):
         # (the slot loops play whole games, the device-resident one from openings of at most 8 plies -- gmk_az_set_slots' limit: say so instead of
         # ignoring the cap or failing inside the library; ADVICE r3)
@@ -540,7 +556,7 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
                 if root_noise is not None:
                     tree.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id)
                 tree.search(network, playouts)
-                if tree.advance(d_moves, d_visits, d_lens, d_winner, reuse_subtree) == 0:
+                if tree.advance(d_moves, d_visits, d_lens, d_winner, reuse_subtree, sample=sample) == 0:
                     break
         overflow = bool((tree.root_stats()["status"] & G.AlphaZeroMCTS.STATUS_ARENA_FULL).any())
         tree.close()
@@ -575,7 +591,8 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
                 st = tree.root_stats()
                 overflow |= bool((st["status"] & G.AlphaZeroMCTS.STATUS_ARENA_FULL).any())
                 visited = st["visits"].max(1) > 0
-                best = np.where(games.over[active] | ~visited, -1, _root_choice(st["visits"], tree.root_proofs()["children"] if proof else None))
+                best = np.where(games.over[active] | ~visited, -1,
+                                _sampled_choice(st["visits"], tree.root_proofs()["children"] if proof else None, games.lens[active], active, sample))
                 games.over[active[(best < 0) & ~games.over[active]]] = True
                 played = np.full(n_games, -1, dtype=np.int64)
                 played[active] = best
@@ -604,7 +621,7 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
                 if root_noise is not None:
                     tree.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id)
                 tree.search(network, playouts)
-                if tree.advance(d_moves, d_visits, d_lens, d_winner, reuse_subtree) == 0:
+                if tree.advance(d_moves, d_visits, d_lens, d_winner, reuse_subtree, sample=sample) == 0:
                     break
         overflow = bool((tree.root_stats()["status"] & G.AlphaZeroMCTS.STATUS_ARENA_FULL).any())
         tree.close()
@@ -623,7 +640,8 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
             st = tree.root_stats()
             overflow |= bool((st["status"] & G.AlphaZeroMCTS.STATUS_ARENA_FULL).any())
             visited = st["visits"].max(1) > 0                    # no child was visited: nothing to play (cannot happen on a live board)
-            played = np.where(games.over | ~visited, -1, _root_choice(st["visits"], tree.root_proofs()["children"] if proof else None)).astype(np.int16)
+            played = np.where(games.over | ~visited, -1,
+                              _sampled_choice(st["visits"], tree.root_proofs()["children"] if proof else None, games.lens, np.arange(n_games), sample)).astype(np.int16)
             games.over |= played < 0
             at = games.lens.copy()
             moved = games.apply(played)

@@ -21,6 +21,13 @@
  *   planes: uint16_t[n][2][16]   plane 0 = black stones, plane 1 = white stones,
  *           word y = row y, bit x = column x (x,y in 0..14), word 15 and bit 15 are zero.  64 B per board.
  *   Position id = y*15 + x (Game.h:45-56).  Player: -1 white, 0 none, +1 black (Game.h:19-21).
+ *
+ * Move choice in self-play
+ *   Every searcher plays its most visited root child, as MCTS::stepForward does (core/lib/src/MCTS.cpp:129-134).  The K7 self-play
+ *   entries can instead draw the first plies of a game in proportion to the visit counts (AlphaZero's temperature schedule):
+ *   gmk_az_advance_sampled, gmk_az_root_choice_sampled and, on the host, gmk_move_sample_host, see "K20" below.  The rule is integer
+ *   arithmetic on a counter-based stream keyed by the game and its stone count (gomoku_sample.h), so every loop plays the same games
+ *   and a record's visit row reproduces its move.  The unsampled entries, the K3 / K6 / K8 self-play loops and matches are unchanged.
  */
 #ifndef GOMOKU_HIP_H_
 #define GOMOKU_HIP_H_
@@ -672,6 +679,29 @@ int gmk_az_proof_stats(gmk_az* a, uint32_t* h_proved, uint32_t* h_stops);
  * The host-driven one-leaf entries that refuse a handle whose D > 0 refuse one whose GMK_OPT_AZ_VCF_DEFEND is 1 in the same way. */
 int gmk_az_defend_stats(gmk_az* a, uint32_t* h_threatened, uint32_t* h_marked, uint32_t* h_searched, uint64_t* h_nodes);
 int gmk_az_defend_verdicts_host(gmk_az* a, int32_t* h_threat_status, int32_t* h_threat_length, int8_t* h_verdict, uint32_t* h_nodes);
+/* ---- K20: self-play moves drawn from the root's visit counts, on the device ----
+ * The rule is stated once, in gomoku_sample.h: a root with fewer than sample_plies stones (openings included) plays child i with probability
+ * w_i / T, w_i = min(visits_i, 65535)^sample_power, through one draw of the counter-based stream keyed by (seed; global game id, stones,
+ * 'samp'); with GMK_OPT_AZ_PROOF the first child marked LOSES is played without a draw and children marked WINS weigh nothing; a root with
+ * sample_plies stones or more, or without weight, plays what gmk_az_advance plays.  sample_power 1, 2, 3 is temperature 1, 1/2, 1/3.
+ * The global game id of slot g is first_game_id + what gmk_az_add_root_noise's counter sampler uses: the game the slot plays under
+ * gmk_az_set_slots, otherwise ids[g] of gmk_az_set_game_ids (default g).
+ * gmk_az_advance_sampled / gmk_az_root_choice_sampled: gmk_az_advance / gmk_az_root_choice with that choice; everything else (records, visit
+ *   rows, re-rooting, the synchronisation of gmk_az_advance) is theirs, and so is GMK_ERR_STATE.  One launch on `stream`, nothing on any other.
+ *   sample_plies outside 0 .. 225 or sample_power outside 1 .. 3: GMK_ERR_ARG, and nothing is launched.  sample_plies = 0 launches exactly the
+ *   kernel the unsampled entry launches.
+ * gmk_move_sample_host: the rule for n roots given by rows, on the host (no GPU, no gmk_init): h_visits uint32[n][225] by cell, not saturated
+ *   (gmk_az_root_stats' visits), h_proofs int8[n][225] (gmk_az_root_proofs' children) or NULL, h_stones int32[n] in 0 .. 225, h_game_ids
+ *   uint32[n] GLOBAL ids; h_cells int16[n], -1 for a root that has nothing to play.  It equals the device entries cell for cell.
+ * Not sampled: gmk_selfplay_run and gmk_trad_selfplay_run (K3, K6 / K8), gmk_az_step, and evaluation matches, which play the most visited child;
+ * the policy target (gmk_visits_to_pi) is unchanged. */
+int gmk_az_advance_sampled(gmk_az* a, uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int reuse_subtree,
+                           int sample_plies, int sample_power, uint64_t seed, uint32_t first_game_id, int32_t* h_unfinished, void* stream);
+int gmk_az_root_choice_sampled(gmk_az* a, int16_t* d_cells, uint16_t* d_visits, int sample_plies, int sample_power,
+                               uint64_t seed, uint32_t first_game_id, void* stream);
+int gmk_move_sample_host(const uint32_t* h_visits /*[n][225], unsaturated*/, const int8_t* h_proofs /*[n][225] or NULL*/,
+                         const int32_t* h_stones, const uint32_t* h_game_ids /* already global */, int n,
+                         int sample_plies, int sample_power, uint64_t seed, int16_t* h_cells /* -1: none */);
 
 /* ---- K12: the referee of a match between two search handles, on the device (match_kernel.hip) ----
  * One ply of n two-agent games without the host in the loop (agents/utils.py:13-63 dual_play, :66-100 eval_agents): the side to move has
