@@ -69,7 +69,8 @@ class GameRecords:
             if t >= 2:
                 states[4, int(rec.moves[game, t - 2])] = 1
             states[5] = cur == 1
-            pi = G.visits_to_pi(rec.visits[game, t].numpy().astype(np.uint32), t)
+            counts = rec.visits[game, t].contiguous().view(torch.int16).numpy().view(np.uint16)     # uint16 carried as int16: 32 768 and above are not negative
+            pi = G.visits_to_pi(counts.astype(np.uint32), t)
             out.append((states.reshape(6, 15, 15), np.array(float(cur * winner)), pi))
             cell[int(rec.moves[game, t])] = cur
         return out
