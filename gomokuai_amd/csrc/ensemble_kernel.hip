@@ -239,7 +239,7 @@ extern "C" int gmk_trad_ensemble_merge(gmk_trad* t, int group, uint32_t* d_visit
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int n_ensembles = t->n_games / group;
     if (const int rc = clear_accumulator(&t->d_ensemble, &t->ensemble_capacity, n_ensembles, s, "gmk_trad_ensemble_merge"); rc != GMK_OK) return rc;
-    hipLaunchKernelGGL(ensemble_gather_trad_kernel, dim3(t->n_games), dim3(64), 0, s, t->arena(), t->d_hdr, t->d_moves, t->d_lens, t->cap, t->n_games, group,
+    hipLaunchKernelGGL(ensemble_gather_trad_kernel, dim3(t->n_games), dim3(64), 0, s, t->a, t->d_hdr, t->d_moves, t->d_lens, t->cap, t->n_games, group,
                        static_cast<Accumulator*>(t->d_ensemble));
     GMK_HIP_CHECK(hipGetLastError());
     return finish(t->d_ensemble, n_ensembles, group, Outputs{d_visits, d_values, d_cells, d_cells_per_game, d_root_visits, d_root_value, d_status}, s);

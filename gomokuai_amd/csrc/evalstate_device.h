@@ -14,6 +14,7 @@
 // 16 result slots apply the matches, 52 lanes test the window's blanks for compounds, 49 lanes update the 7x7 block.
 #pragma once
 #include "capi_common.h"
+#include "wave_fence.h"
 
 namespace gmk::evs {
 
@@ -53,11 +54,7 @@ constexpr int kScratchWords = oItems + kCompoundCap;                            
 __device__ __forceinline__ int dir_stride(int dir) { return dir == 0 ? 1 : dir == 1 ? 15 : dir == 2 ? 16 : 14; }
 __device__ __forceinline__ int group2(int favour_black, int perspective_black) { return (favour_black << 1) | perspective_black; }   // Pattern.h:159-161
 
-__device__ __forceinline__ void wave_phase_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using gmk::wave_phase_fence;                                                     // (wave_fence.h)
 
 struct Ctx {
     uint32_t* st;                // state in LDS

@@ -45,12 +45,6 @@ struct RaveParams {
     int profile;                                 // GMK_RAVE_PROFILE: shader clocks per stage into TradHeader::prof (diagnostic runs only)
 };
 
-__device__ __forceinline__ void wave_phase_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // one stone into the four line words through its cell (the layout of rollout_device.h)
 __device__ __forceinline__ void place_stone(uint32_t* lines, uint32_t cell, uint32_t shift) {
     const uint32_t y = cell / 15u, x = cell - 15u * y;
@@ -96,12 +90,7 @@ void rave_playouts_kernel(RaveParams prm) {
     wave_phase_fence();
     for (int i = lane; i < init; i += 64) place_stone(root_lines, mv[i], (i & 1) ? 16u : 0u);
     if (fresh) {                                                // MCTS::reset / a new search: the root node alone
-        if (lane == 0 && exists) {
-            stat[0] = make_uint2(0u, 0u);
-            info[0] = make_uint2(kNoParent | (root_last << 24), __float_as_uint(1.0f));
-            link_of[0] = 0u;
-            amaf[0] = make_uint2(0u, 0u);
-        }
+        if (lane == 0 && exists) new_root(prm.a, arena, root_last, true);
         n_nodes = 1;
         status = exists ? 0u : 1u;
     }
@@ -348,13 +337,13 @@ extern "C" int gmk_trad_run_poolrave(gmk_trad* t, int playouts, double c_puct, u
     if (!t->positioned) { gmk::set_error("gmk_trad_run_poolrave: gmk_trad_set_positions has not been called"); return GMK_ERR_STATE; }
     if (t->policy == 1 || t->policy == 3) { gmk::set_error("gmk_trad_run_poolrave: this handle searches with gmk_trad_run%s", t->policy == 3 ? "_rave" : " (its nodes carry no AMAF statistics)"); return GMK_ERR_STATE; }
     t->policy = 2;
-    if (!t->d_amaf) {
+    if (!t->a.amaf) {
         const size_t nodes = static_cast<size_t>(t->n_games) * static_cast<size_t>(t->cap);
-        GMK_HIP_CHECK(gmk::device_malloc(&t->d_amaf, nodes * 8));
-        GMK_HIP_CHECK(hipMemset(t->d_amaf, 0, nodes * 8));
+        GMK_HIP_CHECK(gmk::device_malloc(&t->a.amaf, nodes * 8));
+        GMK_HIP_CHECK(hipMemset(t->a.amaf, 0, nodes * 8));
     }
     RaveParams prm;
-    prm.a = t->arena();
+    prm.a = t->a;
     prm.hdr = t->d_hdr; prm.moves = t->d_moves; prm.lens = t->d_lens;
     prm.n_games = t->n_games; prm.cap = t->cap; prm.playouts = playouts;
     prm.seed_lo = static_cast<uint32_t>(seed); prm.seed_hi = static_cast<uint32_t>(seed >> 32); prm.first_game_id = first_game_id; prm.game_ids = t->d_game_ids;
@@ -378,7 +367,7 @@ extern "C" int gmk_trad_run_poolrave(gmk_trad* t, int playouts, double c_puct, u
 
 extern "C" int gmk_trad_root_amaf(gmk_trad* t, uint32_t* h_amaf_visits, float* h_amaf_values) {
     if (!t || !h_amaf_visits || !h_amaf_values) { gmk::set_error("gmk_trad_root_amaf: bad arguments"); return GMK_ERR_ARG; }
-    if (!t->d_amaf) { gmk::set_error("gmk_trad_root_amaf: neither gmk_trad_run_poolrave nor gmk_trad_run_rave has been called on this handle"); return GMK_ERR_STATE; }
+    if (!t->a.amaf) { gmk::set_error("gmk_trad_root_amaf: neither gmk_trad_run_poolrave nor gmk_trad_run_rave has been called on this handle"); return GMK_ERR_STATE; }
     const size_t n = static_cast<size_t>(t->n_games);
     uint32_t* d_visits = nullptr;
     float* d_values = nullptr;
@@ -387,7 +376,7 @@ extern "C" int gmk_trad_root_amaf(gmk_trad* t, uint32_t* h_amaf_visits, float* h
     GMK_TRY(gmk::device_malloc(&d_visits, n * 225 * 4)); GMK_TRY(gmk::device_malloc(&d_values, n * 225 * 4));
     GMK_TRY(hipMemset(d_visits, 0, n * 225 * 4)); GMK_TRY(hipMemset(d_values, 0, n * 225 * 4));
     GMK_TRY(hipDeviceSynchronize());                             // a search may still be running on a stream of the caller's
-    hipLaunchKernelGGL(rave_root_amaf_kernel, dim3(t->n_games), dim3(64), 0, nullptr, t->arena(), t->d_hdr, t->cap, d_visits, d_values);
+    hipLaunchKernelGGL(rave_root_amaf_kernel, dim3(t->n_games), dim3(64), 0, nullptr, t->a, t->d_hdr, t->cap, d_visits, d_values);
     GMK_TRY(hipGetLastError());
     GMK_TRY(hipDeviceSynchronize());
     GMK_TRY(hipMemcpy(h_amaf_visits, d_visits, n * 225 * 4, hipMemcpyDeviceToHost));

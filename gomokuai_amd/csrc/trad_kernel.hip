@@ -89,7 +89,8 @@ struct Game {
     uint32_t* link;
     uint2* front;
     uint8_t* ord;
-    uint2* amaf;
+    uint2* amaf;                                     // null without kRave
+    __device__ __forceinline__ TradArena arena() const { return {stat, info, link, front, ord, amaf}; }
     int cached, init;
     unsigned long long updates;
 };
@@ -124,9 +125,6 @@ __device__ __forceinline__ void trad_root_noise(uint2* info, const uint32_t* lin
         if (i < n) info[first + i] = make_uint2(inf[k].x, cells[inf[k].x >> 24]);
     }
 }
-
-template <bool kWaveOnly> __device__ uint32_t copy_subtree(const TradArena& a, const TradArena& b, size_t base, uint32_t src_root, int lane);
-template <bool kWaveOnly> __device__ __forceinline__ void copy_sync();
 
 // kSelfPlay = false: one search per game (gmk_trad_run); true: the persistent self-play loop (gmk_trad_selfplay_run, persistent = 1).  Two
 // instantiations, so that the bare search does not carry the registers of the turn loop through its playouts.
@@ -164,7 +162,7 @@ void trad_playouts_kernel(TradParams prm) {
     auto use_arena = [&](uint32_t which) {
         const size_t at = arena + ((kSelfPlay && which) ? prm.sp.arena_stride : 0);
         g.stat = prm.stat + at; g.info = prm.info + at; g.link = prm.link + at; g.front = prm.front + at; g.ord = prm.ord + at;
-        if (kRave) g.amaf = prm.amaf + at;
+        g.amaf = kRave ? prm.amaf + at : nullptr;
     };
     use_arena(0);
     g.updates = 0;
@@ -291,13 +289,7 @@ void trad_playouts_kernel(TradParams prm) {
         }
         if (it < 0) {                                           // the prologue ends here: a fresh root where one was asked for
             if (fresh) {
-                if (lane == 0) {
-                    g.stat[0] = make_uint2(0u, 0u);
-                    g.info[0] = make_uint2(kNoParent | ((n_position ? slot_moves[n_position - 1] : 255u) << 24), __float_as_uint(1.0f));
-                    g.link[0] = 0u;
-                    if (kRave) g.amaf[0] = make_uint2(0u, 0u);
-                    g.set_link(0, 0u);
-                }
+                if (lane == 0) { new_root(g.arena(), 0, n_position ? slot_moves[n_position - 1] : 255u, kRave); g.set_link(0, 0u); }
                 n_nodes = 1;
                 status = 0;
             }
@@ -485,50 +477,29 @@ void trad_playouts_kernel(TradParams prm) {
         const TradSelfPlay& sp = prm.sp;
         if (lane == 0 && (status & 1u)) atomicOr(sp.overflow, 1);
         const uint32_t lk = g.link[0], first = lk & 0xFFFFFFu, n = lk >> 24;
-        uint32_t best_visits = 0, best_ord = 0xFFFFFFFFu, best_id = 0;
-        for (uint32_t i = lane; i < n; i += 64) {
-            const uint32_t id = first + i, o = g.ord[id], v = g.stat[id].x + 1u;
-            if (v > best_visits || (v == best_visits && o < best_ord)) { best_visits = v; best_ord = o; best_id = id; }
-        }
-        for (int sft = 32; sft > 0; sft >>= 1) {
-            const uint32_t ov = __shfl_down(best_visits, sft), oo = __shfl_down(best_ord, sft), oi = __shfl_down(best_id, sft);
-            if (ov > best_visits || (ov == best_visits && ov != 0u && oo < best_ord)) { best_visits = ov; best_ord = oo; best_id = oi; }
-        }
-        best_visits = __shfl(best_visits, 0);
-        best_id = __shfl(best_id, 0);
-        bool over = best_visits == 0u || cur_len >= 225;        // no child: nothing the policy wants to play: the game ends where it stands
+        const uint32_t best_id = most_visited_child(g.stat, g.ord, first, n, lane);
+        bool over = best_id == kNoChild || cur_len >= 225;      // no child: nothing the policy wants to play: the game ends where it stands
         int winner = 0;
         if (!over) {
             const uint32_t cell = g.info[best_id].x >> 24;
-            if (sp.rec_visits) {
-                uint16_t* rv = sp.rec_visits + (static_cast<size_t>(sp_game) * 225 + static_cast<size_t>(cur_len)) * 225;
-                for (int i = lane; i < 225; i += 64) rv[i] = 0;
-                wave_phase_fence();
-                for (uint32_t i = lane; i < n; i += 64) rv[g.info[first + i].x >> 24] = static_cast<uint16_t>(min(g.stat[first + i].x, 65535u));
-            }
-            uint32_t* rows = g.path_node;                       // (the path is rebuilt by the next search: sixteen words of it hold the board's rows here)
-            if (lane < 16) rows[lane] = 0u;
-            wave_phase_fence();
-            for (int i = lane; i < cur_len; i += 64) atomicOr(&rows[slot_moves[i] / 15u], 1u << (slot_moves[i] % 15u + ((i & 1) ? 16u : 0u)));
-            const int shift = (cur_len & 1) ? 16 : 0;
-            if (lane == 0) atomicOr(&rows[cell / 15u], 1u << (cell % 15u + shift));
-            wave_phase_fence();
-            const bool five = gmk::five_through<1>(rows, static_cast<int>(cell % 15u), static_cast<int>(cell / 15u), shift);
+            if (sp.rec_visits)
+                visits_by_cell(sp.rec_visits + (static_cast<size_t>(sp_game) * 225 + static_cast<size_t>(cur_len)) * 225, g.stat, g.info, first, n, lane, SyncWave{});
+            // (the path is rebuilt by the next search: sixteen words of it hold the board's rows here)
+            winner = play_cell(slot_moves, cur_len, cell, g.path_node, lane, SyncWave{});
             if (lane == 0) {
                 slot_moves[cur_len] = static_cast<uint8_t>(cell);
                 sp.rec_moves[static_cast<size_t>(sp_game) * 225 + cur_len] = static_cast<uint8_t>(cell);
                 sp.rec_lens[sp_game] = cur_len + 1;
             }
-            over = five || cur_len + 1 == 225;
-            winner = five ? (shift ? -1 : 1) : 0;
+            over = winner != 0 || cur_len + 1 == 225;
             ++cur_len;
         }
         bool kept = false;
         if (!over && sp.reuse) {
             // MCTS::stepForward (MCTS.cpp:129-134): the chosen child's subtree is the next search's tree -- compacted into the slot's other arena
-            const TradArena a{g.stat, g.info, g.link, g.front, g.ord, kRave ? g.amaf : nullptr};
+            const TradArena a = g.arena();
             use_arena(live ^ 1u);
-            const TradArena b{g.stat, g.info, g.link, g.front, g.ord, kRave ? g.amaf : nullptr};
+            const TradArena b = g.arena();
             n_nodes = copy_subtree<true>(a, b, 0, best_id, lane);
             live ^= 1u;
             root_black ^= 1;
@@ -584,74 +555,7 @@ void trad_playouts_kernel(TradParams prm) {
     for (int i = lane; i < kStateWords / 4; i += 64) dst[i] = src[i];
 }
 
-// MCTS::stepForward() / stepForward(move) (MCTS.cpp:129-147): the chosen child's subtree becomes the tree.  The reference
-// frees the siblings; here the kept subtree is copied level by level into the other arena so that node indices stay dense
-// (children consecutive, the root at 0).  A copied node carries its OLD child range and OLD first-child record until the
-// scan reaches it, copies its children and rewrites both.  One wavefront per game.
-
-// The subtree of node src_root of arena a becomes the tree of arena b, level by level (see above); one wavefront.
-// kWaveOnly: the caller is one wavefront of a larger workgroup (the persistent self-play loop of trad_playouts_kernel): its lanes meet at a
-// wavefront barrier with workgroup-scope fences (the CU's L1 is shared by the workgroup) instead of __syncthreads().  Returns the node count.
-template <bool kWaveOnly>
-__device__ __forceinline__ void copy_sync() {
-    if constexpr (kWaveOnly) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    } else {
-        __syncthreads();
-    }
-}
-
-template <bool kWaveOnly>
-__device__ uint32_t copy_subtree(const TradArena& a, const TradArena& b, size_t base, uint32_t src_root, int lane) {
-    if (lane == 0) {
-        b.stat[base] = a.stat[base + src_root];
-        b.info[base] = make_uint2(kNoParent | (a.info[base + src_root].x & 0xFF000000u), a.info[base + src_root].y);
-        b.link[base] = a.link[base + src_root];
-        b.front[base] = a.front[base + src_root];
-        b.ord[base] = 0;
-        if (a.amaf) b.amaf[base] = a.amaf[base + src_root];
-    }
-    copy_sync<kWaveOnly>();
-    uint32_t next = 1;
-    for (uint32_t i0 = 0, chunk = 0; i0 < next; i0 += chunk) {
-        chunk = min(64u, next - i0);                            // nodes appended while this chunk is handled come after it
-        const uint32_t old_link = static_cast<uint32_t>(lane) < chunk ? b.link[base + i0 + lane] : 0u;
-        unsigned long long todo = __ballot((old_link >> 24) != 0u);
-        while (todo) {
-            const int j = __ffsll(static_cast<long long>(todo)) - 1;
-            todo &= todo - 1ull;
-            const uint32_t ol = __shfl(old_link, j), of = ol & 0xFFFFFFu, nk = ol >> 24, node = i0 + static_cast<uint32_t>(j);
-            for (uint32_t k = lane; k < nk; k += 64) {
-                const uint2 inf = a.info[base + of + k];
-                b.stat[base + next + k] = a.stat[base + of + k];
-                b.info[base + next + k] = make_uint2(node | (inf.x & 0xFF000000u), inf.y);
-                b.link[base + next + k] = a.link[base + of + k];
-                b.front[base + next + k] = a.front[base + of + k];
-                b.ord[base + next + k] = a.ord[base + of + k];
-                if (a.amaf) b.amaf[base + next + k] = a.amaf[base + of + k];
-            }
-            if (lane == 0) {
-                const uint32_t new_link = next | (nk << 24);
-                b.link[base + node] = new_link;
-                const uint2 fr = b.front[base + node];              // still the OLD id of the first child in the current order
-                b.front[base + node] = make_uint2((next + ((fr.x & 0xFFFFFFu) - of)) | (fr.x & 0xFF000000u), fr.y);
-                if (node != 0u) {                                   // am I my parent's first child?  then its record of me carries my child range
-                    const uint32_t p = b.info[base + node].x & 0xFFFFFFu;
-                    const uint2 pf = b.front[base + p];
-                    if ((pf.x & 0xFFFFFFu) == node) b.front[base + p] = make_uint2(pf.x, new_link);
-                }
-            }
-            next += nk;
-            copy_sync<kWaveOnly>();
-        }
-        copy_sync<kWaveOnly>();                                        // children written above are scanned below
-    }
-    return next;
-}
-
-
+// MCTS::stepForward() / stepForward(move) for every game: the kept subtree into arena b (copy_subtree, trad_tree.h).  One wavefront per game.
 __global__ __launch_bounds__(64)
 void trad_step_kernel(TradArena a, TradArena b, TradHeader* hdrs, int cap, int n_games, const int16_t* forced, uint8_t* moves, int32_t* lens) {
     const int game = blockIdx.x, lane = threadIdx.x;
@@ -661,55 +565,28 @@ void trad_step_kernel(TradArena a, TradArena b, TradHeader* hdrs, int cap, int n
     uint8_t* mv = moves + static_cast<size_t>(game) * 225;
     const int len = lens[game];
     if (hdr.fresh == 1u) {                                      // the position was set but never searched: its root node does not exist yet
-        if (lane == 0) {
-            a.stat[base] = make_uint2(0u, 0u);
-            a.info[base] = make_uint2(kNoParent | ((len ? mv[len - 1] : 255u) << 24), __float_as_uint(1.0f));
-            a.link[base] = 0u;
-            if (a.amaf) a.amaf[base] = make_uint2(0u, 0u);
-            hdr.n_nodes = 1; hdr.status = 0; hdr.root_black = static_cast<uint32_t>(len & 1);
-        }
+        if (lane == 0) { new_root(a, base, len ? mv[len - 1] : 255u, a.amaf != nullptr); hdr.n_nodes = 1; hdr.status = 0; hdr.root_black = static_cast<uint32_t>(len & 1); }
         __syncthreads();
     }
     const uint32_t lk = a.link[base], first = lk & 0xFFFFFFu, n = lk >> 24;
-    int want = forced ? forced[game] : -1;
+    const int want = forced ? forced[game] : -1;
     // the child to keep: the one of the wanted move, or the most visited one, first in the current order
-    uint32_t best_visits = 0, best_ord = 0xFFFFFFFFu, best_id = 0;
-    for (uint32_t i = lane; i < n; i += 64) {
-        const uint32_t id = first + i, cell = a.info[base + id].x >> 24, o = a.ord[base + id];
-        const uint32_t v = want >= 0 ? (cell == static_cast<uint32_t>(want) ? 1u : 0u) : a.stat[base + id].x + 1u;
-        if (v > best_visits || (v == best_visits && v != 0u && o < best_ord)) { best_visits = v; best_ord = o; best_id = id; }
-    }
-    for (int s = 32; s > 0; s >>= 1) {
-        const uint32_t ov = __shfl_down(best_visits, s), oo = __shfl_down(best_ord, s), oi = __shfl_down(best_id, s);
-        if (ov > best_visits || (ov == best_visits && ov != 0u && oo < best_ord)) { best_visits = ov; best_ord = oo; best_id = oi; }
-    }
-    best_visits = __shfl(best_visits, 0);
-    best_id = __shfl(best_id, 0);
-    const bool found = best_visits != 0u;
-    if (want < 0 && !found) {                                   // stepForward() on a childless root: nothing moves (MCTS.cpp:133)
-        if (lane == 0) {
-            b.stat[base] = a.stat[base]; b.info[base] = a.info[base]; b.link[base] = 0u; b.ord[base] = 0; hdr.n_nodes = 1; hdr.fresh = 2;
-            if (a.amaf) b.amaf[base] = a.amaf[base];
+    const uint32_t child = want >= 0 ? child_of_cell(a.info + base, first, n, static_cast<uint32_t>(want), lane) : most_visited_child(a.stat + base, a.ord + base, first, n, lane);
+    uint32_t src_root = 0u;                                     // nothing moves: the tree stays as it is (copied over, the arenas flip for everybody)
+    if (want < 0 && child == kNoChild) {                        // stepForward() on a childless root (MCTS.cpp:133)
+        if (lane == 0) hdr.fresh = 2;
+    } else {
+        const uint32_t cell = child != kNoChild ? a.info[base + child].x >> 24 : static_cast<uint32_t>(want);
+        if (!legal_reply(mv, len, cell, lane)) {                // not a move of this game
+            if (lane == 0) hdr.status |= 8u;
+        } else {
+            if (lane == 0) { mv[len] = static_cast<uint8_t>(cell); lens[game] = len + 1; hdr.fresh = 2; hdr.root_black ^= 1u; }
+            if (child == kNoChild) {                            // stepForward(move) without such a child: a new node (MCTS.cpp:140-145)
+                if (lane == 0) { new_root(b, base, cell, a.amaf != nullptr); hdr.n_nodes = 1; }
+                return;
+            }
+            src_root = child;
         }
-        return;
-    }
-    const uint32_t cell = found ? a.info[base + best_id].x >> 24 : static_cast<uint32_t>(want);
-    bool legal = cell < 225u && len < 225;
-    for (int i = lane; i < len; i += 64) legal &= mv[i] != cell;
-    legal = __all(legal);
-    if (!legal) {                                               // not a move of this game: the tree stays as it is (copied over, the arenas flip for everybody)
-        if (lane == 0) hdr.status |= 8u;
-        want = -2;
-    }
-    if (lane == 0 && want != -2) { mv[len] = static_cast<uint8_t>(cell); lens[game] = len + 1; hdr.fresh = 2; hdr.root_black ^= 1u; }
-    const uint32_t src_root = want == -2 ? 0u : best_id;
-    if (want != -2 && !found) {                                 // stepForward(move) without such a child: a new node (MCTS.cpp:140-145)
-        if (lane == 0) {
-            b.stat[base] = make_uint2(0u, 0u); b.info[base] = make_uint2(kNoParent | (cell << 24), __float_as_uint(1.0f));
-            b.link[base] = 0u; b.ord[base] = 0; hdr.n_nodes = 1;
-            if (a.amaf) b.amaf[base] = make_uint2(0u, 0u);
-        }
-        return;
     }
     const uint32_t kept = copy_subtree<false>(a, b, base, src_root, lane);
     if (lane == 0) hdr.n_nodes = kept;
@@ -734,43 +611,22 @@ void trad_advance_kernel(TradArena a, TradArena b, TradHeader* hdrs, int cap, in
     // the child to keep: the most visited one, first in the current order (as trad_step_kernel / trad_root_stats_kernel)
     const bool searched = hdr.fresh != 1u;                      // (a position that was never searched has no root node yet)
     const uint32_t lk = searched ? a.link[base] : 0u, first = lk & 0xFFFFFFu, n = lk >> 24;
-    uint32_t best_visits = 0, best_ord = 0xFFFFFFFFu, best_id = 0;
-    for (uint32_t i = lane; i < n; i += 64) {
-        const uint32_t id = first + i, o = a.ord[base + id], v = a.stat[base + id].x + 1u;
-        if (v > best_visits || (v == best_visits && o < best_ord)) { best_visits = v; best_ord = o; best_id = id; }
-    }
-    for (int sft = 32; sft > 0; sft >>= 1) {
-        const uint32_t ov = __shfl_down(best_visits, sft), oo = __shfl_down(best_ord, sft), oi = __shfl_down(best_id, sft);
-        if (ov > best_visits || (ov == best_visits && ov != 0u && oo < best_ord)) { best_visits = ov; best_ord = oo; best_id = oi; }
-    }
-    best_visits = __shfl(best_visits, 0);
-    best_id = __shfl(best_id, 0);
-    bool over = best_visits == 0u || len >= 225;                // no child: nothing the policy wants to play: the game ends where it stands
+    const uint32_t best_id = most_visited_child(a.stat + base, a.ord + base, first, n, lane);
+    bool over = best_id == kNoChild || len >= 225;              // no child: nothing the policy wants to play: the game ends where it stands
     int winner = 0;
     if (!over) {
         const uint32_t cell = a.info[base + best_id].x >> 24;
-        if (sp.rec_visits) {                                    // the root's visit counts by cell, the searched ply's row of the game's record
-            uint16_t* rv = sp.rec_visits + (static_cast<size_t>(game) * 225 + static_cast<size_t>(len)) * 225;
-            for (int i = lane; i < 225; i += 64) rv[i] = 0;
-            __syncthreads();
-            for (uint32_t i = lane; i < n; i += 64) rv[a.info[base + first + i].x >> 24] = static_cast<uint16_t>(min(a.stat[base + first + i].x, 65535u));
-        }
-        // the board after the move (move i is black's when i is even), five or more through it wins, a full board is a tie
-        if (lane < 16) s_rows[lane] = 0u;
-        __syncthreads();
-        for (int i = lane; i < len; i += 64) atomicOr(&s_rows[mv[i] / 15u], 1u << (mv[i] % 15u + ((i & 1) ? 16u : 0u)));
-        const int shift = (len & 1) ? 16 : 0;
-        if (lane == 0) atomicOr(&s_rows[cell / 15u], 1u << (cell % 15u + shift));
-        __syncthreads();
-        const bool five = gmk::five_through<1>(s_rows, static_cast<int>(cell % 15u), static_cast<int>(cell / 15u), shift);
+        if (sp.rec_visits)                                      // the root's visit counts by cell, the searched ply's row of the game's record
+            visits_by_cell(sp.rec_visits + (static_cast<size_t>(game) * 225 + static_cast<size_t>(len)) * 225, a.stat + base, a.info + base, first, n, lane, SyncBlock{});
+        // five or more through the move win, a full board is a tie
+        winner = play_cell(mv, len, cell, s_rows, lane, SyncBlock{});
         if (lane == 0) {
             mv[len] = static_cast<uint8_t>(cell);
             lens[slot] = len + 1;
             sp.rec_moves[static_cast<size_t>(game) * 225 + len] = static_cast<uint8_t>(cell);
             sp.rec_lens[game] = len + 1;
         }
-        over = five || len + 1 == 225;
-        winner = five ? (shift ? -1 : 1) : 0;
+        over = winner != 0 || len + 1 == 225;
         if (!over) {
             if (lane == 0) {
                 atomicAdd(sp.unfinished, 1);
@@ -851,29 +707,23 @@ void trad_root_noise_kernel(TradArena a, const TradHeader* hdrs, int cap, const 
 
 // root statistics by cell and the child MCTS::stepForward would pick (most visited, first in the CURRENT order)
 __global__ __launch_bounds__(64)
-void trad_root_stats_kernel(const uint2* stat, const uint2* info, const uint32_t* link, const uint8_t* ord, const TradHeader* hdrs, int cap,
-                            uint32_t* visits, float* values, float* priors, int32_t* best, uint32_t* root_visits, float* root_value) {
+void trad_root_stats_kernel(TradArena a, const TradHeader* hdrs, int cap, uint32_t* visits, float* values, float* priors, int32_t* best, uint32_t* root_visits, float* root_value) {
     const int game = blockIdx.x, lane = threadIdx.x;
-    const size_t arena = static_cast<size_t>(game) * cap;
+    const size_t base = static_cast<size_t>(game) * cap;
     const bool no_root = hdrs[game].fresh == 1u;                // the position was set but never searched
-    const uint32_t lk = no_root ? 0u : link[arena], first = lk & 0xFFFFFFu, n = lk >> 24;
-    uint32_t best_visits = 0, best_ord = 0xFFFFFFFFu, best_cell = 0;
+    const uint32_t lk = no_root ? 0u : a.link[base], first = lk & 0xFFFFFFu, n = lk >> 24;
     for (uint32_t i = lane; i < n; i += 64) {
-        const uint2 cs = stat[arena + first + i], ci = info[arena + first + i];
-        const uint32_t cell = ci.x >> 24, o = ord[arena + first + i];
-        if (visits) visits[static_cast<size_t>(game) * 225 + cell] = cs.x;
-        if (values) values[static_cast<size_t>(game) * 225 + cell] = __uint_as_float(cs.y);
-        if (priors) priors[static_cast<size_t>(game) * 225 + cell] = __uint_as_float(ci.y);
-        if (best_ord == 0xFFFFFFFFu || cs.x > best_visits || (cs.x == best_visits && o < best_ord)) { best_visits = cs.x; best_ord = o; best_cell = cell; }
+        const uint2 cs = a.stat[base + first + i], ci = a.info[base + first + i];
+        const size_t at = static_cast<size_t>(game) * 225 + (ci.x >> 24);
+        if (visits) visits[at] = cs.x;
+        if (values) values[at] = __uint_as_float(cs.y);
+        if (priors) priors[at] = __uint_as_float(ci.y);
     }
-    for (int s = 32; s > 0; s >>= 1) {
-        const uint32_t ov = __shfl_down(best_visits, s), oo = __shfl_down(best_ord, s), oc = __shfl_down(best_cell, s);
-        if (oo != 0xFFFFFFFFu && (best_ord == 0xFFFFFFFFu || ov > best_visits || (ov == best_visits && oo < best_ord))) { best_visits = ov; best_ord = oo; best_cell = oc; }
-    }
+    const uint32_t best_id = most_visited_child(a.stat + base, a.ord + base, first, n, lane);
     if (lane == 0) {
-        if (best) best[game] = best_ord == 0xFFFFFFFFu ? -1 : static_cast<int32_t>(best_cell);
-        if (root_visits) root_visits[game] = no_root ? 0u : stat[arena].x;
-        if (root_value) root_value[game] = no_root ? 0.0f : __uint_as_float(stat[arena].y);
+        if (best) best[game] = best_id == kNoChild ? -1 : static_cast<int32_t>(a.info[base + best_id].x >> 24);
+        if (root_visits) root_visits[game] = no_root ? 0u : a.stat[base].x;
+        if (root_value) root_value[game] = no_root ? 0.0f : __uint_as_float(a.stat[base].y);
     }
 }
 
@@ -886,22 +736,9 @@ void trad_root_choice_kernel(TradArena a, const TradHeader* hdrs, int cap, int n
     const size_t base = static_cast<size_t>(game) * cap;
     const bool no_root = hdrs[game].fresh == 1u;                // the position was set but never searched
     const uint32_t lk = no_root ? 0u : a.link[base], first = lk & 0xFFFFFFu, n = lk >> 24;
-    uint16_t* rv = visits ? visits + static_cast<size_t>(game) * 225 : nullptr;
-    if (rv) {
-        for (int i = lane; i < 225; i += 64) rv[i] = 0;
-        __syncthreads();
-    }
-    uint32_t best_visits = 0, best_ord = 0xFFFFFFFFu, best_cell = 0;
-    for (uint32_t i = lane; i < n; i += 64) {
-        const uint32_t v = a.stat[base + first + i].x, cell = a.info[base + first + i].x >> 24, o = a.ord[base + first + i];
-        if (rv && cell < 225u) rv[cell] = static_cast<uint16_t>(min(v, 65535u));
-        if (best_ord == 0xFFFFFFFFu || v > best_visits || (v == best_visits && o < best_ord)) { best_visits = v; best_ord = o; best_cell = cell; }
-    }
-    for (int s = 32; s > 0; s >>= 1) {
-        const uint32_t ov = __shfl_down(best_visits, s), oo = __shfl_down(best_ord, s), oc = __shfl_down(best_cell, s);
-        if (oo != 0xFFFFFFFFu && (best_ord == 0xFFFFFFFFu || ov > best_visits || (ov == best_visits && oo < best_ord))) { best_visits = ov; best_ord = oo; best_cell = oc; }
-    }
-    if (lane == 0) cells[game] = best_ord == 0xFFFFFFFFu ? static_cast<int16_t>(-1) : static_cast<int16_t>(best_cell);
+    if (visits) visits_by_cell(visits + static_cast<size_t>(game) * 225, a.stat + base, a.info + base, first, n, lane, SyncBlock{});
+    const uint32_t best_id = most_visited_child(a.stat + base, a.ord + base, first, n, lane);
+    if (lane == 0) cells[game] = best_id == kNoChild ? static_cast<int16_t>(-1) : static_cast<int16_t>(a.info[base + best_id].x >> 24);
 }
 
 // gmk_trad_step with the cells and the referee's verdicts (GMK_MATCH_*) read from device memory.  A game that moved appends the move to its
@@ -921,10 +758,9 @@ void trad_step_device_kernel(TradArena a, TradArena b, TradHeader* hdrs, int cap
     const int len = lens[game], v = verdict[game];
     const uint32_t cell = static_cast<uint32_t>(static_cast<int>(cells[game]));
     bool moved = v == GMK_MATCH_MOVED || v == GMK_MATCH_ENDED;
-    if (moved) {                                                // the referee judged the RECORD; the handle's own position must agree
-        bool legal = cell < 225u && len < 225;
-        for (int i = lane; i < len; i += 64) legal &= mv[i] != cell;
-        if (!__all(legal)) { moved = false; if (lane == 0) hdr.status |= 8u; }
+    if (moved && !legal_reply(mv, len, cell, lane)) {           // the referee judged the RECORD; the handle's own position must agree
+        moved = false;
+        if (lane == 0) hdr.status |= 8u;
     }
     if (fresh) {
         if (moved && lane == 0) {
@@ -935,13 +771,7 @@ void trad_step_device_kernel(TradArena a, TradArena b, TradHeader* hdrs, int cap
         return;
     }
     if (hdr.fresh == 1u) {                                      // the position was set but never searched: its root node does not exist yet
-        if (lane == 0) {
-            a.stat[base] = make_uint2(0u, 0u);
-            a.info[base] = make_uint2(kNoParent | ((len ? mv[len - 1] : 255u) << 24), __float_as_uint(1.0f));
-            a.link[base] = 0u;
-            if (a.amaf) a.amaf[base] = make_uint2(0u, 0u);
-            hdr.n_nodes = 1; hdr.status = 0; hdr.root_black = static_cast<uint32_t>(len & 1); hdr.fresh = 2;
-        }
+        if (lane == 0) { new_root(a, base, len ? mv[len - 1] : 255u, a.amaf != nullptr); hdr.n_nodes = 1; hdr.status = 0; hdr.root_black = static_cast<uint32_t>(len & 1); hdr.fresh = 2; }
         __syncthreads();
     }
     if (!moved) {
@@ -949,45 +779,55 @@ void trad_step_device_kernel(TradArena a, TradArena b, TradHeader* hdrs, int cap
         if (lane == 0) hdr.n_nodes = kept;
         return;
     }
-    uint32_t best_id = 0xFFFFFFFFu;                             // the child of that cell (a cell has at most one)
+    uint32_t child = kNoChild;
     if (v == GMK_MATCH_MOVED) {
-        const uint32_t lk = a.link[base], first = lk & 0xFFFFFFu, n = lk >> 24;
-        for (uint32_t i = lane; i < n; i += 64)
-            if ((a.info[base + first + i].x >> 24) == cell) best_id = first + i;
-        for (int s = 32; s > 0; s >>= 1) best_id = min(best_id, static_cast<uint32_t>(__shfl_xor(best_id, s)));
+        const uint32_t lk = a.link[base];
+        child = child_of_cell(a.info + base, lk & 0xFFFFFFu, lk >> 24, cell, lane);
     }
     __syncthreads();                                            // every lane has read the old move list
     if (lane == 0) { mv[len] = static_cast<uint8_t>(cell); lens[game] = len + 1; hdr.fresh = 2; hdr.root_black ^= 1u; }
-    if (best_id == 0xFFFFFFFFu) {                               // stepForward(move) without such a child (MCTS.cpp:140-145), or the end of the game: a new node
+    if (child == kNoChild) {                                    // stepForward(move) without such a child (MCTS.cpp:140-145), or the end of the game: a new node
         if (lane == 0) {
-            const uint2 st = make_uint2(0u, 0u), inf = make_uint2(kNoParent | (cell << 24), __float_as_uint(1.0f));
-            b.stat[base] = st; b.info[base] = inf; b.link[base] = 0u; b.ord[base] = 0; hdr.n_nodes = 1;
-            if (a.amaf) b.amaf[base] = make_uint2(0u, 0u);
-            if (v == GMK_MATCH_ENDED) {
-                a.stat[base] = st; a.info[base] = inf; a.link[base] = 0u; a.ord[base] = 0;
-                if (a.amaf) a.amaf[base] = make_uint2(0u, 0u);
-                hdr.status |= kStatusIdleSlot;
-            }
+            new_root(b, base, cell, a.amaf != nullptr); hdr.n_nodes = 1;
+            if (v == GMK_MATCH_ENDED) { new_root(a, base, cell, a.amaf != nullptr); hdr.status |= kStatusIdleSlot; }       // (an idle game's childless root is in both arenas)
         }
         return;
     }
-    const uint32_t kept = copy_subtree<false>(a, b, base, best_id, lane);
+    const uint32_t kept = copy_subtree<false>(a, b, base, child, lane);
     if (lane == 0) hdr.n_nodes = kept;
 }
 
 }  // namespace
 
 
+// the five arrays of one arena of `nodes` nodes, all or nothing (the AMAF array has its own makers: ensure_amaf, trad_second_arena)
+static bool arena_alloc(TradArena& a, size_t nodes) {
+    const bool ok = gmk::device_malloc(&a.stat, nodes * 8) == hipSuccess && gmk::device_malloc(&a.info, nodes * 8) == hipSuccess && gmk::device_malloc(&a.link, nodes * 4) == hipSuccess &&
+                    gmk::device_malloc(&a.front, nodes * 8) == hipSuccess && gmk::device_malloc(&a.ord, nodes) == hipSuccess;
+    if (!ok) {
+        (void)gmk::device_free(a.stat); (void)gmk::device_free(a.info); (void)gmk::device_free(a.link); (void)gmk::device_free(a.front); (void)gmk::device_free(a.ord);
+        a.stat = a.info = a.front = nullptr; a.link = nullptr; a.ord = nullptr;
+        (void)hipGetLastError();
+    }
+    return ok;
+}
+
+static void arena_free(TradArena& a) {
+    (void)gmk::device_free(a.stat); (void)gmk::device_free(a.info); (void)gmk::device_free(a.link); (void)gmk::device_free(a.front); (void)gmk::device_free(a.ord); (void)gmk::device_free(a.amaf);
+    a = TradArena{};
+}
+
 extern "C" int gmk_trad_destroy(gmk_trad* t) {
     if (!t) return GMK_OK;
-    if (t->paired) {                                            // both arenas are halves of the five (six) blocks
-        (void)gmk::device_free(t->block_stat); (void)gmk::device_free(t->block_info); (void)gmk::device_free(t->block_link); (void)gmk::device_free(t->block_front); (void)gmk::device_free(t->block_ord);
-        t->d_stat = t->d_stat2 = t->d_info = t->d_info2 = t->d_front = t->d_front2 = nullptr; t->d_link = t->d_link2 = nullptr; t->d_ord = t->d_ord2 = nullptr;
-        if (t->block_amaf) { (void)gmk::device_free(t->block_amaf); t->block_amaf = t->d_amaf = t->d_amaf2 = nullptr; }
+    if (t->paired) {                                            // both arenas are halves of the five blocks; their AMAF arrays only where there is a sixth
+        const bool sixth = t->block.amaf != nullptr;
+        t->a = TradArena{nullptr, nullptr, nullptr, nullptr, nullptr, sixth ? nullptr : t->a.amaf};
+        t->b = TradArena{nullptr, nullptr, nullptr, nullptr, nullptr, sixth ? nullptr : t->b.amaf};
+        arena_free(t->block);
     }
-    (void)gmk::device_free(t->d_states); (void)gmk::device_free(t->d_stat); (void)gmk::device_free(t->d_info); (void)gmk::device_free(t->d_link);
-    (void)gmk::device_free(t->d_front); (void)gmk::device_free(t->d_ord); (void)gmk::device_free(t->d_stat2); (void)gmk::device_free(t->d_info2); (void)gmk::device_free(t->d_front2);
-    (void)gmk::device_free(t->d_link2); (void)gmk::device_free(t->d_ord2); (void)gmk::device_free(t->d_amaf); (void)gmk::device_free(t->d_amaf2); (void)gmk::device_free(t->d_forced); (void)gmk::device_free(t->d_priors); (void)gmk::device_free(t->d_hdr); (void)gmk::device_free(t->d_moves); (void)gmk::device_free(t->d_lens); (void)gmk::device_free(t->d_game_ids); (void)gmk::device_free(t->d_path_spill); (void)gmk::device_free(t->d_ensemble);
+    arena_free(t->a); arena_free(t->b);
+    (void)gmk::device_free(t->d_states); (void)gmk::device_free(t->d_forced); (void)gmk::device_free(t->d_priors); (void)gmk::device_free(t->d_hdr); (void)gmk::device_free(t->d_moves); (void)gmk::device_free(t->d_lens);
+    (void)gmk::device_free(t->d_game_ids); (void)gmk::device_free(t->d_path_spill); (void)gmk::device_free(t->d_ensemble);
     delete t;
     return GMK_OK;
 }
@@ -1009,8 +849,7 @@ extern "C" int gmk_trad_create(int n_games, int node_capacity, gmk_trad** out) {
     t->cap = node_capacity;
     const size_t nodes = static_cast<size_t>(n_games) * node_capacity;
     bool ok = gmk::device_malloc(&t->d_states, static_cast<size_t>(n_games) * kStateWords * 4) == hipSuccess &&
-              gmk::device_malloc(&t->d_stat, nodes * 8) == hipSuccess && gmk::device_malloc(&t->d_info, nodes * 8) == hipSuccess &&
-              gmk::device_malloc(&t->d_link, nodes * 4) == hipSuccess && gmk::device_malloc(&t->d_front, nodes * 8) == hipSuccess && gmk::device_malloc(&t->d_ord, nodes) == hipSuccess &&
+              arena_alloc(t->a, nodes) &&
               gmk::device_malloc(&t->d_hdr, static_cast<size_t>(n_games) * sizeof(TradHeader)) == hipSuccess &&
               gmk::device_malloc(&t->d_moves, static_cast<size_t>(n_games) * 225) == hipSuccess &&
               gmk::device_malloc(&t->d_lens, static_cast<size_t>(n_games) * 4) == hipSuccess &&
@@ -1040,36 +879,21 @@ extern "C" int gmk_trad_set_option(gmk_trad* t, int option, int value) {
 static int pair_arenas(gmk_trad* t) {
     const size_t nodes = static_cast<size_t>(t->n_games) * static_cast<size_t>(t->cap);
     auto point = [&]() {
-        t->d_stat = t->block_stat; t->d_info = t->block_info; t->d_link = t->block_link; t->d_front = t->block_front; t->d_ord = t->block_ord;
-        t->d_stat2 = t->block_stat + nodes; t->d_info2 = t->block_info + nodes; t->d_link2 = t->block_link + nodes; t->d_front2 = t->block_front + nodes; t->d_ord2 = t->block_ord + nodes;
-        if (t->block_amaf) { t->d_amaf = t->block_amaf; t->d_amaf2 = t->block_amaf + nodes; }
+        const TradArena& k = t->block;                              // (without a sixth block the AMAF arrays stay whose they are)
+        t->a = TradArena{k.stat, k.info, k.link, k.front, k.ord, k.amaf ? k.amaf : t->a.amaf};
+        t->b = TradArena{k.stat + nodes, k.info + nodes, k.link + nodes, k.front + nodes, k.ord + nodes, k.amaf ? k.amaf + nodes : t->b.amaf};
     };
     if (t->paired) { point(); return GMK_OK; }                  // (the lock-step loop may have left the halves swapped)
     if (t->policy == 2) { gmk::set_error("gmk_trad_selfplay_run: the persistent loop keeps subtrees for TraditionalPolicy handles only"); return GMK_ERR_STATE; }
     // (a TraditionalPolicy + RAVE handle's AMAF statistics go with its trees; ensure_amaf makes their block when a run needs it)
-    (void)gmk::device_free(t->d_amaf); (void)gmk::device_free(t->d_amaf2);
-    t->d_amaf = t->d_amaf2 = nullptr;
-    uint2 *bs = nullptr, *bi = nullptr, *bf = nullptr;
-    uint32_t* bl = nullptr;
-    uint8_t* bo = nullptr;
-    (void)gmk::device_free(t->d_stat); (void)gmk::device_free(t->d_info); (void)gmk::device_free(t->d_link); (void)gmk::device_free(t->d_front); (void)gmk::device_free(t->d_ord);
-    (void)gmk::device_free(t->d_stat2); (void)gmk::device_free(t->d_info2); (void)gmk::device_free(t->d_link2); (void)gmk::device_free(t->d_front2); (void)gmk::device_free(t->d_ord2);
-    t->d_stat = t->d_stat2 = t->d_info = t->d_info2 = t->d_front = t->d_front2 = nullptr; t->d_link = t->d_link2 = nullptr; t->d_ord = t->d_ord2 = nullptr;
+    arena_free(t->a); arena_free(t->b);
     t->second_arena = false;
     t->positioned = false;
-    const bool ok = gmk::device_malloc(&bs, 2 * nodes * 8) == hipSuccess && gmk::device_malloc(&bi, 2 * nodes * 8) == hipSuccess && gmk::device_malloc(&bl, 2 * nodes * 4) == hipSuccess &&
-                    gmk::device_malloc(&bf, 2 * nodes * 8) == hipSuccess && gmk::device_malloc(&bo, 2 * nodes) == hipSuccess;
-    if (!ok) {
-        (void)gmk::device_free(bs); (void)gmk::device_free(bi); (void)gmk::device_free(bl); (void)gmk::device_free(bf); (void)gmk::device_free(bo);
-        (void)hipGetLastError();
-        // the handle must stay usable: one arena, as gmk_trad_create leaves it
-        if (gmk::device_malloc(&t->d_stat, nodes * 8) != hipSuccess || gmk::device_malloc(&t->d_info, nodes * 8) != hipSuccess || gmk::device_malloc(&t->d_link, nodes * 4) != hipSuccess ||
-            gmk::device_malloc(&t->d_front, nodes * 8) != hipSuccess || gmk::device_malloc(&t->d_ord, nodes) != hipSuccess)
-            (void)hipGetLastError();
+    if (!arena_alloc(t->block, 2 * nodes)) {
+        (void)arena_alloc(t->a, nodes);                          // the handle must stay usable: one arena, as gmk_trad_create leaves it
         gmk::set_error("gmk_trad_selfplay_run: hipMalloc of two arenas per slot (%zu nodes, %.1f GB) failed", 2 * nodes, 2 * nodes * 29.0 / 1e9);
         return GMK_ERR_HIP;
     }
-    t->block_stat = bs; t->block_info = bi; t->block_link = bl; t->block_front = bf; t->block_ord = bo;
     t->paired = true;
     t->second_arena = true;
     if (!t->d_forced && gmk::device_malloc(&t->d_forced, static_cast<size_t>(t->n_games) * 2) != hipSuccess) { (void)hipGetLastError(); gmk::set_error("gmk_trad_selfplay_run: hipMalloc failed"); return GMK_ERR_HIP; }
@@ -1082,18 +906,18 @@ static int pair_arenas(gmk_trad* t) {
 static int ensure_amaf(gmk_trad* t) {
     const size_t nodes = static_cast<size_t>(t->n_games) * static_cast<size_t>(t->cap);
     if (t->paired) {
-        if (t->block_amaf) return GMK_OK;
-        (void)gmk::device_free(t->d_amaf); (void)gmk::device_free(t->d_amaf2);
-        t->d_amaf = t->d_amaf2 = nullptr;
-        GMK_HIP_CHECK(gmk::device_malloc(&t->block_amaf, 2 * nodes * 8));
-        GMK_HIP_CHECK(hipMemset(t->block_amaf, 0, 2 * nodes * 8));
-        const bool swapped = t->d_stat != t->block_stat;        // (the lock-step loop may have left the halves swapped)
-        t->d_amaf = t->block_amaf + (swapped ? nodes : 0); t->d_amaf2 = t->block_amaf + (swapped ? 0 : nodes);
+        if (t->block.amaf) return GMK_OK;
+        (void)gmk::device_free(t->a.amaf); (void)gmk::device_free(t->b.amaf);
+        t->a.amaf = t->b.amaf = nullptr;
+        GMK_HIP_CHECK(gmk::device_malloc(&t->block.amaf, 2 * nodes * 8));
+        GMK_HIP_CHECK(hipMemset(t->block.amaf, 0, 2 * nodes * 8));
+        const bool swapped = t->a.stat != t->block.stat;        // (the lock-step loop may have left the halves swapped)
+        t->a.amaf = t->block.amaf + (swapped ? nodes : 0); t->b.amaf = t->block.amaf + (swapped ? 0 : nodes);
         return GMK_OK;
     }
-    if (!t->d_amaf) {
-        GMK_HIP_CHECK(gmk::device_malloc(&t->d_amaf, nodes * 8));
-        GMK_HIP_CHECK(hipMemset(t->d_amaf, 0, nodes * 8));
+    if (!t->a.amaf) {
+        GMK_HIP_CHECK(gmk::device_malloc(&t->a.amaf, nodes * 8));
+        GMK_HIP_CHECK(hipMemset(t->a.amaf, 0, nodes * 8));
     }
     return GMK_OK;
 }
@@ -1148,6 +972,17 @@ extern "C" int gmk_trad_set_positions(gmk_trad* t, const uint8_t* h_moves, const
     return GMK_OK;
 }
 
+// what both launches of trad_playouts_kernel are told: one search per game, no self-play loop, no profile (the AMAF array: null but on RAVE handles)
+static TradParams trad_params(const gmk_trad* t, const gmk::DeviceState& st, int playouts, double c_puct) {
+    TradParams prm;
+    prm.states = t->d_states; prm.stat = t->a.stat; prm.info = t->a.info; prm.link = t->a.link; prm.front = t->a.front; prm.ord = t->a.ord; prm.amaf = t->a.amaf; prm.hdr = t->d_hdr;
+    prm.moves = t->d_moves; prm.lens = t->d_lens;
+    prm.g_trans = st.d_trans; prm.g_records = st.d_records; prm.trans_words = st.n_states * 4; prm.record_words = st.n_records * 4 + gmk::kPrefixWords; prm.path_spill = t->d_path_spill;
+    prm.n_games = t->n_games; prm.cap = t->cap; prm.playouts = playouts; prm.c_puct = c_puct;
+    prm.profile = 0; prm.selfplay = 0; prm.sp = TradSelfPlay{};
+    return prm;
+}
+
 // gmk_trad_run / gmk_trad_run_rave: `playouts` playouts per game with RAVE::BackPropogate<rave>
 template <bool kRave>
 static int trad_run(gmk_trad* t, int playouts, double c_puct, void* stream, const char* name) {
@@ -1168,12 +1003,7 @@ static int trad_run(gmk_trad* t, int playouts, double c_puct, void* stream, cons
         GMK_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(trad_playouts_kernel<false, kRave>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
-    TradParams prm;
-    prm.states = t->d_states; prm.stat = t->d_stat; prm.info = t->d_info; prm.link = t->d_link; prm.front = t->d_front; prm.ord = t->d_ord; prm.hdr = t->d_hdr;
-    prm.moves = t->d_moves; prm.lens = t->d_lens;
-    prm.g_trans = st.d_trans; prm.g_records = st.d_records; prm.trans_words = st.n_states * 4; prm.record_words = st.n_records * 4 + gmk::kPrefixWords; prm.path_spill = t->d_path_spill;
-    prm.n_games = t->n_games; prm.cap = t->cap; prm.playouts = playouts; prm.c_puct = c_puct;
-    prm.selfplay = 0; prm.sp = TradSelfPlay{}; prm.amaf = kRave ? t->d_amaf : nullptr;
+    TradParams prm = trad_params(t, st, playouts, c_puct);
     static const bool profile = gmk::profile_env("GMK_TRAD_PROFILE") != nullptr;
     prm.profile = profile ? 1 : 0;
     const int grid = (t->n_games + kGamesPerBlock - 1) / kGamesPerBlock;
@@ -1203,47 +1033,46 @@ extern "C" int gmk_trad_root_stats(gmk_trad* t, uint32_t* h_visits, float* h_val
                                    uint32_t* h_root_visits, float* h_root_value, int32_t* h_n_nodes, int32_t* h_status,
                                    uint64_t* h_evaluator_updates);
 
-// the second arena of gmk_trad_step / gmk_trad_step_device (and d_forced), allocated by the first call; the AMAF block follows the first one
+// the second arena of gmk_trad_step / gmk_trad_step_device / the lock-step self-play loop (and d_forced), allocated by the first call, all or
+// nothing: a later call must not find half an arena.  The AMAF array follows the first arena's: a RAVE handle's trees carry theirs along.
 static int trad_second_arena(gmk_trad* t, const char* name) {
     const size_t n = static_cast<size_t>(t->n_games), nodes = n * static_cast<size_t>(t->cap);
     if (!t->second_arena) {
-        const bool ok = gmk::device_malloc(&t->d_stat2, nodes * 8) == hipSuccess && gmk::device_malloc(&t->d_info2, nodes * 8) == hipSuccess &&
-                        gmk::device_malloc(&t->d_link2, nodes * 4) == hipSuccess && gmk::device_malloc(&t->d_front2, nodes * 8) == hipSuccess &&
-                        gmk::device_malloc(&t->d_ord2, nodes) == hipSuccess && gmk::device_malloc(&t->d_forced, n * 2) == hipSuccess;
-        if (!ok) {                                                  // all or nothing: a later call must not find half an arena
-            (void)gmk::device_free(t->d_stat2); (void)gmk::device_free(t->d_info2); (void)gmk::device_free(t->d_link2); (void)gmk::device_free(t->d_front2); (void)gmk::device_free(t->d_ord2); (void)gmk::device_free(t->d_forced);
-            t->d_stat2 = t->d_info2 = t->d_front2 = nullptr; t->d_link2 = nullptr; t->d_ord2 = nullptr; t->d_forced = nullptr;
+        if (!arena_alloc(t->b, nodes) || gmk::device_malloc(&t->d_forced, n * 2) != hipSuccess) {
+            arena_free(t->b);
+            (void)gmk::device_free(t->d_forced);
+            t->d_forced = nullptr;
             (void)hipGetLastError();
             gmk::set_error("%s: hipMalloc of the second arena (%zu nodes) failed", name, nodes);
             return GMK_ERR_HIP;
         }
         t->second_arena = true;
     }
+    if (t->a.amaf && !t->b.amaf && gmk::device_malloc(&t->b.amaf, nodes * 8) != hipSuccess) { gmk::set_error("%s: hipMalloc of the second arena (%zu nodes) failed", name, nodes); return GMK_ERR_HIP; }
     return GMK_OK;
 }
+
+// the step kernels left every game's tree in the other arena
+static void trad_flip(gmk_trad* t) { std::swap(t->a, t->b); }
 
 extern "C" int gmk_trad_step(gmk_trad* t, const int16_t* h_moves) {
     if (!t) { gmk::set_error("gmk_trad_step: bad arguments"); return GMK_ERR_ARG; }
     if (!t->positioned) { gmk::set_error("gmk_trad_step: gmk_trad_set_positions has not been called"); return GMK_ERR_STATE; }
-    const size_t n = static_cast<size_t>(t->n_games), nodes = n * static_cast<size_t>(t->cap);
     if (const int rc = trad_second_arena(t, "gmk_trad_step"); rc != GMK_OK) return rc;
     GMK_HIP_CHECK(hipDeviceSynchronize());
-    if (h_moves) GMK_HIP_CHECK(hipMemcpy(t->d_forced, h_moves, n * 2, hipMemcpyHostToDevice));
-    if (t->d_amaf && !t->d_amaf2 && gmk::device_malloc(&t->d_amaf2, nodes * 8) != hipSuccess) { gmk::set_error("gmk_trad_step: hipMalloc of the second arena (%zu nodes) failed", nodes); return GMK_ERR_HIP; }
-    const TradArena a = t->arena(), b = t->arena2();
-    hipLaunchKernelGGL(trad_step_kernel, dim3(t->n_games), dim3(64), 0, nullptr, a, b, t->d_hdr, t->cap, t->n_games,
+    if (h_moves) GMK_HIP_CHECK(hipMemcpy(t->d_forced, h_moves, static_cast<size_t>(t->n_games) * 2, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(trad_step_kernel, dim3(t->n_games), dim3(64), 0, nullptr, t->a, t->b, t->d_hdr, t->cap, t->n_games,
                        h_moves ? t->d_forced : nullptr, t->d_moves, t->d_lens);
     GMK_HIP_CHECK(hipGetLastError());
     GMK_HIP_CHECK(hipDeviceSynchronize());
-    std::swap(t->d_stat, t->d_stat2); std::swap(t->d_info, t->d_info2); std::swap(t->d_link, t->d_link2);
-    std::swap(t->d_front, t->d_front2); std::swap(t->d_ord, t->d_ord2); std::swap(t->d_amaf, t->d_amaf2);
+    trad_flip(t);
     return GMK_OK;
 }
 
 extern "C" int gmk_trad_root_choice(gmk_trad* t, int16_t* d_cells, uint16_t* d_visits, void* stream) {
     if (!t || !d_cells) { gmk::set_error("gmk_trad_root_choice: bad arguments"); return GMK_ERR_ARG; }
     if (!t->positioned) { gmk::set_error("gmk_trad_root_choice: gmk_trad_set_positions has not been called"); return GMK_ERR_STATE; }
-    hipLaunchKernelGGL(trad_root_choice_kernel, dim3(t->n_games), dim3(64), 0, static_cast<hipStream_t>(stream), t->arena(), t->d_hdr, t->cap, t->n_games, d_cells, d_visits);
+    hipLaunchKernelGGL(trad_root_choice_kernel, dim3(t->n_games), dim3(64), 0, static_cast<hipStream_t>(stream), t->a, t->d_hdr, t->cap, t->n_games, d_cells, d_visits);
     GMK_HIP_CHECK(hipGetLastError());
     return GMK_OK;
 }
@@ -1252,18 +1081,12 @@ extern "C" int gmk_trad_root_choice(gmk_trad* t, int16_t* d_cells, uint16_t* d_v
 extern "C" int gmk_trad_step_device(gmk_trad* t, const int16_t* d_cells, const int32_t* d_verdict, int fresh_root, void* stream) {
     if (!t || !d_cells || !d_verdict) { gmk::set_error("gmk_trad_step_device: bad arguments"); return GMK_ERR_ARG; }
     if (!t->positioned) { gmk::set_error("gmk_trad_step_device: gmk_trad_set_positions has not been called"); return GMK_ERR_STATE; }
-    if (!fresh_root) {
-        const size_t nodes = static_cast<size_t>(t->n_games) * static_cast<size_t>(t->cap);
+    if (!fresh_root)
         if (const int rc = trad_second_arena(t, "gmk_trad_step_device"); rc != GMK_OK) return rc;
-        if (t->d_amaf && !t->d_amaf2 && gmk::device_malloc(&t->d_amaf2, nodes * 8) != hipSuccess) { gmk::set_error("gmk_trad_step_device: hipMalloc of the second arena (%zu nodes) failed", nodes); return GMK_ERR_HIP; }
-    }
-    hipLaunchKernelGGL(trad_step_device_kernel, dim3(t->n_games), dim3(64), 0, static_cast<hipStream_t>(stream), t->arena(), t->arena2(), t->d_hdr, t->cap, t->n_games,
+    hipLaunchKernelGGL(trad_step_device_kernel, dim3(t->n_games), dim3(64), 0, static_cast<hipStream_t>(stream), t->a, t->b, t->d_hdr, t->cap, t->n_games,
                        d_cells, d_verdict, fresh_root ? 1 : 0, t->d_moves, t->d_lens);
     GMK_HIP_CHECK(hipGetLastError());
-    if (!fresh_root) {
-        std::swap(t->d_stat, t->d_stat2); std::swap(t->d_info, t->d_info2); std::swap(t->d_link, t->d_link2);
-        std::swap(t->d_front, t->d_front2); std::swap(t->d_ord, t->d_ord2); std::swap(t->d_amaf, t->d_amaf2);
-    }
+    if (!fresh_root) trad_flip(t);
     return GMK_OK;
 }
 
@@ -1275,7 +1098,7 @@ extern "C" int gmk_trad_add_root_noise(gmk_trad* t, float alpha, float epsilon, 
     if (!t->positioned) { gmk::set_error("gmk_trad_add_root_noise: gmk_trad_set_positions has not been called"); return GMK_ERR_STATE; }
     const size_t n = static_cast<size_t>(t->n_games);
     if (t->noise_sampler == GMK_NOISE_SAMPLER_COUNTER) {        // drawn on the device, one wavefront per game: nothing comes back to the host
-        hipLaunchKernelGGL(trad_root_noise_kernel, dim3(t->n_games), dim3(64), 0, static_cast<hipStream_t>(stream), t->arena(), t->d_hdr, t->cap, t->d_lens, t->d_game_ids, first_game_id,
+        hipLaunchKernelGGL(trad_root_noise_kernel, dim3(t->n_games), dim3(64), 0, static_cast<hipStream_t>(stream), t->a, t->d_hdr, t->cap, t->d_lens, t->d_game_ids, first_game_id,
                            alpha, epsilon, static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32));
         GMK_HIP_CHECK(hipGetLastError());
         return GMK_OK;
@@ -1294,8 +1117,7 @@ extern "C" int gmk_trad_add_root_noise(gmk_trad* t, float alpha, float epsilon, 
     });
     if (!t->d_priors) GMK_HIP_CHECK(gmk::device_malloc(&t->d_priors, n * 225 * 4));
     GMK_HIP_CHECK(hipMemcpy(t->d_priors, priors.data(), n * 225 * 4, hipMemcpyHostToDevice));
-    const TradArena a = t->arena();
-    hipLaunchKernelGGL(trad_set_root_priors_kernel, dim3(t->n_games), dim3(64), 0, nullptr, a, t->d_hdr, t->cap, t->d_priors);
+    hipLaunchKernelGGL(trad_set_root_priors_kernel, dim3(t->n_games), dim3(64), 0, nullptr, t->a, t->d_hdr, t->cap, t->d_priors);
     GMK_HIP_CHECK(hipGetLastError());
     GMK_HIP_CHECK(hipDeviceSynchronize());
     return GMK_OK;
@@ -1316,7 +1138,7 @@ extern "C" int gmk_trad_root_stats(gmk_trad* t, uint32_t* h_visits, float* h_val
     GMK_TRY(gmk::device_malloc(&d_best, n * 4)); GMK_TRY(gmk::device_malloc(&d_root_visits, n * 4)); GMK_TRY(gmk::device_malloc(&d_root_value, n * 4));
     GMK_TRY(hipMemset(d_visits, 0, n * 225 * 4)); GMK_TRY(hipMemset(d_values, 0, n * 225 * 4)); GMK_TRY(hipMemset(d_priors, 0, n * 225 * 4));
     GMK_TRY(hipDeviceSynchronize());                             // a search may still be running on a stream of the caller's
-    hipLaunchKernelGGL(trad_root_stats_kernel, dim3(t->n_games), dim3(64), 0, nullptr, t->d_stat, t->d_info, t->d_link, t->d_ord, t->d_hdr, t->cap,
+    hipLaunchKernelGGL(trad_root_stats_kernel, dim3(t->n_games), dim3(64), 0, nullptr, t->a, t->d_hdr, t->cap,
                        d_visits, d_values, d_priors, d_best, d_root_visits, d_root_value);
     GMK_TRY(hipGetLastError());
     GMK_TRY(hipDeviceSynchronize());
@@ -1431,21 +1253,6 @@ extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int policy, int n_total, uint3
     GMK_TRY(hipMemcpy(d_moves, first_moves.data(), nt * 225, hipMemcpyHostToDevice));
     GMK_TRY(hipMemcpy(d_lens, open_lens.data(), nt * 4, hipMemcpyHostToDevice));
     GMK_TRY(hipMemset(d_winner, 0, nt));
-    if (reuse_subtree && !t->second_arena) {                     // the arenas flip at every step (as gmk_trad_step)
-        const size_t nodes = ns * static_cast<size_t>(t->cap);
-        const bool ok = gmk::device_malloc(&t->d_stat2, nodes * 8) == hipSuccess && gmk::device_malloc(&t->d_info2, nodes * 8) == hipSuccess &&
-                        gmk::device_malloc(&t->d_link2, nodes * 4) == hipSuccess && gmk::device_malloc(&t->d_front2, nodes * 8) == hipSuccess &&
-                        gmk::device_malloc(&t->d_ord2, nodes) == hipSuccess && gmk::device_malloc(&t->d_forced, ns * 2) == hipSuccess;
-        if (!ok) {
-            (void)gmk::device_free(t->d_stat2); (void)gmk::device_free(t->d_info2); (void)gmk::device_free(t->d_link2); (void)gmk::device_free(t->d_front2); (void)gmk::device_free(t->d_ord2); (void)gmk::device_free(t->d_forced);
-            t->d_stat2 = t->d_info2 = t->d_front2 = nullptr; t->d_link2 = nullptr; t->d_ord2 = nullptr; t->d_forced = nullptr;
-            (void)hipGetLastError();
-            gmk::set_error("gmk_trad_selfplay_run: hipMalloc of the second arena (%zu nodes) failed", nodes);
-            cleanup();
-            return GMK_ERR_HIP;
-        }
-        t->second_arena = true;
-    }
     TradSelfPlay sp;
     sp.slot_game = d_state; sp.next_game = d_state + ns; sp.unfinished = d_state + ns + 1; sp.overflow = d_state + ns + 2;
     sp.n_total = n_total; sp.open_moves = d_open_moves; sp.open_lens = d_open_lens; sp.open_stride = open_stride;
@@ -1468,12 +1275,8 @@ extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int policy, int n_total, uint3
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             attr_set = true;
         }
-        TradParams prm;
-        prm.states = t->d_states; prm.stat = t->d_stat; prm.info = t->d_info; prm.link = t->d_link; prm.front = t->d_front; prm.ord = t->d_ord; prm.hdr = t->d_hdr;
-        prm.moves = t->d_moves; prm.lens = t->d_lens;
-        prm.g_trans = st.d_trans; prm.g_records = st.d_records; prm.trans_words = st.n_states * 4; prm.record_words = st.n_records * 4 + gmk::kPrefixWords; prm.path_spill = t->d_path_spill;
-        prm.n_games = n_slots; prm.cap = t->cap; prm.playouts = playouts; prm.c_puct = c_puct;
-        prm.profile = 0; prm.selfplay = 1; prm.sp = sp; prm.amaf = rave ? t->d_amaf : nullptr;
+        TradParams prm = trad_params(t, st, playouts, c_puct);
+        prm.selfplay = 1; prm.sp = sp;
         if (rave) hipLaunchKernelGGL((trad_playouts_kernel<true, true>), dim3((n_slots + kGamesPerBlock - 1) / kGamesPerBlock), dim3(kThreads), lds, s, prm);
         else hipLaunchKernelGGL((trad_playouts_kernel<true, false>), dim3((n_slots + kGamesPerBlock - 1) / kGamesPerBlock), dim3(kThreads), lds, s, prm);
         GMK_TRY(hipGetLastError());
@@ -1484,7 +1287,7 @@ extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int policy, int n_total, uint3
     const long long step_limit = max_steps > 0 ? max_steps : 226ll * (n_total / n_slots + 2);
     for (long long step = 0; step < step_limit && !persistent; ++step) {
         if (noise_alpha > 0.0f && t->noise_sampler == GMK_NOISE_SAMPLER_COUNTER) {     // ... drawn on the device, keyed by the game a slot plays (d_game_ids: the refill kernel keeps it)
-            hipLaunchKernelGGL(trad_root_noise_kernel, dim3(n_slots), dim3(64), 0, s, t->arena(), t->d_hdr, t->cap, t->d_lens, t->d_game_ids, first_game_id,
+            hipLaunchKernelGGL(trad_root_noise_kernel, dim3(n_slots), dim3(64), 0, s, t->a, t->d_hdr, t->cap, t->d_lens, t->d_game_ids, first_game_id,
                                noise_alpha, noise_epsilon, static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32));
             GMK_TRY(hipGetLastError());
         } else if (noise_alpha > 0.0f) {                        // Default::AddNoise at the start of every search (MCTS.cpp:182), keyed by the GAME a slot plays
@@ -1496,19 +1299,16 @@ extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int policy, int n_total, uint3
         rc = policy == 1 ? gmk_trad_run_poolrave(t, playouts, c_puct, seed, first_game_id, s)
            : policy == 2 ? gmk_trad_run_rave(t, playouts, c_puct, s) : gmk_trad_run(t, playouts, c_puct, s);
         if (rc != GMK_OK) break;
-        if (reuse_subtree && t->d_amaf && !t->d_amaf2) GMK_TRY(gmk::device_malloc(&t->d_amaf2, ns * static_cast<size_t>(t->cap) * 8));
+        if (reuse_subtree && (rc = trad_second_arena(t, "gmk_trad_selfplay_run")) != GMK_OK) break;     // the arenas flip at every step (as gmk_trad_step)
         GMK_TRY(hipMemsetAsync(sp.unfinished, 0, 4, s));
-        hipLaunchKernelGGL(trad_advance_kernel, dim3(n_slots), dim3(64), 0, s, t->arena(), t->arena2(), t->d_hdr, t->cap, n_slots, t->d_moves, t->d_lens, sp, reuse_subtree ? 1 : 0);
+        hipLaunchKernelGGL(trad_advance_kernel, dim3(n_slots), dim3(64), 0, s, t->a, t->b, t->d_hdr, t->cap, n_slots, t->d_moves, t->d_lens, sp, reuse_subtree ? 1 : 0);
         hipLaunchKernelGGL(trad_refill_kernel, dim3(1), dim3(64), 0, s, t->d_hdr, n_slots, t->d_moves, t->d_lens, sp);
         GMK_TRY(hipGetLastError());
         ++steps;
         int32_t unfinished = 0;
         GMK_TRY(hipMemcpyAsync(&unfinished, sp.unfinished, 4, hipMemcpyDeviceToHost, s));
         GMK_TRY(hipStreamSynchronize(s));
-        if (reuse_subtree) {
-            std::swap(t->d_stat, t->d_stat2); std::swap(t->d_info, t->d_info2); std::swap(t->d_link, t->d_link2);
-            std::swap(t->d_front, t->d_front2); std::swap(t->d_ord, t->d_ord2); std::swap(t->d_amaf, t->d_amaf2);
-        }
+        if (reuse_subtree) trad_flip(t);
         if (unfinished == 0) break;
     }
     int32_t overflow = 0;

@@ -7,12 +7,19 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <utility>
 #include <vector>
+
+#include "board_device.h"
+#include "wave_fence.h"
 
 namespace gmk {
 namespace tree {
 
+using gmk::wave_phase_fence;
+
 constexpr uint32_t kNoParent = 0xFFFFFFu;
+constexpr uint32_t kNoChild = 0xFFFFFFFFu;       // most_visited_child / child_of_cell: the node has no such child
 
 constexpr uint32_t kStatusIdleSlot = 16u;        // continuous batching (gmk_trad_selfplay_run): the slot's games have run out, the searches skip it
 
@@ -86,21 +93,152 @@ __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
     return min(min(a, b), min(c, d));
 }
 
+// ---- the root's move, once: what the searches' step, advance, statistics and self-play kernels share ----
+// All of it is one wavefront's work on ONE game: the pointers are offset to the game's arena, `first` and `n` are the root's child range.
+// Where a piece has two phases that hand data to each other, the caller passes how ITS lanes meet -- the scopes differ and stay as they
+// are: the persistent turn of trad_playouts_kernel is one wavefront of a 512-thread workgroup (SyncWave; copy_sync<true> around
+// copy_subtree), the one-wavefront kernels are whole workgroups (SyncBlock; copy_sync<false>).
+struct SyncWave { __device__ __forceinline__ void operator()() const { wave_phase_fence(); } };
+struct SyncBlock { __device__ __forceinline__ void operator()() const { __syncthreads(); } };
+
+// MCTS::stepForward()'s choice (MCTS.cpp:129-134): the most visited child, among equals the one that is first in the CURRENT child order
+// (a child without visits counts: of unvisited children the first is taken).  The node id, kNoChild when n == 0.
+__device__ __forceinline__ uint32_t most_visited_child(const uint2* stat, const uint8_t* ord, uint32_t first, uint32_t n, int lane) {
+    uint32_t best = 0u, best_ord = 0u, best_id = kNoChild;      // best: visits + 1, 0 = no child yet
+    const auto take_if_better = [&](uint32_t v, uint32_t o, uint32_t id) {
+        if (v > best || (v == best && v != 0u && o < best_ord)) { best = v; best_ord = o; best_id = id; }
+    };
+    for (uint32_t i = lane; i < n; i += 64) take_if_better(stat[first + i].x + 1u, ord[first + i], first + i);
+    for (int s = 32; s > 0; s >>= 1) {
+        const uint32_t v = __shfl_down(best, s), o = __shfl_down(best_ord, s), id = __shfl_down(best_id, s);
+        take_if_better(v, o, id);
+    }
+    return __shfl(best_id, 0);
+}
+
+// MCTS::stepForward(move)'s search (MCTS.cpp:136-139): the child of that cell (a cell has at most one), kNoChild without one
+__device__ __forceinline__ uint32_t child_of_cell(const uint2* info, uint32_t first, uint32_t n, uint32_t cell, int lane) {
+    uint32_t id = kNoChild;
+    for (uint32_t i = lane; i < n; i += 64) if ((info[first + i].x >> 24) == cell) id = first + i;
+    for (int s = 32; s > 0; s >>= 1) id = min(id, static_cast<uint32_t>(__shfl_xor(id, s)));
+    return id;
+}
+
+// the children's visit counts by cell, saturated at 65 535: a searched ply's row of a game's record, the referee's row
+template <class Sync>
+__device__ __forceinline__ void visits_by_cell(uint16_t* row, const uint2* stat, const uint2* info, uint32_t first, uint32_t n, int lane, Sync sync) {
+    for (int i = lane; i < 225; i += 64) row[i] = 0;
+    sync();
+    for (uint32_t i = lane; i < n; i += 64) row[info[first + i].x >> 24] = static_cast<uint16_t>(min(stat[first + i].x, 65535u));
+}
+
+// Board::applyMove's victory check (Game.cpp:37-49, 88-136) for `cell` played after moves[0 .. len): the board after the move as row
+// words in rows[0 .. 16) (the caller's LDS; move i is black's when i is even, white's stones 16 bits up), five or more through the cell
+// win.  The winner: +1 black, -1 white, 0 nobody (yet).
+template <class Sync>
+__device__ __forceinline__ int play_cell(const uint8_t* moves, int len, uint32_t cell, uint32_t* rows, int lane, Sync sync) {
+    if (lane < 16) rows[lane] = 0u;
+    sync();
+    for (int i = lane; i < len; i += 64) atomicOr(&rows[moves[i] / 15u], 1u << (moves[i] % 15u + ((i & 1) ? 16u : 0u)));
+    const int shift = (len & 1) ? 16 : 0;
+    if (lane == 0) atomicOr(&rows[cell / 15u], 1u << (cell % 15u + shift));
+    sync();
+    const bool five = gmk::five_through<1>(rows, static_cast<int>(cell % 15u), static_cast<int>(cell / 15u), shift);
+    return five ? (shift ? -1 : 1) : 0;
+}
+
+// is `cell` a move that moves[0 .. len) allows: on the board, the board not full, the cell not taken (one answer for the wavefront)
+__device__ __forceinline__ bool legal_reply(const uint8_t* moves, int len, uint32_t cell, int lane) {
+    bool legal = cell < 225u && len < 225;
+    for (int i = lane; i < len; i += 64) legal &= moves[i] != cell;
+    return __all(legal);
+}
+
+// MCTS::reset / stepForward(move) without such a child (MCTS.cpp:140-145): the game's tree is one childless root behind `cell` (255: the
+// empty board), written by ONE lane; amaf: the nodes carry AMAF statistics.  A root's `ord` is never read (the backup and the root choice read their CHILDREN's) and a childless
+// node's `front` is not either (select follows it only where link >> 24 != 0): `ord` is written because some callers always did, `front` by none.
+__device__ __forceinline__ void new_root(const TradArena& a, size_t base, uint32_t cell, bool amaf) {
+    a.stat[base] = make_uint2(0u, 0u);
+    a.info[base] = make_uint2(kNoParent | (cell << 24), __float_as_uint(1.0f));
+    a.link[base] = 0u;
+    a.ord[base] = 0;
+    if (amaf) a.amaf[base] = make_uint2(0u, 0u);
+}
+
+// MCTS::stepForward() / stepForward(move) (MCTS.cpp:129-147): the chosen child's subtree becomes the tree.  The reference
+// frees the siblings; here the kept subtree is copied level by level into the other arena so that node indices stay dense
+// (children consecutive, the root at 0).  A copied node carries its OLD child range and OLD first-child record until the
+// scan reaches it, copies its children and rewrites both.  One wavefront per game.
+// kWaveOnly: the caller is one wavefront of a larger workgroup (the persistent self-play loop of trad_playouts_kernel): its lanes meet at a
+// wavefront barrier with workgroup-scope fences (the CU's L1 is shared by the workgroup) instead of __syncthreads().
+template <bool kWaveOnly>
+__device__ __forceinline__ void copy_sync() {
+    if constexpr (kWaveOnly) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    } else {
+        __syncthreads();
+    }
+}
+
+// The subtree of node src_root of arena a becomes the tree of arena b, level by level (see above); one wavefront.  Returns the node count.
+template <bool kWaveOnly>
+__device__ uint32_t copy_subtree(const TradArena& a, const TradArena& b, size_t base, uint32_t src_root, int lane) {
+    if (lane == 0) {
+        b.stat[base] = a.stat[base + src_root];
+        b.info[base] = make_uint2(kNoParent | (a.info[base + src_root].x & 0xFF000000u), a.info[base + src_root].y);
+        b.link[base] = a.link[base + src_root];
+        b.front[base] = a.front[base + src_root];
+        b.ord[base] = 0;
+        if (a.amaf) b.amaf[base] = a.amaf[base + src_root];
+    }
+    copy_sync<kWaveOnly>();
+    uint32_t next = 1;
+    for (uint32_t i0 = 0, chunk = 0; i0 < next; i0 += chunk) {
+        chunk = min(64u, next - i0);                            // nodes appended while this chunk is handled come after it
+        const uint32_t old_link = static_cast<uint32_t>(lane) < chunk ? b.link[base + i0 + lane] : 0u;
+        unsigned long long todo = __ballot((old_link >> 24) != 0u);
+        while (todo) {
+            const int j = __ffsll(static_cast<long long>(todo)) - 1;
+            todo &= todo - 1ull;
+            const uint32_t ol = __shfl(old_link, j), of = ol & 0xFFFFFFu, nk = ol >> 24, node = i0 + static_cast<uint32_t>(j);
+            for (uint32_t k = lane; k < nk; k += 64) {
+                const uint2 inf = a.info[base + of + k];
+                b.stat[base + next + k] = a.stat[base + of + k];
+                b.info[base + next + k] = make_uint2(node | (inf.x & 0xFF000000u), inf.y);
+                b.link[base + next + k] = a.link[base + of + k];
+                b.front[base + next + k] = a.front[base + of + k];
+                b.ord[base + next + k] = a.ord[base + of + k];
+                if (a.amaf) b.amaf[base + next + k] = a.amaf[base + of + k];
+            }
+            if (lane == 0) {
+                const uint32_t new_link = next | (nk << 24);
+                b.link[base + node] = new_link;
+                const uint2 fr = b.front[base + node];              // still the OLD id of the first child in the current order
+                b.front[base + node] = make_uint2((next + ((fr.x & 0xFFFFFFu) - of)) | (fr.x & 0xFF000000u), fr.y);
+                if (node != 0u) {                                   // am I my parent's first child?  then its record of me carries my child range
+                    const uint32_t p = b.info[base + node].x & 0xFFFFFFu;
+                    const uint2 pf = b.front[base + p];
+                    if ((pf.x & 0xFFFFFFu) == node) b.front[base + p] = make_uint2(pf.x, new_link);
+                }
+            }
+            next += nk;
+            copy_sync<kWaveOnly>();
+        }
+        copy_sync<kWaveOnly>();                                        // children written above are scanned below
+    }
+    return next;
+}
+
 }  // namespace tree
 }  // namespace gmk
 
 struct gmk_trad {
     int n_games = 0, cap = 0;
     uint32_t* d_states = nullptr;
-    uint2 *d_stat = nullptr, *d_info = nullptr;
-    uint32_t* d_link = nullptr;
-    uint2* d_front = nullptr;
-    uint8_t* d_ord = nullptr;
-    uint2* d_amaf = nullptr;                                                // allocated by the first gmk_trad_run_poolrave / gmk_trad_run_rave
-    uint2 *d_stat2 = nullptr, *d_info2 = nullptr, *d_front2 = nullptr;      // second arena, allocated by the first gmk_trad_step
-    uint32_t* d_link2 = nullptr;
-    uint8_t* d_ord2 = nullptr;
-    uint2* d_amaf2 = nullptr;
+    gmk::tree::TradArena a{}, b{};               // the arena that holds the trees; the other one (trad_second_arena: the step kernels copy the kept subtrees into it, then the two flip)
+                                                 // a.amaf: made by the first gmk_trad_run_poolrave / gmk_trad_run_rave; b.amaf follows it
     int16_t* d_forced = nullptr;
     float* d_priors = nullptr;
     gmk::tree::TradHeader* d_hdr = nullptr;
@@ -115,16 +253,10 @@ struct gmk_trad {
     int lockstep = 0;
     // the persistent loop with kept subtrees wants a slot's two arenas a fixed distance apart: both halves of ONE allocation per array
     bool paired = false;
-    uint2 *block_stat = nullptr, *block_info = nullptr, *block_front = nullptr;
-    uint32_t* block_link = nullptr;
-    uint8_t* block_ord = nullptr;
-    uint2* block_amaf = nullptr;                                            // TraditionalPolicy + RAVE handles: the sixth block (ensure_amaf, trad_kernel.hip)
+    gmk::tree::TradArena block{};                // a and b are its halves then; block.amaf (TraditionalPolicy + RAVE handles): ensure_amaf, trad_kernel.hip
     void* d_ensemble = nullptr;                                             // accumulators of gmk_trad_ensemble_merge (ensemble_kernel.hip), [ensemble_capacity] ensembles
     int ensemble_capacity = 0;
-    size_t arena_stride() const { return (paired && d_stat2 > d_stat) ? static_cast<size_t>(d_stat2 - d_stat) : 0; }
+    size_t arena_stride() const { return (paired && b.stat > a.stat) ? static_cast<size_t>(b.stat - a.stat) : 0; }
     int policy = 0;                                                          // 0 not searched yet, 1 TraditionalPolicy (gmk_trad_run), 2 PoolRAVEPolicy (gmk_trad_run_poolrave),
                                                                              // 3 TraditionalPolicy + RAVE (gmk_trad_run_rave): one per handle
-
-    gmk::tree::TradArena arena() const { return {d_stat, d_info, d_link, d_front, d_ord, d_amaf}; }
-    gmk::tree::TradArena arena2() const { return {d_stat2, d_info2, d_link2, d_front2, d_ord2, d_amaf2}; }
 };
