@@ -6,6 +6,7 @@ Replaces the reference's data generation loop -- `network/data_helper.py:58-83` 
 GPU (K3 + `gmk_mcts_advance`) sharded over ranks by global game id, and ONE gather of the compact records
 (moves, per-move root visit counts, winner) to rank 0 over `torch.distributed` (RCCL on MI355X, gloo on CPU).
 """
+import contextlib
 import os
 
 import numpy as np
@@ -116,6 +117,98 @@ def plan_games(n_games, slots="auto", handles="auto", opening_plies=0, reuse_sub
     return [(lo, hi, min(hi - lo, -(-total_slots // handles))) for lo, hi in blocks]
 
 
+# ---- the rules every game loop below shares, each defined once ("Host-side pieces") ----
+def _device(device):
+    """(torch device, the handle of its current stream) of a game loop, the library initialised on it; None = the current device."""
+    G.init(torch.cuda.current_device() if device is None else device.index)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    return dev, torch.cuda.current_stream(dev).cuda_stream
+
+
+def _opening(n_games, seed, first_game_id, opening_plies):
+    """(moves uint8[n, 225], lens int32[n]): game g opens with the first opening_plies plies of the synthetic game first_game_id + g
+    (fewer where that game is shorter); zeros past an opening's end."""
+    moves, lens = np.zeros((n_games, N), dtype=np.uint8), np.zeros(n_games, dtype=np.int32)
+    if opening_plies > 0 and n_games > 0:
+        m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
+        lens = np.minimum(l, opening_plies).astype(np.int32)
+        moves[:, :m.shape[1]] = np.where(np.arange(m.shape[1])[None, :] < lens[:, None], m, 0)
+    return moves, lens
+
+
+def _last_two(moves, lens):
+    """int16[n, 2]: the last move of every row and the one before it, -1 where there is none"""
+    last = np.full((len(lens), 2), -1, dtype=np.int16)
+    g = np.arange(len(lens))
+    has1, has2 = lens > 0, lens > 1
+    last[has1, 0] = moves[g[has1], lens[has1] - 1]
+    last[has2, 1] = moves[g[has2], lens[has2] - 2]
+    return last
+
+
+# Default nodes per game of a searcher, by entry point: (nodes a playout can add, spare nodes, clamped to the 24-bit node index).  The spellings
+# differ for no recorded reason (K3 expands 225 children and is not clamped, K6 / K8 count the root's 226th); they are kept as they were.
+_ARENA = {"games": (N, 1, False), "supervisor": (226, 1, True), "network": (N, 1, True), "match": (226, 256, True)}
+
+
+def _arena_nodes(entry, playouts, kept_subtree=False, node_capacity=None):
+    """node_capacity if given, else the default of `entry` (_ARENA) for searches of `playouts` playouts: one search's worth of nodes, three
+    with kept subtrees."""
+    if node_capacity is not None:
+        return node_capacity
+    per_playout, spare, clamped = _ARENA[entry]
+    nodes = (3 if kept_subtree else 1) * playouts * per_playout + spare
+    return min(nodes, (1 << 24) - 1) if clamped else nodes
+
+
+def _arena_full(status, bit):
+    """Whether a tree arena filled up in some search: `bit` (the handle class's STATUS_ARENA_FULL) in root_stats()' status words."""
+    return bool((status & bit).any())
+
+
+def _record_tensors(n_games, dev, opening=None, visits=True):
+    """(moves uint8[n, 225], lens int32[n], winner int8[n], visits int16[n, 225, 225] or None) on the device for a device-resident loop
+    to fill: zeros, or the games' openings = host arrays (moves, lens) as _opening returns and _HostGames holds them."""
+    d_moves = torch.zeros((n_games, N), dtype=torch.uint8, device=dev) if opening is None else torch.from_numpy(opening[0]).to(dev)
+    d_lens = torch.zeros(n_games, dtype=torch.int32, device=dev) if opening is None else torch.from_numpy(opening[1]).to(dev)
+    d_winner = torch.zeros(n_games, dtype=torch.int8, device=dev)
+    return d_moves, d_lens, d_winner, torch.zeros((n_games, N, N), dtype=torch.int16, device=dev) if visits else None
+
+
+def _records_from_host(games, visits, dev, first_game_id, overflow):
+    """The GameRecords of a host-driven loop: its _HostGames and its ledger visits uint16[n, 225, 225], carried as int16 like the device's"""
+    return GameRecords(torch.from_numpy(games.moves).to(dev), torch.from_numpy(games.lens).to(dev), torch.from_numpy(games.winner).to(dev),
+                       torch.from_numpy(visits.view(np.int16)).to(dev), first_game_id, overflow)
+
+
+def _hand_over(active, over, waiting):
+    """Continuous batching on the host: active int[slots] = the game in each slot, over bool[n], waiting = the games not started yet, a list in
+    game order.  The lowest slots whose game is over take the next waiting games (both changed in place); returns bool[slots], the slots
+    that changed hands."""
+    take = np.nonzero(over[active])[0][:len(waiting)]
+    active[take] = waiting[:len(take)]
+    del waiting[:len(take)]
+    fresh = np.zeros(len(active), dtype=bool)
+    fresh[take] = True
+    return fresh
+
+
+def _agent_tree(kind, kw, n, cap, seed, first_game_id):
+    """The lib handle of n searches by an agent of the reference's schedule (agents/__init__.py AGENT_MAP, config.py:9-19): kind
+    "traditional_mcts" (K6; with kw["use_rave"] K6 + RAVE, TraditionalAgent(c_puct, c_bias, use_rave=True), agents/mcts.py:44-47), "rave_mcts" (K8)
+    or "random_mcts" (K3), kw its c_puct / c_bias / c_rollouts, cap its nodes per game.  None for a name it does not know."""
+    c_puct = float(kw.get("c_puct", 5.0))
+    if kind == "traditional_mcts" and kw.get("use_rave"):
+        return G.TraditionalRAVEMCTS(n, node_capacity=cap, c_puct=c_puct, c_bias=float(kw.get("c_bias", 0.0)))
+    if kind == "traditional_mcts":
+        return G.TraditionalMCTS(n, node_capacity=cap, c_puct=c_puct)
+    if kind == "rave_mcts":
+        return G.PoolRAVEMCTS(n, node_capacity=cap, c_puct=c_puct, seed=seed, first_game_id=first_game_id)
+    if kind == "random_mcts":
+        return G.BatchedMCTS(n, c_puct=c_puct, c_rollouts=int(kw.get("c_rollouts", 5)), seed=seed, node_capacity=cap)
+    return None
+
+
 def play_games(n_games, playouts, seed=G.DEFAULT_SEED, first_game_id=0, c_puct=5.0, c_rollouts=5,
                opening_plies=0, record_visits=True, reuse_subtree=False, root_noise=None, max_moves=N, device=None,
                node_capacity=None, slots="auto", handles="auto", noise_sampler="counter", lockstep=False, prepare_only=False):
@@ -135,105 +228,84 @@ def play_games(n_games, playouts, seed=G.DEFAULT_SEED, first_game_id=0, c_puct=5
     prepare_only: create the search handles this call would create, allocate their tree arenas and give them back -- to the library's block pool,
     where the same call without prepare_only finds them (the arenas are tens of GB, and the driver clears memory it has handed out before at seconds
     per 24 GB: a self-play job pays that once, not per batch; a measurement keeps it out of its timed region this way).  Returns None."""
-    G.init(torch.cuda.current_device() if device is None else device.index)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    dev, stream = _device(device)
+    cap = _arena_nodes("games", playouts, reuse_subtree, node_capacity)
     # (the device-resident loop plays whole games: a cap on the moves per game takes the lock-step path below, which honours it)
     plan = plan_games(n_games, slots, handles, opening_plies, reuse_subtree) if max_moves >= N else None
     if plan is None and max_moves >= N and opening_plies <= 8 and not lockstep:
         plan = [(0, n_games, n_games)]                  # all games at once, the loop on the device all the same (gmk_selfplay_run: ONE launch where it can)
-    if plan is not None:
-        handles = len(plan)
-        open_moves = open_lens = None
-        if opening_plies > 0:
-            m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
-            open_moves, open_lens = m, np.minimum(l, opening_plies).astype(np.int32)
-        cap = node_capacity if node_capacity is not None else playouts * N * (3 if reuse_subtree else 1) + 1
-        d_moves = torch.zeros((n_games, N), dtype=torch.uint8, device=dev)
-        d_lens = torch.zeros(n_games, dtype=torch.int32, device=dev)
-        d_winner = torch.zeros(n_games, dtype=torch.int8, device=dev)
-        d_visits = torch.zeros((n_games, N, N), dtype=torch.int16, device=dev) if record_visits else None
-        noise = root_noise if reuse_subtree else None
-        blocks = [(lo, hi) for lo, hi, _ in plan]
-        trees = [G.BatchedMCTS(n_slots, c_puct=c_puct, c_rollouts=c_rollouts, seed=seed, node_capacity=cap) for _, _, n_slots in plan]
-        for tree in trees:
-            tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS[noise_sampler])
-            tree.set_option(G.OPT_LOCKSTEP, int(bool(lockstep)))
-        if prepare_only:
-            persistent = not lockstep and not (reuse_subtree and root_noise is not None and noise_sampler != "counter")
-            for tree in trees:
-                tree.reserve(two_arenas=reuse_subtree and persistent)
-            for tree in trees:
-                tree.close()
-            return None
-
-        def run_block(i, hip_stream):
-            lo, hi = blocks[i]
-            trees[i].selfplay_run(hi - lo, first_game_id + lo, playouts, d_moves[lo:].data_ptr(), d_visits[lo:].data_ptr() if record_visits else None,
-                                  d_lens[lo:].data_ptr(), d_winner[lo:].data_ptr(), None if open_moves is None else open_moves[lo:hi],
-                                  None if open_lens is None else open_lens[lo:hi], reuse_subtree, noise, hip_stream)
-
-        if handles == 1:
-            run_block(0, stream)
-        else:
-            import threading
-            torch.cuda.current_stream(dev).synchronize()          # the record buffers above are zeroed before another stream writes them
-            side = [torch.cuda.Stream(dev) for _ in range(handles)]
-            failed = [None] * handles
-
-            def worker(i):
-                try:
-                    torch.cuda.set_device(dev)                     # the HIP device is a property of the thread
-                    run_block(i, side[i].cuda_stream)              # returns with its stream drained
-                except BaseException as exc:
-                    failed[i] = exc
-
-            threads = [threading.Thread(target=worker, args=(i,)) for i in range(handles)]
-            for t in threads:
-                t.start()
-            for t in threads:
-                t.join()
-            for exc in failed:
-                if exc is not None:
-                    raise exc
-        overflow = False
-        for tree in trees:
-            overflow = overflow or bool((tree.root_stats()[4] & G.BatchedMCTS.STATUS_ARENA_FULL).any())
-            tree.close()
-        return GameRecords(d_moves, d_lens, d_winner, d_visits, first_game_id, overflow)
-    if prepare_only:
+    if plan is None and prepare_only:
         return None
-    planes = np.zeros((n_games, 2, 16), dtype=np.uint16)
-    last = np.full(n_games, -1, dtype=np.int16)
-    moves0 = np.zeros((n_games, N), dtype=np.uint8)
-    lens0 = np.zeros(n_games, dtype=np.int32)
-    if opening_plies > 0:
-        m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
-        lens0 = np.minimum(l, opening_plies).astype(np.int32)
-        planes = G.moves_to_planes(m, lens0)
-        for g in range(n_games):
-            moves0[g, :lens0[g]] = m[g, :lens0[g]]
-            last[g] = m[g, lens0[g] - 1] if lens0[g] > 0 else -1
-    cap = node_capacity if node_capacity is not None else playouts * N * (3 if reuse_subtree else 1) + 1
-    tree = G.BatchedMCTS(n_games, c_puct=c_puct, c_rollouts=c_rollouts, seed=seed, node_capacity=cap)
-    tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS[noise_sampler])
-    tree.set_roots(planes, last, first_game_id)
-    d_moves = torch.from_numpy(moves0).to(dev)
-    d_lens = torch.from_numpy(lens0).to(dev)
-    d_winner = torch.zeros(n_games, dtype=torch.int8, device=dev)
-    d_visits = torch.zeros((n_games, N, N), dtype=torch.int16, device=dev) if record_visits else None
-    d_unfinished = torch.ones(1, dtype=torch.int32, device=dev)
-    for _ in range(max_moves):
-        if root_noise is not None and reuse_subtree:      # Default::AddNoise at the start of every search (MCTS.cpp:182)
-            tree.add_root_noise(root_noise[0], root_noise[1], stream)
-        tree.run(playouts, stream)
-        tree.advance(d_moves.data_ptr(), d_visits.data_ptr() if record_visits else None, d_lens.data_ptr(),
-                     d_winner.data_ptr(), d_unfinished.data_ptr(), reuse_subtree, stream)
-        if int(d_unfinished.item()) == 0:             # 4-byte readback per move: the only host sync in the loop
-            break
-    status = tree.root_stats()[4]
-    tree.close()
-    return GameRecords(d_moves, d_lens, d_winner, d_visits, first_game_id, bool((status & G.BatchedMCTS.STATUS_ARENA_FULL).any()))
+    open_moves, open_lens = _opening(n_games, seed, first_game_id, opening_plies)
+    d_moves, d_lens, d_winner, d_visits = _record_tensors(n_games, dev, (open_moves, open_lens) if plan is None else None, record_visits)
+    noise = root_noise if reuse_subtree else None       # Default::AddNoise at the start of every search (MCTS.cpp:182)
+    trees = []
+    try:
+        for _, _, n_slots in plan or [(0, n_games, n_games)]:
+            trees.append(G.BatchedMCTS(n_slots, c_puct=c_puct, c_rollouts=c_rollouts, seed=seed, node_capacity=cap))
+            trees[-1].set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS[noise_sampler])
+        if plan is None:
+            tree = trees[0]
+            tree.set_roots(G.moves_to_planes(open_moves, open_lens), _last_two(open_moves, open_lens)[:, 0], first_game_id)
+            d_unfinished = torch.ones(1, dtype=torch.int32, device=dev)
+            for _ in range(max_moves):
+                if noise is not None:
+                    tree.add_root_noise(noise[0], noise[1], stream)
+                tree.run(playouts, stream)
+                tree.advance(d_moves.data_ptr(), d_visits.data_ptr() if record_visits else None, d_lens.data_ptr(),
+                             d_winner.data_ptr(), d_unfinished.data_ptr(), reuse_subtree, stream)
+                if int(d_unfinished.item()) == 0:             # 4-byte readback per move: the only host sync in the loop
+                    break
+        else:
+            for tree in trees:
+                tree.set_option(G.OPT_LOCKSTEP, int(bool(lockstep)))
+            if prepare_only:
+                persistent = not lockstep and not (noise is not None and noise_sampler != "counter")
+                for tree in trees:
+                    tree.reserve(two_arenas=reuse_subtree and persistent)
+                return None
+            if opening_plies <= 0:                       # (the records stay zero: the loop is handed no opening at all)
+                open_moves = open_lens = None
+
+            def run_block(i, hip_stream):
+                lo, hi, _ = plan[i]
+                trees[i].selfplay_run(hi - lo, first_game_id + lo, playouts, d_moves[lo:].data_ptr(), d_visits[lo:].data_ptr() if record_visits else None,
+                                      d_lens[lo:].data_ptr(), d_winner[lo:].data_ptr(), None if open_moves is None else open_moves[lo:hi],
+                                      None if open_lens is None else open_lens[lo:hi], reuse_subtree, noise, hip_stream)
+
+            _on_streams(run_block, len(trees), dev, stream)
+        overflow = any([_arena_full(tree.root_stats()[4], G.BatchedMCTS.STATUS_ARENA_FULL) for tree in trees])
+    finally:
+        for tree in trees:
+            tree.close()
+    return GameRecords(d_moves, d_lens, d_winner, d_visits, first_game_id, overflow)
+
+
+def _on_streams(run, n, dev, stream):
+    """run(i, hip_stream) for i < n: on `stream` when n is 1, otherwise each on a HIP stream and a host thread of its own (run returns with
+    its stream drained); a failure of any is raised."""
+    if n == 1:
+        return run(0, stream)
+    import threading
+    torch.cuda.current_stream(dev).synchronize()          # what the caller zeroed on its stream is there before another stream writes it
+    side = [torch.cuda.Stream(dev) for _ in range(n)]
+    failed = [None] * n
+
+    def worker(i):
+        try:
+            torch.cuda.set_device(dev)                     # the HIP device is a property of the thread
+            run(i, side[i].cuda_stream)
+        except BaseException as exc:
+            failed[i] = exc
+
+    threads = [threading.Thread(target=worker, args=(i,)) for i in range(n)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    for exc in failed:
+        if exc is not None:
+            raise exc
 
 
 class _HostGames:
@@ -278,33 +350,58 @@ class _HostGames:
         self.over[idx] = five | (self.lens[idx] == N)
         return idx
 
-    def open_with(self, moves, lens, plies):
-        for i in range(plies):
-            played = np.where(lens > i, moves[:, i].astype(np.int64), -1)
-            self.apply(played)
+    @classmethod
+    def opened(cls, n_games, seed, first_game_id, opening_plies):
+        """n_games boards after their openings (_opening), played ply by ply: an opening that ends its game stops there"""
+        games = cls(n_games)
+        moves, lens = _opening(n_games, seed, first_game_id, opening_plies)
+        for i in range(int(lens.max()) if n_games else 0):
+            games.apply(np.where(lens > i, moves[:, i].astype(np.int64), -1))
+        return games
 
-    def last_two(self):
-        last = np.full((self.n, 2), -1, dtype=np.int16)
-        g = np.arange(self.n)
-        has1, has2 = self.lens > 0, self.lens > 1
-        last[has1, 0] = self.moves[g[has1], self.lens[has1] - 1]
-        last[has2, 1] = self.moves[g[has2], self.lens[has2] - 2]
-        return last
+    def last_two(self, rows=None):
+        """int16[len(rows), 2]: the last move and the one before it of the games `rows` (default: all of them), -1 where there is none"""
+        return _last_two(self.moves, self.lens) if rows is None else _last_two(self.moves[rows], self.lens[rows])
+
+    def play(self, active, best, rows, visits, stall_ends_game=True, movers=None):
+        """The ledger step of a host-driven loop.  active int[k]: the game in each slot of a searcher; best int[k]: the cell the searcher
+        chose per slot, -1 for none; rows [k, 225]: its root visit counts per slot; movers bool[k] or None: the slots whose side is to move
+        (the others neither play nor stall).  Games that are over take nothing.  A mover without a cell has nothing to play: its game is
+        marked over, or left standing with stall_ends_game=False.  The moves are applied and each mover's row, saturated at 65 535, goes to
+        visits uint16[n, 225, 225] at the ply its move was made.  Returns int16[k]: the cell that went in per slot, -1 where nothing moved."""
+        active = np.asarray(active)
+        live = ~self.over[active] if movers is None else movers & ~self.over[active]
+        step = np.where(live, best, -1)
+        if stall_ends_game:
+            self.over[active[live & (step < 0)]] = True
+        played = np.full(self.n, -1, dtype=np.int64)
+        played[active] = step
+        at = self.lens.copy()                                    # a row belongs to the position it was searched from
+        moved = self.apply(played)
+        slot_of = np.full(self.n, -1, dtype=np.int64)
+        slot_of[active] = np.arange(len(active))
+        visits[moved, at[moved]] = np.minimum(rows[slot_of[moved]], 65535)
+        return step.astype(np.int16)
 
 
-_POLICIES = ("traditional", "poolrave", "traditional_rave")
+# play_supervisor_games' policy names: the reference agent (name, kwargs) each stands for, in the vocabulary of _agent_tree
+_POLICY_AGENTS = {"traditional": ("traditional_mcts", {}), "poolrave": ("rave_mcts", {}), "traditional_rave": ("traditional_mcts", {"use_rave": True})}
+_POLICIES = tuple(_POLICY_AGENTS)
 
 
-def _supervisor_tree(policy, n, cap, c_puct, seed, first_game_id):
+def _supervisor_tree(policy, n, playouts, c_puct, seed, first_game_id, reuse_subtree, node_capacity, noise_sampler):
     """The batched searcher of play_supervisor_games' policy: MCTS(TraditionalPolicy) (K6), MCTS(PoolRAVEPolicy) (K8) or
-    MCTS(TraditionalPolicy(use_rave=True)) (K6 with RAVE::BackPropogate<true>)."""
-    if policy == "poolrave":
-        return G.PoolRAVEMCTS(n, node_capacity=cap, c_puct=c_puct, seed=seed, first_game_id=first_game_id)
-    if policy == "traditional":
-        return G.TraditionalMCTS(n, node_capacity=cap, c_puct=c_puct)
-    if policy == "traditional_rave":
-        return G.TraditionalRAVEMCTS(n, node_capacity=cap, c_puct=c_puct)
-    raise ValueError("play_supervisor_games: policy must be one of %s" % (_POLICIES,))
+    MCTS(TraditionalPolicy(use_rave=True)) (K6 with RAVE::BackPropogate<true>).  PoolRAVE games draw their root noise with "std"."""
+    if policy not in _POLICY_AGENTS:
+        raise ValueError("play_supervisor_games: policy must be one of %s" % (_POLICIES,))
+    kind, kw = _POLICY_AGENTS[policy]
+    tree = _agent_tree(kind, dict(kw, c_puct=c_puct), n, _arena_nodes("supervisor", playouts, reuse_subtree, node_capacity), seed, first_game_id)
+    try:
+        tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS["std" if policy == "poolrave" else noise_sampler])
+    except BaseException:
+        tree.close()
+        raise
+    return tree
 
 
 def _play_supervisor_on_device(n_games, n_slots, playouts, c_puct, seed, first_game_id, opening_plies, device, node_capacity, policy, reuse_subtree, root_noise, max_steps=0,
@@ -312,26 +409,15 @@ def _play_supervisor_on_device(n_games, n_slots, playouts, c_puct, seed, first_g
     """play_supervisor_games with the loop resident on the device (gmk_trad_selfplay_run): the searches, MCTS::stepForward's move, the
     end-of-game check and the hand-over of a finished game's slot are kernels; the host reads four bytes per move.  Same games, same
     records as the host-driven loops below (tests/test_selfplay_gpu.py holds them to each other)."""
-    G.init(torch.cuda.current_device() if device is None else device.index)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    open_moves = open_lens = None
-    if opening_plies > 0:
-        m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
-        open_moves, open_lens = m, np.minimum(l, opening_plies).astype(np.int32)
-    cap = node_capacity if node_capacity is not None else min((3 if reuse_subtree else 1) * playouts * 226 + 1, (1 << 24) - 1)
-    tree = _supervisor_tree(policy, n_slots, cap, c_puct, seed, first_game_id)
-    tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS[noise_sampler])
-    if prepare_only:                                             # the arenas this run would allocate go to the library's pool (see play_games)
-        tree.reserve(two_arenas=bool(reuse_subtree and persistent))
-        tree.close()
-        return None
-    d_moves = torch.zeros((n_games, N), dtype=torch.uint8, device=dev)
-    d_lens = torch.zeros(n_games, dtype=torch.int32, device=dev)
-    d_winner = torch.zeros(n_games, dtype=torch.int8, device=dev)
-    d_visits = torch.zeros((n_games, N, N), dtype=torch.int16, device=dev)
-    torch.cuda.current_stream(dev).synchronize()
+    dev, stream = _device(device)
+    open_moves, open_lens = _opening(n_games, seed, first_game_id, opening_plies) if opening_plies > 0 else (None, None)
+    tree = _supervisor_tree(policy, n_slots, playouts, c_puct, seed, first_game_id, reuse_subtree, node_capacity, noise_sampler)
     try:
+        if prepare_only:                                         # the arenas this run would allocate go to the library's pool (see play_games)
+            tree.reserve(two_arenas=bool(reuse_subtree and persistent))
+            return None
+        d_moves, d_lens, d_winner, d_visits = _record_tensors(n_games, dev)
+        torch.cuda.current_stream(dev).synchronize()
         _, overflow = tree.selfplay_run(n_games, first_game_id, playouts, d_moves.data_ptr(), d_visits.data_ptr(), d_lens.data_ptr(), d_winner.data_ptr(),
                                         open_moves, open_lens, reuse_subtree, root_noise, seed, stream, max_steps, persistent)
     finally:
@@ -356,6 +442,7 @@ def play_supervisor_games(n_games, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, fi
     costs the same time however many of its games are still alive: one wavefront per game, latency bound).
     device_loop (default): the loop runs on the device (gmk_trad_selfplay_run; whole games only, so a max_moves cap takes the host loop);
     device_loop=False: the host drives it ply by ply with numpy boards (root_stats down, positions up every ply) -- the same games.
+    Known gap: through slots (slots < n_games) the host-driven loop plays every game to its end and does not look at max_moves.
     max_steps > 0 (device loop only): stop after that many moves per slot, whatever is unfinished (throughput measurements with every slot busy).
     noise_sampler: "counter" (default) = the counter-based Dirichlet sampler of include/gomoku_noise.h, drawn on the device -- inside the ONE launch of the
     persistent loop, so that the reference agent's semantics (reuse_subtree + root_noise) run at the pace of the plain loop; "std" = std::gamma_distribution
@@ -382,67 +469,29 @@ def play_supervisor_games(n_games, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, fi
         return None
     if max_steps:
         raise ValueError("play_supervisor_games: max_steps is a switch of the device-resident loop")
-    if slots is not None and slots < n_games:
-        return _play_supervisor_slots(n_games, int(slots), playouts, c_puct, seed, first_game_id, opening_plies, device, node_capacity, policy,
-                                      reuse_subtree, root_noise, noise_sampler)
-    G.init(torch.cuda.current_device() if device is None else device.index)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    games = _HostGames(n_games)                                  # host boards: Board::applyMove / checkGameEnd for all games at once
-    if opening_plies > 0:
-        m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
-        games.open_with(m, l, opening_plies)
-    visits = np.zeros((n_games, N, N), dtype=np.uint16)
-    cap = node_capacity if node_capacity is not None else min((3 if reuse_subtree else 1) * playouts * 226 + 1, (1 << 24) - 1)
-    tree = _supervisor_tree(policy, n_games, cap, c_puct, seed, first_game_id)
-    tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS["std" if policy == "poolrave" else noise_sampler])
-    overflow = False
-    for ply in range(max_moves):
-        if games.over.all():
-            break
-        if ply == 0 or not reuse_subtree:
-            tree.set_positions(games.moves, games.lens)
-        if root_noise is not None:
-            tree.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id, stream=stream)
-        tree.run(playouts, stream)
-        st = tree.root_stats()
-        overflow |= bool((st["status"] & G.TraditionalMCTS.STATUS_ARENA_FULL).any())
-        played = np.where(games.over, -1, st["best"]).astype(np.int16)
-        games.over |= played < 0                                 # no child: nothing the policy wants to play (cannot happen on a live board)
-        at = games.lens.copy()
-        moved = games.apply(played)
-        visits[moved, at[moved]] = np.minimum(st["visits"][moved], 65535)
-        if reuse_subtree:
-            tree.step(played)                               # finished games ask for -1 on a childless root: nothing moves
-    tree.close()
-    return GameRecords(torch.from_numpy(games.moves).to(dev), torch.from_numpy(games.lens).to(dev), torch.from_numpy(games.winner).to(dev),
-                       torch.from_numpy(visits.view(np.int16)).to(dev), first_game_id, overflow)
+    # One host-driven loop: all games at once are n_games slots that never change hands, for at most max_moves searches.  Through fewer
+    # slots the bound is what it takes to play every game out -- max_moves is not looked at there (a known gap).
+    n_slots = int(slots) if slots is not None and slots < n_games else n_games
+    steps = max_moves if n_slots == n_games else (n_games // n_slots + 2) * N
+    dev, stream = _device(device)
+    games = _HostGames.opened(n_games, seed, first_game_id, opening_plies)      # host boards: Board::applyMove / checkGameEnd for all games at once
+    tree = _supervisor_tree(policy, n_slots, playouts, c_puct, seed, first_game_id, reuse_subtree, node_capacity, noise_sampler)
+    try:
+        visits, overflow = _supervisor_host_loop(tree, games, n_slots, steps, playouts, reuse_subtree, root_noise, seed, first_game_id, stream)
+    finally:
+        tree.close()
+    return _records_from_host(games, visits, dev, first_game_id, overflow)
 
 
-def _play_supervisor_slots(n_games, slots, playouts, c_puct, seed, first_game_id, opening_plies, device, node_capacity, policy,
-                           reuse_subtree=False, root_noise=None, noise_sampler="std"):
-    G.init(torch.cuda.current_device() if device is None else device.index)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    games = _HostGames(n_games)
-    if opening_plies > 0:
-        m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
-        games.open_with(m, l, opening_plies)
-    visits = np.zeros((n_games, N, N), dtype=np.uint16)
-    cap = node_capacity if node_capacity is not None else min((3 if reuse_subtree else 1) * playouts * 226 + 1, (1 << 24) - 1)
-    tree = _supervisor_tree(policy, slots, cap, c_puct, seed, first_game_id)
-    tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS["std" if policy == "poolrave" else noise_sampler])
-    active = np.arange(slots)                                    # the game in each slot
-    next_game = slots
-    overflow = False
+def _supervisor_host_loop(tree, games, slots, steps, playouts, reuse_subtree, root_noise, seed, first_game_id, stream):
+    """The host-driven loop of play_supervisor_games: the games of `games` (a _HostGames) through `slots` slots of `tree`, at most `steps`
+    searches; a finished game hands its slot to the next unstarted one.  Returns (visits uint16[n, 225, 225], whether an arena filled up)."""
+    visits = np.zeros((games.n, N, N), dtype=np.uint16)
+    active, waiting = np.arange(slots), list(range(slots, games.n))      # the game in each slot, the games not started yet
     fresh = np.ones(slots, dtype=bool)                           # slots whose game starts from a new root at the next search
-    for _ in range((n_games // slots + 2) * N):
-        # a finished game hands its slot to the next unstarted one
-        done = np.nonzero(games.over[active])[0]
-        take = min(len(done), n_games - next_game)
-        active[done[:take]] = np.arange(next_game, next_game + take)
-        fresh[done[:take]] = True
-        next_game += take
+    overflow = False
+    for _ in range(steps):
+        fresh |= _hand_over(active, games.over, waiting)
         if games.over[active].all():
             break
         tree.set_game_ids(active)                                # root noise and rollout streams are the GAME's (first_game_id + its number), whatever slot it runs in
@@ -455,21 +504,11 @@ def _play_supervisor_slots(n_games, slots, playouts, c_puct, seed, first_game_id
             tree.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id, stream=stream)
         tree.run(playouts, stream)
         st = tree.root_stats()
-        overflow |= bool((st["status"] & G.TraditionalMCTS.STATUS_ARENA_FULL).any())
-        best = np.where(games.over[active], -1, st["best"])
-        games.over[active[(best < 0) & ~games.over[active]]] = True
-        played = np.full(n_games, -1, dtype=np.int64)
-        played[active] = best
-        at = games.lens.copy()
-        moved = games.apply(played)
-        slot_of = np.full(n_games, -1, dtype=np.int64)
-        slot_of[active] = np.arange(slots)
-        visits[moved, at[moved]] = np.minimum(st["visits"][slot_of[moved]], 65535)
+        overflow |= _arena_full(st["status"], G.TraditionalMCTS.STATUS_ARENA_FULL)
+        step = games.play(active, st["best"], st["visits"], visits)     # a root without a child: nothing the policy wants to play (cannot happen on a live board)
         if reuse_subtree:
-            tree.step(best.astype(np.int16))                     # finished games ask for -1 on a childless root: nothing moves
-    tree.close()
-    return GameRecords(torch.from_numpy(games.moves).to(dev), torch.from_numpy(games.lens).to(dev), torch.from_numpy(games.winner).to(dev),
-                       torch.from_numpy(visits.view(np.int16)).to(dev), first_game_id, overflow)
+            tree.step(step)                                      # finished games ask for -1 on a childless root: nothing moves
+    return visits, overflow
 
 
 def _vcf_options(vcf):
@@ -535,123 +574,67 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
         # ignoring the cap or failing inside the library)
         raise ValueError("play_network_games: with slots, games are played to their end (max_moves >= 225)" +
                          (" from openings of at most 8 plies on the device loop" if device_loop else "") + "; play all games at once (slots=None) for a move cap")
-    G.init(torch.cuda.current_device() if device is None else device.index)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-    if slots is not None and slots < n_games and device_loop:
-        # continuous batching on the device (gmk_az_set_slots + gmk_az_advance): the batch the network sees stays full of live games
-        # until fewer games than slots remain, with kept subtrees and root noise as well
-        games = _HostGames(n_games)
-        if opening_plies > 0:
-            m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
-            games.open_with(m, l, opening_plies)
-        slots = int(slots)
-        cap = node_capacity if node_capacity is not None else min((3 if reuse_subtree else 1) * playouts * N + 1, (1 << 24) - 1)
-        tree = G.AlphaZeroMCTS(slots, node_capacity=cap, c_puct=c_puct, leaves=leaves, proof=proof, vcf_defend=vcf_defend, **_vcf_options(vcf))
+    slotted = slots is not None and slots < n_games
+    if slotted and not device_loop and reuse_subtree:
+        raise ValueError("play_network_games: slots on the host-driven loop need fresh roots (reuse_subtree=False)")
+    n_slots = int(slots) if slotted else n_games
+    steps = (n_games // n_slots + 2) * N if slotted else max_moves
+    dev, _ = _device(device)
+    games = _HostGames.opened(n_games, seed, first_game_id, opening_plies)
+    tree = G.AlphaZeroMCTS(n_slots, node_capacity=_arena_nodes("network", playouts, reuse_subtree, node_capacity), c_puct=c_puct, leaves=leaves, proof=proof,
+                           vcf_defend=vcf_defend, **_vcf_options(vcf))
+    try:
         tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS[noise_sampler])
-        tree.set_slots(n_games, games.moves[:, :max(int(games.lens.max()), 1)], games.lens)
-        d_moves, d_lens = torch.from_numpy(games.moves).to(dev), torch.from_numpy(games.lens).to(dev)
-        d_winner = torch.zeros(n_games, dtype=torch.int8, device=dev)
-        d_visits = torch.zeros((n_games, N, N), dtype=torch.int16, device=dev)
         with torch.no_grad():
-            for _ in range((n_games // slots + 2) * N):
-                if root_noise is not None:
-                    tree.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id)
-                tree.search(network, playouts)
-                if tree.advance(d_moves, d_visits, d_lens, d_winner, reuse_subtree, sample=sample) == 0:
-                    break
-        overflow = bool((tree.root_stats()["status"] & G.AlphaZeroMCTS.STATUS_ARENA_FULL).any())
-        tree.close()
-        return GameRecords(d_moves, d_lens, d_winner, d_visits, first_game_id, overflow)
-    if slots is not None and slots < n_games:
-        if reuse_subtree:
-            raise ValueError("play_network_games: slots on the host-driven loop need fresh roots (reuse_subtree=False)")
-        games = _HostGames(n_games)
-        if opening_plies > 0:
-            m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
-            games.open_with(m, l, opening_plies)
-        visits = np.zeros((n_games, N, N), dtype=np.uint16)
-        slots = int(slots)
-        tree = G.AlphaZeroMCTS(slots, node_capacity=node_capacity if node_capacity is not None else min(playouts * N + 1, (1 << 24) - 1), c_puct=c_puct, leaves=leaves, proof=proof, vcf_defend=vcf_defend, **_vcf_options(vcf))
-        active, next_game, overflow = np.arange(slots), slots, False
-        with torch.no_grad():
-            for _ in range((n_games // slots + 2) * N):
-                done = np.nonzero(games.over[active])[0]
-                take = min(len(done), n_games - next_game)
-                active[done[:take]] = np.arange(next_game, next_game + take)
-                next_game += take
-                if games.over[active].all():
-                    break
-                tree.set_game_ids(active)
-                sub_moves, sub_lens = games.moves[active], games.lens[active]
-                last = np.full((slots, 2), -1, dtype=np.int16)
-                rows = np.arange(slots)
-                last[sub_lens > 0, 0] = sub_moves[rows[sub_lens > 0], sub_lens[sub_lens > 0] - 1]
-                last[sub_lens > 1, 1] = sub_moves[rows[sub_lens > 1], sub_lens[sub_lens > 1] - 2]
-                tree.set_roots(G.moves_to_planes(sub_moves, sub_lens), last)
-                tree.search(network, playouts)
-                st = tree.root_stats()
-                overflow |= bool((st["status"] & G.AlphaZeroMCTS.STATUS_ARENA_FULL).any())
-                visited = st["visits"].max(1) > 0
-                best = np.where(games.over[active] | ~visited, -1,
-                                _sampled_choice(st["visits"], tree.root_proofs()["children"] if proof else None, games.lens[active], active, sample))
-                games.over[active[(best < 0) & ~games.over[active]]] = True
-                played = np.full(n_games, -1, dtype=np.int64)
-                played[active] = best
-                at = games.lens.copy()
-                moved = games.apply(played)
-                slot_of = np.full(n_games, -1, dtype=np.int64)
-                slot_of[active] = np.arange(slots)
-                visits[moved, at[moved]] = np.minimum(st["visits"][slot_of[moved]], 65535)
-        tree.close()
-        return GameRecords(torch.from_numpy(games.moves).to(dev), torch.from_numpy(games.lens).to(dev), torch.from_numpy(games.winner).to(dev),
-                           torch.from_numpy(visits.view(np.int16)).to(dev), first_game_id, overflow)
-    games = _HostGames(n_games)
-    if opening_plies > 0:
-        m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
-        games.open_with(m, l, opening_plies)
-    cap = node_capacity if node_capacity is not None else min((3 if reuse_subtree else 1) * playouts * N + 1, (1 << 24) - 1)
-    tree = G.AlphaZeroMCTS(n_games, node_capacity=cap, c_puct=c_puct, leaves=leaves, proof=proof, vcf_defend=vcf_defend, **_vcf_options(vcf))
-    tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS[noise_sampler])
-    tree.set_roots(G.moves_to_planes(games.moves, games.lens), games.last_two())
-    if device_loop:
-        d_moves, d_lens = torch.from_numpy(games.moves).to(dev), torch.from_numpy(games.lens).to(dev)
-        d_winner = torch.zeros(n_games, dtype=torch.int8, device=dev)
-        d_visits = torch.zeros((n_games, N, N), dtype=torch.int16, device=dev)
-        with torch.no_grad():
-            for ply in range(max_moves):
-                if root_noise is not None:
-                    tree.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id)
-                tree.search(network, playouts)
-                if tree.advance(d_moves, d_visits, d_lens, d_winner, reuse_subtree, sample=sample) == 0:
-                    break
-        overflow = bool((tree.root_stats()["status"] & G.AlphaZeroMCTS.STATUS_ARENA_FULL).any())
-        tree.close()
-        return GameRecords(d_moves, d_lens, d_winner, d_visits, first_game_id, overflow)
-    visits = np.zeros((n_games, N, N), dtype=np.uint16)
-    overflow = False
-    with torch.no_grad():
-        for ply in range(max_moves):
-            if games.over.all():
-                break
-            if ply > 0 and not reuse_subtree:
+            if not device_loop:
+                # (through slots the host-driven loop has never mixed noise into its fresh roots: kept as it is)
+                visits, overflow = _network_host_loop(tree, games, n_slots, steps, network, playouts, reuse_subtree, None if slotted else root_noise,
+                                                      proof, sample, seed, first_game_id)
+                return _records_from_host(games, visits, dev, first_game_id, overflow)
+            if slotted:
+                # continuous batching on the device (gmk_az_set_slots + gmk_az_advance): the batch the network sees stays full of live games
+                # until fewer games than slots remain, with kept subtrees and root noise as well
+                tree.set_slots(n_games, games.moves[:, :max(int(games.lens.max()), 1)], games.lens)
+            else:
                 tree.set_roots(G.moves_to_planes(games.moves, games.lens), games.last_two())
-            if root_noise is not None:
-                tree.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id)
-            tree.search(network, playouts)
-            st = tree.root_stats()
-            overflow |= bool((st["status"] & G.AlphaZeroMCTS.STATUS_ARENA_FULL).any())
-            visited = st["visits"].max(1) > 0                    # no child was visited: nothing to play (cannot happen on a live board)
-            played = np.where(games.over | ~visited, -1,
-                              _sampled_choice(st["visits"], tree.root_proofs()["children"] if proof else None, games.lens, np.arange(n_games), sample)).astype(np.int16)
-            games.over |= played < 0
-            at = games.lens.copy()
-            moved = games.apply(played)
-            visits[moved, at[moved]] = np.minimum(st["visits"][moved], 65535)
-            if reuse_subtree:
-                tree.step(played)
-    tree.close()
-    return GameRecords(torch.from_numpy(games.moves).to(dev), torch.from_numpy(games.lens).to(dev), torch.from_numpy(games.winner).to(dev),
-                       torch.from_numpy(visits.view(np.int16)).to(dev), first_game_id, overflow)
+            d_moves, d_lens, d_winner, d_visits = _record_tensors(n_games, dev, (games.moves, games.lens))
+            for _ in range(steps):
+                if root_noise is not None:
+                    tree.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id)
+                tree.search(network, playouts)
+                if tree.advance(d_moves, d_visits, d_lens, d_winner, reuse_subtree, sample=sample) == 0:
+                    break
+        overflow = _arena_full(tree.root_stats()["status"], G.AlphaZeroMCTS.STATUS_ARENA_FULL)
+    finally:
+        tree.close()
+    return GameRecords(d_moves, d_lens, d_winner, d_visits, first_game_id, overflow)
+
+
+def _network_host_loop(tree, games, slots, steps, network, playouts, reuse_subtree, root_noise, proof, sample, seed, first_game_id):
+    """The host-driven loop of play_network_games: the games of `games` (a _HostGames) through `slots` slots of the K7 handle `tree`, at
+    most `steps` searches.  With kept subtrees every slot keeps its game (slots == games.n: K7 has no way to give one slot a new root and
+    leave the others their trees).  Returns (visits uint16[n, 225, 225], whether an arena filled up)."""
+    visits = np.zeros((games.n, N, N), dtype=np.uint16)
+    active, waiting = np.arange(slots), list(range(slots, games.n))
+    overflow = False
+    for i in range(steps):
+        _hand_over(active, games.over, waiting)
+        if games.over[active].all():
+            break
+        if i == 0 or not reuse_subtree:
+            tree.set_game_ids(active)
+            tree.set_roots(G.moves_to_planes(games.moves[active], games.lens[active]), games.last_two(active))
+        if root_noise is not None:
+            tree.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id)
+        tree.search(network, playouts)
+        st = tree.root_stats()
+        overflow |= _arena_full(st["status"], G.AlphaZeroMCTS.STATUS_ARENA_FULL)
+        choice = _sampled_choice(st["visits"], tree.root_proofs()["children"] if proof else None, games.lens[active], active, sample)
+        visited = st["visits"].max(1) > 0                        # no child was visited: nothing to play (cannot happen on a live board)
+        step = games.play(active, np.where(visited, choice, -1), st["visits"], visits)
+        if reuse_subtree:
+            tree.step(step)
+    return visits, overflow
 
 
 class _Searcher:
@@ -660,37 +643,26 @@ class _Searcher:
     def __init__(self, spec, n, playouts, seed, first_game_id):
         kind, kw = spec
         self.kind, self.n, self.playouts = kind, n, int(kw.get("c_iterations", playouts))
-        c_puct = float(kw.get("c_puct", 5.0))
         self.first_game_id = first_game_id
-        if kind == "traditional_mcts" and kw.get("use_rave"):  # TraditionalAgent(c_puct, c_bias, use_rave=True) (agents/mcts.py:44-47)
-            self.tree = G.TraditionalRAVEMCTS(n, node_capacity=min(self.playouts * 226 + 256, (1 << 24) - 1), c_puct=c_puct, c_bias=float(kw.get("c_bias", 0.0)))
-        elif kind == "traditional_mcts":                     # AGENT_MAP names of the reference (agents/__init__.py, config.py:9-19)
-            self.tree = G.TraditionalMCTS(n, node_capacity=min(self.playouts * 226 + 256, (1 << 24) - 1), c_puct=c_puct)
-        elif kind == "rave_mcts":
-            self.tree = G.PoolRAVEMCTS(n, node_capacity=min(self.playouts * 226 + 256, (1 << 24) - 1), c_puct=c_puct, seed=seed, first_game_id=first_game_id)
-        elif kind == "random_mcts":
-            self.tree = G.BatchedMCTS(n, playouts_capacity=self.playouts, c_puct=c_puct, c_rollouts=int(kw.get("c_rollouts", 5)), seed=seed)
-        else:
+        cap = _arena_nodes("games" if kind == "random_mcts" else "match", self.playouts)
+        self.tree = _agent_tree(kind, kw, n, cap, seed, first_game_id)
+        if self.tree is None:
             raise ValueError("play_match_games: unknown agent '%s' (traditional_mcts, rave_mcts, random_mcts)" % kind)
 
     def search(self, moves, lens, games, stream):
         """Root visit counts [n, 225] and the move MCTS::stepForward() would make per game (-1: none), from fresh roots.
         games int[n]: the number of the game in each slot; its random streams are keyed by first_game_id + that number."""
         if self.kind == "random_mcts":
-            planes = G.moves_to_planes(moves, lens)
-            last = np.where(lens > 0, moves[np.arange(self.n), np.maximum(lens, 1) - 1].astype(np.int16), np.int16(-1))
-            self.tree.set_roots(planes, last, self.first_game_id)
+            self.tree.set_roots(G.moves_to_planes(moves, lens), _last_two(moves, lens)[:, 0], self.first_game_id)
             self.tree.set_game_ids((self.first_game_id + np.asarray(games)).astype(np.uint32))
             self.tree.run(self.playouts, stream)
             stats = self.tree.root_stats()
-            visits = stats[0]
-            best = np.where(visits.max(1) > 0, visits.argmax(1), -1).astype(np.int32)        # max_element: the first maximum in child (= cell) order
-            return visits, best, bool((stats[4] & G.BatchedMCTS.STATUS_ARENA_FULL).any())
+            return stats[0], _root_choice(stats[0]).astype(np.int32), _arena_full(stats[4], G.BatchedMCTS.STATUS_ARENA_FULL)
         self.tree.set_game_ids(np.asarray(games, dtype=np.uint32))
         self.tree.set_positions(moves, lens)
         self.tree.run(self.playouts, stream)
         st = self.tree.root_stats()
-        return st["visits"], st["best"], bool((st["status"] & G.TraditionalMCTS.STATUS_ARENA_FULL).any())
+        return st["visits"], st["best"], _arena_full(st["status"], G.TraditionalMCTS.STATUS_ARENA_FULL)
 
     def close(self):
         self.tree.close()
@@ -707,59 +679,36 @@ def play_match_games(n_games, supervisor, candidate, playouts=400, seed=G.DEFAUL
     game's random streams are keyed by its own global id first_game_id + g, whatever group and slot it runs in.  slots: games in flight per group (default: all of them); a
     finished game hands its slot to the next unstarted game of its group, which keeps the searches full (see play_supervisor_games).
     Returns (GameRecords, supervisor_is_black bool[n]); the records' visit counts at move i are those of the player who made it."""
-    G.init(torch.cuda.current_device() if device is None else device.index)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    dev, stream = _device(device)
     rng = np.random.RandomState(int((seed ^ (seed >> 32) ^ first_game_id) & 0xFFFFFFFF))
     sup_black = rng.randint(0, 2, n_games).astype(bool)           # random.shuffle(players) per game (data_helper.py:57-58)
-    games = _HostGames(n_games)
-    if opening_plies > 0:
-        m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
-        games.open_with(m, l, opening_plies)
+    games = _HostGames.opened(n_games, seed, first_game_id, opening_plies)
     visits = np.zeros((n_games, N, N), dtype=np.uint16)
-    groups = [np.nonzero(sup_black)[0], np.nonzero(~sup_black)[0]]
     active, waiting, searchers = [], [], []                      # per group: the game in each slot, the games not started yet, [supervisor, candidate]
-    for idx in groups:
-        k = len(idx) if slots is None else min(int(slots), len(idx))
-        active.append(idx[:k].copy())
-        waiting.append(list(idx[k:]))
-        searchers.append([_Searcher(spec, k, playouts, seed, first_game_id) if k else None for spec in (supervisor, candidate)])
     overflow = False
-    for _ in range((2 + (0 if slots is None else n_games // max(1, int(slots)))) * max_moves):
-        if games.over.all():
-            break
-        for gi in (0, 1):
-            act = active[gi]
-            if len(act) == 0:
-                continue
-            done = np.nonzero(games.over[act])[0]                 # a finished game hands its slot to the next one of the group
-            for slot in done[:len(waiting[gi])]:
-                act[slot] = waiting[gi].pop(0)
-            if games.over[act].all():
-                continue
-            for who in (0, 1):                                    # normally one of the two: the games of a group move in lock step
-                # group 0: the supervisor has black, i.e. it moves on even stone counts
-                turn = ((games.lens[act] % 2 == 0) == (gi == 0)) == (who == 0)
-                sel = turn & ~games.over[act]
-                if not sel.any():
+    with contextlib.ExitStack() as handles:
+        for idx in (np.nonzero(sup_black)[0], np.nonzero(~sup_black)[0]):
+            k = len(idx) if slots is None else min(int(slots), len(idx))
+            active.append(idx[:k].copy())
+            waiting.append(list(idx[k:]))
+            searchers.append([handles.enter_context(contextlib.closing(_Searcher(spec, k, playouts, seed, first_game_id))) if k else None
+                              for spec in (supervisor, candidate)])
+        for _ in range((2 + (0 if slots is None else n_games // max(1, int(slots)))) * max_moves):
+            if games.over.all():
+                break
+            for gi, act in enumerate(active):
+                _hand_over(act, games.over, waiting[gi])          # a finished game hands its slot to the next one of the group
+                if games.over[act].all():                         # (an empty group too)
                     continue
-                v, best, full = searchers[gi][who].search(games.moves[act], games.lens[act], act, stream)
-                overflow |= full
-                played = np.full(n_games, -1, dtype=np.int64)
-                played[act[sel]] = best[sel]
-                games.over[act[sel & (best < 0)]] = True
-                at = games.lens.copy()
-                moved = games.apply(played)
-                slot_of = np.full(n_games, -1, dtype=np.int64)
-                slot_of[act] = np.arange(len(act))
-                visits[moved, at[moved]] = np.minimum(v[slot_of[moved]], 65535)
-    for pair in searchers:
-        for srch in pair:
-            if srch is not None:
-                srch.close()
-    rec = GameRecords(torch.from_numpy(games.moves).to(dev), torch.from_numpy(games.lens).to(dev), torch.from_numpy(games.winner).to(dev),
-                      torch.from_numpy(visits.view(np.int16)).to(dev), first_game_id, overflow)
-    return rec, sup_black
+                for who in (0, 1):                                # normally one of the two: the games of a group move in lock step
+                    # group 0: the supervisor has black, i.e. it moves on even stone counts
+                    sel = (((games.lens[act] % 2 == 0) == (gi == 0)) == (who == 0)) & ~games.over[act]
+                    if not sel.any():
+                        continue
+                    v, best, full = searchers[gi][who].search(games.moves[act], games.lens[act], act, stream)
+                    overflow |= full
+                    games.play(act, best, v, visits, movers=sel)
+    return _records_from_host(games, visits, dev, first_game_id, overflow), sup_black
 
 
 def evaluation_sides(n_games):
@@ -786,27 +735,25 @@ class _EvalOpponent:
         kind, kw = spec
         self.kind, self.idx, self.reuse, self.seed, self.first = kind, idx, reuse_subtree, seed, first_game_id
         self.playouts = int(kw.get("c_iterations", 400))
-        k, c_puct = len(idx), float(kw.get("c_puct", 5.0))
+        self.searcher = self.tree = None
         if kind == "random_mcts":
-            self.searcher, self.tree = _Searcher(spec, k, self.playouts, seed, first_game_id), None
+            self.searcher = _Searcher(spec, len(idx), self.playouts, seed, first_game_id)
             return
-        cap = min((3 if reuse_subtree else 1) * self.playouts * 226 + 256, (1 << 24) - 1)
-        if kind == "rave_mcts":
-            self.tree = G.PoolRAVEMCTS(k, node_capacity=cap, c_puct=c_puct, seed=seed, first_game_id=first_game_id)
-        elif kw.get("use_rave"):
-            self.tree = G.TraditionalRAVEMCTS(k, node_capacity=cap, c_puct=c_puct, c_bias=float(kw.get("c_bias", 0.0)))
-        else:
-            self.tree = G.TraditionalMCTS(k, node_capacity=cap, c_puct=c_puct)
-        self.tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS["counter"])
-        self.tree.set_game_ids(np.asarray(idx, dtype=np.uint32))
-        self.tree.set_positions(moves, lens)
+        self.tree = _agent_tree(kind, kw, len(idx), _arena_nodes("match", self.playouts, reuse_subtree), seed, first_game_id)
+        try:
+            self.tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS["counter"])
+            self.tree.set_game_ids(np.asarray(idx, dtype=np.uint32))
+            self.tree.set_positions(moves, lens)
+        except BaseException:
+            self.tree.close()
+            raise
 
     def add_root_noise(self, root_noise, stream=None):
         if root_noise is not None and self.tree is not None:
             self.tree.add_root_noise(root_noise[0], root_noise[1], seed=self.seed, first_game_id=self.first, stream=stream)
 
     def overflow(self):
-        return self.tree is not None and bool((self.tree.root_stats()["status"] & G.TraditionalMCTS.STATUS_ARENA_FULL).any())
+        return self.tree is not None and _arena_full(self.tree.root_stats()["status"], G.TraditionalMCTS.STATUS_ARENA_FULL)
 
     def close(self):
         (self.tree if self.tree is not None else self.searcher).close()
@@ -845,104 +792,84 @@ def play_evaluation_games(n_games, network, opponent, playouts=400, c_puct=5.0, 
         device_loop = kind != "random_mcts"
     if opening_plies > 8:
         raise ValueError("play_evaluation_games: openings of at most 8 plies (an opening cannot be a finished game)")
-    G.init(torch.cuda.current_device() if device is None else device.index)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    dev, stream = _device(device)
     black = evaluation_sides(n_games)
-    games = _HostGames(n_games)
-    if opening_plies > 0:
-        m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
-        games.open_with(m, l, opening_plies)
+    games = _HostGames.opened(n_games, seed, first_game_id, opening_plies)
     start = int(games.lens[0]) if n_games else 0
     assert (games.lens == start).all() and not games.over.any()
     if device_loop:
-        d_moves, d_lens = torch.from_numpy(games.moves).to(dev), torch.from_numpy(games.lens).to(dev)
-        d_winner = torch.zeros(n_games, dtype=torch.int8, device=dev)
-        d_visits = torch.zeros((n_games, N, N), dtype=torch.int16, device=dev)
+        d_moves, d_lens, d_winner, d_visits = _record_tensors(n_games, dev, (games.moves, games.lens))
     else:
         visits = np.zeros((n_games, N, N), dtype=np.uint16)
     overflow, groups = False, []
-    net_cap = node_capacity if node_capacity is not None else min((3 if reuse_subtree else 1) * playouts * N + 1, (1 << 24) - 1)
+    net_cap = _arena_nodes("network", playouts, reuse_subtree, node_capacity)
     for gi, idx in enumerate((np.nonzero(black)[0], np.nonzero(~black)[0])):
         k = len(idx)
         if k == 0:
             groups.append({"games": idx, "unfinished": 0, "live_games": 0})
             continue
-        net = G.AlphaZeroMCTS(k, node_capacity=net_cap, c_puct=c_puct, leaves=leaves, proof=proof, vcf_defend=vcf_defend, **_vcf_options(vcf))
-        net.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS["counter"])
-        net.set_game_ids(np.asarray(idx, dtype=np.uint32))
-        net.set_roots(G.moves_to_planes(games.moves[idx], games.lens[idx]), games.last_two()[idx])
-        opp = _EvalOpponent(opponent, idx, games.moves[idx], games.lens[idx], seed, first_game_id, reuse_subtree)
-        unfinished = k
-        with torch.no_grad():
+        with contextlib.ExitStack() as handles, torch.no_grad():
+            net = handles.enter_context(contextlib.closing(
+                G.AlphaZeroMCTS(k, node_capacity=net_cap, c_puct=c_puct, leaves=leaves, proof=proof, vcf_defend=vcf_defend, **_vcf_options(vcf))))
+            net.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS["counter"])
+            net.set_game_ids(np.asarray(idx, dtype=np.uint32))
+            net.set_roots(G.moves_to_planes(games.moves[idx], games.lens[idx]), games.last_two(idx))
+            opp = handles.enter_context(contextlib.closing(_EvalOpponent(opponent, idx, games.moves[idx], games.lens[idx], seed, first_game_id, reuse_subtree)))
+            unfinished = k
             if device_loop:
                 d_idx = torch.from_numpy(idx.astype(np.int32)).to(dev)
                 d_cells, d_rows = torch.full((k,), -1, dtype=torch.int16, device=dev), torch.zeros((k, N), dtype=torch.int16, device=dev)
                 d_verdict, d_status, d_unfinished = torch.zeros(k, dtype=torch.int32, device=dev), torch.zeros(k, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
-                for ply in range(max_moves):
-                    net_moves = ((start + ply) % 2 == 0) == (gi == 0)         # group 0: the network has black, i.e. it moves on even stone counts
-                    if net_moves:
-                        if root_noise is not None:
-                            net.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id)
-                        net.search(network, playouts)
-                        net.root_choice(d_cells, d_rows)
-                    else:
-                        opp.add_root_noise(root_noise, stream)
-                        opp.tree.run(opp.playouts, stream)
-                        opp.tree.root_choice(d_cells, d_rows)
+            for ply in range(max_moves):
+                if not device_loop and games.over[idx].all():
+                    break
+                net_moves = ((start + ply) % 2 == 0) == (gi == 0)             # group 0: the network has black, i.e. it moves on even stone counts
+                fresh = not device_loop and ply > 0 and not reuse_subtree     # (on the device loop step_device leaves the fresh roots)
+                if net_moves:
+                    if fresh:
+                        net.set_roots(G.moves_to_planes(games.moves[idx], games.lens[idx]), games.last_two(idx))
+                    if root_noise is not None:
+                        net.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id)
+                    net.search(network, playouts)
+                elif opp.tree is not None:
+                    if fresh:
+                        opp.tree.set_positions(games.moves[idx], games.lens[idx])
+                    opp.add_root_noise(root_noise, stream)
+                    opp.tree.run(opp.playouts, stream)
+                if device_loop:
+                    (net if net_moves else opp.tree).root_choice(d_cells, d_rows)
                     G.match_referee(d_cells, d_rows, d_idx, d_moves, d_lens, d_winner, d_visits, d_verdict, d_status, d_unfinished)
                     opp.tree.step_device(d_cells, d_verdict, fresh_root=not reuse_subtree)
                     unfinished = net.step_device(d_cells, d_verdict, fresh_root=not reuse_subtree, unfinished=d_unfinished)
                     if unfinished == 0:
                         break
-                overflow |= bool((net.root_stats()["status"] & G.AlphaZeroMCTS.STATUS_ARENA_FULL).any())
-            else:
-                for ply in range(max_moves):
-                    if games.over[idx].all():
-                        break
-                    net_moves = ((start + ply) % 2 == 0) == (gi == 0)
+                else:
                     if net_moves:
-                        if ply > 0 and not reuse_subtree:
-                            net.set_roots(G.moves_to_planes(games.moves[idx], games.lens[idx]), games.last_two()[idx])
-                        if root_noise is not None:
-                            net.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id)
-                        net.search(network, playouts)
                         st = net.root_stats()
-                        overflow |= bool((st["status"] & G.AlphaZeroMCTS.STATUS_ARENA_FULL).any())
+                        overflow |= _arena_full(st["status"], G.AlphaZeroMCTS.STATUS_ARENA_FULL)
                         v, best = st["visits"], _root_choice(st["visits"], net.root_proofs()["children"] if proof else None)
                     elif opp.tree is None:
                         v, best, full = opp.searcher.search(games.moves[idx], games.lens[idx], idx, stream)
                         overflow |= full
                     else:
-                        if ply > 0 and not reuse_subtree:
-                            opp.tree.set_positions(games.moves[idx], games.lens[idx])
-                        opp.add_root_noise(root_noise, stream)
-                        opp.tree.run(opp.playouts, stream)
                         st = opp.tree.root_stats()
                         v, best = st["visits"], st["best"]
-                    step = np.where(games.over[idx], -1, best).astype(np.int16)
-                    played = np.full(n_games, -1, dtype=np.int64)
-                    played[idx] = step
-                    at = games.lens.copy()
-                    moved = games.apply(played)
-                    slot_of = np.full(n_games, -1, dtype=np.int64)
-                    slot_of[idx] = np.arange(k)
-                    visits[moved, at[moved]] = np.minimum(v[slot_of[moved]], 65535)
+                    step = games.play(idx, best, v, visits, stall_ends_game=False)      # a mover without a child leaves its game where it stands
                     if reuse_subtree:
                         net.step(step)
                         if opp.tree is not None:
                             opp.tree.step(step)
+            if device_loop:
+                overflow |= _arena_full(net.root_stats()["status"], G.AlphaZeroMCTS.STATUS_ARENA_FULL)
+            else:
                 unfinished = int((~games.over[idx]).sum())
             overflow |= opp.overflow()
-        groups.append({"games": idx, "unfinished": unfinished, "live_games": net.live})
-        opp.close()
-        net.close()
+            groups.append({"games": idx, "unfinished": unfinished, "live_games": net.live})
     if device_loop:
         rec = GameRecords(d_moves, d_lens, d_winner, d_visits, first_game_id, overflow)
         winner = d_winner.cpu().numpy()
     else:
-        rec = GameRecords(torch.from_numpy(games.moves).to(dev), torch.from_numpy(games.lens).to(dev), torch.from_numpy(games.winner).to(dev),
-                          torch.from_numpy(visits.view(np.int16)).to(dev), first_game_id, overflow)
+        rec = _records_from_host(games, visits, dev, first_game_id, overflow)
         winner = games.winner
     rec.groups = groups
     return rec, black, evaluation_scores(winner, black)
@@ -958,23 +885,13 @@ def play_pattern_games(n_games, opening_plies=4, seed=G.DEFAULT_SEED, first_game
     move i saw, 0 for opening plies and past the end); the records carry the kernel's status words as `.status` (int32[n], lib.PATTERN_*)."""
     if max_moves < 1:
         raise ValueError("play_pattern_games: max_moves must be at least 1")
-    G.init(torch.cuda.current_device() if device is None else device.index)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-    moves = np.zeros((n_games, N), dtype=np.uint8)
-    lens = np.zeros(n_games, dtype=np.int32)
-    if opening_plies > 0 and n_games > 0:
-        m, l, _ = G.synth_boards(n_games, 0, seed=seed, first_board=first_game_id)
-        lens = np.minimum(l, opening_plies).astype(np.int32)
-        keep = min(int(opening_plies), m.shape[1])
-        moves[:, :keep] = np.where(np.arange(keep)[None, :] < lens[:, None], m[:, :keep], 0)
+    dev, stream = _device(device)
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        d_moves, d_lens = torch.from_numpy(moves).to(dev), torch.from_numpy(lens).to(dev)
-        d_winner = torch.zeros(n_games, dtype=torch.int8, device=dev)
+        d_moves, d_lens, d_winner, _ = _record_tensors(n_games, dev, _opening(n_games, seed, first_game_id, opening_plies), visits=False)
         d_values = torch.zeros((n_games, N), dtype=torch.float32, device=dev)
         d_status = torch.zeros(n_games, dtype=torch.int32, device=dev)
         G.pattern_play(d_moves.data_ptr(), d_lens.data_ptr(), n_games, filter, max_moves if max_moves < N else 0,
-                       d_winner.data_ptr(), d_values.data_ptr(), d_status.data_ptr(), stream.cuda_stream)
+                       d_winner.data_ptr(), d_values.data_ptr(), d_status.data_ptr(), stream)
     rec = GameRecords(d_moves, d_lens, d_winner, None, first_game_id)
     rec.status = d_status
     return rec, d_values

@@ -248,3 +248,177 @@ def test_network_slot_loops_refuse_what_they_would_ignore():
         selfplay.play_network_games(8, None, 4, slots=2, max_moves=10)
     with pytest.raises(ValueError):
         selfplay.play_network_games(8, None, 4, slots=2, opening_plies=12)
+
+
+# ---- the shared pieces of the game loops (selfplay._HostGames.play, _hand_over, _supervisor_host_loop, _arena_nodes, _opening) ----
+def _ledger_script():
+    """Steps (active, best, rows, stall_ends_game, movers) for 6 games: game 0 is won by black at its ninth ply and stays in its slot,
+    a mover stalls with the flag both ways, one step masks a side as the match loop does, and rows carry counts of 32 768 and above and
+    counts above 65 535."""
+    rng = np.random.RandomState(3)
+
+    def rows(k):
+        r = rng.randint(0, 50, size=(k, 225)).astype(np.uint32)
+        r[:, 7] = 32768 + rng.randint(0, 1000, size=k)              # not negative behind the int16 view
+        r[0, 9], r[-1, 11] = 65535, 70000                           # saturates
+        return r
+
+    steps = []
+    for t in range(9):                                              # black: cells 0..4 of row 0, white: row 1 -- five in a row at ply 9
+        cell0 = t // 2 if t % 2 == 0 else 15 + t // 2
+        steps.append((np.array([0, 1, 2]), np.array([cell0, 100 + t, 200 + t]), rows(3), True, None))
+    steps.append((np.array([0, 1, 2]), np.array([30, -1, 209]), rows(3), False, None))          # finished game 0; game 1 stalls and stays
+    steps.append((np.array([0, 1, 2]), np.array([31, 109, -1]), rows(3), True, None))           # game 1 goes on; game 2 stalls and is over
+    steps.append((np.array([3, 2, 4, 5]), np.array([40, 41, -1, 42]), rows(4), True, np.array([True, True, False, False])))   # masked: neither play nor stall
+    steps.append((np.array([3, 2, 4, 5]), np.array([-1, 50, 51, 52]), rows(4), True, np.array([False, False, True, True])))
+    steps.append((np.array([5, 4]), np.array([-1, 60]), rows(2), True, np.array([True, True])))  # a mover of the masked form stalls: over
+    steps.append((np.array([5, 4, 1]), np.array([61, 62, 110]), rows(3), True, None))
+    return steps
+
+
+def test_ledger_matches_a_move_by_move_restatement_on_the_board():
+    """_HostGames.play -- the one ledger step of every host-driven loop -- against core.Board, game by game: who moves, who is marked over,
+    which row lands at which ply (the ply the move was made at), saturation at 65 535, and the step handed back for tree.step."""
+    from gomokuai_amd.selfplay import _HostGames, _records_from_host
+    n = 6
+    hg, visits = _HostGames(n), np.zeros((n, 225, 225), dtype=np.uint16)
+    boards, over, moves, want = [core.Board() for _ in range(n)], [False] * n, [[] for _ in range(n)], np.zeros((n, 225, 225), dtype=np.int64)
+    for active, best, rows, stall, movers in _ledger_script():
+        step = hg.play(active, best, rows, visits, stall_ends_game=stall, movers=movers)
+        expect = np.full(len(active), -1)
+        for s, g in enumerate(active):
+            if over[g] or (movers is not None and not movers[s]):
+                continue
+            if best[s] < 0:
+                over[g] = stall
+                continue
+            want[g, len(moves[g])] = np.minimum(rows[s], 65535)
+            moves[g].append(int(best[s]))
+            boards[g].apply_move(core.Position(int(best[s])))
+            over[g] = bool(boards[g].status["is_end"])
+            expect[s] = best[s]
+        assert step.dtype == np.int16 and (step == expect).all()
+        assert [bool(o) for o in hg.over] == over
+        assert all(list(hg.moves[g, :hg.lens[g]]) == moves[g] for g in range(n))
+    assert int(hg.winner[0]) == 1 == int(boards[0].status["winner"]) and hg.lens[0] == 9 and not hg.winner[1:].any()
+    assert (visits.astype(np.int64) == want).all() and want.max() == 65535 and ((want >= 32768) & (want < 65535)).any()
+    rec = _records_from_host(hg, visits, torch.device("cpu"), 4, True)
+    assert rec.visits.dtype == torch.int16 and (rec.visits.numpy().view(np.uint16).astype(np.int64) == want).all()
+    assert rec.first_game_id == 4 and rec.overflow and (rec.lens.numpy() == [len(m) for m in moves]).all()
+    pi = rec.samples(1)[2][2]                                       # a count of 32 768 and above is the row's weight, not a negative one
+    assert pi.argmax() == 7 and abs(float(pi.sum()) - 1) < 1e-3 and (pi >= 0).all()
+
+
+def test_hand_over_fills_the_lowest_finished_slots_in_game_order():
+    from gomokuai_amd.selfplay import _hand_over
+    over, active, waiting, started = np.zeros(7, dtype=bool), np.arange(3), list(range(3, 7)), [0, 1, 2]
+    for ending in ([], [1], [0, 2], [], [3, 4, 1], [5], [0, 2, 3, 4], [6], []):        # the order in which games end
+        over[ending] = True
+        want_active, want_waiting, want_fresh = active.copy(), list(waiting), np.zeros(3, dtype=bool)
+        for slot in range(3):                                       # the rule, slot by slot
+            if over[want_active[slot]] and want_waiting:
+                want_active[slot], want_fresh[slot] = want_waiting.pop(0), True
+        fresh = _hand_over(active, over, waiting)
+        assert fresh.dtype == bool and (fresh == want_fresh).all() and (active == want_active).all() and waiting == want_waiting
+        started += list(active[fresh])
+    assert started == list(range(7)) and waiting == [] and over.all()
+    # fewer waiting games than finished slots: the lowest slots get them
+    over, active, waiting = np.array([True, True, True, False, False]), np.array([2, 0, 1]), [4]
+    assert list(_hand_over(active, over, waiting)) == [True, False, False] and list(active) == [4, 0, 1] and waiting == []
+    # an empty group
+    active = np.zeros(0, dtype=np.int64)
+    assert _hand_over(active, over, []).shape == (0,) and _hand_over(active, over, [3]).shape == (0,)
+
+
+class _ScriptedTree:
+    """A stand-in for lib.TraditionalMCTS in _supervisor_host_loop: root_stats() is a pure function of the position each slot was given
+    (set_positions, then step), so the games it plays do not depend on slots -- if the loop hands it the right positions."""
+
+    def __init__(self, n):
+        self.n, self.positions, self.ids = n, [None] * n, None
+
+    def set_game_ids(self, ids):
+        self.ids = np.array(ids)
+
+    def set_positions(self, moves, lens):
+        assert moves.shape == (self.n, 225) and lens.shape == (self.n,)
+        for s in range(self.n):
+            if lens[s] >= 0:
+                self.positions[s] = [int(c) for c in moves[s, :lens[s]]]
+
+    def add_root_noise(self, alpha, epsilon, seed, first_game_id, stream):
+        pass
+
+    def run(self, playouts, stream):
+        pass
+
+    def root_stats(self):
+        visits, best = np.zeros((self.n, 225), dtype=np.uint32), np.full(self.n, -1, dtype=np.int32)
+        for s, pos in enumerate(self.positions):
+            empty = [c for c in range(225) if c not in pos]
+            row = (len(pos) % 2) * 7 + pos[0] % 7                   # black and white each fill a row of their own: a five after nine plies or so
+            target = next((c for c in range(15 * row, 15 * row + 15) if c in empty), empty[0])
+            visits[s, empty] = [(c * 7 + len(pos)) % 50 for c in empty]
+            visits[s, target] = 40000 + len(pos)
+            best[s] = target
+        return {"visits": visits, "best": best, "status": np.zeros(self.n, dtype=np.int32)}
+
+    def step(self, cells):
+        assert cells.dtype == np.int16 and cells.shape == (self.n,)
+        for s, c in enumerate(cells):
+            if c >= 0:
+                self.positions[s].append(int(c))
+
+
+@pytest.mark.parametrize("reuse_subtree", [False, True])
+def test_supervisor_host_loop_plays_the_same_games_through_any_slots(reuse_subtree):
+    """The one host-driven loop of play_supervisor_games with a scripted searcher: 9 games through 3 slots give the records of 9 slots,
+    with fresh roots and with kept trees (where only a slot that changed hands gets a new position)."""
+    from gomokuai_amd.selfplay import _HostGames, _supervisor_host_loop
+    out = []
+    for slots, steps in ((9, 225), (3, (9 // 3 + 2) * 225)):
+        games = _HostGames(9)
+        games.apply(np.arange(9) * 16 + 20)                         # a different first stone per game
+        tree = _ScriptedTree(slots)
+        visits, overflow = _supervisor_host_loop(tree, games, slots, steps, 10, reuse_subtree, None, 1, 0, None)
+        assert games.over.all() and not overflow and len(set(tree.ids)) == slots
+        out.append((games.moves, games.lens, games.winner, visits))
+    assert all((a == b).all() for a, b in zip(*out))
+    assert (out[0][2] != 0).all() and int(out[0][1].max()) < 40 and int(out[0][3].max()) >= 40000
+
+
+def test_arena_nodes_are_what_each_entry_point_asked_for():
+    """selfplay._arena_nodes against the expressions of the entry points it replaced, written out: the four spellings, with the clamp to the
+    24-bit node index and without it (play_games)."""
+    from gomokuai_amd.selfplay import _arena_nodes
+    top = (1 << 24) - 1
+    for p in (1, 400, 100000):
+        for kept, k in ((False, 1), (True, 3)):
+            assert _arena_nodes("games", p, kept) == p * 225 * k + 1                              # play_games: not clamped
+            assert _arena_nodes("supervisor", p, kept) == min(k * p * 226 + 1, top)               # play_supervisor_games, all three loops
+            assert _arena_nodes("network", p, kept) == min(k * p * 225 + 1, top)                  # play_network_games, the K7 handle of play_evaluation_games
+            assert _arena_nodes("match", p, kept) == min(k * p * 226 + 256, top)                  # the opponent of play_evaluation_games
+            assert _arena_nodes("network", p, kept, node_capacity=777) == 777
+        assert _arena_nodes("match", p) == min(p * 226 + 256, top)                                # the K6 / K8 searchers of play_match_games
+        assert _arena_nodes("games", p) == p * 225 + 1                                            # its K3 searcher: BatchedMCTS(playouts_capacity=p)
+    assert _arena_nodes("games", 100000, True) == 67500001 > top == _arena_nodes("network", 100000, True)
+
+
+@pytest.mark.parametrize("plies", [0, 1, 4, 12])
+def test_opening_is_the_synthetic_game_cut_to_its_plies(plies):
+    from gomokuai_amd import lib as G
+    from gomokuai_amd.selfplay import _HostGames, _last_two, _opening
+    n, seed, first = 40, 11, 7
+    m, l, _ = G.synth_boards(n, 0, seed=seed, first_board=first)
+    moves, lens = _opening(n, seed, first, plies)
+    assert moves.shape == (n, 225) and moves.dtype == np.uint8 and lens.dtype == np.int32
+    assert (lens == np.minimum(l, plies)).all() and (plies == 0 or (lens == plies).any())
+    last = _last_two(moves, lens)
+    for g in range(n):
+        assert (moves[g, :lens[g]] == m[g, :lens[g]]).all() and not moves[g, lens[g]:].any()
+        assert last[g, 0] == (m[g, lens[g] - 1] if lens[g] > 0 else -1) and last[g, 1] == (m[g, lens[g] - 2] if lens[g] > 1 else -1)
+    games, old = _HostGames.opened(n, seed, first, plies), _HostGames(n)
+    for i in range(plies):                                          # the loop it replaces
+        old.apply(np.where(l > i, m[:, i].astype(np.int64), -1))
+    assert (games.moves == old.moves).all() and (games.lens == old.lens).all() and (games.over == old.over).all() and (games.stones == old.stones).all()
+    assert (games.last_two() == _last_two(old.moves, old.lens)).all() and (games.last_two(np.array([5, 2])) == games.last_two()[[5, 2]]).all()

@@ -11,9 +11,7 @@ n_games, slots, playouts = int(sys.argv[1]) if len(sys.argv) > 1 else 8192, int(
 reuse, noise = True, (0.05, 0.25)
 G.init(0)
 net = FusedPolicyValueNetwork(PolicyValueNetwork(seed=1).cuda().eval())
-games = selfplay._HostGames(n_games)
-m, l, _ = G.synth_boards(n_games, 0)
-games.open_with(m, l, 2)
+games = selfplay._HostGames.opened(n_games, G.DEFAULT_SEED, 0, 2)
 tree = G.AlphaZeroMCTS(slots, node_capacity=3 * playouts * 225 + 1)
 tree.set_slots(n_games, games.moves[:, :2], games.lens)
 dev = torch.device("cuda")

@@ -59,9 +59,7 @@ def selfplay64(reps=3):
 
 def advance_ms():
     n = args.games
-    m, l, _ = G.synth_boards(n, 0, first_board=0)
-    games = selfplay._HostGames(n)
-    games.open_with(m, l, 2)
+    games = selfplay._HostGames.opened(n, G.DEFAULT_SEED, 0, 2)
     planes, last = G.moves_to_planes(games.moves, games.lens), games.last_two()
     tree = G.AlphaZeroMCTS(n, node_capacity=32 * N + 1, c_puct=5.0)
     tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS["counter"])

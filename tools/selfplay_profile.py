@@ -8,9 +8,7 @@ from gomokuai_amd import lib as G
 from gomokuai_amd.selfplay import _HostGames
 torch.cuda.set_device(0); G.init(0)
 n = 2048
-games = _HostGames(n)
-m, l, _ = G.synth_boards(n, 0)
-games.open_with(m, l, 2)
+games = _HostGames.opened(n, G.DEFAULT_SEED, 0, 2)
 tree = G.TraditionalMCTS(n, node_capacity=3 * 1000 * 226 + 1)
 T = {k: 0.0 for k in ("setpos", "noise", "run", "stats", "host", "step")}
 def tick(key, t0):
