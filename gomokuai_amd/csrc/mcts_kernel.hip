@@ -23,8 +23,10 @@
 #include <cstdlib>
 #include <cstring>
 #include <random>
+#include <type_traits>
 #include <vector>
 
+#include "../../include/gomoku_sample.h"
 #include "capi_common.h"
 #include "board_device.h"
 #include "philox.h"
@@ -82,9 +84,19 @@ struct SearchParams {
     size_t arena_stride;                // nodes between a game's two arenas (0: there is one arena)
 };
 
+// K20: the first `plies` plies of a self-play game are drawn in proportion to visits^power (include/gomoku_sample.h has the rule and its
+// serial statement, gmk_sample_choose225 without proofs).  The kernels that take it are the instantiations with one MctsSample among their
+// arguments; the draw is keyed by the handle's seed, the game's global id (GameHeader::game_id) and the stones on its root board.
+struct MctsSample {
+    uint32_t seed_lo, seed_hi;
+    uint32_t plies;                              // S > 0
+    int power;                                   // k in 1..3
+};
+
+template <class... Sample>
 __device__ bool advance_one(int g, int lane, GameHeader* headers, uint2* stats, uint32_t* link, uint32_t* parent, uint2* stats2, uint32_t* link2,
                             uint32_t* parent2, size_t cap, uint8_t* rec_moves, uint16_t* rec_visits, int32_t* rec_lens, int8_t* rec_winner,
-                            int32_t* unfinished, int reuse, int flip_all, const int16_t* forced, const SlotRefill& slots);
+                            int32_t* unfinished, int reuse, int flip_all, const int16_t* forced, const SlotRefill& slots, const Sample&... sm);
 __device__ void root_noise_one(int g, int lane, GameHeader* headers, const uint32_t* link, float* root_prior, size_t cap, size_t arena_stride,
                                float alpha, float epsilon, uint32_t seed_lo, uint32_t seed_hi);
 
@@ -127,11 +139,13 @@ __device__ __forceinline__ int row_scan(int v) {                        // inclu
 // Two instantiations, so that the bare search does not carry the registers of the turn loop through its playouts.
 // kStaged: the rollouts' draws are generated in two stages (the pairs form: wavefronts of three or four games); a separate instantiation, so that
 // the other forms -- BASELINE configs[2] runs on quads -- are the code they were, to the register.
-template <bool kTurns, bool kStaged>
+// Sample: nothing, or one MctsSample (K20, kTurns only): the step between two searches draws the plies before its S, and nothing else changes.
+template <bool kTurns, bool kStaged, class... Sample>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))      // two wavefronts per SIMD: at most 256 registers
 void mcts_playouts_kernel(GameHeader* __restrict__ headers, uint2* __restrict__ stats, uint32_t* __restrict__ link,
                           uint32_t* __restrict__ parent, float* root_prior /* written by this kernel's own root_noise_one between two turns: neither const nor restrict */,
-                          SearchParams prm) {
+                          SearchParams prm, Sample... sm) {
+    static_assert(kTurns || sizeof...(Sample) == 0, "only the self-play loop moves");
     // dynamic LDS, sized by the games G and rollouts R of the block (lds_words() below): the rollout positions as line words
     // [word][rollout lane], the rollouts' random cells [block of eight plies][rollout lane], the games' leaf positions, their paths
     extern __shared__ uint32_t s_lane_lines[];
@@ -543,7 +557,7 @@ void mcts_playouts_kernel(GameHeader* __restrict__ headers, uint2* __restrict__ 
             // the game's live arena and its other one (one and the same without kept subtrees: arena_stride = 0)
             const size_t live = h_[first_ + g].arena ? prm.arena_stride : 0, other = prm.arena_stride - live;
             const bool flipped = advance_one(first_ + g, lane_, h_, st_ + live, lk_ + live, pa_ + live, st_ + other, lk_ + other, pa_ + other, cap, prm.rec_moves, prm.rec_visits,
-                                             prm.rec_lens, prm.rec_winner, prm.unfinished, prm.reuse, 0, nullptr, prm.slots);
+                                             prm.rec_lens, prm.rec_winner, prm.unfinished, prm.reuse, 0, nullptr, prm.slots, sm...);
             if (flipped && lane_ == 0) h_[first_ + g].arena ^= 1u;     // the kept subtree was compacted into the other arena: that one is the tree now
         }
     }
@@ -578,17 +592,54 @@ __global__ void mcts_init_roots_kernel(const GameHeader* __restrict__ headers, u
     parent[base] = kNone;
 }
 
+// The child a sampled ply plays (K20), as an index among the root's n_child children `kids` (their statistics, in ascending cell order, so
+// that child order IS the rule's cell order and the scan runs over the children directly); -1 on a root with `stones` >= S stones or
+// without weight, where the caller plays the most visited child.  Lane l holds the children 4 l .. 4 l + 3: the weights stay in registers,
+// one inclusive scan of the lanes' 64-bit sums gives every lane the prefix before its first child, and the first lane with a prefix above the
+// target holds the choice (as sampled_child in az_kernel.hip).  All 64 lanes call it.
+__device__ __forceinline__ int sampled_child(const uint2* kids, int n_child, int lane, const MctsSample& sm, uint32_t game_id, uint32_t stones) {
+    if (stones >= sm.plies) return -1;
+    uint64_t w[4], sum = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = 4 * lane + j;
+        w[j] = i < n_child ? gmk_sample_weight(kids[i].x, sm.power) : 0;
+        sum += w[j];
+    }
+    uint64_t incl = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t below = __shfl_up(static_cast<unsigned long long>(incl), d);
+        if (lane >= d) incl += below;
+    }
+    const uint64_t total = __shfl(static_cast<unsigned long long>(incl), 63);
+    if (total == 0) return -1;
+    const uint64_t target = gmk_sample_target(total, game_id, stones, sm.seed_lo, sm.seed_hi);
+    uint64_t prefix = incl - sum;
+    int hit = -1;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        prefix += w[j];
+        if (hit < 0 && prefix > target) hit = 4 * lane + j;
+    }
+    const unsigned long long hits = __ballot(hit >= 0);                                // (never empty: target < total)
+    return __shfl(hit, __ffsll(static_cast<long long>(hits)) - 1);
+}
+
 // One self-play move per unfinished game: MCTS::stepForward() (MCTS.cpp:129-134) + Board::applyMove with the
 // victory check (Game.cpp:37-47, 88-136) on the root position, the (move, visit counts) record of
 // agents/utils.py:29-41, and the new root.  One wavefront per game.
 // reuse: the chosen child's subtree is kept (copied into arena 2); flip_all: the caller swaps the arenas of ALL games afterwards (the lock-step
 // loop: whatever a game's tree is after this step has to be in arena 2), otherwise only a game that kept a subtree moves, and the return value
 // says so (the persistent loop: GameHeader::arena).  Returns (wave-uniform) whether the game's tree is in arena 2 now.
+// Sample: nothing, or one MctsSample (K20): a root with fewer stones than its S plays sampled_child's draw where that has one.
+template <class... Sample>
 __device__ bool advance_one(int g, int lane, GameHeader* headers, uint2* stats, uint32_t* link, uint32_t* parent, uint2* stats2, uint32_t* link2,
                             uint32_t* parent2, size_t cap, uint8_t* rec_moves, uint16_t* rec_visits, int32_t* rec_lens, int8_t* rec_winner,
                             int32_t* unfinished, int reuse, int flip_all,
                             const int16_t* forced /* null, or per game: the move to step to (MCTS::stepForward(move)), -1 = the most visited child */,
-                            const SlotRefill& slots) {
+                            const SlotRefill& slots, const Sample&... sm) {
+    static_assert(sizeof...(Sample) <= 1 && (std::is_same_v<Sample, MctsSample> && ...), "at most one MctsSample");
     GameHeader& hdr = headers[g];
     const int rec = slots.slot_game ? slots.slot_game[g] : g;      // the records' row of this slot's game
     if (rec < 0) return false;                                      // a slot that never got a game
@@ -615,7 +666,12 @@ __device__ bool advance_one(int g, int lane, GameHeader* headers, uint2* stats, 
     const int n_child = 225 - static_cast<int>(stones);
     long long best = -1;
     int best_i = 0;
-    if (first) {
+    int drawn = -1;                                                 // a sampled ply's child, -1: the most visited one (or the forced one) is played
+    if constexpr (sizeof...(Sample) == 1)
+        if (first && !can_force) drawn = sampled_child(stats + base + first, n_child, lane, (sm, ...), hdr.game_id, stones);
+    if (drawn >= 0) {
+        best_i = drawn;
+    } else if (first) {
         for (int i = lane; i < n_child; i += 64) {
             // stepForward(): std::max_element, the first maximum; stepForward(move): the child of that move
             const long long v = can_force ? ((link[base + first + i] & 0xFFu) == static_cast<uint32_t>(want) ? 1 : 0) : static_cast<long long>(stats[base + first + i].x);
@@ -767,18 +823,19 @@ void mcts_root_noise_kernel(GameHeader* __restrict__ headers, const uint32_t* __
     if (static_cast<int>(blockIdx.x) < n_games) root_noise_one(blockIdx.x, threadIdx.x, headers, link, root_prior, cap, 0, alpha, epsilon, seed_lo, seed_hi);
 }
 
+template <class... Sample>
 __global__ __launch_bounds__(64)
 void mcts_advance_kernel(GameHeader* __restrict__ headers, uint2* __restrict__ stats, uint32_t* __restrict__ link,
                          uint32_t* __restrict__ parent, uint2* __restrict__ stats2, uint32_t* __restrict__ link2,
                          uint32_t* __restrict__ parent2, size_t cap, int n_games,
                          uint8_t* __restrict__ rec_moves, uint16_t* __restrict__ rec_visits, int32_t* __restrict__ rec_lens,
                          int8_t* __restrict__ rec_winner, int32_t* __restrict__ unfinished, int reuse,
-                         const int16_t* __restrict__ forced, SlotRefill slots, int32_t* __restrict__ counters) {
+                         const int16_t* __restrict__ forced, SlotRefill slots, int32_t* __restrict__ counters, Sample... sm) {
     if (static_cast<int>(blockIdx.x) >= n_games) return;
     // counters[0] counts the games that go on, counters[1] the workgroups that are through: the last one hands the count to the caller and
     // leaves both at zero for the next launch -- no memset in front of every step (a four-byte fill is a launch of its own, and beside a
     // second handle's search it waited milliseconds for a wavefront slot)
-    advance_one(blockIdx.x, threadIdx.x, headers, stats, link, parent, stats2, link2, parent2, cap, rec_moves, rec_visits, rec_lens, rec_winner, &counters[0], reuse, 1, forced, slots);
+    advance_one(blockIdx.x, threadIdx.x, headers, stats, link, parent, stats2, link2, parent2, cap, rec_moves, rec_visits, rec_lens, rec_winner, &counters[0], reuse, 1, forced, slots, sm...);
     if (threadIdx.x == 0) {
         __threadfence();
         if (atomicAdd(&counters[1], 1) == n_games - 1) {
@@ -1007,6 +1064,14 @@ extern "C" int gmk_mcts_run(gmk_mcts* m, int playouts, void* stream) {
     m->last_stream = static_cast<hipStream_t>(stream);
     const int rollout_lanes = m->games_per_block * m->c_rollouts;
     const bool staged = 2 * rollout_lanes <= 64 && 4 * rollout_lanes > 64;      // the pairs form (mcts_playouts_kernel: kStaged)
+    if (prm.persistent && m->persistent_rec.sample_plies > 0) {     // gmk_selfplay_run_sampled: the turn loop whose step draws (K20)
+        const MctsSample sm{prm.seed_lo, prm.seed_hi, static_cast<uint32_t>(m->persistent_rec.sample_plies), m->persistent_rec.sample_power};
+        auto* kernel = staged ? mcts_playouts_kernel<true, true, MctsSample> : mcts_playouts_kernel<true, false, MctsSample>;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds_words(m->games_per_block, m->c_rollouts) * 4, m->last_stream, m->d_headers, m->d_stats, m->d_link, m->d_parent,
+                           m->d_root_prior, prm, sm);
+        GMK_HIP_CHECK(hipGetLastError());
+        return GMK_OK;
+    }
     auto* kernel = prm.persistent ? (staged ? mcts_playouts_kernel<true, true> : mcts_playouts_kernel<true, false>)
                                   : (staged ? mcts_playouts_kernel<false, true> : mcts_playouts_kernel<false, false>);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds_words(m->games_per_block, m->c_rollouts) * 4, m->last_stream, m->d_headers, m->d_stats, m->d_link, m->d_parent,
@@ -1023,10 +1088,20 @@ extern "C" int gmk_mcts_advance(gmk_mcts* m, uint8_t* d_moves, uint16_t* d_visit
     return gmk_mcts_step(m, nullptr, d_moves, d_visits, d_lens, d_winner, d_unfinished, reuse_subtree, stream);
 }
 
-extern "C" int gmk_mcts_step(gmk_mcts* m, const int16_t* d_forced_moves, uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner,
-                             int32_t* d_unfinished, int reuse_subtree, void* stream) {
-    if (m && !m->rooted) { gmk::set_error("gmk_mcts_step: gmk_mcts_set_roots has not been called"); return GMK_ERR_STATE; }
-    if (!m || !d_moves || !d_lens || !d_winner || !d_unfinished) { gmk::set_error("gmk_mcts_step: bad arguments"); return GMK_ERR_ARG; }
+// K20 for the K3 entries: the arguments every sampled entry checks before anything is launched
+static int mcts_sample_args(const char* who, int sample_plies, int sample_power) {
+    if (sample_plies < 0 || sample_plies > 225 || sample_power < 1 || sample_power > GMK_SAMPLE_MAX_POWER) {
+        gmk::set_error("%s: sample_plies takes 0 .. 225 and sample_power 1 .. %d, not %d and %d", who, GMK_SAMPLE_MAX_POWER, sample_plies, sample_power);
+        return GMK_ERR_ARG;
+    }
+    return GMK_OK;
+}
+
+// gmk_mcts_step / gmk_mcts_advance (sample_plies = 0) and gmk_mcts_advance_sampled (no forced moves; the draw is keyed by the handle's seed)
+static int mcts_step(const char* who, gmk_mcts* m, const int16_t* d_forced_moves, uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner,
+                     int32_t* d_unfinished, int reuse_subtree, int sample_plies, int sample_power, void* stream) {
+    if (m && !m->rooted) { gmk::set_error("%s: gmk_mcts_set_roots has not been called", who); return GMK_ERR_STATE; }
+    if (!m || !d_moves || !d_lens || !d_winner || !d_unfinished) { gmk::set_error("%s: bad arguments", who); return GMK_ERR_ARG; }
     hipStream_t s = static_cast<hipStream_t>(stream);
     m->last_stream = s;
     if (reuse_subtree && !m->d_stats2) {
@@ -1036,13 +1111,19 @@ extern "C" int gmk_mcts_step(gmk_mcts* m, const int16_t* d_forced_moves, uint8_t
             (void)gmk::device_free(m->d_stats2); (void)gmk::device_free(m->d_link2); (void)gmk::device_free(m->d_parent2);      // all or nothing: the guard above tests d_stats2
             m->d_stats2 = nullptr; m->d_link2 = nullptr; m->d_parent2 = nullptr;
             (void)hipGetLastError();
-            gmk::set_error("gmk_mcts_step: hipMalloc of the second arena (%zu nodes) failed", nodes);
+            gmk::set_error("%s: hipMalloc of the second arena (%zu nodes) failed", who, nodes);
             return GMK_ERR_HIP;
         }
     }
-    hipLaunchKernelGGL(mcts_advance_kernel, dim3(m->n_games), dim3(64), 0, s, m->d_headers, m->d_stats, m->d_link, m->d_parent,
-                       m->d_stats2, m->d_link2, m->d_parent2, static_cast<size_t>(m->node_capacity), m->n_games,
-                       d_moves, d_visits, d_lens, d_winner, d_unfinished, reuse_subtree, d_forced_moves, m->slots, m->d_step_counters);
+    if (sample_plies > 0)
+        hipLaunchKernelGGL(mcts_advance_kernel<MctsSample>, dim3(m->n_games), dim3(64), 0, s, m->d_headers, m->d_stats, m->d_link, m->d_parent,
+                           m->d_stats2, m->d_link2, m->d_parent2, static_cast<size_t>(m->node_capacity), m->n_games,
+                           d_moves, d_visits, d_lens, d_winner, d_unfinished, reuse_subtree, d_forced_moves, m->slots, m->d_step_counters,
+                           MctsSample{static_cast<uint32_t>(m->seed), static_cast<uint32_t>(m->seed >> 32), static_cast<uint32_t>(sample_plies), sample_power});
+    else
+        hipLaunchKernelGGL(mcts_advance_kernel<>, dim3(m->n_games), dim3(64), 0, s, m->d_headers, m->d_stats, m->d_link, m->d_parent,
+                           m->d_stats2, m->d_link2, m->d_parent2, static_cast<size_t>(m->node_capacity), m->n_games,
+                           d_moves, d_visits, d_lens, d_winner, d_unfinished, reuse_subtree, d_forced_moves, m->slots, m->d_step_counters);
     GMK_HIP_CHECK(hipGetLastError());
     if (reuse_subtree) {                                            // the copy is the live tree from here on
         std::swap(m->d_stats, m->d_stats2);
@@ -1052,16 +1133,29 @@ extern "C" int gmk_mcts_step(gmk_mcts* m, const int16_t* d_forced_moves, uint8_t
     return GMK_OK;
 }
 
+extern "C" int gmk_mcts_step(gmk_mcts* m, const int16_t* d_forced_moves, uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner,
+                             int32_t* d_unfinished, int reuse_subtree, void* stream) {
+    return mcts_step("gmk_mcts_step", m, d_forced_moves, d_moves, d_visits, d_lens, d_winner, d_unfinished, reuse_subtree, 0, 1, stream);
+}
+
+extern "C" int gmk_mcts_advance_sampled(gmk_mcts* m, uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int32_t* d_unfinished, int reuse_subtree,
+                                        int sample_plies, int sample_power, void* stream) {
+    if (const int rc = mcts_sample_args("gmk_mcts_advance_sampled", sample_plies, sample_power); rc != GMK_OK) return rc;
+    return mcts_step("gmk_mcts_advance_sampled", m, nullptr, d_moves, d_visits, d_lens, d_winner, d_unfinished, reuse_subtree, sample_plies, sample_power, stream);
+}
+
 // gmk_mcts_step for callers without device buffers of their own (the one-game searcher behind CorePyExt): the moves
 // come from the host, the record outputs go to scratch buffers owned by the handle.
 // Whole games with continuous batching, resident on the device: see SlotRefill.  The host's part is the launch loop (one search and one
 // step per move of the slots) and a 4-byte readback per move.
-extern "C" int gmk_selfplay_run(gmk_mcts* m, int n_total, uint32_t first_game_id, int playouts, int reuse_subtree, float noise_alpha, float noise_epsilon,
-                                const uint8_t* h_open_moves, int open_stride, const int32_t* h_open_lens,
-                                uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int32_t* h_steps, void* stream) {
+// `who`: the entry that was called (gmk_selfplay_run is the sample_plies = 0 case of gmk_selfplay_run_sampled)
+static int selfplay_run(const char* who, gmk_mcts* m, int n_total, uint32_t first_game_id, int playouts, int reuse_subtree, float noise_alpha, float noise_epsilon,
+                        int sample_plies, int sample_power, const uint8_t* h_open_moves, int open_stride, const int32_t* h_open_lens,
+                        uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int32_t* h_steps, void* stream) {
+    if (const int rc = mcts_sample_args(who, sample_plies, sample_power); rc != GMK_OK) return rc;
     // (playouts >= 1: a root that was never searched has no child to play, and the persistent launch ends only when every game has)
     if (!m || n_total <= 0 || playouts < 1 || !d_moves || !d_lens || !d_winner || (h_open_moves && (!h_open_lens || open_stride <= 0))) {
-        gmk::set_error("gmk_selfplay_run: bad arguments (playouts >= 1)");
+        gmk::set_error("%s: bad arguments (playouts >= 1)", who);
         return GMK_ERR_ARG;
     }
     const int n_slots = m->n_games;
@@ -1069,7 +1163,7 @@ extern "C" int gmk_selfplay_run(gmk_mcts* m, int n_total, uint32_t first_game_id
     std::vector<int32_t> open_lens(nt, 0);
     if (h_open_moves)
         for (size_t g = 0; g < nt; ++g) {
-            if (h_open_lens[g] < 0 || h_open_lens[g] > 8 || h_open_lens[g] > open_stride) { gmk::set_error("gmk_selfplay_run: opening of game %zu has %d moves (0 .. 8)", g, h_open_lens[g]); return GMK_ERR_ARG; }
+            if (h_open_lens[g] < 0 || h_open_lens[g] > 8 || h_open_lens[g] > open_stride) { gmk::set_error("%s: opening of game %zu has %d moves (0 .. 8)", who, g, h_open_lens[g]); return GMK_ERR_ARG; }
             open_lens[g] = h_open_lens[g];
         }
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1082,7 +1176,7 @@ extern "C" int gmk_selfplay_run(gmk_mcts* m, int n_total, uint32_t first_game_id
     for (size_t g = 0; g < nt; ++g)
         for (int i = 0; i < open_lens[g]; ++i) {
             const uint8_t c = h_open_moves[g * open_stride + i];
-            if (c >= 225) { gmk::set_error("gmk_selfplay_run: opening of game %zu holds cell %d", g, c); return GMK_ERR_ARG; }
+            if (c >= 225) { gmk::set_error("%s: opening of game %zu holds cell %d", who, g, c); return GMK_ERR_ARG; }
             first_moves[g * 225 + i] = c;
             if (g < static_cast<size_t>(n_slots)) { planes[g * 32 + (i & 1) * 16 + c / 15] |= static_cast<uint16_t>(1u << (c % 15)); last[g] = c; }
         }
@@ -1124,26 +1218,40 @@ extern "C" int gmk_selfplay_run(gmk_mcts* m, int n_total, uint32_t first_game_id
     int32_t steps = 0;
     rc = GMK_OK;
     if (persistent) {
-        m->persistent_rec = {d_moves, d_visits, d_lens, d_winner, d_unfinished, reuse_subtree ? 1 : 0, noisy ? noise_alpha : 0.0f, noise_epsilon};
+        m->persistent_rec = {d_moves, d_visits, d_lens, d_winner, d_unfinished, reuse_subtree ? 1 : 0, noisy ? noise_alpha : 0.0f, noise_epsilon, sample_plies, sample_power};
         rc = gmk_mcts_run(m, playouts, s);
         m->persistent_rec = {};
-        if (rc == GMK_OK && hipStreamSynchronize(s) != hipSuccess) { gmk::set_error("gmk_selfplay_run: the persistent launch failed"); rc = GMK_ERR_HIP; }
+        if (rc == GMK_OK && hipStreamSynchronize(s) != hipSuccess) { gmk::set_error("%s: the persistent launch failed", who); rc = GMK_ERR_HIP; }
         steps = 1;
     }
     for (long long step = 0; step < 226ll * (n_total / n_slots + 2) && !persistent; ++step) {
         if (noisy) rc = gmk_mcts_add_root_noise(m, noise_alpha, noise_epsilon, s);      // Default::AddNoise at the start of every search (MCTS.cpp:182)
         if (rc == GMK_OK) rc = gmk_mcts_run(m, playouts, s);
-        if (rc == GMK_OK) rc = gmk_mcts_step(m, nullptr, d_moves, d_visits, d_lens, d_winner, d_unfinished, reuse_subtree, s);
+        if (rc == GMK_OK) rc = mcts_step(who, m, nullptr, d_moves, d_visits, d_lens, d_winner, d_unfinished, reuse_subtree, sample_plies, sample_power, s);
         if (rc != GMK_OK) break;
         ++steps;
         int32_t unfinished = 0;
-        if (hipMemcpyAsync(&unfinished, d_unfinished, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { gmk::set_error("gmk_selfplay_run: readback failed"); rc = GMK_ERR_HIP; break; }
+        if (hipMemcpyAsync(&unfinished, d_unfinished, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { gmk::set_error("%s: readback failed", who); rc = GMK_ERR_HIP; break; }
         if (unfinished == 0) break;
     }
     (void)gmk::device_free(d_unfinished);
     m->slots = SlotRefill{};
     if (h_steps) *h_steps = steps;
     return rc;
+}
+
+extern "C" int gmk_selfplay_run(gmk_mcts* m, int n_total, uint32_t first_game_id, int playouts, int reuse_subtree, float noise_alpha, float noise_epsilon,
+                                const uint8_t* h_open_moves, int open_stride, const int32_t* h_open_lens,
+                                uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int32_t* h_steps, void* stream) {
+    return selfplay_run("gmk_selfplay_run", m, n_total, first_game_id, playouts, reuse_subtree, noise_alpha, noise_epsilon, 0, 1, h_open_moves, open_stride, h_open_lens,
+                        d_moves, d_visits, d_lens, d_winner, h_steps, stream);
+}
+
+extern "C" int gmk_selfplay_run_sampled(gmk_mcts* m, int n_total, uint32_t first_game_id, int playouts, int reuse_subtree, float noise_alpha, float noise_epsilon,
+                                        int sample_plies, int sample_power, const uint8_t* h_open_moves, int open_stride, const int32_t* h_open_lens,
+                                        uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int32_t* h_steps, void* stream) {
+    return selfplay_run("gmk_selfplay_run_sampled", m, n_total, first_game_id, playouts, reuse_subtree, noise_alpha, noise_epsilon, sample_plies, sample_power, h_open_moves,
+                        open_stride, h_open_lens, d_moves, d_visits, d_lens, d_winner, h_steps, stream);
 }
 
 extern "C" int gmk_mcts_step_host(gmk_mcts* m, const int16_t* h_moves, int reuse_subtree) {

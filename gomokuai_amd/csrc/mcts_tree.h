@@ -60,7 +60,7 @@ struct gmk_mcts {
     float* d_root_prior = nullptr;     // [n_games][225] by child index, used while GameHeader::noise is set
     float* d_value = nullptr;          // [2 * c_rollouts + 1] rollout sum -> state value
     gmk::mcts::SlotRefill slots{};                // continuous batching (gmk_selfplay_run); all null otherwise
-    struct { uint8_t* moves; uint16_t* visits; int32_t* lens; int8_t* winner; int32_t* unfinished; int reuse; float noise_alpha, noise_epsilon; } persistent_rec{};     // set while gmk_selfplay_run's ONE launch is issued
+    struct { uint8_t* moves; uint16_t* visits; int32_t* lens; int8_t* winner; int32_t* unfinished; int reuse; float noise_alpha, noise_epsilon; int sample_plies, sample_power; } persistent_rec{};     // set while gmk_selfplay_run's ONE launch is issued
     int32_t* d_slot_state = nullptr;   // [n_games + 1] slot_game, next_game
     int32_t* d_step_counters = nullptr; // [2] mcts_advance_kernel's own (zero between launches)
     uint8_t* d_open_moves = nullptr;

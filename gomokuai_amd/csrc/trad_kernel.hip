@@ -131,9 +131,11 @@ __device__ __forceinline__ void trad_root_noise(uint2* info, const uint32_t* lin
 // kRave: TraditionalPolicy with RAVE::BackPropogate<true> (gmk_trad_run_rave, policy 2 of the self-play loop): the same playout, the backup
 // also keeps every child's all-moves-as-first statistics (the node's AMAF record, prm.amaf) against the LEAF position -- the evaluator's
 // row words -- and ranks the children by PUCB + the HandSelect-weighted value, as K8 does on its finished board.
-template <bool kSelfPlay, bool kRave>
+// Sample: nothing, or one TradSample (K20, kSelfPlay only): the plies before its S are drawn by sampled_child, and nothing else changes.
+template <bool kSelfPlay, bool kRave, class... Sample>
 __global__ __launch_bounds__(kThreads)
-void trad_playouts_kernel(TradParams prm) {
+void trad_playouts_kernel(TradParams prm, Sample... sm) {
+    static_assert(kSelfPlay || sizeof...(Sample) == 0, "only the self-play loop moves");
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     // layout: [trans][records, then the four-symbol prefix table: record_words counts both][games: kGamesPerBlock * kPerGame]
     for (int i = threadIdx.x; i < prm.trans_words + prm.record_words; i += kThreads)
@@ -477,13 +479,18 @@ void trad_playouts_kernel(TradParams prm) {
         const TradSelfPlay& sp = prm.sp;
         if (lane == 0 && (status & 1u)) atomicOr(sp.overflow, 1);
         const uint32_t lk = g.link[0], first = lk & 0xFFFFFFu, n = lk >> 24;
-        const uint32_t best_id = most_visited_child(g.stat, g.ord, first, n, lane);
+        // (a sampled ply draws from the root's row by cell: the record's row, written first, or -- no rows asked for -- a row in the game's path
+        // words, which are idle between two searches)
+        uint16_t* const record_row = sp.rec_visits ? sp.rec_visits + (static_cast<size_t>(sp_game) * 225 + static_cast<size_t>(cur_len)) * 225 : nullptr;
+        bool row_written;
+        const uint32_t best_id = root_child(g.stat, g.info, g.ord, first, n, lane, static_cast<uint32_t>(sp_game), static_cast<uint32_t>(cur_len), record_row,
+                                            reinterpret_cast<uint16_t*>(g.path_node), &row_written, SyncWave{}, sm...);
         bool over = best_id == kNoChild || cur_len >= 225;      // no child: nothing the policy wants to play: the game ends where it stands
         int winner = 0;
         if (!over) {
             const uint32_t cell = g.info[best_id].x >> 24;
-            if (sp.rec_visits)
-                visits_by_cell(sp.rec_visits + (static_cast<size_t>(sp_game) * 225 + static_cast<size_t>(cur_len)) * 225, g.stat, g.info, first, n, lane, SyncWave{});
+            if (sp.rec_visits && !row_written)
+                visits_by_cell(record_row, g.stat, g.info, first, n, lane, SyncWave{});
             // (the path is rebuilt by the next search: sixteen words of it hold the board's rows here)
             winner = play_cell(slot_moves, cur_len, cell, g.path_node, lane, SyncWave{});
             if (lane == 0) {
@@ -592,12 +599,25 @@ void trad_step_kernel(TradArena a, TradArena b, TradHeader* hdrs, int cap, int n
     if (lane == 0) hdr.n_nodes = kept;
 }
 
+// the by-cell row of a one-wavefront kernel that samples and was handed no record row: 225 counts in LDS (none in the unsampled kernels)
+template <class... Sample>
+__device__ __forceinline__ uint16_t* sample_row_lds() {
+    if constexpr (sizeof...(Sample) != 0) {
+        __shared__ uint16_t s_row[226];
+        return s_row;
+    } else {
+        return nullptr;
+    }
+}
+
 // The step of the device-resident self-play loop (gmk_trad_selfplay_run): what play_supervisor_games does on the host after every search --
 // MCTS::stepForward()'s choice (MCTS.cpp:129-134), the root visit counts into the game's record, Board::applyMove with its victory check
 // (Game.cpp:37-49, 88-136) -- and the hand-over of a finished game's slot (tree arena, evaluator, wavefront) to the next unstarted game
 // (network/data_helper.py:56-83 plays its games one after the other per worker; here a slot does).  One wavefront per slot.
+// Sample: nothing, or one TradSample (K20): the plies before its S are drawn by sampled_child, and nothing else changes.
+template <class... Sample>
 __global__ __launch_bounds__(64)
-void trad_advance_kernel(TradArena a, TradArena b, TradHeader* hdrs, int cap, int n_slots, uint8_t* moves, int32_t* lens, TradSelfPlay sp, int reuse) {
+void trad_advance_kernel(TradArena a, TradArena b, TradHeader* hdrs, int cap, int n_slots, uint8_t* moves, int32_t* lens, TradSelfPlay sp, int reuse, Sample... sm) {
     __shared__ uint32_t s_rows[16];
     const int slot = blockIdx.x, lane = threadIdx.x;
     if (slot >= n_slots) return;
@@ -611,13 +631,16 @@ void trad_advance_kernel(TradArena a, TradArena b, TradHeader* hdrs, int cap, in
     // the child to keep: the most visited one, first in the current order (as trad_step_kernel / trad_root_stats_kernel)
     const bool searched = hdr.fresh != 1u;                      // (a position that was never searched has no root node yet)
     const uint32_t lk = searched ? a.link[base] : 0u, first = lk & 0xFFFFFFu, n = lk >> 24;
-    const uint32_t best_id = most_visited_child(a.stat + base, a.ord + base, first, n, lane);
+    uint16_t* const record_row = sp.rec_visits ? sp.rec_visits + (static_cast<size_t>(game) * 225 + static_cast<size_t>(len)) * 225 : nullptr;
+    bool row_written;                                           // (a sampled ply draws from the row by cell and writes it first)
+    const uint32_t best_id = root_child(a.stat + base, a.info + base, a.ord + base, first, n, lane, static_cast<uint32_t>(game), static_cast<uint32_t>(len), record_row,
+                                        sample_row_lds<Sample...>(), &row_written, SyncBlock{}, sm...);
     bool over = best_id == kNoChild || len >= 225;              // no child: nothing the policy wants to play: the game ends where it stands
     int winner = 0;
     if (!over) {
         const uint32_t cell = a.info[base + best_id].x >> 24;
-        if (sp.rec_visits)                                      // the root's visit counts by cell, the searched ply's row of the game's record
-            visits_by_cell(sp.rec_visits + (static_cast<size_t>(game) * 225 + static_cast<size_t>(len)) * 225, a.stat + base, a.info + base, first, n, lane, SyncBlock{});
+        if (sp.rec_visits && !row_written)                      // the root's visit counts by cell, the searched ply's row of the game's record
+            visits_by_cell(record_row, a.stat + base, a.info + base, first, n, lane, SyncBlock{});
         // five or more through the move win, a full board is a tie
         winner = play_cell(mv, len, cell, s_rows, lane, SyncBlock{});
         if (lane == 0) {
@@ -729,15 +752,33 @@ void trad_root_stats_kernel(TradArena a, const TradHeader* hdrs, int cap, uint32
 
 // trad_root_stats_kernel's `best` and visit counts, left ON THE DEVICE for the match referee (match_kernel.hip): the cell as int16 (-1: a
 // root without children), the counts by cell saturated like the records' rows (visits may be null).  One wavefront per game.
+// Sample: nothing, or one TradRootSample (K20, gmk_trad_root_choice_sampled): the cell trad_advance_kernel<TradSample> would play for the
+// game the slot holds (game_ids, as the root noise names it) at the stones of its position.
+struct TradRootSample {
+    TradSample sample;
+    const uint32_t* game_ids;                    // [n_games] relative to sample.first_game_id
+    const int32_t* lens;                         // [n_games] stones on the root board
+};
+template <class... Sample>
 __global__ __launch_bounds__(64)
-void trad_root_choice_kernel(TradArena a, const TradHeader* hdrs, int cap, int n_games, int16_t* __restrict__ cells, uint16_t* __restrict__ visits) {
+void trad_root_choice_kernel(TradArena a, const TradHeader* hdrs, int cap, int n_games, int16_t* __restrict__ cells, uint16_t* __restrict__ visits, Sample... sm) {
+    static_assert(sizeof...(Sample) <= 1 && (std::is_same_v<Sample, TradRootSample> && ...), "at most one TradRootSample");
     const int game = blockIdx.x, lane = threadIdx.x;
     if (game >= n_games) return;
     const size_t base = static_cast<size_t>(game) * cap;
     const bool no_root = hdrs[game].fresh == 1u;                // the position was set but never searched
     const uint32_t lk = no_root ? 0u : a.link[base], first = lk & 0xFFFFFFu, n = lk >> 24;
-    if (visits) visits_by_cell(visits + static_cast<size_t>(game) * 225, a.stat + base, a.info + base, first, n, lane, SyncBlock{});
-    const uint32_t best_id = most_visited_child(a.stat + base, a.ord + base, first, n, lane);
+    uint32_t best_id;
+    if constexpr (sizeof...(Sample) == 1) {
+        const TradRootSample& rs = (sm, ...);
+        bool row_written;
+        best_id = root_child(a.stat + base, a.info + base, a.ord + base, first, n, lane, rs.game_ids[game], static_cast<uint32_t>(rs.lens[game]),
+                             visits ? visits + static_cast<size_t>(game) * 225 : nullptr, sample_row_lds<Sample...>(), &row_written, SyncBlock{}, rs.sample);
+        if (visits && !row_written) visits_by_cell(visits + static_cast<size_t>(game) * 225, a.stat + base, a.info + base, first, n, lane, SyncBlock{});
+    } else {
+        if (visits) visits_by_cell(visits + static_cast<size_t>(game) * 225, a.stat + base, a.info + base, first, n, lane, SyncBlock{});
+        best_id = most_visited_child(a.stat + base, a.ord + base, first, n, lane);
+    }
     if (lane == 0) cells[game] = best_id == kNoChild ? static_cast<int16_t>(-1) : static_cast<int16_t>(a.info[base + best_id].x >> 24);
 }
 
@@ -1072,7 +1113,32 @@ extern "C" int gmk_trad_step(gmk_trad* t, const int16_t* h_moves) {
 extern "C" int gmk_trad_root_choice(gmk_trad* t, int16_t* d_cells, uint16_t* d_visits, void* stream) {
     if (!t || !d_cells) { gmk::set_error("gmk_trad_root_choice: bad arguments"); return GMK_ERR_ARG; }
     if (!t->positioned) { gmk::set_error("gmk_trad_root_choice: gmk_trad_set_positions has not been called"); return GMK_ERR_STATE; }
-    hipLaunchKernelGGL(trad_root_choice_kernel, dim3(t->n_games), dim3(64), 0, static_cast<hipStream_t>(stream), t->a, t->d_hdr, t->cap, t->n_games, d_cells, d_visits);
+    hipLaunchKernelGGL(trad_root_choice_kernel<>, dim3(t->n_games), dim3(64), 0, static_cast<hipStream_t>(stream), t->a, t->d_hdr, t->cap, t->n_games, d_cells, d_visits);
+    GMK_HIP_CHECK(hipGetLastError());
+    return GMK_OK;
+}
+
+// K20 for the K6 / K8 entries: the arguments every sampled entry checks before anything is launched; *sm is the kernels' TradSample
+static int trad_sample_args(const char* who, int sample_plies, int sample_power, uint64_t seed, uint32_t first_game_id, TradSample* sm) {
+    if (sample_plies < 0 || sample_plies > 225 || sample_power < 1 || sample_power > GMK_SAMPLE_MAX_POWER) {
+        gmk::set_error("%s: sample_plies takes 0 .. 225 and sample_power 1 .. %d, not %d and %d", who, GMK_SAMPLE_MAX_POWER, sample_plies, sample_power);
+        return GMK_ERR_ARG;
+    }
+    *sm = TradSample{static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), first_game_id, static_cast<uint32_t>(sample_plies), sample_power};
+    return GMK_OK;
+}
+
+// gmk_trad_root_choice with the choice the sampled self-play step makes: the game of slot g is first_game_id + ids[g] of gmk_trad_set_game_ids
+// (default g), its stones are the length of its position.  One launch on `stream`; sample_plies = 0 is gmk_trad_root_choice.
+extern "C" int gmk_trad_root_choice_sampled(gmk_trad* t, int16_t* d_cells, uint16_t* d_visits, int sample_plies, int sample_power, uint64_t seed, uint32_t first_game_id,
+                                            void* stream) {
+    if (!t || !d_cells) { gmk::set_error("gmk_trad_root_choice_sampled: bad arguments"); return GMK_ERR_ARG; }
+    TradSample sm;
+    if (const int rc = trad_sample_args("gmk_trad_root_choice_sampled", sample_plies, sample_power, seed, first_game_id, &sm); rc != GMK_OK) return rc;
+    if (sample_plies == 0) return gmk_trad_root_choice(t, d_cells, d_visits, stream);
+    if (!t->positioned) { gmk::set_error("gmk_trad_root_choice_sampled: gmk_trad_set_positions has not been called"); return GMK_ERR_STATE; }
+    hipLaunchKernelGGL(trad_root_choice_kernel<TradRootSample>, dim3(t->n_games), dim3(64), 0, static_cast<hipStream_t>(stream), t->a, t->d_hdr, t->cap, t->n_games, d_cells, d_visits,
+                       TradRootSample{sm, t->d_game_ids, t->d_lens});
     GMK_HIP_CHECK(hipGetLastError());
     return GMK_OK;
 }
@@ -1182,18 +1248,23 @@ extern "C" int gmk_trad_read_evaluators(gmk_trad* t, int32_t* h_scores, int32_t*
 // The self-play loop of network/data_helper.py:56-83 for the pattern-guided searchers, resident on the device: n_total games through the
 // handle's slots, every move = Default::AddNoise (if asked for) + one search of `playouts` playouts for every slot that has a game +
 // trad_advance_kernel; the host sees four bytes per move (slots that still play) and, with root noise, the slots' game numbers.
-extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int policy, int n_total, uint32_t first_game_id, int playouts, double c_puct, uint64_t seed,
-                                     int reuse_subtree, float noise_alpha, float noise_epsilon,
-                                     const uint8_t* h_open_moves, int open_stride, const int32_t* h_open_lens,
-                                     uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int persistent, int max_steps, int32_t* h_overflow, int32_t* h_steps, void* stream) {
+// `who`: the entry that was called (gmk_trad_selfplay_run is the sample_plies = 0 case of gmk_trad_selfplay_run_sampled).  With S > 0 the step
+// kernels are the instantiations with a TradSample: the persistent turn draws inside the launch, the lock-step loop in trad_advance_kernel.
+static int trad_selfplay_run(const char* who, gmk_trad* t, int policy, int n_total, uint32_t first_game_id, int playouts, double c_puct, uint64_t seed,
+                             int reuse_subtree, float noise_alpha, float noise_epsilon, int sample_plies, int sample_power,
+                             const uint8_t* h_open_moves, int open_stride, const int32_t* h_open_lens,
+                             uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int persistent, int max_steps, int32_t* h_overflow, int32_t* h_steps, void* stream) {
+    TradSample sm;
+    if (const int rc = trad_sample_args(who, sample_plies, sample_power, seed, first_game_id, &sm); rc != GMK_OK) return rc;
+    const bool sampled = sample_plies > 0;
     const bool noisy = noise_alpha > 0.0f && reuse_subtree;     // (a new root has no children: AddNoise is a no-op without kept subtrees)
     if (t && t->lockstep) persistent = 0;
     if (persistent && (policy == 1 || max_steps > 0 || (noisy && t && t->noise_sampler != GMK_NOISE_SAMPLER_COUNTER))) {
-        gmk::set_error("gmk_trad_selfplay_run: the persistent loop plays TraditionalPolicy (+ RAVE) games to their end; root noise inside it comes from the counter-based sampler (GMK_OPT_NOISE_SAMPLER)");
+        gmk::set_error("%s: the persistent loop plays TraditionalPolicy (+ RAVE) games to their end; root noise inside it comes from the counter-based sampler (GMK_OPT_NOISE_SAMPLER)", who);
         return GMK_ERR_ARG;
     }
     if (!t || policy < 0 || policy > 2 || n_total <= 0 || playouts < 0 || max_steps < 0 || !d_moves || !d_lens || !d_winner || (h_open_moves && (!h_open_lens || open_stride <= 0))) {
-        gmk::set_error("gmk_trad_selfplay_run: bad arguments");
+        gmk::set_error("%s: bad arguments", who);
         return GMK_ERR_ARG;
     }
     const int n_slots = t->n_games;
@@ -1201,10 +1272,10 @@ extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int policy, int n_total, uint3
     std::vector<int32_t> open_lens(nt, 0);
     if (h_open_moves)
         for (size_t g = 0; g < nt; ++g) {
-            if (h_open_lens[g] < 0 || h_open_lens[g] > 224 || h_open_lens[g] > open_stride) { gmk::set_error("gmk_trad_selfplay_run: opening of game %zu has %d moves", g, h_open_lens[g]); return GMK_ERR_ARG; }
+            if (h_open_lens[g] < 0 || h_open_lens[g] > 224 || h_open_lens[g] > open_stride) { gmk::set_error("%s: opening of game %zu has %d moves", who, g, h_open_lens[g]); return GMK_ERR_ARG; }
             open_lens[g] = h_open_lens[g];
             for (int i = 0; i < open_lens[g]; ++i)
-                if (h_open_moves[g * open_stride + i] >= 225) { gmk::set_error("gmk_trad_selfplay_run: opening of game %zu holds cell %d", g, h_open_moves[g * open_stride + i]); return GMK_ERR_ARG; }
+                if (h_open_moves[g * open_stride + i] >= 225) { gmk::set_error("%s: opening of game %zu holds cell %d", who, g, h_open_moves[g * open_stride + i]); return GMK_ERR_ARG; }
         }
     hipStream_t s = static_cast<hipStream_t>(stream);
     GMK_HIP_CHECK(hipDeviceSynchronize());
@@ -1225,7 +1296,7 @@ extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int policy, int n_total, uint3
     int rc = GMK_OK;
     if (persistent && reuse_subtree) rc = pair_arenas(t);       // a slot's two arenas, a fixed stride apart
     if (rc == GMK_OK && persistent && policy == 2) {            // (the lock-step loop's gmk_trad_run_rave makes them itself)
-        if (t->policy == 1 || t->policy == 2) { gmk::set_error("gmk_trad_selfplay_run: this handle searches with another policy"); return GMK_ERR_STATE; }
+        if (t->policy == 1 || t->policy == 2) { gmk::set_error("%s: this handle searches with another policy", who); return GMK_ERR_STATE; }
         rc = ensure_amaf(t);
     }
     if (rc == GMK_OK) rc = gmk_trad_set_game_ids(t, ids.data());
@@ -1241,7 +1312,7 @@ extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int policy, int n_total, uint3
     uint8_t* d_open_moves = nullptr;
     int32_t* d_open_lens = nullptr;
     auto cleanup = [&]() { (void)gmk::device_free(d_state); (void)gmk::device_free(d_open_moves); (void)gmk::device_free(d_open_lens); };
-#define GMK_TRY(expr) do { if ((expr) != hipSuccess) { gmk::set_error("gmk_trad_selfplay_run: %s failed", #expr); cleanup(); return GMK_ERR_HIP; } } while (0)
+#define GMK_TRY(expr) do { if ((expr) != hipSuccess) { gmk::set_error("%s: %s failed", who, #expr); cleanup(); return GMK_ERR_HIP; } } while (0)
     GMK_TRY(gmk::device_malloc(&d_state, state.size() * 4));
     GMK_TRY(hipMemcpy(d_state, state.data(), state.size() * 4, hipMemcpyHostToDevice));
     GMK_TRY(gmk::device_malloc(&d_open_lens, nt * 4));
@@ -1266,19 +1337,23 @@ extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int policy, int n_total, uint3
         // ONE launch: every wavefront plays game after game at its own pace (trad_playouts_kernel, prm.selfplay)
         gmk::DeviceState& st = gmk::device_state();
         const bool rave = policy == 2;
-        if (t->policy == 2 || t->policy == (rave ? 1 : 3)) { gmk::set_error("gmk_trad_selfplay_run: this handle searches with another policy"); cleanup(); return GMK_ERR_STATE; }
+        if (t->policy == 2 || t->policy == (rave ? 1 : 3)) { gmk::set_error("%s: this handle searches with another policy", who); cleanup(); return GMK_ERR_STATE; }
         t->policy = rave ? 3 : 1;
         const size_t lds = static_cast<size_t>(kGamesPerBlock * kPerGame + st.n_states * 4 + st.n_records * 4 + gmk::kPrefixWords) * 4;
-        bool& attr_set = rave ? t->attr_set_selfplay_rave : t->attr_set_selfplay;
+        bool& attr_set = sampled ? (rave ? t->attr_set_sampled_rave : t->attr_set_sampled) : (rave ? t->attr_set_selfplay_rave : t->attr_set_selfplay);
+        const void* kernel = sampled ? (rave ? reinterpret_cast<const void*>(trad_playouts_kernel<true, true, TradSample>) : reinterpret_cast<const void*>(trad_playouts_kernel<true, false, TradSample>))
+                                     : (rave ? reinterpret_cast<const void*>(trad_playouts_kernel<true, true>) : reinterpret_cast<const void*>(trad_playouts_kernel<true, false>));
         if (!attr_set) {
-            GMK_TRY(hipFuncSetAttribute(rave ? reinterpret_cast<const void*>(trad_playouts_kernel<true, true>) : reinterpret_cast<const void*>(trad_playouts_kernel<true, false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            GMK_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             attr_set = true;
         }
         TradParams prm = trad_params(t, st, playouts, c_puct);
         prm.selfplay = 1; prm.sp = sp;
-        if (rave) hipLaunchKernelGGL((trad_playouts_kernel<true, true>), dim3((n_slots + kGamesPerBlock - 1) / kGamesPerBlock), dim3(kThreads), lds, s, prm);
-        else hipLaunchKernelGGL((trad_playouts_kernel<true, false>), dim3((n_slots + kGamesPerBlock - 1) / kGamesPerBlock), dim3(kThreads), lds, s, prm);
+        const dim3 grid((n_slots + kGamesPerBlock - 1) / kGamesPerBlock);
+        if (sampled && rave) hipLaunchKernelGGL((trad_playouts_kernel<true, true, TradSample>), grid, dim3(kThreads), lds, s, prm, sm);
+        else if (sampled) hipLaunchKernelGGL((trad_playouts_kernel<true, false, TradSample>), grid, dim3(kThreads), lds, s, prm, sm);
+        else if (rave) hipLaunchKernelGGL((trad_playouts_kernel<true, true>), grid, dim3(kThreads), lds, s, prm);
+        else hipLaunchKernelGGL((trad_playouts_kernel<true, false>), grid, dim3(kThreads), lds, s, prm);
         GMK_TRY(hipGetLastError());
         GMK_TRY(hipStreamSynchronize(s));
         steps = 1;
@@ -1299,9 +1374,10 @@ extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int policy, int n_total, uint3
         rc = policy == 1 ? gmk_trad_run_poolrave(t, playouts, c_puct, seed, first_game_id, s)
            : policy == 2 ? gmk_trad_run_rave(t, playouts, c_puct, s) : gmk_trad_run(t, playouts, c_puct, s);
         if (rc != GMK_OK) break;
-        if (reuse_subtree && (rc = trad_second_arena(t, "gmk_trad_selfplay_run")) != GMK_OK) break;     // the arenas flip at every step (as gmk_trad_step)
+        if (reuse_subtree && (rc = trad_second_arena(t, who)) != GMK_OK) break;     // the arenas flip at every step (as gmk_trad_step)
         GMK_TRY(hipMemsetAsync(sp.unfinished, 0, 4, s));
-        hipLaunchKernelGGL(trad_advance_kernel, dim3(n_slots), dim3(64), 0, s, t->a, t->b, t->d_hdr, t->cap, n_slots, t->d_moves, t->d_lens, sp, reuse_subtree ? 1 : 0);
+        if (sampled) hipLaunchKernelGGL(trad_advance_kernel<TradSample>, dim3(n_slots), dim3(64), 0, s, t->a, t->b, t->d_hdr, t->cap, n_slots, t->d_moves, t->d_lens, sp, reuse_subtree ? 1 : 0, sm);
+        else hipLaunchKernelGGL(trad_advance_kernel<>, dim3(n_slots), dim3(64), 0, s, t->a, t->b, t->d_hdr, t->cap, n_slots, t->d_moves, t->d_lens, sp, reuse_subtree ? 1 : 0);
         hipLaunchKernelGGL(trad_refill_kernel, dim3(1), dim3(64), 0, s, t->d_hdr, n_slots, t->d_moves, t->d_lens, sp);
         GMK_TRY(hipGetLastError());
         ++steps;
@@ -1321,4 +1397,20 @@ extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int policy, int n_total, uint3
     // the handle is left with idle slots: position it again (gmk_trad_set_positions) before any other use
     t->positioned = false;
     return rc;
+}
+
+extern "C" int gmk_trad_selfplay_run(gmk_trad* t, int policy, int n_total, uint32_t first_game_id, int playouts, double c_puct, uint64_t seed,
+                                     int reuse_subtree, float noise_alpha, float noise_epsilon,
+                                     const uint8_t* h_open_moves, int open_stride, const int32_t* h_open_lens,
+                                     uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int persistent, int max_steps, int32_t* h_overflow, int32_t* h_steps, void* stream) {
+    return trad_selfplay_run("gmk_trad_selfplay_run", t, policy, n_total, first_game_id, playouts, c_puct, seed, reuse_subtree, noise_alpha, noise_epsilon, 0, 1, h_open_moves, open_stride,
+                             h_open_lens, d_moves, d_visits, d_lens, d_winner, persistent, max_steps, h_overflow, h_steps, stream);
+}
+
+extern "C" int gmk_trad_selfplay_run_sampled(gmk_trad* t, int policy, int n_total, uint32_t first_game_id, int playouts, double c_puct, uint64_t seed,
+                                             int reuse_subtree, float noise_alpha, float noise_epsilon, int sample_plies, int sample_power,
+                                             const uint8_t* h_open_moves, int open_stride, const int32_t* h_open_lens,
+                                             uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int persistent, int max_steps, int32_t* h_overflow, int32_t* h_steps, void* stream) {
+    return trad_selfplay_run("gmk_trad_selfplay_run_sampled", t, policy, n_total, first_game_id, playouts, c_puct, seed, reuse_subtree, noise_alpha, noise_epsilon, sample_plies, sample_power,
+                             h_open_moves, open_stride, h_open_lens, d_moves, d_visits, d_lens, d_winner, persistent, max_steps, h_overflow, h_steps, stream);
 }

@@ -7,9 +7,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
+#include "../../include/gomoku_sample.h"
 #include "board_device.h"
 #include "wave_fence.h"
 
@@ -132,6 +134,86 @@ __device__ __forceinline__ void visits_by_cell(uint16_t* row, const uint2* stat,
     for (uint32_t i = lane; i < n; i += 64) row[info[first + i].x >> 24] = static_cast<uint16_t>(min(stat[first + i].x, 65535u));
 }
 
+// K20: the first `plies` plies of a self-play game are drawn in proportion to visits^power (include/gomoku_sample.h has the rule and its
+// serial statement, gmk_sample_choose225 without proofs).  The kernels that take it are the instantiations with one TradSample among their
+// arguments; the game id is the GLOBAL one, the id the root noise is keyed by.
+struct TradSample {
+    uint32_t seed_lo, seed_hi, first_game_id;
+    uint32_t plies;                              // S > 0
+    int power;                                   // k in 1..3
+};
+
+// The cell the rule draws from a root's visit counts BY CELL (`row`: what visits_by_cell wrote, in LDS or in the game's record; the caller's
+// lanes have met since), -1 for a row without weight.  The children are not kept in cell order, so the choice is a function of the row and
+// not of them: lane l holds the cells 4 l .. 4 l + 3, cell order is lane order, the weights stay in registers, one inclusive scan of the
+// lanes' 64-bit sums gives every lane the prefix before its first cell, and the first lane with a prefix above the target holds the choice.
+__device__ __forceinline__ int sampled_cell(const uint16_t* row, int lane, const TradSample& sm, uint32_t game_id, uint32_t stones) {
+    uint64_t w[4], sum = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = 4 * lane + j;
+        w[j] = c < 225 ? gmk_sample_weight(row[c], sm.power) : 0;
+        sum += w[j];
+    }
+    uint64_t incl = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t below = __shfl_up(static_cast<unsigned long long>(incl), d);
+        if (lane >= d) incl += below;
+    }
+    const uint64_t total = __shfl(static_cast<unsigned long long>(incl), 63);
+    if (total == 0) return -1;
+    const uint64_t target = gmk_sample_target(total, game_id, stones, sm.seed_lo, sm.seed_hi);
+    uint64_t prefix = incl - sum;
+    int hit = -1;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        prefix += w[j];
+        if (hit < 0 && prefix > target) hit = 4 * lane + j;
+    }
+    const unsigned long long hits = __ballot(hit >= 0);                                // (never empty: target < total)
+    return __shfl(hit, __ffsll(static_cast<long long>(hits)) - 1);
+}
+
+// The child a sampled ply plays, called where most_visited_child is and with its result: on a root with `stones` >= S stones, without
+// children or without weight it IS most_visited_child.  Otherwise the root's row by cell is written first -- into `record_row` (the searched
+// ply's row of the game's record; *row_written says so and the caller does not write it again) or, without one, into `lds_row` (225
+// uint16_t of the caller's LDS) -- and the drawn cell's child is looked up.
+template <class Sync>
+__device__ __forceinline__ uint32_t sampled_child(const uint2* stat, const uint2* info, const uint8_t* ord, uint32_t first, uint32_t n, int lane, const TradSample& sm,
+                                                  uint32_t game_id, uint32_t stones, uint16_t* record_row, uint16_t* lds_row, bool* row_written, Sync sync) {
+    *row_written = false;
+    if (stones >= sm.plies || n == 0u) return most_visited_child(stat, ord, first, n, lane);
+    int cell;
+    if (record_row) {
+        visits_by_cell(record_row, stat, info, first, n, lane, sync);
+        sync();
+        cell = sampled_cell(record_row, lane, sm, game_id, stones);
+        *row_written = true;
+    } else {
+        visits_by_cell(lds_row, stat, info, first, n, lane, sync);
+        sync();
+        cell = sampled_cell(lds_row, lane, sm, game_id, stones);
+    }
+    if (cell < 0) return most_visited_child(stat, ord, first, n, lane);
+    return child_of_cell(info, first, n, static_cast<uint32_t>(cell), lane);
+}
+
+// The root choice of a kernel instantiated without a TradSample (most_visited_child, and nothing more is read or written) or with one
+// (sampled_child for the game `game` -- relative to the sample's first_game_id -- at `stones` stones)
+template <class Sync, class... Sample>
+__device__ __forceinline__ uint32_t root_child(const uint2* stat, const uint2* info, const uint8_t* ord, uint32_t first, uint32_t n, int lane, uint32_t game, uint32_t stones,
+                                               uint16_t* record_row, uint16_t* lds_row, bool* row_written, Sync sync, const Sample&... sm) {
+    static_assert(sizeof...(Sample) <= 1 && (std::is_same_v<Sample, TradSample> && ...), "at most one TradSample");
+    if constexpr (sizeof...(Sample) == 1) {
+        const TradSample& one = (sm, ...);
+        return sampled_child(stat, info, ord, first, n, lane, one, one.first_game_id + game, stones, record_row, lds_row, row_written, sync);
+    } else {
+        *row_written = false;
+        return most_visited_child(stat, ord, first, n, lane);
+    }
+}
+
 // Board::applyMove's victory check (Game.cpp:37-49, 88-136) for `cell` played after moves[0 .. len): the board after the move as row
 // words in rows[0 .. 16) (the caller's LDS; move i is black's when i is even, white's stones 16 bits up), five or more through the cell
 // win.  The winner: +1 black, -1 white, 0 nobody (yet).
@@ -247,7 +329,7 @@ struct gmk_trad {
     std::vector<uint32_t> game_ids;                                         // the game a slot is playing, relative to the callers' first_game_id (default: the slot number)
     uint32_t* d_game_ids = nullptr;
     uint32_t* d_path_spill = nullptr;            // [n_games][kPathSpill] K6: the child ranges of path levels the LDS copy has no room for
-    bool attr_set = false, attr_set_selfplay = false, attr_set_rave = false, attr_set_selfplay_rave = false, positioned = false, second_arena = false;
+    bool attr_set = false, attr_set_selfplay = false, attr_set_rave = false, attr_set_selfplay_rave = false, attr_set_sampled = false, attr_set_sampled_rave = false, positioned = false, second_arena = false;
     // gmk_trad_set_option
     int noise_sampler = 0;                       // GMK_NOISE_SAMPLER_STD: where Default::AddNoise draws from
     int lockstep = 0;

@@ -66,6 +66,7 @@ EXPORTS = [
     "gmk_evalstate_create", "gmk_evalstate_destroy", "gmk_evalstate_reset", "gmk_evalstate_update", "gmk_evalstate_update_host", "gmk_evalstate_read",
     "gmk_az_create", "gmk_az_destroy", "gmk_az_set_roots", "gmk_az_select", "gmk_az_expand", "gmk_az_select_host", "gmk_az_expand_host", "gmk_az_read_node_host", "gmk_az_read_children_host", "gmk_az_set_leaf_host", "gmk_az_rollout_host", "gmk_az_expand_stages_host", "gmk_az_write_stats_host", "gmk_az_step", "gmk_az_root_choice", "gmk_az_step_device", "gmk_az_advance", "gmk_az_set_slots", "gmk_az_live_games", "gmk_az_set_game_ids", "gmk_az_add_root_noise", "gmk_az_set_option", "gmk_az_add_playouts", "gmk_az_playouts_owed", "gmk_az_root_stats", "gmk_az_vcf_stats", "gmk_az_vcf_verdicts_host", "gmk_az_defend_stats", "gmk_az_defend_verdicts_host", "gmk_az_root_proofs", "gmk_az_proof_stats",
     "gmk_az_advance_sampled", "gmk_az_root_choice_sampled", "gmk_move_sample_host",
+    "gmk_mcts_advance_sampled", "gmk_selfplay_run_sampled", "gmk_trad_selfplay_run_sampled", "gmk_trad_root_choice_sampled",
     "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_root_choice", "gmk_trad_step_device", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_run_rave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
     "gmk_pvnet_set_precision", "gmk_pvnet_get_precision", "gmk_bf16_round_host",
     "gmk_pattern_policy", "gmk_pattern_policy_host", "gmk_pattern_play",
@@ -133,6 +134,9 @@ def load():
     L.gmk_mcts_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]
     L.gmk_mcts_step_host.argtypes = [vp, vp, C.c_int]
     L.gmk_selfplay_run.argtypes = [vp, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_float, C.c_float, vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(C.c_int32), vp]
+    L.gmk_mcts_advance_sampled.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    L.gmk_selfplay_run_sampled.argtypes = [vp, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(C.c_int32), vp]
+    L.gmk_trad_root_choice_sampled.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp]
     L.gmk_mcts_add_root_noise.argtypes = [vp, C.c_float, C.c_float, vp]
     L.gmk_mcts_set_option.argtypes = [vp, C.c_int, C.c_int]
     L.gmk_mcts_reserve.argtypes = [vp, C.c_int]
@@ -190,6 +194,8 @@ def load():
     L.gmk_trad_run_rave.argtypes = [vp, C.c_int, C.c_double, vp]
     L.gmk_trad_selfplay_run.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_double, C.c_uint64, C.c_int, C.c_float, C.c_float,
                                         vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
+    L.gmk_trad_selfplay_run_sampled.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_double, C.c_uint64, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
+                                                vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
     L.gmk_trad_root_amaf.argtypes = [vp, vp, vp]
     L.gmk_pvnet_create.argtypes = [vp] * 10 + [C.POINTER(vp)]
     L.gmk_pvnet_destroy.argtypes = [vp]
@@ -410,9 +416,14 @@ class BatchedMCTS:
         _check(load().gmk_mcts_root_stats(self.h, visits.ctypes.data, q.ctypes.data, rv.ctypes.data, nodes.ctypes.data, status.ctypes.data))
         return visits, q, rv, nodes, status
 
-    def advance(self, d_moves, d_visits, d_lens, d_winner, d_unfinished, reuse_subtree=False, stream=None):
-        """One self-play move for every unfinished game (device pointers as ints)."""
-        _check(load().gmk_mcts_advance(self.h, d_moves, d_visits, d_lens, d_winner, d_unfinished, int(reuse_subtree), stream))
+    def advance(self, d_moves, d_visits, d_lens, d_winner, d_unfinished, reuse_subtree=False, stream=None, sample=None):
+        """One self-play move for every unfinished game (device pointers as ints).  sample = (plies, power): gmk_mcts_advance_sampled -- a
+        game with fewer than `plies` stones on its root board plays a child drawn in proportion to visits^power (power 1..3;
+        include/gomoku_sample.h), keyed by the handle's seed, the game's global id and its stones."""
+        if sample is None:
+            _check(load().gmk_mcts_advance(self.h, d_moves, d_visits, d_lens, d_winner, d_unfinished, int(reuse_subtree), stream))
+        else:
+            _check(load().gmk_mcts_advance_sampled(self.h, d_moves, d_visits, d_lens, d_winner, d_unfinished, int(reuse_subtree), int(sample[0]), int(sample[1]), stream))
 
     def step(self, d_forced_moves, d_moves, d_visits, d_lens, d_winner, d_unfinished, reuse_subtree=False, stream=None):
         """MCTS::stepForward(move) per game: d_forced_moves int16[n] on the device, -1 = the most visited child."""
@@ -430,10 +441,11 @@ class BatchedMCTS:
         _check(load().gmk_mcts_reserve(self.h, int(bool(two_arenas))))
 
     def selfplay_run(self, n_total, first_game_id, playouts, d_moves, d_visits, d_lens, d_winner, open_moves=None, open_lens=None,
-                     reuse_subtree=False, root_noise=None, stream=None):
+                     reuse_subtree=False, root_noise=None, stream=None, sample=None):
         """gmk_selfplay_run: the handle's games are slots that play n_total whole games between them (continuous batching on the
         device).  open_moves uint8[n_total, stride] / open_lens int32[n_total] (host) or None; outputs are device pointers (ints),
-        indexed by game.  Returns the number of search launches it took."""
+        indexed by game.  sample = (plies, power): gmk_selfplay_run_sampled, the games advance(sample=) plays.  Returns the number of
+        search launches it took."""
         played = C.c_int32()
         om = ol = None
         stride = 0
@@ -443,9 +455,13 @@ class BatchedMCTS:
             assert om.ndim == 2 and om.shape[0] == n_total and ol.shape == (n_total,)
             stride = om.shape[1]
         alpha, eps = root_noise if root_noise is not None else (0.0, 0.0)
-        _check(load().gmk_selfplay_run(self.h, int(n_total), int(first_game_id), int(playouts), int(reuse_subtree), float(alpha), float(eps),
-                                       None if om is None else om.ctypes.data, stride, None if ol is None else ol.ctypes.data,
-                                       d_moves, d_visits, d_lens, d_winner, C.byref(played), stream))
+        opening = (None if om is None else om.ctypes.data, stride, None if ol is None else ol.ctypes.data)
+        if sample is None:
+            _check(load().gmk_selfplay_run(self.h, int(n_total), int(first_game_id), int(playouts), int(reuse_subtree), float(alpha), float(eps),
+                                           *opening, d_moves, d_visits, d_lens, d_winner, C.byref(played), stream))
+        else:
+            _check(load().gmk_selfplay_run_sampled(self.h, int(n_total), int(first_game_id), int(playouts), int(reuse_subtree), float(alpha), float(eps),
+                                                   int(sample[0]), int(sample[1]), *opening, d_moves, d_visits, d_lens, d_winner, C.byref(played), stream))
         return played.value
 
     def ensemble_merge(self, group, visits=None, values=None, cells=None, cells_per_game=None, root_visits=None, root_value=None, status=None, stream=None):
@@ -1106,10 +1122,16 @@ class TraditionalMCTS:
             assert m.shape == (self.n,)
             _check(load().gmk_trad_step(self.h, m.ctypes.data))
 
-    def root_choice(self, cells, visits=None, stream=None):
+    def root_choice(self, cells, visits=None, stream=None, sample=None):
         """gmk_trad_root_choice: root_stats()["best"] into cells (torch int16[n] on the GPU) and the root children's visit counts by cell,
-        saturated at 65 535, into visits (2-byte torch [n, 225], or None); nothing comes to the host."""
-        _root_choice(load().gmk_trad_root_choice, self, cells, visits, stream)
+        saturated at 65 535, into visits (2-byte torch [n, 225], or None); nothing comes to the host.
+        sample = (plies, power, seed, first_game_id): gmk_trad_root_choice_sampled, the choice selfplay_run(sample=) makes for the games of
+        set_game_ids at the stones of their positions."""
+        if sample is None:
+            _root_choice(load().gmk_trad_root_choice, self, cells, visits, stream)
+        else:
+            args = _sample_args(sample)
+            _root_choice(lambda h, c, v, s: load().gmk_trad_root_choice_sampled(h, c, v, *args, s), self, cells, visits, stream)
 
     def step_device(self, cells, verdict, fresh_root=False, stream=None):
         """gmk_trad_step_device: step() with the cells (torch int16[n]) and the referee's verdicts (torch int32[n], MATCH_*) on the GPU."""
@@ -1135,10 +1157,12 @@ class TraditionalMCTS:
         _check(load().gmk_trad_reserve(self.h, int(bool(two_arenas))))
 
     def selfplay_run(self, n_total, first_game_id, playouts, d_moves, d_visits, d_lens, d_winner, open_moves=None, open_lens=None,
-                     reuse_subtree=False, root_noise=None, seed=DEFAULT_SEED, stream=None, max_steps=0, persistent=False):
+                     reuse_subtree=False, root_noise=None, seed=DEFAULT_SEED, stream=None, max_steps=0, persistent=False, sample=None):
         """gmk_trad_selfplay_run: the handle's games are slots that play n_total whole games between them, the loop resident on the
         device (search, MCTS::stepForward's move, end-of-game check and slot hand-over are kernels).  open_moves uint8[n_total, stride] /
         open_lens int32[n_total] (host) or None; the outputs are device pointers (ints), indexed by game.
+        sample = (plies, power): gmk_trad_selfplay_run_sampled -- a game with fewer than `plies` stones plays a cell drawn in proportion to
+        visits^power (include/gomoku_sample.h), keyed by this call's seed and first_game_id.
         Returns (search launches, whether a search stopped at its node capacity)."""
         steps, overflow = C.c_int32(), C.c_int32()
         om = ol = None
@@ -1149,10 +1173,13 @@ class TraditionalMCTS:
             assert om.ndim == 2 and om.shape[0] == n_total and ol.shape == (n_total,)
             stride = om.shape[1]
         alpha, eps = root_noise if root_noise is not None else (0.0, 0.0)
-        _check(load().gmk_trad_selfplay_run(self.h, self._POOLRAVE, int(n_total), int(first_game_id), int(playouts), self.c_puct, int(seed),
-                                            int(bool(reuse_subtree)), float(alpha), float(eps),
-                                            None if om is None else om.ctypes.data, stride, None if ol is None else ol.ctypes.data,
-                                            d_moves, d_visits, d_lens, d_winner, int(bool(persistent)), int(max_steps), C.byref(overflow), C.byref(steps), stream))
+        head = (self.h, self._POOLRAVE, int(n_total), int(first_game_id), int(playouts), self.c_puct, int(seed), int(bool(reuse_subtree)), float(alpha), float(eps))
+        tail = (None if om is None else om.ctypes.data, stride, None if ol is None else ol.ctypes.data,
+                d_moves, d_visits, d_lens, d_winner, int(bool(persistent)), int(max_steps), C.byref(overflow), C.byref(steps), stream)
+        if sample is None:
+            _check(load().gmk_trad_selfplay_run(*head, *tail))
+        else:
+            _check(load().gmk_trad_selfplay_run_sampled(*head, int(sample[0]), int(sample[1]), *tail))
         return steps.value, bool(overflow.value)
 
     def root_stats(self):

@@ -211,7 +211,8 @@ def _agent_tree(kind, kw, n, cap, seed, first_game_id):
 
 def play_games(n_games, playouts, seed=G.DEFAULT_SEED, first_game_id=0, c_puct=5.0, c_rollouts=5,
                opening_plies=0, record_visits=True, reuse_subtree=False, root_noise=None, max_moves=N, device=None,
-               node_capacity=None, slots="auto", handles="auto", noise_sampler="counter", lockstep=False, prepare_only=False):
+               node_capacity=None, slots="auto", handles="auto", noise_sampler="counter", lockstep=False, prepare_only=False,
+               sample_plies=0, sample_power=1):
     """Plays n_games complete games on the current GPU: every move = one K3 search of `playouts` playouts for all
     unfinished games, then `gmk_mcts_advance`.  Game g uses the global id first_game_id + g for its RNG streams, so
     the records do not depend on how games are spread over GPUs, slots or handles.
@@ -227,7 +228,11 @@ def play_games(n_games, playouts, seed=G.DEFAULT_SEED, first_game_id=0, c_puct=5
     forces the search-by-search loop (the form the tests hold the persistent one to).
     prepare_only: create the search handles this call would create, allocate their tree arenas and give them back -- to the library's block pool,
     where the same call without prepare_only finds them (the arenas are tens of GB, and the driver clears memory it has handed out before at seconds
-    per 24 GB: a self-play job pays that once, not per batch; a measurement keeps it out of its timed region this way).  Returns None."""
+    per 24 GB: a self-play job pays that once, not per batch; a measurement keeps it out of its timed region this way).  Returns None.
+    sample_plies = S > 0: a game plays its first S plies (openings count) in proportion to visits^sample_power (1, 2, 3 = temperature 1, 1/2, 1/3)
+    and the most visited child afterwards (lib.BatchedMCTS.advance(sample=), include/gomoku_sample.h): the draw is keyed by seed, the game's
+    global id and its stone count, so the records are the same on every path and a ply's visit row gives its move again."""
+    sample = _sample_schedule("play_games", sample_plies, sample_power)
     dev, stream = _device(device)
     cap = _arena_nodes("games", playouts, reuse_subtree, node_capacity)
     # (the device-resident loop plays whole games: a cap on the moves per game takes the lock-step path below, which honours it)
@@ -253,7 +258,7 @@ def play_games(n_games, playouts, seed=G.DEFAULT_SEED, first_game_id=0, c_puct=5
                     tree.add_root_noise(noise[0], noise[1], stream)
                 tree.run(playouts, stream)
                 tree.advance(d_moves.data_ptr(), d_visits.data_ptr() if record_visits else None, d_lens.data_ptr(),
-                             d_winner.data_ptr(), d_unfinished.data_ptr(), reuse_subtree, stream)
+                             d_winner.data_ptr(), d_unfinished.data_ptr(), reuse_subtree, stream, sample)
                 if int(d_unfinished.item()) == 0:             # 4-byte readback per move: the only host sync in the loop
                     break
         else:
@@ -271,7 +276,7 @@ def play_games(n_games, playouts, seed=G.DEFAULT_SEED, first_game_id=0, c_puct=5
                 lo, hi, _ = plan[i]
                 trees[i].selfplay_run(hi - lo, first_game_id + lo, playouts, d_moves[lo:].data_ptr(), d_visits[lo:].data_ptr() if record_visits else None,
                                       d_lens[lo:].data_ptr(), d_winner[lo:].data_ptr(), None if open_moves is None else open_moves[lo:hi],
-                                      None if open_lens is None else open_lens[lo:hi], reuse_subtree, noise, hip_stream)
+                                      None if open_lens is None else open_lens[lo:hi], reuse_subtree, noise, hip_stream, sample)
 
             _on_streams(run_block, len(trees), dev, stream)
         overflow = any([_arena_full(tree.root_stats()[4], G.BatchedMCTS.STATUS_ARENA_FULL) for tree in trees])
@@ -279,6 +284,13 @@ def play_games(n_games, playouts, seed=G.DEFAULT_SEED, first_game_id=0, c_puct=5
         for tree in trees:
             tree.close()
     return GameRecords(d_moves, d_lens, d_winner, d_visits, first_game_id, overflow)
+
+
+def _sample_schedule(who, sample_plies, sample_power):
+    """(plies, power) of a self-play loop's sampled plies, None for sample_plies = 0; the bounds are the C-ABI's"""
+    if not (0 <= int(sample_plies) <= N and 1 <= int(sample_power) <= 3):
+        raise ValueError("%s: sample_plies takes 0 .. 225 and sample_power 1, 2 or 3" % who)
+    return (int(sample_plies), int(sample_power)) if int(sample_plies) > 0 else None
 
 
 def _on_streams(run, n, dev, stream):
@@ -405,7 +417,7 @@ def _supervisor_tree(policy, n, playouts, c_puct, seed, first_game_id, reuse_sub
 
 
 def _play_supervisor_on_device(n_games, n_slots, playouts, c_puct, seed, first_game_id, opening_plies, device, node_capacity, policy, reuse_subtree, root_noise, max_steps=0,
-                               persistent=False, noise_sampler="std", prepare_only=False):
+                               persistent=False, noise_sampler="std", prepare_only=False, sample=None):
     """play_supervisor_games with the loop resident on the device (gmk_trad_selfplay_run): the searches, MCTS::stepForward's move, the
     end-of-game check and the hand-over of a finished game's slot are kernels; the host reads four bytes per move.  Same games, same
     records as the host-driven loops below (tests/test_selfplay_gpu.py holds them to each other)."""
@@ -419,7 +431,7 @@ def _play_supervisor_on_device(n_games, n_slots, playouts, c_puct, seed, first_g
         d_moves, d_lens, d_winner, d_visits = _record_tensors(n_games, dev)
         torch.cuda.current_stream(dev).synchronize()
         _, overflow = tree.selfplay_run(n_games, first_game_id, playouts, d_moves.data_ptr(), d_visits.data_ptr(), d_lens.data_ptr(), d_winner.data_ptr(),
-                                        open_moves, open_lens, reuse_subtree, root_noise, seed, stream, max_steps, persistent)
+                                        open_moves, open_lens, reuse_subtree, root_noise, seed, stream, max_steps, persistent, sample)
     finally:
         tree.close()
     return GameRecords(d_moves, d_lens, d_winner, d_visits, first_game_id, overflow)
@@ -427,7 +439,7 @@ def _play_supervisor_on_device(n_games, n_slots, playouts, c_puct, seed, first_g
 
 def play_supervisor_games(n_games, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, first_game_id=0, opening_plies=0, max_moves=N,
                           device=None, node_capacity=None, reuse_subtree=False, root_noise=None, policy="traditional", slots=None, device_loop=True, max_steps=0,
-                          noise_sampler="counter", prepare_only=False):
+                          noise_sampler="counter", prepare_only=False, sample_plies=0, sample_power=1):
     """n_games complete games of the reference's self-play SUPERVISOR against itself (config.py:9-12: "traditional_mcts",
     MCTS(TraditionalPolicy) on both sides), all games side by side on the current GPU: every move = one K6 search of
     `playouts` playouts per unfinished game (the games' evaluators are kept and synchronised like the policy objects of
@@ -447,9 +459,13 @@ def play_supervisor_games(n_games, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, fi
     noise_sampler: "counter" (default) = the counter-based Dirichlet sampler of include/gomoku_noise.h, drawn on the device -- inside the ONE launch of the
     persistent loop, so that the reference agent's semantics (reuse_subtree + root_noise) run at the pace of the plain loop; "std" = std::gamma_distribution
     over std::mt19937 on the host (lock step).  PoolRAVE games draw "std" whatever is asked (their loop is lock step anyway).
+    sample_plies = S > 0: a game plays its first S plies (openings count) in proportion to visits^sample_power and MCTS::stepForward()'s choice
+    afterwards, for every policy and on every loop (lib.TraditionalMCTS.selfplay_run(sample=), include/gomoku_sample.h); in the host-driven loop
+    the host makes the same choice from the root's row (lib.move_sample_host) and steps the trees to it.
     Returns the same GameRecords as play_games (moves, per-move root visit counts, winner), so to_samples() / gather_records() apply."""
     if policy not in _POLICIES:
         raise ValueError("play_supervisor_games: policy must be one of %s" % (_POLICIES,))
+    sample = _sample_schedule("play_supervisor_games", sample_plies, sample_power)
     if device_loop and max_moves >= N:
         n_slots = n_games if slots is None else max(1, min(int(slots), n_games))
         # "persistent": one launch, every slot plays game after game at its own pace (TraditionalPolicy, whole games; kept subtrees are compacted
@@ -464,7 +480,7 @@ def play_supervisor_games(n_games, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, fi
             raise ValueError("play_supervisor_games: the persistent loop plays TraditionalPolicy (+ RAVE) games to their end, with root noise from the counter-based sampler only")
         persistent = can_persist and (device_loop == "persistent" or (device_loop is True and (n_slots < n_games or reuse_subtree)))
         return _play_supervisor_on_device(n_games, n_slots, playouts, c_puct, seed, first_game_id,
-                                          opening_plies, device, node_capacity, policy, reuse_subtree, root_noise, max_steps, persistent, noise_sampler, prepare_only)
+                                          opening_plies, device, node_capacity, policy, reuse_subtree, root_noise, max_steps, persistent, noise_sampler, prepare_only, sample)
     if prepare_only:
         return None
     if max_steps:
@@ -477,15 +493,28 @@ def play_supervisor_games(n_games, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, fi
     games = _HostGames.opened(n_games, seed, first_game_id, opening_plies)      # host boards: Board::applyMove / checkGameEnd for all games at once
     tree = _supervisor_tree(policy, n_slots, playouts, c_puct, seed, first_game_id, reuse_subtree, node_capacity, noise_sampler)
     try:
-        visits, overflow = _supervisor_host_loop(tree, games, n_slots, steps, playouts, reuse_subtree, root_noise, seed, first_game_id, stream)
+        visits, overflow = _supervisor_host_loop(tree, games, n_slots, steps, playouts, reuse_subtree, root_noise, seed, first_game_id, stream, sample)
     finally:
         tree.close()
     return _records_from_host(games, visits, dev, first_game_id, overflow)
 
 
-def _supervisor_host_loop(tree, games, slots, steps, playouts, reuse_subtree, root_noise, seed, first_game_id, stream):
+def _supervisor_choice(st, stones, games, sample, seed, first_game_id):
+    """The cell every slot of a K6 / K8 searcher plays from its root_stats() `st`: MCTS::stepForward()'s choice (st["best"]), or with sample =
+    (plies, power) the cell the sampled step kernels draw (lib.move_sample_host) where the root has fewer than `plies` stones and its row has
+    weight.  stones int[k], games int[k]: the stones on the slots' root boards and the numbers of their games."""
+    if sample is None:
+        return st["best"]
+    plies, power = sample
+    ids = (first_game_id + np.asarray(games, dtype=np.int64)) & 0xFFFFFFFF
+    drawn = G.move_sample_host(st["visits"], stones, ids, plies, power, seed)
+    return np.where((np.asarray(stones) < plies) & (st["visits"].max(1) > 0), drawn, st["best"]).astype(st["best"].dtype)
+
+
+def _supervisor_host_loop(tree, games, slots, steps, playouts, reuse_subtree, root_noise, seed, first_game_id, stream, sample=None):
     """The host-driven loop of play_supervisor_games: the games of `games` (a _HostGames) through `slots` slots of `tree`, at most `steps`
-    searches; a finished game hands its slot to the next unstarted one.  Returns (visits uint16[n, 225, 225], whether an arena filled up)."""
+    searches; a finished game hands its slot to the next unstarted one.  sample = (plies, power): the host chooses the sampled plies' moves
+    (_supervisor_choice) and the trees step to them.  Returns (visits uint16[n, 225, 225], whether an arena filled up)."""
     visits = np.zeros((games.n, N, N), dtype=np.uint16)
     active, waiting = np.arange(slots), list(range(slots, games.n))      # the game in each slot, the games not started yet
     fresh = np.ones(slots, dtype=bool)                           # slots whose game starts from a new root at the next search
@@ -505,7 +534,8 @@ def _supervisor_host_loop(tree, games, slots, steps, playouts, reuse_subtree, ro
         tree.run(playouts, stream)
         st = tree.root_stats()
         overflow |= _arena_full(st["status"], G.TraditionalMCTS.STATUS_ARENA_FULL)
-        step = games.play(active, st["best"], st["visits"], visits)     # a root without a child: nothing the policy wants to play (cannot happen on a live board)
+        best = _supervisor_choice(st, games.lens[active], active, sample, seed, first_game_id)
+        step = games.play(active, best, st["visits"], visits)          # a root without a child: nothing the policy wants to play (cannot happen on a live board)
         if reuse_subtree:
             tree.step(step)                                      # finished games ask for -1 on a childless root: nothing moves
     return visits, overflow

@@ -693,8 +693,21 @@ int gmk_az_defend_verdicts_host(gmk_az* a, int32_t* h_threat_status, int32_t* h_
  * gmk_move_sample_host: the rule for n roots given by rows, on the host (no GPU, no gmk_init): h_visits uint32[n][225] by cell, not saturated
  *   (gmk_az_root_stats' visits), h_proofs int8[n][225] (gmk_az_root_proofs' children) or NULL, h_stones int32[n] in 0 .. 225, h_game_ids
  *   uint32[n] GLOBAL ids; h_cells int16[n], -1 for a root that has nothing to play.  It equals the device entries cell for cell.
- * Not sampled: gmk_selfplay_run and gmk_trad_selfplay_run (K3, K6 / K8), gmk_az_step, and evaluation matches, which play the most visited child;
- * the policy target (gmk_visits_to_pi) is unchanged. */
+ * K3 and K6 / K8 (the searches whose games bootstrap the training loop) draw by the same rule, without proofs, from the root's visit counts BY CELL:
+ * gmk_mcts_advance_sampled / gmk_selfplay_run_sampled: gmk_mcts_advance / gmk_selfplay_run with that choice, keyed by the HANDLE's seed
+ *   (gmk_mcts_create) and the game's global id (first_game_id + index, or gmk_mcts_set_game_ids); a ply at or past sample_plies, or a root
+ *   without weight, plays gmk_mcts_advance's first maximum in cell order.  The persistent launch, GMK_OPT_LOCKSTEP and the host-drawn noise
+ *   sampler play the same games.
+ * gmk_trad_selfplay_run_sampled: gmk_trad_selfplay_run with that choice for all three policies, keyed by that call's seed and first_game_id,
+ *   in the persistent launch and in the lock-step loop alike; gmk_trad_root_choice_sampled: gmk_trad_root_choice with it, the game of slot g
+ *   being first_game_id + ids[g] of gmk_trad_set_game_ids (default g) and its stones the length of its position.  A ply at or past
+ *   sample_plies, or a root without weight, plays MCTS::stepForward()'s choice as before: the most visited child, among equals the first in
+ *   the CURRENT child order (not gmk_sample_greedy225's first in cell order).
+ *   All four: sample_plies outside 0 .. 225 or sample_power outside 1 .. 3 is GMK_ERR_ARG, nothing is launched and the handle stays usable;
+ *   sample_plies = 0 launches exactly the kernels of the unsampled entry.  The two run entries are synchronous like their unsampled forms; the
+ *   other two are one launch on `stream`.
+ * Not sampled: gmk_mcts_step with forced moves, gmk_trad_step, gmk_az_step, the ensembles (gmk_*_ensemble_merge) and evaluation matches, which play
+ * the most visited child; the policy target (gmk_visits_to_pi) is unchanged. */
 int gmk_az_advance_sampled(gmk_az* a, uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int reuse_subtree,
                            int sample_plies, int sample_power, uint64_t seed, uint32_t first_game_id, int32_t* h_unfinished, void* stream);
 int gmk_az_root_choice_sampled(gmk_az* a, int16_t* d_cells, uint16_t* d_visits, int sample_plies, int sample_power,
@@ -702,6 +715,16 @@ int gmk_az_root_choice_sampled(gmk_az* a, int16_t* d_cells, uint16_t* d_visits, 
 int gmk_move_sample_host(const uint32_t* h_visits /*[n][225], unsaturated*/, const int8_t* h_proofs /*[n][225] or NULL*/,
                          const int32_t* h_stones, const uint32_t* h_game_ids /* already global */, int n,
                          int sample_plies, int sample_power, uint64_t seed, int16_t* h_cells /* -1: none */);
+int gmk_mcts_advance_sampled(gmk_mcts* m, uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int32_t* d_unfinished, int reuse_subtree,
+                             int sample_plies, int sample_power, void* stream);
+int gmk_selfplay_run_sampled(gmk_mcts* m, int n_total, uint32_t first_game_id, int playouts, int reuse_subtree, float noise_alpha, float noise_epsilon,
+                             int sample_plies, int sample_power, const uint8_t* h_open_moves, int open_stride, const int32_t* h_open_lens,
+                             uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int32_t* h_steps, void* stream);
+int gmk_trad_selfplay_run_sampled(gmk_trad* t, int policy, int n_total, uint32_t first_game_id, int playouts, double c_puct, uint64_t seed,
+                                  int reuse_subtree, float noise_alpha, float noise_epsilon, int sample_plies, int sample_power,
+                                  const uint8_t* h_open_moves, int open_stride, const int32_t* h_open_lens,
+                                  uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int persistent, int max_steps, int32_t* h_overflow, int32_t* h_steps, void* stream);
+int gmk_trad_root_choice_sampled(gmk_trad* t, int16_t* d_cells, uint16_t* d_visits, int sample_plies, int sample_power, uint64_t seed, uint32_t first_game_id, void* stream);
 
 /* ---- K12: the referee of a match between two search handles, on the device (match_kernel.hip) ----
  * One ply of n two-agent games without the host in the loop (agents/utils.py:13-63 dual_play, :66-100 eval_agents): the side to move has
