@@ -30,6 +30,7 @@
 
 #include "board_device.h"
 #include "capi_common.h"
+#include "host_staging.h"
 #include "philox.h"
 #include "rollout_device.h"
 #include "root_noise.h"
@@ -1356,8 +1357,7 @@ extern "C" int gmk_az_destroy(gmk_az* a) {
 }
 
 extern "C" int gmk_az_create(int n_games, int node_capacity, double c_puct, gmk_az** out) {
-    gmk::DeviceState& st = gmk::device_state();
-    if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (!out || n_games <= 0 || node_capacity < 256) { gmk::set_error("gmk_az_create: bad arguments"); return GMK_ERR_ARG; }
     gmk_az* a = new gmk_az;
     a->t.n_games = n_games; a->t.cap = node_capacity; a->t.c_puct = c_puct;
@@ -2096,36 +2096,32 @@ extern "C" int gmk_az_root_stats(gmk_az* a, uint32_t* h_visits, float* h_values,
     if (!a) { gmk::set_error("gmk_az_root_stats: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_root_stats: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
     const size_t n = static_cast<size_t>(a->t.n_games);
-    uint32_t *d_visits = nullptr, *d_root_visits = nullptr;
-    float *d_values = nullptr, *d_priors = nullptr, *d_root_value = nullptr;
-    auto cleanup = [&]() { (void)gmk::device_free(d_visits); (void)gmk::device_free(d_values); (void)gmk::device_free(d_priors); (void)gmk::device_free(d_root_visits); (void)gmk::device_free(d_root_value); };
-#define GMK_TRY(expr) do { if ((expr) != hipSuccess) { gmk::set_error("%s failed", #expr); cleanup(); return GMK_ERR_HIP; } } while (0)
-    GMK_TRY(gmk::device_malloc(&d_visits, n * 225 * 4)); GMK_TRY(gmk::device_malloc(&d_values, n * 225 * 4)); GMK_TRY(gmk::device_malloc(&d_priors, n * 225 * 4));
-    GMK_TRY(gmk::device_malloc(&d_root_visits, n * 4)); GMK_TRY(gmk::device_malloc(&d_root_value, n * 4));
-    GMK_TRY(hipMemset(d_visits, 0, n * 225 * 4)); GMK_TRY(hipMemset(d_values, 0, n * 225 * 4)); GMK_TRY(hipMemset(d_priors, 0, n * 225 * 4));
-    GMK_TRY(hipDeviceSynchronize());
+    // One block, the pool's at any size: the host-driven loops read the roots once per ply.  The kernel writes visits, values and priors only where
+    // the root has a child, and a block that comes back from the pool is not cleared: the clear of the three is what makes the other cells read 0.
+    gmk::Staging st("gmk_az_root_stats", gmk::kPoolKeeps);
+    uint32_t *d_visits, *d_root_visits;
+    float *d_values, *d_priors, *d_root_value;
+    st.out(d_visits, h_visits, n * 225, true); st.out(d_values, h_values, n * 225, true); st.out(d_priors, h_priors, n * 225, true);
+    st.out(d_root_visits, h_root_visits, n, true); st.out(d_root_value, h_root_value, n, true);
+    if (const int rc = st.take(); rc != GMK_OK) return rc;
+    GMK_STAGED(st, hipMemset(d_visits, 0, reinterpret_cast<char*>(d_priors + n * 225) - reinterpret_cast<char*>(d_visits)));      // visits | values | priors lie side by side
+    GMK_STAGED(st, hipDeviceSynchronize());
     hipLaunchKernelGGL(az_root_stats_kernel, dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, d_visits, d_values, d_priors, d_root_visits, d_root_value);
-    GMK_TRY(hipGetLastError());
-    GMK_TRY(hipDeviceSynchronize());
-    if (h_visits) GMK_TRY(hipMemcpy(h_visits, d_visits, n * 225 * 4, hipMemcpyDeviceToHost));
-    if (h_values) GMK_TRY(hipMemcpy(h_values, d_values, n * 225 * 4, hipMemcpyDeviceToHost));
-    if (h_priors) GMK_TRY(hipMemcpy(h_priors, d_priors, n * 225 * 4, hipMemcpyDeviceToHost));
-    if (h_root_visits) GMK_TRY(hipMemcpy(h_root_visits, d_root_visits, n * 4, hipMemcpyDeviceToHost));
-    if (h_root_value) GMK_TRY(hipMemcpy(h_root_value, d_root_value, n * 4, hipMemcpyDeviceToHost));
+    GMK_STAGED(st, hipGetLastError());
+    GMK_STAGED(st, hipDeviceSynchronize());
+    if (const int rc = st.download(); rc != GMK_OK) return rc;
     std::vector<AzHeader> hdr(n);
-    GMK_TRY(hipMemcpy(hdr.data(), a->t.hdr, n * sizeof(AzHeader), hipMemcpyDeviceToHost));
-#undef GMK_TRY
+    GMK_STAGED(st, hipMemcpy(hdr.data(), a->t.hdr, n * sizeof(AzHeader), hipMemcpyDeviceToHost));
     for (size_t g = 0; g < n; ++g) {
         if (h_n_nodes) h_n_nodes[g] = static_cast<int32_t>(hdr[g].n_nodes);
         if (h_status) h_status[g] = static_cast<int32_t>(hdr[g].status);
     }
-    cleanup();
     return GMK_OK;
 }
 
 // ---- K7 + K14: the read-out ----
 extern "C" int gmk_az_vcf_stats(gmk_az* a, uint32_t* h_leaves, uint32_t* h_wins, uint32_t* h_cut, uint64_t* h_nodes) {
-    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (!a) { gmk::set_error("gmk_az_vcf_stats: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_vcf_stats: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
     const size_t n = static_cast<size_t>(a->t.n_games);
@@ -2142,7 +2138,7 @@ extern "C" int gmk_az_vcf_stats(gmk_az* a, uint32_t* h_leaves, uint32_t* h_wins,
 }
 
 extern "C" int gmk_az_vcf_verdicts_host(gmk_az* a, int32_t* h_status, int32_t* h_move, int32_t* h_length, uint32_t* h_nodes) {
-    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (!a) { gmk::set_error("gmk_az_vcf_verdicts_host: bad arguments"); return GMK_ERR_ARG; }
     if (a->vcf.max_depth == 0 || !a->vcf.verdict) { gmk::set_error("gmk_az_vcf_verdicts_host: the leaves are not solved (GMK_OPT_AZ_VCF_DEPTH = 0)"); return GMK_ERR_STATE; }
     const size_t rows = static_cast<size_t>(a->n_live) * static_cast<size_t>(a->lv.leaves);
@@ -2160,25 +2156,23 @@ extern "C" int gmk_az_vcf_verdicts_host(gmk_az* a, int32_t* h_status, int32_t* h
 
 // ---- K7 + proofs: the read-outs ----
 extern "C" int gmk_az_root_proofs(gmk_az* a, int8_t* h_root, int8_t* h_children) {
-    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (!a) { gmk::set_error("gmk_az_root_proofs: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_root_proofs: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
     const size_t n = static_cast<size_t>(a->t.n_games);
-    int8_t* d_out = nullptr;
-    GMK_HIP_CHECK(hipDeviceSynchronize());
-    GMK_HIP_CHECK(gmk::device_malloc(&d_out, n * 226));
-    hipLaunchKernelGGL(az_root_proofs_kernel, dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, d_out + n * 225, d_out);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess && h_children) e = hipMemcpy(h_children, d_out, n * 225, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && h_root) e = hipMemcpy(h_root, d_out + n * 225, n, hipMemcpyDeviceToHost);
-    (void)gmk::device_free(d_out);
-    GMK_HIP_CHECK(e);
-    return GMK_OK;
+    gmk::Staging st("gmk_az_root_proofs");                        // one block: the children's rows | the roots; the kernel writes both
+    int8_t *d_children, *d_root;
+    st.out(d_children, h_children, n * 225, true); st.out(d_root, h_root, n, true);
+    GMK_STAGED(st, hipDeviceSynchronize());
+    if (const int rc = st.take(); rc != GMK_OK) return rc;
+    hipLaunchKernelGGL(az_root_proofs_kernel, dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, d_root, d_children);
+    GMK_STAGED(st, hipGetLastError());
+    GMK_STAGED(st, hipDeviceSynchronize());
+    return st.download();
 }
 
 extern "C" int gmk_az_proof_stats(gmk_az* a, uint32_t* h_proved, uint32_t* h_stops) {
-    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (!a) { gmk::set_error("gmk_az_proof_stats: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_proof_stats: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
     const size_t n = static_cast<size_t>(a->t.n_games);
@@ -2194,7 +2188,7 @@ extern "C" int gmk_az_proof_stats(gmk_az* a, uint32_t* h_proved, uint32_t* h_sto
 
 // ---- K7 + K15: the read-outs ----
 extern "C" int gmk_az_defend_stats(gmk_az* a, uint32_t* h_threatened, uint32_t* h_marked, uint32_t* h_searched, uint64_t* h_nodes) {
-    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (!a) { gmk::set_error("gmk_az_defend_stats: bad arguments"); return GMK_ERR_ARG; }
     if (!a->rooted) { gmk::set_error("gmk_az_defend_stats: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
     const size_t n = static_cast<size_t>(a->t.n_games);
@@ -2211,7 +2205,7 @@ extern "C" int gmk_az_defend_stats(gmk_az* a, uint32_t* h_threatened, uint32_t* 
 }
 
 extern "C" int gmk_az_defend_verdicts_host(gmk_az* a, int32_t* h_threat_status, int32_t* h_threat_length, int8_t* h_verdict, uint32_t* h_nodes) {
-    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (!a) { gmk::set_error("gmk_az_defend_verdicts_host: bad arguments"); return GMK_ERR_ARG; }
     if (!az_defend_active(a) || !a->df.threat) { gmk::set_error("gmk_az_defend_verdicts_host: the defence solver is not asked (GMK_OPT_AZ_VCF_DEFEND with GMK_OPT_AZ_VCF_DEPTH > 0 and GMK_OPT_AZ_PROOF)"); return GMK_ERR_STATE; }
     const size_t rows = static_cast<size_t>(a->n_live) * static_cast<size_t>(a->lv.leaves);

@@ -59,4 +59,13 @@ inline hipError_t device_malloc(T** p, size_t bytes) { return device_malloc_byte
         }                                                                                     \
     } while (0)
 
+// The first line of every entry that needs the device: there is no other way to compute what it returns.
+#define GMK_NEED_INIT()                                                                      \
+    do {                                                                                     \
+        if (!gmk::device_state().ready) {                                                    \
+            gmk::set_error("gmk_init has not succeeded (no CPU fallback)");                  \
+            return GMK_ERR_STATE;                                                            \
+        }                                                                                    \
+    } while (0)
+
 }  // namespace gmk

@@ -48,6 +48,7 @@
 #include <vector>
 
 #include "capi_common.h"
+#include "host_staging.h"
 
 namespace {
 
@@ -1105,7 +1106,7 @@ int g_stage_vecs = 0;
 extern "C" int gmk_eval_batch(const uint16_t* d_planes, int n, int32_t* d_scores, int32_t* d_density,
                               uint32_t* d_totals, int32_t* d_status, void* stream) {
     gmk::DeviceState& st = gmk::device_state();
-    if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (n < 0 || (n > 0 && !d_planes)) { gmk::set_error("gmk_eval_batch: bad arguments"); return GMK_ERR_ARG; }
     if (n == 0) return GMK_OK;
     if (!g_jobs_uploaded) {
@@ -1180,31 +1181,22 @@ extern "C" int gmk_eval_launch_info(int n, int* grid, int* block, int* lds_bytes
 
 extern "C" int gmk_eval_batch_host(const uint16_t* h_planes, int n, int32_t* h_scores, int32_t* h_density,
                                    uint32_t* h_totals, int32_t* h_status) {
-    gmk::DeviceState& st = gmk::device_state();
-    if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (n < 0 || (n > 0 && !h_planes)) { gmk::set_error("gmk_eval_batch_host: bad arguments"); return GMK_ERR_ARG; }
     if (n == 0) return GMK_OK;
-    uint16_t* d_planes = nullptr;
-    int32_t *d_scores = nullptr, *d_density = nullptr, *d_status = nullptr;
-    uint32_t* d_totals = nullptr;
+    // one block, planes | scores | density | totals | status, from the driver and back to it: the library's pool does not keep it.  The kernel
+    // writes every output, asked for or not.
     const size_t nb = static_cast<size_t>(n);
-    int rc = GMK_OK;
-    auto cleanup = [&]() { (void)hipFree(d_planes); (void)hipFree(d_scores); (void)hipFree(d_density); (void)hipFree(d_totals); (void)hipFree(d_status); };
-#define GMK_TRY(expr) do { if ((expr) != hipSuccess) { gmk::set_error("%s failed", #expr); cleanup(); return GMK_ERR_HIP; } } while (0)
-    GMK_TRY(hipMalloc(&d_planes, nb * 64));
-    GMK_TRY(hipMalloc(&d_scores, nb * 3600));
-    GMK_TRY(hipMalloc(&d_density, nb * 3600));
-    GMK_TRY(hipMalloc(&d_totals, nb * 44));
-    GMK_TRY(hipMalloc(&d_status, nb * 4));
-    GMK_TRY(hipMemcpy(d_planes, h_planes, nb * 64, hipMemcpyHostToDevice));
-    rc = gmk_eval_batch(d_planes, n, d_scores, d_density, d_totals, d_status, nullptr);
-    if (rc != GMK_OK) { cleanup(); return rc; }
-    GMK_TRY(hipDeviceSynchronize());
-    if (h_scores) GMK_TRY(hipMemcpy(h_scores, d_scores, nb * 3600, hipMemcpyDeviceToHost));
-    if (h_density) GMK_TRY(hipMemcpy(h_density, d_density, nb * 3600, hipMemcpyDeviceToHost));
-    if (h_totals) GMK_TRY(hipMemcpy(h_totals, d_totals, nb * 44, hipMemcpyDeviceToHost));
-    if (h_status) GMK_TRY(hipMemcpy(h_status, d_status, nb * 4, hipMemcpyDeviceToHost));
-#undef GMK_TRY
-    cleanup();
-    return GMK_OK;
+    gmk::Staging st("gmk_eval_batch_host", 0, false);
+    uint16_t* d_planes;
+    int32_t *d_scores, *d_density, *d_status;
+    uint32_t* d_totals;
+    st.in(d_planes, h_planes, nb * 32);
+    st.out(d_scores, h_scores, nb * 900, true); st.out(d_density, h_density, nb * 900, true); st.out(d_totals, h_totals, nb * 11, true);
+    st.out(d_status, h_status, nb, true);
+    int rc = st.take();
+    if (rc == GMK_OK) rc = gmk_eval_batch(d_planes, n, d_scores, d_density, d_totals, d_status, nullptr);
+    if (rc != GMK_OK) return rc;
+    GMK_STAGED(st, hipDeviceSynchronize());
+    return st.download();
 }

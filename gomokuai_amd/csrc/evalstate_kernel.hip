@@ -84,8 +84,7 @@ extern "C" int gmk_evalstate_reset(gmk_evalstate* e) {
 }
 
 extern "C" int gmk_evalstate_create(int n_games, gmk_evalstate** out) {
-    gmk::DeviceState& st = gmk::device_state();
-    if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (!out || n_games <= 0) { gmk::set_error("gmk_evalstate_create: bad arguments"); return GMK_ERR_ARG; }
     gmk_evalstate* e = new gmk_evalstate;
     e->n_games = n_games;

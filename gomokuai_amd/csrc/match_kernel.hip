@@ -68,7 +68,7 @@ void match_referee_kernel(int n, int rows, const int16_t* __restrict__ cells, co
 
 extern "C" int gmk_match_referee(int n, int rows, const int16_t* d_cells, const uint16_t* d_visit_rows, const int32_t* d_row_of, uint8_t* d_moves, int32_t* d_lens,
                                  int8_t* d_winner, uint16_t* d_visits, int32_t* d_verdict, int32_t* d_status, int32_t* d_unfinished, void* stream) {
-    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (n <= 0 || rows <= 0 || !d_cells || !d_moves || !d_lens || !d_winner || !d_verdict || !d_status || !d_unfinished) { gmk::set_error("gmk_match_referee: bad arguments"); return GMK_ERR_ARG; }
     hipStream_t s = static_cast<hipStream_t>(stream);
     GMK_HIP_CHECK(hipMemsetAsync(d_unfinished, 0, 4, s));

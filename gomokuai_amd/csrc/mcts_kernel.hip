@@ -28,6 +28,7 @@
 
 #include "../../include/gomoku_sample.h"
 #include "capi_common.h"
+#include "host_staging.h"
 #include "board_device.h"
 #include "philox.h"
 #include "rollout_device.h"
@@ -881,7 +882,7 @@ __global__ void mcts_root_stats_kernel(const GameHeader* __restrict__ headers, c
 
 extern "C" int gmk_mcts_create(int n_games, int node_capacity, double c_puct, int c_rollouts, uint64_t seed, gmk_mcts** out) {
     gmk::DeviceState& st = gmk::device_state();
-    if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (!out || n_games <= 0 || node_capacity < 2 || node_capacity >= (1 << 24) || c_rollouts < 1 || c_rollouts > 64) {
         gmk::set_error("gmk_mcts_create: bad arguments (2 <= node_capacity < 2^24: a node's first-child index shares a word with its cell)");
         return GMK_ERR_ARG;
@@ -1327,28 +1328,18 @@ extern "C" int gmk_mcts_root_stats(gmk_mcts* m, uint32_t* h_visits, float* h_roo
     if (m && !m->rooted) { gmk::set_error("gmk_mcts_root_stats: gmk_mcts_set_roots has not been called"); return GMK_ERR_STATE; }
     if (!m) return GMK_ERR_ARG;
     const size_t n = static_cast<size_t>(m->n_games);
-    uint32_t *d_visits = nullptr, *d_rv = nullptr, *d_nodes = nullptr;
-    float* d_q = nullptr;
-    int32_t* d_status = nullptr;
-    auto cleanup = [&]() { (void)gmk::device_free(d_visits); (void)gmk::device_free(d_rv); (void)gmk::device_free(d_nodes); (void)gmk::device_free(d_q); (void)gmk::device_free(d_status); };
-#define GMK_TRY(expr) do { if ((expr) != hipSuccess) { gmk::set_error("%s failed", #expr); cleanup(); return GMK_ERR_HIP; } } while (0)
-    GMK_TRY(gmk::device_malloc(&d_visits, n * 225 * 4));
-    GMK_TRY(gmk::device_malloc(&d_rv, n * 4));
-    GMK_TRY(gmk::device_malloc(&d_nodes, n * 4));
-    GMK_TRY(gmk::device_malloc(&d_q, n * 4));
-    GMK_TRY(gmk::device_malloc(&d_status, n * 4));
+    gmk::Staging st("gmk_mcts_root_stats");                       // one block; the kernel clears its rows of visits and writes every output
+    uint32_t *d_visits, *d_rv, *d_nodes;
+    float* d_q;
+    int32_t* d_status;
+    st.out(d_visits, h_visits, n * 225, true); st.out(d_q, h_root_value, n, true); st.out(d_rv, h_root_visits, n, true); st.out(d_nodes, h_nodes, n, true);
+    st.out(d_status, h_status, n, true);
+    if (const int rc = st.take(); rc != GMK_OK) return rc;
     hipLaunchKernelGGL(mcts_root_stats_kernel, dim3(m->n_games), dim3(64), 0, m->last_stream, m->d_headers, m->d_stats, m->d_link,
                        static_cast<size_t>(m->node_capacity), m->arena_stride(), m->n_games, d_visits, d_q, d_rv, d_nodes, d_status);
-    GMK_TRY(hipGetLastError());
-    GMK_TRY(hipStreamSynchronize(m->last_stream));
-    if (h_visits) GMK_TRY(hipMemcpy(h_visits, d_visits, n * 225 * 4, hipMemcpyDeviceToHost));
-    if (h_root_value) GMK_TRY(hipMemcpy(h_root_value, d_q, n * 4, hipMemcpyDeviceToHost));
-    if (h_root_visits) GMK_TRY(hipMemcpy(h_root_visits, d_rv, n * 4, hipMemcpyDeviceToHost));
-    if (h_nodes) GMK_TRY(hipMemcpy(h_nodes, d_nodes, n * 4, hipMemcpyDeviceToHost));
-    if (h_status) GMK_TRY(hipMemcpy(h_status, d_status, n * 4, hipMemcpyDeviceToHost));
-#undef GMK_TRY
-    cleanup();
-    return GMK_OK;
+    GMK_STAGED(st, hipGetLastError());
+    GMK_STAGED(st, hipStreamSynchronize(m->last_stream));
+    return st.download();
 }
 
 extern "C" int gmk_mcts_alg_bytes(gmk_mcts* m, uint64_t* bytes) {

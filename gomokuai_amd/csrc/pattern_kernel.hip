@@ -16,6 +16,7 @@
 
 #include "evalstate_device.h"
 #include "heuristic_device.h"
+#include "host_staging.h"
 
 namespace {
 
@@ -236,14 +237,6 @@ int launch(PatternParams prm, hipStream_t stream) {
 
 using gmk::misaligned;
 
-#define GMK_NEED_INIT()                                                                      \
-    do {                                                                                     \
-        if (!gmk::device_state().ready) {                                                    \
-            gmk::set_error("gmk_init has not succeeded (no CPU fallback)");                  \
-            return GMK_ERR_STATE;                                                            \
-        }                                                                                    \
-    } while (0)
-
 }  // namespace
 
 extern "C" int gmk_pattern_policy(const uint8_t* d_moves, int stride, const int32_t* d_lens, int n, int filter,
@@ -268,29 +261,20 @@ extern "C" int gmk_pattern_policy_host(const uint8_t* h_moves, int stride, const
     GMK_NEED_INIT();
     if (n < 0 || (n > 0 && (!h_moves || !h_lens || stride <= 0))) { gmk::set_error("gmk_pattern_policy_host: bad arguments"); return GMK_ERR_ARG; }
     if (n == 0) return GMK_OK;
-    // one device block: moves | lens | probs | value | best | status (each part 16-byte aligned).  It is asked for at the size from which the
-    // library's pool keeps blocks (16 MB) even when the batch is small, so that the next call gets it back without a trip to the driver.
-    const auto up16 = [](size_t b) { return (b + 15) & ~size_t(15); };
+    // one device block: moves | lens | probs | value | best | status.  It is asked for at the size from which the library's pool keeps blocks
+    // (16 MB) even when the batch is small, so that the next call gets it back without a trip to the driver.
     const size_t un = static_cast<size_t>(n);
-    const size_t o_lens = up16(un * static_cast<size_t>(stride)), o_probs = o_lens + up16(un * 4), o_value = o_probs + up16(un * kCells * 4),
-                 o_best = o_value + up16(un * 4), o_status = o_best + up16(un * 4), total = std::max(o_status + up16(un * 4), size_t(16) << 20);
-    char* d = nullptr;
-    GMK_HIP_CHECK(gmk::device_malloc(&d, total));
-    int rc = GMK_OK;
-    if (hipMemcpy(d, h_moves, un * static_cast<size_t>(stride), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d + o_lens, h_lens, un * 4, hipMemcpyHostToDevice) != hipSuccess) rc = GMK_ERR_HIP;
-    if (rc == GMK_OK)
-        rc = gmk_pattern_policy(reinterpret_cast<const uint8_t*>(d), stride, reinterpret_cast<const int32_t*>(d + o_lens), n, filter,
-                                h_probs ? reinterpret_cast<float*>(d + o_probs) : nullptr, h_value ? reinterpret_cast<float*>(d + o_value) : nullptr,
-                                h_best ? reinterpret_cast<int32_t*>(d + o_best) : nullptr, h_status ? reinterpret_cast<int32_t*>(d + o_status) : nullptr, nullptr);
-    if (rc == GMK_OK && hipDeviceSynchronize() != hipSuccess) rc = GMK_ERR_HIP;
-    if (rc == GMK_OK && ((h_probs && hipMemcpy(h_probs, d + o_probs, un * kCells * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-                         (h_value && hipMemcpy(h_value, d + o_value, un * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-                         (h_best && hipMemcpy(h_best, d + o_best, un * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-                         (h_status && hipMemcpy(h_status, d + o_status, un * 4, hipMemcpyDeviceToHost) != hipSuccess))) rc = GMK_ERR_HIP;
-    if (rc == GMK_ERR_HIP) gmk::set_error("gmk_pattern_policy_host: a HIP call failed: %s", hipGetErrorString(hipGetLastError()));
-    (void)gmk::device_free(d);
-    return rc;
+    gmk::Staging st("gmk_pattern_policy_host", gmk::kPoolKeeps);
+    uint8_t* d_moves;
+    int32_t *d_lens, *d_best, *d_status;
+    float *d_probs, *d_value;
+    st.in(d_moves, h_moves, un * static_cast<size_t>(stride)); st.in(d_lens, h_lens, un);
+    st.out(d_probs, h_probs, un * kCells); st.out(d_value, h_value, un); st.out(d_best, h_best, un); st.out(d_status, h_status, un);
+    int rc = st.take();
+    if (rc == GMK_OK) rc = gmk_pattern_policy(d_moves, stride, d_lens, n, filter, d_probs, d_value, d_best, d_status, nullptr);
+    if (rc != GMK_OK) return rc;                                  // the device form's code and text, untouched
+    GMK_STAGED(st, hipDeviceSynchronize());
+    return st.download();
 }
 
 extern "C" int gmk_pattern_play(uint8_t* d_moves, int32_t* d_lens, int n, int filter, int max_moves,

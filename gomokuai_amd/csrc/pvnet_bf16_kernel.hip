@@ -286,8 +286,7 @@ extern "C" int gmk_pvnet_get_precision(gmk_pvnet* net, int* precision) {
 
 extern "C" int gmk_pvnet_set_precision(gmk_pvnet* net, int precision) {
     if (!net || (precision != GMK_PVNET_F32 && precision != GMK_PVNET_BF16)) { gmk::set_error("gmk_pvnet_set_precision: bad arguments"); return GMK_ERR_ARG; }
-    gmk::DeviceState& st = gmk::device_state();
-    if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (precision == GMK_PVNET_BF16) {
         // the float32 buffers hold the weights exactly (pure gathers): read them back, pack on the host, copy -- all blocking, like gmk_pvnet_set_dense
         const size_t n1 = (1 * 7 + 2) * 256, n2 = (2 * 36 + 5) * 256, n3 = (4 * 72 + 5) * 256, nh = gmk::pvpack::kHeadFloats;   // pack_layer's sizes

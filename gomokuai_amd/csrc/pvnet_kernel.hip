@@ -581,8 +581,7 @@ extern "C" int gmk_pvnet_destroy(gmk_pvnet* net) {
 
 extern "C" int gmk_pvnet_create(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
                                 const float* wp, const float* bp, const float* wv, const float* bv, gmk_pvnet** out) {
-    gmk::DeviceState& st = gmk::device_state();
-    if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !wp || !bp || !wv || !bv || !out) { gmk::set_error("gmk_pvnet_create: bad arguments"); return GMK_ERR_ARG; }
     std::vector<float> p1, p2, p3, ph, bias;
     pack_layer(w1, 6, 32, p1);
@@ -642,8 +641,7 @@ int launch_trunk(gmk_pvnet* net, const float* d_states, int n, float* d_pflat, f
 }  // namespace
 
 extern "C" int gmk_pvnet_forward(gmk_pvnet* net, const float* d_states, int n, float* d_pflat, float* d_vflat, void* stream) {
-    gmk::DeviceState& st = gmk::device_state();
-    if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (!net || n < 0 || (n > 0 && (!d_states || !d_pflat || !d_vflat))) { gmk::set_error("gmk_pvnet_forward: bad arguments"); return GMK_ERR_ARG; }
     if (n == 0) return GMK_OK;
     return launch_trunk(net, d_states, n, d_pflat, d_vflat, static_cast<hipStream_t>(stream));
@@ -651,8 +649,7 @@ extern "C" int gmk_pvnet_forward(gmk_pvnet* net, const float* d_states, int n, f
 
 extern "C" int gmk_pvnet_set_dense(gmk_pvnet* net, const float* w_policy, const float* b_policy, const float* w_hidden, const float* b_hidden,
                                    const float* w_out, float b_out) {
-    gmk::DeviceState& st = gmk::device_state();
-    if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (!net || !w_policy || !b_policy || !w_hidden || !b_hidden || !w_out) { gmk::set_error("gmk_pvnet_set_dense: bad arguments"); return GMK_ERR_ARG; }
     std::vector<float> wp, dense;                               // the layouts: pvnet_pack.h, pack_dense
     gmk::pvpack::pack_dense(w_policy, b_policy, w_hidden, b_hidden, w_out, wp, dense);
@@ -668,8 +665,7 @@ extern "C" int gmk_pvnet_set_dense(gmk_pvnet* net, const float* w_policy, const 
 }
 
 extern "C" int gmk_pvnet_evaluate(gmk_pvnet* net, const float* d_states, int n, float* d_value, float* d_probs, void* stream) {
-    gmk::DeviceState& st = gmk::device_state();
-    if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (!net || n < 0 || (n > 0 && (!d_states || !d_value || !d_probs))) { gmk::set_error("gmk_pvnet_evaluate: bad arguments"); return GMK_ERR_ARG; }
     if (!net->has_dense) { gmk::set_error("gmk_pvnet_evaluate: the dense layers have not been set (gmk_pvnet_set_dense)"); return GMK_ERR_STATE; }
     if (n == 0) return GMK_OK;

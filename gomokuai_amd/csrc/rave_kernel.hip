@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "capi_common.h"
+#include "host_staging.h"
 #include "rollout_device.h"
 #include "trad_tree.h"
 
@@ -331,8 +332,7 @@ void rave_root_amaf_kernel(TradArena a, const TradHeader* hdrs, int cap, uint32_
 }  // namespace
 
 extern "C" int gmk_trad_run_poolrave(gmk_trad* t, int playouts, double c_puct, uint64_t seed, uint32_t first_game_id, void* stream) {
-    gmk::DeviceState& st = gmk::device_state();
-    if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (!t || playouts < 0) { gmk::set_error("gmk_trad_run_poolrave: bad arguments"); return GMK_ERR_ARG; }
     if (!t->positioned) { gmk::set_error("gmk_trad_run_poolrave: gmk_trad_set_positions has not been called"); return GMK_ERR_STATE; }
     if (t->policy == 1 || t->policy == 3) { gmk::set_error("gmk_trad_run_poolrave: this handle searches with gmk_trad_run%s", t->policy == 3 ? "_rave" : " (its nodes carry no AMAF statistics)"); return GMK_ERR_STATE; }
@@ -369,19 +369,17 @@ extern "C" int gmk_trad_root_amaf(gmk_trad* t, uint32_t* h_amaf_visits, float* h
     if (!t || !h_amaf_visits || !h_amaf_values) { gmk::set_error("gmk_trad_root_amaf: bad arguments"); return GMK_ERR_ARG; }
     if (!t->a.amaf) { gmk::set_error("gmk_trad_root_amaf: neither gmk_trad_run_poolrave nor gmk_trad_run_rave has been called on this handle"); return GMK_ERR_STATE; }
     const size_t n = static_cast<size_t>(t->n_games);
-    uint32_t* d_visits = nullptr;
-    float* d_values = nullptr;
-    auto cleanup = [&]() { (void)gmk::device_free(d_visits); (void)gmk::device_free(d_values); };
-#define GMK_TRY(expr) do { if ((expr) != hipSuccess) { gmk::set_error("%s failed", #expr); cleanup(); return GMK_ERR_HIP; } } while (0)
-    GMK_TRY(gmk::device_malloc(&d_visits, n * 225 * 4)); GMK_TRY(gmk::device_malloc(&d_values, n * 225 * 4));
-    GMK_TRY(hipMemset(d_visits, 0, n * 225 * 4)); GMK_TRY(hipMemset(d_values, 0, n * 225 * 4));
-    GMK_TRY(hipDeviceSynchronize());                             // a search may still be running on a stream of the caller's
+    // One block, the pool's at any size (it is read with gmk_trad_root_stats, once per ply).  The kernel writes only the cells that have a child,
+    // and a block that comes back from the pool is not cleared: the clear of the two is what makes the other cells read 0.
+    gmk::Staging st("gmk_trad_root_amaf", gmk::kPoolKeeps);
+    uint32_t* d_visits;
+    float* d_values;
+    st.out(d_visits, h_amaf_visits, n * 225); st.out(d_values, h_amaf_values, n * 225);
+    if (const int rc = st.take(); rc != GMK_OK) return rc;
+    GMK_STAGED(st, hipMemset(d_visits, 0, reinterpret_cast<char*>(d_values + n * 225) - reinterpret_cast<char*>(d_visits)));      // visits | values lie side by side
+    GMK_STAGED(st, hipDeviceSynchronize());                      // a search may still be running on a stream of the caller's
     hipLaunchKernelGGL(rave_root_amaf_kernel, dim3(t->n_games), dim3(64), 0, nullptr, t->a, t->d_hdr, t->cap, d_visits, d_values);
-    GMK_TRY(hipGetLastError());
-    GMK_TRY(hipDeviceSynchronize());
-    GMK_TRY(hipMemcpy(h_amaf_visits, d_visits, n * 225 * 4, hipMemcpyDeviceToHost));
-    GMK_TRY(hipMemcpy(h_amaf_values, d_values, n * 225 * 4, hipMemcpyDeviceToHost));
-#undef GMK_TRY
-    cleanup();
-    return GMK_OK;
+    GMK_STAGED(st, hipGetLastError());
+    GMK_STAGED(st, hipDeviceSynchronize());
+    return st.download();
 }

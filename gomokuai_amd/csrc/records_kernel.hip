@@ -101,8 +101,7 @@ void samples_from_packed_kernel(const uint8_t* __restrict__ buf, int n, const in
 extern "C" int gmk_samples_from_records(const uint8_t* d_moves, const int32_t* d_lens, const uint16_t* d_visits, const int8_t* d_winner,
                                         const int32_t* d_sample_game, const int32_t* d_sample_move, int n_samples, int augment,
                                         uint8_t* d_states, float* d_values, float* d_pi, void* stream) {
-    gmk::DeviceState& st = gmk::device_state();
-    if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (n_samples < 0 || (n_samples > 0 && (!d_moves || !d_lens || !d_visits || !d_winner || !d_sample_game || !d_sample_move || !d_states || !d_values || !d_pi))) {
         gmk::set_error("gmk_samples_from_records: bad arguments");
         return GMK_ERR_ARG;
@@ -117,8 +116,7 @@ extern "C" int gmk_samples_from_records(const uint8_t* d_moves, const int32_t* d
 extern "C" int gmk_samples_from_packed(const uint8_t* d_buf, int n, const int64_t* d_offsets, const int32_t* d_sample_game,
                                        const int32_t* d_sample_move, int n_samples, int augment, uint8_t* d_states, float* d_values, float* d_pi,
                                        void* stream) {
-    gmk::DeviceState& st = gmk::device_state();
-    if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (n < 0 || n_samples < 0 || (n_samples > 0 && (n == 0 || !d_buf || !d_offsets || !d_sample_game || !d_sample_move || !d_states || !d_values || !d_pi))) {
         gmk::set_error("gmk_samples_from_packed: bad arguments");
         return GMK_ERR_ARG;

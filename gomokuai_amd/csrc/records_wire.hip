@@ -245,14 +245,6 @@ int scan(const int32_t* d_lens, int n, int64_t* d_offsets, hipStream_t stream) {
     return GMK_OK;
 }
 
-#define GMK_NEED_INIT()                                                                      \
-    do {                                                                                     \
-        if (!gmk::device_state().ready) {                                                    \
-            gmk::set_error("gmk_init has not succeeded (no CPU fallback)");                  \
-            return GMK_ERR_STATE;                                                            \
-        }                                                                                    \
-    } while (0)
-
 }  // namespace
 
 extern "C" int gmk_records_scan(const int32_t* d_lens, int n, int64_t* d_offsets, void* stream) {

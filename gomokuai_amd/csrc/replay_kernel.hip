@@ -421,14 +421,6 @@ using gmk::misaligned;
 
 constexpr int64_t kMaxCapacityPlies = int64_t(1) << 40;
 
-#define GMK_NEED_INIT()                                                                      \
-    do {                                                                                     \
-        if (!gmk::device_state().ready) {                                                    \
-            gmk::set_error("gmk_init has not succeeded (no CPU fallback)");                  \
-            return GMK_ERR_STATE;                                                            \
-        }                                                                                    \
-    } while (0)
-
 }  // namespace
 
 struct gmk_replay {

@@ -26,6 +26,7 @@
 #include "board_device.h"
 #include "evalstate_device.h"
 #include "heuristic_device.h"
+#include "host_staging.h"
 #include "philox.h"
 #include "root_noise.h"
 #include "noise_device.h"
@@ -882,8 +883,7 @@ extern "C" int gmk_trad_reset_evaluators(gmk_trad* t) {
 }
 
 extern "C" int gmk_trad_create(int n_games, int node_capacity, gmk_trad** out) {
-    gmk::DeviceState& st = gmk::device_state();
-    if (!st.ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (!out || n_games <= 0 || node_capacity < 256 || node_capacity >= (1 << 24)) { gmk::set_error("gmk_trad_create: bad arguments (256 <= node_capacity < 2^24)"); return GMK_ERR_ARG; }
     gmk_trad* t = new gmk_trad;
     t->n_games = n_games;
@@ -1195,34 +1195,29 @@ extern "C" int gmk_trad_root_stats(gmk_trad* t, uint32_t* h_visits, float* h_val
     if (!t) { gmk::set_error("gmk_trad_root_stats: bad arguments"); return GMK_ERR_ARG; }
     if (!t->positioned) { gmk::set_error("gmk_trad_root_stats: gmk_trad_set_positions has not been called"); return GMK_ERR_STATE; }
     const size_t n = static_cast<size_t>(t->n_games);
-    uint32_t *d_visits = nullptr, *d_root_visits = nullptr;
-    float *d_values = nullptr, *d_priors = nullptr, *d_root_value = nullptr;
-    int32_t* d_best = nullptr;
-    auto cleanup = [&]() { (void)gmk::device_free(d_visits); (void)gmk::device_free(d_values); (void)gmk::device_free(d_priors); (void)gmk::device_free(d_best); (void)gmk::device_free(d_root_visits); (void)gmk::device_free(d_root_value); };
-#define GMK_TRY(expr) do { if ((expr) != hipSuccess) { gmk::set_error("%s failed", #expr); cleanup(); return GMK_ERR_HIP; } } while (0)
-    GMK_TRY(gmk::device_malloc(&d_visits, n * 225 * 4)); GMK_TRY(gmk::device_malloc(&d_values, n * 225 * 4)); GMK_TRY(gmk::device_malloc(&d_priors, n * 225 * 4));
-    GMK_TRY(gmk::device_malloc(&d_best, n * 4)); GMK_TRY(gmk::device_malloc(&d_root_visits, n * 4)); GMK_TRY(gmk::device_malloc(&d_root_value, n * 4));
-    GMK_TRY(hipMemset(d_visits, 0, n * 225 * 4)); GMK_TRY(hipMemset(d_values, 0, n * 225 * 4)); GMK_TRY(hipMemset(d_priors, 0, n * 225 * 4));
-    GMK_TRY(hipDeviceSynchronize());                             // a search may still be running on a stream of the caller's
+    // One block, the pool's at any size: the host-driven loops read the roots once per ply.  The kernel writes visits, values and priors only where
+    // the root has a child, and a block that comes back from the pool is not cleared: the clear of the three is what makes the other cells read 0.
+    gmk::Staging st("gmk_trad_root_stats", gmk::kPoolKeeps);
+    uint32_t *d_visits, *d_root_visits;
+    float *d_values, *d_priors, *d_root_value;
+    int32_t* d_best;
+    st.out(d_visits, h_visits, n * 225, true); st.out(d_values, h_values, n * 225, true); st.out(d_priors, h_priors, n * 225, true);
+    st.out(d_best, h_best, n, true); st.out(d_root_visits, h_root_visits, n, true); st.out(d_root_value, h_root_value, n, true);
+    if (const int rc = st.take(); rc != GMK_OK) return rc;
+    GMK_STAGED(st, hipMemset(d_visits, 0, reinterpret_cast<char*>(d_priors + n * 225) - reinterpret_cast<char*>(d_visits)));      // visits | values | priors lie side by side
+    GMK_STAGED(st, hipDeviceSynchronize());                      // a search may still be running on a stream of the caller's
     hipLaunchKernelGGL(trad_root_stats_kernel, dim3(t->n_games), dim3(64), 0, nullptr, t->a, t->d_hdr, t->cap,
                        d_visits, d_values, d_priors, d_best, d_root_visits, d_root_value);
-    GMK_TRY(hipGetLastError());
-    GMK_TRY(hipDeviceSynchronize());
-    if (h_visits) GMK_TRY(hipMemcpy(h_visits, d_visits, n * 225 * 4, hipMemcpyDeviceToHost));
-    if (h_values) GMK_TRY(hipMemcpy(h_values, d_values, n * 225 * 4, hipMemcpyDeviceToHost));
-    if (h_priors) GMK_TRY(hipMemcpy(h_priors, d_priors, n * 225 * 4, hipMemcpyDeviceToHost));
-    if (h_best) GMK_TRY(hipMemcpy(h_best, d_best, n * 4, hipMemcpyDeviceToHost));
-    if (h_root_visits) GMK_TRY(hipMemcpy(h_root_visits, d_root_visits, n * 4, hipMemcpyDeviceToHost));
-    if (h_root_value) GMK_TRY(hipMemcpy(h_root_value, d_root_value, n * 4, hipMemcpyDeviceToHost));
+    GMK_STAGED(st, hipGetLastError());
+    GMK_STAGED(st, hipDeviceSynchronize());
+    if (const int rc = st.download(); rc != GMK_OK) return rc;
     std::vector<TradHeader> hdr(n);
-    GMK_TRY(hipMemcpy(hdr.data(), t->d_hdr, n * sizeof(TradHeader), hipMemcpyDeviceToHost));
-#undef GMK_TRY
+    GMK_STAGED(st, hipMemcpy(hdr.data(), t->d_hdr, n * sizeof(TradHeader), hipMemcpyDeviceToHost));
     for (size_t g = 0; g < n; ++g) {
         if (h_n_nodes) h_n_nodes[g] = static_cast<int32_t>(hdr[g].n_nodes);
         if (h_status) h_status[g] = static_cast<int32_t>(hdr[g].status);
         if (h_evaluator_updates) h_evaluator_updates[g] = hdr[g].evaluator_updates;
     }
-    cleanup();
     return GMK_OK;
 }
 
@@ -1308,22 +1303,16 @@ static int trad_selfplay_run(const char* who, gmk_trad* t, int policy, int n_tot
         for (size_t g = nt; g < ns; ++g) hdr[g].status |= kStatusIdleSlot;
         GMK_HIP_CHECK(hipMemcpy(t->d_hdr, hdr.data(), ns * sizeof(TradHeader), hipMemcpyHostToDevice));
     }
-    int32_t* d_state = nullptr;
+    // the slots' state | the openings' lengths | the openings, in one block that goes when this returns, whichever way
+    gmk::Staging stage(who);
+    int32_t *d_state, *d_open_lens;
     uint8_t* d_open_moves = nullptr;
-    int32_t* d_open_lens = nullptr;
-    auto cleanup = [&]() { (void)gmk::device_free(d_state); (void)gmk::device_free(d_open_moves); (void)gmk::device_free(d_open_lens); };
-#define GMK_TRY(expr) do { if ((expr) != hipSuccess) { gmk::set_error("%s: %s failed", who, #expr); cleanup(); return GMK_ERR_HIP; } } while (0)
-    GMK_TRY(gmk::device_malloc(&d_state, state.size() * 4));
-    GMK_TRY(hipMemcpy(d_state, state.data(), state.size() * 4, hipMemcpyHostToDevice));
-    GMK_TRY(gmk::device_malloc(&d_open_lens, nt * 4));
-    GMK_TRY(hipMemcpy(d_open_lens, open_lens.data(), nt * 4, hipMemcpyHostToDevice));
-    if (h_open_moves) {
-        GMK_TRY(gmk::device_malloc(&d_open_moves, nt * static_cast<size_t>(open_stride)));
-        GMK_TRY(hipMemcpy(d_open_moves, h_open_moves, nt * static_cast<size_t>(open_stride), hipMemcpyHostToDevice));
-    }
-    GMK_TRY(hipMemcpy(d_moves, first_moves.data(), nt * 225, hipMemcpyHostToDevice));
-    GMK_TRY(hipMemcpy(d_lens, open_lens.data(), nt * 4, hipMemcpyHostToDevice));
-    GMK_TRY(hipMemset(d_winner, 0, nt));
+    stage.in(d_state, state.data(), state.size()); stage.in(d_open_lens, open_lens.data(), nt);
+    if (h_open_moves) stage.in(d_open_moves, h_open_moves, nt * static_cast<size_t>(open_stride));
+    if (const int rc_take = stage.take(); rc_take != GMK_OK) return rc_take;
+    GMK_STAGED(stage, hipMemcpy(d_moves, first_moves.data(), nt * 225, hipMemcpyHostToDevice));
+    GMK_STAGED(stage, hipMemcpy(d_lens, open_lens.data(), nt * 4, hipMemcpyHostToDevice));
+    GMK_STAGED(stage, hipMemset(d_winner, 0, nt));
     TradSelfPlay sp;
     sp.slot_game = d_state; sp.next_game = d_state + ns; sp.unfinished = d_state + ns + 1; sp.overflow = d_state + ns + 2;
     sp.n_total = n_total; sp.open_moves = d_open_moves; sp.open_lens = d_open_lens; sp.open_stride = open_stride;
@@ -1337,14 +1326,14 @@ static int trad_selfplay_run(const char* who, gmk_trad* t, int policy, int n_tot
         // ONE launch: every wavefront plays game after game at its own pace (trad_playouts_kernel, prm.selfplay)
         gmk::DeviceState& st = gmk::device_state();
         const bool rave = policy == 2;
-        if (t->policy == 2 || t->policy == (rave ? 1 : 3)) { gmk::set_error("%s: this handle searches with another policy", who); cleanup(); return GMK_ERR_STATE; }
+        if (t->policy == 2 || t->policy == (rave ? 1 : 3)) { gmk::set_error("%s: this handle searches with another policy", who); return GMK_ERR_STATE; }
         t->policy = rave ? 3 : 1;
         const size_t lds = static_cast<size_t>(kGamesPerBlock * kPerGame + st.n_states * 4 + st.n_records * 4 + gmk::kPrefixWords) * 4;
         bool& attr_set = sampled ? (rave ? t->attr_set_sampled_rave : t->attr_set_sampled) : (rave ? t->attr_set_selfplay_rave : t->attr_set_selfplay);
         const void* kernel = sampled ? (rave ? reinterpret_cast<const void*>(trad_playouts_kernel<true, true, TradSample>) : reinterpret_cast<const void*>(trad_playouts_kernel<true, false, TradSample>))
                                      : (rave ? reinterpret_cast<const void*>(trad_playouts_kernel<true, true>) : reinterpret_cast<const void*>(trad_playouts_kernel<true, false>));
         if (!attr_set) {
-            GMK_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            GMK_STAGED(stage, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             attr_set = true;
         }
         TradParams prm = trad_params(t, st, playouts, c_puct);
@@ -1354,8 +1343,8 @@ static int trad_selfplay_run(const char* who, gmk_trad* t, int policy, int n_tot
         else if (sampled) hipLaunchKernelGGL((trad_playouts_kernel<true, false, TradSample>), grid, dim3(kThreads), lds, s, prm, sm);
         else if (rave) hipLaunchKernelGGL((trad_playouts_kernel<true, true>), grid, dim3(kThreads), lds, s, prm);
         else hipLaunchKernelGGL((trad_playouts_kernel<true, false>), grid, dim3(kThreads), lds, s, prm);
-        GMK_TRY(hipGetLastError());
-        GMK_TRY(hipStreamSynchronize(s));
+        GMK_STAGED(stage, hipGetLastError());
+        GMK_STAGED(stage, hipStreamSynchronize(s));
         steps = 1;
     }
     std::vector<int32_t> slot_game(ns);
@@ -1364,9 +1353,9 @@ static int trad_selfplay_run(const char* who, gmk_trad* t, int policy, int n_tot
         if (noise_alpha > 0.0f && t->noise_sampler == GMK_NOISE_SAMPLER_COUNTER) {     // ... drawn on the device, keyed by the game a slot plays (d_game_ids: the refill kernel keeps it)
             hipLaunchKernelGGL(trad_root_noise_kernel, dim3(n_slots), dim3(64), 0, s, t->a, t->d_hdr, t->cap, t->d_lens, t->d_game_ids, first_game_id,
                                noise_alpha, noise_epsilon, static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32));
-            GMK_TRY(hipGetLastError());
+            GMK_STAGED(stage, hipGetLastError());
         } else if (noise_alpha > 0.0f) {                        // Default::AddNoise at the start of every search (MCTS.cpp:182), keyed by the GAME a slot plays
-            GMK_TRY(hipMemcpy(slot_game.data(), d_state, ns * 4, hipMemcpyDeviceToHost));
+            GMK_STAGED(stage, hipMemcpy(slot_game.data(), d_state, ns * 4, hipMemcpyDeviceToHost));
             for (size_t g = 0; g < ns; ++g) t->game_ids[g] = slot_game[g] >= 0 ? static_cast<uint32_t>(slot_game[g]) : 0u;
             rc = gmk_trad_add_root_noise(t, noise_alpha, noise_epsilon, seed, first_game_id, s);
             if (rc != GMK_OK) break;
@@ -1375,23 +1364,21 @@ static int trad_selfplay_run(const char* who, gmk_trad* t, int policy, int n_tot
            : policy == 2 ? gmk_trad_run_rave(t, playouts, c_puct, s) : gmk_trad_run(t, playouts, c_puct, s);
         if (rc != GMK_OK) break;
         if (reuse_subtree && (rc = trad_second_arena(t, who)) != GMK_OK) break;     // the arenas flip at every step (as gmk_trad_step)
-        GMK_TRY(hipMemsetAsync(sp.unfinished, 0, 4, s));
+        GMK_STAGED(stage, hipMemsetAsync(sp.unfinished, 0, 4, s));
         if (sampled) hipLaunchKernelGGL(trad_advance_kernel<TradSample>, dim3(n_slots), dim3(64), 0, s, t->a, t->b, t->d_hdr, t->cap, n_slots, t->d_moves, t->d_lens, sp, reuse_subtree ? 1 : 0, sm);
         else hipLaunchKernelGGL(trad_advance_kernel<>, dim3(n_slots), dim3(64), 0, s, t->a, t->b, t->d_hdr, t->cap, n_slots, t->d_moves, t->d_lens, sp, reuse_subtree ? 1 : 0);
         hipLaunchKernelGGL(trad_refill_kernel, dim3(1), dim3(64), 0, s, t->d_hdr, n_slots, t->d_moves, t->d_lens, sp);
-        GMK_TRY(hipGetLastError());
+        GMK_STAGED(stage, hipGetLastError());
         ++steps;
         int32_t unfinished = 0;
-        GMK_TRY(hipMemcpyAsync(&unfinished, sp.unfinished, 4, hipMemcpyDeviceToHost, s));
-        GMK_TRY(hipStreamSynchronize(s));
+        GMK_STAGED(stage, hipMemcpyAsync(&unfinished, sp.unfinished, 4, hipMemcpyDeviceToHost, s));
+        GMK_STAGED(stage, hipStreamSynchronize(s));
         if (reuse_subtree) trad_flip(t);
         if (unfinished == 0) break;
     }
     int32_t overflow = 0;
-    if (rc == GMK_OK) GMK_TRY(hipMemcpy(&overflow, sp.overflow, 4, hipMemcpyDeviceToHost));
-    if (rc == GMK_OK) GMK_TRY(hipMemcpy(t->d_game_ids, t->game_ids.data(), ns * 4, hipMemcpyHostToDevice));      // the loop's kernels wrote it: it mirrors game_ids again
-#undef GMK_TRY
-    cleanup();
+    if (rc == GMK_OK) GMK_STAGED(stage, hipMemcpy(&overflow, sp.overflow, 4, hipMemcpyDeviceToHost));
+    if (rc == GMK_OK) GMK_STAGED(stage, hipMemcpy(t->d_game_ids, t->game_ids.data(), ns * 4, hipMemcpyHostToDevice));      // the loop's kernels wrote it: it mirrors game_ids again
     if (h_overflow) *h_overflow = overflow;
     if (h_steps) *h_steps = steps;
     // the handle is left with idle slots: position it again (gmk_trad_set_positions) before any other use

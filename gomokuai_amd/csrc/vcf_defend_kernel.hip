@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "vcf_device.h"
+#include "host_staging.h"
 
 namespace {
 
@@ -171,7 +172,7 @@ bool bad_arguments(const void* moves, int stride, const void* lens, int n, int m
 extern "C" int gmk_vcf_defend(const uint8_t* d_moves, int stride, const int32_t* d_lens, int n, int max_depth, uint32_t budget, int flags,
                               int32_t* d_threat_status, int32_t* d_threat_length, uint8_t* d_threat_pv, uint32_t* d_threat_nodes,
                               uint8_t* d_verdict, uint8_t* d_cell_length, uint32_t* d_cell_nodes, void* stream) {
-    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (bad_arguments(d_moves, stride, d_lens, n, max_depth, flags, d_threat_status, d_threat_length, d_threat_pv, d_verdict) || misaligned(d_lens, 4) ||
         misaligned(d_threat_status, 4) || misaligned(d_threat_length, 4) || misaligned(d_threat_nodes, 4) || misaligned(d_cell_nodes, 4)) {
         gmk::set_error("gmk_vcf_defend: bad arguments (n >= 0, stride >= 1, max_depth in [1, %d], flags 0 or GMK_VCF_ITERATIVE; the threat's status, length "
@@ -186,14 +187,9 @@ extern "C" int gmk_vcf_defend(const uint8_t* d_moves, int stride, const int32_t*
     prm.moves = d_moves; prm.lens = d_lens; prm.stride = stride; prm.n = n; prm.max_depth = max_depth; prm.flags = flags; prm.budget = budget;
     prm.threat_status = d_threat_status; prm.threat_length = d_threat_length; prm.threat_pv = d_threat_pv;
     prm.verdict = d_verdict; prm.cell_length = d_cell_length; prm.cell_nodes = d_cell_nodes;
-    // A wavefront walks a slice of the jobs, four at a time.  Small batches spread over the chip one quartet per wavefront -- one position is 57
-    // wavefronts; large ones give every wavefront 64 jobs, so that a group reads a position once for sixteen of its cells and has other jobs to
-    // take while a neighbour is deep in a search.
-    const int cus = std::max(1, gmk::device_state().cu_count);
-    const long long jobs = static_cast<long long>(n) * 225;
-    prm.per_wave = jobs <= 4ll * 8 * cus ? 4 : static_cast<int>(std::max(64ll, (jobs >> 30) + 1));      // the grid stays below 2^30 workgroups for any n
-    const long long grid = (jobs + prm.per_wave - 1) / prm.per_wave;
-    hipLaunchKernelGGL(vcf_defend_kernel, dim3(static_cast<unsigned>(grid)), dim3(64), 0, static_cast<hipStream_t>(stream), prm);
+    const SlicePlan plan = cell_slices(n, gmk::device_state().cu_count);
+    prm.per_wave = plan.per_wave;
+    hipLaunchKernelGGL(vcf_defend_kernel, dim3(plan.grid), dim3(64), 0, static_cast<hipStream_t>(stream), prm);
     GMK_HIP_CHECK(hipGetLastError());
     return GMK_OK;
 }
@@ -201,39 +197,27 @@ extern "C" int gmk_vcf_defend(const uint8_t* d_moves, int stride, const int32_t*
 extern "C" int gmk_vcf_defend_host(const uint8_t* h_moves, int stride, const int32_t* h_lens, int n, int max_depth, uint32_t budget, int flags,
                                    int32_t* h_threat_status, int32_t* h_threat_length, uint8_t* h_threat_pv, uint32_t* h_threat_nodes,
                                    uint8_t* h_verdict, uint8_t* h_cell_length, uint32_t* h_cell_nodes) {
-    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (bad_arguments(h_moves, stride, h_lens, n, max_depth, flags, h_threat_status, h_threat_length, h_threat_pv, h_verdict)) {
         gmk::set_error("gmk_vcf_defend_host: bad arguments (n >= 0, stride >= 1, max_depth in [1, %d], flags 0 or GMK_VCF_ITERATIVE; the threat's status, "
                        "length and pv and h_verdict not NULL)", GMK_VCF_MAX_DEPTH);
         return GMK_ERR_ARG;
     }
     if (n == 0) return GMK_OK;
-    // one device block: moves | lens | threat status | length | nodes | pv | verdict | cell length | cell nodes, each part 16-byte aligned
-    const auto up16 = [](size_t b) { return (b + 15) & ~size_t(15); };
+    // one device block: moves | lens | threat status | length | nodes | pv | verdict | cell length | cell nodes
     const size_t un = static_cast<size_t>(n), cells = un * 225;
-    const size_t o_lens = up16(un * static_cast<size_t>(stride)), o_status = o_lens + up16(un * 4), o_length = o_status + up16(un * 4),
-                 o_nodes = o_length + up16(un * 4), o_pv = o_nodes + up16(un * 4), o_verdict = o_pv + up16(un * GMK_VCF_PV),
-                 o_cell_length = o_verdict + up16(cells), o_cell_nodes = o_cell_length + up16(cells), total = o_cell_nodes + up16(cells * 4);
-    char* d = nullptr;
-    GMK_HIP_CHECK(gmk::device_malloc(&d, total));
-    int rc = GMK_OK;
-    if (hipMemcpy(d, h_moves, un * static_cast<size_t>(stride), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d + o_lens, h_lens, un * 4, hipMemcpyHostToDevice) != hipSuccess) rc = GMK_ERR_HIP;
+    gmk::Staging st("gmk_vcf_defend_host");
+    uint8_t *d_moves, *d_pv, *d_verdict, *d_cell_length;
+    int32_t *d_lens, *d_status, *d_length;
+    uint32_t *d_nodes, *d_cell_nodes;
+    st.in(d_moves, h_moves, un * static_cast<size_t>(stride)); st.in(d_lens, h_lens, un);
+    st.out(d_status, h_threat_status, un); st.out(d_length, h_threat_length, un); st.out(d_nodes, h_threat_nodes, un);
+    st.out(d_pv, h_threat_pv, un * GMK_VCF_PV); st.out(d_verdict, h_verdict, cells); st.out(d_cell_length, h_cell_length, cells);
+    st.out(d_cell_nodes, h_cell_nodes, cells);
+    int rc = st.take();
     if (rc == GMK_OK)
-        rc = gmk_vcf_defend(reinterpret_cast<const uint8_t*>(d), stride, reinterpret_cast<const int32_t*>(d + o_lens), n, max_depth, budget, flags,
-                            reinterpret_cast<int32_t*>(d + o_status), reinterpret_cast<int32_t*>(d + o_length), reinterpret_cast<uint8_t*>(d + o_pv),
-                            h_threat_nodes ? reinterpret_cast<uint32_t*>(d + o_nodes) : nullptr, reinterpret_cast<uint8_t*>(d + o_verdict),
-                            h_cell_length ? reinterpret_cast<uint8_t*>(d + o_cell_length) : nullptr,
-                            h_cell_nodes ? reinterpret_cast<uint32_t*>(d + o_cell_nodes) : nullptr, nullptr);
-    if (rc == GMK_OK && hipDeviceSynchronize() != hipSuccess) rc = GMK_ERR_HIP;
-    if (rc == GMK_OK && (hipMemcpy(h_threat_status, d + o_status, un * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                         hipMemcpy(h_threat_length, d + o_length, un * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                         hipMemcpy(h_threat_pv, d + o_pv, un * GMK_VCF_PV, hipMemcpyDeviceToHost) != hipSuccess ||
-                         hipMemcpy(h_verdict, d + o_verdict, cells, hipMemcpyDeviceToHost) != hipSuccess ||
-                         (h_threat_nodes && hipMemcpy(h_threat_nodes, d + o_nodes, un * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-                         (h_cell_length && hipMemcpy(h_cell_length, d + o_cell_length, cells, hipMemcpyDeviceToHost) != hipSuccess) ||
-                         (h_cell_nodes && hipMemcpy(h_cell_nodes, d + o_cell_nodes, cells * 4, hipMemcpyDeviceToHost) != hipSuccess))) rc = GMK_ERR_HIP;
-    if (rc == GMK_ERR_HIP) gmk::set_error("gmk_vcf_defend_host: a HIP call failed: %s", hipGetErrorString(hipGetLastError()));
-    (void)gmk::device_free(d);
-    return rc;
+        rc = gmk_vcf_defend(d_moves, stride, d_lens, n, max_depth, budget, flags, d_status, d_length, d_pv, d_nodes, d_verdict, d_cell_length, d_cell_nodes, nullptr);
+    if (rc != GMK_OK) return rc;                                  // the device form's code and text, untouched
+    GMK_STAGED(st, hipDeviceSynchronize());
+    return st.download();
 }

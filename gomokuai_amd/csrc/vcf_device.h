@@ -320,4 +320,18 @@ __device__ __forceinline__ Planes load_moves(const uint8_t* moves, int stride, c
     return pl;
 }
 
+// ---- the host's side of K15 and K17: the slices of n * 225 jobs ----
+// A wavefront walks a slice of the jobs, four at a time.  Small batches spread over the chip one quartet per wavefront -- one position is 57
+// wavefronts; large ones give every wavefront 64 jobs, so that a group reads a position once for sixteen of its cells and has other jobs to
+// take while a neighbour is deep in a search.  The grid stays below 2^30 workgroups for any n.
+struct SlicePlan {
+    int per_wave;
+    unsigned grid;
+};
+inline SlicePlan cell_slices(int n, int cu_count) {
+    const long long jobs = static_cast<long long>(n) * kCells, cus = cu_count > 1 ? cu_count : 1, large = (jobs >> 30) + 1;
+    const int per_wave = jobs <= 4ll * 8 * cus ? 4 : static_cast<int>(large > 64 ? large : 64);
+    return {per_wave, static_cast<unsigned>((jobs + per_wave - 1) / per_wave)};
+}
+
 }  // namespace gmk::vcf

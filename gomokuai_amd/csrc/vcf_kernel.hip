@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "vcf_device.h"
+#include "host_staging.h"
 
 namespace {
 
@@ -102,7 +103,7 @@ constexpr int kKnownFlags = GMK_VCF_OPPONENT | GMK_VCF_ITERATIVE;
 
 extern "C" int gmk_vcf_solve(const uint8_t* d_moves, int stride, const int32_t* d_lens, int n, int max_depth, uint32_t budget, int flags,
                              int32_t* d_status, int32_t* d_move, int32_t* d_length, uint32_t* d_nodes, uint8_t* d_pv, void* stream) {
-    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (n < 0 || stride < 1 || max_depth < 1 || max_depth > GMK_VCF_MAX_DEPTH || (flags & ~kKnownFlags) != 0 || (n > 0 && (!d_moves || !d_lens)) ||
         misaligned(d_lens, 4) || misaligned(d_status, 4) || misaligned(d_move, 4) || misaligned(d_length, 4) || misaligned(d_nodes, 4)) {
         gmk::set_error("gmk_vcf_solve: bad arguments (n >= 0, stride >= 1, max_depth in [1, %d], flags in [0, 3]; d_lens and the int32 outputs 4-byte aligned)",
@@ -125,34 +126,24 @@ extern "C" int gmk_vcf_solve(const uint8_t* d_moves, int stride, const int32_t* 
 
 extern "C" int gmk_vcf_solve_host(const uint8_t* h_moves, int stride, const int32_t* h_lens, int n, int max_depth, uint32_t budget, int flags,
                                   int32_t* h_status, int32_t* h_move, int32_t* h_length, uint32_t* h_nodes, uint8_t* h_pv) {
-    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (n < 0 || stride < 1 || max_depth < 1 || max_depth > GMK_VCF_MAX_DEPTH || (flags & ~kKnownFlags) != 0 || (n > 0 && (!h_moves || !h_lens))) {
         gmk::set_error("gmk_vcf_solve_host: bad arguments (n >= 0, stride >= 1, max_depth in [1, %d], flags in [0, 3])", GMK_VCF_MAX_DEPTH);
         return GMK_ERR_ARG;
     }
     if (n == 0) return GMK_OK;
-    // one device block: moves | lens | status | move | length | nodes | pv, each part 16-byte aligned
-    const auto up16 = [](size_t b) { return (b + 15) & ~size_t(15); };
+    // one device block: moves | lens | status | move | length | nodes | pv
     const size_t un = static_cast<size_t>(n);
-    const size_t o_lens = up16(un * static_cast<size_t>(stride)), o_status = o_lens + up16(un * 4), o_move = o_status + up16(un * 4),
-                 o_length = o_move + up16(un * 4), o_nodes = o_length + up16(un * 4), o_pv = o_nodes + up16(un * 4), total = o_pv + up16(un * GMK_VCF_PV);
-    char* d = nullptr;
-    GMK_HIP_CHECK(gmk::device_malloc(&d, total));
-    int rc = GMK_OK;
-    if (hipMemcpy(d, h_moves, un * static_cast<size_t>(stride), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d + o_lens, h_lens, un * 4, hipMemcpyHostToDevice) != hipSuccess) rc = GMK_ERR_HIP;
-    if (rc == GMK_OK)
-        rc = gmk_vcf_solve(reinterpret_cast<const uint8_t*>(d), stride, reinterpret_cast<const int32_t*>(d + o_lens), n, max_depth, budget, flags,
-                           h_status ? reinterpret_cast<int32_t*>(d + o_status) : nullptr, h_move ? reinterpret_cast<int32_t*>(d + o_move) : nullptr,
-                           h_length ? reinterpret_cast<int32_t*>(d + o_length) : nullptr, h_nodes ? reinterpret_cast<uint32_t*>(d + o_nodes) : nullptr,
-                           h_pv ? reinterpret_cast<uint8_t*>(d + o_pv) : nullptr, nullptr);
-    if (rc == GMK_OK && hipDeviceSynchronize() != hipSuccess) rc = GMK_ERR_HIP;
-    if (rc == GMK_OK && ((h_status && hipMemcpy(h_status, d + o_status, un * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-                         (h_move && hipMemcpy(h_move, d + o_move, un * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-                         (h_length && hipMemcpy(h_length, d + o_length, un * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-                         (h_nodes && hipMemcpy(h_nodes, d + o_nodes, un * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-                         (h_pv && hipMemcpy(h_pv, d + o_pv, un * GMK_VCF_PV, hipMemcpyDeviceToHost) != hipSuccess))) rc = GMK_ERR_HIP;
-    if (rc == GMK_ERR_HIP) gmk::set_error("gmk_vcf_solve_host: a HIP call failed: %s", hipGetErrorString(hipGetLastError()));
-    (void)gmk::device_free(d);
-    return rc;
+    gmk::Staging st("gmk_vcf_solve_host");
+    uint8_t *d_moves, *d_pv;
+    int32_t *d_lens, *d_status, *d_move, *d_length;
+    uint32_t* d_nodes;
+    st.in(d_moves, h_moves, un * static_cast<size_t>(stride)); st.in(d_lens, h_lens, un);
+    st.out(d_status, h_status, un); st.out(d_move, h_move, un); st.out(d_length, h_length, un); st.out(d_nodes, h_nodes, un);
+    st.out(d_pv, h_pv, un * GMK_VCF_PV);
+    int rc = st.take();
+    if (rc == GMK_OK) rc = gmk_vcf_solve(d_moves, stride, d_lens, n, max_depth, budget, flags, d_status, d_move, d_length, d_nodes, d_pv, nullptr);
+    if (rc != GMK_OK) return rc;                                  // the device form's code and text, untouched
+    GMK_STAGED(st, hipDeviceSynchronize());
+    return st.download();
 }

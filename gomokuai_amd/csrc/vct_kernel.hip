@@ -15,10 +15,10 @@
 #include <algorithm>
 #include <cstring>
 #include <exception>
-#include <utility>
 #include <vector>
 
 #include "capi_common.h"
+#include "host_staging.h"
 
 namespace {
 
@@ -251,35 +251,7 @@ bool bad_arguments(const void* moves, int stride, const void* lens, int n, int m
            max_threats > GMK_VCT_MAX_THREATS || max_positions < 1 || (n > 0 && (!moves || !lens));
 }
 
-// The workspace: a few blocks per level, each carved into the arrays that were asked for; all are freed when the call returns, whichever way.
-struct Blocks {
-    std::vector<void*> held;
-    std::vector<std::pair<void*, size_t>> wanted;               // (where the array's pointer goes, its bytes) of the block to come
-    template <class T>
-    void want(T*& p, size_t count) {
-        p = nullptr;
-        wanted.emplace_back(static_cast<void*>(&p), (std::max<size_t>(1, count) * sizeof(T) + 15) & ~size_t(15));
-    }
-    bool take() {                                               // one allocation for everything wanted since the last one
-        size_t total = 0;
-        for (const auto& w : wanted) total += w.second;
-        void* block = nullptr;
-        if (gmk::device_malloc_bytes(&block, total) != hipSuccess) { wanted.clear(); return false; }
-        held.push_back(block);
-        char* at = static_cast<char*>(block);
-        for (const auto& w : wanted) {
-            std::memcpy(w.first, &at, sizeof(at));              // every T* has the representation of a char* here
-            at += w.second;
-        }
-        wanted.clear();
-        return true;
-    }
-    void release() {
-        for (void* p : held) (void)gmk::device_free(p);
-        held.clear();
-    }
-    ~Blocks() { release(); }
-};
+using gmk::Blocks;                                              // the workspace: a few blocks per level (host_staging.h)
 
 struct Level {
     LevelView view{};
@@ -298,7 +270,7 @@ inline unsigned blocks_for(long long count) { return static_cast<unsigned>((coun
 
 int vct_solve(const uint8_t* d_moves, int stride, const int32_t* d_lens, int n, int max_depth, uint32_t budget, int flags, int max_threats,
               int max_positions, int32_t* d_status, int32_t* d_move, int32_t* d_threats, uint32_t* d_positions, uint8_t* d_pv, void* stream) {
-    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (bad_arguments(d_moves, stride, d_lens, n, max_depth, flags, max_threats, max_positions) || misaligned(d_lens, 4) || misaligned(d_status, 4) ||
         misaligned(d_move, 4) || misaligned(d_threats, 4) || misaligned(d_positions, 4)) {
         gmk::set_error("gmk_vct_solve: bad arguments (n >= 0, stride >= 1, max_depth in [1, %d], flags 0 or GMK_VCF_ITERATIVE, max_threats in [1, %d], "
@@ -494,39 +466,26 @@ extern "C" int gmk_vct_solve(const uint8_t* d_moves, int stride, const int32_t* 
 extern "C" int gmk_vct_solve_host(const uint8_t* h_moves, int stride, const int32_t* h_lens, int n, int max_depth, uint32_t budget, int flags,
                                   int max_threats, int max_positions, int32_t* h_status, int32_t* h_move, int32_t* h_threats, uint32_t* h_positions,
                                   uint8_t* h_pv) {
-    if (!gmk::device_state().ready) { gmk::set_error("gmk_init has not succeeded (no CPU fallback)"); return GMK_ERR_STATE; }
+    GMK_NEED_INIT();
     if (bad_arguments(h_moves, stride, h_lens, n, max_depth, flags, max_threats, max_positions)) {
         gmk::set_error("gmk_vct_solve_host: bad arguments (n >= 0, stride >= 1, max_depth in [1, %d], flags 0 or GMK_VCF_ITERATIVE, max_threats in [1, %d], "
                        "max_positions >= 1)", GMK_VCF_MAX_DEPTH, GMK_VCT_MAX_THREATS);
         return GMK_ERR_ARG;
     }
     if (n == 0) return GMK_OK;
-    // one device block: moves | lens | status | move | threats | positions | pv, each part 16-byte aligned
-    const auto up16 = [](size_t b) { return (b + 15) & ~size_t(15); };
+    // one device block: moves | lens | status | move | threats | positions | pv
     const size_t un = static_cast<size_t>(n);
-    const size_t o_lens = up16(un * static_cast<size_t>(stride)), o_status = o_lens + up16(un * 4), o_move = o_status + up16(un * 4),
-                 o_threats = o_move + up16(un * 4), o_positions = o_threats + up16(un * 4), o_pv = o_positions + up16(un * 4),
-                 total = o_pv + up16(un * GMK_VCT_PV);
-    char* d = nullptr;
-    GMK_HIP_CHECK(gmk::device_malloc(&d, total));
-    int rc = GMK_OK;
-    if (hipMemcpy(d, h_moves, un * static_cast<size_t>(stride), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d + o_lens, h_lens, un * 4, hipMemcpyHostToDevice) != hipSuccess) rc = GMK_ERR_HIP;
-    bool inner = false;
-    if (rc == GMK_OK) {
-        rc = gmk_vct_solve(reinterpret_cast<const uint8_t*>(d), stride, reinterpret_cast<const int32_t*>(d + o_lens), n, max_depth, budget, flags, max_threats,
-                           max_positions, h_status ? reinterpret_cast<int32_t*>(d + o_status) : nullptr, h_move ? reinterpret_cast<int32_t*>(d + o_move) : nullptr,
-                           h_threats ? reinterpret_cast<int32_t*>(d + o_threats) : nullptr,
-                           h_positions ? reinterpret_cast<uint32_t*>(d + o_positions) : nullptr, h_pv ? reinterpret_cast<uint8_t*>(d + o_pv) : nullptr, nullptr);
-        inner = rc != GMK_OK;                                      // the error text is the device form's
-    }
-    if (rc == GMK_OK && hipDeviceSynchronize() != hipSuccess) rc = GMK_ERR_HIP;
-    if (rc == GMK_OK && ((h_status && hipMemcpy(h_status, d + o_status, un * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-                         (h_move && hipMemcpy(h_move, d + o_move, un * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-                         (h_threats && hipMemcpy(h_threats, d + o_threats, un * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-                         (h_positions && hipMemcpy(h_positions, d + o_positions, un * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-                         (h_pv && hipMemcpy(h_pv, d + o_pv, un * GMK_VCT_PV, hipMemcpyDeviceToHost) != hipSuccess))) rc = GMK_ERR_HIP;
-    if (rc == GMK_ERR_HIP && !inner) gmk::set_error("gmk_vct_solve_host: a HIP call failed: %s", hipGetErrorString(hipGetLastError()));
-    (void)gmk::device_free(d);
-    return rc;
+    gmk::Staging st("gmk_vct_solve_host");
+    uint8_t *d_moves, *d_pv;
+    int32_t *d_lens, *d_status, *d_move, *d_threats;
+    uint32_t* d_positions;
+    st.in(d_moves, h_moves, un * static_cast<size_t>(stride)); st.in(d_lens, h_lens, un);
+    st.out(d_status, h_status, un); st.out(d_move, h_move, un); st.out(d_threats, h_threats, un); st.out(d_positions, h_positions, un);
+    st.out(d_pv, h_pv, un * GMK_VCT_PV);
+    int rc = st.take();
+    if (rc == GMK_OK)
+        rc = gmk_vct_solve(d_moves, stride, d_lens, n, max_depth, budget, flags, max_threats, max_positions, d_status, d_move, d_threats, d_positions, d_pv, nullptr);
+    if (rc != GMK_OK) return rc;                                  // the device form's code and text, untouched
+    GMK_STAGED(st, hipDeviceSynchronize());
+    return st.download();
 }

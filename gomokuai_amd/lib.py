@@ -791,15 +791,20 @@ class EvaluatorStates:
 PATTERN_OVER, PATTERN_EVALUATOR_ERROR, PATTERN_ILLEGAL, PATTERN_STALLED = 1, 2, 4, 8      # status bits of gmk_pattern_policy / gmk_pattern_play
 
 
-def pattern_policy(moves, lens, filter=True):
-    """moves u8[n, stride] (host), lens i32[n]: one move list per position, black first -> {"probs" f32[n,225], "value" f32[n], "best" i32[n],
-    "status" i32[n]} for the player to move: what PatternEvalAgent (filter=True) or MaxEvaluatedRollout (filter=False) sees there.
-    Runs on the GPU through gmk_pattern_policy_host; raises without one."""
+def _move_lists(moves, lens):
+    """The host front ends' move lists: moves u8[n, stride] and lens i32[n], contiguous -> (moves, lens, n, stride); the library is initialised."""
     init()
     moves = np.ascontiguousarray(moves, dtype=np.uint8)
     lens = np.ascontiguousarray(lens, dtype=np.int32)
     assert moves.ndim == 2 and lens.shape == (moves.shape[0],)
-    n, stride = moves.shape
+    return (moves, lens) + moves.shape
+
+
+def pattern_policy(moves, lens, filter=True):
+    """moves u8[n, stride] (host), lens i32[n]: one move list per position, black first -> {"probs" f32[n,225], "value" f32[n], "best" i32[n],
+    "status" i32[n]} for the player to move: what PatternEvalAgent (filter=True) or MaxEvaluatedRollout (filter=False) sees there.
+    Runs on the GPU through gmk_pattern_policy_host; raises without one."""
+    moves, lens, n, stride = _move_lists(moves, lens)
     out = {"probs": np.zeros((n, N), np.float32), "value": np.zeros(n, np.float32), "best": np.zeros(n, np.int32), "status": np.zeros(n, np.int32)}
     _check(load().gmk_pattern_policy_host(moves.ctypes.data, stride, lens.ctypes.data, n, int(bool(filter)),
                                           out["probs"].ctypes.data, out["value"].ctypes.data, out["best"].ctypes.data, out["status"].ctypes.data))
@@ -832,11 +837,7 @@ def vcf_solve(moves, lens, max_depth=16, budget=100000, opponent=False, iterativ
     "nodes" u32[n], "pv" u8[n, 64]}: is there a forced win by continuous fours for the side to move (opponent=True: for the other side, moving
     first), within max_depth attacker moves and `budget` four-making candidates?  Exact; the contract is in include/gomoku_hip.h.
     Runs on the GPU through gmk_vcf_solve_host; raises without one."""
-    init()
-    moves = np.ascontiguousarray(moves, dtype=np.uint8)
-    lens = np.ascontiguousarray(lens, dtype=np.int32)
-    assert moves.ndim == 2 and lens.shape == (moves.shape[0],)
-    n, stride = moves.shape
+    moves, lens, n, stride = _move_lists(moves, lens)
     out = {"status": np.zeros(n, np.int32), "move": np.zeros(n, np.int32), "length": np.zeros(n, np.int32), "nodes": np.zeros(n, np.uint32),
            "pv": np.full((n, VCF_PV), 255, np.uint8)}
     if n:
@@ -864,11 +865,7 @@ def vcf_defend(moves, lens, max_depth=16, budget=100000, iterative=False):
     the 225 cells what a stone of the side to move there does about it: "verdict" u8[n, 225] (VCF_CELL_*), "length" u8[n, 225] (the
     attacker's moves where the cell LOSES) and "nodes" u32[n, 225] (the candidates tried where the cell was searched).  Exact; the contract is
     in include/gomoku_hip.h ("K15").  Runs on the GPU through gmk_vcf_defend_host; raises without one."""
-    init()
-    moves = np.ascontiguousarray(moves, dtype=np.uint8)
-    lens = np.ascontiguousarray(lens, dtype=np.int32)
-    assert moves.ndim == 2 and lens.shape == (moves.shape[0],)
-    n, stride = moves.shape
+    moves, lens, n, stride = _move_lists(moves, lens)
     out = {"threat_status": np.zeros(n, np.int32), "threat_length": np.zeros(n, np.int32), "threat_pv": np.full((n, VCF_PV), 255, np.uint8),
            "threat_nodes": np.zeros(n, np.uint32), "verdict": np.zeros((n, 225), np.uint8), "length": np.zeros((n, 225), np.uint8),
            "nodes": np.zeros((n, 225), np.uint32)}
@@ -902,11 +899,7 @@ def vcf_threats(moves, lens, max_depth=16, budget=100000, iterative=False):
     cells what a stone of the side to move there threatens: "verdict" u8[n, 225] (VCF_THREAT_*), "length" u8[n, 225] (the moves of the win by
     fours that a WINS cell threatens; 1 or 2 for a FOUR) and "nodes" u32[n, 225] (the candidates tried where the cell was searched).  Exact;
     the contract is in include/gomoku_hip.h ("K17").  Runs on the GPU through gmk_vcf_threats_host; raises without one."""
-    init()
-    moves = np.ascontiguousarray(moves, dtype=np.uint8)
-    lens = np.ascontiguousarray(lens, dtype=np.int32)
-    assert moves.ndim == 2 and lens.shape == (moves.shape[0],)
-    n, stride = moves.shape
+    moves, lens, n, stride = _move_lists(moves, lens)
     out = {"own_status": np.zeros(n, np.int32), "own_move": np.zeros(n, np.int32), "own_length": np.zeros(n, np.int32),
            "own_nodes": np.zeros(n, np.uint32), "own_pv": np.full((n, VCF_PV), 255, np.uint8), "verdict": np.zeros((n, 225), np.uint8),
            "length": np.zeros((n, 225), np.uint8), "nodes": np.zeros((n, 225), np.uint32)}
@@ -931,11 +924,7 @@ def vct_solve(moves, lens, max_depth=16, budget=100000, iterative=False, max_thr
     moves that threaten a win by fours (each answered by every reply that holds) and then a win by fours?  max_depth, budget and iterative are
     those of every inner vcf_solve; max_positions caps the positions of one root on one level.  Exact; the contract is in
     include/gomoku_hip.h ("K17").  Runs on the GPU through gmk_vct_solve_host; raises without one."""
-    init()
-    moves = np.ascontiguousarray(moves, dtype=np.uint8)
-    lens = np.ascontiguousarray(lens, dtype=np.int32)
-    assert moves.ndim == 2 and lens.shape == (moves.shape[0],)
-    n, stride = moves.shape
+    moves, lens, n, stride = _move_lists(moves, lens)
     out = {"status": np.zeros(n, np.int32), "move": np.full(n, -1, np.int32), "threats": np.zeros(n, np.int32), "positions": np.zeros(n, np.uint32),
            "pv": np.full((n, VCT_PV), 255, np.uint8)}
     if n:
@@ -1199,6 +1188,15 @@ class TraditionalMCTS:
         return out
 
 
+def _root_stats_with_amaf(self):
+    """root_stats() of the two RAVE searchers: TraditionalMCTS's, and the root children's AMAF statistics."""
+    out = TraditionalMCTS.root_stats(self)
+    out["amaf_visits"] = np.zeros((self.n, N), np.uint32)
+    out["amaf_values"] = np.zeros((self.n, N), np.float32)
+    _check(load().gmk_trad_root_amaf(self.h, out["amaf_visits"].ctypes.data, out["amaf_values"].ctypes.data))
+    return out
+
+
 class PoolRAVEMCTS(TraditionalMCTS):
     """n_games searches of MCTS(policy=PoolRAVEPolicy(c_puct)) side by side on the GPU (K8): the tree, step, noise and root
     statistics of TraditionalMCTS, playouts with one random rollout each and RAVE::BackPropogate<true>."""
@@ -1215,12 +1213,7 @@ class PoolRAVEMCTS(TraditionalMCTS):
     def add_root_noise(self, alpha=0.05, epsilon=0.25, seed=None, first_game_id=None, stream=None):
         super().add_root_noise(alpha, epsilon, self.seed if seed is None else seed, self.first_game_id if first_game_id is None else first_game_id, stream)
 
-    def root_stats(self):
-        out = super().root_stats()
-        out["amaf_visits"] = np.zeros((self.n, N), np.uint32)
-        out["amaf_values"] = np.zeros((self.n, N), np.float32)
-        _check(load().gmk_trad_root_amaf(self.h, out["amaf_visits"].ctypes.data, out["amaf_values"].ctypes.data))
-        return out
+    root_stats = _root_stats_with_amaf
 
 
 class TraditionalRAVEMCTS(TraditionalMCTS):
@@ -1237,12 +1230,7 @@ class TraditionalRAVEMCTS(TraditionalMCTS):
     def run(self, playouts, stream=0):
         _check(load().gmk_trad_run_rave(self.h, int(playouts), self.c_puct, stream))
 
-    def root_stats(self):
-        out = super().root_stats()
-        out["amaf_visits"] = np.zeros((self.n, N), np.uint32)
-        out["amaf_values"] = np.zeros((self.n, N), np.float32)
-        _check(load().gmk_trad_root_amaf(self.h, out["amaf_visits"].ctypes.data, out["amaf_values"].ctypes.data))
-        return out
+    root_stats = _root_stats_with_amaf
 
 
 # ---------------- K7: network-guided search, many games in lock step ----------------
