@@ -20,8 +20,8 @@
 //     bonus) comes from the rows dilated by the three row patterns of the 7x7 mask, with DPP row shifts; the score block -- [cell][4 groups] in
 //     LDS -- is written ONCE, with the bonus in it;
 //   * phase 1: the 72 lines that can hold a pattern (>= 5 cells) are spread over the 64 lanes (the 8 shortest ride
-//     behind the shortest primaries: 19 steps per lane, fully unrolled); a lane's lines are one stream of 2-bit symbols,
-//     a step is one LDS lookup; emitting transitions are queued by ballot prefix, in the shadow of the next step's lookup (the queue's fill
+//     behind the shortest primaries: 17 steps per lane, fully unrolled); a lane's lines are one stream of 2-bit symbols without leading pads,
+//     walked from the state the root reaches on '?'; a step is one LDS lookup, and the first ten carry a piece of phase 0 in their shadow; emitting transitions are queued by ballot prefix, in the shadow of the next step's lookup (the queue's fill
 //     level lives on the scalar unit, clamped there: no per-lane bounds check);
 //   * phase 2: one lane per queued transition: one 16-byte record read gives the (<= 2) matches, each with a
 //     compact list of <= 4 score deposits -- a colour's own and opponent view of a cell are the halves of one 64-bit word, so a deposit is ONE
@@ -43,6 +43,10 @@
 //     block added to a 64-bit scalar base: global_store_dword offset, value, s[base]); the occupied bits come from 7 x 16 words the burst puts
 //     in LDS once (two 16-byte reads per pass).  Everything the prologue reads is one image the host builds once: 23 KB staged 16 bytes per lane, 32 bytes of constants per lane, all loads issued at once.
 // HBM traffic per board: 64 B in, 7 248 B out (7 312 B algorithmic); everything else stays on chip.
+// Round 11 (profiles/r11_k1_*) shortened each board's chain of dependent LDS round trips: the scan lost its two leading-pad steps
+// (19 -> 17: -1.3 % of the launch on its own), and what phase 0 writes for phase 2 and later moved out of the way of the line words into the scan's
+// first lookups (-0.5 % on top).  Asking for the next hand-out behind phase 5's block reads and fetching the next deposit round's record and jobs
+// ahead were built, measured as no gain (+0.3 % and +-0.1 %) and are not in the source.
 #include <algorithm>
 #include <cstdlib>
 #include <vector>
@@ -84,27 +88,28 @@ constexpr int kMiscWords = 48;                   // [0] stones black | white << 
 constexpr int kBoardWords = kZeroWords + kLineWords + kQueueCap + kMiscWords;
 static_assert(kZeroWords % 4 == 0 && kBoardWords % 4 == 0, "16-byte alignment of the per-board blocks");
 constexpr int kStaticTableWords = 128 + kLineWords + 512 + 1560 + 4;   // lane jobs, the lines' '?' pads (phase 4), the bits-to-bytes table, the weight table of phase D,
-                                                                        // and the workgroup's hand-out counter (four words: one used)
+                                                                        // and the workgroup's hand-out counter (four words: [0] the counter, [1] the row the scan starts from, read from the image, never from LDS)
 
 // Lane -> line jobs.  A job word holds what the scan and the deposits need of a line, ready to use: bits 0..4 symbols in its stream
-// segment (len + 3: one leading and two trailing pads), 5..6 dir, 7..11 cell stride, 12..19 its first cell, 20..26 line word index.
+// segment (len + 2: its cells and two trailing pads), 5..6 dir, 7..11 cell stride, 12..19 its first cell, 20..26 line word index.
 // Everything a launch reads besides the boards is ONE image in device memory that the host builds once (build_stage_image): first what every workgroup
 // stages in LDS, in LDS order and ready to use -- the automaton, the emission records, the lane jobs, the lines' '?' pads, the bits-to-bytes table, the
-// weight table of phase D, the hand-out counter's start value -- copied 16 bytes per lane; behind it a 32-byte record per lane with what the prologue
+// weight table of phase D, the hand-out counter's start value and the scan's start row -- copied 16 bytes per lane; behind it a 32-byte record per lane with what the prologue
 // would otherwise derive from the lane number: its two jobs, its two all-blank line words ((1 << 2 len) - 1: words lane and 64 + lane), then [0] row * 4
 // and [1] column of the lane's cell in each of the four passes over the board (cell = 64 pass + lane, the last one clamped to 224), a byte per pass, and
 // [2], [3] where the first cell of the lane's two lines sits in its line word (bit 2 x0 for a diagonal, 2 y0 for an anti-diagonal, 0 for rows and columns).
 // Every load of the prologue is issued before the first of them is waited for: their latencies overlap.  (They used to be a dozen loops and
 // constant-memory reads, each waiting for its own load: a dozen memory latencies in a row at the head of every launch.)
 constexpr int kLaneRecordVecs = 2;
-constexpr int kScanSteps = 19;                    // symbols in the longest lane stream (lane_tables checks it)
+constexpr int kSegPads = 2;                       // the '?' behind a line's cells in its stream segment (none in front: phase 1 says why)
+constexpr int kScanSteps = 17;                    // symbols in the longest lane stream (lane_tables checks it)
 
 __device__ __forceinline__ int dir_stride(int dir) { return (0x0E100F01u >> (8 * dir)) & 0xFFu; }      // 1, 15, 16, 14: a shift, not three branches
 
-// '?' cells '?' '?' of one line as a symbol stream, first symbol in the low bits: exactly 2 * (len + 3) bits
-// (1 leading + 2 trailing pads instead of the reference's 6 + 6; '?' = 2 is the off-board symbol)
+// cells '?' '?' of one line as a symbol stream, first symbol in the low bits: exactly 2 * (len + 2) bits
+// (no leading and 2 trailing pads instead of the reference's 6 + 6; '?' = 2 is the off-board symbol)
 __device__ __forceinline__ uint64_t line_symbols(uint32_t line_word, int len) {
-    return 2ull | (static_cast<uint64_t>(line_word) << 2) | (0xAull << (2 * len + 2));
+    return static_cast<uint64_t>(line_word) | (0xAull << (2 * len));
 }
 
 // Phases of one board only exchange data between lanes of the SAME wavefront through LDS.  LDS instructions of
@@ -418,6 +423,9 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
     const uint4 stage_a = g_stage[min(tid, stage_vecs - 1)], stage_b = g_stage[min(tid + kThreads, stage_vecs - 1)];
     const uint4* lane_record = g_stage + stage_vecs + kLaneRecordVecs * (tid & 63);
     const uint4 lane_lines = lane_record[0], lane_consts = lane_record[1];
+    // the table word the scan starts from: the row the root reaches on '?' (the word behind the hand-out counter's start value in the image; a
+    // wave-uniform address, so a scalar load)
+    const uint32_t scan_start = reinterpret_cast<const uint32_t*>(g_stage)[trans_words + record_words + kStaticTableWords - 3];
     uint32_t* s_pads = s_jobs + 128;                                         // a line word's '?' pads: symbol 2 in every 2-bit slot of the word that is not one of the
                                                                              // line's cells (phase 4 ORs them in: its window then reads '?' off the line wherever the line starts in its word)
     uint2* s_lut = reinterpret_cast<uint2*>(s_jobs + 128 + kLineWords);      // byte -> its eight bits as bytes (the stone operands of phase D)
@@ -506,47 +514,40 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
         if (live) { idx_next = boards_done == 0 ? kBoardsPerBlock + wave : hand_out(); fetch_row(wg_first + min(idx_next, wg_boards - 1)); }
         GMK_STAMP(11);
 
-        if (live) {
-            // ---- phase 0: clear accumulators, take the two bit-planes (64 B), turn them into line words ----
-            {
-                // (the counters; the score block is written below, with the area bonus in it)
-                uint4* z = reinterpret_cast<uint4*>(s_cnt) + lane;
-    #pragma unroll
-                for (int i = 0; i < kCntWords / 4; i += 64)
-                    if (i + 64 <= kCntWords / 4 || lane < kCntWords / 4 - i) z[i] = make_uint4(0u, 0u, 0u, 0u);
-            }
-            // The lane masks of this phase come from a copy of the lane number that the compiler cannot see through: a compare per board each.  Hoisted
-            // out of the board loop they are scalar register pairs that do not fit and come back by two v_readlane each, per board.
-            int lane_m = lane;
-            asm volatile("" : "+v"(lane_m));
-            s_lines[lane] = line_init_lo;                       // (the all-blank line words wait in two registers, not in LDS: no read before the write)
-            if (lane_m < kLineWords - 64) s_lines[64 + lane] = line_init_hi;
-            if (lane_m < kMiscWords) s_misc[lane] = 0;
+        // Phase 0 in two parts.  In front of the scan stands only what its first lookup needs: the blank line words, the stones' XORs, and the clear of
+        // s_misc (the scan flags into s_misc[2]).  Everything else of phase 0 -- the counters' and the totals copies' clears, the stone count, the area
+        // bonus and the score block's four 16-byte writes -- is read by phase 2 at the earliest and is issued INSIDE the scan, one piece behind each of
+        // its first lookups (late_piece): LDS serves a wavefront in order, so in front of the line words those seven wide writes (~13 cycles each on the
+        // store path) and four ds_bpermute stood between every board and its first lookup.
+        uint32_t late_row = 0;
+        int late_lane = lane, late_gate = 0;
+        auto late_piece = [&](int piece) {
+            if (piece == 0) {
 #ifndef GMK_K1_TOTALS_HOT
-            // Per-type totals: one atomic per match on eight addresses is 64 lanes on eight LDS words -- up to ~25 of them on the same one, served
-            // one after the other (phase 2 is 41 % of the LDS pipe's cycles, profiles/r04_k1_lds_phases.txt).  kTotalsCopies copies, a lane adds to copy
-            // lane & (kTotalsCopies - 1); they live in the last words of the transition queue (a board that is not flagged queues < kQueueCap - 64 entries) and are
-            // summed behind phase 2.
-            if (lane < 8 * kTotalsCopies) s_queue[kQueueCap - 8 * kTotalsCopies + lane] = 0;
+                // (in front of the scan's first queue write, as it always was: a flagged board's last entries may lie where the copies do)
+                if (lane < 8 * kTotalsCopies) s_queue[kQueueCap - 8 * kTotalsCopies + lane] = 0;
 #endif
-            const uint32_t my_row = take_row(lane_m, board);
-            wave_phase_fence();
-            {
+            } else if (piece <= 3) {
+                // (the counters; the score block is written below, with the area bonus in it)
+                constexpr int kVecs = kCntWords / 4;
+                static_assert(kVecs > 128 && kVecs <= 192, "three pieces of 64 lanes clear the counters");
+                const int i = 64 * (piece - 1);
+                if (i + 64 <= kVecs || late_lane < kVecs - i) (reinterpret_cast<uint4*>(s_cnt) + lane)[i] = make_uint4(0u, 0u, 0u, 0u);
+            } else if (piece == 4) {
                 // stones per colour: a row reduction in registers (an atomicAdd of fifteen lanes on one word is turned by the compiler
                 // into a serial loop over those lanes)
-                uint32_t cnt = static_cast<uint32_t>(__popc(my_row & 0x7FFFu)) | (static_cast<uint32_t>(__popc(my_row >> 16)) << 16);
+                uint32_t cnt = static_cast<uint32_t>(__popc(late_row & 0x7FFFu)) | (static_cast<uint32_t>(__popc(late_row >> 16)) << 16);
                 cnt += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(cnt), 0x118, 0xF, 0xF, false));       // row_shr:8
                 cnt += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(cnt), 0x114, 0xF, 0xF, false));       // row_shr:4
                 cnt += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(cnt), 0x112, 0xF, 0xF, false));       // row_shr:2
                 cnt += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(cnt), 0x111, 0xF, 0xF, false));       // row_shr:1
-                if (lane_m == 15) s_misc[0] = cnt;                // lane 15 holds the sum of lanes 0 .. 15 (my_row is zero in lane 15)
-            }
-            {
+                if (late_lane == 15) s_misc[0] = cnt;             // lane 15 holds the sum of lanes 0 .. 15 (the row is zero in lane 15)
+            } else if (piece == 5) {
                 // Where is a colour's density count positive (<=> its weight positive: the +160 of Pattern.cpp:268)?  Wherever a stone
                 // of the colour lies under the 7x7 BlockWeights mask (Pattern.cpp:598-609) around the cell: the rows, dilated by the
                 // mask's row patterns -- 1001001 three rows away, 0111110 one and two rows away, 1110111 in the row itself -- and OR-ed
                 // over the seven rows, for both colours at once (black in the low, white in the high half word), restricted to empty cells.
-                const uint32_t r = my_row;
+                const uint32_t r = late_row;
                 // packed 16-bit shifts: nothing crosses from one half word into the other, so no masks.  Bit 15 of a row is zero (the planes'
                 // contract, include/gomoku_hip.h), so nothing comes down from it; what a left shift leaves there is cut off by `empty` below.
                 const v2u16 rr = __builtin_bit_cast(v2u16, r);
@@ -559,18 +560,32 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                 g |= static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, far, 0x113, 0xF, 0xF, true)) | static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, far, 0x103, 0xF, 0xF, true));       // rows y -+ 3
                 const uint32_t empty = ~(r | (r >> 16)) & 0x7FFFu;
                 if (lane < 15) s_rows[3 + lane] = r;            // (three zero rows on either side: the density gate of phase 3b reads rows y - 3 .. y + 3 unchecked)
+                late_gate = static_cast<int>(g & (empty | (empty << 16)));
+            } else if (piece <= 9) {
                 // The score block starts at the area bonus instead of zero: +160 in a colour's own view where its gate bit is set
                 // (Pattern.cpp:268), one 16-byte write per cell [white own, white opp, black opp, black own]; the gate word of the
                 // cell's row comes from that row's lane.
-                const int gate = static_cast<int>(g & (empty | (empty << 16)));
-    #pragma unroll
-                for (int pass = 0; pass < 4; ++pass) {
-                    const uint32_t gw = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(static_cast<int>((cell_row4 >> (8 * pass)) & 0xFFu), gate)) >> ((cell_col >> (8 * pass)) & 0xFFu);
-                    if (pass < 3 || lane < kCells - 192)
-                        reinterpret_cast<uint4*>(s_scores)[64 * pass + lane] = make_uint4(static_cast<uint32_t>(__builtin_amdgcn_sbfe(static_cast<int>(gw), 16, 1)) & 160u, 0u, 0u,
-                                                                                          static_cast<uint32_t>(__builtin_amdgcn_sbfe(static_cast<int>(gw), 0, 1)) & 160u);
-                }
+                const int pass = piece - 6;
+                const uint32_t gw = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(static_cast<int>((cell_row4 >> (8 * pass)) & 0xFFu), late_gate)) >> ((cell_col >> (8 * pass)) & 0xFFu);
+                if (pass < 3 || lane < kCells - 192)
+                    reinterpret_cast<uint4*>(s_scores)[64 * pass + lane] = make_uint4(static_cast<uint32_t>(__builtin_amdgcn_sbfe(static_cast<int>(gw), 16, 1)) & 160u, 0u, 0u,
+                                                                                      static_cast<uint32_t>(__builtin_amdgcn_sbfe(static_cast<int>(gw), 0, 1)) & 160u);
             }
+        };
+        constexpr int kLatePieces = 10;
+        static_assert(kLatePieces <= kScanSteps, "a piece per lookup");
+        if (live) {
+            // ---- phase 0, the part in front of the scan: take the two bit-planes (64 B), turn them into line words ----
+            // The lane masks of this phase come from a copy of the lane number that the compiler cannot see through: a compare per board each.  Hoisted
+            // out of the board loop they are scalar register pairs that do not fit and come back by two v_readlane each, per board.
+            int lane_m = lane;
+            asm volatile("" : "+v"(lane_m));
+            s_lines[lane] = line_init_lo;                       // (the all-blank line words wait in two registers, not in LDS: no read before the write)
+            if (lane_m < kLineWords - 64) s_lines[64 + lane] = line_init_hi;
+            if (lane_m < kMiscWords) s_misc[lane] = 0;
+            const uint32_t my_row = take_row(lane_m, board);
+            late_row = my_row; late_lane = lane_m;
+            wave_phase_fence();
             {
                 // a stone turns its cell's blank (3) into black (0) or white (1) in the four lines through it: one XOR each.
                 // Four lanes share a row (cells 0-3, 4-7, 8-11, 12-14), so the loop runs as long as the fullest quarter row.
@@ -608,22 +623,26 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
         if (live) {
             // ---- phase 1: walk the DFA along this lane's lines; transitions that emit go to the queue ----
             // The lane's one or two lines become ONE stream of 2-bit DFA symbols:
-            //   '?' cells '?' '?'  ['?' cells '?' '?']  '?' '?' ...
-            // (after "??" the automaton sits in its '?' self-loop state, which the next line's leading '?' keeps: no reset
-            // between the two lines).  The stream is kept shifted left by 2, so a step is: symbol * 4 = low word & 12, LDS
+            //   cells '?' '?'  [cells '?' '?']  '?' '?' ...
+            // walked from S, the state the root reaches on '?', and not from the root.  The root on '?' goes to S and emits nothing, S on '?' stays in S and
+            // emits nothing, and from every state "??" leads to S (scan_start_row checks all three when the image is built and refuses a table without them):
+            // a leading '?' in front of either line would be a lookup that reports nothing and changes nothing, so there is none -- seventeen steps where
+            // there were nineteen -- and there is no reset between the two lines.  BOTH trailing pads stay: of the 21 523 239 lines of 5 to 15 cells, 59 050
+            // report a match on the symbol behind the first trailing pad (a match ending one symbol back, found while falling back); sharing that symbol
+            // with the second line's first cell would put the first line's late match into a record of the second line.  The stream is kept shifted left by 2, so a step is: symbol * 4 = low word & 12, LDS
             // address = (previous word's next-row offset) | symbol * 4, one lookup.  Emitting transitions are queued raw
             // (record, lane, step); the slot is a ballot prefix (this wave is the only producer), decoding happens in phase 2.
             int n_queued = 0;                                       // wave-uniform
             if (phase_mask & 2) {
-                const int len_a = static_cast<int>(job_a & 31u) - 3, len_b = static_cast<int>(job_b & 31u) - 3;
+                const int len_a = static_cast<int>(job_a & 31u) - kSegPads, len_b = static_cast<int>(job_b & 31u) - kSegPads;
                 uint64_t syms = line_symbols(s_lines[(job_a >> 20) & 127u] >> norm_a, len_a);      // (a diagonal's word shifted down to its first cell)
-                syms |= line_symbols(s_lines[(job_b >> 20) & 127u] >> norm_b, len_b) << (2 * len_a + 6);
-                syms |= 0xAAAAAAAAAAAAAAAAull << (2 * (len_a + len_b) + 12);
+                syms |= line_symbols(s_lines[(job_b >> 20) & 127u] >> norm_b, len_b) << (2 * (len_a + kSegPads));
+                syms |= 0xAAAAAAAAAAAAAAAAull << (2 * (len_a + len_b + 2 * kSegPads));
                 // The stream is kept shifted left by 2: symbol s at bits 2 s + 2, so that the four bits from 2 s up are (symbol s - 1, symbol s) and
                 // one v_bfe + one v_bfi make the lookup address: (table word & 0x3FF3) | (those four bits & 12) -- the row offsets are multiples of 16.
                 const uint32_t cur = static_cast<uint32_t>(syms) << 2;        // symbols 0..14 at bits 2..31
                 const uint32_t rest = static_cast<uint32_t>(syms >> 28);      // symbols 15.. at bits 2.. (bits 0, 1: symbol 14)
-                uint32_t tw = 0;                                    // the previous step's table word (row 0 = root)
+                uint32_t tw = scan_start;                           // the previous step's table word: the row of the state behind a '?'
                 // The emission of step s is queued BEHIND the lookup of step s + 1 (the next address needs the table word only): the
                 // prefix count and the queue write then run in the shadow of that lookup's LDS round trip.  A queue entry is the table
                 // word itself with the low 17 bits (next row, kinds) replaced by lane | step << 6: the record number stays where it is.
@@ -651,13 +670,22 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                     const uint32_t addr = dfa_address(tw, four);
                     const uint32_t before = tw;
                     tw = *lds_word(addr);                       // (the table is at LDS address 0: the address is used as it is)
+                    if (step < kLatePieces) __builtin_amdgcn_sched_barrier(0);
                     if (step > 0) push(before, step - 1);
+                    // (a piece of phase 0 in this lookup's shadow, and held there: left to itself the compiler gathers the pieces in front of the scan again)
+                    if (step < kLatePieces) { late_piece(step); __builtin_amdgcn_sched_barrier(0); }
                 }
                 push(tw, kScanSteps - 1);
                 n_queued = static_cast<int>((q_at - q_base) >> 2);
                 if (q_at >= q_full) s_misc[2] = 1;                  // (flagged at kQueueCap - 64 = 384 entries: 2.0 x the 192 of the synthetic and dense test boards,
                                                                     //  1.14 x the 338 of the heaviest legal position a search found, DESIGN.md "K1's fixed capacities")
             }
+#ifdef GMK_PROFILE
+            else {                                                  // (profiling flavour, a mask without the scan: phase 0's pieces on their own)
+#pragma unroll
+                for (int piece = 0; piece < kLatePieces; ++piece) late_piece(piece);
+            }
+#endif
             wave_phase_fence();
             GMK_STAMP(2);
 
@@ -668,14 +696,14 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                     const uint32_t qe = qe_next;
                     qe_next = s_queue[min(m + 64, kQueueCap - 1)];      // (the next round's entry is on its way while this one is worked on;
                                                                          //  fetching its record and line jobs ahead as well measured no gain)
-                    // which line of which lane, and where on it (symbol 0 of a line's segment is its leading pad)
+                    // which line of which lane, and where on it (symbol 0 of a line's segment is its first cell; the two behind its last cell are pads)
                     const int src_lane = qe & 63, src_step = (qe >> 6) & 31;
                     const uint4 rec_now = s_rec[qe >> 17];
                     const uint32_t ja_now = s_jobs[src_lane * 2], jb_now = s_jobs[src_lane * 2 + 1];
                     const int seg_a = ja_now & 31u;
                     const bool second = src_step >= seg_a;
                     const uint32_t job = second ? jb_now : ja_now;
-                    const int pos = src_step - 1 - (second ? seg_a : 0);
+                    const int pos = src_step - (second ? seg_a : 0);
                     const int dir = (job >> 5) & 3, stride = (job >> 7) & 31;
                     const int cell_at = static_cast<int>((job >> 12) & 255u) + pos * stride;
                     deposit_match(rec_now.x, rec_now.y, cell_at, dir, -stride, s_scores, s_cnt, s_misc, my_totals);
@@ -989,18 +1017,18 @@ int lane_tables(uint32_t* jobs_out, uint32_t* pads_out, uint32_t* records_out) {
     for (int k = 4; k <= 24; ++k) { const int x0 = std::min(k, 14); lines.push_back({std::min(k, 28 - k) + 1, x0, k - x0, 3}); }
     std::stable_sort(lines.begin(), lines.end(), [](const LineJob& a, const LineJob& b) { return a.len > b.len; });
     uint32_t jobs[128];
-    for (uint32_t& j : jobs) j = 3u | (15u << 20);                // "no line": length 0 (three pads) on a line word that stays zero
+    for (uint32_t& j : jobs) j = static_cast<uint32_t>(kSegPads) | (15u << 20);                // "no line": length 0 (two pads) on a line word that stays zero
     auto pack = [](const LineJob& l) {
         const int line = l.dir == 0 ? l.y0 : l.dir == 1 ? kColBase + l.x0 : l.dir == 2 ? kDiagBase + l.x0 - l.y0 + 14 : kAntiBase + l.x0 + l.y0;
         const int stride = l.dir == 0 ? 1 : l.dir == 1 ? 15 : l.dir == 2 ? 16 : 14;
-        return static_cast<uint32_t>((l.len + 3) | (l.dir << 5) | (stride << 7) | ((l.y0 * 15 + l.x0) << 12) | (line << 20));
+        return static_cast<uint32_t>((l.len + kSegPads) | (l.dir << 5) | (stride << 7) | ((l.y0 * 15 + l.x0) << 12) | (line << 20));
     };
     int steps = 0;
     for (int lane = 0; lane < 64; ++lane) {
         jobs[lane * 2] = pack(lines[lane]);
-        int total = lines[lane].len + 3;
+        int total = lines[lane].len + kSegPads;
         const int extra = 64 + (63 - lane);                   // shortest leftovers ride behind the shortest primaries
-        if (extra < static_cast<int>(lines.size())) { jobs[lane * 2 + 1] = pack(lines[extra]); total += lines[extra].len + 3; }
+        if (extra < static_cast<int>(lines.size())) { jobs[lane * 2 + 1] = pack(lines[extra]); total += lines[extra].len + kSegPads; }
         steps = std::max(steps, total);
     }
     uint32_t init[kLineWords] = {};                              // every cell of every line blank (symbol 3)
@@ -1062,6 +1090,27 @@ int density_weights(int8_t* t /* kWtabWords * 4 bytes, zeroed */) {
     return GMK_OK;
 }
 
+// Where the scan starts and what lets a lane's stream do without leading pads (phase 1): the root on '?' emits nothing and goes to a state S;
+// S on '?' stays in S and emits nothing; from EVERY state "??" leads to S.  So a segment "cells ? ?" walked from S reports what "? cells ? ?"
+// reports from the root, and leaves the automaton in S for the lane's second segment.  row_out: the row offset of S, the table word the scan
+// starts from.  A table without these properties is an error, not a slower path.
+int scan_start_row(const gmk::DeviceTables& t, uint32_t* row_out) {
+    constexpr uint32_t kPad = 2;                                  // '?' in the device's symbol codes
+    const std::vector<uint32_t>& tr = t.dev_trans;
+    const uint32_t n = static_cast<uint32_t>(t.n_states);
+    if (n == 0 || tr.size() != static_cast<size_t>(n) * 4) { gmk::set_error("K1 scan: no automaton"); return GMK_ERR_STATE; }
+    const uint32_t first = tr[kPad], start = gmk::dev_trans_row(first);
+    if (gmk::dev_trans_record(first) != 0 || start % 16 != 0 || start / 16 >= n) { gmk::set_error("K1 scan: the root emits on '?' or leaves the table"); return GMK_ERR_STATE; }
+    const uint32_t loop = tr[start / 4 + kPad];
+    if (gmk::dev_trans_record(loop) != 0 || gmk::dev_trans_row(loop) != start) { gmk::set_error("K1 scan: state %u does not loop on '?' without emitting", start / 16); return GMK_ERR_STATE; }
+    for (uint32_t s = 0; s < n; ++s) {
+        const uint32_t mid = gmk::dev_trans_row(tr[s * 4 + kPad]);
+        if (mid % 16 != 0 || mid / 16 >= n || gmk::dev_trans_row(tr[mid / 4 + kPad]) != start) { gmk::set_error("K1 scan: \"??\" from state %u does not lead to state %u", s, start / 16); return GMK_ERR_STATE; }
+    }
+    *row_out = start;
+    return GMK_OK;
+}
+
 // The image of the kernel's tables (see kLaneRecordVecs): [automaton][records][lane jobs 128][pads][bits-to-bytes 512][weights][hand-out 4], then the lane
 // records.  Built once; the automaton and the records are copied from the device state's tables.
 int build_stage_image(const gmk::DeviceState& st, uint4** d_out, int* stage_vecs) {
@@ -1074,6 +1123,8 @@ int build_stage_image(const gmk::DeviceState& st, uint4** d_out, int* stage_vecs
     rc = density_weights(reinterpret_cast<int8_t*>(wtab));
     if (rc != GMK_OK) return rc;
     handout[0] = 2u * kBoardsPerBlock;
+    rc = scan_start_row(gmk::production_automaton().device(), &handout[1]);
+    if (rc != GMK_OK) return rc;
     const size_t staged_words = trans_words + record_words + kStaticTableWords;
     if (staged_words % 4 != 0) { gmk::set_error("K1 tables: %zu staged words are not whole 16-byte pieces", staged_words); return GMK_ERR_STATE; }
     uint32_t* d = nullptr;
