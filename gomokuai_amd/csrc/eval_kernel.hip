@@ -20,8 +20,8 @@
 //     bonus) comes from the rows dilated by the three row patterns of the 7x7 mask, with DPP row shifts; the score block -- [cell][4 groups] in
 //     LDS -- is written ONCE, with the bonus in it;
 //   * phase 1: the 72 lines that can hold a pattern (>= 5 cells) are spread over the 64 lanes (the 8 shortest ride
-//     behind the shortest primaries: 17 steps per lane, fully unrolled); a lane's lines are one stream of 2-bit symbols without leading pads,
-//     walked from the state the root reaches on '?'; a step is one LDS lookup, and the first ten carry a piece of phase 0 in their shadow; emitting transitions are queued by ballot prefix, in the shadow of the next step's lookup (the queue's fill
+//     behind the shortest primaries: 17 symbols per lane, fully unrolled); a lane's lines are one stream of 2-bit symbols without leading pads,
+//     walked from the state the root reaches on '?'; the first four symbols are one read of a 256-entry table, every further one is one LDS lookup: 14 round trips, and the first ten carry a piece of phase 0 in their shadow; emitting transitions are queued by ballot prefix, in the shadow of the next step's lookup (the queue's fill
 //     level lives on the scalar unit, clamped there: no per-lane bounds check);
 //   * phase 2: one lane per queued transition: one 16-byte record read gives the (<= 2) matches, each with a
 //     compact list of <= 4 score deposits -- a colour's own and opponent view of a cell are the halves of one 64-bit word, so a deposit is ONE
@@ -31,7 +31,7 @@
 //     the density gate "count >= 2" from seven row popcounts, the compound decision in closed form (components n, threes s), +-600 deposits,
 //     components queued by ballot prefix with their line word and slot in the entry;
 //   * phase 4: seven lanes per compound component, nine per round: its counter-move cells from the 13-symbol window around it (one
-//     v_alignbit of the line word with its '?' pads);
+//     v_alignbit of the line word with its '?' pads), walked as one read of the root's four-symbol prefix table and three or four lookups;
 //   * phase 5: the 3.6 KB score block leaves LDS transposed to [group][cell]: sixteen non-temporal dword stores of 256 contiguous bytes, in
 //     ADDRESS order (the two parts of a cache line that two pieces share reach the L2 back to back);
 //   * phase D, once per group, by the wavefront that is handed board 12 k of its workgroup's run for the run's k-th group: the density planes of the
@@ -41,12 +41,16 @@
 //     sixteen boards all exist (every group but the last of a launch whose board count is not a multiple of sixteen) stores without guards, one
 //     straight-line block per pass: per pair of stores three vector instructions (the occupied bit, two XORs) and two scalar ones (the board's
 //     block added to a 64-bit scalar base: global_store_dword offset, value, s[base]); the occupied bits come from 7 x 16 words the burst puts
-//     in LDS once (two 16-byte reads per pass).  Everything the prologue reads is one image the host builds once: 23 KB staged 16 bytes per lane, 32 bytes of constants per lane, all loads issued at once.
+//     in LDS once (two 16-byte reads per pass).  Everything the prologue reads is one image the host builds once: 24 KB staged 16 bytes per lane, 32 bytes of constants per lane, all loads issued at once.
 // HBM traffic per board: 64 B in, 7 248 B out (7 312 B algorithmic); everything else stays on chip.
 // Round 11 (profiles/r11_k1_*) shortened each board's chain of dependent LDS round trips: the scan lost its two leading-pad steps
 // (19 -> 17: -1.3 % of the launch on its own), and what phase 0 writes for phase 2 and later moved out of the way of the line words into the scan's
 // first lookups (-0.5 % on top).  Asking for the next hand-out behind phase 5's block reads and fetching the next deposit round's record and jobs
 // ahead were built, measured as no gain (+0.3 % and +-0.1 %) and are not in the source.
+// Round 12 (profiles/r12_k1_*) took lookups whose reports nobody uses out of the same chain: the scan's first four symbols are cells, and no four cells
+// from its start state report a match, so they are one 16-bit read of a 256-entry table of the row they lead to (14 round trips where there were 17, four
+// ballots and pushes fewer: -1.6 % of the launch on its own); a rescan lane's first four symbols from the root are one read of DeviceTables::dev_prefix4,
+// as in K2's window matcher (5 reads where there were 8: -1.2 % on its own); together -3.3 %.  Both tables are staged with the others (+1 KB of LDS).
 #include <algorithm>
 #include <cstdlib>
 #include <vector>
@@ -87,14 +91,16 @@ constexpr int kMiscWords = 48;                   // [0] stones black | white << 
                                                  // [19..33] the rows (black | white << 16) between three zero rows on either side ([16..18], [34..36])
 constexpr int kBoardWords = kZeroWords + kLineWords + kQueueCap + kMiscWords;
 static_assert(kZeroWords % 4 == 0 && kBoardWords % 4 == 0, "16-byte alignment of the per-board blocks");
-constexpr int kStaticTableWords = 128 + kLineWords + 512 + 1560 + 4;   // lane jobs, the lines' '?' pads (phase 4), the bits-to-bytes table, the weight table of phase D,
-                                                                        // and the workgroup's hand-out counter (four words: [0] the counter, [1] the row the scan starts from, read from the image, never from LDS)
+constexpr int kPrefixTableWords = gmk::kPrefixWords;   // a table of the row reached over four symbols: 256 entries of 16 bits, key s0 | s1 << 2 | s2 << 4 | s3 << 6
+constexpr int kStaticTableWords = 128 + kLineWords + 512 + 1560 + 2 * kPrefixTableWords + 4;   // lane jobs, the lines' '?' pads (phase 4), the bits-to-bytes table, the weight table of phase D,
+                                                                        // the two prefix tables (from S for the scan, from the root for the rescans: DeviceTables::dev_prefix4),
+                                                                        // and the workgroup's hand-out counter (four words: [0] the counter, [1] the row of S, the state the scan's prefix table is walked from: the host's note, no kernel reads it)
 
 // Lane -> line jobs.  A job word holds what the scan and the deposits need of a line, ready to use: bits 0..4 symbols in its stream
 // segment (len + 2: its cells and two trailing pads), 5..6 dir, 7..11 cell stride, 12..19 its first cell, 20..26 line word index.
 // Everything a launch reads besides the boards is ONE image in device memory that the host builds once (build_stage_image): first what every workgroup
 // stages in LDS, in LDS order and ready to use -- the automaton, the emission records, the lane jobs, the lines' '?' pads, the bits-to-bytes table, the
-// weight table of phase D, the hand-out counter's start value and the scan's start row -- copied 16 bytes per lane; behind it a 32-byte record per lane with what the prologue
+// weight table of phase D, the two four-symbol prefix tables (phases 1 and 4), the hand-out counter's start value and the row of the scan's start state -- copied 16 bytes per lane; behind it a 32-byte record per lane with what the prologue
 // would otherwise derive from the lane number: its two jobs, its two all-blank line words ((1 << 2 len) - 1: words lane and 64 + lane), then [0] row * 4
 // and [1] column of the lane's cell in each of the four passes over the board (cell = 64 pass + lane, the last one clamped to 224), a byte per pass, and
 // [2], [3] where the first cell of the lane's two lines sits in its line word (bit 2 x0 for a diagonal, 2 y0 for an anti-diagonal, 0 for rows and columns).
@@ -103,6 +109,7 @@ constexpr int kStaticTableWords = 128 + kLineWords + 512 + 1560 + 4;   // lane j
 constexpr int kLaneRecordVecs = 2;
 constexpr int kSegPads = 2;                       // the '?' behind a line's cells in its stream segment (none in front: phase 1 says why)
 constexpr int kScanSteps = 17;                    // symbols in the longest lane stream (lane_tables checks it)
+constexpr int kScanPrefixSyms = 4;                // of them, the leading ones that one read of the scan's prefix table stands for (lane_tables checks that they are cells)
 
 __device__ __forceinline__ int dir_stride(int dir) { return (0x0E100F01u >> (8 * dir)) & 0xFFu; }      // 1, 15, 16, 14: a shift, not three branches
 
@@ -119,6 +126,11 @@ __device__ __forceinline__ uint64_t line_symbols(uint32_t line_word, int len) {
 // the 32-bit word at a byte address of LDS (no base added: the staged automaton starts at address 0)
 __device__ __forceinline__ const __attribute__((address_space(3))) uint32_t* lds_word(uint32_t byte_address) {
     return reinterpret_cast<const __attribute__((address_space(3))) uint32_t*>(static_cast<uintptr_t>(byte_address));
+}
+
+// ... and the 16-bit one (an entry of a prefix table)
+__device__ __forceinline__ const __attribute__((address_space(3))) uint16_t* lds_half(uint32_t byte_address) {
+    return reinterpret_cast<const __attribute__((address_space(3))) uint16_t*>(static_cast<uintptr_t>(byte_address));
 }
 
 __device__ __forceinline__ __attribute__((address_space(3))) uint32_t* lds_word_rw(uint32_t byte_address) {
@@ -418,20 +430,20 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
     uint32_t* s_jobs = lds + trans_words + record_words;
 
     // the loads of the prologue, all of them in front of their first use: the staged image (two pieces of 16 bytes per lane cover 32 KB; the
-    // automaton's image is 23 KB) and this lane's record
+    // automaton's image is 24 KB) and this lane's record
     const int tid = threadIdx.x;
     const uint4 stage_a = g_stage[min(tid, stage_vecs - 1)], stage_b = g_stage[min(tid + kThreads, stage_vecs - 1)];
     const uint4* lane_record = g_stage + stage_vecs + kLaneRecordVecs * (tid & 63);
     const uint4 lane_lines = lane_record[0], lane_consts = lane_record[1];
-    // the table word the scan starts from: the row the root reaches on '?' (the word behind the hand-out counter's start value in the image; a
-    // wave-uniform address, so a scalar load)
-    const uint32_t scan_start = reinterpret_cast<const uint32_t*>(g_stage)[trans_words + record_words + kStaticTableWords - 3];
     uint32_t* s_pads = s_jobs + 128;                                         // a line word's '?' pads: symbol 2 in every 2-bit slot of the word that is not one of the
                                                                              // line's cells (phase 4 ORs them in: its window then reads '?' off the line wherever the line starts in its word)
     uint2* s_lut = reinterpret_cast<uint2*>(s_jobs + 128 + kLineWords);      // byte -> its eight bits as bytes (the stone operands of phase D)
     uint32_t* s_wtab_words = s_jobs + 128 + kLineWords + 512;
     const v4i* s_wtab = reinterpret_cast<const v4i*>(s_wtab_words);
-    uint32_t* s_handout = s_wtab_words + kWtabWords;        // [0] boards handed out: starts at 2 x kBoardsPerBlock (every wavefront's first two boards are its own: see below)
+    // the prefix tables' byte addresses (the kernel's LDS starts at address 0): the scan's, walked from S, and behind it the rescans', walked from the root
+    const uint32_t scan_prefix_at = static_cast<uint32_t>(trans_words + record_words + 128 + kLineWords + 512 + kWtabWords) * 4u;
+    const uint32_t root_prefix_at = scan_prefix_at + 4u * kPrefixTableWords;
+    uint32_t* s_handout = s_wtab_words + kWtabWords + 2 * kPrefixTableWords;        // [0] boards handed out: starts at 2 x kBoardsPerBlock (every wavefront's first two boards are its own: see below)
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane0 = threadIdx.x & 63;
     uint32_t* s_scores = lds + trans_words + record_words + kStaticTableWords + wave * kBoardWords;      // int32 scores, accumulated with ds_add
@@ -573,7 +585,7 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
             }
         };
         constexpr int kLatePieces = 10;
-        static_assert(kLatePieces <= kScanSteps, "a piece per lookup");
+        static_assert(kLatePieces <= kScanSteps - kScanPrefixSyms + 1, "a piece per lookup");
         if (live) {
             // ---- phase 0, the part in front of the scan: take the two bit-planes (64 B), turn them into line words ----
             // The lane masks of this phase come from a copy of the lane number that the compiler cannot see through: a compare per board each.  Hoisted
@@ -642,7 +654,6 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                 // one v_bfe + one v_bfi make the lookup address: (table word & 0x3FF3) | (those four bits & 12) -- the row offsets are multiples of 16.
                 const uint32_t cur = static_cast<uint32_t>(syms) << 2;        // symbols 0..14 at bits 2..31
                 const uint32_t rest = static_cast<uint32_t>(syms >> 28);      // symbols 15.. at bits 2.. (bits 0, 1: symbol 14)
-                uint32_t tw = scan_start;                           // the previous step's table word: the row of the state behind a '?'
                 // The emission of step s is queued BEHIND the lookup of step s + 1 (the next address needs the table word only): the
                 // prefix count and the queue write then run in the shadow of that lookup's LDS round trip.  A queue entry is the table
                 // word itself with the low 17 bits (next row, kinds) replaced by lane | step << 6: the record number stays where it is.
@@ -664,16 +675,26 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                         q_at = min(q_at + 4u * static_cast<uint32_t>(__popcll(emitters)), q_full);
                     }
                 };
+                // The first four symbols are cells of the lane's first line (every first line has five or more), and no walk of four cells from S
+                // reports anything (scan_prefix_table checks all 81 when the image is built): ONE 16-bit read of the row S reaches over them, at
+                // table + 2 * (the stream's first eight bits), stands for four lookups, ballots and pushes -- fourteen dependent round trips where
+                // there were seventeen.  `cur` is the stream shifted left by 2 with bit 1 clear, so twice the key is its bits 1..9 (at most 510:
+                // the read cannot leave the table).  The pushes keep their steps' numbers, 4..16: the queue is what seventeen lookups would leave.
+                uint32_t tw = *lds_half(scan_prefix_at + __builtin_amdgcn_ubfe(cur, 1, 9));      // the previous step's table word (here a bare row offset)
+                __builtin_amdgcn_sched_barrier(0);
+                late_piece(0);
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int step = 0; step < kScanSteps; ++step) {
+                for (int step = kScanPrefixSyms; step < kScanSteps; ++step) {
+                    const int nth = step - kScanPrefixSyms + 1;         // which lookup of the scan this is, the prefix read being the first
                     const uint32_t four = step < 15 ? __builtin_amdgcn_ubfe(cur, 2 * step, 4) : __builtin_amdgcn_ubfe(rest, 2 * (step - 15), 4);
                     const uint32_t addr = dfa_address(tw, four);
                     const uint32_t before = tw;
                     tw = *lds_word(addr);                       // (the table is at LDS address 0: the address is used as it is)
-                    if (step < kLatePieces) __builtin_amdgcn_sched_barrier(0);
-                    if (step > 0) push(before, step - 1);
+                    if (nth < kLatePieces) __builtin_amdgcn_sched_barrier(0);
+                    if (step > kScanPrefixSyms) push(before, step - 1);
                     // (a piece of phase 0 in this lookup's shadow, and held there: left to itself the compiler gathers the pieces in front of the scan again)
-                    if (step < kLatePieces) { late_piece(step); __builtin_amdgcn_sched_barrier(0); }
+                    if (nth < kLatePieces) { late_piece(nth); __builtin_amdgcn_sched_barrier(0); }
                 }
                 push(tw, kScanSteps - 1);
                 n_queued = static_cast<int>((q_at - q_base) >> 2);
@@ -858,7 +879,7 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
             //      the cell with a blank there (Compound::updateAntis, Pattern.cpp:520-543), scanning the 13-symbol window
             //      centred on the cell.  Such a match ends at window index 6..12; seven lanes share a component (nine components
             //      per round, lane 63 idle), lane kk looks at the transition at index 6 + kk only (the automaton forgets its start
-            //      state after 7 symbols, so <= 8 lookups from the root bring it to the right state), and the lowest lane with a hit applies it ----
+            //      state after 7 symbols, so <= 8 symbols from the root bring it to the right state: one read of the root's prefix table and <= 4 lookups), and the lowest lane with a hit applies it ----
             if (phase_mask & 16) {
                 const int n_comp = n_comp_q;
                 int lane_4 = lane;                                  // (an opaque copy: the lane's place is derived here, not kept in registers
@@ -880,10 +901,16 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                         const int first = static_cast<int>((ent >> 20) & 15u) + start - 6;                  // -6 .. 13
                         const uint32_t cur = __builtin_amdgcn_alignbit(first >= 0 ? 0xAAAAAAAAu : word, first >= 0 ? word : 0xAAAAAAAAu,
                                                                        static_cast<uint32_t>(2 * first) & 31u) << 2;      // kept shifted left by 2 as in phase 1
-                        uint32_t tw = 0;
+                        // Only the last transition's report is used, so the first four symbols from the root ('?' among them) are ONE read of
+                        // DeviceTables::dev_prefix4, as in the incremental evaluator's window matcher (evalstate_device.h); four ordinary lookups
+                        // follow, of which the lane of window index 6 (started at index 0 like that of index 7) keeps the third's word.
+                        uint32_t tw = *lds_half(root_prefix_at + __builtin_amdgcn_ubfe(cur, 1, 9)), tw_third = 0;
     #pragma unroll
-                        for (int i = 0; i < 8; ++i)
-                            if (start + i <= k) tw = *lds_word(dfa_address(tw, __builtin_amdgcn_ubfe(cur, 2 * i, 4)));      // v_bfe + v_bfi, as in phase 1
+                        for (int i = 4; i < 8; ++i) {
+                            if (i == 7) tw_third = tw;
+                            tw = *lds_word(dfa_address(tw, __builtin_amdgcn_ubfe(cur, 2 * i, 4)));      // v_bfe + v_bfi, as in phase 1
+                        }
+                        if (kk == 0) tw = tw_third;
                         if ((gmk::dev_trans_kinds(tw) >> tslot) & 1u) {                     // the record holds the wanted type
                             const uint4 rec = s_rec[gmk::dev_trans_record(tw)];
                             const int want = 5 - tslot;                                     // LiveThree 5, DeadThree 4, LiveTwo 3
@@ -1026,6 +1053,7 @@ int lane_tables(uint32_t* jobs_out, uint32_t* pads_out, uint32_t* records_out) {
     int steps = 0;
     for (int lane = 0; lane < 64; ++lane) {
         jobs[lane * 2] = pack(lines[lane]);
+        if (lines[lane].len < kScanPrefixSyms) { gmk::set_error("lane jobs: lane %d starts with a line of %d cells, the scan's prefix read takes %d", lane, lines[lane].len, kScanPrefixSyms); return GMK_ERR_STATE; }
         int total = lines[lane].len + kSegPads;
         const int extra = 64 + (63 - lane);                   // shortest leftovers ride behind the shortest primaries
         if (extra < static_cast<int>(lines.size())) { jobs[lane * 2 + 1] = pack(lines[extra]); total += lines[extra].len + kSegPads; }
@@ -1111,20 +1139,56 @@ int scan_start_row(const gmk::DeviceTables& t, uint32_t* row_out) {
     return GMK_OK;
 }
 
-// The image of the kernel's tables (see kLaneRecordVecs): [automaton][records][lane jobs 128][pads][bits-to-bytes 512][weights][hand-out 4], then the lane
+// The scan's prefix table: entry s0 | s1 << 2 | s2 << 4 | s3 << 6 is the row offset S (`start`, from scan_start_row) reaches over those four symbols.
+// The scan reads it in place of its first four lookups and queues nothing for them, which is right only if none of the 3^4 walks over four CELL
+// symbols (black 0, white 1, blank 3: a lane's first four symbols are cells, lane_tables) reports anything on any of its transitions.  With the
+// production table none does, and 24 of the 243 walks over five cells do: four is the limit (tests/test_eval_scan_prefix.py).  A table where a walk
+// over four does report is an error, not a slower path.
+// (The root's table, DeviceTables::dev_prefix4, cannot serve: S is not the root, and 30 of the 256 keys end elsewhere from it.)
+int scan_prefix_table(const gmk::DeviceTables& t, uint32_t start, uint16_t* out /* 256 entries */) {
+    const std::vector<uint32_t>& tr = t.dev_trans;
+    for (uint32_t key = 0; key < 256; ++key) {
+        uint32_t row = start;
+        bool cells = true, reports = false;
+        for (int i = 0; i < kScanPrefixSyms; ++i) {
+            const uint32_t sym = (key >> (2 * i)) & 3u;
+            if (row % 16 != 0 || row / 4 + sym >= tr.size()) { gmk::set_error("K1 scan prefix: a walk from state %u leaves the table", start / 16); return GMK_ERR_STATE; }
+            const uint32_t tw = tr[row / 4 + sym];
+            cells = cells && sym != 2u;
+            reports = reports || gmk::dev_trans_record(tw) != 0;
+            row = gmk::dev_trans_row(tw);
+        }
+        if (cells && reports) { gmk::set_error("K1 scan prefix: the cells of key 0x%02x report a match within four symbols of state %u", key, start / 16); return GMK_ERR_STATE; }
+        out[key] = static_cast<uint16_t>(row);
+    }
+    return GMK_OK;
+}
+
+// The image of the kernel's tables (see kLaneRecordVecs): [automaton][records][lane jobs 128][pads][bits-to-bytes 512][weights][scan prefix 128][root prefix 128][hand-out 4], then the lane
 // records.  Built once; the automaton and the records are copied from the device state's tables.
 int build_stage_image(const gmk::DeviceState& st, uint4** d_out, int* stage_vecs) {
     const size_t trans_words = static_cast<size_t>(st.n_states) * 4, record_words = static_cast<size_t>(st.n_records) * 4;
     std::vector<uint32_t> rest(kStaticTableWords + 64 * 4 * kLaneRecordVecs, 0u);
-    uint32_t* jobs = rest.data(), *pads = jobs + 128, *lut = pads + kLineWords, *wtab = lut + 512, *handout = wtab + kWtabWords, *records = handout + 4;
+    uint32_t* jobs = rest.data(), *pads = jobs + 128, *lut = pads + kLineWords, *wtab = lut + 512, *scan_prefix = wtab + kWtabWords, *root_prefix = scan_prefix + kPrefixTableWords,
+              *handout = root_prefix + kPrefixTableWords, *records = handout + 4;
     int rc = lane_tables(jobs, pads, records);
     if (rc != GMK_OK) return rc;
     for (uint32_t b = 0; b < 256; ++b) { lut[2 * b] = ((b & 15u) * 0x204081u) & 0x01010101u; lut[2 * b + 1] = ((b >> 4) * 0x204081u) & 0x01010101u; }
     rc = density_weights(reinterpret_cast<int8_t*>(wtab));
     if (rc != GMK_OK) return rc;
     handout[0] = 2u * kBoardsPerBlock;
-    rc = scan_start_row(gmk::production_automaton().device(), &handout[1]);
+    const gmk::DeviceTables& tables = gmk::production_automaton().device();
+    rc = scan_start_row(tables, &handout[1]);
     if (rc != GMK_OK) return rc;
+    // the two prefix tables, 256 entries of 16 bits each, two entries to a word: the scan's from S, the rescans' from the root
+    uint16_t halves[256];
+    rc = scan_prefix_table(tables, handout[1], halves);
+    if (rc != GMK_OK) return rc;
+    if (tables.dev_prefix4.size() != 256) { gmk::set_error("K1 tables: no four-symbol prefix table of the root"); return GMK_ERR_STATE; }
+    for (int i = 0; i < kPrefixTableWords; ++i) {
+        scan_prefix[i] = static_cast<uint32_t>(halves[2 * i]) | static_cast<uint32_t>(halves[2 * i + 1]) << 16;
+        root_prefix[i] = static_cast<uint32_t>(tables.dev_prefix4[2 * i]) | static_cast<uint32_t>(tables.dev_prefix4[2 * i + 1]) << 16;
+    }
     const size_t staged_words = trans_words + record_words + kStaticTableWords;
     if (staged_words % 4 != 0) { gmk::set_error("K1 tables: %zu staged words are not whole 16-byte pieces", staged_words); return GMK_ERR_STATE; }
     uint32_t* d = nullptr;
