@@ -532,7 +532,7 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
         // its first lookups (late_piece): LDS serves a wavefront in order, so in front of the line words those seven wide writes (~13 cycles each on the
         // store path) and four ds_bpermute stood between every board and its first lookup.
         uint32_t late_row = 0;
-        int late_lane = lane, late_gate = 0;
+        int late_lane = lane, late_gate = 0, late_gw = 0;         // (late_gw: the gate word the next score-block piece uses, asked for one lookup ahead)
         auto late_piece = [&](int piece) {
             if (piece == 0) {
 #ifndef GMK_K1_TOTALS_HOT
@@ -573,15 +573,23 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                 const uint32_t empty = ~(r | (r >> 16)) & 0x7FFFu;
                 if (lane < 15) s_rows[3 + lane] = r;            // (three zero rows on either side: the density gate of phase 3b reads rows y - 3 .. y + 3 unchecked)
                 late_gate = static_cast<int>(g & (empty | (empty << 16)));
+                // (the first score-block piece's gate word: asked for here, one lookup ahead of its use, see below)
+                late_gw = __builtin_amdgcn_ds_bpermute(static_cast<int>(cell_row4 & 0xFFu), late_gate);
             } else if (piece <= 9) {
                 // The score block starts at the area bonus instead of zero: +160 in a colour's own view where its gate bit is set
                 // (Pattern.cpp:268), one 16-byte write per cell [white own, white opp, black opp, black own]; the gate word of the
-                // cell's row comes from that row's lane.
+                // cell's row comes from that row's lane.  The ds_bpermute that fetches it is issued by the piece BEFORE, behind that piece's own write: it
+                // then comes back ahead of the lookup this step waits for anyway.  Issued here it came back behind that lookup, and the wait in front of
+                // the next lookup's address covered it, the queue write and the lookup together.
+                // No lane mask on the fourth write, so that the wait behind it is a counted one: its 31 lanes behind the last cell fetch the gate word
+                // of lane 16, which holds no row and is zero on every board (lane_tables), and write 16 bytes of zeros onto the first counter words,
+                // which the pieces before have cleared and nobody has counted into yet.
                 const int pass = piece - 6;
-                const uint32_t gw = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(static_cast<int>((cell_row4 >> (8 * pass)) & 0xFFu), late_gate)) >> ((cell_col >> (8 * pass)) & 0xFFu);
-                if (pass < 3 || lane < kCells - 192)
-                    reinterpret_cast<uint4*>(s_scores)[64 * pass + lane] = make_uint4(static_cast<uint32_t>(__builtin_amdgcn_sbfe(static_cast<int>(gw), 16, 1)) & 160u, 0u, 0u,
-                                                                                      static_cast<uint32_t>(__builtin_amdgcn_sbfe(static_cast<int>(gw), 0, 1)) & 160u);
+                const uint32_t gw = static_cast<uint32_t>(late_gw) >> ((cell_col >> (8 * pass)) & 0xFFu);
+                static_assert(4 * 256 - kScoreWords <= kCntWords, "the fourth write's lanes behind the last cell land on counter words");
+                reinterpret_cast<uint4*>(s_scores)[64 * pass + lane] = make_uint4(static_cast<uint32_t>(__builtin_amdgcn_sbfe(static_cast<int>(gw), 16, 1)) & 160u, 0u, 0u,
+                                                                                  static_cast<uint32_t>(__builtin_amdgcn_sbfe(static_cast<int>(gw), 0, 1)) & 160u);
+                if (pass < 3) late_gw = __builtin_amdgcn_ds_bpermute(static_cast<int>((cell_row4 >> (8 * (pass + 1))) & 0xFFu), late_gate);
             }
         };
         constexpr int kLatePieces = 10;
@@ -654,8 +662,8 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                 // one v_bfe + one v_bfi make the lookup address: (table word & 0x3FF3) | (those four bits & 12) -- the row offsets are multiples of 16.
                 const uint32_t cur = static_cast<uint32_t>(syms) << 2;        // symbols 0..14 at bits 2..31
                 const uint32_t rest = static_cast<uint32_t>(syms >> 28);      // symbols 15.. at bits 2.. (bits 0, 1: symbol 14)
-                // The emission of step s is queued BEHIND the lookup of step s + 1 (the next address needs the table word only): the
-                // prefix count and the queue write then run in the shadow of that lookup's LDS round trip.  A queue entry is the table
+                // The emission of step s is worked out BEHIND the lookup of step s + 1 (the next address needs the table word only): the
+                // prefix count runs in the shadow of that lookup's LDS round trip; the write follows behind lookup s + 2 (below).  A queue entry is the table
                 // word itself with the low 17 bits (next row, kinds) replaced by lane | step << 6: the record number stays where it is.
                 // Where the queue stands is a byte address kept by the scalar unit; a lane adds its prefix count (the vector unit is
                 // what this kernel is bound by: 4 cycles per wave-instruction on a SIMD whatever the lanes do).
@@ -664,16 +672,23 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                 // lanes add, without a per-lane clamp (a vector instruction per step); a board that gets there is flagged below.
                 const uint32_t q_full = q_base + 4u * (kQueueCap - 64);
                 uint32_t q_at = q_base;                             // wave-uniform
+                // A step's queue write is DEFERRED by one lookup more: `push` only works out a lane's address and entry (in the shadow of lookup s + 1) and
+                // `flush` writes them immediately behind lookup s + 2, one instruction after it.  The write is conditional, so the compiler's wait in front
+                // of the next lookup's address is lgkmcnt(0) wherever a path around a write exists, and LDS answers a wavefront in order: written where it
+                // was worked out, five vector instructions behind the lookup, the write's acknowledgement stood on every step's chain.  (Every lane writing,
+                // the idle ones into 64 dump words, makes the waits counted at the price of a v_cndmask per step and measured less: DESIGN.md, round 13.)
+                uint32_t pend_at = 0, pend_entry = 0;
+                bool pend = false;
+                auto flush = [&]() { if (pend) *lds_word_rw(pend_at) = pend_entry; };
                 auto push = [&](uint32_t word, int step) {
                     const bool emits = word > 0x1FFFFu;
                     const unsigned long long emitters = __ballot(emits);
-                    if (emitters) {
-                        if (emits) {
-                            const uint32_t ahead = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(emitters >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(emitters), 0u));
-                            *lds_word_rw(q_at + 4u * ahead) = (word & ~0x1FFFFu) | (static_cast<uint32_t>(lane) | static_cast<uint32_t>(step) << 6);
-                        }
-                        q_at = min(q_at + 4u * static_cast<uint32_t>(__popcll(emitters)), q_full);
-                    }
+                    const uint32_t ahead = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(emitters >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(emitters), 0u));
+                    pend = emits;
+                    pend_at = q_at + 4u * ahead;
+                    pend_entry = (word & ~0x1FFFFu) | (static_cast<uint32_t>(lane) | static_cast<uint32_t>(step) << 6);
+                    asm volatile("" : "+v"(pend_at), "+v"(pend_entry));       // (worked out HERE: left to itself the compiler sinks both to where they are written)
+                    q_at = min(q_at + 4u * static_cast<uint32_t>(__popcll(emitters)), q_full);
                 };
                 // The first four symbols are cells of the lane's first line (every first line has five or more), and no walk of four cells from S
                 // reports anything (scan_prefix_table checks all 81 when the image is built): ONE 16-bit read of the row S reaches over them, at
@@ -691,12 +706,15 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                     const uint32_t addr = dfa_address(tw, four);
                     const uint32_t before = tw;
                     tw = *lds_word(addr);                       // (the table is at LDS address 0: the address is used as it is)
-                    if (nth < kLatePieces) __builtin_amdgcn_sched_barrier(0);
+                    flush();                                    // (the entries of step - 2, back to back with the lookup and held there)
+                    __builtin_amdgcn_sched_barrier(0);
                     if (step > kScanPrefixSyms) push(before, step - 1);
                     // (a piece of phase 0 in this lookup's shadow, and held there: left to itself the compiler gathers the pieces in front of the scan again)
                     if (nth < kLatePieces) { late_piece(nth); __builtin_amdgcn_sched_barrier(0); }
                 }
+                flush();                                        // (the last two steps' entries: no lookup left to stand behind)
                 push(tw, kScanSteps - 1);
+                flush();
                 n_queued = static_cast<int>((q_at - q_base) >> 2);
                 if (q_at >= q_full) s_misc[2] = 1;                  // (flagged at kQueueCap - 64 = 384 entries: 2.0 x the 192 of the synthetic and dense test boards,
                                                                     //  1.14 x the 338 of the heaviest legal position a search found, DESIGN.md "K1's fixed capacities")
@@ -1068,6 +1086,9 @@ int lane_tables(uint32_t* jobs_out, uint32_t* pads_out, uint32_t* records_out) {
         uint32_t row4 = 0, col = 0;
         for (int pass = 0; pass < 4; ++pass) {
             const int c = std::min(64 * pass + lane, kCells - 1);
+            // (behind the last cell: the gate word of lane 16, which holds no row and is zero on every board -- the 16 bytes such a lane writes
+            // are zeros on the first counter words, which are zero there: phase 0's fourth score-block write needs no lane mask)
+            if (64 * pass + lane >= kCells) { row4 |= static_cast<uint32_t>(4 * 16) << (8 * pass); continue; }
             row4 |= static_cast<uint32_t>(4 * (c / 15)) << (8 * pass);
             col |= static_cast<uint32_t>(c % 15) << (8 * pass);
         }
