@@ -575,6 +575,7 @@ extern "C" int gmk_pvnet_destroy(gmk_pvnet* net) {
     if (!net) return GMK_OK;
     (void)hipFree(net->d_w1); (void)hipFree(net->d_w2); (void)hipFree(net->d_w3); (void)hipFree(net->d_wh); (void)hipFree(net->d_b);
     (void)hipFree(net->d_wp); (void)hipFree(net->d_dense); (void)gmk::device_free(net->d_flat); (void)hipFree(net->d_q);
+    gmk::pvnet_sym_release(net);
     delete net;
     return GMK_OK;
 }

@@ -103,10 +103,15 @@ struct gmk_pvnet {
     int precision = 0;                               // GMK_PVNET_F32
     unsigned short* d_q = nullptr;
     bool bf16_attr_set = false;
+    // "K22" (gmk_pvnet_evaluate_sym, pvnet_sym_kernel.hip): expanded states, their outputs and the picks, [sym_capacity] rows, grown on demand
+    float* d_sym = nullptr;
+    int sym_capacity = 0;
 };
 
 namespace gmk {
 // pvnet_bf16_kernel.hip: the bf16 trunk in place of pvnet_trunk_kernel, and d_q refreshed from d_w1 .. d_wh by one kernel on `stream`
 int pvnet_bf16_launch(gmk_pvnet* net, const float* d_states, int n, float* d_pflat, float* d_vflat, void* stream);
 int pvnet_bf16_refresh(gmk_pvnet* net, void* stream);
+// pvnet_sym_kernel.hip: gives d_sym back
+void pvnet_sym_release(gmk_pvnet* net);
 }  // namespace gmk

@@ -10,7 +10,8 @@
 namespace gmk {
 
 // index permutation of network/data_helper.py:36-55: out[j] = in[perm(j)] for np.rot90(a, k) then optional np.fliplr
-__device__ __forceinline__ int augment_source(int j, int k, bool flip) {
+// (constexpr, and callable on the host, for the tables pvnet_sym_kernel.hip builds at compile time; include/gomoku_symmetry.h is the C statement)
+constexpr __host__ __device__ __forceinline__ int augment_source(int j, int k, bool flip) {
     int r = j / 15, c = j % 15;
     if (flip) c = 14 - c;                     // fliplr(b)[r][c] = b[r][14 - c]
     for (int i = 0; i < k; ++i) {             // rot90(a)[r][c] = a[c][14 - r]
@@ -18,6 +19,17 @@ __device__ __forceinline__ int augment_source(int j, int k, bool flip) {
         r = nr; c = nc;
     }
     return r * 15 + c;
+}
+
+// inverse of augment_source for symmetry a = 2k + flip: the output cell that shows source cell c
+constexpr __host__ __device__ __forceinline__ int augment_target(int c, int a) {
+    int r = c / 15, x = c % 15;
+    for (int i = 0; i < (a >> 1); ++i) {       // rot90 undone: (r, x) <- (14 - x, r)
+        const int nr = 14 - x, nx = r;
+        r = nr; x = nx;
+    }
+    if (a & 1) x = 14 - x;
+    return r * 15 + x;
 }
 
 struct StrideRecords {

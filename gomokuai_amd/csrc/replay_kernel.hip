@@ -185,17 +185,6 @@ void replay_append_packed_kernel(const uint8_t* __restrict__ buf, int n, const i
 }
 
 // ---- draw: one wavefront per sample ----
-// inverse of augment_source for symmetry a = 2k + flip: the output cell that shows source cell c
-__device__ __forceinline__ int augment_target(int c, int a) {
-    int r = c / 15, x = c % 15;
-    for (int i = 0; i < (a >> 1); ++i) {       // rot90 undone: (r, x) <- (14 - x, r)
-        const int nr = 14 - x, nx = r;
-        r = nr; x = nx;
-    }
-    if (a & 1) x = 14 - x;
-    return r * 15 + x;
-}
-
 template <class OutT>
 __global__ __launch_bounds__(kThreads)
 void replay_draw_kernel(const uint64_t* __restrict__ state, const GameDesc* __restrict__ desc, const uint8_t* __restrict__ ring_moves,
@@ -230,7 +219,7 @@ void replay_draw_kernel(const uint64_t* __restrict__ state, const GameDesc* __re
     for (int q = 0; q < 4; ++q) {
         const int idx = lane + 64 * q;
         const int c = idx < t ? ring_moves[(d.mstart + idx) % cap] : 0;
-        mv[q] = augment_target(c, a);
+        mv[q] = gmk::augment_target(c, a);
     }
     int cell[4] = {0, 0, 0, 0};
     int last1 = -1, last2 = -1;

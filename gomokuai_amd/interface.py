@@ -10,6 +10,7 @@ is host-side interop only.
     python -m gomokuai_amd.interface botzone   --agent traditional:5 --vcf 16 --ms 960              < request.json
     python -m gomokuai_amd.interface botzone   --agent traditional:5 --vcf 16 --vcf-defend --ms 960 < request.json
     python -m gomokuai_amd.interface botzone   --agent traditional:5 --vcf 16 --vct 2 --ms 960        < request.json
+    python -m gomokuai_amd.interface botzone   --agent network:run.pt --leaves 8 --symmetry all --ms 960 < request.json
 """
 import datetime
 import json
@@ -176,6 +177,85 @@ class EnsembleAgent(Agent):
         self.moves = None
 
 
+class NetworkAgent(Agent):
+    """The trained network at play: K7 (lib.AlphaZeroMCTS, one game, `leaves` leaves per step) with `network` at the leaves, the reference's
+    PyConvNetAgent (agents/alphazero.py:5-9) on the device.  network: a network.FusedPolicyValueNetwork; symmetry "all" (default) or "random"
+    evaluates the leaves through network.symmetric(symmetry) (K22) -- one game's batch is `leaves` rows, so all eight orientations still sit on
+    the flat part of the network's cost --, None or "none" leaves the network as it is.  Every get_action takes a fresh root from the board's
+    move list, searches `iterations` playouts -- or, with `milliseconds`, chunks of `chunk` playouts until the time has passed (at least one
+    chunk, at most max_playouts: the arena is sized for that), as EnsembleAgent does -- and plays the most visited root child, the first
+    maximum in cell order (gmk_az_root_choice)."""
+
+    def __init__(self, network, milliseconds=None, iterations=None, leaves=8, symmetry="all", c_puct=5.0, quiet=False, chunk=64, max_playouts=2048):
+        if milliseconds is None and iterations is None:
+            raise ValueError("NetworkAgent: give milliseconds or iterations")
+        if symmetry in (None, "none"):
+            self.network, self.symmetry = network, None
+        elif symmetry in ("all", "random"):
+            if not hasattr(network, "symmetric"):
+                raise ValueError("NetworkAgent: symmetry needs a network with symmetric(mode) (network.FusedPolicyValueNetwork)")
+            self.network, self.symmetry = network.symmetric(symmetry), symmetry
+        else:
+            raise ValueError("NetworkAgent: symmetry is \"all\", \"random\" or None, not %r" % (symmetry,))
+        self.ms, self.iterations, self.leaves, self.c_puct, self.quiet, self.chunk = milliseconds, iterations, int(leaves), float(c_puct), quiet, int(chunk)
+        self.max_playouts = int(iterations) if iterations is not None else int(max_playouts)
+        self.tree, self.cells, self.moves, self.playouts, self.seconds, self.value = None, None, [], 0, 0.0, 0.0
+
+    def name(self):
+        return "NetworkAgent:%s:L%d:%s" % ("%dms" % self.ms if self.iterations is None else "%dit" % self.iterations, self.leaves, self.symmetry or "none")
+
+    def sync_with_board(self, board):
+        self.moves = [int(p.id) for p in board.move_record]
+
+    def get_action(self, board):
+        import time
+        import torch
+        from . import lib as G
+        from .selfplay import _arena_nodes, _last_two
+        t0 = time.perf_counter()
+        self.moves = [int(p.id) for p in board.move_record]
+        if self.tree is None:
+            self.tree = G.AlphaZeroMCTS(1, node_capacity=_arena_nodes("network", self.max_playouts), c_puct=self.c_puct, leaves=self.leaves)
+            self.cells = torch.full((1,), -1, dtype=torch.int16, device="cuda")
+        moves, lens = np.zeros((1, G.N), np.uint8), np.array([len(self.moves)], np.int32)
+        moves[0, :len(self.moves)] = self.moves
+        self.tree.set_roots(G.moves_to_planes(moves, lens), _last_two(moves, lens))
+        self.playouts = 0
+        with torch.no_grad():
+            if self.iterations is not None:
+                self.tree.search(self.network, int(self.iterations))
+                self.playouts = int(self.iterations)
+            else:
+                while True:                                        # at least one chunk
+                    k = min(self.chunk, self.max_playouts - self.playouts)
+                    self.tree.search(self.network, k)
+                    torch.cuda.current_stream().synchronize()
+                    self.playouts += k
+                    if (time.perf_counter() - t0) * 1000.0 >= self.ms or self.playouts >= self.max_playouts:
+                        break
+        self.tree.root_choice(self.cells)
+        cell = int(self.cells.cpu()[0])
+        self.value = float(self.tree.root_stats()["root_value"][0])
+        self.seconds = time.perf_counter() - t0
+        if cell < 0:
+            raise RuntimeError("NetworkAgent: the root has no child to play (the game is over)")
+        if not self.quiet:
+            print(self.value)
+        return _core().Position(cell)
+
+    def debug_message(self):
+        return {"playouts": self.playouts, "leaves": self.leaves, "symmetry": self.symmetry or "none", "root_value": self.value,
+                "duration": "%dms" % int(self.seconds * 1000)}
+
+    def reset(self):
+        self.moves = []
+
+    def close(self):
+        if self.tree is not None:
+            self.tree.close()
+            self.tree = None
+
+
 class PatternEvalAgent(Agent):
     """Agent.h:108-161: no search, the move with the largest Heuristic::EvaluationProbs after DecisiveFilter on the agent's own
     incremental evaluator (Heuristic.hpp:16-28, 94-161); the centre on an empty board.  On the GPU that is the policy head of K6:
@@ -333,8 +413,10 @@ class VCFAgent(Agent):
         return message
 
 
-def make_agent(spec, milliseconds=960, iterations=None, quiet=False, replicas=1, seed=None, vcf=0, vcf_defend=False, vct=0):
-    """'random', 'human', 'pattern', 'random-mcts[:c_puct[:c_rollouts]]', 'traditional[:c_puct]', 'poolrave[:c_puct[:c_bias]]'.
+def make_agent(spec, milliseconds=960, iterations=None, quiet=False, replicas=1, seed=None, vcf=0, vcf_defend=False, vct=0, leaves=8, symmetry="all"):
+    """'random', 'human', 'pattern', 'random-mcts[:c_puct[:c_rollouts]]', 'traditional[:c_puct]', 'poolrave[:c_puct[:c_bias]]',
+    'network:PATH[:c_puct]' (NetworkAgent on the weights network.load_weights reads from PATH, with `leaves` leaves per step and the
+    leaves evaluated under `symmetry`: "all", "random" or "none"; `replicas` does not apply to it).
     replicas > 1 turns the three MCTS kinds into an EnsembleAgent of that many trees per position ('traditional' with the reference's root
     noise, alpha 0.05 / epsilon 0.25: its search has no other source of difference); replicas = 1 builds the agents as ever.
     vcf = D > 0 puts the forced-win solver in front of the agent (VCFAgent, depth D); 'human' and 'random' stay as they are.
@@ -349,9 +431,20 @@ def make_agent(spec, milliseconds=960, iterations=None, quiet=False, replicas=1,
     if not 0 <= vct <= G.VCT_MAX_THREATS:
         raise ValueError("vct must be in 0 .. %d" % G.VCT_MAX_THREATS)
     if vcf > 0 and spec.split(":")[0] not in ("human", "random"):
-        return VCFAgent(make_agent(spec, milliseconds, iterations, quiet, replicas, seed), depth=vcf, defend=vcf_defend, threats=vct)
+        return VCFAgent(make_agent(spec, milliseconds, iterations, quiet, replicas, seed, leaves=leaves, symmetry=symmetry), depth=vcf, defend=vcf_defend, threats=vct)
     core = _core()
     kind, *args = spec.split(":")
+    if kind == "network":
+        if symmetry not in (None, "none", "all", "random"):
+            raise ValueError("symmetry must be \"all\", \"random\" or \"none\"")
+        if not 1 <= int(leaves) <= G.AZ_MAX_LEAVES:
+            raise ValueError("leaves must be in 1 .. %d" % G.AZ_MAX_LEAVES)
+        if not args or not args[0] or len(args) > 2:
+            raise ValueError("the network agent is 'network:PATH[:c_puct]'")
+        from .network import FusedPolicyValueNetwork, load_weights
+        module = load_weights(args[0]).cuda().eval()
+        return NetworkAgent(FusedPolicyValueNetwork(module), milliseconds=None if iterations is not None else milliseconds, iterations=iterations,
+                            leaves=leaves, symmetry=symmetry, c_puct=float(args[1]) if len(args) > 1 else 5.0, quiet=quiet)
     num = [float(a) for a in args]
     if kind == "random":
         return RandomAgent()
@@ -498,6 +591,8 @@ def main(argv=None):
     ap.add_argument("--vcf", type=int, default=0, metavar="DEPTH", help="put the exact forced-win solver (continuous fours, up to DEPTH own moves) in front of the agents; 0: off")
     ap.add_argument("--vcf-defend", action="store_true", help="with --vcf: also refuse moves that lose to the opponent's forced win by fours, as far as any cell holds")
     ap.add_argument("--vct", type=int, default=0, metavar="T", help="with --vcf: also play a forced win by at most T moves that threaten a win by fours (fours and threes); 0: off.  This search runs after the agent's own and is not bounded by --ms")
+    ap.add_argument("--leaves", type=int, default=8, metavar="L", help="the network agent: leaves per search step (1 .. 8)")
+    ap.add_argument("--symmetry", choices=["all", "random", "none"], default="all", help="the network agent: evaluate every leaf averaged over the board's eight orientations, in one orientation picked per position, or as it stands")
     args = ap.parse_args(argv)
     if args.vcf_defend and args.vcf <= 0:
         ap.error("--vcf-defend needs --vcf DEPTH")
@@ -506,16 +601,18 @@ def main(argv=None):
     from . import lib as G
     if not 0 <= args.vct <= G.VCT_MAX_THREATS:
         ap.error("--vct takes 0 .. %d" % G.VCT_MAX_THREATS)
+    if not 1 <= args.leaves <= G.AZ_MAX_LEAVES:
+        ap.error("--leaves takes 1 .. %d" % G.AZ_MAX_LEAVES)
     if args.seed is not None:
         _core().set_seed(args.seed)
         random.seed(args.seed)
     quiet = args.mode != "console"                                  # a bot's stdout carries the protocol only
-    agent = make_agent(args.agent, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed, vcf=args.vcf, vcf_defend=args.vcf_defend, vct=args.vct)
+    agent = make_agent(args.agent, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed, vcf=args.vcf, vcf_defend=args.vcf_defend, vct=args.vct, leaves=args.leaves, symmetry=args.symmetry)
     if args.mode == "botzone":
         return botzone_interface(agent)
     if args.mode == "keepalive":
         return keep_alive_botzone_interface(agent)
-    return console_interface(agent, make_agent(args.agent2, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed, vcf=args.vcf, vcf_defend=args.vcf_defend, vct=args.vct))
+    return console_interface(agent, make_agent(args.agent2, args.ms, args.iterations, quiet, replicas=args.replicas, seed=args.seed, vcf=args.vcf, vcf_defend=args.vcf_defend, vct=args.vct, leaves=args.leaves, symmetry=args.symmetry))
 
 
 if __name__ == "__main__":

@@ -51,6 +51,7 @@ AZ_PROOF_NONE, AZ_PROOF_WINS, AZ_PROOF_LOSES = 0, 1, 2
 OPT_AZ_VCF_DEFEND = 7                          # K7 + K15: the replies that lose to a forced win by fours, proven at the leaves (AlphaZeroMCTS(vcf_defend=))
 PVNET_F32, PVNET_BF16 = 0, 1                   # GMK_PVNET_*: gmk_pvnet_set_precision (FusedPolicyValueNetwork(precision=))
 PVNET_PRECISIONS = {"f32": PVNET_F32, "bf16": PVNET_BF16}
+PVNET_SYMMETRIES = {"none": 0, "all": 1, "random": 2}      # GMK_PVNET_SYM_*: gmk_pvnet_evaluate_sym (FusedPolicyValueNetwork.symmetric(mode); K22)
 AZ_MAX_LEAVES = 8                              # GMK_AZ_MAX_LEAVES: leaves per game per step of a K7 handle (AlphaZeroMCTS(leaves=))
 NOISE_SAMPLERS = {"std": 0, "counter": 1}      # std::gamma_distribution on the host / the counter-based sampler of include/gomoku_noise.h on the device
 
@@ -69,6 +70,7 @@ EXPORTS = [
     "gmk_mcts_advance_sampled", "gmk_selfplay_run_sampled", "gmk_trad_selfplay_run_sampled", "gmk_trad_root_choice_sampled",
     "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_root_choice", "gmk_trad_step_device", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_run_rave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
     "gmk_pvnet_set_precision", "gmk_pvnet_get_precision", "gmk_bf16_round_host",
+    "gmk_pvnet_evaluate_sym", "gmk_pvnet_sym_pick_host",
     "gmk_pattern_policy", "gmk_pattern_policy_host", "gmk_pattern_play",
     "gmk_vcf_solve", "gmk_vcf_solve_host", "gmk_vcf_defend", "gmk_vcf_defend_host",
     "gmk_vcf_threats", "gmk_vcf_threats_host", "gmk_vct_solve", "gmk_vct_solve_host",
@@ -205,6 +207,8 @@ def load():
     L.gmk_pvnet_set_precision.argtypes = [vp, C.c_int]
     L.gmk_pvnet_get_precision.argtypes = [vp, C.POINTER(C.c_int)]
     L.gmk_bf16_round_host.argtypes = [vp, C.c_size_t, vp]
+    L.gmk_pvnet_evaluate_sym.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint64, vp, vp, vp]
+    L.gmk_pvnet_sym_pick_host.argtypes = [vp, C.c_int, C.c_uint64, vp]
     L.gmk_samples_from_records.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.gmk_records_scan.argtypes = [vp, C.c_int, vp, vp]
     L.gmk_records_packed_bytes.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_uint64), vp]
@@ -981,6 +985,17 @@ def move_sample_host(visits, stones, game_ids, plies, power, seed, proofs=None):
     _check(load().gmk_move_sample_host(visits.ctypes.data, None if proofs is None else proofs.ctypes.data, stones.ctypes.data, game_ids.ctypes.data, n,
                                        int(plies), int(power), int(seed) & 0xFFFFFFFFFFFFFFFF, cells.ctypes.data))
     return cells
+
+
+def pvnet_sym_pick_host(states, seed=DEFAULT_SEED):
+    """gmk_pvnet_sym_pick_host: the symmetry 0..7 that gmk_pvnet_evaluate_sym's "random" mode evaluates each position in, int32[n]; needs no GPU.
+    states float32 [n, 6, 15, 15] (Board.encoded_states()); the pick depends on a row's content and the seed only (include/gomoku_symmetry.h)."""
+    states = np.ascontiguousarray(states, dtype=np.float32)
+    n = states.shape[0]
+    assert states.size == n * 6 * N
+    sym = np.zeros(n, dtype=np.int32)
+    _check(load().gmk_pvnet_sym_pick_host(states.ctypes.data, n, int(seed) & 0xFFFFFFFFFFFFFFFF, sym.ctypes.data))
+    return sym
 
 
 def _check_step_device(tree, cells, verdict):

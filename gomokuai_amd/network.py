@@ -137,6 +137,12 @@ class FusedPolicyValueNetwork:
                                                        torch.cuda.current_stream(states.device).cuda_stream))
         return value, probs
 
+    def symmetric(self, mode, seed=None):
+        """This network evaluated over the board's symmetries (gmk_pvnet_evaluate_sym, K22) -> a SymmetricNetwork with this network's __call__
+        and eval_state.  mode "all": the average over the eight orientations; "random": one orientation per position, picked from the position's
+        content and `seed` (default lib.DEFAULT_SEED); "none": this network's own outputs.  An unknown mode is a ValueError."""
+        return SymmetricNetwork(self, mode, seed)
+
     @torch.no_grad()
     def dense_reference(self, states):
         """The dense layers through PyTorch on the kernel's trunk outputs (what __call__ did before the second kernel existed): a check, not a path."""
@@ -155,11 +161,70 @@ class FusedPolicyValueNetwork:
         return float(value[0]), probs[0].cpu().numpy()
 
 
+class SymmetricNetwork:
+    """FusedPolicyValueNetwork.symmetric(mode, seed): the callable every self-play and match loop takes, network(states) -> (value, probs), through
+    gmk_pvnet_evaluate_sym (include/gomoku_symmetry.h states the rule).  It holds no weights and no handle of its own: it evaluates with whatever
+    `fused` holds when it is called, so later load_from() / set_precision() calls on `fused` are followed.  Capturable: the expand kernel, the
+    network's two kernels and the reduce kernel go to torch's current stream, nothing synchronises (the handle's workspace grows at the first
+    call of a batch size, which AlphaZeroMCTS.search(graph=True) makes eagerly)."""
+
+    def __init__(self, fused, mode, seed=None):
+        from . import lib as G
+        if mode not in G.PVNET_SYMMETRIES:                                  # before anything touches the device: a typo is a ValueError on any machine
+            raise ValueError("symmetric: mode must be one of %s, not %r" % (sorted(G.PVNET_SYMMETRIES), mode))
+        self.fused, self.G, self.mode = fused, G, mode
+        self.seed = (G.DEFAULT_SEED if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
+
+    @property
+    def net(self):
+        return self.fused.net
+
+    @torch.no_grad()
+    def __call__(self, states):
+        """states float32 [B, 6, 15, 15] on the GPU -> (value [B], probs [B, 225]); every kernel goes to torch's current stream."""
+        assert states.is_cuda and states.dtype == torch.float32 and states.is_contiguous() and tuple(states.shape[1:]) == (6, 15, 15)
+        n = states.shape[0]
+        value = torch.empty((n,), dtype=torch.float32, device=states.device)
+        probs = torch.empty((n, 225), dtype=torch.float32, device=states.device)
+        self.G._check(self.G.load().gmk_pvnet_evaluate_sym(self.fused.h, states.data_ptr(), n, self.G.PVNET_SYMMETRIES[self.mode], self.seed, value.data_ptr(),
+                                                           probs.data_ptr(), torch.cuda.current_stream(states.device).cuda_stream))
+        return value, probs
+
+    @torch.no_grad()
+    def eval_state(self, board):
+        """FusedPolicyValueNetwork.eval_state through the symmetries: one position -> (value, probs[225]) on the host."""
+        dev = next(self.fused.net.parameters()).device
+        states = torch.from_numpy(np.asarray(board.encoded_states(), dtype=np.float32)[None]).to(dev)
+        value, probs = self(states)
+        return float(value[0]), probs[0].cpu().numpy()
+
+
 # the trainer's tensor names (lib.TRAIN_TENSORS) -> how a PolicyValueNetwork holds them
 _MODULE_TENSORS = (("w1", "conv.0.weight"), ("b1", "conv.0.bias"), ("w2", "conv.1.weight"), ("b2", "conv.1.bias"), ("w3", "conv.2.weight"), ("b3", "conv.2.bias"),
                    ("w_policy_conv", "policy_conv.weight"), ("b_policy_conv", "policy_conv.bias"), ("w_value_conv", "value_conv.weight"), ("b_value_conv", "value_conv.bias"),
                    ("w_policy", "policy_dense.weight"), ("b_policy", "policy_dense.bias"), ("w_hidden", "value_hidden.weight"), ("b_hidden", "value_hidden.bias"),
                    ("w_out", "value_out.weight"), ("b_out", "value_out.bias"))
+
+
+def load_weights(path):
+    """A PolicyValueNetwork (on the host) with the weights in `path`: either a torch.save'd PolicyValueNetwork.state_dict(), or a file
+    TrainingLoop.save wrote, whose state["trainer"]["params"] holds the sixteen tensors under the trainer's names.  Read with weights_only=True."""
+    import os
+    state = torch.load(os.fspath(path), map_location="cpu", weights_only=True)
+    net = PolicyValueNetwork()
+    if isinstance(state, dict) and isinstance(state.get("trainer"), dict) and "params" in state["trainer"]:
+        params, sd = state["trainer"]["params"], net.state_dict()
+        missing = [name for name, _ in _MODULE_TENSORS if name not in params]
+        if missing:
+            raise ValueError("load_weights: %s is a training checkpoint without %s" % (path, ", ".join(missing)))
+        with torch.no_grad():
+            for name, key in _MODULE_TENSORS:
+                sd[key].copy_(torch.as_tensor(params[name], dtype=torch.float32).reshape(sd[key].shape))
+    elif isinstance(state, dict) and all(key in state for _, key in _MODULE_TENSORS):
+        net.load_state_dict(state)
+    else:
+        raise ValueError("load_weights: %s holds neither a PolicyValueNetwork.state_dict() nor a TrainingLoop checkpoint" % (path,))
+    return net
 
 
 def module_arrays(net):

@@ -573,9 +573,20 @@ def _sampled_choice(visits, proofs, stones, games, sample):
     return G.move_sample_host(visits, stones, ids, plies, power, seed, proofs).astype(np.int64)
 
 
+def _symmetric(who, network, symmetry, seed):
+    """`network` as the loops of `who` call it: itself for symmetry None, network.symmetric(symmetry, seed) for "random" or "all" (K22)."""
+    if symmetry is None:
+        return network
+    if symmetry not in ("random", "all"):
+        raise ValueError("%s: symmetry is None, \"random\" or \"all\", not %r" % (who, symmetry))
+    if not hasattr(network, "symmetric"):
+        raise ValueError("%s: symmetry needs a network with symmetric(mode, seed) (network.FusedPolicyValueNetwork)" % who)
+    return network.symmetric(symmetry, seed)
+
+
 def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, first_game_id=0, opening_plies=0, max_moves=N,
                        device=None, node_capacity=None, reuse_subtree=True, root_noise=(0.05, 0.25), slots=None, device_loop=True, noise_sampler="counter", leaves=1,
-                       vcf=None, proof=False, vcf_defend=False, sample_plies=0, sample_power=1):
+                       vcf=None, proof=False, vcf_defend=False, sample_plies=0, sample_power=1, symmetry=None):
     """n_games complete games of the network-guided searcher against itself (agents/alphazero.py:5-9 on both sides: the
     reference's AlphaZero self-play), all games in lock step on the current GPU: every move = `playouts` lock-step playouts of
     K7 with `network(states [n,6,15,15]) -> (value [n], probs [n,225])` at the leaves (network.FusedPolicyValueNetwork = K9),
@@ -595,9 +606,13 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
     overflow says when an arena filled).  sample_plies = S > 0: a game plays its first S plies (openings count) in proportion to
     visits^sample_power (1, 2, 3: temperature 1, 1/2, 1/3) and its most visited child afterwards, AlphaZero's self-play schedule
     (lib.AlphaZeroMCTS.advance(sample=), include/gomoku_sample.h): the draw is keyed by seed, the game's global id and its stone count, so
-    these too are the same games on every loop, and a record's visit row gives its move again.  Returns GameRecords like play_games."""
+    these too are the same games on every loop, and a record's visit row gives its move again.  symmetry = "random" or "all": the leaves are
+    evaluated through network.symmetric(symmetry, seed) -- one orientation of the board per leaf, picked from the leaf's position and `seed`, or
+    the average over all eight (K22, include/gomoku_symmetry.h); the pick does not depend on a row's place in the batch, so these are the same
+    games on every loop as well.  None: `network` as it is.  Returns GameRecords like play_games."""
     if not (0 <= int(sample_plies) <= N and 1 <= int(sample_power) <= 3):
         raise ValueError("play_network_games: sample_plies takes 0 .. 225 and sample_power 1, 2 or 3")
+    network = _symmetric("play_network_games", network, symmetry, seed)
     sample = (int(sample_plies), int(sample_power), seed, first_game_id) if int(sample_plies) > 0 else None
     if slots is not None and slots < n_games and (max_moves < N or (device_loop and opening_plies > 8)):
         # (the slot loops play whole games, the device-resident one from openings of at most 8 plies -- gmk_az_set_slots' limit: say so instead of
@@ -790,7 +805,8 @@ class _EvalOpponent:
 
 
 def play_evaluation_games(n_games, network, opponent, playouts=400, c_puct=5.0, seed=G.DEFAULT_SEED, first_game_id=0, opening_plies=0, max_moves=N,
-                          reuse_subtree=True, root_noise=(0.05, 0.25), device_loop=None, device=None, leaves=1, vcf=None, proof=False, vcf_defend=False, node_capacity=None):
+                          reuse_subtree=True, root_noise=(0.05, 0.25), device_loop=None, device=None, leaves=1, vcf=None, proof=False, vcf_defend=False, node_capacity=None,
+                          symmetry=None):
     """The reference's evaluation match (network/train.py:88-126 evaluate_network -> agents/utils.py:66-100 eval_agents): n_games games of the
     network-guided searcher (K7 with `network` = network.FusedPolicyValueNetwork at the leaves, `playouts` playouts a move) against
     `opponent` = (name, kwargs) as in DATA_CONFIG["schedule"] ("traditional_mcts" -- with {"use_rave": True} TraditionalPolicy + RAVE --,
@@ -811,8 +827,11 @@ def play_evaluation_games(n_games, network, opponent, playouts=400, c_puct=5.0, 
     replies that lose to the opponent's forced win by fours (lib.AlphaZeroMCTS(vcf_defend=)); it applies to the K7 handle only.  Such a search
     spends its playouts below the few replies that hold, so a kept subtree stays nearly whole while the replies are forced: node_capacity (the K7
     handle's nodes per game; None: three searches' worth with kept subtrees) makes room, and the records' overflow says when an arena filled.
+    symmetry = "random" or "all": the network's leaves are evaluated through network.symmetric(symmetry, seed) (K22: one orientation per leaf, or
+    the average over all eight -- a match's batch is small enough for the eight to ride on the network's launch cost); None: `network` as it is.
     Returns (GameRecords, network_is_black bool[n], scores float[n]); the records' visit counts at move i are the mover's, and
     records.groups lists per group the games, the unfinished count and the K7 handle's live games after the loop."""
+    network = _symmetric("play_evaluation_games", network, symmetry, seed)
     kind = opponent[0]
     if kind not in _EVAL_OPPONENTS:
         raise ValueError("play_evaluation_games: unknown opponent '%s' (%s)" % (kind, ", ".join(_EVAL_OPPONENTS)))

@@ -39,9 +39,11 @@ class EvaluationSchedule:
     network's searches in the match (selfplay.play_evaluation_games(leaves=); 1 = the reference's search, one leaf at a time).  vcf: (depth,
     budget) of the forced-win solver at the leaves of those searches (selfplay.play_evaluation_games(vcf=)), None = off.  proof: those searches
     carry proven wins and losses up their trees (selfplay.play_evaluation_games(proof=)).  vcf_defend: with vcf and proof, they prove the replies
-    that lose to the opponent's forced win by fours (selfplay.play_evaluation_games(vcf_defend=))."""
+    that lose to the opponent's forced win by fours (selfplay.play_evaluation_games(vcf_defend=)).  symmetry: "random" or "all" -- the network's
+    leaves evaluated in one orientation of the board or averaged over all eight (selfplay.play_evaluation_games(symmetry=), K22); None = as they stand."""
 
-    def __init__(self, supervisor=SUPERVISOR, candidates=CANDIDATES, eval_rounds=11, c_iterations=400, leaves=1, vcf=None, proof=False, vcf_defend=False):
+    def __init__(self, supervisor=SUPERVISOR, candidates=CANDIDATES, eval_rounds=11, c_iterations=400, leaves=1, vcf=None, proof=False, vcf_defend=False,
+                 symmetry=None):
         if not candidates:
             raise ValueError("EvaluationSchedule: at least one candidate (None = the supervisor)")
         if not 1 <= int(leaves) <= 8:
@@ -52,6 +54,9 @@ class EvaluationSchedule:
         self.vcf = None if vcf is None else (int(vcf[0]), int(vcf[1]))
         self.proof = bool(proof)
         self.vcf_defend = bool(vcf_defend)
+        if symmetry not in (None, "random", "all"):
+            raise ValueError("EvaluationSchedule: symmetry is None, \"random\" or \"all\"")
+        self.symmetry = symmetry
         self.supervisor, self.candidates = supervisor, list(candidates)
         self.eval_rounds, self.c_iterations = int(eval_rounds), int(c_iterations)
         self.schedule_level, self.ref_iterations, self.best_win_rate = 0, self.c_iterations, 0.0
@@ -192,6 +197,8 @@ class TrainingLoop:
             options.setdefault("proof", True)
         if getattr(sch, "vcf_defend", False):
             options.setdefault("vcf_defend", True)
+        if getattr(sch, "symmetry", None) is not None:
+            options.setdefault("symmetry", sch.symmetry)
         rec, network_is_black, scores = selfplay.play_evaluation_games(sch.eval_rounds, network, (name, kwargs), playouts=self.eval_playouts, **options)
         win_rate = float(scores.mean())
         events = sch.update(win_rate)

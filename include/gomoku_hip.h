@@ -832,6 +832,31 @@ int gmk_pvnet_set_precision(gmk_pvnet* net, int precision);
 int gmk_pvnet_get_precision(gmk_pvnet* net, int* precision);
 int gmk_bf16_round_host(const float* src, size_t n, uint16_t* dst);
 
+/* ---- K22: the network evaluated over the board's eight symmetries ----
+ * The rule -- the numbering of the symmetries, the transform T_a of a position, the back-transform of a policy row and the pick of
+ * GMK_PVNET_SYM_RANDOM -- is stated once, in gomoku_symmetry.h.  gmk_pvnet_evaluate_sym takes gmk_pvnet_evaluate's arguments plus a mode:
+ *   GMK_PVNET_SYM_NONE    exactly the launches of gmk_pvnet_evaluate.
+ *   GMK_PVNET_SYM_ALL     per row: (v_a, q_a) = gmk_pvnet_evaluate(T_a(s)) for a = 0 .. 7, p_a = q_a back-transformed;
+ *                         value = (v_0 + v_1 + .. + v_7) * 0.125f, probs[c] = (p_0[c] + .. + p_7[c]) * 0.125f, float32 sums in this order
+ *                         (the library is built with -ffp-contract=off): the result is defined bit for bit by gmk_pvnet_evaluate, which is
+ *                         isolated by row in both precisions.
+ *   GMK_PVNET_SYM_RANDOM  value = v_a, probs = p_a with a = the pick: a function of the row's content and `seed` only, never of the row's
+ *                         index or the batch.  `seed` is ignored by the other two modes.
+ * Launches: one expand kernel (n rows -> 8n or n transformed rows, and the picks), gmk_pvnet_evaluate's two kernels on those rows in the
+ * handle's precision, one reduce kernel; all on `stream`, nothing on any other stream.  d_states is not written and nothing past row n of
+ * the outputs is written.  n = 0 is a no-op.  GMK_ERR_ARG for a NULL handle, a NULL pointer with n > 0, n < 0 or another mode -- before
+ * anything touches a GPU --, GMK_ERR_STATE before gmk_init or gmk_pvnet_set_dense.
+ * The handle owns the workspace (the expanded states, their 8n or n rows of outputs, the picks) and the head activations of those rows.
+ * Both grow on demand and never shrink; growth synchronises `stream` and allocates, so it must not happen during a stream capture: let
+ * the first call of a batch size and mode happen eagerly.  AlphaZeroMCTS.search(graph=True) does: its first step runs eagerly with the
+ * full batch and sizes the workspace, the captured step only launches.  One handle serves one stream at a time, as for gmk_pvnet_evaluate.
+ * gmk_pvnet_sym_pick_host: h_sym[i] = the pick of GMK_PVNET_SYM_RANDOM for row i of h_states float32 [n][6][225].  Needs no GPU and no
+ *   gmk_init.  GMK_ERR_ARG for n < 0 or a NULL pointer with n > 0. */
+enum { GMK_PVNET_SYM_NONE = 0, GMK_PVNET_SYM_ALL = 1, GMK_PVNET_SYM_RANDOM = 2 };
+int gmk_pvnet_evaluate_sym(gmk_pvnet* net, const float* d_states, int n, int mode, uint64_t seed, float* d_value, float* d_probs,
+                           void* stream);
+int gmk_pvnet_sym_pick_host(const float* h_states, int n, uint64_t seed, int32_t* h_sym);
+
 /* ---- K10: the pattern heuristic on its own, per position and for whole greedy games ----
  * Heuristic::EvaluationProbs, DecisiveFilter and EvaluationValue (core/lib/include/algorithms/Heuristic.hpp:16-45, 94-161) for a batch, outside
  * any tree.  filter: 1 = EvaluationProbs + DecisiveFilter (PatternEvalAgent::getAction, core/interface/src/Agent.h:107-160, and
