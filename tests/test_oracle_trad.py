@@ -1,6 +1,7 @@
 """The oracle's restatement of the pattern-guided search (oracle/go_trad.c: Traditional.h:17-69, Heuristic.hpp:16-45,
 94-200, MonteCarlo.hpp:149-184).  The reference has no tests for this part and cannot be built here, so
-the float part is "parity unpinned"; these tests hold the behaviour its code prescribes."""
+these tests hold the behaviour its code prescribes.
+What the float part MEANS is held to a float64 statement in tests/test_heuristic_f64.py (tests/heuristic_f64_reference.py)."""
 import numpy as np
 
 c = lambda y, x: y * 15 + x

@@ -1,7 +1,8 @@
 """K10 parity: the pattern policy on the device (gmk_pattern_policy, gmk_pattern_play; Heuristic.hpp:16-45, 61-83, 94-161) against the CPU
 oracle.  filter=1 is held to oracle.trad_heuristic (go_trad.c: TraditionalPolicy::hybridSimulate), filter=0 and the whole-game loop to the
 Python restatement of the same float order (tests/trad_rave_reference.py) fed from oracle.Evaluator.  Both sides add in one fixed order and
-K6 already meets the oracle bit for bit with this code, so everything is compared on BITS: no tolerances."""
+K6 already meets the oracle bit for bit with this code, so everything is compared on BITS: no tolerances.
+The kernels against an independent float64 statement of the formula, within a derived bound: tests/test_heuristic_f64_gpu.py."""
 import functools
 
 import numpy as np
