@@ -12,7 +12,7 @@ LIB = os.path.join(HERE, "libgomoku_hip.so")
 # (GMK_HIP_LIB=prof, see lib.py); never by the tests, bench.py or __graft_entry__.
 PROF_LIB = os.path.join(HERE, "libgomoku_hip_prof.so")
 
-LIB_SOURCES = ["capi.hip", "eval_kernel.hip", "evalstate_kernel.hip", "trad_kernel.hip", "rave_kernel.hip", "az_kernel.hip", "pvnet_kernel.hip", "pvnet_bf16_kernel.hip", "pvnet_sym_kernel.hip", "mcts_kernel.hip", "records_kernel.hip", "records_wire.hip", "replay_kernel.hip", "pattern_kernel.hip", "vcf_kernel.hip", "vcf_defend_kernel.hip", "vcf_threats_kernel.hip", "vct_kernel.hip", "train_kernel.hip", "match_kernel.hip", "ensemble_kernel.hip", "pattern_tables.cpp", "synth.cpp"]
+LIB_SOURCES = ["capi.hip", "eval_kernel.hip", "evalstate_kernel.hip", "trad_kernel.hip", "rave_kernel.hip", "az_kernel.hip", "pvnet_kernel.hip", "pvnet_bf16_kernel.hip", "pvnet_sym_kernel.hip", "mcts_kernel.hip", "records_kernel.hip", "records_wire.hip", "replay_kernel.hip", "pattern_kernel.hip", "vcf_kernel.hip", "vcf_defend_kernel.hip", "vcf_threats_kernel.hip", "vct_kernel.hip", "train_kernel.hip", "match_kernel.hip", "ensemble_kernel.hip", "noise_kernel.hip", "pattern_tables.cpp", "synth.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: MCTS numerics (f64 PUCB from f32 operands, f32 running mean) must match the CPU
 # restatement bit for bit; hipcc fuses multiply-add by default.

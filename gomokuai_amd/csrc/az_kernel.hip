@@ -1858,7 +1858,8 @@ extern "C" int gmk_az_set_option(gmk_az* a, int option, int value) {
 // Default::AddNoise on every root with children, seeded like gmk_mcts_add_root_noise / gmk_trad_add_root_noise.  The counter sampler is one
 // launch on `stream` and does not wait.  The std sampler draws on the host: it waits for `stream`, then for the device, and returns finished.
 extern "C" int gmk_az_add_root_noise(gmk_az* a, float alpha, float epsilon, uint64_t seed, uint32_t first_game_id, void* stream) {
-    if (!a || !(alpha > 0.0f)) { gmk::set_error("gmk_az_add_root_noise: bad arguments"); return GMK_ERR_ARG; }
+    if (!a) { gmk::set_error("gmk_az_add_root_noise: bad arguments"); return GMK_ERR_ARG; }
+    if (!gmk::noise_args_ok("gmk_az_add_root_noise", alpha, epsilon)) return GMK_ERR_ARG;
     if (!a->rooted) { gmk::set_error("gmk_az_add_root_noise: gmk_az_set_roots has not been called"); return GMK_ERR_STATE; }
     if (az_marks_up(a, "gmk_az_add_root_noise")) return GMK_ERR_STATE;
     const size_t n = static_cast<size_t>(a->t.n_games);

@@ -27,6 +27,18 @@ DeviceState& device_state();
 // The entry points' test of a pointer argument's alignment (NULL is aligned).
 inline bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
 
+// The entry points' test of Default::AddNoise's parameters (include/gomoku_hip.h, "Root noise parameters"): alpha finite and > 0,
+// 0 <= epsilon <= 1, both written as comparisons a NaN fails.  false: the error text names the argument, and nothing may be launched.
+inline bool noise_args_ok(const char* who, float alpha, float epsilon) {
+    if (!(alpha > 0.0f && alpha <= 3.402823466e+38f)) { set_error("%s: alpha = %g (must be finite and > 0)", who, static_cast<double>(alpha)); return false; }
+    if (!(epsilon >= 0.0f && epsilon <= 1.0f)) { set_error("%s: epsilon = %g (must lie in [0, 1])", who, static_cast<double>(epsilon)); return false; }
+    return true;
+}
+// The same for the self-play entries, where noise_alpha == 0 means "no noise" and epsilon is then ignored
+inline bool selfplay_noise_args_ok(const char* who, float noise_alpha, float noise_epsilon) {
+    return noise_alpha == 0.0f || noise_args_ok(who, noise_alpha, noise_epsilon);
+}
+
 // Profiling switches (phase masks, in-kernel timers, launch-shape overrides) exist in the -DGMK_PROFILE build only:
 // `python -m gomokuai_amd.build --profile` makes libgomoku_hip_prof.so, which tools/*.sh load with GMK_HIP_LIB=prof.
 // The production library never reads the environment, so a stray variable cannot change a result.

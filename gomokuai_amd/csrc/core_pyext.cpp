@@ -15,6 +15,7 @@
 #include <array>
 #include <chrono>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <random>
 #include <sstream>
@@ -673,8 +674,14 @@ PYBIND11_MODULE(CorePyExt, mod) {
 
     mod.add_object("GameConfig", py::dict("width"_a = kW, "height"_a = kH, "board_size"_a = kN, "max_renju"_a = kRenju));
     // extension: make searches reproducible (the reference seeds from random_device and has no such hook)
-    mod.def("set_root_noise", [](float alpha, float epsilon) { g_root_noise_alpha = alpha; g_root_noise_epsilon = epsilon; }, "alpha"_a = 0.05f, "epsilon"_a = 0.25f,
-            "MI355X build only: the Dirichlet noise Default::AddNoise mixes into the root priors before every search (alpha 0 = none)");
+    // the rule of include/gomoku_hip.h ("Root noise parameters"): alpha 0 turns the noise off; any other alpha is finite and > 0, epsilon then lies
+    // in [0, 1] (comparisons a NaN fails); a refused pair leaves the parameters as they were
+    mod.def("set_root_noise", [](float alpha, float epsilon) {
+                if (alpha != 0.0f && !(alpha > 0.0f && alpha <= std::numeric_limits<float>::max())) throw py::value_error("set_root_noise: alpha must be 0 (no noise) or finite and > 0");
+                if (alpha != 0.0f && !(epsilon >= 0.0f && epsilon <= 1.0f)) throw py::value_error("set_root_noise: epsilon must lie in [0, 1]");
+                g_root_noise_alpha = alpha; g_root_noise_epsilon = epsilon;
+            }, "alpha"_a = 0.05f, "epsilon"_a = 0.25f,
+            "MI355X build only: the Dirichlet noise Default::AddNoise mixes into the root priors before every search (alpha 0 = none; any other alpha finite and > 0, epsilon in [0, 1], else ValueError)");
     mod.def("set_seed", [](uint64_t seed) { g_search_seed = seed; g_next_game_id = 0; rng().seed(static_cast<uint32_t>(seed)); }, "seed"_a);
 
     py::enum_<Player>(mod, "Player", "Gomoku player types")

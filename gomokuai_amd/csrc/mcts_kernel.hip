@@ -1154,6 +1154,7 @@ static int selfplay_run(const char* who, gmk_mcts* m, int n_total, uint32_t firs
                         int sample_plies, int sample_power, const uint8_t* h_open_moves, int open_stride, const int32_t* h_open_lens,
                         uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int32_t* h_steps, void* stream) {
     if (const int rc = mcts_sample_args(who, sample_plies, sample_power); rc != GMK_OK) return rc;
+    if (!gmk::selfplay_noise_args_ok(who, noise_alpha, noise_epsilon)) return GMK_ERR_ARG;
     // (playouts >= 1: a root that was never searched has no child to play, and the persistent launch ends only when every game has)
     if (!m || n_total <= 0 || playouts < 1 || !d_moves || !d_lens || !d_winner || (h_open_moves && (!h_open_lens || open_stride <= 0))) {
         gmk::set_error("%s: bad arguments (playouts >= 1)", who);
@@ -1279,7 +1280,8 @@ extern "C" int gmk_mcts_step_host(gmk_mcts* m, const int16_t* h_moves, int reuse
 // (root_noise.h).  Host side: 225 floats a game.
 extern "C" int gmk_mcts_add_root_noise(gmk_mcts* m, float alpha, float epsilon, void* stream) {
     if (m && !m->rooted) { gmk::set_error("gmk_mcts_add_root_noise: gmk_mcts_set_roots has not been called"); return GMK_ERR_STATE; }
-    if (!m || !(alpha > 0.0f)) { gmk::set_error("gmk_mcts_add_root_noise: bad arguments"); return GMK_ERR_ARG; }
+    if (!m) { gmk::set_error("gmk_mcts_add_root_noise: bad arguments"); return GMK_ERR_ARG; }
+    if (!gmk::noise_args_ok("gmk_mcts_add_root_noise", alpha, epsilon)) return GMK_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
     m->last_stream = s;
     const size_t n = static_cast<size_t>(m->n_games);

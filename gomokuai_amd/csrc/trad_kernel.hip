@@ -1160,7 +1160,8 @@ extern "C" int gmk_trad_step_device(gmk_trad* t, const int16_t* d_cells, const i
 // The counter sampler is one launch on `stream` and does not wait (d_game_ids mirrors game_ids: gmk_trad_set_game_ids and the end of
 // gmk_trad_selfplay_run keep it so).  The std sampler draws on the host: it waits for `stream`, then for the device, and returns finished.
 extern "C" int gmk_trad_add_root_noise(gmk_trad* t, float alpha, float epsilon, uint64_t seed, uint32_t first_game_id, void* stream) {
-    if (!t || !(alpha > 0.0f)) { gmk::set_error("gmk_trad_add_root_noise: bad arguments"); return GMK_ERR_ARG; }
+    if (!t) { gmk::set_error("gmk_trad_add_root_noise: bad arguments"); return GMK_ERR_ARG; }
+    if (!gmk::noise_args_ok("gmk_trad_add_root_noise", alpha, epsilon)) return GMK_ERR_ARG;
     if (!t->positioned) { gmk::set_error("gmk_trad_add_root_noise: gmk_trad_set_positions has not been called"); return GMK_ERR_STATE; }
     const size_t n = static_cast<size_t>(t->n_games);
     if (t->noise_sampler == GMK_NOISE_SAMPLER_COUNTER) {        // drawn on the device, one wavefront per game: nothing comes back to the host
@@ -1251,6 +1252,7 @@ static int trad_selfplay_run(const char* who, gmk_trad* t, int policy, int n_tot
                              uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int persistent, int max_steps, int32_t* h_overflow, int32_t* h_steps, void* stream) {
     TradSample sm;
     if (const int rc = trad_sample_args(who, sample_plies, sample_power, seed, first_game_id, &sm); rc != GMK_OK) return rc;
+    if (!gmk::selfplay_noise_args_ok(who, noise_alpha, noise_epsilon)) return GMK_ERR_ARG;
     const bool sampled = sample_plies > 0;
     const bool noisy = noise_alpha > 0.0f && reuse_subtree;     // (a new root has no children: AddNoise is a no-op without kept subtrees)
     if (t && t->lockstep) persistent = 0;

@@ -81,6 +81,7 @@ EXPORTS = [
     "gmk_train_create", "gmk_train_destroy", "gmk_train_forward", "gmk_train_grads", "gmk_train_step", "gmk_train_params", "gmk_train_set_params",
     "gmk_train_get_block", "gmk_train_set_block", "gmk_train_set_step_count", "gmk_train_export", "gmk_train_info",
     "gmk_train_kernel_gemm", "gmk_train_kernel_reduce", "gmk_train_kernel_im2col", "gmk_train_kernel_col2im",
+    "gmk_noise_mix_rows",
 ]
 
 
@@ -140,6 +141,7 @@ def load():
     L.gmk_selfplay_run_sampled.argtypes = [vp, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(C.c_int32), vp]
     L.gmk_trad_root_choice_sampled.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp]
     L.gmk_mcts_add_root_noise.argtypes = [vp, C.c_float, C.c_float, vp]
+    L.gmk_noise_mix_rows.argtypes = [vp, vp, vp, vp, C.c_int, C.c_float, C.c_float, C.c_uint64, vp]
     L.gmk_mcts_set_option.argtypes = [vp, C.c_int, C.c_int]
     L.gmk_mcts_reserve.argtypes = [vp, C.c_int]
     L.gmk_trad_reserve.argtypes = [vp, C.c_int]
@@ -953,6 +955,21 @@ MATCH_STATUS_REFUSED, MATCH_STATUS_BAD_ROW = 1, 2                      # bits of
 def _current_stream(stream):
     import torch
     return torch.cuda.current_stream().cuda_stream if stream is None else stream
+
+
+def noise_mix_rows(priors, game_ids, stones, alpha, epsilon, seed, draws=None, stream=None):
+    """gmk_noise_mix_rows, a diagnostic entry: Default::AddNoise with the counter-based sampler on n rows of priors by cell, in place, one
+    wavefront per row, on `stream` (default: torch's current stream); the call does not wait.  priors float32[n, 225] (0: no child), game_ids and
+    stones uint32[n] (any 4-byte integer tensor: the bits count), draws None or float32[n, 225] for the gamma variates before the normalisation;
+    all on the device and contiguous.  alpha finite and > 0, 0 <= epsilon <= 1, else GmkError."""
+    import torch
+    n = priors.shape[0]
+    assert priors.is_cuda and priors.dtype == torch.float32 and tuple(priors.shape) == (n, N) and priors.is_contiguous()
+    for ids in (game_ids, stones):
+        assert ids.is_cuda and ids.element_size() == 4 and tuple(ids.shape) == (n,) and ids.is_contiguous()
+    assert draws is None or (draws.is_cuda and draws.dtype == torch.float32 and tuple(draws.shape) == (n, N) and draws.is_contiguous())
+    _check(load().gmk_noise_mix_rows(priors.data_ptr(), None if draws is None else draws.data_ptr(), game_ids.data_ptr(), stones.data_ptr(), n,
+                                     float(alpha), float(epsilon), int(seed) & 0xFFFFFFFFFFFFFFFF, _current_stream(stream)))
 
 
 def _root_choice(entry, tree, cells, visits, stream):

@@ -200,6 +200,15 @@ int gmk_mcts_step(gmk_mcts* m, const int16_t* d_forced_moves, uint8_t* d_moves, 
                   int8_t* d_winner, int32_t* d_unfinished, int reuse_subtree, void* stream);
 /* the same from host memory, synchronous, without game records: h_moves int16[n] */
 int gmk_mcts_step_host(gmk_mcts* m, const int16_t* h_moves, int reuse_subtree);
+/* Root noise parameters -- the ONE rule for every entry that takes Default::AddNoise's alpha and epsilon:
+ *   gmk_mcts_add_root_noise, gmk_trad_add_root_noise, gmk_az_add_root_noise, gmk_noise_mix_rows:
+ *     alpha is finite and > 0, and 0 <= epsilon <= 1 (tested as comparisons, so a NaN is refused).
+ *   gmk_selfplay_run, gmk_selfplay_run_sampled, gmk_trad_selfplay_run, gmk_trad_selfplay_run_sampled:
+ *     noise_alpha == 0 means "no noise" and noise_epsilon is then ignored; any other noise_alpha follows the rule above.
+ * Anything else returns GMK_ERR_ARG with a message that names the argument, before anything is launched and before anything on the handle
+ * changes.  (alpha = +inf or epsilon = NaN would make every mixed prior NaN, epsilon > 1 some of them negative, and the searches would go on.)
+ * epsilon == 0 leaves the priors as they are; epsilon == 1 leaves none (AddNoise scales the priors by 1 - epsilon FIRST and draws only for the
+ * entries that are not 0 then: every entry is masked and ends at 0, in the serial statement too); alpha >= 1 draws without the boost. */
 /* Default::AddNoise (MonteCarlo.hpp:97-108, Statistical.hpp:29-34) on every unfinished game whose root has children:
  * P <- (1-epsilon) P + epsilon * normalized(gamma(alpha,1)); the reference calls it at the start of every runPlayouts
  * (MCTS.cpp:182) with alpha 0.05, epsilon 0.25.  No-op for childless (fresh) roots.  The priors stay in force until the
@@ -222,6 +231,17 @@ enum { GMK_OPT_NOISE_SAMPLER = 1, GMK_OPT_LOCKSTEP = 2, GMK_OPT_AZ_LEAVES = 3 /*
 #define GMK_AZ_MAX_LEAVES 8
 enum { GMK_NOISE_SAMPLER_STD = 0, GMK_NOISE_SAMPLER_COUNTER = 1 };
 int gmk_mcts_set_option(gmk_mcts *m, int option, int value);
+/* Diagnostic: the mixing of GMK_NOISE_SAMPLER_COUNTER on rows of priors the CALLER supplies -- the device function every search kernel inlines
+ * around its own child-to-cell gather, keyed and shaped as a test chooses (tests/test_noise_rows_gpu.py holds it to the serial statement in
+ * include/gomoku_noise.h, gmk_noise_mix225, bit for bit).  One wavefront per row; lane l owns the cells l, l + 64, l + 128, l + 192.
+ *   d_priors   float[n][225] by cell, mixed IN PLACE; an entry equal to 0 is "no child": it takes no draw and stays 0 (so does an entry that
+ *              the scaling by 1 - epsilon rounds to 0)
+ *   d_draws    NULL, or float[n][225]: the gamma(alpha, 1) variate of every entry that took a draw, before the normalisation; 0 elsewhere
+ *   d_game_ids, d_stones   uint32[n]: words 0 and 1 of row i's counter (the GLOBAL game id and the stones on the root board); seed: the key
+ * n >= 0 (0: nothing happens); for n > 0 the pointers other than d_draws are non-null; every pointer is 4-byte aligned; alpha and epsilon as
+ * "Root noise parameters" above.  One launch on `stream`; the call does not wait. */
+int gmk_noise_mix_rows(float *d_priors, float *d_draws, const uint32_t *d_game_ids, const uint32_t *d_stones,
+                       int n, float alpha, float epsilon, uint64_t seed, void *stream);
 /* The handle's tree arenas, now: one arena per game (what the first gmk_mcts_set_roots allocates) or, two_arenas != 0, the two arenas per game of
  * the persistent loop with kept subtrees (what gmk_selfplay_run allocates).  Tens of GB, and the driver clears memory it has handed out before
  * (seconds per 24 GB): for callers that want that outside a region they time, or want the blocks in the library's pool before a batch starts

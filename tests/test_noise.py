@@ -1,6 +1,8 @@
 """The counter-based Dirichlet sampler of Default::AddNoise (include/gomoku_noise.h), on the CPU: the header as gcc compiled it into the oracle
 against an independent restatement in Python floats (IEEE binary64, the same operations in the same order), against libm, and against the
-distribution it claims to draw from.  The GPU side of the same header is held to the oracle by tests/test_selfplay_gpu.py."""
+distribution it claims to draw from.  The GPU side of the same header is held to the oracle, bit for bit, by tests/test_noise_rows_gpu.py (the
+mixing on rows a test supplies) and tests/test_root_noise_gpu.py (every searcher's kernel around it), and through game records by
+tests/test_selfplay_gpu.py."""
 import math
 import struct
 
@@ -172,3 +174,33 @@ def test_mix_is_add_noise(oracle):
     expect = (p * np.float32(1 - np.float32(0.25))).astype(np.float32) + np.float32(0.25) * (draws / nrm).astype(np.float32)
     assert (q == expect.astype(np.float32)).all()
     assert abs(float(np.sqrt((((q - p * np.float32(0.75)) / np.float32(0.25)).astype(np.float64) ** 2).sum())) - 1.0) < 1e-5      # a unit vector was mixed in
+
+
+def test_what_the_argument_rule_keeps_out(oracle):
+    """Why include/gomoku_hip.h ("Root noise parameters") refuses them: by the serial statement alpha = +inf and epsilon = NaN make every mixed prior
+    non-finite, and epsilon = 2 makes priors negative; the ends of epsilon's range are harmless."""
+    L = oracle.lib()
+
+    def mixed(alpha, epsilon):
+        q = np.full(225, np.float32(1) / np.float32(225), dtype=np.float32)
+        L.go_noise_mix225(q.ctypes.data, alpha, epsilon, 3, 17, 99)
+        return q
+    assert not np.isfinite(mixed(float("inf"), 0.25)).any()
+    assert np.isnan(mixed(0.05, float("nan"))).all()
+    assert (mixed(0.05, 2.0) < 0).any()
+    assert (mixed(0.05, 0.0) == np.float32(1) / np.float32(225)).all() and not mixed(0.05, 1.0).any()
+
+
+def test_set_root_noise_follows_the_rule():
+    """CorePyExt.set_root_noise: alpha 0 turns the noise off (epsilon is then ignored); any other alpha is finite and > 0 and epsilon lies in [0, 1]."""
+    from gomokuai_amd import core
+    try:
+        core.set_root_noise(0.3, 0.5)
+        for alpha, epsilon in ((-1.0, 0.25), (float("nan"), 0.25), (float("inf"), 0.25), (0.05, -0.5), (0.05, 2.0), (0.05, float("nan"))):
+            with pytest.raises(ValueError):
+                core.set_root_noise(alpha, epsilon)
+        core.set_root_noise(0.0, float("nan"))
+        core.set_root_noise(alpha=1.0, epsilon=1.0)
+        core.set_root_noise(alpha=2.5, epsilon=0.0)
+    finally:
+        core.set_root_noise(0.05, 0.25)
