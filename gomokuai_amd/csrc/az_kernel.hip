@@ -37,6 +37,7 @@
 #include "noise_device.h"
 #include "vcf_device.h"
 #include "../../include/gomoku_sample.h"
+#include "../../include/gomoku_gumbel.h"
 
 namespace {
 
@@ -355,6 +356,196 @@ __device__ bool az_defend_marks(const AzTree& t, size_t arena, AzHeader* hdr, co
     return true;
 }
 
+// ---- K21: Gumbel root search (gmk_az_set_gumbel; the rule and its serial statements are in include/gomoku_gumbel.h) ----
+// At the root a playout does not take PUCB's child but the one sequential halving schedules among the Gumbel-top-m children; below it the
+// descent is descend_from's, unchanged.  One wavefront per game, and the root is handled BY CELL, as the header states it: the root children's
+// prior, visits, value and index are scattered into LDS (GumbelLds), lane l owns the cells l + 64 j, and every step of the rule is the header's
+// function on a lane's cells plus a reduction over the wavefront.  Per game in HBM (AzGumbelGame): the base scores s_c, the visit snapshot and the
+// considered set, valid while ready[game] != 0.  Set-up is lazy: the first root step (or root choice) that finds children and ready == 0 makes
+// it -- ranks are counted against the 225 scores in LDS, nothing is sorted.  Whatever moves or replaces a root clears ready.
+struct AzGumbelGame {                            // 2936 B
+    double score[kCells];                        // s_c by cell
+    uint32_t base[kCells];                       // visits[c] at set-up
+    uint8_t considered[kCells], pad[3];
+    uint32_t m_eff, pad1;
+};
+static_assert(sizeof(AzGumbelGame) == 2936, "AzGumbelGame layout");
+struct AzGumbel {
+    AzGumbelGame* st;                            // [n_games]
+    uint32_t* ready;                             // [n_games]
+    const int32_t* slot_game;                    // as AzSample's
+    const uint32_t* game_ids;
+    uint32_t first_game_id, seed_lo, seed_hi;
+    int m, n;                                    // max_considered, n_sims
+    double c_visit, c_scale;
+};
+struct GumbelLds {
+    double score[kCells];
+    float prior[kCells];                         // 0: no child
+    uint32_t visits[kCells];
+    float value[kCells];
+    uint16_t child[kCells + 1];                  // the child's index among the root's children
+};
+__device__ __forceinline__ uint32_t gumbel_game_id(const AzGumbel& gm, int slot) {
+    return gm.first_game_id + (gm.slot_game ? static_cast<uint32_t>(max(gm.slot_game[slot], 0)) : gm.game_ids[slot]);
+}
+// The root's children by cell into L.  All 64 lanes, uniform control flow; L is complete on return.
+__device__ __forceinline__ void gumbel_load(GumbelLds& L, const uint2* kids, const uint2* stat, const float* prior, uint32_t first, uint32_t n, int lane) {
+    __syncthreads();                                             // nobody reads an older root's L any more
+    for (int c = lane; c < kCells; c += 64) { L.prior[c] = 0.0f; L.visits[c] = 0u; L.value[c] = 0.0f; L.child[c] = 0; }
+    __syncthreads();
+    for (uint32_t i = lane; i < n; i += 64) {
+        const uint32_t cell = (kids[first + i].y >> 8) & 0xFFu;
+        const uint2 s = stat[first + i];
+        L.prior[cell] = prior[first + i];
+        L.visits[cell] = s.x;
+        L.value[cell] = __uint_as_float(s.y);
+        L.child[cell] = static_cast<uint16_t>(i);
+    }
+    __syncthreads();
+}
+// gmk_gumbel_setup225 for the root in L, into st.  All 64 lanes; st is written and visible to the wavefront on return.
+__device__ __forceinline__ void gumbel_setup(GumbelLds& L, AzGumbelGame& st, const AzGumbel& gm, uint32_t game_id, uint32_t stones, uint32_t n, int lane) {
+#pragma unroll 1
+    for (int c = lane; c < kCells; c += 64)
+        L.score[c] = L.prior[c] != 0.0f ? gmk_gumbel_score(L.prior[c], game_id, stones, static_cast<uint32_t>(c), gm.seed_lo, gm.seed_hi) : 0.0;
+    __syncthreads();
+#pragma unroll 1
+    for (int c = lane; c < kCells; c += 64) {
+        const bool child = L.prior[c] != 0.0f;
+        int rank = 0;
+        if (child) {
+            const double mine = L.score[c];
+            for (int b = 0; b < kCells; ++b) rank += (L.prior[b] != 0.0f && gmk_gumbel_before(L.score[b], b, mine, c)) ? 1 : 0;
+        }
+        st.score[c] = L.score[c];
+        st.base[c] = L.visits[c];
+        st.considered[c] = (child && rank < gm.m) ? 1 : 0;
+    }
+    if (lane == 0) st.m_eff = min(n, static_cast<uint32_t>(gm.m));
+    __threadfence_block();
+    __syncthreads();
+}
+// What pick and move read of the root: per cell of this lane the key s_c + sigma_c, r_c and whether it is considered; over the wavefront
+// t = the sum of r_c, the smallest and the largest r_c of a considered child, and whether there is one.
+struct GumbelView { double key[4]; uint32_t r[4]; bool cons[4]; uint32_t t, least, most; bool any; };
+__device__ __forceinline__ GumbelView gumbel_view(const GumbelLds& L, const AzGumbelGame& st, const AzGumbel& gm, float root_value, int lane) {
+    GumbelView g;
+    uint32_t top = 0u;
+    g.t = 0u; g.least = 0xFFFFFFFFu; g.most = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = lane + 64 * j;
+        const bool child = c < kCells && L.prior[c] != 0.0f;
+        g.cons[j] = child && st.considered[c] != 0;
+        g.r[j] = child ? L.visits[c] - st.base[c] : 0u;
+        g.t += g.r[j];
+        if (child) top = max(top, L.visits[c]);
+        if (g.cons[j]) { g.least = min(g.least, g.r[j]); g.most = max(g.most, g.r[j]); }
+    }
+    g.t = wave_sum(g.t);
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        top = max(top, static_cast<uint32_t>(__shfl_xor(static_cast<int>(top), s)));
+        g.least = min(g.least, static_cast<uint32_t>(__shfl_xor(static_cast<int>(g.least), s)));
+        g.most = max(g.most, static_cast<uint32_t>(__shfl_xor(static_cast<int>(g.most), s)));
+    }
+    g.any = g.least != 0xFFFFFFFFu;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = lane + 64 * j;
+        g.key[j] = g.cons[j] ? st.score[c] + gmk_gumbel_sigma(gm.c_visit, gm.c_scale, top, gmk_gumbel_qhat(L.visits[c], L.value[c], root_value)) : 0.0;
+    }
+    return g;
+}
+// gmk_gumbel_best225: the cell, -1 when no considered child has that count; the same in every lane
+__device__ __forceinline__ int gumbel_best(const GumbelView& g, uint32_t count, int lane) {
+    constexpr int kNone = 0x7FFFFFFF;
+    double best_key = 0.0;
+    int best = kNone;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (g.cons[j] && g.r[j] == count && (best == kNone || g.key[j] > best_key)) { best_key = g.key[j]; best = lane + 64 * j; }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const double ok = __shfl_xor(best_key, s);
+        const int oc = __shfl_xor(best, s);
+        if (oc != kNone && (best == kNone || ok > best_key || (ok == best_key && oc < best))) { best_key = ok; best = oc; }
+    }
+    return best == kNone ? -1 : best;
+}
+// gmk_gumbel_pick225 / gmk_gumbel_move225
+__device__ __forceinline__ int gumbel_pick(const GumbelView& g, const AzGumbelGame& st, const AzGumbel& gm, int lane) {
+    if (!g.any) return -1;
+    if (g.t < static_cast<uint32_t>(gm.n)) {
+        const int cell = gumbel_best(g, gmk_gumbel_sequence_at(static_cast<int>(st.m_eff), gm.n, static_cast<int>(g.t)), lane);
+        if (cell >= 0) return cell;
+    }
+    return gumbel_best(g, g.least, lane);
+}
+__device__ __forceinline__ int gumbel_move(const GumbelView& g, int lane) { return g.any ? gumbel_best(g, g.most, lane) : -1; }
+// gmk_gumbel_row225 into out[225]; all 64 lanes
+__device__ __forceinline__ void gumbel_row(const GumbelLds& L, const AzGumbel& gm, float root_value, uint16_t* out, int lane) {
+    uint32_t top_v = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = lane + 64 * j;
+        if (c < kCells && L.prior[c] != 0.0f) top_v = max(top_v, L.visits[c]);
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) top_v = max(top_v, static_cast<uint32_t>(__shfl_xor(static_cast<int>(top_v), s)));
+    double x[4], top = 0.0;
+    bool child[4], any = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = lane + 64 * j;
+        child[j] = c < kCells && L.prior[c] != 0.0f;
+        x[j] = 0.0;
+        if (!child[j]) continue;
+        x[j] = gmk_gumbel_logit(L.prior[c]) + gmk_gumbel_sigma(gm.c_visit, gm.c_scale, top_v, gmk_gumbel_qhat(L.visits[c], L.value[c], root_value));
+        if (!any || x[j] > top) top = x[j];
+        any = true;
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const double ot = __shfl_xor(top, s);
+        const bool oa = __shfl_xor(static_cast<int>(any), s) != 0;
+        if (oa && (!any || ot > top)) top = ot;
+        any = any || oa;
+    }
+    double e[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) e[j] = child[j] ? gmk_noise_exp(x[j] - top) : 0.0;
+    double p = e[0];                                             // gmk_gumbel_sum225: the lane's cells in order, a tree inside every row of 16 lanes, the four rows
+#pragma unroll
+    for (int j = 1; j < 4; ++j) if (lane + 64 * j < kCells) p += e[j];
+#pragma unroll
+    for (int off = 8; off >= 1; off >>= 1) {
+        const double other = __shfl_down(p, off, 16);
+        p = p + (((lane & 15) + off < 16) ? other : 0.0);
+    }
+    const double z = (__shfl(p, 0) + __shfl(p, 16)) + (__shfl(p, 32) + __shfl(p, 48));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = lane + 64 * j;
+        if (c < kCells) out[c] = child[j] ? gmk_gumbel_weight(e[j], z) : static_cast<uint16_t>(0);
+    }
+}
+// The root choice of the Gumbel forms of az_advance_kernel and az_root_choice_kernel: L is loaded, a root whose set-up is missing (was_ready == 0:
+// nothing was searched since it became the root) gets it, and the move follows.  The child's index, 0xFFFFFFFF on a root without children.
+__device__ __forceinline__ uint32_t gumbel_child(GumbelLds& L, const AzTree& t, size_t base, uint32_t first, uint32_t n, int lane, uint32_t stones, int slot,
+                                                 const AzGumbel& gm, uint32_t was_ready) {
+    if (n == 0u) return 0xFFFFFFFFu;
+    gumbel_load(L, t.kids + base, t.stat + base, t.prior + base, first, n, lane);
+    AzGumbelGame& st = gm.st[slot];
+    if (was_ready == 0u) gumbel_setup(L, st, gm, gumbel_game_id(gm, slot), stones, n, lane);
+    const GumbelView g = gumbel_view(L, st, gm, __uint_as_float(t.stat[base].y), lane);
+    const int cell = gumbel_move(g, lane);
+    return cell < 0 ? 0xFFFFFFFFu : static_cast<uint32_t>(L.child[cell]);
+}
+template <class... Extra>
+constexpr bool kIsGumbel = (std::is_same_v<Extra, AzGumbel> || ...);
+
 // ---- Several leaves per game per step, with virtual loss (GMK_OPT_AZ_LEAVES = L > 1) ----
 // A search of few games gives the network a batch of few rows; with L leaves per game a step carries live x L rows and a search of P playouts
 // takes about P / L steps.  The descents of one step are steered apart by a per-node in-flight count v (a side array, all zero between
@@ -399,10 +590,10 @@ __device__ __forceinline__ PendingLeaf pending_leaf(const AzTree& t, const AzLea
 // kProof: the descent stops at a proven node below the root (stopped: its proof), children marked LOSES are taken and children marked WINS
 // avoided.  kInflight: the in-flight counts steer it (the formula above); <.., false> neither loads nor adds them.
 struct Descent { uint32_t node; int stones; uint32_t last, last2, stopped; };     // where it ended, with the position's stone count and last two moves
+// descend_from: the same from the node d names, whose stones are in s_rows already (K21: the root step is not PUCB's).
 template <bool kProof, bool kInflight>
-__device__ __forceinline__ Descent descend(const uint2* stat, const uint2* kids, const float* prior, const uint16_t* inflight, uint32_t* s_rows, double c_puct,
-                                           int stones, uint32_t last, uint32_t last2, int lane) {
-    Descent d{0u, stones, last, last2, GMK_AZ_PROOF_NONE};
+__device__ __forceinline__ Descent descend_from(Descent d, const uint2* stat, const uint2* kids, const float* prior, const uint16_t* inflight, uint32_t* s_rows,
+                                                double c_puct, int lane) {
     for (;;) {
         const uint2 k = kids[d.node];
         if constexpr (kProof) {
@@ -451,6 +642,11 @@ __device__ __forceinline__ Descent descend(const uint2* stat, const uint2* kids,
         d.last = cell;
     }
     return d;
+}
+template <bool kProof, bool kInflight>
+__device__ __forceinline__ Descent descend(const uint2* stat, const uint2* kids, const float* prior, const uint16_t* inflight, uint32_t* s_rows, double c_puct,
+                                           int stones, uint32_t last, uint32_t last2, int lane) {
+    return descend_from<kProof, kInflight>(Descent{0u, stones, last, last2, GMK_AZ_PROOF_NONE}, stat, kids, prior, inflight, s_rows, c_puct, lane);
 }
 
 // Board::checkGameEnd (Game.cpp:88-136): five through the last stone (winner: +1 black, -1 white), or a full board
@@ -577,6 +773,52 @@ void az_select_kernel(AzTree t, float* __restrict__ out_states) {
     const Descent d = descend<kProof, false>(t.stat + arena, t.kids + arena, t.prior + arena, nullptr, s_rows, t.c_puct, static_cast<int>(hdr->stones),
                                              hdr->last_move, hdr->last_move2, lane);
     if (settled_at_once<kProof>(t, arena, hdr, s_rows, d, lane)) {                     // no network row
+        if (lane == 0) hdr->leaf_pending = 0;
+        if (out_states) zero_row(out_states + row * 6 * kCells, lane);
+        return;
+    }
+    if (lane == 0) { hdr->leaf = d.node; hdr->leaf_pending = 1; hdr->leaf_stones = static_cast<uint32_t>(d.stones); }
+    if (lane < 16) hdr->leaf_rows[lane] = s_rows[lane];
+    write_planes(out_states + row * 6 * kCells, s_rows, d.stones, d.last, d.last2, lane);
+}
+
+// K21: az_select_kernel<false> with the Gumbel root step.  A root without children is the leaf, as it is there: the playout that expands it is
+// just a playout, and the next one makes the set-up.
+__global__ __launch_bounds__(64)
+void az_select_gumbel_kernel(AzTree t, float* __restrict__ out_states, AzGumbel gm) {
+    __shared__ uint32_t s_rows[16];
+    __shared__ GumbelLds s_g;
+    const int game = blockIdx.x, lane = threadIdx.x;
+    if (game >= t.n_games) return;
+    AzHeader* hdr = t.hdr + game;
+    if (hdr->status & kStatusOver) return;
+    const size_t row = static_cast<size_t>(t.row_of[game]);
+    const size_t arena = static_cast<size_t>(game) * t.cap;
+    if (lane < 16) s_rows[lane] = hdr->rows[lane];
+    __syncthreads();
+    Descent d{0u, static_cast<int>(hdr->stones), hdr->last_move, hdr->last_move2, GMK_AZ_PROOF_NONE};
+    const uint2 rk = t.kids[arena];
+    const uint32_t first = rk.x, n = rk.y & 0xFFu;
+    if (n != 0u) {
+        gumbel_load(s_g, t.kids + arena, t.stat + arena, t.prior + arena, first, n, lane);
+        AzGumbelGame& st = gm.st[game];
+        if (gm.ready[game] == 0u) {
+            gumbel_setup(s_g, st, gm, gumbel_game_id(gm, game), hdr->stones, n, lane);
+            if (lane == 0) gm.ready[game] = 1u;
+        }
+        const GumbelView g = gumbel_view(s_g, st, gm, __uint_as_float(t.stat[arena].y), lane);
+        const int cell = gumbel_pick(g, st, gm, lane);              // (never -1: a root with children has a considered one)
+        if (cell >= 0) {
+            d.node = first + s_g.child[cell];
+            if (lane == 0) s_rows[cell / 15] |= 1u << (cell % 15 + ((d.stones & 1) ? 16 : 0));
+            __syncthreads();
+            ++d.stones;
+            d.last2 = d.last;
+            d.last = static_cast<uint32_t>(cell);
+            d = descend_from<false, false>(d, t.stat + arena, t.kids + arena, t.prior + arena, nullptr, s_rows, t.c_puct, lane);
+        }
+    }
+    if (settled_at_once<false>(t, arena, hdr, s_rows, d, lane)) {
         if (lane == 0) hdr->leaf_pending = 0;
         if (out_states) zero_row(out_states + row * 6 * kCells, lane);
         return;
@@ -1035,7 +1277,8 @@ void az_step_kernel(AzTree t, AzArena b, const int16_t* forced) {
 // game goes on, and the tree is re-rooted: the child's subtree into the other arena (reuse) or a new root.  A root without a visited
 // child ends the game where it stands.  Finished games leave a childless root behind in both arenas, so that no kernel ever walks a
 // stale tree.  One wavefront per game.
-// Sample: nothing, or one AzSample (K20): the plies before its S are drawn by sampled_child, and nothing else changes.
+// Sample: nothing, or one AzSample (K20): the plies before its S are drawn by sampled_child, and nothing else changes.  Or one AzGumbel (K21): the
+// move is the Gumbel rule's, the row written is the improved-policy row, and the slot's ready word is cleared.
 template <bool kProof, class... Sample>
 __global__ __launch_bounds__(64)
 void az_advance_kernel(AzTree t, AzArena b, uint8_t* __restrict__ rec_moves, uint16_t* __restrict__ rec_visits, int32_t* __restrict__ rec_lens,
@@ -1046,13 +1289,24 @@ void az_advance_kernel(AzTree t, AzArena b, uint8_t* __restrict__ rec_moves, uin
     AzHeader& hdr = t.hdr[slot];
     const size_t base = static_cast<size_t>(slot) * t.cap;
     const int game = sl.slot_game ? sl.slot_game[slot] : slot;      // the rows of the records
+    GumbelLds* gl = nullptr;
+    uint32_t was_ready = 0u;
+    if constexpr (kIsGumbel<Sample...>) {
+        __shared__ GumbelLds s_g;
+        gl = &s_g;
+        was_ready = (sm.ready[slot], ...);
+        __syncthreads();                                         // every lane has read the word
+        if (lane == 0) ((sm.ready[slot] = 0u), ...);
+    }
     if ((hdr.status & kStatusOver) || game < 0) {
         if (reuse && lane == 0) new_root(b, base, 0u);
         return;
     }
     const uint2 rk = t.kids[base];
     const uint32_t first = rk.x, n = rk.y & 0xFFu;
-    const uint32_t best_i = root_child<kProof>(t.kids + base, t.stat + base, first, n, lane, hdr, slot, sm...);
+    uint32_t best_i;
+    if constexpr (kIsGumbel<Sample...>) best_i = gumbel_child(*gl, t, base, first, n, lane, hdr.stones, slot, sm..., was_ready);
+    else best_i = root_child<kProof>(t.kids + base, t.stat + base, first, n, lane, hdr, slot, sm...);
     const uint32_t stones = hdr.stones;
     const int len = rec_lens[game];
     bool over = best_i == 0xFFFFFFFFu || stones >= 225u || len >= 225;                 // nothing the search wants to play
@@ -1060,7 +1314,11 @@ void az_advance_kernel(AzTree t, AzArena b, uint8_t* __restrict__ rec_moves, uin
     uint32_t cell = 255u;
     if (!over) {
         cell = (t.kids[base + first + best_i].y >> 8) & 0xFFu;
-        if (rec_visits) visits_by_cell(rec_visits + (static_cast<size_t>(game) * kCells + static_cast<size_t>(len)) * kCells, t.kids + base, t.stat + base, first, n, lane);
+        if constexpr (kIsGumbel<Sample...>) {
+            if (rec_visits) gumbel_row(*gl, sm..., __uint_as_float(t.stat[base].y), rec_visits + (static_cast<size_t>(game) * kCells + static_cast<size_t>(len)) * kCells, lane);
+        } else {
+            if (rec_visits) visits_by_cell(rec_visits + (static_cast<size_t>(game) * kCells + static_cast<size_t>(len)) * kCells, t.kids + base, t.stat + base, first, n, lane);
+        }
         const int shift = (stones & 1u) ? 16 : 0;                // black moves on even stone counts
         if (lane < 16) s_rows[lane] = hdr.rows[lane] | ((lane == static_cast<int>(cell / 15u)) ? 1u << (cell % 15u + shift) : 0u);
         __syncthreads();
@@ -1199,7 +1457,8 @@ void az_root_noise_kernel(AzTree t, const int32_t* __restrict__ slot_game, const
 // The cell MCTS::stepForward() would play for every game, left ON THE DEVICE for the match referee (match_kernel.hip): the most visited root
 // child, first maximum in child (= cell) order, exactly az_advance_kernel's choice; -1 for a root without a visited child.  visits (may be
 // null): the root children's visit counts by cell, saturated like the records' rows.  One wavefront per game.
-// Sample: nothing, or one AzSample (K20): az_advance_kernel's sampled choice.
+// Sample: nothing, or one AzSample (K20): az_advance_kernel's sampled choice.  Or one AzGumbel (K21): its Gumbel choice, `visits` gets the
+// improved-policy row (zeros for a root without children), and the game's ready word is cleared.
 template <bool kProof, class... Sample>
 __global__ __launch_bounds__(64)
 void az_root_choice_kernel(AzTree t, int16_t* __restrict__ cells, uint16_t* __restrict__ visits, Sample... sm) {
@@ -1208,9 +1467,22 @@ void az_root_choice_kernel(AzTree t, int16_t* __restrict__ cells, uint16_t* __re
     const size_t base = static_cast<size_t>(game) * t.cap;
     const uint2 rk = t.kids[base];
     const uint32_t first = rk.x, n = rk.y & 0xFFu;
-    const uint32_t best_i = root_child<kProof>(t.kids + base, t.stat + base, first, n, lane, t.hdr[game], game, sm...);
-    if (lane == 0) cells[game] = best_i == 0xFFFFFFFFu ? static_cast<int16_t>(-1) : static_cast<int16_t>((t.kids[base + first + best_i].y >> 8) & 0xFFu);
-    if (visits) visits_by_cell(visits + static_cast<size_t>(game) * kCells, t.kids + base, t.stat + base, first, n, lane);
+    if constexpr (kIsGumbel<Sample...>) {
+        __shared__ GumbelLds s_g;
+        const uint32_t was_ready = (sm.ready[game], ...);
+        __syncthreads();                                         // every lane has read the word
+        if (lane == 0) ((sm.ready[game] = 0u), ...);
+        const uint32_t best_i = gumbel_child(s_g, t, base, first, n, lane, t.hdr[game].stones, game, sm..., was_ready);
+        if (lane == 0) cells[game] = best_i == 0xFFFFFFFFu ? static_cast<int16_t>(-1) : static_cast<int16_t>((t.kids[base + first + best_i].y >> 8) & 0xFFu);
+        if (visits) {
+            if (n != 0u) gumbel_row(s_g, sm..., __uint_as_float(t.stat[base].y), visits + static_cast<size_t>(game) * kCells, lane);
+            else for (int i = lane; i < kCells; i += 64) visits[static_cast<size_t>(game) * kCells + i] = 0;
+        }
+    } else {
+        const uint32_t best_i = root_child<kProof>(t.kids + base, t.stat + base, first, n, lane, t.hdr[game], game, sm...);
+        if (lane == 0) cells[game] = best_i == 0xFFFFFFFFu ? static_cast<int16_t>(-1) : static_cast<int16_t>((t.kids[base + first + best_i].y >> 8) & 0xFFu);
+        if (visits) visits_by_cell(visits + static_cast<size_t>(game) * kCells, t.kids + base, t.stat + base, first, n, lane);
+    }
 }
 
 // gmk_az_step with the cells and the referee's verdicts (GMK_MATCH_*) read from device memory.  A game that moved follows the move -- the
@@ -1336,6 +1608,8 @@ struct gmk_az {
     bool proof = false;                                          // GMK_OPT_AZ_PROOF: the <true> proof instantiations are launched
     bool defend = false;                                         // GMK_OPT_AZ_VCF_DEFEND; it acts only with D > 0 and proof (az_defend_active)
     AzDefend df{};                                               //   its buffers come when it first acts
+    bool gumbel = false;                                         // K21: gmk_az_set_gumbel with max_considered > 0
+    AzGumbel gm{};                                               //   its parameters; st and ready come with the first use
     // device scratch of the host-driven form (gmk_az_select_host / gmk_az_expand_host)
     float *h_states = nullptr, *h_values = nullptr, *h_probs = nullptr;
     int16_t* h_paths = nullptr;
@@ -1351,6 +1625,7 @@ extern "C" int gmk_az_destroy(gmk_az* a) {
     (void)gmk::device_free(a->h_states); (void)gmk::device_free(a->h_values); (void)gmk::device_free(a->h_probs); (void)gmk::device_free(a->h_paths); (void)gmk::device_free(a->h_lens);
     (void)gmk::device_free(a->lv.inflight); (void)gmk::device_free(a->lv.pend); (void)gmk::device_free(a->d_owed);
     (void)gmk::device_free(a->vcf.verdict);
+    (void)gmk::device_free(a->gm.st); (void)gmk::device_free(a->gm.ready);
     (void)gmk::device_free(a->df.threat); (void)gmk::device_free(a->df.pv); (void)gmk::device_free(a->df.occupied); (void)gmk::device_free(a->df.cells);
     delete a;
     return GMK_OK;
@@ -1417,6 +1692,21 @@ static int az_reset_leaves(gmk_az* a) {
     return GMK_OK;
 }
 
+// K21: the roots have moved or been replaced, so every set-up is void: a clear of the ready words behind the caller's launches, on their stream.
+// With Gumbel off nothing is issued.
+static int az_gumbel_clear(gmk_az* a, hipStream_t s) {
+    if (!a->gumbel) return GMK_OK;
+    GMK_HIP_CHECK(hipMemsetAsync(a->gm.ready, 0, static_cast<size_t>(a->t.n_games) * 4, s));
+    return GMK_OK;
+}
+// the kernels' AzGumbel: the handle's parameters and the games its slots play now
+static AzGumbel az_gumbel_args(const gmk_az* a) {
+    AzGumbel g = a->gm;
+    g.slot_game = a->slots.slot_game;
+    g.game_ids = a->d_game_ids;
+    return g;
+}
+
 extern "C" int gmk_az_live_games(gmk_az* a, int32_t* n_live) {
     if (!a || !n_live) { gmk::set_error("gmk_az_live_games: bad arguments"); return GMK_ERR_ARG; }
     *n_live = a->n_live;
@@ -1453,6 +1743,7 @@ extern "C" int gmk_az_set_roots(gmk_az* a, const uint16_t* h_planes, const int16
     if (const int rc = az_reset_leaves(a); rc != GMK_OK) return rc;
     hipLaunchKernelGGL(az_init_roots_kernel, dim3((a->t.n_games + 255) / 256), dim3(256), 0, nullptr, a->t);
     GMK_HIP_CHECK(hipGetLastError());
+    if (const int rc = az_gumbel_clear(a, nullptr); rc != GMK_OK) return rc;
     GMK_HIP_CHECK(hipDeviceSynchronize());
     a->rooted = true;
     if (const int rc = az_compact(a, nullptr); rc != GMK_OK) return rc;
@@ -1517,6 +1808,7 @@ extern "C" int gmk_az_set_slots(gmk_az* a, int n_total, const uint8_t* h_open_mo
     if (const int rc = az_reset_leaves(a); rc != GMK_OK) return rc;
     hipLaunchKernelGGL(az_init_roots_kernel, dim3((a->t.n_games + 255) / 256), dim3(256), 0, nullptr, a->t);
     GMK_HIP_CHECK(hipGetLastError());
+    if (const int rc = az_gumbel_clear(a, nullptr); rc != GMK_OK) return rc;
     GMK_HIP_CHECK(hipDeviceSynchronize());
     for (size_t g = 0; g < ns; ++g) a->game_ids[g] = state[g] >= 0 ? static_cast<uint32_t>(state[g]) : 0u;
     if (const int rc = az_upload_game_ids(a); rc != GMK_OK) return rc;
@@ -1593,6 +1885,11 @@ extern "C" int gmk_az_select(gmk_az* a, float* d_states, void* stream) {
         hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, a->lv, d_states);
         GMK_HIP_CHECK(hipGetLastError());
         a->select_issued = true;
+        return az_vcf_leaves(a, stream);
+    }
+    if (a->gumbel) {                                             // K21 (one leaf, no proofs: gmk_az_set_gumbel and gmk_az_set_option see to it)
+        hipLaunchKernelGGL(az_select_gumbel_kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_states, az_gumbel_args(a));
+        GMK_HIP_CHECK(hipGetLastError());
         return az_vcf_leaves(a, stream);
     }
     const auto kernel = az_proof_variant(a, [](auto proof) { return &az_select_kernel<proof>; });
@@ -1675,6 +1972,7 @@ extern "C" int gmk_az_step(gmk_az* a, const int16_t* h_moves) {
     const auto kernel = az_proof_variant(a, [](auto proof) { return &az_step_kernel<proof>; });
     hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, nullptr, a->t, a->other, h_moves ? a->d_forced : nullptr);
     GMK_HIP_CHECK(hipGetLastError());
+    if (const int rc = az_gumbel_clear(a, nullptr); rc != GMK_OK) return rc;
     GMK_HIP_CHECK(hipDeviceSynchronize());
     az_flip_arenas(a);
     return GMK_OK;
@@ -1691,9 +1989,11 @@ static int az_sample_args(const gmk_az* a, const char* who, int sample_plies, in
 }
 
 // gmk_az_root_choice and gmk_az_root_choice_sampled (sm: null, or what is to be sampled): one launch on `stream`
-static int az_root_choice(gmk_az* a, const char* who, int16_t* d_cells, uint16_t* d_visits, const AzSample* sm, void* stream) {
+static int az_root_choice(gmk_az* a, const char* who, int16_t* d_cells, uint16_t* d_visits, const AzSample* sm, void* stream, const AzGumbel* gm = nullptr) {
     if (!a->rooted) { gmk::set_error("%s: gmk_az_set_roots has not been called", who); return GMK_ERR_STATE; }
-    if (sm && sm->plies != 0u) {
+    if (gm) {
+        hipLaunchKernelGGL((az_root_choice_kernel<false, AzGumbel>), dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_cells, d_visits, *gm);
+    } else if (sm && sm->plies != 0u) {
         const auto kernel = az_proof_variant(a, [](auto proof) { return &az_root_choice_kernel<proof, AzSample>; });
         hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, static_cast<hipStream_t>(stream), a->t, d_cells, d_visits, *sm);
     } else {
@@ -1730,6 +2030,7 @@ extern "C" int gmk_az_step_device(gmk_az* a, const int16_t* d_cells, const int32
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(az_step_device_kernel, dim3(a->t.n_games), dim3(64), 0, s, a->t, a->other, d_cells, d_verdict, fresh_root ? 1 : 0);
     GMK_HIP_CHECK(hipGetLastError());
+    if (const int rc = az_gumbel_clear(a, s); rc != GMK_OK) return rc;
     int32_t unfinished = 0;
     if (h_unfinished) GMK_HIP_CHECK(hipMemcpyAsync(&unfinished, d_unfinished, 4, hipMemcpyDeviceToHost, s));
     if (const int rc = az_compact(a, s); rc != GMK_OK) return rc;   // (synchronises)
@@ -1741,7 +2042,7 @@ extern "C" int gmk_az_step_device(gmk_az* a, const int16_t* d_cells, const int32
 // One self-play move of every game still played (az_advance_kernel).  h_unfinished: the games that go on.  sm: null (gmk_az_advance), or what
 // gmk_az_advance_sampled is to sample.
 static int az_advance(gmk_az* a, const char* who, uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int reuse_subtree, const AzSample* sm,
-                      int32_t* h_unfinished, void* stream) {
+                      int32_t* h_unfinished, void* stream, const AzGumbel* gm = nullptr) {
     if (!a->rooted) { gmk::set_error("%s: gmk_az_set_roots has not been called", who); return GMK_ERR_STATE; }
     if (az_marks_up(a, who)) return GMK_ERR_STATE;
     if (reuse_subtree)
@@ -1749,7 +2050,10 @@ static int az_advance(gmk_az* a, const char* who, uint8_t* d_moves, uint16_t* d_
     if (!a->d_unfinished) GMK_HIP_CHECK(gmk::device_malloc(&a->d_unfinished, 4));
     hipStream_t s = static_cast<hipStream_t>(stream);
     GMK_HIP_CHECK(hipMemsetAsync(a->d_unfinished, 0, 4, s));
-    if (sm && sm->plies != 0u) {
+    if (gm) {                                                    // K21: the kernel clears the ready words itself
+        hipLaunchKernelGGL((az_advance_kernel<false, AzGumbel>), dim3(a->t.n_games), dim3(64), 0, s, a->t, a->other, d_moves, d_visits, d_lens, d_winner, a->d_unfinished,
+                           reuse_subtree ? 1 : 0, a->slots, *gm);
+    } else if (sm && sm->plies != 0u) {
         const auto kernel = az_proof_variant(a, [](auto proof) { return &az_advance_kernel<proof, AzSample>; });
         hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, s, a->t, a->other, d_moves, d_visits, d_lens, d_winner, a->d_unfinished, reuse_subtree ? 1 : 0, a->slots, *sm);
     } else {
@@ -1757,6 +2061,8 @@ static int az_advance(gmk_az* a, const char* who, uint8_t* d_moves, uint16_t* d_
         hipLaunchKernelGGL(kernel, dim3(a->t.n_games), dim3(64), 0, s, a->t, a->other, d_moves, d_visits, d_lens, d_winner, a->d_unfinished, reuse_subtree ? 1 : 0, a->slots);
     }
     GMK_HIP_CHECK(hipGetLastError());
+    if (!gm)
+        if (const int rc = az_gumbel_clear(a, s); rc != GMK_OK) return rc;
     int32_t unfinished = 0;
     GMK_HIP_CHECK(hipMemcpyAsync(&unfinished, a->d_unfinished, 4, hipMemcpyDeviceToHost, s));
     if (const int rc = az_compact(a, s); rc != GMK_OK) return rc;   // (synchronises: both numbers are here now, and they agree)
@@ -1798,8 +2104,137 @@ extern "C" int gmk_move_sample_host(const uint32_t* h_visits, const int8_t* h_pr
     return GMK_OK;
 }
 
+// ---- K21: the option, the two entries that move by the rule, and the header's statements on the host ----
+extern "C" int gmk_az_set_gumbel(gmk_az* a, int max_considered, int n_sims, double c_visit, double c_scale, uint64_t seed, uint32_t first_game_id) {
+    if (!a) { gmk::set_error("gmk_az_set_gumbel: bad arguments"); return GMK_ERR_ARG; }
+    if (max_considered == 0) {                                   // off: every entry launches what it launched before
+        a->gumbel = false;
+        return GMK_OK;
+    }
+    if (max_considered < 1 || max_considered > kCells || n_sims < 1 || n_sims > GMK_GUMBEL_MAX_SIMS || !(c_visit >= 0.0 && c_visit <= 1e300) || !(c_scale >= 0.0 && c_scale <= 1e300)) {
+        gmk::set_error("gmk_az_set_gumbel: max_considered takes 0 (off) .. 225, n_sims 1 .. %d, c_visit and c_scale finite values >= 0; not %d, %d, %g, %g", GMK_GUMBEL_MAX_SIMS,
+                       max_considered, n_sims, c_visit, c_scale);
+        return GMK_ERR_ARG;
+    }
+    if (a->lv.leaves > 1) { gmk::set_error("gmk_az_set_gumbel: the Gumbel root search takes one leaf per step (GMK_OPT_AZ_LEAVES = %d)", a->lv.leaves); return GMK_ERR_STATE; }
+    if (a->proof) { gmk::set_error("gmk_az_set_gumbel: the Gumbel root search does not carry proofs (GMK_OPT_AZ_PROOF = 1)"); return GMK_ERR_STATE; }
+    const size_t n = static_cast<size_t>(a->t.n_games);
+    GMK_HIP_CHECK(hipDeviceSynchronize());
+    if (!a->gm.st) {
+        if (gmk::device_malloc(&a->gm.st, n * sizeof(AzGumbelGame)) != hipSuccess || gmk::device_malloc(&a->gm.ready, n * 4) != hipSuccess) {
+            (void)gmk::device_free(a->gm.st); (void)gmk::device_free(a->gm.ready);
+            a->gm.st = nullptr; a->gm.ready = nullptr;
+            (void)hipGetLastError();
+            gmk::set_error("gmk_az_set_gumbel: hipMalloc of the per-game state (%zu games) failed", n);
+            return GMK_ERR_HIP;
+        }
+    }
+    GMK_HIP_CHECK(hipMemset(a->gm.ready, 0, n * 4));             // other parameters, other set-ups
+    a->gm.first_game_id = first_game_id;
+    a->gm.seed_lo = static_cast<uint32_t>(seed);
+    a->gm.seed_hi = static_cast<uint32_t>(seed >> 32);
+    a->gm.m = max_considered;
+    a->gm.n = n_sims;
+    a->gm.c_visit = c_visit;
+    a->gm.c_scale = c_scale;
+    a->gumbel = true;
+    return GMK_OK;
+}
+
+extern "C" int gmk_az_root_choice_gumbel(gmk_az* a, int16_t* d_cells, uint16_t* d_visits, void* stream) {
+    if (!a || !d_cells) { gmk::set_error("gmk_az_root_choice_gumbel: bad arguments"); return GMK_ERR_ARG; }
+    if (!a->gumbel) { gmk::set_error("gmk_az_root_choice_gumbel: the Gumbel root search is off (gmk_az_set_gumbel)"); return GMK_ERR_STATE; }
+    const AzGumbel gm = az_gumbel_args(a);
+    return az_root_choice(a, "gmk_az_root_choice_gumbel", d_cells, d_visits, nullptr, stream, &gm);
+}
+
+extern "C" int gmk_az_advance_gumbel(gmk_az* a, uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int reuse_subtree, int32_t* h_unfinished,
+                                     void* stream) {
+    if (!a || !d_moves || !d_lens || !d_winner) { gmk::set_error("gmk_az_advance_gumbel: bad arguments"); return GMK_ERR_ARG; }
+    if (!a->gumbel) { gmk::set_error("gmk_az_advance_gumbel: the Gumbel root search is off (gmk_az_set_gumbel)"); return GMK_ERR_STATE; }
+    const AzGumbel gm = az_gumbel_args(a);
+    return az_advance(a, "gmk_az_advance_gumbel", d_moves, d_visits, d_lens, d_winner, reuse_subtree, nullptr, h_unfinished, stream, &gm);
+}
+
+// The statements of include/gomoku_gumbel.h for n roots given by rows, on the host: they need no GPU and no gmk_init
+static bool gumbel_rule_args(const char* who, int n, bool pointers, double c_visit, double c_scale) {
+    if (n < 0 || (n > 0 && !pointers) || !(c_visit >= 0.0 && c_visit <= 1e300) || !(c_scale >= 0.0 && c_scale <= 1e300)) {
+        gmk::set_error("%s: bad arguments (n >= 0, no NULL row with n > 0, c_visit and c_scale finite and >= 0)", who);
+        return false;
+    }
+    return true;
+}
+extern "C" int gmk_gumbel_sequence_host(int m_eff, int n_sims, uint32_t* h_seq) {
+    if (m_eff < 1 || m_eff > kCells || n_sims < 1 || n_sims > GMK_GUMBEL_MAX_SIMS || !h_seq) {
+        gmk::set_error("gmk_gumbel_sequence_host: bad arguments (m_eff 1 .. 225, n_sims 1 .. %d)", GMK_GUMBEL_MAX_SIMS);
+        return GMK_ERR_ARG;
+    }
+    gmk_gumbel_sequence(m_eff, n_sims, h_seq);
+    for (int t = 0; t < n_sims; ++t)                             // the kernels walk the phases instead of keeping the sequence: the two must agree
+        if (gmk_gumbel_sequence_at(m_eff, n_sims, t) != h_seq[t]) { gmk::set_error("gmk_gumbel_sequence_host: the walk disagrees with the sequence at %d", t); return GMK_ERR_STATE; }
+    return GMK_OK;
+}
+extern "C" int gmk_gumbel_setup_host(const float* h_prior, const uint32_t* h_visits, const int32_t* h_stones, const uint32_t* h_game_ids, int n, int max_considered,
+                                     uint64_t seed, double* h_draws, double* h_score, uint32_t* h_base, uint8_t* h_considered, int32_t* h_m_eff) {
+    if (n < 0 || (n > 0 && (!h_prior || !h_visits || !h_stones || !h_game_ids || !h_score || !h_base || !h_considered || !h_m_eff)) || max_considered < 1 ||
+        max_considered > kCells) {
+        gmk::set_error("gmk_gumbel_setup_host: bad arguments (max_considered 1 .. 225)");
+        return GMK_ERR_ARG;
+    }
+    for (int g = 0; g < n; ++g)
+        if (h_stones[g] < 0 || h_stones[g] > kCells) { gmk::set_error("gmk_gumbel_setup_host: row %d has %d stones", g, h_stones[g]); return GMK_ERR_ARG; }
+    const uint32_t lo = static_cast<uint32_t>(seed), hi = static_cast<uint32_t>(seed >> 32);
+    for (int g = 0; g < n; ++g) {
+        const size_t at = static_cast<size_t>(g) * kCells;
+        h_m_eff[g] = gmk_gumbel_setup225(h_prior + at, h_visits + at, max_considered, h_game_ids[g], static_cast<uint32_t>(h_stones[g]), lo, hi, h_score + at, h_base + at,
+                                         h_considered + at);
+        if (h_draws)
+            for (int c = 0; c < kCells; ++c) h_draws[at + c] = gmk_gumbel_draw(h_game_ids[g], static_cast<uint32_t>(h_stones[g]), static_cast<uint32_t>(c), lo, hi);
+    }
+    return GMK_OK;
+}
+extern "C" int gmk_gumbel_pick_host(const float* h_prior, const uint32_t* h_visits, const float* h_value, const float* h_root_value, const double* h_score,
+                                    const uint32_t* h_base, const uint8_t* h_considered, const int32_t* h_m_eff, int n, int n_sims, double c_visit, double c_scale,
+                                    int16_t* h_cells) {
+    if (!gumbel_rule_args("gmk_gumbel_pick_host", n, h_prior && h_visits && h_value && h_root_value && h_score && h_base && h_considered && h_m_eff && h_cells, c_visit, c_scale))
+        return GMK_ERR_ARG;
+    if (n_sims < 1 || n_sims > GMK_GUMBEL_MAX_SIMS) { gmk::set_error("gmk_gumbel_pick_host: n_sims takes 1 .. %d, not %d", GMK_GUMBEL_MAX_SIMS, n_sims); return GMK_ERR_ARG; }
+    for (int g = 0; g < n; ++g)
+        if (h_m_eff[g] < 0 || h_m_eff[g] > kCells) { gmk::set_error("gmk_gumbel_pick_host: row %d has m_eff = %d", g, h_m_eff[g]); return GMK_ERR_ARG; }
+    for (int g = 0; g < n; ++g) {
+        const size_t at = static_cast<size_t>(g) * kCells;
+        h_cells[g] = static_cast<int16_t>(gmk_gumbel_pick225(h_prior + at, h_visits + at, h_value + at, h_root_value[g], h_score + at, h_base + at, h_considered + at,
+                                                             h_m_eff[g], n_sims, c_visit, c_scale));
+    }
+    return GMK_OK;
+}
+extern "C" int gmk_gumbel_move_host(const float* h_prior, const uint32_t* h_visits, const float* h_value, const float* h_root_value, const double* h_score,
+                                    const uint32_t* h_base, const uint8_t* h_considered, int n, double c_visit, double c_scale, int16_t* h_cells) {
+    if (!gumbel_rule_args("gmk_gumbel_move_host", n, h_prior && h_visits && h_value && h_root_value && h_score && h_base && h_considered && h_cells, c_visit, c_scale))
+        return GMK_ERR_ARG;
+    for (int g = 0; g < n; ++g) {
+        const size_t at = static_cast<size_t>(g) * kCells;
+        h_cells[g] = static_cast<int16_t>(gmk_gumbel_move225(h_prior + at, h_visits + at, h_value + at, h_root_value[g], h_score + at, h_base + at, h_considered + at, c_visit,
+                                                             c_scale));
+    }
+    return GMK_OK;
+}
+extern "C" int gmk_gumbel_row_host(const float* h_prior, const uint32_t* h_visits, const float* h_value, const float* h_root_value, int n, double c_visit, double c_scale,
+                                   uint16_t* h_rows) {
+    if (!gumbel_rule_args("gmk_gumbel_row_host", n, h_prior && h_visits && h_value && h_root_value && h_rows, c_visit, c_scale)) return GMK_ERR_ARG;
+    for (int g = 0; g < n; ++g) {
+        const size_t at = static_cast<size_t>(g) * kCells;
+        gmk_gumbel_row225(h_prior + at, h_visits + at, h_value + at, h_root_value[g], c_visit, c_scale, h_rows + at);
+    }
+    return GMK_OK;
+}
+
 extern "C" int gmk_az_set_option(gmk_az* a, int option, int value) {
     if (a && az_marks_up(a, "gmk_az_set_option")) return GMK_ERR_STATE;
+    if (a && a->gumbel && ((option == GMK_OPT_AZ_LEAVES && value > 1 && value <= GMK_AZ_MAX_LEAVES) || (option == GMK_OPT_AZ_PROOF && value == 1))) {
+        gmk::set_error("gmk_az_set_option: the Gumbel root search (gmk_az_set_gumbel) takes one leaf per step and carries no proofs; switch it off first");
+        return GMK_ERR_STATE;
+    }
     if (a && option == GMK_OPT_AZ_LEAVES && value >= 1 && value <= GMK_AZ_MAX_LEAVES) {
         if (value > 1 && !a->lv.inflight) {                      // the side buffers: in-flight counts (all zero between steps) and the pending leaves
             const size_t n = static_cast<size_t>(a->t.n_games), nodes = n * static_cast<size_t>(a->t.cap);

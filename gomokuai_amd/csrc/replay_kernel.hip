@@ -185,12 +185,12 @@ void replay_append_packed_kernel(const uint8_t* __restrict__ buf, int n, const i
 }
 
 // ---- draw: one wavefront per sample ----
-template <class OutT>
-__global__ __launch_bounds__(kThreads)
-void replay_draw_kernel(const uint64_t* __restrict__ state, const GameDesc* __restrict__ desc, const uint8_t* __restrict__ ring_moves,
-                        const uint16_t* __restrict__ ring_visits, uint64_t cap, uint64_t max_games, uint64_t seed, uint64_t step, int batch,
-                        int augment, OutT* __restrict__ out_states, float* __restrict__ out_values, float* __restrict__ out_pi,
-                        int64_t* __restrict__ out_picked, int32_t* __restrict__ status) {
+// kPolicy (GMK_TARGET_POLICY, K21): the row is a distribution already, pi_c = (float)((double)w_c / (double)sum w); the sum is an integer below 2^24
+template <class OutT, bool kPolicy>
+__device__ __forceinline__ void replay_draw_body(const uint64_t* __restrict__ state, const GameDesc* __restrict__ desc, const uint8_t* __restrict__ ring_moves,
+                                                 const uint16_t* __restrict__ ring_visits, uint64_t cap, uint64_t max_games, uint64_t seed, uint64_t step, int batch,
+                                                 int augment, OutT* __restrict__ out_states, float* __restrict__ out_values, float* __restrict__ out_pi,
+                                                 int64_t* __restrict__ out_picked, int32_t* __restrict__ status) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));      // (uniform: what follows up to the lanes' loads is scalar work)
     const int64_t i = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave;
@@ -240,35 +240,49 @@ void replay_draw_kernel(const uint64_t* __restrict__ state, const GameDesc* __re
     // w = 128 .. 1; slots 225.. are zero).  This lane holds slots l, l+64, l+128, l+192: w = 128 and w = 64 are the two local adds
     // (s0 + s2) + (s1 + s3), w = 32 .. 1 take lane l + w's partial sum, so lane 0 ends with the same association and the same bits.
     const uint16_t* vrow = ring_visits + (x % cap) * kCells;
-    float v[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int idx = lane + 64 * q;
-        v[q] = idx < kCells ? static_cast<float>(vrow[idx]) : 0.0f;
-    }
-    float fs = (v[0] * v[0] + v[2] * v[2]) + (v[1] * v[1] + v[3] * v[3]);
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) fs += __shfl_down(fs, w);
-    const float sq = __shfl(fs, 0);
-    const float temperature = t < 15 ? 1.0f : 0.01f;                  // MCTS.cpp:114 (stones on the board = t)
-    const float eps = 1.1920929e-07f;
-    double e[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        float u = v[q];
-        if (sq > 0.0f) u = u / sqrtf(sq);                             // VectorXf::normalized()
-        u = u ? u + 1.0f : u;                                         // MCTS.cpp:112
-        e[q] = lane + 64 * q < kCells ? exp(static_cast<double>(logf(u + eps) / temperature)) : 0.0;   // Statistical.hpp:38-39
-    }
-    double ds = (e[0] + e[2]) + (e[1] + e[3]);
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) ds += __shfl_down(ds, w);
-    const double total = __shfl(ds, 0);
     float pr[4];
+    if constexpr (kPolicy) {
+        uint32_t wv[4], ws = 0u;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float f = static_cast<float>(e[q] / total);
-        pr[q] = f > eps ? f : 0.0f;
+        for (int q = 0; q < 4; ++q) {
+            const int idx = lane + 64 * q;
+            wv[q] = idx < kCells ? vrow[idx] : 0u;
+            ws += wv[q];
+        }
+#pragma unroll
+        for (int w = 32; w > 0; w >>= 1) ws += static_cast<uint32_t>(__shfl_xor(static_cast<int>(ws), w));
+#pragma unroll
+        for (int q = 0; q < 4; ++q) pr[q] = ws ? static_cast<float>(static_cast<double>(wv[q]) / static_cast<double>(ws)) : 0.0f;
+    } else {
+        float v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int idx = lane + 64 * q;
+            v[q] = idx < kCells ? static_cast<float>(vrow[idx]) : 0.0f;
+        }
+        float fs = (v[0] * v[0] + v[2] * v[2]) + (v[1] * v[1] + v[3] * v[3]);
+#pragma unroll
+        for (int w = 32; w > 0; w >>= 1) fs += __shfl_down(fs, w);
+        const float sq = __shfl(fs, 0);
+        const float temperature = t < 15 ? 1.0f : 0.01f;                  // MCTS.cpp:114 (stones on the board = t)
+        const float eps = 1.1920929e-07f;
+        double e[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float u = v[q];
+            if (sq > 0.0f) u = u / sqrtf(sq);                             // VectorXf::normalized()
+            u = u ? u + 1.0f : u;                                         // MCTS.cpp:112
+            e[q] = lane + 64 * q < kCells ? exp(static_cast<double>(logf(u + eps) / temperature)) : 0.0;   // Statistical.hpp:38-39
+        }
+        double ds = (e[0] + e[2]) + (e[1] + e[3]);
+#pragma unroll
+        for (int w = 32; w > 0; w >>= 1) ds += __shfl_down(ds, w);
+        const double total = __shfl(ds, 0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float f = static_cast<float>(e[q] / total);
+            pr[q] = f > eps ? f : 0.0f;
+        }
     }
 
     // ---- write the tuple; pi of output cell j is pi of source cell augment_source(j), held by lane src & 63 in register src >> 6 ----
@@ -303,6 +317,22 @@ void replay_draw_kernel(const uint64_t* __restrict__ state, const GameDesc* __re
             out_picked[3 * i + 2] = a;
         }
     }
+}
+template <class OutT>
+__global__ __launch_bounds__(kThreads)
+void replay_draw_kernel(const uint64_t* __restrict__ state, const GameDesc* __restrict__ desc, const uint8_t* __restrict__ ring_moves,
+                        const uint16_t* __restrict__ ring_visits, uint64_t cap, uint64_t max_games, uint64_t seed, uint64_t step, int batch,
+                        int augment, OutT* __restrict__ out_states, float* __restrict__ out_values, float* __restrict__ out_pi,
+                        int64_t* __restrict__ out_picked, int32_t* __restrict__ status) {
+    replay_draw_body<OutT, false>(state, desc, ring_moves, ring_visits, cap, max_games, seed, step, batch, augment, out_states, out_values, out_pi, out_picked, status);
+}
+template <class OutT>
+__global__ __launch_bounds__(kThreads)
+void replay_draw_policy_kernel(const uint64_t* __restrict__ state, const GameDesc* __restrict__ desc, const uint8_t* __restrict__ ring_moves,
+                               const uint16_t* __restrict__ ring_visits, uint64_t cap, uint64_t max_games, uint64_t seed, uint64_t step, int batch,
+                               int augment, OutT* __restrict__ out_states, float* __restrict__ out_values, float* __restrict__ out_pi,
+                               int64_t* __restrict__ out_picked, int32_t* __restrict__ status) {
+    replay_draw_body<OutT, true>(state, desc, ring_moves, ring_visits, cap, max_games, seed, step, batch, augment, out_states, out_values, out_pi, out_picked, status);
 }
 
 // ---- the image (replay_image.h): the descriptors need a kernel each way, the plies and the visit rows are plain copies ----
@@ -552,18 +582,27 @@ extern "C" int gmk_replay_size(gmk_replay* h, int64_t* games, int64_t* plies, in
     return GMK_OK;
 }
 
-extern "C" int gmk_replay_sample(gmk_replay* h, int batch, int64_t step, int augment, int states_float, void* d_states, float* d_values, float* d_pi,
-                                 int64_t* d_picked, int32_t* d_status, void* stream) {
+// gmk_replay_sample and gmk_replay_sample_target: the mode is a property of the draw, not of the stored bytes
+static int replay_sample(const char* who, gmk_replay* h, int batch, int64_t step, int augment, int target, int states_float, void* d_states, float* d_values, float* d_pi,
+                         int64_t* d_picked, int32_t* d_status, void* stream) {
     GMK_NEED_INIT();
     if (!h || batch < 0 || (batch > 0 && (!d_states || !d_values || !d_pi || !d_status || misaligned(d_values, 4) || misaligned(d_pi, 4) ||
                                           misaligned(d_status, 4) || misaligned(d_picked, 8) || (states_float && misaligned(d_states, 4))))) {
-        gmk::set_error("gmk_replay_sample: bad arguments (batch >= 0; float outputs and d_status 4-byte, d_picked 8-byte aligned)");
+        gmk::set_error("%s: bad arguments (batch >= 0; float outputs and d_status 4-byte, d_picked 8-byte aligned)", who);
         return GMK_ERR_ARG;
     }
+    if (target != GMK_TARGET_VISITS && target != GMK_TARGET_POLICY) { gmk::set_error("%s: target %d is neither GMK_TARGET_VISITS nor GMK_TARGET_POLICY", who, target); return GMK_ERR_ARG; }
     if (batch == 0) return GMK_OK;
     const dim3 grid((batch + kWavesPerBlock - 1) / kWavesPerBlock), block(kThreads);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (states_float)
+    if (target == GMK_TARGET_POLICY) {
+        if (states_float)
+            hipLaunchKernelGGL(replay_draw_policy_kernel<float>, grid, block, 0, s, h->d_state, h->d_desc, h->d_moves, h->d_visits, h->cap, h->max_games, h->seed,
+                               static_cast<uint64_t>(step), batch, augment, static_cast<float*>(d_states), d_values, d_pi, d_picked, d_status);
+        else
+            hipLaunchKernelGGL(replay_draw_policy_kernel<uint8_t>, grid, block, 0, s, h->d_state, h->d_desc, h->d_moves, h->d_visits, h->cap, h->max_games, h->seed,
+                               static_cast<uint64_t>(step), batch, augment, static_cast<uint8_t*>(d_states), d_values, d_pi, d_picked, d_status);
+    } else if (states_float)
         hipLaunchKernelGGL(replay_draw_kernel<float>, grid, block, 0, s, h->d_state, h->d_desc, h->d_moves, h->d_visits, h->cap, h->max_games, h->seed,
                            static_cast<uint64_t>(step), batch, augment, static_cast<float*>(d_states), d_values, d_pi, d_picked, d_status);
     else
@@ -571,6 +610,14 @@ extern "C" int gmk_replay_sample(gmk_replay* h, int batch, int64_t step, int aug
                            static_cast<uint64_t>(step), batch, augment, static_cast<uint8_t*>(d_states), d_values, d_pi, d_picked, d_status);
     GMK_HIP_CHECK(hipGetLastError());
     return GMK_OK;
+}
+extern "C" int gmk_replay_sample(gmk_replay* h, int batch, int64_t step, int augment, int states_float, void* d_states, float* d_values, float* d_pi,
+                                 int64_t* d_picked, int32_t* d_status, void* stream) {
+    return replay_sample("gmk_replay_sample", h, batch, step, augment, GMK_TARGET_VISITS, states_float, d_states, d_values, d_pi, d_picked, d_status, stream);
+}
+extern "C" int gmk_replay_sample_target(gmk_replay* h, int batch, int64_t step, int augment, int target, int states_float, void* d_states, float* d_values, float* d_pi,
+                                        int64_t* d_picked, int32_t* d_status, void* stream) {
+    return replay_sample("gmk_replay_sample_target", h, batch, step, augment, target, states_float, d_states, d_values, d_pi, d_picked, d_status, stream);
 }
 
 extern "C" int gmk_replay_draw_host(uint64_t seed, int64_t step, int64_t population, int64_t batch, int64_t* h_index) {

@@ -67,6 +67,9 @@ EXPORTS = [
     "gmk_evalstate_create", "gmk_evalstate_destroy", "gmk_evalstate_reset", "gmk_evalstate_update", "gmk_evalstate_update_host", "gmk_evalstate_read",
     "gmk_az_create", "gmk_az_destroy", "gmk_az_set_roots", "gmk_az_select", "gmk_az_expand", "gmk_az_select_host", "gmk_az_expand_host", "gmk_az_read_node_host", "gmk_az_read_children_host", "gmk_az_set_leaf_host", "gmk_az_rollout_host", "gmk_az_expand_stages_host", "gmk_az_write_stats_host", "gmk_az_step", "gmk_az_root_choice", "gmk_az_step_device", "gmk_az_advance", "gmk_az_set_slots", "gmk_az_live_games", "gmk_az_set_game_ids", "gmk_az_add_root_noise", "gmk_az_set_option", "gmk_az_add_playouts", "gmk_az_playouts_owed", "gmk_az_root_stats", "gmk_az_vcf_stats", "gmk_az_vcf_verdicts_host", "gmk_az_defend_stats", "gmk_az_defend_verdicts_host", "gmk_az_root_proofs", "gmk_az_proof_stats",
     "gmk_az_advance_sampled", "gmk_az_root_choice_sampled", "gmk_move_sample_host",
+    "gmk_az_set_gumbel", "gmk_az_advance_gumbel", "gmk_az_root_choice_gumbel",
+    "gmk_gumbel_sequence_host", "gmk_gumbel_setup_host", "gmk_gumbel_pick_host", "gmk_gumbel_move_host", "gmk_gumbel_row_host",
+    "gmk_samples_from_records_target", "gmk_samples_from_packed_target", "gmk_replay_sample_target",
     "gmk_mcts_advance_sampled", "gmk_selfplay_run_sampled", "gmk_trad_selfplay_run_sampled", "gmk_trad_root_choice_sampled",
     "gmk_trad_create", "gmk_trad_destroy", "gmk_trad_reset_evaluators", "gmk_trad_set_game_ids", "gmk_trad_set_positions", "gmk_trad_run", "gmk_trad_step", "gmk_trad_root_choice", "gmk_trad_step_device", "gmk_trad_add_root_noise", "gmk_trad_set_option", "gmk_trad_reserve", "gmk_trad_root_stats", "gmk_trad_read_evaluators", "gmk_trad_run_poolrave", "gmk_trad_run_rave", "gmk_trad_root_amaf", "gmk_trad_selfplay_run", "gmk_pvnet_create", "gmk_pvnet_destroy", "gmk_pvnet_forward", "gmk_pvnet_set_dense", "gmk_pvnet_evaluate",
     "gmk_pvnet_set_precision", "gmk_pvnet_get_precision", "gmk_bf16_round_host",
@@ -166,6 +169,17 @@ def load():
     L.gmk_az_advance_sampled.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_int32), vp]
     L.gmk_az_root_choice_sampled.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp]
     L.gmk_move_sample_host.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64, vp]
+    L.gmk_az_set_gumbel.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_uint64, C.c_uint32]
+    L.gmk_az_advance_gumbel.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_int32), vp]
+    L.gmk_az_root_choice_gumbel.argtypes = [vp, vp, vp, vp]
+    L.gmk_gumbel_sequence_host.argtypes = [C.c_int, C.c_int, vp]
+    L.gmk_gumbel_setup_host.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_uint64, vp, vp, vp, vp, vp]
+    L.gmk_gumbel_pick_host.argtypes = [vp] * 8 + [C.c_int, C.c_int, C.c_double, C.c_double, vp]
+    L.gmk_gumbel_move_host.argtypes = [vp] * 7 + [C.c_int, C.c_double, C.c_double, vp]
+    L.gmk_gumbel_row_host.argtypes = [vp] * 4 + [C.c_int, C.c_double, C.c_double, vp]
+    L.gmk_samples_from_records_target.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.gmk_samples_from_packed_target.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.gmk_replay_sample_target.argtypes = [vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     L.gmk_az_add_root_noise.argtypes = [vp, C.c_float, C.c_float, C.c_uint64, C.c_uint32, vp]
     L.gmk_az_set_option.argtypes = [vp, C.c_int, C.c_int]
     L.gmk_az_add_playouts.argtypes = [vp, C.c_int, vp]
@@ -494,11 +508,24 @@ def visits_to_pi(visits, stones):
     return pi
 
 
+TARGET_VISITS, TARGET_POLICY = 0, 1             # GMK_TARGET_*: how a record's row becomes pi (K21: TARGET_POLICY for the rows of the Gumbel entries)
+TARGETS = {"visits": TARGET_VISITS, "policy": TARGET_POLICY}
+
+
+def _target(target):
+    """"visits" / "policy" / None (visits) or a GMK_TARGET_* value -> the value; anything else is handed to the library, which refuses it"""
+    return TARGET_VISITS if target is None else TARGETS[target] if isinstance(target, str) else int(target)
+
+
 def samples_from_records(d_moves, d_lens, d_visits, d_winner, d_sample_game, d_sample_move, n_samples, augment,
-                         d_states, d_values, d_pi, stream=None):
-    """Device-pointer form of gmk_samples_from_records (K4 + K5)."""
-    _check(load().gmk_samples_from_records(d_moves, d_lens, d_visits, d_winner, d_sample_game, d_sample_move, n_samples,
-                                           int(augment), d_states, d_values, d_pi, stream))
+                         d_states, d_values, d_pi, stream=None, target=None):
+    """Device-pointer form of gmk_samples_from_records (K4 + K5); target: gmk_samples_from_records_target with that mode."""
+    if target is None:
+        _check(load().gmk_samples_from_records(d_moves, d_lens, d_visits, d_winner, d_sample_game, d_sample_move, n_samples,
+                                               int(augment), d_states, d_values, d_pi, stream))
+    else:
+        _check(load().gmk_samples_from_records_target(d_moves, d_lens, d_visits, d_winner, d_sample_game, d_sample_move, n_samples,
+                                                      int(augment), _target(target), d_states, d_values, d_pi, stream))
 
 
 # ---------------- game records on the wire (device pointers; include/gomoku_hip.h) ----------------
@@ -528,10 +555,14 @@ def records_unpack(d_buf, n_bytes, n, has_visits, d_offsets, d_moves, d_lens, d_
                                      d_status, stream))
 
 
-def samples_from_packed(d_buf, n, d_offsets, d_sample_game, d_sample_move, n_samples, augment, d_states, d_values, d_pi, stream=None):
-    """Device-pointer form of gmk_samples_from_packed (K4 + K5 on the wire form)."""
-    _check(load().gmk_samples_from_packed(d_buf, int(n), d_offsets, d_sample_game, d_sample_move, int(n_samples), int(augment),
-                                          d_states, d_values, d_pi, stream))
+def samples_from_packed(d_buf, n, d_offsets, d_sample_game, d_sample_move, n_samples, augment, d_states, d_values, d_pi, stream=None, target=None):
+    """Device-pointer form of gmk_samples_from_packed (K4 + K5 on the wire form); target: gmk_samples_from_packed_target with that mode."""
+    if target is None:
+        _check(load().gmk_samples_from_packed(d_buf, int(n), d_offsets, d_sample_game, d_sample_move, int(n_samples), int(augment),
+                                              d_states, d_values, d_pi, stream))
+    else:
+        _check(load().gmk_samples_from_packed_target(d_buf, int(n), d_offsets, d_sample_game, d_sample_move, int(n_samples), int(augment), _target(target),
+                                                     d_states, d_values, d_pi, stream))
 
 
 # ---------------- replay buffer (device pointers; include/gomoku_hip.h) ----------------
@@ -590,9 +621,14 @@ class ReplayHandle:
         _check(load().gmk_replay_size(self.h, *[C.byref(x) for x in v], stream))
         return tuple(x.value for x in v)
 
-    def sample(self, batch, step, augment, states_float, d_states, d_values, d_pi, d_picked, d_status, stream=None):
-        _check(load().gmk_replay_sample(self.h, int(batch), int(step), int(bool(augment)), int(bool(states_float)), d_states, d_values, d_pi,
-                                        d_picked, d_status, stream))
+    def sample(self, batch, step, augment, states_float, d_states, d_values, d_pi, d_picked, d_status, stream=None, target=None):
+        """gmk_replay_sample; target ("visits" / "policy" / a TARGET_* value): gmk_replay_sample_target with that mode."""
+        if target is None:
+            _check(load().gmk_replay_sample(self.h, int(batch), int(step), int(bool(augment)), int(bool(states_float)), d_states, d_values, d_pi,
+                                            d_picked, d_status, stream))
+        else:
+            _check(load().gmk_replay_sample_target(self.h, int(batch), int(step), int(bool(augment)), _target(target), int(bool(states_float)), d_states, d_values,
+                                                   d_pi, d_picked, d_status, stream))
 
     def image_bytes(self, stream=None):
         """The size of the image of what is held now; synchronises `stream`."""
@@ -1004,6 +1040,73 @@ def move_sample_host(visits, stones, game_ids, plies, power, seed, proofs=None):
     return cells
 
 
+# ---------------- K21: the Gumbel root rule on the host (include/gomoku_gumbel.h; no GPU) ----------------
+GUMBEL_MAX_SIMS = 4096
+GUMBEL_C_VISIT, GUMBEL_C_SCALE = 50.0, 1.0      # the paper's; parameters, not tuned here
+
+
+def _rows(a, dtype, n=None, width=N):
+    a = np.ascontiguousarray(a, dtype=dtype)
+    assert a.ndim == (2 if width else 1) and (n is None or a.shape[0] == n) and (not width or a.shape[1] == width), a.shape
+    return a
+
+
+def gumbel_sequence_host(m_eff, n_sims):
+    """gmk_gumbel_sequence_host: the sequential-halving schedule seq[0 .. n_sims) for m_eff considered children, uint32[n_sims]."""
+    seq = np.zeros(max(int(n_sims), 0), dtype=np.uint32)
+    _check(load().gmk_gumbel_sequence_host(int(m_eff), int(n_sims), seq.ctypes.data))
+    return seq
+
+
+def gumbel_setup_host(prior, visits, stones, game_ids, max_considered, seed):
+    """gmk_gumbel_setup_host: the set-up of n roots given by rows by cell (prior float32[n, 225], 0 = no child; visits uint32[n, 225]; stones
+    int32[n]; game_ids uint32[n], GLOBAL) -> {"draws" float64[n, 225] (g_c of every cell), "score" float64[n, 225] (s_c, 0 without a child), "base"
+    uint32[n, 225], "considered" uint8[n, 225], "m_eff" int32[n]}."""
+    prior = _rows(prior, np.float32)
+    n = prior.shape[0]
+    visits, stones, game_ids = _rows(visits, np.uint32, n), _rows(stones, np.int32, n, 0), _rows(game_ids, np.uint32, n, 0)
+    out = {"draws": np.zeros((n, N), np.float64), "score": np.zeros((n, N), np.float64), "base": np.zeros((n, N), np.uint32),
+           "considered": np.zeros((n, N), np.uint8), "m_eff": np.zeros(n, np.int32)}
+    _check(load().gmk_gumbel_setup_host(prior.ctypes.data, visits.ctypes.data, stones.ctypes.data, game_ids.ctypes.data, n, int(max_considered),
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, *[out[k].ctypes.data for k in ("draws", "score", "base", "considered", "m_eff")]))
+    return out
+
+
+def _gumbel_state(prior, visits, value, root_value, setup):
+    prior = _rows(prior, np.float32)
+    n = prior.shape[0]
+    rows = [prior, _rows(visits, np.uint32, n), _rows(value, np.float32, n), _rows(root_value, np.float32, n, 0)]
+    if setup is not None:
+        rows += [_rows(setup["score"], np.float64, n), _rows(setup["base"], np.uint32, n), _rows(setup["considered"], np.uint8, n)]
+    return n, rows
+
+
+def gumbel_pick_host(prior, visits, value, root_value, setup, n_sims, c_visit=GUMBEL_C_VISIT, c_scale=GUMBEL_C_SCALE):
+    """gmk_gumbel_pick_host: the cell the next playout's root step descends into, int16[n] (-1: a root without children).  value float32[n, 225]
+    the children's stored means, root_value float32[n] the roots' own; setup: what gumbel_setup_host returned."""
+    n, rows = _gumbel_state(prior, visits, value, root_value, setup)
+    m_eff = _rows(setup["m_eff"], np.int32, n, 0)
+    cells = np.zeros(n, dtype=np.int16)
+    _check(load().gmk_gumbel_pick_host(*[r.ctypes.data for r in rows], m_eff.ctypes.data, n, int(n_sims), float(c_visit), float(c_scale), cells.ctypes.data))
+    return cells
+
+
+def gumbel_move_host(prior, visits, value, root_value, setup, c_visit=GUMBEL_C_VISIT, c_scale=GUMBEL_C_SCALE):
+    """gmk_gumbel_move_host: the move, int16[n] (-1: a root without children)."""
+    n, rows = _gumbel_state(prior, visits, value, root_value, setup)
+    cells = np.zeros(n, dtype=np.int16)
+    _check(load().gmk_gumbel_move_host(*[r.ctypes.data for r in rows], n, float(c_visit), float(c_scale), cells.ctypes.data))
+    return cells
+
+
+def gumbel_row_host(prior, visits, value, root_value, c_visit=GUMBEL_C_VISIT, c_scale=GUMBEL_C_SCALE):
+    """gmk_gumbel_row_host: the improved-policy rows, uint16[n, 225]: what the Gumbel entries write where the plain ones write visit counts."""
+    n, rows = _gumbel_state(prior, visits, value, root_value, None)
+    out = np.zeros((n, N), dtype=np.uint16)
+    _check(load().gmk_gumbel_row_host(*[r.ctypes.data for r in rows], n, float(c_visit), float(c_scale), out.ctypes.data))
+    return out
+
+
 def pvnet_sym_pick_host(states, seed=DEFAULT_SEED):
     """gmk_pvnet_sym_pick_host: the symmetry 0..7 that gmk_pvnet_evaluate_sym's "random" mode evaluates each position in, int32[n]; needs no GPU.
     states float32 [n, 6, 15, 15] (Board.encoded_states()); the pick depends on a row's content and the seed only (include/gomoku_symmetry.h)."""
@@ -1281,9 +1384,12 @@ class AlphaZeroMCTS:
     vcf_defend = True (it acts only with vcf_depth > 0 and proof): select() also asks what the opponent threatens at every pending leaf the solver
     did not answer, and under a forced win by fours which replies lose to it (vcf_defend's table); expand() marks those children as the
     opponent's proven wins and proves a leaf without a holding reply lost (OPT_AZ_VCF_DEFEND; include/gomoku_hip.h, "K7 + K15").
-    defend_stats() and defend_verdicts() read it out."""
+    defend_stats() and defend_verdicts() read it out.
+    gumbel = (max_considered, n_sims, c_visit, c_scale, seed, first_game_id): the root step of select() is Gumbel AlphaZero's (gmk_az_set_gumbel;
+    include/gomoku_gumbel.h, "K21"): sequential halving over the Gumbel-top-m root children, PUCB below; advance(gumbel=True) and
+    root_choice(gumbel=True) then move by the rule and write the improved-policy row where the visit counts went.  leaves = 1 and proof = False only."""
 
-    def __init__(self, n_games, node_capacity=1 << 16, c_puct=5.0, leaves=1, vcf_depth=0, vcf_budget=64, proof=False, vcf_defend=False):
+    def __init__(self, n_games, node_capacity=1 << 16, c_puct=5.0, leaves=1, vcf_depth=0, vcf_budget=64, proof=False, vcf_defend=False, gumbel=None):
         import torch
         init()
         self.n = n_games
@@ -1302,6 +1408,14 @@ class AlphaZeroMCTS:
             self.set_option(OPT_AZ_PROOF, 1)
         if vcf_defend:
             self.set_option(OPT_AZ_VCF_DEFEND, 1)
+        if gumbel is not None:
+            self.set_gumbel(*gumbel)
+
+    def set_gumbel(self, max_considered, n_sims=1, c_visit=GUMBEL_C_VISIT, c_scale=GUMBEL_C_SCALE, seed=DEFAULT_SEED, first_game_id=0):
+        """gmk_az_set_gumbel: max_considered = 0 switches the Gumbel root search off, 1 .. 225 on with n_sims (1 .. 4096) playouts per move to
+        schedule; waits for the device and voids every root's set-up."""
+        _check(load().gmk_az_set_gumbel(self.h, int(max_considered), int(n_sims), float(c_visit), float(c_scale), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                        int(first_game_id) & 0xFFFFFFFF))
 
     def close(self):
         if getattr(self, "h", None) and load is not None:
@@ -1355,11 +1469,16 @@ class AlphaZeroMCTS:
             assert m.shape == (self.n,)
             _check(load().gmk_az_step(self.h, m.ctypes.data))
 
-    def root_choice(self, cells, visits=None, stream=None, sample=None):
+    def root_choice(self, cells, visits=None, stream=None, sample=None, gumbel=False):
         """gmk_az_root_choice: the most visited root child (first maximum in cell order, -1 without one) into cells (torch int16[n] on the
         GPU) and the root children's visit counts by cell, saturated at 65 535, into visits (2-byte torch [n, 225], or None).
-        sample = (plies, power, seed, first_game_id): gmk_az_root_choice_sampled, the choice advance(sample=) makes."""
-        if sample is None:
+        sample = (plies, power, seed, first_game_id): gmk_az_root_choice_sampled, the choice advance(sample=) makes.
+        gumbel = True: gmk_az_root_choice_gumbel, the choice advance(gumbel=True) makes; visits gets the improved-policy row, and the roots'
+        set-ups are void afterwards (the choice is taken once per root)."""
+        if gumbel:
+            assert sample is None
+            _root_choice(load().gmk_az_root_choice_gumbel, self, cells, visits, stream)
+        elif sample is None:
             _root_choice(load().gmk_az_root_choice, self, cells, visits, stream)
         else:
             args = _sample_args(sample)
@@ -1388,19 +1507,24 @@ class AlphaZeroMCTS:
             _check(load().gmk_az_set_slots(self.h, int(n_total), m.ctypes.data, m.shape[1], l.ctypes.data))
         self._refresh_live()
 
-    def advance(self, moves, visits, lens, winner, reuse_subtree=True, stream=None, sample=None):
+    def advance(self, moves, visits, lens, winner, reuse_subtree=True, stream=None, sample=None, gumbel=False):
         """One self-play move for every game still played, on the device (gmk_az_advance): moves uint8[n,225], visits int16/uint16
         [n,225,225] or None, lens int32[n], winner int8[n] are torch tensors on the GPU (the games' records, openings included);
         returns the number of games that go on.  sample = (plies, power, seed, first_game_id): gmk_az_advance_sampled -- a game with fewer
         than `plies` stones on its root board plays a child drawn in proportion to visits^power (power 1..3; include/gomoku_sample.h), keyed by
-        seed and the game's global id as add_root_noise keys its draws; None: every game plays its most visited child."""
+        seed and the game's global id as add_root_noise keys its draws; None: every game plays its most visited child.
+        gumbel = True: gmk_az_advance_gumbel -- the move is the Gumbel rule's and `visits` gets the improved-policy row (set_gumbel must be on)."""
         import torch
         stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
         rows = getattr(self, "n_total", None) or self.n
         assert moves.dtype == torch.uint8 and moves.shape == (rows, N) and lens.dtype == torch.int32 and lens.shape == (rows,) and winner.dtype == torch.int8 and winner.shape == (rows,)
         assert visits is None or (visits.element_size() == 2 and visits.shape == (rows, N, N))
         unfinished = C.c_int32(0)
-        if sample is None:
+        if gumbel:
+            assert sample is None
+            _check(load().gmk_az_advance_gumbel(self.h, moves.data_ptr(), visits.data_ptr() if visits is not None else None, lens.data_ptr(), winner.data_ptr(),
+                                                int(bool(reuse_subtree)), C.byref(unfinished), stream))
+        elif sample is None:
             _check(load().gmk_az_advance(self.h, moves.data_ptr(), visits.data_ptr() if visits is not None else None, lens.data_ptr(), winner.data_ptr(),
                                          int(bool(reuse_subtree)), C.byref(unfinished), stream))
         else:

@@ -31,11 +31,12 @@ class GameRecords:
         return GameRecords(self.moves.cpu(), self.lens.cpu(), self.winner.cpu(),
                            None if self.visits is None else self.visits.cpu(), self.first_game_id, self.overflow)
 
-    def to_samples(self, augment=False, first_move=0):
+    def to_samples(self, augment=False, first_move=0, target=None):
         """All training tuples of all games, built ON THE GPU (K4 + K5, optionally with the eight-fold augmentation of
         network/data_helper.py:36-55): -> (states uint8[S,6,15,15], values float32[S], pi float32[S,225]) as torch
         tensors on the records' device, samples ordered by (game, move[, symmetry]).  first_move skips opening plies
-        that were not searched."""
+        that were not searched.  target = "policy": the rows are improved-policy rows (play_network_games(gumbel=)), pi = row / sum(row);
+        "visits" or None: MCTS::evalState's transform of visit counts."""
         assert self.visits is not None and self.moves.is_cuda
         dev = self.moves.device
         game, move = _sample_lists(self.lens.cpu().numpy(), first_move)
@@ -47,7 +48,7 @@ class GameRecords:
         pi = torch.empty((n * copies, N), dtype=torch.float32, device=dev)
         G.samples_from_records(self.moves.data_ptr(), self.lens.data_ptr(), self.visits.data_ptr(), self.winner.data_ptr(),
                                d_game.data_ptr(), d_move.data_ptr(), n, augment, states.data_ptr(), values.data_ptr(), pi.data_ptr(),
-                               torch.cuda.current_stream(dev).cuda_stream)
+                               torch.cuda.current_stream(dev).cuda_stream, target=target)
         return states, values, pi
 
     def samples(self, game):
@@ -586,7 +587,7 @@ def _symmetric(who, network, symmetry, seed):
 
 def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, first_game_id=0, opening_plies=0, max_moves=N,
                        device=None, node_capacity=None, reuse_subtree=True, root_noise=(0.05, 0.25), slots=None, device_loop=True, noise_sampler="counter", leaves=1,
-                       vcf=None, proof=False, vcf_defend=False, sample_plies=0, sample_power=1, symmetry=None):
+                       vcf=None, proof=False, vcf_defend=False, sample_plies=0, sample_power=1, symmetry=None, gumbel=None):
     """n_games complete games of the network-guided searcher against itself (agents/alphazero.py:5-9 on both sides: the
     reference's AlphaZero self-play), all games in lock step on the current GPU: every move = `playouts` lock-step playouts of
     K7 with `network(states [n,6,15,15]) -> (value [n], probs [n,225])` at the leaves (network.FusedPolicyValueNetwork = K9),
@@ -609,9 +610,25 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
     these too are the same games on every loop, and a record's visit row gives its move again.  symmetry = "random" or "all": the leaves are
     evaluated through network.symmetric(symmetry, seed) -- one orientation of the board per leaf, picked from the leaf's position and `seed`, or
     the average over all eight (K22, include/gomoku_symmetry.h); the pick does not depend on a row's place in the batch, so these are the same
-    games on every loop as well.  None: `network` as it is.  Returns GameRecords like play_games."""
+    games on every loop as well.  None: `network` as it is.
+    gumbel = (max_considered, c_visit, c_scale): Gumbel AlphaZero at the root (K21, include/gomoku_gumbel.h; lib.AlphaZeroMCTS(gumbel=)) with
+    n_sims = playouts -- the playouts of a move go to the Gumbel-top-m root children by sequential halving, the move is the rule's, and the
+    records' rows are improved-policy rows, to be read with target="policy" (GameRecords.to_samples, ReplayBuffer).  The draws are keyed by seed,
+    the game's global id and its stone count, so every loop plays the same games, rows included.  The Gumbel noise is the exploration:
+    root_noise must be None, and leaves > 1, proof, vcf_defend and sample_plies > 0 do not go with it (ValueError).  Playing strength against
+    the plain search is not measured yet.  Returns GameRecords like play_games."""
     if not (0 <= int(sample_plies) <= N and 1 <= int(sample_power) <= 3):
         raise ValueError("play_network_games: sample_plies takes 0 .. 225 and sample_power 1, 2 or 3")
+    gumbel_args = None
+    if gumbel is not None:
+        if root_noise is not None:
+            raise ValueError("play_network_games: gumbel does not go with root noise -- pass root_noise=None, the Gumbel noise is the exploration")
+        for name, bad in (("leaves > 1", leaves != 1), ("proof", proof), ("vcf_defend", vcf_defend), ("sample_plies > 0", int(sample_plies) > 0)):
+            if bad:
+                raise ValueError("play_network_games: gumbel does not go with %s (the Gumbel root search takes one leaf per step, carries no proofs "
+                                 "and chooses its moves itself)" % name)
+        m, c_visit, c_scale = gumbel
+        gumbel_args = (int(m), int(playouts), float(c_visit), float(c_scale), seed, first_game_id)
     network = _symmetric("play_network_games", network, symmetry, seed)
     sample = (int(sample_plies), int(sample_power), seed, first_game_id) if int(sample_plies) > 0 else None
     if slots is not None and slots < n_games and (max_moves < N or (device_loop and opening_plies > 8)):
@@ -627,14 +644,14 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
     dev, _ = _device(device)
     games = _HostGames.opened(n_games, seed, first_game_id, opening_plies)
     tree = G.AlphaZeroMCTS(n_slots, node_capacity=_arena_nodes("network", playouts, reuse_subtree, node_capacity), c_puct=c_puct, leaves=leaves, proof=proof,
-                           vcf_defend=vcf_defend, **_vcf_options(vcf))
+                           vcf_defend=vcf_defend, gumbel=gumbel_args, **_vcf_options(vcf))
     try:
         tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS[noise_sampler])
         with torch.no_grad():
             if not device_loop:
                 # (through slots the host-driven loop has never mixed noise into its fresh roots: kept as it is)
                 visits, overflow = _network_host_loop(tree, games, n_slots, steps, network, playouts, reuse_subtree, None if slotted else root_noise,
-                                                      proof, sample, seed, first_game_id)
+                                                      proof, sample, seed, first_game_id, gumbel is not None)
                 return _records_from_host(games, visits, dev, first_game_id, overflow)
             if slotted:
                 # continuous batching on the device (gmk_az_set_slots + gmk_az_advance): the batch the network sees stays full of live games
@@ -647,7 +664,7 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
                 if root_noise is not None:
                     tree.add_root_noise(root_noise[0], root_noise[1], seed=seed, first_game_id=first_game_id)
                 tree.search(network, playouts)
-                if tree.advance(d_moves, d_visits, d_lens, d_winner, reuse_subtree, sample=sample) == 0:
+                if tree.advance(d_moves, d_visits, d_lens, d_winner, reuse_subtree, sample=sample, gumbel=gumbel is not None) == 0:
                     break
         overflow = _arena_full(tree.root_stats()["status"], G.AlphaZeroMCTS.STATUS_ARENA_FULL)
     finally:
@@ -655,11 +672,15 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
     return GameRecords(d_moves, d_lens, d_winner, d_visits, first_game_id, overflow)
 
 
-def _network_host_loop(tree, games, slots, steps, network, playouts, reuse_subtree, root_noise, proof, sample, seed, first_game_id):
+def _network_host_loop(tree, games, slots, steps, network, playouts, reuse_subtree, root_noise, proof, sample, seed, first_game_id, gumbel=False):
     """The host-driven loop of play_network_games: the games of `games` (a _HostGames) through `slots` slots of the K7 handle `tree`, at
     most `steps` searches.  With kept subtrees every slot keeps its game (slots == games.n: K7 has no way to give one slot a new root and
-    leave the others their trees).  Returns (visits uint16[n, 225, 225], whether an arena filled up)."""
+    leave the others their trees).  gumbel: the handle's Gumbel root search is on -- the move and the row come from root_choice(gumbel=True), and
+    the row recorded is its improved-policy row.  Returns (visits uint16[n, 225, 225], whether an arena filled up)."""
     visits = np.zeros((games.n, N, N), dtype=np.uint16)
+    if gumbel:
+        d_cells = torch.zeros(slots, dtype=torch.int16, device="cuda")
+        d_rows = torch.zeros((slots, N), dtype=torch.int16, device="cuda")
     active, waiting = np.arange(slots), list(range(slots, games.n))
     overflow = False
     for i in range(steps):
@@ -674,6 +695,13 @@ def _network_host_loop(tree, games, slots, steps, network, playouts, reuse_subtr
         tree.search(network, playouts)
         st = tree.root_stats()
         overflow |= _arena_full(st["status"], G.AlphaZeroMCTS.STATUS_ARENA_FULL)
+        if gumbel:
+            tree.root_choice(d_cells, d_rows, gumbel=True)
+            choice, rows = d_cells.cpu().numpy().astype(np.int64), d_rows.cpu().numpy().view(np.uint16)
+            step = games.play(active, choice, rows, visits)
+            if reuse_subtree:
+                tree.step(step)
+            continue
         choice = _sampled_choice(st["visits"], tree.root_proofs()["children"] if proof else None, games.lens[active], active, sample)
         visited = st["visits"].max(1) > 0                        # no child was visited: nothing to play (cannot happen on a live board)
         step = games.play(active, np.where(visited, choice, -1), st["visits"], visits)
@@ -1107,9 +1135,14 @@ class ReplayBuffer:
     the tuples of a minibatch when it is drawn: `batch_size` distinct samples per step (random.sample), a sample = one sampled ply under
     one of the eight symmetries.  At most capacity_plies stored plies and max_games games are held; an append makes the oldest whole
     games leave until the new ones fit (the reference trims before it extends and may overshoot; this capacity is an allocation).
-    extend / extend_packed / sample are asynchronous on the current stream of the buffer's device; len(), stats() and status() synchronise it."""
+    extend / extend_packed / sample are asynchronous on the current stream of the buffer's device; len(), stats() and status() synchronise it.
+    target = "policy": the rows held are improved-policy rows (play_network_games(gumbel=)) and sample() / batches() read them as distributions
+    (lib.TARGET_POLICY); "visits": visit counts through MCTS::evalState's transform, as before.  The stored bytes and state_dict() do not depend on it."""
 
-    def __init__(self, capacity_plies, max_games=None, seed=G.DEFAULT_SEED, device=None):
+    def __init__(self, capacity_plies, max_games=None, seed=G.DEFAULT_SEED, device=None, target="visits"):
+        if target not in G.TARGETS:
+            raise ValueError("ReplayBuffer: target is \"visits\" or \"policy\", not %r" % (target,))
+        self.target = target                                   # how sample() reads a row: a property of the draw, not of what is stored or checkpointed
         capacity_plies = int(capacity_plies)
         if capacity_plies < N:
             raise ValueError("ReplayBuffer: capacity_plies must be at least 225 (one full game)")
@@ -1187,7 +1220,8 @@ class ReplayBuffer:
         pi = torch.empty((batch_size, N), dtype=torch.float32, device=dev)
         picked = torch.empty((batch_size, 3), dtype=torch.int64, device=dev) if return_picked else None
         self._h.sample(batch_size, step, augment, dtype == torch.float32, states.data_ptr(), values.data_ptr(), pi.data_ptr(),
-                       None if picked is None else picked.data_ptr(), self._status[1:].data_ptr(), _stream(dev))
+                       None if picked is None else picked.data_ptr(), self._status[1:].data_ptr(), _stream(dev),
+                       target=None if self.target == "visits" else self.target)
         return (states, values, pi, picked) if return_picked else (states, values, pi)
 
     def stats(self):
@@ -1238,10 +1272,11 @@ class ReplayBuffer:
         self._step = step
 
     @classmethod
-    def from_state_dict(cls, state, capacity_plies=None, max_games=None, device=None):
-        """A new buffer with the saved seed that holds the saved games; the sizes default to the saved ones."""
+    def from_state_dict(cls, state, capacity_plies=None, max_games=None, device=None, target="visits"):
+        """A new buffer with the saved seed that holds the saved games; the sizes default to the saved ones.  target is not saved (the stored
+        bytes do not depend on it): a resumed run passes the one it was started with."""
         buf = cls(state["capacity_plies"] if capacity_plies is None else capacity_plies, state["max_games"] if max_games is None else max_games,
-                  seed=state["seed"], device=device)
+                  seed=state["seed"], device=device, target=target)
         try:
             buf.load_state_dict(state)
         except Exception:

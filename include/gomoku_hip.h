@@ -28,6 +28,9 @@
  *   gmk_az_advance_sampled, gmk_az_root_choice_sampled and, on the host, gmk_move_sample_host, see "K20" below.  The rule is integer
  *   arithmetic on a counter-based stream keyed by the game and its stone count (gomoku_sample.h), so every loop plays the same games
  *   and a record's visit row reproduces its move.  The unsampled entries, the K3 / K6 / K8 self-play loops and matches are unchanged.
+ *   K7 self-play at few playouts per move can instead run Gumbel AlphaZero at the root (gmk_az_set_gumbel, gmk_az_advance_gumbel,
+ *   gmk_az_root_choice_gumbel; gomoku_gumbel.h states the rule, see "K21" below): the record's row is then the improved policy, read
+ *   back with GMK_TARGET_POLICY.
  */
 #ifndef GOMOKU_HIP_H_
 #define GOMOKU_HIP_H_
@@ -271,6 +274,17 @@ int gmk_visits_to_pi(const uint32_t *visits, int stones, float *pi);
 int gmk_samples_from_records(const uint8_t *d_moves, const int32_t *d_lens, const uint16_t *d_visits, const int8_t *d_winner,
                              const int32_t *d_sample_game, const int32_t *d_sample_move, int n_samples, int augment,
                              uint8_t *d_states, float *d_values, float *d_pi, void *stream);
+/* The policy target's mode (K21).  A row written by gmk_az_advance_gumbel / gmk_az_root_choice_gumbel is a distribution, not visit counts:
+ *   GMK_TARGET_VISITS  MCTS::evalState's transform of the row, what the entries without `target` compute (their outputs stay bit for bit);
+ *   GMK_TARGET_POLICY  pi_c = (float)((double)w_c / (double)sum of w): the sum is an integer below 2^24, so no order of adding enters; a row
+ *                      of zeros gives zeros.
+ * The mode is a property of the draw, not of the stored bytes: records, the wire form, the replay image and its checkpoints do not change, and
+ * a resumed run passes the same mode again.  gmk_samples_from_records_target, gmk_samples_from_packed_target (below) and
+ * gmk_replay_sample_target are their plain forms with `target` behind `augment`; any other value is GMK_ERR_ARG, and nothing is launched. */
+enum { GMK_TARGET_VISITS = 0, GMK_TARGET_POLICY = 1 };
+int gmk_samples_from_records_target(const uint8_t *d_moves, const int32_t *d_lens, const uint16_t *d_visits, const int8_t *d_winner,
+                                    const int32_t *d_sample_game, const int32_t *d_sample_move, int n_samples, int augment, int target,
+                                    uint8_t *d_states, float *d_values, float *d_pi, void *stream);
 
 /* ---- game records on the wire (the exchange step: selfplay.pack_records / unpack_records, on the device) ----
  * Wire form of n games, one byte block:  lens int32[n] | winner int8[n] | moves uint8[T] | visits uint16[T][225] (optional),
@@ -300,6 +314,9 @@ int gmk_records_unpack(const uint8_t *d_buf, uint64_t n_bytes, int n, int has_vi
 int gmk_samples_from_packed(const uint8_t *d_buf, int n, const int64_t *d_offsets, const int32_t *d_sample_game,
                             const int32_t *d_sample_move, int n_samples, int augment, uint8_t *d_states, float *d_values,
                             float *d_pi, void *stream);
+int gmk_samples_from_packed_target(const uint8_t *d_buf, int n, const int64_t *d_offsets, const int32_t *d_sample_game,
+                                   const int32_t *d_sample_move, int n_samples, int augment, int target, uint8_t *d_states, float *d_values,
+                                   float *d_pi, void *stream);
 
 /* ---- replay buffer: game records kept in HBM, training minibatches drawn from them ----
  * Takes the place of DataHelper.buffer + DataHelper.generate_batch (network/data_helper.py:67-83, 97-139).  The handle keeps RECORDS, not
@@ -391,6 +408,9 @@ int gmk_replay_append_packed(gmk_replay *h, const uint8_t *d_buf, int n, const i
 int gmk_replay_size(gmk_replay *h, int64_t *games, int64_t *plies, int64_t *population, int64_t *evicted_games, void *stream);
 int gmk_replay_sample(gmk_replay *h, int batch, int64_t step, int augment, int states_float, void *d_states, float *d_values, float *d_pi,
                       int64_t *d_picked, int32_t *d_status, void *stream);
+/* gmk_replay_sample with the policy target's mode (GMK_TARGET_*, above); GMK_TARGET_VISITS is gmk_replay_sample */
+int gmk_replay_sample_target(gmk_replay *h, int batch, int64_t step, int augment, int target, int states_float, void *d_states, float *d_values,
+                             float *d_pi, int64_t *d_picked, int32_t *d_status, void *stream);
 int gmk_replay_draw_host(uint64_t seed, int64_t step, int64_t population, int64_t batch, int64_t *h_index);
 int gmk_replay_image_bytes(gmk_replay *h, int64_t *bytes, void *stream);
 int gmk_replay_snapshot(gmk_replay *h, uint8_t *d_image, int64_t capacity_bytes, int32_t *d_status, void *stream);
@@ -745,6 +765,47 @@ int gmk_trad_selfplay_run_sampled(gmk_trad* t, int policy, int n_total, uint32_t
                                   const uint8_t* h_open_moves, int open_stride, const int32_t* h_open_lens,
                                   uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int persistent, int max_steps, int32_t* h_overflow, int32_t* h_steps, void* stream);
 int gmk_trad_root_choice_sampled(gmk_trad* t, int16_t* d_cells, uint16_t* d_visits, int sample_plies, int sample_power, uint64_t seed, uint32_t first_game_id, void* stream);
+
+/* ---- K21: Gumbel root search for K7 self-play, with its policy target ----
+ * At few playouts per move (32 .. 64 over up to 225 children) PUCB spreads the playouts thinly, the most visited child is a noisy choice and the
+ * visit row carries little policy improvement.  Gumbel AlphaZero (Danihelka et al., ICLR 2022) samples m root children without replacement
+ * (Gumbel-top-m), spends the playouts on them by sequential halving and learns from the completed-Q improved policy.  The rule -- draws, considered
+ * set, schedule, root step, move, policy row -- is stated once, in gomoku_gumbel.h, in binary64 operations that are the same bits on the host and on
+ * gfx950.  It acts at the ROOT only: below it the descent is PUCB's, unchanged.
+ * gmk_az_set_gumbel(a, max_considered, n_sims, c_visit, c_scale, seed, first_game_id): max_considered = 0 switches it off (the default: every
+ *   entry then launches exactly what it launched before); otherwise max_considered in 1 .. 225, n_sims in 1 .. 4096, c_visit and c_scale finite
+ *   and >= 0 (the paper's 50 and 1.0 are parameters, not tuned here), else GMK_ERR_ARG.  GMK_ERR_STATE while GMK_OPT_AZ_LEAVES > 1 or
+ *   GMK_OPT_AZ_PROOF = 1; while it is on, gmk_az_set_option returns GMK_ERR_STATE for those two values.  GMK_OPT_AZ_VCF_DEPTH composes: it
+ *   changes the expand kernels only.  The first use allocates 2940 B per game.  Synchronises.  The draws of slot g are keyed by (seed; first_game_id +
+ *   the game the slot plays, as K20 names it; the stones on the root board; 'gmbl'; the cell).
+ *   While it is on, gmk_az_select's root step is the rule's: the first root step that finds children makes the set-up for that root (the playout
+ *   that expands a childless root is just a playout), and every entry that moves or replaces a root -- gmk_az_set_roots, gmk_az_set_slots,
+ *   gmk_az_step, gmk_az_step_device, gmk_az_advance, gmk_az_advance_sampled, and this call -- voids the set-ups, behind its launches on its stream.
+ *   gmk_az_add_root_noise stays callable: the rule reads whatever priors stand at set-up.
+ * gmk_az_advance_gumbel / gmk_az_root_choice_gumbel: gmk_az_advance / gmk_az_root_choice with the rule's move, and with the improved-policy row
+ *   (uint16, adds up to 65535 within 225) where they write the visit counts: the record, wire and replay formats stay what they are, and the
+ *   row is read with GMK_TARGET_POLICY below.  A root that was not searched since it became the root gets its set-up here (every r_c is 0: the
+ *   move is the considered child with the largest s_c + sigma_c).  Both void the set-up of every root they read, so the choice is taken once per
+ *   root.  GMK_ERR_STATE while the option is off; otherwise as their plain forms.  One launch on `stream`.
+ * gmk_gumbel_*_host: the header's serial statements for n roots given by rows [n][225] by cell, on the host (no GPU, no gmk_init; they are the
+ *   tests' and a binder's view of the rule): _sequence_host the schedule seq[0 .. n_sims) for m_eff; _setup_host the draws g_c (h_draws, of all
+ *   225 cells, may be NULL), s_c, the visit snapshot, the considered set and m_eff; _pick_host the cell of the next playout's root step;
+ *   _move_host the move; _row_host the improved-policy row.  -1 where a root has no children.  h_stones in 0 .. 225, h_game_ids GLOBAL.
+ * Out of scope: Gumbel below the root, GMK_OPT_AZ_LEAVES > 1, proofs and the defence solver, evaluation matches, the ensembles, K3, K6 and K8.
+ * Playing strength and training benefit are not measured yet. */
+int gmk_az_set_gumbel(gmk_az* a, int max_considered, int n_sims, double c_visit, double c_scale, uint64_t seed, uint32_t first_game_id);
+int gmk_az_advance_gumbel(gmk_az* a, uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner, int reuse_subtree, int32_t* h_unfinished, void* stream);
+int gmk_az_root_choice_gumbel(gmk_az* a, int16_t* d_cells, uint16_t* d_visits, void* stream);
+int gmk_gumbel_sequence_host(int m_eff, int n_sims, uint32_t* h_seq);
+int gmk_gumbel_setup_host(const float* h_prior, const uint32_t* h_visits, const int32_t* h_stones, const uint32_t* h_game_ids /* already global */, int n,
+                          int max_considered, uint64_t seed, double* h_draws /* or NULL */, double* h_score, uint32_t* h_base, uint8_t* h_considered, int32_t* h_m_eff);
+int gmk_gumbel_pick_host(const float* h_prior, const uint32_t* h_visits, const float* h_value, const float* h_root_value /*[n]*/, const double* h_score,
+                         const uint32_t* h_base, const uint8_t* h_considered, const int32_t* h_m_eff, int n, int n_sims, double c_visit, double c_scale,
+                         int16_t* h_cells);
+int gmk_gumbel_move_host(const float* h_prior, const uint32_t* h_visits, const float* h_value, const float* h_root_value, const double* h_score,
+                         const uint32_t* h_base, const uint8_t* h_considered, int n, double c_visit, double c_scale, int16_t* h_cells);
+int gmk_gumbel_row_host(const float* h_prior, const uint32_t* h_visits, const float* h_value, const float* h_root_value, int n, double c_visit, double c_scale,
+                        uint16_t* h_rows);
 
 /* ---- K12: the referee of a match between two search handles, on the device (match_kernel.hip) ----
  * One ply of n two-agent games without the host in the loop (agents/utils.py:13-63 dual_play, :66-100 eval_agents): the side to move has
