@@ -20,10 +20,13 @@
 //     bonus) comes from the rows dilated by the three row patterns of the 7x7 mask, with DPP row shifts; the score block -- [cell][4 groups] in
 //     LDS -- is written ONCE, with the bonus in it;
 //   * phase 1: the 72 lines that can hold a pattern (>= 5 cells) are spread over the 64 lanes (the 8 shortest ride
-//     behind the shortest primaries: 17 symbols per lane, fully unrolled); a lane's lines are one stream of 2-bit symbols without leading pads,
+//     behind the shortest primaries of their own direction: 17 symbols per lane, fully unrolled); a lane's lines are one stream of 2-bit symbols without leading pads,
 //     walked from the state the root reaches on '?'; the first four symbols are one read of a 256-entry table, every further one is one LDS lookup: 14 round trips, and the first ten carry a piece of phase 0 in their shadow; emitting transitions are queued by ballot prefix, in the shadow of the next step's lookup (the queue's fill
-//     level lives on the scalar unit, clamped there: no per-lane bounds check);
-//   * phase 2: one lane per queued transition: one 16-byte record read gives the (<= 2) matches, each with a
+//     level lives on the scalar unit, clamped there: no per-lane bounds check).  A queue entry is the table word with its low 17 bits replaced by
+//     the PLACE of the consumed symbol -- bits 0..8 its cell (0..256), 9..10 the direction, 11..16 minus the stride, signed -- which the scan lane keeps
+//     as a running value: the lane record's place word, + the stride per step, + a jump across the seam of a two-line lane ("Lane -> lines" below);
+//   * phase 2: one lane per queued transition: cell, direction and the step back are three field extracts of the entry (nothing is looked up:
+//     until round 14 the entry held (lane, step) and every deposit round decoded the lane's jobs from a table in LDS), one 16-byte record read gives the (<= 2) matches, each with a
 //     compact list of <= 4 score deposits -- a colour's own and opponent view of a cell are the halves of one 64-bit word, so a deposit is ONE
 //     ds_add_u64 whose value decides -- and 4-bit per-(cell, colour, direction, type) counters;
 //   * phase 3: one lane per cell: compound candidates from the counters -- a colour's half word h of the OR-ed counters makes one iff
@@ -92,16 +95,25 @@ constexpr int kMiscWords = 48;                   // [0] stones black | white << 
 constexpr int kBoardWords = kZeroWords + kLineWords + kQueueCap + kMiscWords;
 static_assert(kZeroWords % 4 == 0 && kBoardWords % 4 == 0, "16-byte alignment of the per-board blocks");
 constexpr int kPrefixTableWords = gmk::kPrefixWords;   // a table of the row reached over four symbols: 256 entries of 16 bits, key s0 | s1 << 2 | s2 << 4 | s3 << 6
-constexpr int kStaticTableWords = 128 + kLineWords + 512 + 1560 + 2 * kPrefixTableWords + 4;   // lane jobs, the lines' '?' pads (phase 4), the bits-to-bytes table, the weight table of phase D,
+constexpr int kStaticTableWords = kLineWords + 512 + 1560 + 2 * kPrefixTableWords + 4;   // the lines' '?' pads (phase 4), the bits-to-bytes table, the weight table of phase D,
                                                                         // the two prefix tables (from S for the scan, from the root for the rescans: DeviceTables::dev_prefix4),
                                                                         // and the workgroup's hand-out counter (four words: [0] the counter, [1] the row of S, the state the scan's prefix table is walked from: the host's note, no kernel reads it)
 
-// Lane -> line jobs.  A job word holds what the scan and the deposits need of a line, ready to use: bits 0..4 symbols in its stream
-// segment (len + 2: its cells and two trailing pads), 5..6 dir, 7..11 cell stride, 12..19 its first cell, 20..26 line word index.
+// Lane -> lines.  A lane walks one line, or two of the SAME direction (lanes 56..59: an 8-cell diagonal or anti-diagonal with a 5-cell one behind it,
+// lanes 60..63: 7 cells with 6 behind), so direction and stride are lane constants, and what the scan needs of its lines is two words of the lane's record:
+//   the lines word   bits 0..4 symbols in the first line's stream segment (len + 2: its cells and two trailing pads), 5..9 the second's (2: no line),
+//                    10..16 and 17..23 the two line word indices, 24..31 (byte 3, which an SDWA operand selects) the cell stride;
+//   the place word   bits 0..16 the place of the stream's symbol 4 as a queue entry carries it -- 0..8 the cell (up to 256: the main diagonal's second
+//                    trailing pad), 9..10 the direction, 11..16 MINUS the stride as a signed 6-bit field --, 17..26 the jump, signed: what is added
+//                    besides the stride where the stream steps from the first line's second pad to the second line's first cell, step 10 on lanes
+//                    56..59 and step 9 on lanes 60..63 (first cell of the second line - (first cell of the first + segment * stride)); 0 elsewhere.
+// The place of step s is the place word + (s - 4) * stride (+ the jump): plain integer adds on the packed word, exact in its low 17 bits because the
+// true cell is never negative and never above 511; what the adds leave above bit 16 is not looked at.  The host checks both words against the plain
+// statement -- segment, place on the line, first cell + place * stride -- for every lane and step when it builds the image (lane_tables).
 // Everything a launch reads besides the boards is ONE image in device memory that the host builds once (build_stage_image): first what every workgroup
-// stages in LDS, in LDS order and ready to use -- the automaton, the emission records, the lane jobs, the lines' '?' pads, the bits-to-bytes table, the
+// stages in LDS, in LDS order and ready to use -- the automaton, the emission records, the lines' '?' pads, the bits-to-bytes table, the
 // weight table of phase D, the two four-symbol prefix tables (phases 1 and 4), the hand-out counter's start value and the row of the scan's start state -- copied 16 bytes per lane; behind it a 32-byte record per lane with what the prologue
-// would otherwise derive from the lane number: its two jobs, its two all-blank line words ((1 << 2 len) - 1: words lane and 64 + lane), then [0] row * 4
+// would otherwise derive from the lane number: its lines word and place word, its two all-blank line words ((1 << 2 len) - 1: words lane and 64 + lane), then [0] row * 4
 // and [1] column of the lane's cell in each of the four passes over the board (cell = 64 pass + lane, the last one clamped to 224), a byte per pass, and
 // [2], [3] where the first cell of the lane's two lines sits in its line word (bit 2 x0 for a diagonal, 2 y0 for an anti-diagonal, 0 for rows and columns).
 // Every load of the prologue is issued before the first of them is waited for: their latencies overlap.  (They used to be a dozen loops and
@@ -110,6 +122,8 @@ constexpr int kLaneRecordVecs = 2;
 constexpr int kSegPads = 2;                       // the '?' behind a line's cells in its stream segment (none in front: phase 1 says why)
 constexpr int kScanSteps = 17;                    // symbols in the longest lane stream (lane_tables checks it)
 constexpr int kScanPrefixSyms = 4;                // of them, the leading ones that one read of the scan's prefix table stands for (lane_tables checks that they are cells)
+constexpr int kPairedLanes = 8, kFirstPairedLane = 64 - kPairedLanes;        // the lanes that walk two lines: the last eight, the longer first lines in front
+constexpr int kSeamStepLong = 8 + kSegPads, kSeamStepShort = 7 + kSegPads;   // the step that is the second line's first cell: lanes 56..59 (8 cells first), lanes 60..63 (7 cells)
 
 __device__ __forceinline__ int dir_stride(int dir) { return (0x0E100F01u >> (8 * dir)) & 0xFFu; }      // 1, 15, 16, 14: a shift, not three branches
 
@@ -143,6 +157,33 @@ __device__ __forceinline__ uint32_t dfa_address(uint32_t table_word, uint32_t fo
     uint32_t addr;
     asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(addr) : "s"(0x3FF3u), "v"(table_word), "v"(four));
     return addr;
+}
+
+// The scan's running place (the lane record's place word, see "Lane -> lines") one step on: + the stride, byte 3 of the lines word, selected by the
+// instruction itself.  Output and input are separate operands: tied, the compiler copies the place on every step.
+__device__ __forceinline__ uint32_t place_advance(uint32_t place, uint32_t lines_word) {
+    uint32_t next;
+    asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(next) : "v"(place), "v"(lines_word));
+    return next;
+}
+
+// ... and across the seam of a two-line lane: + the jump, on the four lanes kFirstLane .. kFirstLane + 3 only: they are one bank (four lanes) of one DPP
+// row (sixteen), and the row and bank masks leave every other lane's place as it is: no compare, no exec mask.
+// A DPP operand must not be read within two wait states of the vector instruction that wrote it, and the compiler pads nothing for an instruction it
+// cannot see: the s_nop 1 in front belongs to the add (the jump's field extract is a lane constant the compiler may hoist or work out right here).
+template <int kFirstLane>
+__device__ __forceinline__ uint32_t place_jump(uint32_t place, int jump) {
+    static_assert(kFirstLane >= 0 && kFirstLane < 64 && kFirstLane % 4 == 0, "four lanes of one DPP bank");
+    constexpr int kRow = kFirstLane / 16, kBank = (kFirstLane % 16) / 4;
+    asm("s_nop 1\n\tv_add_u32_dpp %0, %1, %0 quad_perm:[0,1,2,3] row_mask:%2 bank_mask:%3" : "+v"(place) : "v"(jump), "n"(1 << kRow), "n"(1 << kBank));
+    return place;
+}
+
+// a queue entry: the table word with its low 17 bits replaced by the place's, one v_bfi_b32
+__device__ __forceinline__ uint32_t queue_entry(uint32_t table_word, uint32_t place) {
+    uint32_t entry;
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(entry) : "s"(0x1FFFFu), "v"(place), "v"(table_word));
+    return entry;
 }
 
 // both 16-bit halves of a word decremented, no borrow from the low half into the high one: one v_pk_sub_u16
@@ -425,9 +466,9 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
 #endif
 #endif
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    // layout: [trans (LDS address 0)][records (16-byte aligned)][lane jobs 128][line pads 96][boards: kBoardsPerBlock * kBoardWords]
+    // layout: [trans (LDS address 0)][records (16-byte aligned)][line pads 96][the other tables of kStaticTableWords][boards: kBoardsPerBlock * kBoardWords]
     const uint4* s_rec = reinterpret_cast<const uint4*>(lds + trans_words);
-    uint32_t* s_jobs = lds + trans_words + record_words;
+    uint32_t* s_static = lds + trans_words + record_words;
 
     // the loads of the prologue, all of them in front of their first use: the staged image (two pieces of 16 bytes per lane cover 32 KB; the
     // automaton's image is 24 KB) and this lane's record
@@ -435,13 +476,13 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
     const uint4 stage_a = g_stage[min(tid, stage_vecs - 1)], stage_b = g_stage[min(tid + kThreads, stage_vecs - 1)];
     const uint4* lane_record = g_stage + stage_vecs + kLaneRecordVecs * (tid & 63);
     const uint4 lane_lines = lane_record[0], lane_consts = lane_record[1];
-    uint32_t* s_pads = s_jobs + 128;                                         // a line word's '?' pads: symbol 2 in every 2-bit slot of the word that is not one of the
+    uint32_t* s_pads = s_static;                                             // a line word's '?' pads: symbol 2 in every 2-bit slot of the word that is not one of the
                                                                              // line's cells (phase 4 ORs them in: its window then reads '?' off the line wherever the line starts in its word)
-    uint2* s_lut = reinterpret_cast<uint2*>(s_jobs + 128 + kLineWords);      // byte -> its eight bits as bytes (the stone operands of phase D)
-    uint32_t* s_wtab_words = s_jobs + 128 + kLineWords + 512;
+    uint2* s_lut = reinterpret_cast<uint2*>(s_static + kLineWords);      // byte -> its eight bits as bytes (the stone operands of phase D)
+    uint32_t* s_wtab_words = s_static + kLineWords + 512;
     const v4i* s_wtab = reinterpret_cast<const v4i*>(s_wtab_words);
     // the prefix tables' byte addresses (the kernel's LDS starts at address 0): the scan's, walked from S, and behind it the rescans', walked from the root
-    const uint32_t scan_prefix_at = static_cast<uint32_t>(trans_words + record_words + 128 + kLineWords + 512 + kWtabWords) * 4u;
+    const uint32_t scan_prefix_at = static_cast<uint32_t>(trans_words + record_words + kLineWords + 512 + kWtabWords) * 4u;
     const uint32_t root_prefix_at = scan_prefix_at + 4u * kPrefixTableWords;
     uint32_t* s_handout = s_wtab_words + kWtabWords + 2 * kPrefixTableWords;        // [0] boards handed out: starts at 2 x kBoardsPerBlock (every wavefront's first two boards are its own: see below)
 
@@ -465,7 +506,7 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
     const bool planes_out = out_density != nullptr && (phase_mask & 64) && !(phase_mask & 1024);
     int lane = lane0;
     // (from the lane's record, not from the staged copies: those are not there yet)
-    const uint32_t job_a = lane_lines.x, job_b = lane_lines.y;
+    const uint32_t lines_word = lane_lines.x, place_word = lane_lines.y;      // ("Lane -> lines" above)
     const uint32_t line_init_lo = lane_lines.z, line_init_hi = lane_lines.w;
     const uint32_t cell_row4 = lane_consts.x, cell_col = lane_consts.y, norm_a = lane_consts.z, norm_b = lane_consts.w;
     uint32_t* s_rows = s_misc + 16;                      // row y at [3 + y]
@@ -634,7 +675,7 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
 #ifdef GMK_PROFILE
         if (boards_done == 0) GMK_TL(2, __builtin_amdgcn_s_memtime());
 #endif
-        if (boards_done == 0) __syncthreads();                  // the tables are staged (the automaton at LDS address 0, the records, jobs, the tables of phase D,
+        if (boards_done == 0) __syncthreads();                  // the tables are staged (the automaton at LDS address 0, the records, the pads, the tables of phase D,
                                                                 // the hand-out counter): from here on the wavefronts never wait for each other
 #ifdef GMK_PROFILE
         if (boards_done == 0) GMK_TL(3, __builtin_amdgcn_s_memtime());
@@ -650,13 +691,13 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
             // there were nineteen -- and there is no reset between the two lines.  BOTH trailing pads stay: of the 21 523 239 lines of 5 to 15 cells, 59 050
             // report a match on the symbol behind the first trailing pad (a match ending one symbol back, found while falling back); sharing that symbol
             // with the second line's first cell would put the first line's late match into a record of the second line.  The stream is kept shifted left by 2, so a step is: symbol * 4 = low word & 12, LDS
-            // address = (previous word's next-row offset) | symbol * 4, one lookup.  Emitting transitions are queued raw
-            // (record, lane, step); the slot is a ballot prefix (this wave is the only producer), decoding happens in phase 2.
+            // address = (previous word's next-row offset) | symbol * 4, one lookup.  Emitting transitions are queued as
+            // (record, place of the symbol: `push` below); the slot is a ballot prefix (this wave is the only producer), phase 2 uses the entry as it is.
             int n_queued = 0;                                       // wave-uniform
             if (phase_mask & 2) {
-                const int len_a = static_cast<int>(job_a & 31u) - kSegPads, len_b = static_cast<int>(job_b & 31u) - kSegPads;
-                uint64_t syms = line_symbols(s_lines[(job_a >> 20) & 127u] >> norm_a, len_a);      // (a diagonal's word shifted down to its first cell)
-                syms |= line_symbols(s_lines[(job_b >> 20) & 127u] >> norm_b, len_b) << (2 * (len_a + kSegPads));
+                const int len_a = static_cast<int>(lines_word & 31u) - kSegPads, len_b = static_cast<int>((lines_word >> 5) & 31u) - kSegPads;
+                uint64_t syms = line_symbols(s_lines[(lines_word >> 10) & 127u] >> norm_a, len_a);      // (a diagonal's word shifted down to its first cell)
+                syms |= line_symbols(s_lines[(lines_word >> 17) & 127u] >> norm_b, len_b) << (2 * (len_a + kSegPads));
                 syms |= 0xAAAAAAAAAAAAAAAAull << (2 * (len_a + len_b + 2 * kSegPads));
                 // The stream is kept shifted left by 2: symbol s at bits 2 s + 2, so that the four bits from 2 s up are (symbol s - 1, symbol s) and
                 // one v_bfe + one v_bfi make the lookup address: (table word & 0x3FF3) | (those four bits & 12) -- the row offsets are multiples of 16.
@@ -664,13 +705,16 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                 const uint32_t rest = static_cast<uint32_t>(syms >> 28);      // symbols 15.. at bits 2.. (bits 0, 1: symbol 14)
                 // The emission of step s is worked out BEHIND the lookup of step s + 1 (the next address needs the table word only): the
                 // prefix count runs in the shadow of that lookup's LDS round trip; the write follows behind lookup s + 2 (below).  A queue entry is the table
-                // word itself with the low 17 bits (next row, kinds) replaced by lane | step << 6: the record number stays where it is.
+                // word itself with the low 17 bits (next row, kinds) replaced by the place of the symbol (`push`): the record number stays where it is.
                 // Where the queue stands is a byte address kept by the scalar unit; a lane adds its prefix count (the vector unit is
                 // what this kernel is bound by: 4 cycles per wave-instruction on a SIMD whatever the lanes do).
                 const uint32_t q_base = static_cast<uint32_t>(s_queue - lds) * 4u;     // (the kernel's LDS starts at address 0)
                 // The scalar unit keeps the fill level at most 64 entries below the capacity: a step's (at most 64) entries then fit whatever the
                 // lanes add, without a per-lane clamp (a vector instruction per step); a board that gets there is flagged below.
-                const uint32_t q_full = q_base + 4u * (kQueueCap - 64);
+                constexpr int kQueueFlagAt = kQueueCap - 64;        // the most entries the scan leaves: n_queued <= kQueueFlagAt
+                const uint32_t q_full = q_base + 4u * kQueueFlagAt;
+                // (phase 2 reads one round ahead, entry m + 64 for m < n_queued: inside the queue without a clamp)
+                static_assert(kQueueFlagAt > 0 && (kQueueFlagAt - 1) + 64 < kQueueCap, "the deposits' read one round ahead stays inside the queue");
                 uint32_t q_at = q_base;                             // wave-uniform
                 // A step's queue write is DEFERRED by one lookup more: `push` only works out a lane's address and entry (in the shadow of lookup s + 1) and
                 // `flush` writes them immediately behind lookup s + 2, one instruction after it.  The write is conditional, so the compiler's wait in front
@@ -680,13 +724,22 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                 uint32_t pend_at = 0, pend_entry = 0;
                 bool pend = false;
                 auto flush = [&]() { if (pend) *lds_word_rw(pend_at) = pend_entry; };
+                // The entry carries the PLACE of the consumed symbol -- cell, direction, minus the stride, as the deposits use them -- and not (lane, step):
+                // the place runs along with the steps, one add each (the stride comes out of the lines word by an SDWA byte select; the jump across a
+                // two-line lane's seam is one DPP add on its four lanes at step 9 and one at step 10), where lane | step << 6 was one OR each.
+                uint32_t place = place_word;                        // the place of step kScanPrefixSyms, the first step pushed
+                const int seam_jump = __builtin_amdgcn_sbfe(static_cast<int>(place_word), 17, 10);
                 auto push = [&](uint32_t word, int step) {
                     const bool emits = word > 0x1FFFFu;
                     const unsigned long long emitters = __ballot(emits);
                     const uint32_t ahead = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(emitters >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(emitters), 0u));
                     pend = emits;
                     pend_at = q_at + 4u * ahead;
-                    pend_entry = (word & ~0x1FFFFu) | (static_cast<uint32_t>(lane) | static_cast<uint32_t>(step) << 6);
+                    if (step > kScanPrefixSyms) place = place_advance(place, lines_word);
+                    static_assert(kPairedLanes == 8, "two banks of four lanes: the long first lines in front");
+                    if (step == kSeamStepShort) place = place_jump<kFirstPairedLane + 4>(place, seam_jump);   // lanes 60..63
+                    if (step == kSeamStepLong) place = place_jump<kFirstPairedLane>(place, seam_jump);        // lanes 56..59
+                    pend_entry = queue_entry(word, place);
                     asm volatile("" : "+v"(pend_at), "+v"(pend_entry));       // (worked out HERE: left to itself the compiler sinks both to where they are written)
                     q_at = min(q_at + 4u * static_cast<uint32_t>(__popcll(emitters)), q_full);
                 };
@@ -730,23 +783,17 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
 
             // ---- phase 2: one lane per emitting transition: the score deposits of its 1-2 matches ----
             if (phase_mask & 4) {
-                uint32_t qe_next = s_queue[min(lane, kQueueCap - 1)];      // (entry: record number << 17 | step << 6 | lane)
+                uint32_t qe_next = s_queue[lane];                   // (entry: record number << 17 | minus the stride << 11 | direction << 9 | cell)
                 for (int m = lane; m < n_queued; m += 64) {
                     const uint32_t qe = qe_next;
-                    qe_next = s_queue[min(m + 64, kQueueCap - 1)];      // (the next round's entry is on its way while this one is worked on;
-                                                                         //  fetching its record and line jobs ahead as well measured no gain)
-                    // which line of which lane, and where on it (symbol 0 of a line's segment is its first cell; the two behind its last cell are pads)
-                    const int src_lane = qe & 63, src_step = (qe >> 6) & 31;
+                    qe_next = s_queue[m + 64];                      // (the next round's entry is on its way while this one is worked on; m + 64 < n_queued + 64
+                                                                    //  <= kQueueCap, the scan's assert: no clamp.  Fetching its record ahead as well measured no gain)
+                    // the entry says where the consumed symbol lies and how to walk back from it: nothing to look up, nothing to work out
                     const uint4 rec_now = s_rec[qe >> 17];
-                    const uint32_t ja_now = s_jobs[src_lane * 2], jb_now = s_jobs[src_lane * 2 + 1];
-                    const int seg_a = ja_now & 31u;
-                    const bool second = src_step >= seg_a;
-                    const uint32_t job = second ? jb_now : ja_now;
-                    const int pos = src_step - (second ? seg_a : 0);
-                    const int dir = (job >> 5) & 3, stride = (job >> 7) & 31;
-                    const int cell_at = static_cast<int>((job >> 12) & 255u) + pos * stride;
-                    deposit_match(rec_now.x, rec_now.y, cell_at, dir, -stride, s_scores, s_cnt, s_misc, my_totals);
-                    if (rec_now.z) deposit_match(rec_now.z, rec_now.w, cell_at, dir, -stride, s_scores, s_cnt, s_misc, my_totals);
+                    const int cell_at = qe & 511u, dir = (qe >> 9) & 3u;
+                    const int back_step = __builtin_amdgcn_sbfe(static_cast<int>(qe), 11, 6);
+                    deposit_match(rec_now.x, rec_now.y, cell_at, dir, back_step, s_scores, s_cnt, s_misc, my_totals);
+                    if (rec_now.z) deposit_match(rec_now.z, rec_now.w, cell_at, dir, back_step, s_scores, s_cnt, s_misc, my_totals);
                 }
             }
             wave_phase_fence();
@@ -1053,29 +1100,58 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
 // ---- host side ----
 struct LineJob { int len, x0, y0, dir; };
 
-// The lane jobs and '?' pads as they lie in LDS (jobs_out: 128 words, pads_out: kLineWords) and the 64 lane records (records_out: 8 words each).
-int lane_tables(uint32_t* jobs_out, uint32_t* pads_out, uint32_t* records_out) {
+// The '?' pads as they lie in LDS (pads_out: kLineWords) and the 64 lane records (records_out: 8 words each), the lines word and the place word
+// ("Lane -> lines" above) checked against the plain statement: a record that differs from it is an error, not a wrong score.
+int lane_tables(uint32_t* pads_out, uint32_t* records_out) {
     std::vector<LineJob> lines;
     for (int i = 0; i < 15; ++i) lines.push_back({15, 0, i, 0});
     for (int i = 0; i < 15; ++i) lines.push_back({15, i, 0, 1});
     for (int d = -10; d <= 10; ++d) lines.push_back({15 - std::abs(d), d > 0 ? d : 0, d > 0 ? 0 : -d, 2});
     for (int k = 4; k <= 24; ++k) { const int x0 = std::min(k, 14); lines.push_back({std::min(k, 28 - k) + 1, x0, k - x0, 3}); }
     std::stable_sort(lines.begin(), lines.end(), [](const LineJob& a, const LineJob& b) { return a.len > b.len; });
-    uint32_t jobs[128];
-    for (uint32_t& j : jobs) j = static_cast<uint32_t>(kSegPads) | (15u << 20);                // "no line": length 0 (two pads) on a line word that stays zero
-    auto pack = [](const LineJob& l) {
-        const int line = l.dir == 0 ? l.y0 : l.dir == 1 ? kColBase + l.x0 : l.dir == 2 ? kDiagBase + l.x0 - l.y0 + 14 : kAntiBase + l.x0 + l.y0;
-        const int stride = l.dir == 0 ? 1 : l.dir == 1 ? 15 : l.dir == 2 ? 16 : 14;
-        return static_cast<uint32_t>((l.len + kSegPads) | (l.dir << 5) | (stride << 7) | ((l.y0 * 15 + l.x0) << 12) | (line << 20));
-    };
+    if (lines.size() != 64 + kPairedLanes) { gmk::set_error("lane lines: %zu lines for 64 lanes and %d second lines", lines.size(), kPairedLanes); return GMK_ERR_STATE; }
+    auto line_word = [](const LineJob& l) { return l.dir == 0 ? l.y0 : l.dir == 1 ? kColBase + l.x0 : l.dir == 2 ? kDiagBase + l.x0 - l.y0 + 14 : kAntiBase + l.x0 + l.y0; };
+    auto stride_of = [](int dir) { return dir == 0 ? 1 : dir == 1 ? 15 : dir == 2 ? 16 : 14; };
+    auto first_cell = [](const LineJob& l) { return l.y0 * 15 + l.x0; };
+    // The eight leftovers ride behind the eight shortest primaries, each behind a line of its OWN direction (the sort is stable: of every length the
+    // two diagonals stand in front of the two anti-diagonals): the 5-cell lines 68..71 behind the 8-cell lines of lanes 56..59, the 6-cell lines 64..67
+    // behind the 7-cell lines of lanes 60..63.  8 + 2 + 5 + 2 = 7 + 2 + 6 + 2 = 17 symbols.
+    auto second_line = [](int lane) { return lane < kFirstPairedLane ? -1 : lane < kFirstPairedLane + 4 ? lane + 12 : lane + 4; };
+    uint32_t lines_words[64], place_words[64];
     int steps = 0;
     for (int lane = 0; lane < 64; ++lane) {
-        jobs[lane * 2] = pack(lines[lane]);
-        if (lines[lane].len < kScanPrefixSyms) { gmk::set_error("lane jobs: lane %d starts with a line of %d cells, the scan's prefix read takes %d", lane, lines[lane].len, kScanPrefixSyms); return GMK_ERR_STATE; }
-        int total = lines[lane].len + kSegPads;
-        const int extra = 64 + (63 - lane);                   // shortest leftovers ride behind the shortest primaries
-        if (extra < static_cast<int>(lines.size())) { jobs[lane * 2 + 1] = pack(lines[extra]); total += lines[extra].len + kSegPads; }
-        steps = std::max(steps, total);
+        const LineJob& a = lines[lane];
+        const LineJob* b = second_line(lane) < 0 ? nullptr : &lines[second_line(lane)];
+        if (a.len < kScanPrefixSyms) { gmk::set_error("lane lines: lane %d starts with a line of %d cells, the scan's prefix read takes %d", lane, a.len, kScanPrefixSyms); return GMK_ERR_STATE; }
+        if (b && b->dir != a.dir) { gmk::set_error("lane lines: lane %d walks lines of directions %d and %d", lane, a.dir, b->dir); return GMK_ERR_STATE; }
+        const int seg_a = a.len + kSegPads, seg_b = b ? b->len + kSegPads : kSegPads, stride = stride_of(a.dir);
+        // (where the kernel adds the jump is fixed in its text: place_jump's lanes and steps)
+        if (b && seg_a != (lane < kFirstPairedLane + 4 ? kSeamStepLong : kSeamStepShort)) { gmk::set_error("lane lines: lane %d steps to its second line at step %d", lane, seg_a); return GMK_ERR_STATE; }
+        const int jump = b ? first_cell(*b) - (first_cell(a) + seg_a * stride) : 0;
+        if (jump < -512 || jump > 511) { gmk::set_error("lane lines: lane %d jumps %d cells", lane, jump); return GMK_ERR_STATE; }
+        // "no line": length 0 (two pads) on line word 15, which stays zero
+        lines_words[lane] = static_cast<uint32_t>(seg_a | seg_b << 5 | line_word(a) << 10 | (b ? line_word(*b) : 15) << 17 | stride << 24);
+        place_words[lane] = static_cast<uint32_t>(first_cell(a) + kScanPrefixSyms * stride) | static_cast<uint32_t>(a.dir) << 9 | (static_cast<uint32_t>(-stride) & 63u) << 11
+                            | (static_cast<uint32_t>(jump) & 1023u) << 17;
+        steps = std::max(steps, seg_a + (b ? seg_b : 0));
+        // The two words against the plain statement, every step the scan pushes: which segment, the place on its line, first cell + place * stride,
+        // direction and stride -- what phase 2 used to work out from (lane, step) -- against the kernel's arithmetic on the packed word.  (A lane with one
+        // line goes on along it behind its pads: the stream's filler, which reports nothing.)
+        uint32_t place = place_words[lane];
+        const int jump_field = static_cast<int>(place_words[lane] << 5) >> 22;                       // v_bfe_i32 17, 10
+        for (int step = kScanPrefixSyms; step < kScanSteps; ++step) {
+            if (step > kScanPrefixSyms) place += lines_words[lane] >> 24;
+            if (step == kSeamStepShort && lane >= kFirstPairedLane + 4) place += static_cast<uint32_t>(jump_field);
+            if (step == kSeamStepLong && lane >= kFirstPairedLane && lane < kFirstPairedLane + 4) place += static_cast<uint32_t>(jump_field);
+            const bool second = b && step >= seg_a;
+            const LineJob& l = second ? *b : a;
+            const int cell = first_cell(l) + (step - (second ? seg_a : 0)) * stride_of(l.dir);
+            const uint32_t want = static_cast<uint32_t>(cell) | static_cast<uint32_t>(l.dir) << 9 | (static_cast<uint32_t>(-stride_of(l.dir)) & 63u) << 11;
+            if (cell < 0 || cell > 511 || (place & 0x1FFFFu) != want) {
+                gmk::set_error("lane lines: lane %d step %d carries place 0x%05x, the plain statement gives 0x%05x", lane, step, place & 0x1FFFFu, want);
+                return GMK_ERR_STATE;
+            }
+        }
     }
     uint32_t init[kLineWords] = {};                              // every cell of every line blank (symbol 3)
     for (int i = 0; i < 15; ++i) init[i] = init[kColBase + i] = 0x3FFFFFFFu;
@@ -1095,19 +1171,18 @@ int lane_tables(uint32_t* jobs_out, uint32_t* pads_out, uint32_t* records_out) {
         consts[lane][0] = row4;
         consts[lane][1] = col;
         for (int k = 0; k < 2; ++k) {
-            const uint32_t job = jobs[lane * 2 + k], dir = (job >> 5) & 3u, first = (job >> 12) & 255u;
-            consts[lane][2 + k] = dir == 2u ? 2u * (first % 15u) : dir == 3u ? 2u * (first / 15u) : 0u;
+            const int at = k == 0 ? lane : second_line(lane);
+            consts[lane][2 + k] = at < 0 ? 0u : lines[at].dir == 2 ? 2u * static_cast<uint32_t>(lines[at].x0) : lines[at].dir == 3 ? 2u * static_cast<uint32_t>(lines[at].y0) : 0u;
         }
     }
-    for (int i = 0; i < 128; ++i) jobs_out[i] = jobs[i];
     for (int i = 0; i < kLineWords; ++i) pads_out[i] = ~init[i] & 0xAAAAAAAAu;
     for (int lane = 0; lane < 64; ++lane) {
         uint32_t* r = records_out + 8 * lane;
-        r[0] = jobs[lane * 2]; r[1] = jobs[lane * 2 + 1];
+        r[0] = lines_words[lane]; r[1] = place_words[lane];
         r[2] = init[lane]; r[3] = init[std::min(64 + lane, kLineWords - 1)];
         for (int k = 0; k < 4; ++k) r[4 + k] = consts[lane][k];
     }
-    if (steps != kScanSteps) { gmk::set_error("lane jobs: %d scan steps, the kernel is built for %d", steps, kScanSteps); return GMK_ERR_STATE; }
+    if (steps != kScanSteps) { gmk::set_error("lane lines: %d scan steps, the kernel is built for %d", steps, kScanSteps); return GMK_ERR_STATE; }
     return GMK_OK;
 }
 
@@ -1185,14 +1260,14 @@ int scan_prefix_table(const gmk::DeviceTables& t, uint32_t start, uint16_t* out 
     return GMK_OK;
 }
 
-// The image of the kernel's tables (see kLaneRecordVecs): [automaton][records][lane jobs 128][pads][bits-to-bytes 512][weights][scan prefix 128][root prefix 128][hand-out 4], then the lane
+// The image of the kernel's tables (see kLaneRecordVecs): [automaton][records][pads][bits-to-bytes 512][weights][scan prefix 128][root prefix 128][hand-out 4], then the lane
 // records.  Built once; the automaton and the records are copied from the device state's tables.
 int build_stage_image(const gmk::DeviceState& st, uint4** d_out, int* stage_vecs) {
     const size_t trans_words = static_cast<size_t>(st.n_states) * 4, record_words = static_cast<size_t>(st.n_records) * 4;
     std::vector<uint32_t> rest(kStaticTableWords + 64 * 4 * kLaneRecordVecs, 0u);
-    uint32_t* jobs = rest.data(), *pads = jobs + 128, *lut = pads + kLineWords, *wtab = lut + 512, *scan_prefix = wtab + kWtabWords, *root_prefix = scan_prefix + kPrefixTableWords,
+    uint32_t* pads = rest.data(), *lut = pads + kLineWords, *wtab = lut + 512, *scan_prefix = wtab + kWtabWords, *root_prefix = scan_prefix + kPrefixTableWords,
               *handout = root_prefix + kPrefixTableWords, *records = handout + 4;
-    int rc = lane_tables(jobs, pads, records);
+    int rc = lane_tables(pads, records);
     if (rc != GMK_OK) return rc;
     for (uint32_t b = 0; b < 256; ++b) { lut[2 * b] = ((b & 15u) * 0x204081u) & 0x01010101u; lut[2 * b + 1] = ((b >> 4) * 0x204081u) & 0x01010101u; }
     rc = density_weights(reinterpret_cast<int8_t*>(wtab));
@@ -1313,6 +1388,12 @@ extern "C" int gmk_eval_launch_info(int n, int* grid, int* block, int* lds_bytes
     if (block) *block = kThreads;
     if (lds_bytes) *lds_bytes = static_cast<int>(l.lds);
     return GMK_OK;
+}
+
+extern "C" int gmk_eval_lane_records(uint32_t* records) {
+    if (!records) { gmk::set_error("gmk_eval_lane_records: bad arguments"); return GMK_ERR_ARG; }
+    uint32_t pads[kLineWords];
+    return lane_tables(pads, records);
 }
 
 extern "C" int gmk_eval_batch_host(const uint16_t* h_planes, int n, int32_t* h_scores, int32_t* h_density,

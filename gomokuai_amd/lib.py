@@ -60,7 +60,7 @@ EXPORTS = [
     "gmk_init", "gmk_shutdown", "gmk_pool_release", "gmk_pool_poison", "gmk_last_error", "gmk_device_info",
     "gmk_tables_info", "gmk_tables_pattern", "gmk_tables_copy", "gmk_tables_copy_dat", "gmk_tables_scan",
     "gmk_synth_boards", "gmk_moves_to_planes",
-    "gmk_eval_batch", "gmk_eval_batch_host", "gmk_eval_launch_info",
+    "gmk_eval_batch", "gmk_eval_batch_host", "gmk_eval_launch_info", "gmk_eval_lane_records",
     "gmk_mcts_create", "gmk_mcts_destroy", "gmk_mcts_set_roots", "gmk_mcts_set_game_ids", "gmk_mcts_run", "gmk_mcts_root_stats",
     "gmk_mcts_alg_bytes", "gmk_mcts_launch_info", "gmk_visits_to_pi", "gmk_mcts_advance", "gmk_mcts_step", "gmk_mcts_step_host", "gmk_mcts_add_root_noise", "gmk_mcts_set_option", "gmk_mcts_reserve", "gmk_selfplay_run", "gmk_samples_from_records",
     "gmk_records_scan", "gmk_records_packed_bytes", "gmk_records_pack", "gmk_records_unpack", "gmk_samples_from_packed",
@@ -125,6 +125,7 @@ def load():
     L.gmk_eval_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     L.gmk_eval_batch_host.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.gmk_eval_launch_info.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.gmk_eval_lane_records.argtypes = [vp]
     L.gmk_mcts_create.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_uint64, C.POINTER(vp)]
     L.gmk_mcts_destroy.argtypes = [vp]
     L.gmk_mcts_set_roots.argtypes = [vp, vp, vp, C.c_uint32]
@@ -389,6 +390,13 @@ def eval_launch_info(n):
     g, b, l = C.c_int(), C.c_int(), C.c_int()
     _check(load().gmk_eval_launch_info(n, C.byref(g), C.byref(b), C.byref(l)))
     return {"grid": g.value, "block": b.value, "lds_bytes": l.value}
+
+
+def eval_lane_records():
+    """K1's 64 lane records as the host builds and checks them, [64, 8] uint32: [:, 0] the lines word, [:, 1] the place word (host only)."""
+    rec = np.zeros((64, 8), dtype=np.uint32)
+    _check(load().gmk_eval_lane_records(rec.ctypes.data))
+    return rec
 
 
 # ---------------- K3: batched MCTS (RandomPolicy) ----------------

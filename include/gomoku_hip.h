@@ -120,6 +120,9 @@ int gmk_eval_batch_host(const uint16_t *h_planes, int n,
                         int32_t *h_scores, int32_t *h_density, uint32_t *h_totals, int32_t *h_status);
 /* launch geometry the library chose for gmk_eval_batch (for profiling reports) */
 int gmk_eval_launch_info(int n, int *grid, int *block, int *lds_bytes);
+/* for tests and diagnostics only (no caller needs it to evaluate): the 64 lane records of gmk_eval_batch's scan as the host builds and checks them (8 words each; [0] the lines word, [1] the place word: eval_kernel.hip,
+ * "Lane -> lines").  Host only: needs neither a device nor gmk_init. */
+int gmk_eval_lane_records(uint32_t *records /* 64 * 8 words */);
 
 /* ---- K2: incrementally maintained evaluator states ----
  * One handle = n_games Evaluator objects (core/lib/include/Pattern.h:142-220) living in HBM, 17 792 B each.  Unlike K1 it keeps
