@@ -30,11 +30,13 @@
 //     compact list of <= 4 score deposits -- a colour's own and opponent view of a cell are the halves of one 64-bit word, so a deposit is ONE
 //     ds_add_u64 whose value decides -- and 4-bit per-(cell, colour, direction, type) counters;
 //   * phase 3: one lane per cell: compound candidates from the counters -- a colour's half word h of the OR-ed counters makes one iff
-//     h & ((h - 1) | 0xEEEE): v_or3, v_pk_add_u16, v_bitop3, v_cmp per pass in front of the ballot (the static listing, profiles/r10_k1_frame_counts.txt); phase 3b: one lane per (candidate, colour):
-//     the density gate "count >= 2" from seven row popcounts, the compound decision in closed form (components n, threes s), +-600 deposits,
-//     components queued by ballot prefix with their line word and slot in the entry;
+//     h & ((h - 1) | 0xEEEE): v_or3, v_pk_add_u16, v_bitop3, v_cmp per pass in front of the ballot (the static listing, profiles/r10_k1_frame_counts.txt); phase 3b: four lanes per (candidate, colour), sixteen pairs per round (round 15):
+//     the compound decision in closed form (components n, threes s) in every lane of the quad, +-600 deposits by its lane 0, the two components queued
+//     by its lanes 0 and 1 -- one entry per lane, slots by a ballot prefix over quads -- with their line word and slot in the entry.  The reference's density
+//     gate "count >= 2" is not evaluated: a pair that gets here always passes it (phase 3b says why; tests/test_eval_density_gate.py);
 //   * phase 4: seven lanes per compound component, nine per round: its counter-move cells from the 13-symbol window around it (one
-//     v_alignbit of the line word with its '?' pads), walked as one read of the root's four-symbol prefix table and three or four lookups;
+//     v_alignbit of the line word with its '?' pads), walked as one read of the root's four-symbol prefix table and three or four lookups; whether the
+//     match found has its '_' on the cell is one zero-nibble test of its four deposit fields (counter_match; tests/test_eval_nibble_match.py);
 //   * phase 5: the 3.6 KB score block leaves LDS transposed to [group][cell]: sixteen non-temporal dword stores of 256 contiguous bytes, in
 //     ADDRESS order (the two parts of a cache line that two pieces share reach the L2 back to back);
 //   * phase D, once per group, by the wavefront that is handed board 12 k of its workgroup's run for the run's k-th group: the density planes of the
@@ -253,12 +255,12 @@ __device__ __forceinline__ int counter_match(uint32_t w0, int k, int want) {
     const int back = k - static_cast<int>((w0 >> 27) & 1u) - 6;
     if (!w0 || type != want || back < 0 || back >= len) return -1;
     const int n_dep = (w0 >> 8) & 7;
-    bool on_q = false;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        const uint32_t f = (w0 >> (11 + 4 * d)) & 15u;
-        on_q |= d < n_dep && f == (8u | static_cast<uint32_t>(back));               // '_' on q
-    }
+    // Is one of the first n_dep deposit fields (four bits each, from bit 11) the '_' at `back`, 8 | back?  XOR-ed with that value in every nibble the
+    // sought field is a ZERO nibble, and (x - 0x1111) & ~x & 0x8888 flags the lowest zero nibble of x exactly; above it the borrow may flag nibbles
+    // that hold 1, which does not matter for "any": a wrong flag has a true one below it, inside the mask whenever it is itself
+    // (tests/test_eval_nibble_match.py: every record word of the tables and every 16-bit field, against the four compares this replaces)
+    const uint32_t x = ((w0 >> 11) & 0xFFFFu) ^ (static_cast<uint32_t>(back) * 0x1111u + 0x8888u);
+    const bool on_q = ((x - 0x1111u) & ~x & 0x8888u & ((1u << (4 * n_dep)) - 1u)) != 0u;   // '_' on q (n_dep <= 7: the shift stays below 32)
     return on_q ? back : -1;
 }
 
@@ -612,7 +614,7 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                 g |= static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, near, 0x112, 0xF, 0xF, true)) | static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, near, 0x102, 0xF, 0xF, true));     // rows y -+ 2
                 g |= static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, far, 0x113, 0xF, 0xF, true)) | static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, far, 0x103, 0xF, 0xF, true));       // rows y -+ 3
                 const uint32_t empty = ~(r | (r >> 16)) & 0x7FFFu;
-                if (lane < 15) s_rows[3 + lane] = r;            // (three zero rows on either side: the density gate of phase 3b reads rows y - 3 .. y + 3 unchecked)
+                if (lane < 15) s_rows[3 + lane] = r;            // (three zero rows on either side: phase 3b's density gate read rows y - 3 .. y + 3 unchecked until round 15; nothing reads them now)
                 late_gate = static_cast<int>(g & (empty | (empty << 16)));
                 // (the first score-block piece's gate word: asked for here, one lookup ahead of its use, see below)
                 late_gw = __builtin_amdgcn_ds_bpermute(static_cast<int>(cell_row4 & 0xFFu), late_gate);
@@ -848,48 +850,48 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
             wave_phase_fence();
             GMK_STAMP(4);
 
-            // ---- phase 3b: one lane per candidate cell and colour: the compound decision (Pattern.cpp:440-486), critical-point deposits,
-            //      counter-move rescans queued in the upper half of the queue ----
+            // ---- phase 3b: four lanes (a quad) per candidate cell and colour, sixteen such pairs per round: the compound decision
+            //      (Pattern.cpp:440-486) in every lane of the quad, critical-point deposits by its lane 0, the two counter-move rescans queued in
+            //      the upper half of the queue by its lanes 0 and 1, one entry each.  What a board pays for is the length of the round, not the
+            //      lanes it leaves idle (a typical board has two to four pairs): a lane builds ONE entry where it built two ----
             // (an empty cell is a candidate at most once and a board with a counter has a stone: n_cand <= 224 = kQueueCap / 2, the list cannot overflow)
             if (n_cand > kQueueCap / 2) { s_misc[2] = 1; n_cand = kQueueCap / 2; }
             if (phase_mask & 2048) n_cand = 0;
-            // The rescan queue works in ROUNDS: a round of phase 3b queues at most 64 x 2 entries, and phase 4 empties the queue once the next
+            // The rescan queue works in ROUNDS: a round of phase 3b queues at most 16 x 2 entries, and phase 4 empties the queue once the next
             // round's might not fit, and behind the last round.  (Legal positions queue more than the upper half holds -- 116 compounds of this
             // kind = 232 entries on a position of tests/golden/k1_saturated.npz -- and used to be flagged with their rescans dropped.)  The
-            // benchmark's boards have at most 32 candidates: one round, phase 4 once, as before; a board without candidates skips both.
-            constexpr int kRescanFlush = kQueueCap / 2 - 2 * 64;    // fill level above which another round might not fit
-            static_assert(kRescanFlush > 0 && kRescanFlush + 2 * 64 <= kQueueCap / 2, "a round of phase 3b fits behind the flush level");
+            // benchmark's boards have a median of under two candidates and at most 32: one round on most, four at the most, phase 4 once; a board
+            // without candidates skips both.  A saturated position (121 candidates) takes 16 rounds where it took 4 with 64 pairs per round.
+            constexpr int kPairsPerRound = 16;                      // (candidate, colour) pairs per round: four lanes each
+            constexpr int kRescanFlush = kQueueCap / 2 - 2 * kPairsPerRound;    // fill level above which another round might not fit
+            static_assert(kRescanFlush > 0 && kRescanFlush + 2 * kPairsPerRound <= kQueueCap / 2, "a round of phase 3b fits behind the flush level");
             int n_comp_q = 0;                                       // components queued for phase 4 (wave-uniform: slots by ballot prefix)
             if (phase_mask & 8)
-            for (int v0 = 0; v0 < 2 * n_cand; v0 += 64) {           // one lane per (candidate cell, colour): 0 white, 1 black
-                const int v = v0 + lane;
-                const int flag_shift = 8 + (v & 1);                // this lane's colour flag in a candidate entry (bit 8 white, bit 9 black)
-                const uint32_t ce = s_queue[v >> 1];                // (< n_cand + 32 <= 256: inside the queue; lanes past the end are masked below)
+            for (int v0 = 0; v0 < 2 * n_cand; v0 += kPairsPerRound) {      // four lanes per (candidate cell, colour): 0 white, 1 black
+                int lane_3 = lane;                                  // (an opaque copy: the quad's place is derived here, not kept in registers across the board loop)
+                asm volatile("" : "+v"(lane_3));
+                const int j = lane_3 & 3, v = v0 + (lane_3 >> 2);
+                const int flag_shift = 8 + (v & 1);                // this pair's colour flag in a candidate entry (bit 8 white, bit 9 black)
+                const uint32_t ce = s_queue[v >> 1];                // (< n_cand + 8 <= 232: inside the queue; pairs past the end are masked below.  One address per quad: a broadcast)
                 const int q = ce & 255, c = v & 1;
                 bool queue = false;
-                uint32_t ent1 = 0, ent2 = 0;
-                if (v < 2 * n_cand && ((ce >> flag_shift) & 1u)) {
-                    // this colour's four direction nibbles of the three counter words (read together with the rows below: one round trip)
+                uint32_t ent = 0;
+                if (v < 2 * n_cand && ((ce >> flag_shift) & 1u)) {  // (the same in the four lanes of a quad)
+                    // this colour's four direction nibbles of the three counter words
                     const uint32_t f3 = (s_cnt[q] >> (16 * c)) & 0xFFFFu, fd = (s_cnt[kCells + q] >> (16 * c)) & 0xFFFFu, f2 = (s_cnt[2 * kCells + q] >> (16 * c)) & 0xFFFFu;
-                    // the density gate (Pattern.cpp:182): the colour's density COUNT at the cell must be two or more: its stones under the
-                    // non-zero cells of the 7x7 BlockWeights mask around q, counted from the rows (black low, white high half word)
-                    uint32_t dens = 0;
                     const int qy = (q * 0x8889) >> 19, qx = q - 15 * qy;
+                    // The reference's density gate (Pattern.cpp:182: the colour's density COUNT at the cell must be two or more) is not evaluated: it holds for
+                    // every pair that gets here.  The pair's flag says that a LiveThree, DeadThree or LiveTwo match of the colour has a '_' on q; in every such
+                    // pattern every '_' has two or more of the pattern's own stones within three cells on its line, and the count's 7x7 mask covers all
+                    // eight line directions out to three cells (tests/test_eval_density_gate.py checks both on the tables; until round 15 seven row reads,
+                    // masks and popcounts per pair worked the count out, about 35 of the round's 140 vector instructions, and no board ever failed it).
                     {
-                        const int half = c ? 0 : 16;
-    #pragma unroll
-                        for (int dy = -3; dy <= 3; ++dy) {
-                            const uint32_t pattern = dy == 0 ? 0x77u : (dy == 3 || dy == -3) ? 0x49u : 0x3Eu;      // 1110111, 1001001, 0111110
-                            const uint32_t mask = ((pattern << qx) >> 3) & 0x7FFFu;
-                            dens += __popc((s_rows[3 + qy + dy] >> half) & mask);
-                        }
-                    }
-                    if (dens >= 2u) {
                         // The reference walks the directions in order through a state machine S0, L2, LD3, To33, To43, To44 (Pattern.cpp:440-486); in
                         // each direction the component is the first of LiveThree, DeadThree, LiveTwo with a non-zero counter, taken once or twice (the
                         // counters count like its 2-bit shift flags: 0, 1, 2 or more, Pattern.cpp:395-400).  Its outcome does not depend on the order:
                         // with n components of which s are threes (weight 2, a LiveTwo 1), the state ends at 3 + min(2, s) for n >= 2 -- the first two
                         // transitions add w1 + w2 + 1, every further one w - 1, capped at 5 -- and the "triple" flag is n >= 3.  So: nibble masks.
+                        // (Worked out in every lane of the quad: the instructions are wave-wide anyway.)
                         const uint32_t up3 = (f3 >> 1) | (f3 >> 2) | (f3 >> 3), upd = (fd >> 1) | (fd >> 2) | (fd >> 3), up2 = (f2 >> 1) | (f2 >> 2) | (f2 >> 3);
                         const uint32_t sel3 = (f3 | up3) & 0x1111u;                                          // directions whose component is a LiveThree
                         const uint32_t seld = (fd | upd) & 0x1111u & ~sel3;                                  // ... a DeadThree
@@ -898,45 +900,45 @@ void eval_positions_kernel(const uint16_t* __restrict__ planes, int n_boards, in
                         const uint32_t twice_strong = (sel3 & up3) | (seld & upd), twice = twice_strong | (sel2 & up2);     // taken twice (counter >= 2)
                         const int n_comp = __popc(any_dir) + __popc(twice), threes = __popc(strong) + __popc(twice_strong);
                         if (n_comp < 2) {
-                            s_misc[2] = 1;                                                                   // reference reads out of bounds here
+                            if (j == 0) s_misc[2] = 1;                                                       // reference reads out of bounds here
                         } else {
-                            const int ctype = min(threes, 2);
-                            atomicAdd(&s_misc[12 + ctype], c ? 0x10000u : 1u);
-                            // updateCritical, both perspectives: the colour's pair of the cell
-                            const uint32_t crit = 600u * static_cast<uint32_t>(n_comp);
-                            atomicAdd(reinterpret_cast<unsigned long long*>(s_scores) + 2 * q + c, (static_cast<unsigned long long>(crit) << 32) | crit);
+                            if (j == 0) {                                                                    // once per pair
+                                const int ctype = min(threes, 2);
+                                atomicAdd(&s_misc[12 + ctype], c ? 0x10000u : 1u);
+                                // updateCritical, both perspectives: the colour's pair of the cell
+                                const uint32_t crit = 600u * static_cast<uint32_t>(n_comp);
+                                atomicAdd(reinterpret_cast<unsigned long long*>(s_scores) + 2 * q + c, (static_cast<unsigned long long>(crit) << 32) | crit);
+                            }
                             // exactly two components, no live three among them: queue their counter-move rescans, in direction order, with what
                             // phase 4 needs of each line ready in the entry: q | colour << 8 | direction << 9 | type slot << 11 | line word << 13 |
                             // q's slot in the word << 20.  A line word holds cell x at slot x (rows, diagonals) or y (columns, anti-diagonals), so
-                            // per direction d = 0..3 the word is byte d of `lines` and the slot nibble d of `slots`
+                            // per direction d = 0..3 the word is byte d of `lines` and the slot nibble d of `slots`.  Lane 0 of the quad builds the
+                            // first component's entry, lane 1 the second's (lanes 2 and 3 build it too and write nothing)
                             queue = n_comp < 3 && !sel3;
-                            const uint32_t b1 = static_cast<uint32_t>(__ffs(any_dir) - 1);                   // 4 d1
                             const uint32_t others = any_dir & (any_dir - 1u);
-                            const uint32_t b2 = others ? static_cast<uint32_t>(__ffs(others) - 1) : b1;       // 4 d2
+                            const uint32_t pick = (j == 0 || !others) ? any_dir : others;                    // a component taken twice is both entries
+                            const uint32_t b = static_cast<uint32_t>(__ffs(pick) - 1);                       // 4 d
                             const uint32_t ux = static_cast<uint32_t>(qx), uy = static_cast<uint32_t>(qy);
                             const uint32_t lines = (static_cast<uint32_t>(kColBase) << 8 | static_cast<uint32_t>(kDiagBase + 14) << 16 | static_cast<uint32_t>(kAntiBase) << 24)
                                                    + ((ux << 8) * 0x10101u) + uy * 0xFF0001u;               // y | 20 + x | 50 + x - y | 65 + x + y
                             const uint32_t slots = ux * 0x0101u + uy * 0x1010u;                              // x | y | x | y
-                            const uint32_t head = static_cast<uint32_t>(q) | (static_cast<uint32_t>(c) << 8);
-                            auto entry = [&](uint32_t b) {
-                                const uint32_t tslot = ((seld >> b) & 1u) ? 1u : 2u;                         // DeadThree 1, LiveTwo 2
-                                return head | (b >> 2) << 9 | tslot << 11 | __builtin_amdgcn_ubfe(lines, 2 * b, 8) << 13 | __builtin_amdgcn_ubfe(slots, b, 4) << 20;
-                            };
-                            ent1 = entry(b1);
-                            ent2 = entry(b2);
+                            const uint32_t tslot = ((seld >> b) & 1u) ? 1u : 2u;                             // DeadThree 1, LiveTwo 2
+                            ent = static_cast<uint32_t>(q) | (static_cast<uint32_t>(c) << 8) | (b >> 2) << 9 | tslot << 11 | __builtin_amdgcn_ubfe(lines, 2 * b, 8) << 13
+                                  | __builtin_amdgcn_ubfe(slots, b, 4) << 20;
                         }
                     }
                 }
-                const unsigned long long queuers = __ballot(queue);
-                if (queue) {
+                // quads are counted, not lanes: of each quad only its LAST lane stays in the ballot, so that what a lane counts below itself is the
+                // queueing quads in front of its own, whichever lane of the quad it is
+                const unsigned long long queuers = __ballot(queue) & 0x8888888888888888ull;
+                if (queue && j < 2) {
                     const uint32_t slot = static_cast<uint32_t>(n_comp_q) + 2u * __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(queuers >> 32),
                                                                                                           __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(queuers), 0u));
-                    // (slots are even, and slot + 1 <= kRescanFlush + 2 * 63 + 1 < kQueueCap / 2: no bounds check)
-                    s_queue[kQueueCap / 2 + slot] = ent1;
-                    s_queue[kQueueCap / 2 + slot + 1] = ent2;
+                    // (slot + j <= kRescanFlush + 2 * 15 + 1 < kQueueCap / 2: no bounds check)
+                    s_queue[kQueueCap / 2 + slot + static_cast<uint32_t>(j)] = ent;
                 }
                 n_comp_q += 2 * __popcll(queuers);
-                if (v0 + 64 < 2 * n_cand && n_comp_q <= kRescanFlush) continue;      // more candidates and room for their round: on with phase 3b
+                if (v0 + kPairsPerRound < 2 * n_cand && n_comp_q <= kRescanFlush) continue;      // more candidates and room for their round: on with phase 3b
             wave_phase_fence();
             GMK_STAMP(5);
 

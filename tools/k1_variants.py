@@ -47,8 +47,60 @@ def run(names):
                                             "" if ref is None else ("outputs = base" if sums.get(n) == ref else "OUTPUTS DIFFER FROM base: %s" % sums.get(n))))
 
 
+def one_process(names, rounds=9, launches=300):
+    """every build's library loaded into THIS process (separate copies: separate paths), `rounds` rounds of `launches` event-timed launches each, the builds
+    taken in turn within a round and the turn order rotated from round to round; the four outputs of every build compared with the first build's, word for word"""
+    import ctypes as C
+    import numpy as np, torch
+    from gomokuai_amd import lib as G
+    names = names or sorted(f[len("libgomoku_hip_"):-3] for f in os.listdir(VAR) if f.endswith(".so"))
+    n = int(os.environ.get("GMK_EVAL_BOARDS", "65536"))
+    torch.cuda.set_device(0); G.init(0)
+    _, _, planes = G.synth_boards(n, int(os.environ.get("GMK_EVAL_KIND", "0")))
+    dev = torch.device("cuda", 0)
+    d_planes = torch.from_numpy(planes.view(np.int16).reshape(n, 32)).to(dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    libs, outs = {}, {}
+    for name in names:
+        L = C.CDLL(os.path.join(VAR, "libgomoku_hip_%s.so" % name))
+        L.gmk_init.argtypes = [C.c_int]
+        L.gmk_eval_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        if L.gmk_init(0) < 0:
+            raise SystemExit("%s: gmk_init failed" % name)
+        libs[name] = L
+        outs[name] = [torch.full((n, w), 0x5A5A5A5A, dtype=torch.int32, device=dev) for w in (900, 900, 11, 1)]
+
+    def launch(name):
+        o = outs[name]
+        if libs[name].gmk_eval_batch(d_planes.data_ptr(), n, o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), stream) < 0:
+            raise SystemExit("%s: gmk_eval_batch failed" % name)
+
+    for name in names:
+        for _ in range(10): launch(name)
+    torch.cuda.synchronize()
+    same = {name: all(torch.equal(a, b) for a, b in zip(outs[names[0]], outs[name])) for name in names}
+    times = {name: [] for name in names}
+    for rnd in range(rounds):
+        for k in range(len(names)):
+            name = names[(k + rnd) % len(names)]
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(launches): launch(name)
+            e1.record(); torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / launches)
+    ref = sorted(times[names[0]])[rounds // 2]
+    for name in names:
+        t = sorted(times[name])
+        print("%-12s %s   median %.4f  min %.4f  max %.4f  (%+.2f %% of %s's median)   outputs %s" % (name, " ".join("%.4f" % x for x in times[name]), t[rounds // 2], t[0], t[-1],
+              100.0 * (t[rounds // 2] / ref - 1.0), names[0], "= %s's" % names[0] if same[name] else "DIFFER FROM %s's" % names[0]), flush=True)
+    if not all(same.values()):
+        raise SystemExit(1)
+
+
 if __name__ == "__main__":
     if sys.argv[1] == "build":
         build(sys.argv[2:])
+    elif sys.argv[1] == "oneproc":       # (on the GPU box: ms per launch, every build in one process)
+        one_process(sys.argv[2:])
     else:
         run(sys.argv[2:])
