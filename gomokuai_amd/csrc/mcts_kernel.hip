@@ -878,6 +878,134 @@ __global__ void mcts_root_stats_kernel(const GameHeader* __restrict__ headers, c
     }
 }
 
+// The move gmk_mcts_step would make with a forced move of -1 and the root children's visit counts, left ON THE DEVICE for the match referee
+// (match_kernel.hip; K6's twin is trad_root_choice_kernel): the most visited root child, first maximum in child order (= cell order), as
+// int16 -- -1 for a finished game and for a root without a visited child -- and the counts by cell saturated like the records' rows (visits
+// may be null; a finished game's row is zero).  It reads the arena the game's tree is in now, as mcts_root_stats_kernel does.  One
+// wavefront per game.
+__global__ __launch_bounds__(64)
+void mcts_root_choice_kernel(const GameHeader* __restrict__ headers, const uint2* __restrict__ stats, const uint32_t* __restrict__ link, size_t cap,
+                             size_t arena_stride, int n_games, int16_t* __restrict__ cells, uint16_t* __restrict__ visits) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g >= n_games) return;
+    const GameHeader& hdr = headers[g];
+    const size_t base = static_cast<size_t>(g) * cap + (hdr.arena ? arena_stride : 0);
+    const uint32_t first = (hdr.status & 1u) ? 0u : link[base + hdr.root] >> 8;
+    const int n_child = first ? 225 - static_cast<int>(hdr.stones) : 0;
+    uint16_t* row = visits ? visits + static_cast<size_t>(g) * 225 : nullptr;
+    if (row) {
+        for (int i = lane; i < 225; i += 64) row[i] = 0;
+        __syncthreads();                                            // a child's count goes to its CELL: another lane's zero must be there first
+    }
+    long long best = 0;                                             // a child without a visit is not played
+    int best_i = 225;
+    for (int i = lane; i < n_child; i += 64) {
+        const uint32_t v = stats[base + first + i].x;
+        if (row) row[link[base + first + i] & 0xFFu] = static_cast<uint16_t>(min(v, 65535u));
+        if (static_cast<long long>(v) > best) { best = v; best_i = i; }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const long long o = __shfl_xor(best, m, 64);
+        const int oi = __shfl_xor(best_i, m, 64);
+        if (o > best || (o == best && oi < best_i)) { best = o; best_i = oi; }
+    }
+    if (lane == 0) cells[g] = best > 0 ? static_cast<int16_t>(link[base + first + static_cast<uint32_t>(best_i)] & 0xFFu) : static_cast<int16_t>(-1);
+}
+
+// gmk_mcts_step with the cells and the referee's verdicts (GMK_MATCH_*) read from device memory (K6's twin is trad_step_device_kernel).  A
+// game that MOVED follows the move: the child's subtree into the other arena (fresh == 0; a root that was never expanded has no such child
+// and gets a new node, MCTS.cpp:140-145) or a one-node root in its own arena (fresh != 0).  A game that ENDED takes the move behind a
+// one-node root and is finished (status bit 0: the searches skip it).  A game that was REFUSED or OVER, a game that finished earlier and a
+// MOVED game whose cell is not legal on its root position (status bit 2) keep position, status and tree -- copied over node by node when the
+// arenas flip, which they do for every game of the handle with fresh == 0.  One wavefront per game.
+// The subtree copy restates the tail of advance_one: that function is inlined into the persistent instantiations of mcts_playouts_kernel,
+// whose registers this kernel must not touch.
+__global__ __launch_bounds__(64)
+void mcts_step_device_kernel(GameHeader* __restrict__ headers, uint2* stats, uint32_t* link, uint32_t* parent, uint2* stats2, uint32_t* link2, uint32_t* parent2, size_t cap, int n_games,
+                             const int16_t* __restrict__ cells, const int32_t* __restrict__ verdict, int fresh) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g >= n_games) return;
+    GameHeader& hdr = headers[g];
+    const size_t base = static_cast<size_t>(g) * cap;
+    const uint32_t status = hdr.status, root = hdr.root, stones = hdr.stones;
+    const uint32_t n_nodes = static_cast<uint32_t>(min(static_cast<size_t>(hdr.n_nodes), cap));
+    const int v = verdict[g], cell = cells[g];
+    bool moved = !(status & 1u) && (v == GMK_MATCH_MOVED || v == GMK_MATCH_ENDED);
+    int child_i = 0;                                                // the cell's child: its rank among the root position's empty cells
+    if (moved) {
+        const bool on_board = cell >= 0 && cell < 225 && stones < 225u;
+        const int cy = on_board ? cell / 15 : 0, cx = on_board ? cell % 15 : 0;
+        bool legal = on_board;
+        for (int y = 0; y <= cy; ++y) {
+            const uint32_t r = hdr.rows[y], open = ~(r | (r >> 16)) & 0x7FFFu;
+            if (y < cy) child_i += __popc(open);
+            else { child_i += __popc(open & ((1u << cx) - 1u)); legal = legal && ((open >> cx) & 1u); }
+        }
+        if (!legal) {                                               // the referee judged the RECORD; the handle's own position must agree
+            moved = false;
+            if (lane == 0) hdr.status = status | 4u;
+        }
+    }
+    if (!moved) {
+        if (!fresh)
+            for (uint32_t i = lane; i < n_nodes; i += 64) { stats2[base + i] = stats[base + i]; link2[base + i] = link[base + i]; parent2[base + i] = parent[base + i]; }
+        return;
+    }
+    const uint32_t first = link[base + root] >> 8;
+    const bool keep = !fresh && first != 0u && v == GMK_MATCH_MOVED;
+    const uint32_t child = first + static_cast<uint32_t>(child_i);
+    __syncthreads();                                                // every lane has read the old header
+    if (lane == 0) {
+        hdr.rows[cell / 15] |= 1u << (cell % 15 + ((stones & 1u) ? 16 : 0));      // black moves on even stone counts
+        hdr.stones = stones + 1u;
+        hdr.last_move = static_cast<uint32_t>(cell);
+        hdr.playouts_done = 0;
+        hdr.noise = 0;
+        hdr.root = 0;
+        if (v == GMK_MATCH_ENDED) hdr.status = status | 1u;
+        if (!keep) {                                                // MCTS::reset + syncWithBoard: a fresh one-node tree
+            hdr.n_nodes = 1;
+            (fresh ? stats : stats2)[base] = make_uint2(0u, 0u);
+            (fresh ? link : link2)[base] = static_cast<uint32_t>(cell);
+            (fresh ? parent : parent2)[base] = kNone;
+        }
+    }
+    if (!keep) return;
+    // updateRoot (MCTS.cpp:63-67): the subtree of the move, level by level into the other arena so that node indices stay dense; a node's
+    // `link` there carries its OLD first-child index until the scan reaches it and copies its children (as in advance_one)
+    if (lane == 0) {
+        stats2[base] = stats[base + child];
+        link2[base] = link[base + child];
+        parent2[base] = kNone;
+    }
+    __syncthreads();
+    uint32_t next = 1, level_end = 1;
+    int depth = 0;
+    for (uint32_t i0 = 0; i0 < next;) {
+        if (i0 == level_end) { ++depth; level_end = next; }
+        const uint32_t chunk = min(64u, level_end - i0);
+        const uint32_t old_first = (static_cast<uint32_t>(lane) < chunk) ? (link2[base + i0 + lane] >> 8) : 0u;
+        unsigned long long todo = __ballot(old_first != 0u);
+        const uint32_t n = 225u - (stones + 1u + static_cast<uint32_t>(depth));
+        while (todo) {
+            const int j = __ffsll(static_cast<long long>(todo)) - 1;
+            todo &= todo - 1ull;
+            const uint32_t of = __shfl(old_first, j, 64), node = i0 + static_cast<uint32_t>(j);
+            for (uint32_t k = lane; k < n; k += 64) {
+                stats2[base + next + k] = stats[base + of + k];
+                link2[base + next + k] = link[base + of + k];
+                parent2[base + next + k] = node;
+            }
+            if (lane == 0) link2[base + node] = (next << 8) | (link2[base + node] & 0xFFu);
+            next += n;
+        }
+        __syncthreads();
+        i0 += chunk;
+    }
+    if (lane == 0) hdr.n_nodes = next;
+}
+
 }  // namespace
 
 extern "C" int gmk_mcts_create(int n_games, int node_capacity, double c_puct, int c_rollouts, uint64_t seed, gmk_mcts** out) {
@@ -1098,6 +1226,22 @@ static int mcts_sample_args(const char* who, int sample_plies, int sample_power)
     return GMK_OK;
 }
 
+// the second arena of the steps that keep subtrees (gmk_mcts_step, gmk_mcts_advance*, gmk_mcts_step_device), allocated by the first of them, all
+// or nothing: a later call must not find half an arena
+static int mcts_second_arena(gmk_mcts* m, const char* who) {
+    if (m->d_stats2) return GMK_OK;
+    const size_t nodes = static_cast<size_t>(m->n_games) * static_cast<size_t>(m->node_capacity);
+    if (gmk::device_malloc(&m->d_stats2, nodes * sizeof(uint2)) != hipSuccess || gmk::device_malloc(&m->d_link2, nodes * 4) != hipSuccess ||
+        gmk::device_malloc(&m->d_parent2, nodes * 4) != hipSuccess) {
+        (void)gmk::device_free(m->d_stats2); (void)gmk::device_free(m->d_link2); (void)gmk::device_free(m->d_parent2);
+        m->d_stats2 = nullptr; m->d_link2 = nullptr; m->d_parent2 = nullptr;
+        (void)hipGetLastError();
+        gmk::set_error("%s: hipMalloc of the second arena (%zu nodes) failed", who, nodes);
+        return GMK_ERR_HIP;
+    }
+    return GMK_OK;
+}
+
 // gmk_mcts_step / gmk_mcts_advance (sample_plies = 0) and gmk_mcts_advance_sampled (no forced moves; the draw is keyed by the handle's seed)
 static int mcts_step(const char* who, gmk_mcts* m, const int16_t* d_forced_moves, uint8_t* d_moves, uint16_t* d_visits, int32_t* d_lens, int8_t* d_winner,
                      int32_t* d_unfinished, int reuse_subtree, int sample_plies, int sample_power, void* stream) {
@@ -1105,17 +1249,8 @@ static int mcts_step(const char* who, gmk_mcts* m, const int16_t* d_forced_moves
     if (!m || !d_moves || !d_lens || !d_winner || !d_unfinished) { gmk::set_error("%s: bad arguments", who); return GMK_ERR_ARG; }
     hipStream_t s = static_cast<hipStream_t>(stream);
     m->last_stream = s;
-    if (reuse_subtree && !m->d_stats2) {
-        const size_t nodes = static_cast<size_t>(m->n_games) * static_cast<size_t>(m->node_capacity);
-        if (gmk::device_malloc(&m->d_stats2, nodes * sizeof(uint2)) != hipSuccess || gmk::device_malloc(&m->d_link2, nodes * 4) != hipSuccess ||
-            gmk::device_malloc(&m->d_parent2, nodes * 4) != hipSuccess) {
-            (void)gmk::device_free(m->d_stats2); (void)gmk::device_free(m->d_link2); (void)gmk::device_free(m->d_parent2);      // all or nothing: the guard above tests d_stats2
-            m->d_stats2 = nullptr; m->d_link2 = nullptr; m->d_parent2 = nullptr;
-            (void)hipGetLastError();
-            gmk::set_error("%s: hipMalloc of the second arena (%zu nodes) failed", who, nodes);
-            return GMK_ERR_HIP;
-        }
-    }
+    if (reuse_subtree)
+        if (const int rc = mcts_second_arena(m, who); rc != GMK_OK) return rc;
     if (sample_plies > 0)
         hipLaunchKernelGGL(mcts_advance_kernel<MctsSample>, dim3(m->n_games), dim3(64), 0, s, m->d_headers, m->d_stats, m->d_link, m->d_parent,
                            m->d_stats2, m->d_link2, m->d_parent2, static_cast<size_t>(m->node_capacity), m->n_games,
@@ -1272,6 +1407,41 @@ extern "C" int gmk_mcts_step_host(gmk_mcts* m, const int16_t* h_moves, int reuse
     const int rc = gmk_mcts_step(m, d_forced, d_moves, nullptr, d_lens, d_winner, d_unfinished, reuse_subtree, nullptr);
     if (rc != GMK_OK) return rc;
     GMK_HIP_CHECK(hipDeviceSynchronize());
+    return GMK_OK;
+}
+
+// the two calls a device-resident match makes of a K3 handle (K12): what they want of the handle before anything is launched
+static int mcts_match_state(const char* who, const gmk_mcts* m) {
+    if (!m->rooted) { gmk::set_error("%s: gmk_mcts_set_roots has not been called", who); return GMK_ERR_STATE; }
+    if (m->slots.slot_game) { gmk::set_error("%s: the handle plays through slots (gmk_selfplay_run)", who); return GMK_ERR_STATE; }
+    return GMK_OK;
+}
+
+extern "C" int gmk_mcts_root_choice(gmk_mcts* m, int16_t* d_cells, uint16_t* d_visits, void* stream) {
+    if (!m || !d_cells) { gmk::set_error("gmk_mcts_root_choice: bad arguments"); return GMK_ERR_ARG; }
+    if (const int rc = mcts_match_state("gmk_mcts_root_choice", m); rc != GMK_OK) return rc;
+    hipLaunchKernelGGL(mcts_root_choice_kernel, dim3(m->n_games), dim3(64), 0, static_cast<hipStream_t>(stream), m->d_headers, m->d_stats, m->d_link,
+                       static_cast<size_t>(m->node_capacity), m->arena_stride(), m->n_games, d_cells, d_visits);
+    GMK_HIP_CHECK(hipGetLastError());
+    return GMK_OK;
+}
+
+// gmk_mcts_step from device memory, on the caller's stream (mcts_step_device_kernel): nothing is copied and nothing is waited for
+extern "C" int gmk_mcts_step_device(gmk_mcts* m, const int16_t* d_cells, const int32_t* d_verdict, int fresh_root, void* stream) {
+    if (!m || !d_cells || !d_verdict) { gmk::set_error("gmk_mcts_step_device: bad arguments"); return GMK_ERR_ARG; }
+    if (const int rc = mcts_match_state("gmk_mcts_step_device", m); rc != GMK_OK) return rc;
+    if (!fresh_root)
+        if (const int rc = mcts_second_arena(m, "gmk_mcts_step_device"); rc != GMK_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    m->last_stream = s;
+    hipLaunchKernelGGL(mcts_step_device_kernel, dim3(m->n_games), dim3(64), 0, s, m->d_headers, m->d_stats, m->d_link, m->d_parent, m->d_stats2, m->d_link2, m->d_parent2,
+                       static_cast<size_t>(m->node_capacity), m->n_games, d_cells, d_verdict, fresh_root ? 1 : 0);
+    GMK_HIP_CHECK(hipGetLastError());
+    if (!fresh_root) {                                              // the copy is the live tree from here on
+        std::swap(m->d_stats, m->d_stats2);
+        std::swap(m->d_link, m->d_link2);
+        std::swap(m->d_parent, m->d_parent2);
+    }
     return GMK_OK;
 }
 

@@ -77,7 +77,7 @@ EXPORTS = [
     "gmk_pattern_policy", "gmk_pattern_policy_host", "gmk_pattern_play",
     "gmk_vcf_solve", "gmk_vcf_solve_host", "gmk_vcf_defend", "gmk_vcf_defend_host",
     "gmk_vcf_threats", "gmk_vcf_threats_host", "gmk_vct_solve", "gmk_vct_solve_host",
-    "gmk_match_referee",
+    "gmk_match_referee", "gmk_mcts_root_choice", "gmk_mcts_step_device",
     "gmk_mcts_ensemble_merge", "gmk_trad_ensemble_merge", "gmk_ensemble_merge_host",
     "gmk_replay_create", "gmk_replay_destroy", "gmk_replay_reset", "gmk_replay_append", "gmk_replay_append_packed", "gmk_replay_size",
     "gmk_replay_sample", "gmk_replay_draw_host", "gmk_replay_image_bytes", "gmk_replay_snapshot", "gmk_replay_restore", "gmk_replay_image_check_host",
@@ -140,6 +140,8 @@ def load():
     L.gmk_mcts_advance.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]
     L.gmk_mcts_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]
     L.gmk_mcts_step_host.argtypes = [vp, vp, C.c_int]
+    L.gmk_mcts_root_choice.argtypes = [vp, vp, vp, vp]
+    L.gmk_mcts_step_device.argtypes = [vp, vp, vp, C.c_int, vp]
     L.gmk_selfplay_run.argtypes = [vp, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_float, C.c_float, vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(C.c_int32), vp]
     L.gmk_mcts_advance_sampled.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     L.gmk_selfplay_run_sampled.argtypes = [vp, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(C.c_int32), vp]
@@ -456,6 +458,24 @@ class BatchedMCTS:
     def step(self, d_forced_moves, d_moves, d_visits, d_lens, d_winner, d_unfinished, reuse_subtree=False, stream=None):
         """MCTS::stepForward(move) per game: d_forced_moves int16[n] on the device, -1 = the most visited child."""
         _check(load().gmk_mcts_step(self.h, d_forced_moves, d_moves, d_visits, d_lens, d_winner, d_unfinished, int(reuse_subtree), stream))
+
+    def step_host(self, moves, reuse_subtree=False):
+        """gmk_mcts_step_host: step() with the moves from the host (int16[n], -1 = the most visited child), synchronous, without game records."""
+        m = np.ascontiguousarray(moves, dtype=np.int16)
+        assert m.shape == (self.n,)
+        _check(load().gmk_mcts_step_host(self.h, m.ctypes.data, int(bool(reuse_subtree))))
+
+    def root_choice(self, cells, visits=None, stream=None):
+        """gmk_mcts_root_choice: the most visited root child (first maximum in cell order; -1 without a visited one or in a finished game) into
+        cells (torch int16[n] on the GPU) and the root children's visit counts by cell, saturated at 65 535, into visits (2-byte torch
+        [n, 225], or None); nothing comes to the host."""
+        _root_choice(load().gmk_mcts_root_choice, self, cells, visits, stream)
+
+    def step_device(self, cells, verdict, fresh_root=False, stream=None):
+        """gmk_mcts_step_device: step() with the cells (torch int16[n]) and the referee's verdicts (torch int32[n], MATCH_*) on the GPU; the
+        subtree is kept unless fresh_root."""
+        _check_step_device(self, cells, verdict)
+        _check(load().gmk_mcts_step_device(self.h, cells.data_ptr(), verdict.data_ptr(), int(bool(fresh_root)), _current_stream(stream)))
 
     def add_root_noise(self, alpha=0.05, epsilon=0.25, stream=None):
         _check(load().gmk_mcts_add_root_noise(self.h, alpha, epsilon, stream))

@@ -366,9 +366,13 @@ class _HostGames:
     @classmethod
     def opened(cls, n_games, seed, first_game_id, opening_plies):
         """n_games boards after their openings (_opening), played ply by ply: an opening that ends its game stops there"""
-        games = cls(n_games)
-        moves, lens = _opening(n_games, seed, first_game_id, opening_plies)
-        for i in range(int(lens.max()) if n_games else 0):
+        return cls.from_opening(*_opening(n_games, seed, first_game_id, opening_plies))
+
+    @classmethod
+    def from_opening(cls, moves, lens):
+        """The boards after the openings (moves uint8[n, 225], lens int32[n]), played ply by ply: an opening that ends its game stops there"""
+        games = cls(len(lens))
+        for i in range(int(lens.max()) if len(lens) else 0):
             games.apply(np.where(lens > i, moves[:, i].astype(np.int64), -1))
         return games
 
@@ -585,6 +589,16 @@ def _symmetric(who, network, symmetry, seed):
     return network.symmetric(symmetry, seed)
 
 
+def _gumbel_goes_with(who, root_noise, leaves, proof, vcf_defend, sample_plies):
+    """ValueError for what the Gumbel root search (K21) of a loop `who` does not go with: root noise, leaves > 1, proofs, sampled plies."""
+    if root_noise is not None:
+        raise ValueError("%s: gumbel does not go with root noise -- pass root_noise=None, the Gumbel noise is the exploration" % who)
+    for name, bad in (("leaves > 1", leaves != 1), ("proof", proof), ("vcf_defend", vcf_defend), ("sample_plies > 0", int(sample_plies) > 0)):
+        if bad:
+            raise ValueError("%s: gumbel does not go with %s (the Gumbel root search takes one leaf per step, carries no proofs "
+                             "and chooses its moves itself)" % (who, name))
+
+
 def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SEED, first_game_id=0, opening_plies=0, max_moves=N,
                        device=None, node_capacity=None, reuse_subtree=True, root_noise=(0.05, 0.25), slots=None, device_loop=True, noise_sampler="counter", leaves=1,
                        vcf=None, proof=False, vcf_defend=False, sample_plies=0, sample_power=1, symmetry=None, gumbel=None):
@@ -616,17 +630,12 @@ def play_network_games(n_games, network, playouts, c_puct=5.0, seed=G.DEFAULT_SE
     records' rows are improved-policy rows, to be read with target="policy" (GameRecords.to_samples, ReplayBuffer).  The draws are keyed by seed,
     the game's global id and its stone count, so every loop plays the same games, rows included.  The Gumbel noise is the exploration:
     root_noise must be None, and leaves > 1, proof, vcf_defend and sample_plies > 0 do not go with it (ValueError).  Playing strength against
-    the plain search is not measured yet.  Returns GameRecords like play_games."""
+    the plain search: first figures in profiles/agent_match.json (play_agent_match).  Returns GameRecords like play_games."""
     if not (0 <= int(sample_plies) <= N and 1 <= int(sample_power) <= 3):
         raise ValueError("play_network_games: sample_plies takes 0 .. 225 and sample_power 1, 2 or 3")
     gumbel_args = None
     if gumbel is not None:
-        if root_noise is not None:
-            raise ValueError("play_network_games: gumbel does not go with root noise -- pass root_noise=None, the Gumbel noise is the exploration")
-        for name, bad in (("leaves > 1", leaves != 1), ("proof", proof), ("vcf_defend", vcf_defend), ("sample_plies > 0", int(sample_plies) > 0)):
-            if bad:
-                raise ValueError("play_network_games: gumbel does not go with %s (the Gumbel root search takes one leaf per step, carries no proofs "
-                                 "and chooses its moves itself)" % name)
+        _gumbel_goes_with("play_network_games", root_noise, leaves, proof, vcf_defend, sample_plies)
         m, c_visit, c_scale = gumbel
         gumbel_args = (int(m), int(playouts), float(c_visit), float(c_scale), seed, first_game_id)
     network = _symmetric("play_network_games", network, symmetry, seed)
@@ -942,6 +951,243 @@ def play_evaluation_games(n_games, network, opponent, playouts=400, c_puct=5.0, 
                 unfinished = int((~games.over[idx]).sum())
             overflow |= opp.overflow()
             groups.append({"games": idx, "unfinished": unfinished, "live_games": net.live})
+    if device_loop:
+        rec = GameRecords(d_moves, d_lens, d_winner, d_visits, first_game_id, overflow)
+        winner = d_winner.cpu().numpy()
+    else:
+        rec = _records_from_host(games, visits, dev, first_game_id, overflow)
+        winner = games.winner
+    rec.groups = groups
+    return rec, black, evaluation_scores(winner, black)
+
+
+_MATCH_AGENTS = _EVAL_OPPONENTS + ("network",)
+_NETWORK_AGENT_KEYS = ("network", "playouts", "c_puct", "leaves", "vcf", "proof", "vcf_defend", "symmetry", "gumbel", "sample_plies", "sample_power", "node_capacity")
+
+
+def _match_agent(spec, root_noise):
+    """An agent spec of play_agent_match, checked without the library: (kind, kwargs), kwargs a copy.  ValueError names what is wrong."""
+    who = "play_agent_match"
+    try:
+        kind, kw = spec
+        kw = dict(kw)
+    except (TypeError, ValueError):
+        raise ValueError("%s: an agent is (kind, kwargs), not %r" % (who, spec)) from None
+    if kind not in _MATCH_AGENTS:
+        raise ValueError("%s: unknown agent '%s' (%s)" % (who, kind, ", ".join(_MATCH_AGENTS)))
+    if kind == "random_mcts" and int(kw.get("c_iterations", 400)) < 2:
+        raise ValueError("%s: random_mcts needs c_iterations >= 2 (the first playout only expands the root: there is no child to play)" % who)
+    if kind != "network":
+        return kind, kw
+    unknown = sorted(set(kw) - set(_NETWORK_AGENT_KEYS))
+    if unknown:
+        raise ValueError("%s: a network agent takes %s, not %s" % (who, ", ".join(_NETWORK_AGENT_KEYS), ", ".join(unknown)))
+    if kw.get("network") is None:
+        raise ValueError("%s: a network agent needs its network (network.FusedPolicyValueNetwork)" % who)
+    if kw.get("symmetry") not in (None, "random", "all"):
+        raise ValueError("%s: symmetry is None, \"random\" or \"all\", not %r" % (who, kw["symmetry"]))
+    _sample_schedule(who, kw.get("sample_plies", 0), kw.get("sample_power", 1))
+    if kw.get("gumbel") is not None:
+        _gumbel_goes_with(who, root_noise, kw.get("leaves", 1), kw.get("proof", False), kw.get("vcf_defend", False), kw.get("sample_plies", 0))
+        if len(tuple(kw["gumbel"])) != 3:
+            raise ValueError("%s: gumbel = (max_considered, c_visit, c_scale)" % who)
+    return kind, kw
+
+
+class _MatchSide:
+    """One agent's side of one group of play_agent_match: its own handle over the group's games `idx`, rooted at their positions in `games`
+    (a _HostGames), and the calls both loops make of it whatever the handle is -- K7 with its network and options, K6 / K6 + RAVE / K8, or K3."""
+
+    def __init__(self, spec, idx, games, seed, first_game_id, reuse_subtree, dev):
+        self.kind, kw = spec
+        self.idx, self.seed, self.first = idx, seed, first_game_id
+        k = len(idx)
+        self.sample = self.network = None
+        self.gumbel = self.proof = False
+        if self.kind == "network":
+            self.playouts = int(kw.get("playouts", 400))
+            self.network = _symmetric("play_agent_match", kw["network"], kw.get("symmetry"), seed)
+            self.proof = bool(kw.get("proof", False))
+            plies = _sample_schedule("play_agent_match", kw.get("sample_plies", 0), kw.get("sample_power", 1))
+            self.sample = None if plies is None else plies + (seed, first_game_id)
+            gumbel_args = None
+            if kw.get("gumbel") is not None:
+                m, c_visit, c_scale = kw["gumbel"]
+                gumbel_args, self.gumbel = (int(m), self.playouts, float(c_visit), float(c_scale), seed, first_game_id), True
+            self.tree = G.AlphaZeroMCTS(k, node_capacity=_arena_nodes("network", self.playouts, reuse_subtree, kw.get("node_capacity")), c_puct=float(kw.get("c_puct", 5.0)),
+                                        leaves=int(kw.get("leaves", 1)), proof=self.proof, vcf_defend=bool(kw.get("vcf_defend", False)), gumbel=gumbel_args,
+                                        **_vcf_options(kw.get("vcf")))
+            self.full = G.AlphaZeroMCTS.STATUS_ARENA_FULL
+        else:
+            self.playouts = int(kw.get("c_iterations", 400))
+            k3 = self.kind == "random_mcts"
+            self.tree = _agent_tree(self.kind, kw, k, _arena_nodes("games" if k3 else "match", self.playouts, reuse_subtree), seed, first_game_id)
+            self.full = G.BatchedMCTS.STATUS_ARENA_FULL if k3 else G.TraditionalMCTS.STATUS_ARENA_FULL
+        try:
+            self.tree.set_option(G.OPT_NOISE_SAMPLER, G.NOISE_SAMPLERS["counter"])
+            self.set_position(games, first=True)
+            if self.gumbel or self.sample is not None:           # the host loop's root_choice lands here
+                self.d_cells, self.d_rows = torch.zeros(k, dtype=torch.int16, device=dev), torch.zeros((k, N), dtype=torch.int16, device=dev)
+        except BaseException:
+            self.tree.close()
+            raise
+
+    def set_position(self, games, first=False):
+        """Fresh roots at the games' positions; the games' numbers key every random stream of the handle (first: they are told once)."""
+        idx = self.idx
+        if self.kind == "network":
+            if first:
+                self.tree.set_game_ids(np.asarray(idx, dtype=np.uint32))
+            self.tree.set_roots(G.moves_to_planes(games.moves[idx], games.lens[idx]), games.last_two(idx))
+        elif self.kind == "random_mcts":                         # (gmk_mcts_set_roots numbers the games itself: their ids follow it every time)
+            self.tree.set_roots(G.moves_to_planes(games.moves[idx], games.lens[idx]), games.last_two(idx)[:, 0], self.first)
+            self.tree.set_game_ids(((self.first + np.asarray(idx, dtype=np.int64)) & 0xFFFFFFFF).astype(np.uint32))
+        else:
+            if first:
+                self.tree.set_game_ids(np.asarray(idx, dtype=np.uint32))
+            self.tree.set_positions(games.moves[idx], games.lens[idx])
+
+    def search(self, root_noise, stream):
+        """Default::AddNoise on the roots that have children, if asked for, then the agent's playouts"""
+        if self.kind == "network":
+            if root_noise is not None:
+                self.tree.add_root_noise(root_noise[0], root_noise[1], seed=self.seed, first_game_id=self.first)
+            self.tree.search(self.network, self.playouts)
+        elif self.kind == "random_mcts":
+            if root_noise is not None:
+                self.tree.add_root_noise(root_noise[0], root_noise[1], stream)
+            self.tree.run(self.playouts, stream)
+        else:
+            if root_noise is not None:
+                self.tree.add_root_noise(root_noise[0], root_noise[1], seed=self.seed, first_game_id=self.first, stream=stream)
+            self.tree.run(self.playouts, stream)
+
+    def choose_device(self, d_cells, d_rows):
+        """The move of every game and its record row into device memory: greedy, sampled or the Gumbel rule's, by the spec"""
+        if self.gumbel:
+            self.tree.root_choice(d_cells, d_rows, gumbel=True)
+        elif self.sample is not None:
+            self.tree.root_choice(d_cells, d_rows, sample=self.sample)
+        else:
+            self.tree.root_choice(d_cells, d_rows)
+
+    def status(self):
+        st = self.tree.root_stats()
+        return st[4] if self.kind == "random_mcts" else st["status"]
+
+    def overflow(self):
+        return _arena_full(self.status(), self.full)
+
+    def choose_host(self, stones):
+        """(cells int[k], -1: none; rows [k, 225]; whether an arena filled) of the same choice through the host; stones int[k] on the root boards"""
+        st = self.tree.root_stats()
+        if self.kind == "random_mcts":
+            return _root_choice(st[0]), st[0], _arena_full(st[4], self.full)
+        full = _arena_full(st["status"], self.full)
+        if self.kind != "network":
+            return st["best"], st["visits"], full
+        if self.gumbel:
+            self.tree.root_choice(self.d_cells, self.d_rows, gumbel=True)
+            return self.d_cells.cpu().numpy().astype(np.int64), self.d_rows.cpu().numpy().view(np.uint16), full
+        proofs = self.tree.root_proofs()["children"] if self.proof else None
+        if self.sample is None:
+            return _root_choice(st["visits"], proofs), st["visits"], full
+        choice = _sampled_choice(st["visits"], proofs, stones, self.idx, self.sample)
+        return np.where(st["visits"].max(1) > 0, choice, -1), st["visits"], full
+
+    def step_host(self, step):
+        """Both trees follow the move with their subtrees kept: step int16[k], the cell that went in"""
+        if self.kind == "random_mcts":
+            self.tree.step_host(step, reuse_subtree=True)
+        else:
+            self.tree.step(step)
+
+    @property
+    def live(self):
+        return self.tree.live if self.kind == "network" else None
+
+    def close(self):
+        self.tree.close()
+
+
+def play_agent_match(n_games, first, second, seed=G.DEFAULT_SEED, first_game_id=0, opening_plies=4, paired=True, max_moves=N, reuse_subtree=True,
+                     root_noise=None, device_loop=True, device=None):
+    """A match between any two agents the project has: n_games games of `first` against `second`, each an agent spec (kind, kwargs).
+    kind "traditional_mcts" (K6; {"use_rave": True}: K6 + RAVE), "rave_mcts" (K8) and "random_mcts" (K3) as in DATA_CONFIG["schedule"] -- kwargs c_puct,
+    c_bias, c_rollouts, and c_iterations, the playout budget -- or "network": K7 with kwargs network (a network.FusedPolicyValueNetwork, required),
+    playouts, c_puct, leaves, vcf = (depth, budget), proof, vcf_defend, symmetry (None, "random", "all"), gumbel = (max_considered, c_visit, c_scale)
+    with n_sims = playouts, sample_plies, sample_power and node_capacity, each as play_network_games reads it.  Each side has its own handle with its own
+    options and its own network, so K7 plays K7 with any two sets of them.  gumbel does not go with leaves > 1, proof, vcf_defend or sample_plies > 0 on
+    its side, nor with root_noise (ValueError, checked before the library is touched).
+    `first` has black in even games (evaluation_sides).  paired (n_games even): the games 2p and 2p + 1 start from the same opening -- the first
+    opening_plies plies (at most 8) of synthetic game first_game_id + 2p -- with the colours exchanged, so an opening's bias cancels within the
+    pair (rating.summary(paired=True) reads the scores that way); paired=False: every game has its own opening, as in play_evaluation_games.
+    Every random stream (root noise, sampled plies, Gumbel draws, K3 and K8 rollouts) is keyed by the game's global id first_game_id + g.
+    The games in which `first` has black and the others form two groups, each with one handle per side; every ply of a group is the mover's root
+    noise (root_noise = (alpha, epsilon); None, the default: a strength match explores nothing -- variety comes from the openings and sample_plies),
+    its search, its root choice, the referee (K12) and the step of both handles -- the subtree kept (reuse_subtree) or a fresh root.
+    device_loop: all of that is kernels on the current stream and the host reads the unfinished count once per ply and group; False: the same
+    match through the host (root_stats down, numpy boards, moves up), kept for the tests: both play the same games byte for byte.
+    Returns (GameRecords, first_is_black bool[n], scores float[n]: 1 / 0.5 / 0 for `first`); the records' visit rows are the mover's,
+    records.groups lists per group the games, the unfinished count and "live_games": per side the K7 handle's live games (None for another
+    handle), and records.overflow says whether an arena of any of the four handles filled up."""
+    first, second = _match_agent(first, root_noise), _match_agent(second, root_noise)
+    if paired and n_games % 2:
+        raise ValueError("play_agent_match: a paired match has an even number of games")
+    if not 0 <= opening_plies <= 8:
+        raise ValueError("play_agent_match: openings of at most 8 plies (an opening cannot be a finished game)")
+    dev, stream = _device(device)
+    black = evaluation_sides(n_games)
+    open_moves, open_lens = _opening(n_games, seed, first_game_id, opening_plies)
+    if paired:
+        open_moves[1::2], open_lens[1::2] = open_moves[0::2], open_lens[0::2]
+    games = _HostGames.from_opening(open_moves, open_lens)
+    start = int(games.lens[0]) if n_games else 0
+    assert (games.lens == start).all() and not games.over.any()
+    if device_loop:
+        d_moves, d_lens, d_winner, d_visits = _record_tensors(n_games, dev, (games.moves, games.lens))
+    else:
+        visits = np.zeros((n_games, N, N), dtype=np.uint16)
+    overflow, groups = False, []
+    for gi, idx in enumerate((np.nonzero(black)[0], np.nonzero(~black)[0])):
+        k = len(idx)
+        if k == 0:
+            groups.append({"games": idx, "unfinished": 0, "live_games": (None, None)})
+            continue
+        with contextlib.ExitStack() as handles, torch.no_grad():
+            sides = [handles.enter_context(contextlib.closing(_MatchSide(spec, idx, games, seed, first_game_id, reuse_subtree, dev))) for spec in (first, second)]
+            unfinished = k
+            if device_loop:
+                d_idx = torch.from_numpy(idx.astype(np.int32)).to(dev)
+                d_cells, d_rows = torch.full((k,), -1, dtype=torch.int16, device=dev), torch.zeros((k, N), dtype=torch.int16, device=dev)
+                d_verdict, d_status, d_unfinished = torch.zeros(k, dtype=torch.int32, device=dev), torch.zeros(k, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+            for ply in range(max_moves):
+                if not device_loop and games.over[idx].all():
+                    break
+                mover = sides[0 if ((start + ply) % 2 == 0) == (gi == 0) else 1]      # group 0: `first` has black, i.e. it moves on even stone counts
+                if not device_loop and ply > 0 and not reuse_subtree:                   # (on the device loop step_device leaves the fresh roots)
+                    mover.set_position(games)
+                mover.search(root_noise, stream)
+                if device_loop:
+                    mover.choose_device(d_cells, d_rows)
+                    G.match_referee(d_cells, d_rows, d_idx, d_moves, d_lens, d_winner, d_visits, d_verdict, d_status, d_unfinished)
+                    for side in sides:
+                        side.tree.step_device(d_cells, d_verdict, fresh_root=not reuse_subtree)
+                    unfinished = int(d_unfinished.item())             # four bytes per ply and group: the only host sync of the loop
+                    if unfinished == 0:
+                        break
+                else:
+                    best, rows, full = mover.choose_host(games.lens[idx])
+                    overflow |= full
+                    step = games.play(idx, best, rows, visits, stall_ends_game=False)      # a mover without a child leaves its game where it stands
+                    if reuse_subtree:
+                        for side in sides:
+                            side.step_host(step)
+            if device_loop:
+                overflow |= any([side.overflow() for side in sides])
+            else:
+                unfinished = int((~games.over[idx]).sum())
+            groups.append({"games": idx, "unfinished": unfinished, "live_games": tuple(side.live for side in sides)})
     if device_loop:
         rec = GameRecords(d_moves, d_lens, d_winner, d_visits, first_game_id, overflow)
         winner = d_winner.cpu().numpy()

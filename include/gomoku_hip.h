@@ -206,6 +206,20 @@ int gmk_mcts_step(gmk_mcts* m, const int16_t* d_forced_moves, uint8_t* d_moves, 
                   int8_t* d_winner, int32_t* d_unfinished, int reuse_subtree, void* stream);
 /* the same from host memory, synchronous, without game records: h_moves int16[n] */
 int gmk_mcts_step_host(gmk_mcts* m, const int16_t* h_moves, int reuse_subtree);
+/* The two calls a device-resident match makes of a K3 handle (K12, see gmk_match_referee below).
+ * gmk_mcts_root_choice: the cell gmk_mcts_step would play with a forced move of -1 -- the most visited root child, first maximum in its
+ * order, -1 for a root without a visited child or a finished game -- as d_cells int16[n], and the root children's visit counts by cell
+ * saturated at 65 535 as d_visits uint16[n][225] (may be NULL; a finished game's row is zero), both in device memory, on `stream`; nothing
+ * is copied to the host.  It reads the arena the game's tree is in now (after a step that kept subtrees: the other one).
+ * gmk_mcts_step_device: gmk_mcts_step with the cells read from d_cells and the launch on `stream`, steered by the referee's verdicts
+ * d_verdict int32[n] (GMK_MATCH_*): a game that MOVED follows the move, one that ENDED takes the move and is finished (status bit 0: later
+ * gmk_mcts_run calls skip it), one that was REFUSED or OVER keeps its tree, its position and its status whatever d_cells holds (-1 is
+ * "nothing" here, not "the most visited child").  An illegal cell under MOVED sets status bit 2 and plays nothing.  fresh_root = 0 keeps
+ * the subtree as gmk_mcts_step with reuse_subtree does (a move without a child starts a new node); fresh_root != 0 leaves a moved game a
+ * one-node root at the position after the move.
+ * Both return GMK_ERR_STATE for a handle without roots or one that plays through slots (gmk_selfplay_run). */
+int gmk_mcts_root_choice(gmk_mcts* m, int16_t* d_cells, uint16_t* d_visits, void* stream);
+int gmk_mcts_step_device(gmk_mcts* m, const int16_t* d_cells, const int32_t* d_verdict, int fresh_root, void* stream);
 /* Root noise parameters -- the ONE rule for every entry that takes Default::AddNoise's alpha and epsilon:
  *   gmk_mcts_add_root_noise, gmk_trad_add_root_noise, gmk_az_add_root_noise, gmk_noise_mix_rows:
  *     alpha is finite and > 0, and 0 <= epsilon <= 1 (tested as comparisons, so a NaN is refused).
