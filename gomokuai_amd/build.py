@@ -25,7 +25,7 @@ def _stale(target, sources):
     t = os.path.getmtime(target)
     deps = list(sources) + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     include = os.path.join(os.path.dirname(HERE), "include")
-    deps += [os.path.join(include, f) for f in ("gomoku_hip.h", "gomoku_noise.h", "gomoku_sample.h", "gomoku_symmetry.h", "gomoku_gumbel.h")]
+    deps += [os.path.join(include, f) for f in ("gomoku_hip.h", "gomoku_noise.h", "gomoku_sample.h", "gomoku_symmetry.h", "gomoku_gumbel.h", "gomoku_pattern_states.h")]
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 

@@ -14,6 +14,7 @@
 #include <atomic>
 #include <mutex>
 
+#include "../../include/gomoku_pattern_states.h"
 #include "evalstate_device.h"
 #include "heuristic_device.h"
 #include "host_staging.h"
@@ -194,6 +195,126 @@ void pattern_kernel(PatternParams prm) {
     }
 }
 
+// K23: the same verdict for a row of network planes, float32 [6][225] (Board.encoded_states, K7's leaf batch).  The row's canonical move list
+// (include/gomoku_pattern_states.h) is never written anywhere: four ballots per plane give the stone sets as scalar masks, the header's check
+// and walk run on them, and every cell the walk hands out goes to the update the list form feeds.  Its own loop around evaluate() and
+// evaluator_step(), so that the two instantiations above stay the code they were.
+struct StatesParams {
+    const float* states;                         // [n][6][225]
+    int n, filter, norm;
+    float* value;                                // [n]
+    float* probs;                                // [n][225]
+    int32_t* status;                             // [n] or nullptr
+    uint32_t* counter;
+    const uint32_t* g_trans;
+    const uint32_t* g_records;
+    int trans_words, record_words;
+};
+
+__global__ __launch_bounds__(kThreads)
+void pattern_states_kernel(StatesParams prm) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    for (int i = threadIdx.x; i < prm.trans_words + prm.record_words; i += kThreads)
+        lds[i] = i < prm.trans_words ? prm.g_trans[i] : prm.g_records[i - prm.trans_words];
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint32_t* base = lds + prm.trans_words + prm.record_words + wave * kPerWave;
+    const Ctx c{base, base + kStateWords, reinterpret_cast<const char*>(lds), reinterpret_cast<const uint4*>(lds + prm.trans_words),
+                reinterpret_cast<const char*>(lds + prm.trans_words + prm.record_words - gmk::kPrefixWords), lane};
+    int32_t* meta = reinterpret_cast<int32_t*>(c.st + oMeta);
+
+    for (;;) {
+        uint32_t taken = 0;
+        if (lane == 0) taken = atomicAdd(prm.counter, 1u);
+        taken = __builtin_amdgcn_readfirstlane(taken);
+        if (taken >= static_cast<uint32_t>(prm.n)) break;
+        const size_t item = taken;
+        const float* s = prm.states + item * static_cast<size_t>(GMK_PATTERN_PLANES * kCells);
+        // front: lane l holds the cells l + 64 j of planes 0, 1, 3 and 4; one ballot per plane and j
+        gmk_pattern_masks m;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int q = lane + 64 * j;
+            const bool in = q < kCells;
+            const float f0 = in ? s[q] : 0.0f, f1 = in ? s[kCells + q] : 0.0f, f3 = in ? s[3 * kCells + q] : 0.0f, f4 = in ? s[4 * kCells + q] : 0.0f;
+            m.own[j] = __ballot(gmk_pattern_is_set(f0));
+            m.opp[j] = __ballot(gmk_pattern_is_set(f1));
+            m.last[j] = __ballot(gmk_pattern_is_set(f3));
+            m.last2[j] = __ballot(gmk_pattern_is_set(f4));
+        }
+        m.black_to_move = __builtin_amdgcn_readfirstlane(static_cast<int>(gmk_pattern_is_set(s[5 * kCells])));
+        uint32_t status = static_cast<uint32_t>(gmk_pattern_check(&m));
+        Verdict now;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) now.probs.v[j] = 0.0f;
+        now.value = 0.0f;
+        now.best = -1;
+        reset_state(c);
+        if (status == 0u) {
+            gmk_pattern_walk w;
+            gmk_pattern_walk_begin(&m, &w);
+            int ply = 0;
+            for (;;) {
+                int mv;
+                if (ply < w.plies) {
+                    mv = gmk_pattern_walk_next(&w, ply);
+                    // as the list form: a move after the end is not a position (the cell is empty and below 225 by construction)
+                    if (meta[1] == 0 || ((c.st[oLines + mv / 15] >> (2 * (mv % 15))) & 3u) != 3u) { status |= kIllegal; break; }
+                } else {
+                    bool ended = meta[1] == 0;                  // Evaluator::checkGameEnd (Pattern.cpp:344-354)
+                    if (!ended && meta[0] == kCells) {
+                        if (lane == 0) { meta[1] = 0; meta[2] = 0; }
+                        wave_phase_fence();
+                        ended = true;
+                    }
+                    if (ended) status |= kOver; else now = evaluate(c, prm.filter);
+                    break;
+                }
+                evaluator_step(c, mv);                          // the one place where moves are applied
+                wave_phase_fence();
+                ++ply;
+            }
+            if (meta[3] != 0) status |= kEvaluatorError;
+        }
+        // back: the prior, the value and the status of the row
+        const bool live = !(status & (kOver | kIllegal));
+        Cells out;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) out.v[j] = live ? now.probs.v[j] : 0.0f;
+        if (live && prm.norm == GMK_PATTERN_NORM_SUM) {
+            double p = static_cast<double>(out.v[0]);           // gmk_gumbel_sum225, as gumbel_row adds it up (az_kernel.hip)
+#pragma unroll
+            for (int j = 1; j < 4; ++j) if (lane + 64 * j < kCells) p += static_cast<double>(out.v[j]);
+#pragma unroll
+            for (int off = 8; off >= 1; off >>= 1) {
+                const double other = __shfl_down(p, off, 16);
+                p = p + (((lane & 15) + off < 16) ? other : 0.0);
+            }
+            const double sum = (__shfl(p, 0) + __shfl(p, 16)) + (__shfl(p, 32) + __shfl(p, 48));
+            if (sum == 0.0) {
+                // the uniform fallback; every stone of the row is on the evaluator's board by now, so the empty cells are read there
+                const int empty = kCells - meta[0];
+                const float u = (status == 0u && empty > 0) ? static_cast<float>(1.0 / static_cast<double>(empty)) : 0.0f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int q = min(lane + 64 * j, kCells - 1);
+                    out.v[j] = ((c.st[oLines + q / 15] >> (2 * (q % 15))) & 3u) == 3u ? u : 0.0f;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) out.v[j] = static_cast<float>(static_cast<double>(out.v[j]) / sum);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (lane + 64 * j < kCells) prm.probs[item * kCells + lane + 64 * j] = out.v[j];
+        if (lane == 0) {
+            prm.value[item] = live ? now.value : 0.0f;
+            if (prm.status) prm.status[item] = static_cast<int32_t>(status);
+        }
+        wave_phase_fence();
+    }
+}
+
 // The work counters: every launch takes the next word of a small ring and clears it on its stream, so launches on different streams (and
 // launches queued behind each other) never share one.  256 launches would have to be in flight at once for two of them to meet.
 constexpr unsigned kCounterRing = 256;
@@ -290,4 +411,83 @@ extern "C" int gmk_pattern_play(uint8_t* d_moves, int32_t* d_lens, int n, int fi
     prm.stride = kCells; prm.n = n; prm.filter = filter != 0; prm.max_moves = max_moves;
     prm.winner = d_winner; prm.values = d_values; prm.status = d_status;
     return launch<true>(prm, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int gmk_pattern_evaluate_states(const float* d_states, int n, int filter, int norm,
+                                           float* d_value, float* d_probs, int32_t* d_status, void* stream) {
+    if (n < 0 || (n > 0 && (!d_states || !d_value || !d_probs)) || (filter != 0 && filter != 1) ||
+        (norm != GMK_PATTERN_NORM_L2 && norm != GMK_PATTERN_NORM_SUM) || misaligned(d_states, 4) || misaligned(d_value, 4) || misaligned(d_probs, 4) ||
+        misaligned(d_status, 4)) {
+        gmk::set_error("gmk_pattern_evaluate_states: bad arguments (n >= 0; d_states, d_value and d_probs set and 4-byte aligned; filter 0 or 1; "
+                       "norm GMK_PATTERN_NORM_L2 or GMK_PATTERN_NORM_SUM)");
+        return GMK_ERR_ARG;
+    }
+    GMK_NEED_INIT();
+    if (n == 0) return GMK_OK;
+    const gmk::DeviceState& st = gmk::device_state();
+    StatesParams prm{};
+    prm.states = d_states; prm.n = n; prm.filter = filter; prm.norm = norm;
+    prm.value = d_value; prm.probs = d_probs; prm.status = d_status;
+    prm.g_trans = st.d_trans;
+    prm.g_records = st.d_records;
+    prm.trans_words = st.n_states * 4;
+    prm.record_words = st.n_records * 4 + gmk::kPrefixWords;
+    const size_t lds = static_cast<size_t>(kWaves * kPerWave + prm.trans_words + prm.record_words) * 4;
+    if (lds > 160 * 1024) { gmk::set_error("K23: the pattern tables do not fit beside %d evaluator states in LDS", kWaves); return GMK_ERR_CAPACITY; }
+    static bool attr_set = false;
+    if (!attr_set) {
+        GMK_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pattern_states_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_set = true;
+    }
+    const hipStream_t hs = static_cast<hipStream_t>(stream);
+    const int rc = next_counter(hs, &prm.counter);
+    if (rc != GMK_OK) return rc;
+    const int grid = std::max(1, std::min((n + kWaves - 1) / kWaves, st.cu_count > 0 ? st.cu_count : 1));
+    hipLaunchKernelGGL(pattern_states_kernel, dim3(grid), dim3(kThreads), lds, hs, prm);
+    GMK_HIP_CHECK(hipGetLastError());
+    return GMK_OK;
+}
+
+extern "C" int gmk_pattern_evaluate_states_host(const float* h_states, int n, int filter, int norm,
+                                                float* h_value, float* h_probs, int32_t* h_status) {
+    if (n < 0 || (n > 0 && (!h_states || !h_value || !h_probs)) || (filter != 0 && filter != 1) ||
+        (norm != GMK_PATTERN_NORM_L2 && norm != GMK_PATTERN_NORM_SUM)) {
+        gmk::set_error("gmk_pattern_evaluate_states_host: bad arguments");
+        return GMK_ERR_ARG;
+    }
+    GMK_NEED_INIT();
+    if (n == 0) return GMK_OK;
+    const size_t un = static_cast<size_t>(n);
+    gmk::Staging st("gmk_pattern_evaluate_states_host", gmk::kPoolKeeps);
+    float *d_states, *d_value, *d_probs;
+    int32_t* d_status;
+    st.in(d_states, h_states, un * GMK_PATTERN_PLANES * kCells);
+    st.out(d_probs, h_probs, un * kCells); st.out(d_value, h_value, un); st.out(d_status, h_status, un);
+    int rc = st.take();
+    if (rc == GMK_OK) rc = gmk_pattern_evaluate_states(d_states, n, filter, norm, d_value, d_probs, h_status ? d_status : nullptr, nullptr);
+    if (rc != GMK_OK) return rc;
+    GMK_STAGED(st, hipDeviceSynchronize());
+    return st.download();
+}
+
+// the decode and the canonical list of include/gomoku_pattern_states.h, on the host: no GPU, no gmk_init
+extern "C" int gmk_pattern_states_list_host(const float* h_states, int n, uint8_t* h_moves, int32_t* h_lens, int32_t* h_status) {
+    if (n < 0 || (n > 0 && (!h_states || !h_moves || !h_lens || !h_status))) { gmk::set_error("gmk_pattern_states_list_host: bad arguments"); return GMK_ERR_ARG; }
+    for (int i = 0; i < n; ++i)
+        h_status[i] = gmk_pattern_list225(h_states + static_cast<size_t>(i) * GMK_PATTERN_PLANES * kCells, h_moves + static_cast<size_t>(i) * kCells, h_lens + i);
+    return GMK_OK;
+}
+
+// the normalisation and the uniform fallback of the same header, on the host; it knows no evaluator status: a row that decodes counts as live
+extern "C" int gmk_pattern_states_finish_host(const float* h_vec, const float* h_states, int n, int norm, float* h_probs) {
+    if (n < 0 || (n > 0 && (!h_vec || !h_states || !h_probs)) || (norm != GMK_PATTERN_NORM_L2 && norm != GMK_PATTERN_NORM_SUM)) {
+        gmk::set_error("gmk_pattern_states_finish_host: bad arguments");
+        return GMK_ERR_ARG;
+    }
+    for (int i = 0; i < n; ++i) {
+        gmk_pattern_masks m;
+        gmk_pattern_masks_of(h_states + static_cast<size_t>(i) * GMK_PATTERN_PLANES * kCells, &m);
+        gmk_pattern_finish225(h_vec + static_cast<size_t>(i) * kCells, norm, gmk_pattern_check(&m) == 0, m.own, m.opp, h_probs + static_cast<size_t>(i) * kCells);
+    }
+    return GMK_OK;
 }

@@ -11,6 +11,7 @@ is host-side interop only.
     python -m gomokuai_amd.interface botzone   --agent traditional:5 --vcf 16 --vcf-defend --ms 960 < request.json
     python -m gomokuai_amd.interface botzone   --agent traditional:5 --vcf 16 --vct 2 --ms 960        < request.json
     python -m gomokuai_amd.interface botzone   --agent network:run.pt --leaves 8 --symmetry all --ms 960 < request.json
+    python -m gomokuai_amd.interface botzone   --agent pattern-az:5 --leaves 8 --ms 960               < request.json
 """
 import datetime
 import json
@@ -416,7 +417,9 @@ class VCFAgent(Agent):
 def make_agent(spec, milliseconds=960, iterations=None, quiet=False, replicas=1, seed=None, vcf=0, vcf_defend=False, vct=0, leaves=8, symmetry="all"):
     """'random', 'human', 'pattern', 'random-mcts[:c_puct[:c_rollouts]]', 'traditional[:c_puct]', 'poolrave[:c_puct[:c_bias]]',
     'network:PATH[:c_puct]' (NetworkAgent on the weights network.load_weights reads from PATH, with `leaves` leaves per step and the
-    leaves evaluated under `symmetry`: "all", "random" or "none"; `replicas` does not apply to it).
+    leaves evaluated under `symmetry`: "all", "random" or "none"; `replicas` does not apply to it),
+    'pattern-az[:c_puct]' (the same search with no network: NetworkAgent over network.PatternEvaluator(), the pattern heuristic as K7's prior
+    and value (K23), with `leaves` leaves per step; `symmetry` and `replicas` do not apply to it).
     replicas > 1 turns the three MCTS kinds into an EnsembleAgent of that many trees per position ('traditional' with the reference's root
     noise, alpha 0.05 / epsilon 0.25: its search has no other source of difference); replicas = 1 builds the agents as ever.
     vcf = D > 0 puts the forced-win solver in front of the agent (VCFAgent, depth D); 'human' and 'random' stay as they are.
@@ -445,6 +448,14 @@ def make_agent(spec, milliseconds=960, iterations=None, quiet=False, replicas=1,
         module = load_weights(args[0]).cuda().eval()
         return NetworkAgent(FusedPolicyValueNetwork(module), milliseconds=None if iterations is not None else milliseconds, iterations=iterations,
                             leaves=leaves, symmetry=symmetry, c_puct=float(args[1]) if len(args) > 1 else 5.0, quiet=quiet)
+    if kind == "pattern-az":
+        if not 1 <= int(leaves) <= G.AZ_MAX_LEAVES:
+            raise ValueError("leaves must be in 1 .. %d" % G.AZ_MAX_LEAVES)
+        if len(args) > 1:
+            raise ValueError("the pattern search agent is 'pattern-az[:c_puct]'")
+        from .network import PatternEvaluator
+        return NetworkAgent(PatternEvaluator(), milliseconds=None if iterations is not None else milliseconds, iterations=iterations,
+                            leaves=leaves, symmetry=None, c_puct=float(args[0]) if args and args[0] else 5.0, quiet=quiet)
     num = [float(a) for a in args]
     if kind == "random":
         return RandomAgent()
@@ -582,7 +593,9 @@ def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("mode", choices=["botzone", "keepalive", "console"])
-    ap.add_argument("--agent", default="traditional:5")
+    ap.add_argument("--agent", default="traditional:5",
+                    help="random, human, pattern, random-mcts[:c_puct[:c_rollouts]], traditional[:c_puct], poolrave[:c_puct[:c_bias]], "
+                         "network:PATH[:c_puct], pattern-az[:c_puct] (the network agent's search over the pattern heuristic; honours --leaves)")
     ap.add_argument("--agent2", default="traditional:7", help="console mode: the second agent")
     ap.add_argument("--ms", type=int, default=960, help="search time per move (the reference's default constraint)")
     ap.add_argument("--iterations", type=int, default=None, help="playouts per move instead of a time budget")
@@ -591,7 +604,7 @@ def main(argv=None):
     ap.add_argument("--vcf", type=int, default=0, metavar="DEPTH", help="put the exact forced-win solver (continuous fours, up to DEPTH own moves) in front of the agents; 0: off")
     ap.add_argument("--vcf-defend", action="store_true", help="with --vcf: also refuse moves that lose to the opponent's forced win by fours, as far as any cell holds")
     ap.add_argument("--vct", type=int, default=0, metavar="T", help="with --vcf: also play a forced win by at most T moves that threaten a win by fours (fours and threes); 0: off.  This search runs after the agent's own and is not bounded by --ms")
-    ap.add_argument("--leaves", type=int, default=8, metavar="L", help="the network agent: leaves per search step (1 .. 8)")
+    ap.add_argument("--leaves", type=int, default=8, metavar="L", help="the network and pattern-az agents: leaves per search step (1 .. 8)")
     ap.add_argument("--symmetry", choices=["all", "random", "none"], default="all", help="the network agent: evaluate every leaf averaged over the board's eight orientations, in one orientation picked per position, or as it stands")
     args = ap.parse_args(argv)
     if args.vcf_defend and args.vcf <= 0:

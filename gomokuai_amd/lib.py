@@ -75,6 +75,7 @@ EXPORTS = [
     "gmk_pvnet_set_precision", "gmk_pvnet_get_precision", "gmk_bf16_round_host",
     "gmk_pvnet_evaluate_sym", "gmk_pvnet_sym_pick_host",
     "gmk_pattern_policy", "gmk_pattern_policy_host", "gmk_pattern_play",
+    "gmk_pattern_evaluate_states", "gmk_pattern_evaluate_states_host", "gmk_pattern_states_list_host", "gmk_pattern_states_finish_host",
     "gmk_vcf_solve", "gmk_vcf_solve_host", "gmk_vcf_defend", "gmk_vcf_defend_host",
     "gmk_vcf_threats", "gmk_vcf_threats_host", "gmk_vct_solve", "gmk_vct_solve_host",
     "gmk_match_referee", "gmk_mcts_root_choice", "gmk_mcts_step_device",
@@ -237,6 +238,10 @@ def load():
     L.gmk_pattern_policy.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.gmk_pattern_policy_host.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.gmk_pattern_play.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.gmk_pattern_evaluate_states.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.gmk_pattern_evaluate_states_host.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.gmk_pattern_states_list_host.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.gmk_pattern_states_finish_host.argtypes = [vp, vp, C.c_int, C.c_int, vp]
     L.gmk_vcf_solve.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp]
     L.gmk_vcf_solve_host.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp, vp]
     L.gmk_vcf_defend.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -889,6 +894,93 @@ def pattern_policy_device(d_moves, stride, d_lens, n, filter=True, d_probs=None,
 def pattern_play(d_moves, d_lens, n, filter=True, max_moves=0, d_winner=None, d_values=None, d_status=None, stream=None):
     """gmk_pattern_play: the n openings in d_moves u8[n,225] / d_lens i32[n] (device pointers) are played out greedily in one launch."""
     _check(load().gmk_pattern_play(d_moves, d_lens, int(n), int(bool(filter)), int(max_moves), d_winner, d_values, d_status, stream))
+
+
+# ---------------- K23: the pattern heuristic for rows of network planes (include/gomoku_pattern_states.h) ----------------
+PATTERN_NORM_L2, PATTERN_NORM_SUM = 0, 1                     # GMK_PATTERN_NORM_*
+PATTERN_NORMS = {"l2": PATTERN_NORM_L2, "sum": PATTERN_NORM_SUM}
+
+
+def _pattern_norm(norm):
+    if norm in PATTERN_NORMS:
+        return PATTERN_NORMS[norm]
+    if norm in (PATTERN_NORM_L2, PATTERN_NORM_SUM) and not isinstance(norm, bool):
+        return int(norm)
+    raise ValueError("norm is 'l2' or 'sum', not %r" % (norm,))
+
+
+def _state_rows(states):
+    """Host rows of planes: anything of n x 6 x 225 float32 values -> (contiguous f32[n, 6, 225], n)."""
+    states = np.ascontiguousarray(states, dtype=np.float32)
+    if states.size % (6 * N) or (states.ndim < 2 and states.size):
+        raise ValueError("states hold n x 6 x 225 values")
+    states = states.reshape(-1, 6, N)
+    return states, states.shape[0]
+
+
+def pattern_evaluate_states(states, filter=True, norm="sum", value=None, probs=None, status=None, stream=None):
+    """gmk_pattern_evaluate_states on torch tensors on the GPU: states f32 [n, 6, 15, 15] (or [n, 6, 225]), contiguous -> (value f32[n],
+    probs f32[n, 225], status i32[n]).  Outputs that are passed in are written in place (status=False: no status is asked for and None is
+    returned for it).  Asynchronous on `stream` (an int handle; None: torch's current stream); nothing is synchronised."""
+    import torch
+    norm = _pattern_norm(norm)
+    if not (isinstance(states, torch.Tensor) and states.is_cuda and states.dtype == torch.float32 and states.is_contiguous()):
+        raise ValueError("states is a contiguous float32 tensor on the GPU")
+    if states.numel() % (6 * N) or (states.dim() < 2 and states.numel()):
+        raise ValueError("states hold n x 6 x 225 values")
+    n = states.numel() // (6 * N)
+    init()
+    dev = states.device
+    if value is None:
+        value = torch.empty(n, dtype=torch.float32, device=dev)
+    if probs is None:
+        probs = torch.empty((n, N), dtype=torch.float32, device=dev)
+    if status is None:
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+    elif status is False:
+        status = None
+    for t, dt, count in ((value, torch.float32, n), (probs, torch.float32, n * N), (status, torch.int32, n)):
+        if t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= count):
+            raise ValueError("the outputs are contiguous GPU tensors: value f32[n], probs f32[n, 225], status i32[n]")
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(load().gmk_pattern_evaluate_states(states.data_ptr(), n, int(bool(filter)), norm, value.data_ptr(), probs.data_ptr(),
+                                              None if status is None else status.data_ptr(), stream))
+    return value, probs, status
+
+
+def pattern_evaluate_states_host(states, filter=True, norm="sum"):
+    """gmk_pattern_evaluate_states_host: host rows f32 [n, 6, 225] -> {"value" f32[n], "probs" f32[n, 225], "status" i32[n]}.  Runs on the GPU;
+    raises without one."""
+    norm = _pattern_norm(norm)
+    states, n = _state_rows(states)
+    init()
+    out = {"value": np.zeros(n, np.float32), "probs": np.zeros((n, N), np.float32), "status": np.zeros(n, np.int32)}
+    _check(load().gmk_pattern_evaluate_states_host(states.ctypes.data, n, int(bool(filter)), norm, out["value"].ctypes.data, out["probs"].ctypes.data,
+                                                   out["status"].ctypes.data))
+    return out
+
+
+def pattern_states_list_host(states):
+    """gmk_pattern_states_list_host: the canonical move lists of host rows f32 [n, 6, 225] -> (moves u8[n, 225], zero past the length, lens i32[n],
+    status i32[n] = 0 or PATTERN_ILLEGAL).  Needs no GPU and no init()."""
+    states, n = _state_rows(states)
+    moves, lens, status = np.zeros((n, N), np.uint8), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    _check(load().gmk_pattern_states_list_host(states.ctypes.data, n, moves.ctypes.data, lens.ctypes.data, status.ctypes.data))
+    return moves, lens, status
+
+
+def pattern_states_finish_host(vec, states, norm="sum"):
+    """gmk_pattern_states_finish_host: K10's vectors f32[n, 225] of the rows' canonical lists -> the priors f32[n, 225] under `norm` (a row that is
+    no position: zeros).  Needs no GPU and no init()."""
+    norm = _pattern_norm(norm)
+    states, n = _state_rows(states)
+    vec = np.ascontiguousarray(vec, dtype=np.float32)
+    if vec.shape != (n, N):
+        raise ValueError("vec is f32[n, 225], one row per row of states")
+    probs = np.zeros((n, N), np.float32)
+    _check(load().gmk_pattern_states_finish_host(vec.ctypes.data, states.ctypes.data, n, norm, probs.ctypes.data))
+    return probs
 
 
 # ---------------- K14: the forced-win solver by continuous fours (gmk_vcf_solve) ----------------

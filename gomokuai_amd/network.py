@@ -199,6 +199,51 @@ class SymmetricNetwork:
         return float(value[0]), probs[0].cpu().numpy()
 
 
+class PatternEvaluator:
+    """The reference's hand-written pattern heuristic where a network goes (K23, gmk_pattern_evaluate_states): network(states) -> (value, probs)
+    for K7 (lib.AlphaZeroMCTS.search), the self-play and match loops of selfplay.py and NetworkAgent, with no weights and nothing to train.
+    A row of planes is decoded into its canonical move list and evaluated as K10 evaluates a list (include/gomoku_pattern_states.h states the
+    rule): probs = Heuristic::EvaluationProbs, after DecisiveFilter when `filter`; value = EvaluationValue for the player to move.
+    norm "sum" (default): the prior sums to 1, uniform over the empty cells where the heuristic sees nothing; "l2": K10's L2-normalised vector
+    as it is.  A row that is not a position -- the zero row of a leaf whose game is over -- gets zeros, which K7 ignores.
+    One kernel on torch's current stream, nothing synchronises: capturable after one eager call.  The output tensors are kept per device and
+    batch size and written again by the next call of that size: take a copy of what has to outlive it."""
+
+    def __init__(self, filter=True, norm="sum"):
+        from . import lib as G
+        self.G, self.filter, self.norm = G, bool(filter), norm
+        self._norm = G._pattern_norm(norm)                                   # a typo is a ValueError on any machine
+        self._outputs = {}
+
+    @torch.no_grad()
+    def __call__(self, states):
+        """states float32 [B, 6, 15, 15] on the GPU -> (value [B], probs [B, 225]) on torch's current stream."""
+        assert states.is_cuda and states.dtype == torch.float32 and states.is_contiguous() and tuple(states.shape[1:]) == (6, 15, 15)
+        n = states.shape[0]
+        key = (states.device, n)
+        if key not in self._outputs:
+            self._outputs[key] = (torch.zeros((n,), dtype=torch.float32, device=states.device),
+                                  torch.zeros((n, 225), dtype=torch.float32, device=states.device))
+        value, probs = self._outputs[key]
+        self.G.pattern_evaluate_states(states, self.filter, self._norm, value=value, probs=probs, status=False)
+        return value, probs
+
+    def symmetric(self, mode, seed=None):
+        """None or "none": this evaluator.  Anything else is a ValueError: the heuristic is a fixed rule, not a learned function whose
+        orientations are worth averaging or drawing from."""
+        if mode in (None, "none"):
+            return self
+        raise ValueError("PatternEvaluator.symmetric: mode is None or \"none\", not %r -- the pattern heuristic is not a learned function to "
+                         "average over the board's symmetries" % (mode,))
+
+    @torch.no_grad()
+    def eval_state(self, board):
+        """One position -> (value, probs[225]) on the host: what CorePyExt.MCTS's Policy(eval_state=...) and NetworkAgent call."""
+        states = torch.from_numpy(np.ascontiguousarray(np.asarray(board.encoded_states(), dtype=np.float32).reshape(1, 6, 15, 15))).cuda()
+        value, probs = self(states)
+        return float(value[0]), probs[0].cpu().numpy()
+
+
 # the trainer's tensor names (lib.TRAIN_TENSORS) -> how a PolicyValueNetwork holds them
 _MODULE_TENSORS = (("w1", "conv.0.weight"), ("b1", "conv.0.bias"), ("w2", "conv.1.weight"), ("b2", "conv.1.bias"), ("w3", "conv.2.weight"), ("b3", "conv.2.bias"),
                    ("w_policy_conv", "policy_conv.weight"), ("b_policy_conv", "policy_conv.bias"), ("w_value_conv", "value_conv.weight"), ("b_value_conv", "value_conv.bias"),

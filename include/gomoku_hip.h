@@ -985,6 +985,36 @@ int gmk_pattern_policy_host(const uint8_t* h_moves, int stride, const int32_t* h
 int gmk_pattern_play(uint8_t* d_moves, int32_t* d_lens, int n, int filter, int max_moves,
                      int8_t* d_winner, float* d_values, int32_t* d_status, void* stream);
 
+/* ---- K23: the pattern heuristic for rows of network planes: K10 as K7's leaf evaluator ----
+ * The rule is include/gomoku_pattern_states.h, which the kernel and the host forms compile: row g of d_states float32 [n][6][225] (the planes
+ * of Board.encoded_states / gmk_az_select) is decoded (a cell is set iff x != 0), checked, turned into its CANONICAL move list and put through
+ * gmk_pattern_policy's path with `filter`.  The canonical order is this project's definition -- the real order of a position's moves is not
+ * in the planes -- so a K7 leaf need not get the bits K6 gets for the same game.
+ * gmk_pattern_evaluate_states: d_value float32[n] (EvaluationValue for the player to move, in [-1, 1]: what gmk_az_expand takes), d_probs
+ *   float32[n][225], d_status int32[n] or NULL: gmk_pattern_policy's bits 0, 1, 2 for the canonical list; bit 2 (GMK_PATTERN_ILLEGAL) also for
+ *   a row that is not a position, the all-zero row of a finished K7 leaf among them.  Rows with bit 0 or 2 get zero outputs.
+ *   norm GMK_PATTERN_NORM_L2: probs = K10's L2-normalised vector, bit for bit.  GMK_PATTERN_NORM_SUM: probs_c = (float)((double)v_c / S), S
+ *   the binary64 sum in gmk_noise_sum225's order; S == 0 on a live row: uniform over the empty cells.
+ *   Asynchronous on `stream`, nothing runs on any other stream; d_states is not written and nothing past row n of an output is.  n = 0
+ *   does nothing.  GMK_ERR_ARG, before anything touches a GPU, for n < 0, a NULL d_states / d_value / d_probs with n > 0, a filter other than
+ *   0 or 1 or an unknown norm; GMK_ERR_STATE before gmk_init (no CPU fallback).  The work counter of a launch comes from gmk_pattern_policy's
+ *   ring, which the first call of either allocates: let that call happen outside a stream capture; afterwards the entry can be captured.
+ * gmk_pattern_evaluate_states_host: the same with host buffers (stages, runs, synchronises); h_status may be NULL.
+ * gmk_pattern_states_list_host: the decode and the canonical list alone: h_moves uint8[n][225] (entries past the length are not written),
+ *   h_lens int32[n], h_status int32[n] = 0 or GMK_PATTERN_ILLEGAL (length 0).  Needs no GPU and no gmk_init.
+ * gmk_pattern_states_finish_host: h_probs float32[n][225] from h_vec float32[n][225] (K10's vectors of the rows' lists) under `norm`.  It
+ *   knows no evaluator status: a row that decodes as a position counts as live, any other row gets zeros.  Needs no GPU and no gmk_init. */
+#ifndef GMK_PATTERN_NORM_DEFINED
+#define GMK_PATTERN_NORM_DEFINED
+enum { GMK_PATTERN_NORM_L2 = 0, GMK_PATTERN_NORM_SUM = 1 };
+#endif
+int gmk_pattern_evaluate_states(const float* d_states, int n, int filter, int norm,
+                                float* d_value, float* d_probs, int32_t* d_status, void* stream);
+int gmk_pattern_evaluate_states_host(const float* h_states, int n, int filter, int norm,
+                                     float* h_value, float* h_probs, int32_t* h_status);
+int gmk_pattern_states_list_host(const float* h_states, int n, uint8_t* h_moves, int32_t* h_lens, int32_t* h_status);
+int gmk_pattern_states_finish_host(const float* h_vec, const float* h_states, int n, int norm, float* h_probs);
+
 /* ---- K14: the forced-win solver by continuous fours (VCF), exact, per position and in batch ----
  * No counterpart in the reference; the contract is this block.  All of it is geometry on the 15 x 15 board, the pattern automaton is not involved.
  * Position g is the move list d_moves[g*stride .. + d_lens[g]), black first and alternating; a cell is y * 15 + x.  The ATTACKER is the side to
